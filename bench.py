@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: gesture frames/sec of the ZeroEGGS training step on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 works both ways: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...`
 (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* from the environment), or as the plain command above -- bench.py then
@@ -11,10 +11,23 @@ A "step" is ONE full training iteration of BASELINE.json configs[1]: configs_v1 
 batch 32 per GPU of 256-frame windows cut from synthetic 60-fps 2-minute clips that are resident in HBM, style
 examples of length 384: gather -> speech encoder -> style VAE -> 255-step decoder rollout -> FK/L1 loss -> BPTT ->
 (RCCL all-reduce) -> fused RAdam.  Nothing is skipped or cached inside the timed region; training-mode dropout is on.
-Prints ONE JSON line on rank 0 (contract: task statement / DESIGN.md "Measurement").  At N = 1 the line also carries
-the other BASELINE.json configs as extra keys: `decode` (B=1, 1800 frames), `decode_30min` (configs[4]),
-`generate_30min` (configs[4] through generate_gesture(), per-stage ms), `v2_label_b64` (configs[3]) and the CPU baselines
-(the unmodified reference timed on this box: oracle/ref_timing.py).
+Prints ONE JSON line on rank 0 (contract: task statement / DESIGN.md "Measurement").  A plain run does only what the
+headline needs: set-up, W warm-up steps, the K timed steps (`ms_per_step` = the timed region / K), the outputs of the last
+timed step if --dump-outputs is given, the line.  --full adds everything else, after the timed region: the roofline of the
+decoder sweeps (3 more iterations), the un-overlapped all-reduce (N > 1) and, at N = 1, the other BASELINE.json configs as
+extra keys: `decode` (B=1, 1800 frames), `decode_30min` (configs[4]), `generate_30min` (configs[4] through
+generate_gesture(), per-stage ms), `v2_label_b64` (configs[3]) and the CPU baselines (the unmodified reference timed on
+this box: oracle/ref_timing.py); --no-extras / --no-generate / --no-cpu-baseline leave parts of it out.
+
+--dump-outputs DIR writes what a caller of the timed step (TrainEngine.step, as zeggs.train() drives it) receives from the
+LAST timed step, as float32 / float64 .npy files: loss.npy (the returned loss), loss_terms.npy (the 19 terms of
+TrainEngine.last_terms) and params_sample.npy, a fixed seeded sample of 4 Mi entries of the flat parameter buffer after the
+optimizer step (16 MB; the weights the caller's modules now hold).  The gradient buffer is the engine's scratch, zeroed by
+the next step and read by no caller: it is not written.  Inputs are seeded: the same arguments give the same inputs in
+every run, so two builds can be compared output for output.  The engine's float-atomic reductions (GEMM stream-K partial
+tiles, bias / LayerNorm / attention gradients, loss terms) still vary the last bits from run to run: one step
+(--steps 1 --warmup 0) repeats the loss exactly and the weights to rounding, while 25 chained training steps amplify the
+difference (weights up to ~1e-4 apart).
 """
 import argparse
 import ctypes
@@ -134,6 +147,23 @@ def dominant_kernel_note():
             return (f"train_bwd_persistent_k ({sh['train_bwd_persistent_k']} % of kernel time, read from {path}): its figures are "
                     f"roofline.backward; train_fwd_persistent_k ({sh['train_fwd_persistent_k']} %) is the top-level entry")
     return "train_bwd_persistent_k (no kernel-statistics csv found under profiles/): its figures are roofline.backward"
+
+
+DUMP_SAMPLE = 1 << 22        # entries of the flat parameter buffer --dump-outputs writes (of 25.5 M)
+
+
+def dump_outputs(path, eng, loss):
+    """--dump-outputs: the loss, its terms and a fixed seeded sample of the weights updated by the step whose loss is `loss`
+    (the last timed one) -> path/<name>.npy"""
+    out = Path(path)
+    out.mkdir(parents=True, exist_ok=True)
+    n = eng.flat_p.numel()
+    idx = np.sort(np.random.default_rng(0).choice(n, size=min(n, DUMP_SAMPLE), replace=False))
+    at = torch.as_tensor(idx, device=eng.flat_p.device)
+    arrays = {"loss": loss.detach().double().reshape(1), "loss_terms": eng.last_terms.detach().double().reshape(-1),
+              "params_sample": eng.flat_p[at]}
+    for name, t in arrays.items():
+        np.save(out / f"{name}.npy", t.cpu().numpy())
 
 
 def sweep_ms(which):
@@ -723,8 +753,13 @@ def self_launch(a):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the loss, loss terms and a seeded sample of the updated weights of the last timed step "
+                         "to DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: roofline sweeps, extra configurations, CPU baselines (default: the headline only)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-overlap", action="store_true",
                     help="ONE blocking all-reduce after the backward instead of the overlapped decoder-slice exchange")
@@ -733,8 +768,8 @@ def main():
     ap.add_argument("--no-early-step", action="store_true",
                     help="the whole optimizer step at the end of the iteration (default: the decoder's slice on the weight-gradient stream)")
     ap.add_argument("--no-prefetch", action="store_true", help="gather every batch at the start of its own step")
-    ap.add_argument("--no-extras", action="store_true", help="skip decode / decode_30min / v2_label_b64 (N = 1 only)")
-    ap.add_argument("--no-generate", action="store_true", help="skip generate_30min (configs[4] through generate_gesture())")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip decode / decode_30min / v2_label_b64 (N = 1 only)")
+    ap.add_argument("--no-generate", action="store_true", help="with --full: skip generate_30min (configs[4] through generate_gesture())")
     ap.add_argument("--force-process-group", action="store_true",
                     help="initialise the RCCL process group and run the gradient all-reduce even at --gpus 1")
     ap.add_argument("--launch-selftest", action="store_true",
@@ -744,6 +779,8 @@ def main():
                          "fresh process per extra: a second or third engine in one process maps its streams onto hardware queues "
                          "less luckily than the first, tools/prio_probe.py)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be >= 1")
     if a.extra:
         dev = rank_device(0)
         torch.cuda.set_device(dev)
@@ -757,7 +794,7 @@ def main():
     # second engine in one process runs slower than the first on some boxes (stream -> hardware-queue mapping), and a child
     # that starts while its parent holds queues on the same GPU is scheduled against them (FiLM: 42 instead of 36 ms).
     pre_extras = {}
-    if a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_extras and not a.launch_selftest:
+    if a.full and a.gpus == 1 and "WORLD_SIZE" not in os.environ and not a.no_extras and not a.launch_selftest:
         for key in EXTRA_ENGINES:
             pre_extras[key] = extra_in_fresh_process(key)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -826,10 +863,11 @@ def main():
         torch.cuda.synchronize()
 
     step_events = []
+    last_loss = [None]
 
     def run(first, last):       # steps first .. last-1; the next batch is gathered beside the current step (never across `last`:
         for it in range(first, last):                       # the timed region gathers exactly its own K batches)
-            eng.step(indices(it), EXAMPLE_LEN)
+            last_loss[0] = eng.step(indices(it), EXAMPLE_LEN)
             if it + 1 < last and not (a.no_wgrad_overlap or a.no_prefetch):
                 eng.prefetch(indices(it + 1), EXAMPLE_LEN)
             if not os.environ.get("ZEGGS_BENCH_NO_STEP_EVENTS"):      # (tools/gap_probe.sh: does the per-step event cost the iteration anything?)
@@ -860,15 +898,16 @@ def main():
         per_rank = [round(float(t) / a.steps * 1e3, 3) for t in allt]
         torch.distributed.all_reduce(el, op=torch.distributed.ReduceOp.MAX)
     elapsed = float(el)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, eng, last_loss[0])
     fw, bw = [fwd_in], [bwd_in]
     loss = None
-    for k in range(3):                                       # a few more iterations, sweeps read after each one
+    for k in range(3 if a.full else 0):                      # a few more iterations, sweeps read after each one
         loss = eng.step(indices(a.warmup + a.steps + k), EXAMPLE_LEN)
         fw.append(sweep_ms(0))
         bw.append(sweep_ms(1))
-    loss = float(loss.detach())
     ar_blocking = None
-    if use_pg:      # the whole exchange un-overlapped (3 more iterations): what the overlap hides = blocking - exposed
+    if use_pg and a.full:       # the whole exchange un-overlapped (3 more iterations): what the overlap hides = blocking - exposed
         keep, eng.overlap_allreduce, eng.allreduce_events = (eng.overlap_allreduce, list(eng.allreduce_events or [])), False, []
         for k in range(3):
             eng.step(indices(a.warmup + a.steps + 3 + k), EXAMPLE_LEN)
@@ -885,13 +924,37 @@ def main():
                                    "from synthetic 60fps 2-min clips, style example 384 frames, full train step "
                                    "(gather+fwd+loss+bwd+allreduce+RAdam)",
                        "global_batch": gb, "window": WINDOW, "parallelism": f"dp{world}"},
-            "final_loss": round(loss, 4),
         }
+        if loss is not None:
+            out["final_loss"] = round(float(loss.detach()), 4)
         if len(step_ms):
             out["step_ms_hip_events"] = {"n": int(len(step_ms)), "p50": round(float(np.percentile(step_ms, 50)), 3),
                                          "p95": round(float(np.percentile(step_ms, 95)), 3),
                                          "min": round(float(step_ms.min()), 3), "max": round(float(step_ms.max()), 3)}
         out["dataset_build_s"] = round(t_data, 2)
+        if use_pg:
+            ar = [e0.elapsed_time(e1) for e0, e1 in eng.allreduce_events[:a.steps]]
+            out["rccl_ranks"] = {"world_size": torch.distributed.get_world_size(), "ranks": census}
+            out["per_rank_ms_per_step"] = per_rank
+            out["allreduce_ms"] = round(float(np.mean(ar)), 3) if ar else None
+            out["allreduce_exposed_ms"] = out["allreduce_ms"]
+            out["per_gpu_frames_per_sec"] = round(BATCH * WINDOW * a.steps / elapsed, 1)
+            # what one of these ranks would do alone: the iteration without the exposed part of the exchange (to be checked
+            # against the N = 1 line of the same build)
+            out["n1_equivalent_frames_per_sec"] = round(BATCH * WINDOW / max(1e-9, (ms - (out["allreduce_ms"] or 0.0)) * 1e-3), 1)
+            out["allreduce_bytes"] = int(eng.flat_gx.numel() * 4)
+            out["allreduce_note"] = ("allreduce_ms = the EXPOSED part: the decoder slice (91 % of the payload) is reduced "
+                                     "underneath the encoders' backward" if eng.overlap_allreduce else
+                                     "one blocking all-reduce of the flat gradient buffer after the backward")
+            if ar_blocking is not None:         # (--full)
+                out["allreduce_blocking_ms"] = round(ar_blocking, 3)
+                out["allreduce_overlapped_ms"] = round(max(0.0, ar_blocking - (out["allreduce_ms"] or 0.0)), 3) if eng.overlap_allreduce else 0.0
+        out["streams"] = ("single stream" if eng.wgrad_stream is None else
+                          "decoder weight-gradient GEMMs and the weight-only packs of the next sweeps on the library's second "
+                          "stream, speech encoder and the next batch's gather on a third"
+                          + ("" if not a.no_prefetch else " (no batch prefetch)"))
+        out["cpu_baseline"] = None
+    if rank == 0 and a.full:
         nst = WINDOW - 1
         f_us, b_us = float(np.mean(fw)) * 1e3 / nst, float(np.mean(bw)) * 1e3 / nst
         pmc = None
@@ -925,27 +988,6 @@ def main():
             "note": "HIP events (library hook zeggs_timing_ms, recorded on the stream the kernels run on) around the "
                     "255-step stage sweeps: the last timed iteration + 3 more; traffic = FETCH_SIZE(x2)+WRITE_SIZE "
                     f"from {pmc['file'] if pmc else 'n/a'}; at B=32 the step is also at the fp32 MFMA ridge"}
-        if use_pg:
-            ar = [e0.elapsed_time(e1) for e0, e1 in eng.allreduce_events[:a.steps]]
-            out["rccl_ranks"] = {"world_size": torch.distributed.get_world_size(), "ranks": census}
-            out["per_rank_ms_per_step"] = per_rank
-            out["allreduce_ms"] = round(float(np.mean(ar)), 3) if ar else None
-            out["allreduce_exposed_ms"] = out["allreduce_ms"]
-            out["allreduce_blocking_ms"] = round(ar_blocking, 3)
-            out["allreduce_overlapped_ms"] = round(max(0.0, ar_blocking - (out["allreduce_ms"] or 0.0)), 3) if eng.overlap_allreduce else 0.0
-            out["per_gpu_frames_per_sec"] = round(BATCH * WINDOW * a.steps / elapsed, 1)
-            # what one of these ranks would do alone: the iteration without the exposed part of the exchange (to be checked
-            # against the N = 1 line of the same build)
-            out["n1_equivalent_frames_per_sec"] = round(BATCH * WINDOW / max(1e-9, (ms - (out["allreduce_ms"] or 0.0)) * 1e-3), 1)
-            out["allreduce_bytes"] = int(eng.flat_gx.numel() * 4)
-            out["allreduce_note"] = ("allreduce_ms = the EXPOSED part: the decoder slice (91 % of the payload) is reduced "
-                                     "underneath the encoders' backward" if eng.overlap_allreduce else
-                                     "one blocking all-reduce of the flat gradient buffer after the backward")
-        out["streams"] = ("single stream" if eng.wgrad_stream is None else
-                          "decoder weight-gradient GEMMs and the weight-only packs of the next sweeps on the library's second "
-                          "stream, speech encoder and the next batch's gather on a third"
-                          + ("" if not a.no_prefetch else " (no batch prefetch)"))
-        out["cpu_baseline"] = None
         if world == 1 and not a.no_extras:
             out["wgrad_gemm_alone"] = wgrad_gemm_alone(dev)
             out["decode"] = decode_rate(de, dev)

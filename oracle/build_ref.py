@@ -21,6 +21,7 @@ Writes
 import hashlib
 import io
 import json
+import os
 import shutil
 import tarfile
 from pathlib import Path
@@ -41,7 +42,7 @@ def members():
 def build(force=False):
     """-> True if the snapshot exists afterwards.  No-op (False) where /root/reference is absent and nothing was built."""
     arc = OUT / "zeggs_reference.tar.gz"
-    if not REF.is_dir():
+    if not os.path.isdir(REF):          # (False, not PermissionError, where a parent directory is not readable by this user)
         return arc.exists()
     OUT.mkdir(parents=True, exist_ok=True)
     files = members()

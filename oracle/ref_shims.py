@@ -11,6 +11,7 @@ omegaconf, sox, ffmpeg check, scipy.signal.hann alias); no reference source is
 modified or copied.  Recipe documented in SURVEY.md Appendix A.
 """
 import importlib.util
+import os
 import sys
 import types
 from pathlib import Path
@@ -24,7 +25,7 @@ def root():
     """Directory that holds ZEGGS/, configs/ and data/processed_v*/ of the reference (None: neither source exists)."""
     global _root
     if _root is None:
-        if REF.is_dir():
+        if os.path.isdir(REF):          # (False, not PermissionError, where a parent directory is not readable by this user)
             _root = REF.parent
         elif SNAPSHOT.exists():
             import atexit
@@ -44,7 +45,7 @@ def available():
 
 
 def source():
-    return "unmodified /root/reference/ZEGGS" if REF.is_dir() else "oracle/_ref snapshot of the unmodified reference (oracle/build_ref.py)"
+    return f"unmodified {REF}" if os.path.isdir(REF) else "oracle/_ref snapshot of the unmodified reference (oracle/build_ref.py)"
 
 
 def load():

@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT
 O=$R/gpurun_out
-rm -rf $O/ks; rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline > $O/ks.log 2>&1
+rm -rf $O/ks; rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline > $O/ks.log 2>&1
 DB=$(find $O/ks -name "*.db" | head -1)
 python $R/tools/rocpd_stats.py $DB $O/r02_bench_kernel_stats.csv
 python $R/tools/rocpd_stages.py $DB $O/r02_stage_breakdown.csv

@@ -10,7 +10,7 @@ for n in 12 6; do
   rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --steps $n --warmup 2 --no-cpu-baseline --no-extras > $O/ks.log 2>&1
   python $R/tools/rocpd_stats.py $(find $O/ks -name "*.db" | head -1) $O/r03_train_only_kernel_stats_${n}steps.csv
 done
-rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-generate > $O/ks.log 2>&1
+rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-generate > $O/ks.log 2>&1
 python $R/tools/rocpd_stats.py $(find $O/ks -name "*.db" | head -1) $O/r03_bench_kernel_stats.csv
 rm -rf $O/ks
 # 2. one iteration as a timeline

@@ -10,7 +10,7 @@ for n in 12 6; do
   rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --steps $n --warmup 2 --no-cpu-baseline --no-extras > $O/ks.log 2>&1
   python $R/tools/rocpd_stats.py $(find $O/ks -name "*.db" | head -1) $O/r04_train_only_kernel_stats_${n}steps.csv
 done
-rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-generate > $O/ks.log 2>&1
+rm -rf $O/ks; $T rocprofv3 --kernel-trace --stats -d $O/ks -o k -- python $R/bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-generate > $O/ks.log 2>&1
 python $R/tools/rocpd_stats.py $(find $O/ks -name "*.db" | head -1) $O/r04_bench_kernel_stats.csv
 rm -rf $O/ks
 # 2. one iteration as a timeline
@@ -58,7 +58,7 @@ if [ -f $R/ubisoft-laforge-zeroeggs_amd/zeggs/libzeggs_stat.so ]; then
 fi
 # 6. the data-parallel schedule through RCCL on ONE rank (the exchange of the final kernels, early decoder optimizer slices
 #    behind their own all-reduce): same iteration as the headline line + the exposed exchange
-cd $R && $T python bench.py --force-process-group --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/r04_bench_rccl_single_rank.json 2> $O/rccl.err; tail -c 300 $O/rccl.err
+cd $R && $T python bench.py --full --force-process-group --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/r04_bench_rccl_single_rank.json 2> $O/rccl.err; tail -c 300 $O/rccl.err
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/r04_bench_rccl_single_rank.json").read().splitlines() if l.startswith("{")][-1])   # (RCCL prints its banner first)

@@ -22,7 +22,7 @@ for c in FETCH_SIZE WRITE_SIZE; do
 done
 python $R/tools/rocpd_pmc2.py $(find $O/pmc_FETCH_SIZE -name "*.db" | head -1) $(find $O/pmc_WRITE_SIZE -name "*.db" | head -1) $O/r06_decoder_step_pmc.json | cut -c1-400
 rm -rf $O/pmc_FETCH_SIZE $O/pmc_WRITE_SIZE
-cd $R && $T python bench.py --force-process-group --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/r06_bench_rccl_single_rank.json 2> $O/rccl.err; tail -c 300 $O/rccl.err
+cd $R && $T python bench.py --full --force-process-group --no-extras --no-cpu-baseline --steps 20 --warmup 5 > $O/r06_bench_rccl_single_rank.json 2> $O/rccl.err; tail -c 300 $O/rccl.err
 python - <<PY
 import json
 d = json.loads([l for l in open("$O/r06_bench_rccl_single_rank.json").read().splitlines() if l.startswith("{")][-1])   # (RCCL prints its banner first)

@@ -10,7 +10,7 @@ for w in $WHAT; do
     tests)    timeout 900 python -m pytest tests -m gpu -q -x --no-header -p no:cacheprovider > $O/${TAG}_tests.log 2>&1; echo "tests rc=$?"; tail -5 $O/${TAG}_tests.log ;;
     testsall) timeout 1200 python -m pytest tests -m gpu -q --no-header -p no:cacheprovider > $O/${TAG}_tests.log 2>&1; echo "tests rc=$?"; tail -15 $O/${TAG}_tests.log ;;
     bench)    timeout 600 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras > $O/${TAG}_bench.log 2>&1; echo "bench rc=$?"; tail -1 $O/${TAG}_bench.log | cut -c1-400 ;;
-    benchfull) timeout 900 python bench.py --steps 20 --warmup 5 > $O/${TAG}_benchfull.log 2>&1; echo "benchfull rc=$?"; tail -1 $O/${TAG}_benchfull.log | cut -c1-300 ;;
+    benchfull) timeout 900 python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_benchfull.log 2>&1; echo "benchfull rc=$?"; tail -1 $O/${TAG}_benchfull.log | cut -c1-300 ;;
     timeline) timeout 600 bash tools/prof_timeline.sh; cp $O/timeline.csv $O/${TAG}_timeline.csv; cp $O/timeline_summary.txt $O/${TAG}_timeline_summary.txt ;;
     *)        echo "custom: $w"; timeout 900 bash -c "$w" > $O/${TAG}_custom.log 2>&1; tail -20 $O/${TAG}_custom.log ;;
   esac
