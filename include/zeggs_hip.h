@@ -465,7 +465,16 @@ int zeggs_scale_copy(float* dst, const float* src, long n, const float* dev_scal
 int zeggs_randn(float* out, long n, uint64_t seed, void* stream);
 /* x[i] *= mask(seed, i) / (1 - p): the counter-hash dropout mask every encoder kernel applies (F.dropout /
  * nn.Dropout of ZEGGS/modules.py:258-272, 361-388); element i depends on (seed, i) only, so forward and backward
- * regenerate the same mask without storing it */
+ * regenerate the same mask without storing it.
+ * THE MASK CONTRACT (what tests/helpers.py device_masks_* read back through this entry point).  A call of an encoder with
+ * ZeggsSpeechDims.seed / ZeggsStyleDims.seed = s masks, forward and backward alike,
+ *   speech encoder, p = 0.2:  ELU(layer0) with seed s + 1, element (b T + t) H + c;   ELU(layer1) with s + 2, (b T + t) O + c
+ *   style encoder:  LayerNorm convs.2 output   p = 0.2, s + 1, element (b L + l) H + c
+ *                   LayerNorm convs.6 output   p = 0.2, s + 2, (b L + l) E + c     (before the positional table is added)
+ *                   attention probabilities    p = 0.1, s + 3, ((b NH + h) L + q) L + k
+ *                   attention out-projection   p = 0.1, s + 4, (b L + l) E + c     (before its residual)
+ *                   feed-forward output        p = 0.1, s + 5, (b L + l) E + c     (before its residual)
+ * i.e. the position in the contiguous [B T, C] / [B L, C] / [B, NH, L, L] array, whatever padded buffer a kernel keeps it in */
 int zeggs_dropout(float* x, long n, float p, uint64_t seed, void* stream);
 int zeggs_broadcast_time(float* out /* [B,T,S] */, const float* z /* [B,S] */, int B, int T, int S, void* stream);
 int zeggs_sum_time(float* dz /* [B,S] */, const float* dout /* [B,T,S] */, int B, int T, int S, void* stream);

@@ -578,6 +578,207 @@ def gold_train_iter_fp64(ref):
     np.savez_compressed(GOLD / "train_iter_fp64.npz", **out)
 
 
+class _MaskedDropout:
+    """Stand-in for torch.nn.functional.dropout -- the one function every dropout site of the reference goes through, the
+    internal dropout of nn.MultiheadAttention included -- that consumes pre-drawn keep-scale tensors in call order instead of
+    drawing.  Masks are given in this project's layout and brought to the layout the reference's call sees."""
+
+    def __init__(self, scales, ps):
+        self.queue = list(zip(scales, ps))
+        self.seen = []
+
+    def __call__(self, x, p=0.5, training=True, inplace=False):
+        if not training:
+            return x
+        m, pm = self.queue.pop(0)
+        assert abs(p - pm) < 1e-12, (p, pm)
+        self.seen.append(tuple(x.shape))
+        if m.shape != x.shape:
+            if x.dim() == 3 and m.dim() == 3 and tuple(m.transpose(1, 2).shape) == tuple(x.shape):
+                m = m.transpose(1, 2)                      # speech encoder: the reference drops on [B, C, T]
+            else:
+                m = m.reshape(x.shape)                     # attention probabilities: [B * NH, L, L]
+        return x * m.to(x.dtype)
+
+
+NETS_TRAIN_CASES = (dict(tag="a", B=3, T=21, L=21, seed=4100), dict(tag="b", B=2, T=45, L=64, seed=4200))
+
+
+def nets_train_inputs(case):
+    """The seeded inputs of one nets_train.npz case (shared with the tests: only the seeds are stored)."""
+    rng = np.random.default_rng(case["seed"])
+    B, T, L = case["B"], case["T"], case["L"]
+    audio = rng.standard_normal((B, T, synth.N_AUDIO)).astype(np.float32)
+    ex = rng.standard_normal((B, L, synth.POSE_IN)).astype(np.float32)
+    eps = rng.standard_normal((B, 64)).astype(np.float32)
+    w_speech = rng.standard_normal((B, T, 64)).astype(np.float32)
+    w_z, w_mu, w_lv = (rng.standard_normal((B, 64)).astype(np.float32) for _ in range(3))
+    return audio, ex, eps, w_speech, (w_z, w_mu, w_lv)
+
+
+def gold_nets_train(ref):
+    """The reference's SpeechEncoder and StyleEncoder(attn, use_vae) in .train() with SEEDED dropout masks, float32 and float64:
+    outputs in full, every parameter gradient (of a seeded weighted sum of the outputs) as fingerprint + samples.  Masks are
+    stored bit-packed in this project's element order; inputs as seeds."""
+    import torch.nn.functional as F
+    from oracle import nets as onets
+    out = {}
+    for case in NETS_TRAIN_CASES:
+        tag, B, T, L = case["tag"], case["B"], case["T"], case["L"]
+        audio, ex, eps, w_speech, w_style = nets_train_inputs(case)
+        keeps = onets.draw_keeps(onets.speech_mask_shapes(B, T) + onets.style_mask_shapes(B, L),
+                                 onets.SPEECH_P + onets.STYLE_P, case["seed"] + 1)
+        bits, shapes = onets.pack_keeps(keeps)
+        out.update({f"{tag}_dims": np.array([B, T, L]), f"{tag}_seed": np.int64(case["seed"]), f"{tag}_mask_bits": bits,
+                    f"{tag}_mask_shapes": shapes, f"{tag}_in_fp": np.stack([fingerprint(torch.as_tensor(a)) for a in
+                                                                             (audio, ex, eps, w_speech, *w_style)])})
+        for dt, sfx in ((torch.float32, ""), (torch.float64, "64")):
+            se, _, st = build_ref_nets(ref)
+            se, st = se.to(dt).train(), st.to(dt).train()
+            ps = onets.SPEECH_P + onets.STYLE_P
+            drop = _MaskedDropout(onets.keep_scales(keeps, ps, dt), ps)
+            t = lambda a: torch.as_tensor(a).to(dt)  # noqa: E731
+            saved = (torch.randn_like, F.dropout)
+            torch.randn_like = lambda x, *a, **k: t(eps)
+            F.dropout = drop
+            try:
+                speech = se(t(audio))
+                z, mu, logvar = st(t(ex), 1.0)
+            finally:
+                torch.randn_like, F.dropout = saved
+            assert not drop.queue and drop.seen == [(B, 64, T), (B, 64, T), (B, L, 512), (B, L, 128), (B * 4, L, L), (B, L, 128),
+                                                    (B, L, 128)], drop.seen
+            ((speech * t(w_speech)).sum() + sum((o * t(w)).sum() for o, w in zip((z, mu, logvar), w_style))).backward()
+            for k, v in (("speech", speech), ("z", z), ("mu", mu), ("logvar", logvar)):
+                out[f"{tag}_{k}{sfx}"] = v.detach().numpy()
+            for ntag, net in (("speech", se), ("style", st)):
+                for k, p in net.named_parameters():
+                    g = p.grad.detach().flatten()
+                    out[f"{tag}_gfp{sfx}_{ntag}.{k}"] = fingerprint(g)
+                    out[f"{tag}_gsamp{sfx}_{ntag}.{k}"] = g[torch.as_tensor(sample_idx(g.numel()))].numpy()
+                    out[f"{tag}_gmax{sfx}_{ntag}.{k}"] = np.float64(g.abs().max())
+    np.savez_compressed(GOLD / "nets_train.npz", **out)
+    print("nets_train.npz", (GOLD / "nets_train.npz").stat().st_size, "bytes")
+
+
+def gold_train_iter_dropout(ref):
+    """The two iterations of train_iter.npz (its batches and VAE noise replayed) through the UNMODIFIED reference train() with
+    dropout ON: every F.dropout call consumes a seeded mask.  float32 (the record layout of train_iter.npz: loss, terms, gradient
+    fingerprints / samples, weight samples after the RAdam step) and float64 (`*64`, the yardstick of how far the reference's own
+    float32 run is from exact arithmetic under these masks).  The batches themselves are NOT stored again: they are
+    train_iter.npz's, whose checksums are kept."""
+    import torch.nn.functional as F
+    from oracle import nets as onets
+    gd = np.load(GOLD / "train_iter.npz")
+    window, B, n_it = int(gd["window"]), int(gd["batch"]), len(gd["loss"])
+    ps = onets.SPEECH_P + onets.STYLE_P              # (the exemplar length changes per iteration: change_pace, 12 then 24)
+    keeps = [onets.draw_keeps(onets.speech_mask_shapes(B, window) + onets.style_mask_shapes(B, gd[f"it{it}_batch10"].shape[1]),
+                              ps, 7300 + it) for it in range(n_it)]
+    out = dict(window=np.int64(window), batch=np.int64(B), mask_p=np.array(ps),
+               batch_check=np.stack([fingerprint(torch.as_tensor(gd[f"it{it}_batch{j}"]).double())
+                                     for it in range(n_it) for j in range(11)]))
+    for it in range(n_it):
+        out[f"it{it}_mask_bits"], out[f"it{it}_mask_shapes"] = onets.pack_keeps(keeps[it])
+        out[f"it{it}_eps"] = gd[f"it{it}_eps"]
+
+    def run(dt):
+        tmp = Path(tempfile.mkdtemp(prefix="zeggs_gold_drop_"))
+        (tmp / "data").mkdir(), (tmp / "models").mkdir(), (tmp / "logs").mkdir()
+        npz, jsn = tmp / "data" / "processed_data.npz", tmp / "data" / "data_definition.json"
+        np.savez(npz, **{k[5:]: gd[k] for k in gd.files if k.startswith("data_")})
+        json.dump(synth.data_definition(), open(jsn, "w"))
+        rec = dict(loss=[], terms=[], grads=[], weights=[])
+        state = dict(it=0)
+        drop = _MaskedDropout([m for it in range(n_it) for m in onets.keep_scales(keeps[it], ps, dt)], ps * n_it)
+
+        class ReplayDL:
+            def __init__(self, ds, **kw):
+                pass
+
+            def __iter__(self):
+                for it in range(n_it):
+                    yield [torch.as_tensor(gd[f"it{it}_batch{j}"]).to(dt) for j in range(11)]
+
+        class RecWriter:
+            def __init__(self, *a, **k): pass
+            def add_hparams(self, *a, **k): pass
+            def add_scalar(self, *a, **k): pass
+            def add_scalars(self, tag, d, it):
+                rec["terms"].append([float(v) for v in d.values()])
+
+        def fake_randn_like(x, *a, **k):
+            if tuple(x.shape) == (B, 64):
+                return torch.as_tensor(gd[f"it{min(state['it'], n_it - 1)}_eps"]).to(x.dtype)
+            return torch.zeros_like(x)
+
+        def typed_module(cls):
+            def make(*a, **k):
+                m = cls(*a, **k).to(dt)
+                m.register_forward_pre_hook(lambda mod, args: tuple(x.to(dt) if torch.is_tensor(x) and x.is_floating_point()
+                                                                    else x for x in args))
+                return m
+            return make
+
+        orig_step = ref.optimizers.RAdam.step
+
+        def rec_step(self, closure=None):
+            pl = [p for g in self.param_groups for p in g["params"]]
+            rec["grads"].append([(fingerprint(p.grad), p.grad.flatten()[sample_idx(p.numel())].clone()) for p in pl])
+            state["it"] += 1
+            r = orig_step(self, closure)
+            rec["weights"].append([p.detach().flatten()[sample_idx(p.numel())].clone() for p in pl])
+            return r
+
+        orig_backward = torch.Tensor.backward
+
+        def rec_backward(self, *a, **k):
+            rec["loss"].append(float(self.detach()))
+            return orig_backward(self, *a, **k)
+
+        rt = ref.train
+        saved = (rt.DataLoader, rt.SummaryWriter, torch.randn_like, F.dropout, rt.SpeechEncoder, rt.Decoder, rt.StyleEncoder,
+                 torch.save)
+        rt.DataLoader, rt.SummaryWriter, torch.randn_like, F.dropout = ReplayDL, RecWriter, fake_randn_like, drop
+        rt.SpeechEncoder, rt.Decoder, rt.StyleEncoder = (typed_module(c) for c in saved[4:7])
+        torch.save = lambda *a, **k: None                  # (the pre-hooks are not picklable; no checkpoint is needed here)
+        ref.optimizers.RAdam.step = rt.RAdam.step = rec_step
+        torch.Tensor.backward = rec_backward
+        random.seed(0)
+        train_opt = dict(niterations=0.001, batchsize=B, window=window, change_pace=True, learning_rate=1e-4,
+                         learning_rate_decay=0.995, eps=1e-5, resume=False, use_gpu=False, thread_count=1, seed=SEED,
+                         use_tensorboard=True, style_encoding_type="example", generate_samples_step=10 ** 9, use_script=False)
+        try:
+            rt.train(tmp / "models", tmp / "logs", npz, jsn, train_opt, NET_OPT)
+        finally:
+            (rt.DataLoader, rt.SummaryWriter, torch.randn_like, F.dropout, rt.SpeechEncoder, rt.Decoder, rt.StyleEncoder,
+             torch.save) = saved
+            ref.optimizers.RAdam.step = rt.RAdam.step = orig_step
+            torch.Tensor.backward = orig_backward
+        assert not drop.queue and len(drop.seen) == 7 * n_it, drop.seen
+        return rec
+
+    r32, r64 = run(torch.float32), run(torch.float64)
+    out.update(loss=np.array(r32["loss"]), terms=np.array(r32["terms"]), loss64=np.array(r64["loss"]),
+               terms64=np.array(r64["terms"]))
+    for it in range(n_it):
+        out[f"it{it}_grad_fp"] = np.stack([g[0] for g in r32["grads"][it]])
+        out[f"it{it}_grad_samples"] = np.concatenate([g[1].numpy() for g in r32["grads"][it]])
+        out[f"it{it}_weight_samples"] = np.concatenate([w.numpy() for w in r32["weights"][it]])
+        out[f"it{it}_grad_fp64"] = np.stack([g[0] for g in r64["grads"][it]])
+        out[f"it{it}_grad_samples64"] = np.concatenate([g[1].numpy() for g in r64["grads"][it]])
+        out[f"it{it}_weight_samples64"] = np.concatenate([w.numpy() for w in r64["weights"][it]])
+        # the reference's own float32-vs-float64 gap under these masks, per tensor: max |g32 - g64| / max |g64| at the samples
+        off, gaps = 0, []
+        for g32, g64 in zip(r32["grads"][it], r64["grads"][it]):
+            a, b = g32[1].double().numpy(), g64[1].numpy()
+            gaps.append(np.abs(a - b).max() / max(np.abs(b).max(), 1e-300))
+        out[f"it{it}_ref32_vs_ref64"] = np.array(gaps)
+        print(f"train_iter_dropout: iteration {it}: loss {r32['loss'][it]:.8f} (fp64 {r64['loss'][it]:.8f}), reference fp32 vs "
+              f"fp64 gradients: worst tensor {max(gaps):.2e} of its largest entry")
+    np.savez_compressed(GOLD / "train_iter_dropout.npz", **out)
+    print("train_iter_dropout.npz", (GOLD / "train_iter_dropout.npz").stat().st_size, "bytes")
+
+
 def gold_train_iter_perturb(ref, n_seeds=10, rel=1e-7):
     """is iteration 1 of train_iter.npz ill-conditioned in the REFERENCE itself?  The two recorded
     iterations are replayed through the unmodified reference train() in float32, `n_seeds` times, with every floating-point
@@ -817,6 +1018,10 @@ def main():
         gold_train_iter(ref)
     if "train" in which or "train_fp64" in which:
         gold_train_iter_fp64(ref)
+    if "nets" in which or "nets_train" in which:
+        gold_nets_train(ref)
+    if "train" in which or "train_dropout" in which:
+        gold_train_iter_dropout(ref)
     if "train_perturb" in which:
         gold_train_iter_perturb(ref)
 

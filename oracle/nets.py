@@ -88,18 +88,91 @@ def quat_to_xform(q):
 
 
 # ----------------------------------------------------------------------------
-# Speech encoder (modules.py:249-272), eval mode (dropout = identity)
+# Training-mode dropout with GIVEN masks.  A mask is the keep-scale of every element (0 or 1 / (1 - p)), laid out as
+# the HIP kernels index it: [B, T, C] / [B, L, C] row-major, attention probabilities [B, NH, L, L].  `masks=None`
+# everywhere below is eval mode (no multiplication at all).  A site's entry may be a pair (forward, backward): the value
+# is then computed with the first mask and the gradient with the second -- a deliberately WRONG backward that the
+# negative controls of tests/test_oracle_golden.py use to show that such an error is visible.
 # ----------------------------------------------------------------------------
-def speech_encoder(w, x, prefix=""):
-    """x: [B, T, F] already normalised ((a - mean)/std, train.py:232-234)."""
+SPEECH_SITES = 2      # after each ELU (modules.py:258-269), p = 0.2
+STYLE_SITES = 5       # both conv-stack LayerNorms p = 0.2 (modules.py:361-388); attention probabilities, attention output,
+#                       feed-forward output p = 0.1 (modules.py:529-555, 590-603)
+
+
+def _drop(h, m):
+    if m is None:
+        return h
+    if isinstance(m, (tuple, list)):
+        fwd, bwd = (t.to(h.dtype) for t in m)
+        return h * bwd + (h * fwd - h * bwd).detach()
+    return h * m.to(h.dtype)
+
+
+def _site(masks, i, n):
+    if masks is None:
+        return None
+    assert len(masks) == n, f"{n} dropout sites, {len(masks)} masks"
+    return masks[i]
+
+
+def speech_mask_shapes(B, T, H=64, O=64):
+    return [(B, T, H), (B, T, O)]
+
+
+def style_mask_shapes(B, L, H=512, E=128, NH=4):
+    return [(B, L, H), (B, L, E), (B, NH, L, L), (B, L, E), (B, L, E)]
+
+
+SPEECH_P = (0.2, 0.2)
+STYLE_P = (0.2, 0.2, 0.1, 0.1, 0.1)
+
+
+def draw_keeps(shapes, ps, seed):
+    """Seeded Bernoulli keep flags (bool arrays) for the given sites: element kept with probability 1 - p."""
+    import numpy as np
+    rng = np.random.default_rng(seed)
+    return [rng.random(tuple(sh)) >= p for sh, p in zip(shapes, ps)]
+
+
+def keep_scales(keeps, ps, dtype=torch.float64):
+    """bool keep flags -> keep-scale tensors (0 or 1 / (1 - p)); the division is done in `dtype`, as F.dropout does."""
+    return [torch.as_tensor(k).to(dtype) / torch.tensor(1.0 - p, dtype=dtype) for k, p in zip(keeps, ps)]
+
+
+def pack_keeps(keeps):
+    """-> (bits uint8 [ceil(n / 8)], shapes int64 [sites, 4] padded with ones): what the fixtures store of a mask set"""
+    import numpy as np
+    bits = np.packbits(np.concatenate([np.asarray(k, bool).ravel() for k in keeps]))
+    return bits, np.array([tuple(k.shape) + (1,) * (4 - k.ndim) for k in keeps], np.int64)
+
+
+def unpack_keeps(bits, shapes, ndims):
+    import numpy as np
+    flat = np.unpackbits(np.asarray(bits, np.uint8)).astype(bool)
+    out, off = [], 0
+    for sh, nd in zip(np.asarray(shapes), ndims):
+        n = int(np.prod(sh))
+        out.append(flat[off:off + n].reshape(tuple(int(v) for v in sh[:nd])))
+        off += n
+    assert off <= flat.size < off + 8
+    return out
+
+
+# ----------------------------------------------------------------------------
+# Speech encoder (modules.py:249-272); masks=None: eval mode (dropout = identity)
+# ----------------------------------------------------------------------------
+def speech_encoder(w, x, prefix="", masks=None):
+    """x: [B, T, F] already normalised ((a - mean)/std, train.py:232-234).  masks: None or the two [B, T, C] keep-scales
+    (the reference drops on the channel-major [B, C, T] tensor, modules.py:267-268: same elements, transposed)."""
     p = prefix
     h = x.transpose(1, 2)                                        # [B, F, T]
     h = F.elu(F.conv1d(h, w[p + "layer0.weight"], w[p + "layer0.bias"]))
+    h = _drop(h.transpose(1, 2), _site(masks, 0, SPEECH_SITES)).transpose(1, 2)
     k = w[p + "layer1.weight"].shape[-1]
     pad = (k - 1) // 2
     h = F.pad(h, (pad, k - 1 - pad), mode="replicate")           # padding="same", replicate
     h = F.elu(F.conv1d(h, w[p + "layer1.weight"], w[p + "layer1.bias"]))
-    h = h.transpose(1, 2)                                        # [B, T, C]
+    h = _drop(h.transpose(1, 2), _site(masks, 1, SPEECH_SITES))  # [B, T, C]
     return F.elu(F.linear(h, w[p + "layer2.weight"], w[p + "layer2.bias"]))
 
 
@@ -121,9 +194,10 @@ def _conv3(x, wt, b):
     return F.conv1d(x.transpose(1, 2), wt, b, padding=1).transpose(1, 2)
 
 
-def _mha(x, in_w, in_b, out_w, out_b, nheads=4):
-    """nn.MultiheadAttention(E, 4) self-attention, no mask (modules.py:529-550).
-    Packed in_proj rows ordered q, k, v; scores scaled by 1/sqrt(head_dim)."""
+def _mha(x, in_w, in_b, out_w, out_b, nheads=4, pmask=None):
+    """nn.MultiheadAttention(E, 4, dropout=0.1) self-attention, no mask (modules.py:529-550).
+    Packed in_proj rows ordered q, k, v; scores scaled by 1/sqrt(head_dim); pmask: keep-scale [B, NH, L, L] of the
+    attention probabilities (the module's internal dropout acts on the softmax output, before the product with v)."""
     B, L, E = x.shape
     hd = E // nheads
     qkv = F.linear(x, in_w, in_b)                                # [B, L, 3E]
@@ -132,31 +206,33 @@ def _mha(x, in_w, in_b, out_w, out_b, nheads=4):
     k = k.reshape(B, L, nheads, hd).transpose(1, 2)
     v = v.reshape(B, L, nheads, hd).transpose(1, 2)
     s = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(hd)
-    a = torch.softmax(s, dim=-1)
+    a = _drop(torch.softmax(s, dim=-1), pmask)
     o = torch.matmul(a, v).transpose(1, 2).reshape(B, L, E)
     return F.linear(o, out_w, out_b)
 
 
-def style_encoder_attn(w, x, prefix="encoder."):
-    """x: [B, L, 1134] normalised -> [B, Eout]   (eval mode)."""
+def style_encoder_attn(w, x, prefix="encoder.", masks=None):
+    """x: [B, L, 1134] normalised -> [B, Eout].  masks=None: eval mode; else the five keep-scales in site order
+    ([B, L, H], [B, L, E], [B, NH, L, L], [B, L, E], [B, L, E])."""
     p = prefix
+    m = [_site(masks, i, STYLE_SITES) for i in range(STYLE_SITES)]
     h = F.relu(_conv3(x, w[p + "convs.0.conv.weight"], w[p + "convs.0.conv.bias"]))
-    h = F.layer_norm(h, h.shape[-1:], w[p + "convs.2.weight"], w[p + "convs.2.bias"], 1e-5)
+    h = _drop(F.layer_norm(h, h.shape[-1:], w[p + "convs.2.weight"], w[p + "convs.2.bias"], 1e-5), m[0])
     h = F.relu(_conv3(h, w[p + "convs.4.conv.weight"], w[p + "convs.4.conv.bias"]))
-    h = F.layer_norm(h, h.shape[-1:], w[p + "convs.6.weight"], w[p + "convs.6.bias"], 1e-5)
+    h = _drop(F.layer_norm(h, h.shape[-1:], w[p + "convs.6.weight"], w[p + "convs.6.bias"], 1e-5), m[1])
     L, E = h.shape[1], h.shape[2]
     h = h + positional_table(L, E, h.dtype)[None]                # modules.py:403,410
     b = p + "blocks.0."
     a = _mha(h, w[b + "attention.multi_head_attention.in_proj_weight"],
              w[b + "attention.multi_head_attention.in_proj_bias"],
              w[b + "attention.multi_head_attention.out_proj.weight"],
-             w[b + "attention.multi_head_attention.out_proj.bias"])
-    a = F.layer_norm(a + h, (E,), w[b + "attention.layer_norm.weight"],
+             w[b + "attention.multi_head_attention.out_proj.bias"], pmask=m[2])
+    a = F.layer_norm(_drop(a, m[3]) + h, (E,), w[b + "attention.layer_norm.weight"],
                      w[b + "attention.layer_norm.bias"], 1e-5)   # modules.py:555
     f = F.relu(_conv3(a, w[b + "feed_forward.convs.0.conv.weight"],
                       w[b + "feed_forward.convs.0.conv.bias"]))
     f = _conv3(f, w[b + "feed_forward.convs.2.conv.weight"], w[b + "feed_forward.convs.2.conv.bias"])
-    f = F.layer_norm(f + a, (E,), w[b + "feed_forward.layer_norm.weight"],
+    f = F.layer_norm(_drop(f, m[4]) + a, (E,), w[b + "feed_forward.layer_norm.weight"],
                      w[b + "feed_forward.layer_norm.bias"], 1e-5)  # modules.py:603
     return f.sum(dim=1) / L                                      # modules.py:416
 
@@ -179,10 +255,15 @@ def style_encoder_gru(w, x, prefix="encoder."):
                     w[p + "projection_layer.linear_layer.bias"])
 
 
-def style_encoder(w, x, eps, temperature=1.0, S=64):
+def style_encoder(w, x, eps, temperature=1.0, S=64, masks=None):
     """StyleEncoder.forward with use_vae (modules.py:289-302); `eps` is the
-    injected N(0,1) sample that the reference draws with randn_like."""
-    out = style_encoder_gru(w, x) if "encoder.rnn_layer.weight_ih_l0" in w else style_encoder_attn(w, x)   # type
+    injected N(0,1) sample that the reference draws with randn_like.  masks: see style_encoder_attn (the GRU type has
+    no dropout)."""
+    if "encoder.rnn_layer.weight_ih_l0" in w:       # type
+        assert masks is None
+        out = style_encoder_gru(w, x)
+    else:
+        out = style_encoder_attn(w, x, masks=masks)
     mu, logvar = out[:, :S], out[:, S:]
     std = torch.exp(0.5 * logvar) / temperature
     return mu + eps * std, mu, logvar

@@ -209,3 +209,285 @@ def grads_at_forward_point(g, it, state_dicts, O_point, kl_iteration=None):
     (loss_e + sum((o * ge.detach()).sum() for o, ge in zip(O64, g_e))).backward()
     grads = [v.grad if v.grad is not None else torch.zeros_like(v) for w in (ws[0], ws[1], ws[2]) for v in w.values()]
     return grads, [o.detach() for o in O64], [x.detach() for x in g_e]
+
+
+# ----------------------------------------------------------------------------- training mode: dropout masks and VAE noise
+# Mask contract (include/zeggs_hip.h, beside zeggs_dropout): a site's mask is a pure function of (seed + offset, element index);
+# element index = position in the contiguous [B * T, C] / [B * L, C] activation, attention ((b * NH + h) * L + q) * L + k;
+# offsets: speech encoder +1, +2 (after each ELU), style encoder +1 ... +5 (both conv-stack LayerNorms, attention
+# probabilities, attention output, feed-forward output).  zeggs_dropout(ones, n, p, seed) therefore returns the keep-scale.
+def relerr(got, ref):
+    got, ref = got.detach().double().cpu(), ref.detach().double().cpu()
+    return float((got - ref).abs().max() / max(1e-12, float(ref.abs().max())))
+
+
+def oracle_iteration_core(ws, audio_n, target, gaze, example_n, eps, it, masks=None):
+    """Loss + gradients of one training iteration computed by the oracle.  ws: the three state dicts (speech, decoder, style)
+    with requires_grad set; audio_n / example_n: normalised inputs; target: the 8 ground-truth tensors (root_pos, root_rot,
+    root_vel, root_vrt, lpos, ltxy, lvel, lvrt); masks: None (eval-mode encoders) or the 7 keep-scales, speech sites first."""
+    from oracle import loss as oloss
+    from oracle import nets as onets
+    dtype = audio_n.dtype
+    s = {k: v.to(dtype) for k, v in stats_tensors().items()}
+    speech = onets.speech_encoder(ws[0], audio_n, masks=None if masks is None else masks[:2])
+    z, mu, logvar = onets.style_encoder(ws[2], example_n, eps, masks=None if masks is None else masks[2:])
+    T = audio_n.shape[1]
+    O = onets.decoder_rollout(ws[1], *[t[:, 0] for t in target], gaze, speech, z.unsqueeze(1).repeat(1, T, 1),
+                              s["in_mean"], s["in_std"], s["out_mean"], s["out_std"], synth.DT)
+    loss, terms = oloss.training_loss(O, tuple(target), gaze, synth.PARENTS, synth.DT, mu, logvar, iteration=it)
+    loss.backward()
+    return loss, terms, ws
+
+
+def oracle_iteration(g, it, nets, s, dtype, masks=None):
+    """oracle_iteration_core on iteration `it` of a train_iter*.npz record `g` with the weights of `nets`."""
+    b = [torch.as_tensor(g[f"it{it}_batch{j}"]).to(dtype) for j in range(11)]
+    audio, gaze, wstyle = b[0], b[9], b[10]
+    sdd = {k: v.to(dtype) for k, v in s.items()}
+    ws = [sd(m, dtype) for m in nets]
+    for w in ws:
+        for v in w.values():
+            v.requires_grad_(True)
+    return oracle_iteration_core(ws, (audio - sdd["a_mean"]) / sdd["a_std"], b[1:9], gaze,
+                                 (wstyle - sdd["in_mean"]) / sdd["in_std"], torch.as_tensor(g[f"it{it}_eps"]).to(dtype), it,
+                                 masks=masks)
+
+
+def fixture_masks(g, prefix, dtype=torch.float64):
+    """the keep-scales a fixture stores bit-packed (oracle/nets.py pack_keeps): speech sites [B, T, C] x 2, then the style
+    encoder's five"""
+    from oracle import nets as onets
+    keeps = onets.unpack_keeps(g[prefix + "mask_bits"], g[prefix + "mask_shapes"], (3, 3, 3, 3, 4, 3, 3))
+    return onets.keep_scales(keeps, onets.SPEECH_P + onets.STYLE_P, dtype)
+
+
+def build_style(H, S, seed=SEED):
+    """a seeded attention style encoder (VAE) of hidden width H and encoding size S (E = 2 S)"""
+    torch.manual_seed(seed)
+    return modules.StyleEncoder(synth.POSE_IN, H, S, type="attn", use_vae=True)
+
+
+def build_speech(H, O, seed=SEED):
+    torch.manual_seed(seed)
+    return modules.SpeechEncoder(synth.N_AUDIO, H, O)
+
+
+def speech_case(B, T, O, seed):
+    """seeded inputs of a speech-encoder comparison: x [B, T, F], weights of the differentiated sum"""
+    gen = torch.Generator().manual_seed(seed)
+    return torch.randn(B, T, synth.N_AUDIO, generator=gen), torch.randn(B, T, O, generator=gen)
+
+
+def style_case(B, L, S, seed):
+    """seeded inputs of a style-encoder comparison: x [B, L, 1134], eps [B, S], weights of z / mu / logvar"""
+    gen = torch.Generator().manual_seed(seed)
+    return (torch.randn(B, L, synth.POSE_IN, generator=gen), torch.randn(B, S, generator=gen),
+            [torch.randn(B, S, generator=gen) for _ in range(3)])
+
+
+def f64_weights(module):
+    return {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in module.state_dict().items()}
+
+
+def oracle_speech(module, x, wgt, masks=None):
+    """float64 oracle: -> (output, {name: gradient}) of sum(out * wgt)"""
+    from oracle import nets as onets
+    w = f64_weights(module)
+    out = onets.speech_encoder(w, x.double(), masks=masks)
+    (out * wgt.double()).sum().backward()
+    return out.detach(), {k: v.grad for k, v in w.items()}
+
+
+def oracle_style(module, x, eps, wts, masks=None, temperature=0.9):
+    """float64 oracle: -> ((z, mu, logvar), {name: gradient}) of sum(z wz + mu wm + logvar wl)"""
+    from oracle import nets as onets
+    w = f64_weights(module)
+    outs = onets.style_encoder(w, x.double(), eps.double(), temperature, S=eps.shape[1], masks=masks)
+    sum((o * wt.double()).sum() for o, wt in zip(outs, wts)).backward()
+    return tuple(o.detach() for o in outs), {k: v.grad for k, v in w.items()}
+
+
+def worst_relerr(got, ref):
+    """largest relerr over a dict of tensors (every parameter in full)"""
+    assert set(got) == set(ref)
+    return max(relerr(got[k], ref[k]) for k in ref)
+
+
+def corruptions(masks, ps, seed):
+    """The negative controls of one mask set: for every site, (label, masks with that site REDRAWN at the same rate -- what a
+    wrong seed offset or a transposed index gives) and (label, masks whose BACKWARD at that site uses the redrawn mask while the
+    forward keeps the right one -- a backward that does not regenerate the forward's mask)."""
+    from oracle import nets as onets
+    other = onets.keep_scales(onets.draw_keeps([tuple(m.shape) for m in masks], ps, seed), ps, masks[0].dtype)
+    out = []
+    for i in range(len(masks)):
+        fwd = list(masks)
+        fwd[i] = other[i]
+        out.append((f"site {i + 1} redrawn", True, fwd))
+        bwd = list(masks)
+        bwd[i] = (masks[i], other[i])
+        out.append((f"site {i + 1} backward mask differs", False, bwd))
+    return out
+
+
+# ---- the device's own masks, read back through the public ABI
+class recorded_seeds:
+    """Context manager: wraps ops.next_seed and records (caller, seed) of every draw -- `caller` is the name of the ops function
+    that drew ("speech_encoder", "style_encoder_attn", "randn").  Restores ops.next_seed on exit."""
+
+    def __enter__(self):
+        import sys
+        from zeggs import ops
+        self.ops, self.orig, self.draws = ops, ops.next_seed, []
+
+        def next_seed():
+            s = self.orig()
+            self.draws.append((sys._getframe(1).f_code.co_name, s))
+            return s
+        ops.next_seed = next_seed
+        return self
+
+    def __exit__(self, *exc):
+        self.ops.next_seed = self.orig
+        return False
+
+    def of(self, caller):
+        got = [s for c, s in self.draws if c == caller]
+        assert len(got) == 1, (caller, self.draws)
+        return got[0]
+
+
+def _device_keep_scale(shape, p, seed, device="cuda:0"):
+    """zeggs_dropout on ones: element i of the contiguous array gets mask(seed, i) / (1 - p)"""
+    import ctypes
+    from zeggs import ops
+    x = torch.ones(*shape, device=device, dtype=torch.float32)
+    rc = ops.lib().zeggs_dropout(ctypes.c_void_p(x.data_ptr()), ctypes.c_long(x.numel()), ctypes.c_float(p),
+                                 ctypes.c_uint64(int(seed)), ops._stream())
+    assert rc == 0, ops.lib().zeggs_last_error().decode()
+    torch.cuda.synchronize()
+    m = x.cpu().double()
+    keep = m != 0
+    assert bool(((m - 1.0 / (1.0 - p)).abs() < 1e-6)[keep].all())      # every element is 0 or 1 / (1 - p)
+    return keep.double() / (1.0 - p)                                    # the exact float64 scale
+
+
+def device_masks_speech(seed, B, T, H, O):
+    from oracle import nets as onets
+    return [_device_keep_scale(sh, p, seed + 1 + i)
+            for i, (sh, p) in enumerate(zip(onets.speech_mask_shapes(B, T, H, O), onets.SPEECH_P))]
+
+
+def device_masks_style(seed, B, L, H, E, NH=4):
+    from oracle import nets as onets
+    return [_device_keep_scale(sh, p, seed + 1 + i)
+            for i, (sh, p) in enumerate(zip(onets.style_mask_shapes(B, L, H, E, NH), onets.STYLE_P))]
+
+
+def device_eps(seed, B, S, device="cuda:0"):
+    from zeggs import ops
+    return ops.randn((B, S), device, seed=seed).cpu()
+
+
+# ---- the training-mode matrix (tests/test_gpu_training_mode.py runs it on the device, tests/test_oracle_golden.py proves on the
+# CPU that a mask error at any site of any of these shapes is at least 10x the bounds)
+SPEECH_OUT_BOUND, SPEECH_GRAD_BOUND = 1e-5, 2e-4      # tests/test_gpu_parity.py::test_speech_encoder_forward_backward
+STYLE_OUT_BOUND, STYLE_GRAD_BOUND = 2e-5, 3e-4        # tests/test_gpu_parity.py::test_style_encoder_forward_backward
+ENGINE_GRAD_BOUND = 5e-4                              # tests/test_gpu_parity.py::test_train_iteration_vs_reference, iteration 0
+SPEECH_WIDTHS = ((64, 64), (30, 50))                  # (H, O); the second pair: neither width divisible by 4
+SPEECH_SHAPES = ((3, 70), (1, 31), (2, 15), (2, 200))     # (B, T); the kernel is 31 wide: T = 31 and 15 are all replicate edge
+# (H, E) -> lengths: every pair at one multiple of 32 and one other length, the default widths at all five
+STYLE_MATRIX = (((512, 128), (9, 33, 77, 128, 200)), ((200, 256), (77, 128)), ((256, 192), (9, 128)), ((30, 64), (128, 200)),
+                ((130, 128), (33, 128)), ((520, 128), (128, 200)), ((64, 520), (9, 128)))
+STYLE_REFUSED = ((1030, 128), (9,))                   # forward only: the backward of a row wider than 1024 is refused
+ENGINE_CASES = (dict(B=2, window=8, L=16, noise_seed=31, data_seed=41), dict(B=5, window=8, L=33, noise_seed=32, data_seed=42))
+
+
+def style_batch(H, E, L):
+    return 3 if (H, E) == (512, 128) else 2
+
+
+def engine_case_data(case):
+    return synth.make_processed(3, 0, case["window"] + 40, seed=case["data_seed"])
+
+
+def engine_case_idx(case, n_windows):
+    return np.random.default_rng(case["data_seed"]).permutation(n_windows)[:case["B"]]
+
+
+def host_batch(data, window, idx, ex_len, dtype=torch.float64):
+    """The batch of TrainEngine.step(idx, ex_len) rebuilt on the host in `dtype` from the processed data (reference
+    dataset.py:98-204: windows, the example's rows with its empty gaze slot, normalisation as train.py:232-250).
+    -> audio_n [B, T, F], target (8 tensors), gaze, example_n [B, L, 1134]"""
+    from zeggs import engine
+    ds = engine.DeviceDataset(data, window, torch.device("cpu"))
+    f = lambda k: torch.as_tensor(np.asarray(data[k])).to(dtype)  # noqa: E731
+    starts = ds.win_start[idx]
+    win = lambda k: torch.stack([f(k)[s:s + window] for s in starts])  # noqa: E731
+    audio_n = (win("X_audio_features") - f("audio_input_mean")) / f("audio_input_std")
+    target = [win(k) for k in ("Y_root_pos", "Y_root_rot", "Y_root_vel", "Y_root_vrt", "Y_lpos", "Y_ltxy", "Y_lvel", "Y_lvrt")]
+    rows = torch.as_tensor(ds.example_rows(idx, ex_len))
+    n = len(data["Y_root_pos"])
+    pose = torch.cat([f(k).reshape(n, -1) for k in ("Y_root_vel", "Y_root_vrt", "Y_lpos", "Y_ltxy", "Y_lvel", "Y_lvrt")], dim=1)
+    ex = torch.cat([pose[rows], torch.zeros(*rows.shape, 3, dtype=dtype)], dim=-1)
+    example_n = (ex - f("anim_input_mean")) / f("anim_input_std")
+    return audio_n, target, win("Y_gaze_pos"), example_n, ds
+
+
+# ---- ReLU kinks.  The style encoder has three ReLUs.  A unit whose float64 pre-activation is closer to zero than float32 can
+# resolve lands on either side in a float32 implementation (here: by the run-to-run order of the float atomics of the first
+# convolutions' split products), and its one-sided derivatives differ by 1: measured at (H, E) = (512, 128), B = 3, L = 33 -- one
+# unit of the feed-forward ReLU at 4.2e-7 of the largest pre-activation moved the worst gradient by 1.2e-2 in 3 runs of 10, and
+# flipping that one unit in the ORACLE reproduced the device's 20 gradient errors digit for digit.  Both one-sided derivatives are
+# gradients of the same function at that point, so the oracle offers both: units with |pre| < KINK * max |pre| of their ReLU (an
+# oracle-only criterion) are "near", and the comparison takes the assignment of sides closest to the device's gradients.
+# KINK = 2^-20 = 16 units of float32 roundoff: a K-term float32 dot product carries ~ sqrt(K) 2^-24 of its rms (K = 3402 for the
+# first convolution: 3.5e-6 of the rms, 5e-7 of the largest entry), doubled for the error of its inputs.
+KINK = 2.0 ** -20
+
+
+class relu_sites:
+    """Context manager around an ORACLE evaluation: records the near-kink units of every F.relu call as (call number, flat index);
+    the units listed in `flips` get the derivative of the other side (the value, |pre| ~ 0, is left alone)."""
+
+    def __init__(self, flips=()):
+        self.flips, self.near, self.n = set(flips), [], 0
+
+    def __enter__(self):
+        import torch.nn.functional as F
+        self.F, self.orig = F, F.relu
+        F.relu = self._relu
+        return self
+
+    def __exit__(self, *exc):
+        self.F.relu = self.orig
+        return False
+
+    def _relu(self, t, *a, **k):
+        site, self.n = self.n, self.n + 1
+        y = self.orig(t, *a, **k)
+        mag = t.detach().abs()
+        self.near += [(site, int(j)) for j in (mag < KINK * mag.max()).flatten().nonzero().flatten()]
+        for s, j in sorted(self.flips):
+            if s == site:
+                tj = t.flatten()[j]
+                d = 1.0 if float(tj.detach()) <= 0 else -1.0               # derivative 1 instead of 0, or 0 instead of 1
+                y = y.flatten().index_add(0, torch.tensor([j]), (d * (tj - tj.detach())).reshape(1)).reshape(t.shape)
+        return y
+
+
+def oracle_at_kinks(run, got):
+    """run() -> (outs, {name: gradient}) evaluates a float64 oracle; got: the implementation's gradients.  -> (outs, grads, near,
+    flipped): the oracle with, for every near-kink unit in turn, the side that brings it closer to `got` (no near unit: run())."""
+    with relu_sites() as rs:
+        outs, grads = run()
+    near, flips = list(rs.near), set()
+    assert len(near) <= 16, f"{len(near)} ReLU units within {KINK:.1e} of their kink"
+    best = worst_relerr(got, grads)
+    for unit in near:
+        with relu_sites(flips | {unit}):
+            _, alt = run()
+        e = worst_relerr(got, alt)
+        if e < best:
+            best, grads, flips = e, alt, flips | {unit}
+    return outs, grads, near, sorted(flips)

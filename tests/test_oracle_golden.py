@@ -47,27 +47,7 @@ def test_oracle_nets_forward_vs_reference(golden_dir):
         np.testing.assert_allclose(o.numpy(), g["O_" + n], atol=1e-4, rtol=1e-5, err_msg=n)
 
 
-def _oracle_iteration(g, it, nets, s, dtype):
-    """Loss + grads of one training iteration computed by the oracle."""
-    se, de, st = nets
-    b = [torch.as_tensor(g[f"it{it}_batch{j}"]).to(dtype) for j in range(11)]
-    audio, rpos, rrot, rvel, rvrt, lpos, ltxy, lvel, lvrt, gaze, wstyle = b
-    sdd = {k: v.to(dtype) for k, v in s.items()}
-    ws = [helpers.sd(m, dtype) for m in (se, de, st)]
-    for w in ws:
-        for v in w.values():
-            v.requires_grad_(True)
-    speech = onets.speech_encoder(ws[0], (audio - sdd["a_mean"]) / sdd["a_std"])
-    z, mu, logvar = onets.style_encoder(ws[2], (wstyle - sdd["in_mean"]) / sdd["in_std"],
-                                        torch.as_tensor(g[f"it{it}_eps"]).to(dtype))
-    T = audio.shape[1]
-    O = onets.decoder_rollout(ws[1], rpos[:, 0], rrot[:, 0], rvel[:, 0], rvrt[:, 0], lpos[:, 0], ltxy[:, 0],
-                              lvel[:, 0], lvrt[:, 0], gaze, speech, z.unsqueeze(1).repeat(1, T, 1),
-                              sdd["in_mean"], sdd["in_std"], sdd["out_mean"], sdd["out_std"], synth.DT)
-    loss, terms = oloss.training_loss(O, (rpos, rrot, rvel, rvrt, lpos, ltxy, lvel, lvrt), gaze,
-                                      synth.PARENTS, synth.DT, mu, logvar, iteration=it)
-    loss.backward()
-    return loss, terms, ws
+_oracle_iteration = helpers.oracle_iteration      # (shared with tests/test_gpu_training_mode.py)
 
 
 def test_oracle_train_iteration_vs_reference(golden_dir):
@@ -364,3 +344,185 @@ def test_iteration1_conditioning_and_the_forward_point_arbiter(golden_dir):
           f"of |dL/dO| = {share:.3f}")
     assert worst_arb < 5e-4, worst_arb
     assert worst64 > 5 * worst_arb                # the fp64-point comparison is the ill-conditioned one
+
+
+# ----------------------------------------------------------------------------- training mode: dropout masks
+def _nets_train_case(g, case):
+    from oracle import make_golden
+    audio, ex, eps, w_speech, w_style = make_golden.nets_train_inputs(case)
+    got = np.stack([helpers.fingerprint(torch.as_tensor(a)) for a in (audio, ex, eps, w_speech, *w_style)])
+    np.testing.assert_allclose(got, g[case["tag"] + "_in_fp"], rtol=1e-12, err_msg="seeded input generator drifted")
+    return audio, ex, eps, w_speech, w_style
+
+
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64], ids=["fp32", "fp64"])
+def test_oracle_masked_encoders_vs_reference_training_mode(golden_dir, dtype):
+    """nets_train.npz: the reference's SpeechEncoder and StyleEncoder(attn, VAE) in .train() with seeded dropout masks (every
+    F.dropout call consumed a stored mask) against the oracle given THE SAME masks -- outputs in full, every parameter gradient
+    (fingerprint + samples), at B = 3, L = 21 and B = 2, T = 45, L = 64.  Bounds: float32 run -- those of
+    test_oracle_nets_forward_vs_reference (2e-6, z 5e-6) and of test_oracle_train_iteration_vs_reference (gradient samples 2e-4 of
+    the largest, |g| sum 1e-3); float64 run -- those of test_oracle_fp64_vs_reference_fp64_both_iterations (1e-11, gradients
+    1e-9 of the largest entry)."""
+    from oracle import make_golden
+    g = np.load(golden_dir / "nets_train.npz")
+    f64 = dtype == torch.float64
+    sfx = "64" if f64 else ""
+    se, _, st = helpers.build_nets()
+    for case in make_golden.NETS_TRAIN_CASES:
+        tag = case["tag"]
+        audio, ex, eps, w_speech, w_style = _nets_train_case(g, case)
+        masks = helpers.fixture_masks(g, tag + "_", dtype)
+        t = lambda a: torch.as_tensor(a).to(dtype)  # noqa: E731
+        ws = [{k: v.clone().requires_grad_(True) for k, v in helpers.sd(m, dtype).items()} for m in (se, st)]
+        speech = onets.speech_encoder(ws[0], t(audio), masks=masks[:2])
+        z, mu, logvar = onets.style_encoder(ws[1], t(ex), t(eps), 1.0, masks=masks[2:])
+        for name, got in (("speech", speech), ("mu", mu), ("logvar", logvar), ("z", z)):
+            ref = g[f"{tag}_{name}{sfx}"]
+            if f64:
+                assert np.abs(got.detach().numpy() - ref).max() <= 1e-11 * np.abs(ref).max(), (tag, name)
+            else:
+                np.testing.assert_allclose(got.detach().numpy(), ref, atol=5e-6 if name == "z" else 2e-6, err_msg=f"{tag} {name}")
+        ((speech * t(w_speech)).sum() + sum((o * t(w)).sum() for o, w in zip((z, mu, logvar), w_style))).backward()
+        for ntag, w in (("speech", ws[0]), ("style", ws[1])):
+            for k, v in w.items():
+                got = v.grad.flatten()[helpers.sample_idx(v.numel())].numpy()
+                ref, gmax = g[f"{tag}_gsamp{sfx}_{ntag}.{k}"], float(g[f"{tag}_gmax{sfx}_{ntag}.{k}"])
+                fp = g[f"{tag}_gfp{sfx}_{ntag}.{k}"]
+                if f64:
+                    assert np.abs(got - ref).max() <= 1e-9 * gmax, (tag, ntag, k)
+                    np.testing.assert_allclose(helpers.fingerprint(v.grad)[1], fp[1], rtol=1e-9)
+                else:
+                    scale = max(1e-6, float(np.abs(ref).max()))
+                    np.testing.assert_allclose(got, ref, atol=2e-4 * scale + 1e-8, err_msg=f"{tag} {ntag}.{k}")
+                    np.testing.assert_allclose(helpers.fingerprint(v.grad)[1], fp[1], rtol=1e-3)
+
+
+def test_oracle_train_iteration_with_dropout_vs_reference(golden_dir):
+    """train_iter_dropout.npz: the two iterations of train_iter.npz through the reference's train() with dropout ON (seeded masks
+    consumed by every F.dropout call).  Iteration 0 of the oracle with the same masks: float32 against the float32 run with the
+    bounds of test_oracle_train_iteration_vs_reference (loss, 18 terms, gradient samples + |g| sums, weights after one RAdam step),
+    float64 against the float64 run with those of test_oracle_fp64_vs_reference_fp64_both_iterations."""
+    g, gd = np.load(golden_dir / "train_iter.npz"), np.load(golden_dir / "train_iter_dropout.npz")
+    chk = np.stack([helpers.fingerprint(torch.as_tensor(g[f"it{it}_batch{j}"]).double()) for it in range(2) for j in range(11)])
+    np.testing.assert_allclose(chk, gd["batch_check"], rtol=1e-12)            # the batches are train_iter.npz's
+    np.testing.assert_array_equal(g["it0_eps"], gd["it0_eps"])
+    s = helpers.stats_tensors()
+    # float32
+    loss, terms, ws = helpers.oracle_iteration(g, 0, helpers.build_nets(), s, torch.float32,
+                                               masks=helpers.fixture_masks(gd, "it0_", torch.float32))
+    np.testing.assert_allclose(float(loss), gd["loss"][0], rtol=2e-6)
+    np.testing.assert_allclose(terms.detach().numpy(), gd["terms"][0], rtol=2e-5, atol=1e-7)
+    plist = [v for w in ws for k, v in w.items()]
+    off, gs, ws_after = 0, gd["it0_grad_samples"], gd["it0_weight_samples"]
+    for i, p in enumerate(plist):
+        idx = helpers.sample_idx(p.numel())
+        got = p.grad.flatten()[idx].numpy()
+        ref = gs[off:off + len(idx)]
+        scale = max(1e-6, float(np.abs(ref).max()))
+        np.testing.assert_allclose(got, ref, atol=2e-4 * scale + 1e-8, err_msg=f"grad of param {i}")
+        np.testing.assert_allclose(helpers.fingerprint(p.grad)[1], gd["it0_grad_fp"][i][1], rtol=1e-3)
+        pn, gn = p.detach().flatten()[idx].numpy().copy(), got.copy()
+        m, v = np.zeros_like(pn), np.zeros_like(pn)
+        oradam.radam_step(pn, gn, m, v, 1, 1e-4, 1e-5)
+        np.testing.assert_allclose(pn, ws_after[off:off + len(idx)], atol=1e-7)
+        off += len(idx)
+    assert off == len(gs)
+    # float64
+    loss, terms, ws = helpers.oracle_iteration(g, 0, helpers.build_nets(), s, torch.float64,
+                                               masks=helpers.fixture_masks(gd, "it0_", torch.float64))
+    np.testing.assert_allclose(float(loss), gd["loss64"][0], rtol=1e-11)
+    np.testing.assert_allclose(terms.detach().numpy(), gd["terms64"][0], rtol=1e-9, atol=1e-12)
+    got = np.concatenate([p.grad.flatten()[helpers.sample_idx(p.numel())].numpy() for w in ws for p in w.values()])
+    ref = gd["it0_grad_samples64"]
+    assert got.shape == ref.shape and np.abs(got - ref).max() <= 1e-9 * np.abs(ref).max()
+    # the masks did something: the iteration is not the eval-mode one
+    assert np.abs(gd["it0_grad_samples"] - g["it0_grad_samples"]).max() > 1e-2 * np.abs(g["it0_grad_samples"]).max()
+    # the reference's own float32-vs-float64 gradient gap under these masks, per tensor (the yardstick a float32 implementation
+    # in training mode can be held to): recorded, a few 1e-4 at iteration 0
+    print(f"\nreference fp32 vs fp64 under dropout, worst tensor: iteration 0 {gd['it0_ref32_vs_ref64'].max():.2e}, "
+          f"iteration 1 {gd['it1_ref32_vs_ref64'].max():.2e}")
+
+
+def _control(label, base_out, base_grads, run, masks, ps, seed, out_bound, grad_bound):
+    """every corruption of `masks` (helpers.corruptions) moves the worst parameter gradient by > 10 x grad_bound, and -- the
+    forward ones -- the outputs by > 10 x out_bound.  -> the smallest separations seen (output, gradient), as multiples of the
+    bounds."""
+    sep_o, sep_g = float("inf"), float("inf")
+    for what, is_fwd, bad in helpers.corruptions(masks, ps, seed):
+        outs, grads = run(bad)
+        eg = helpers.worst_relerr(grads, base_grads)
+        eo = max(helpers.relerr(a, b) for a, b in zip(outs, base_out))
+        assert eg > 10 * grad_bound, f"{label}: {what}: worst gradient moves by {eg:.2e}, the bound is {grad_bound:.0e}"
+        sep_g = min(sep_g, eg / grad_bound)
+        if out_bound is None:
+            continue
+        if is_fwd:
+            assert eo > 10 * out_bound, f"{label}: {what}: outputs move by {eo:.2e}, the bound is {out_bound:.0e}"
+            sep_o = min(sep_o, eo / out_bound)
+        else:
+            assert eo < 1e-12, f"{label}: {what}: a backward-only corruption moved the outputs ({eo:.2e})"
+    return sep_o, sep_g
+
+
+@pytest.mark.parametrize("H,O", helpers.SPEECH_WIDTHS)
+def test_negative_control_speech_mask_errors_exceed_the_gpu_bounds(H, O):
+    """What makes tests/test_gpu_training_mode.py able to fail: in the float64 oracle, replace ONE site's mask by another draw of
+    the same rate (a wrong seed offset / a transposed element index), or let the backward use another mask than the forward --
+    at the shortest (T = 8, the engine step's window) and the longest (T = 200) sequence of each width pair the worst parameter
+    gradient moves by more than 10x the GPU tests' gradient bound (the larger of the encoder bound 2e-4 and the engine step's
+    5e-4), and the output by more than 10x its bound (1e-5)."""
+    se = helpers.build_speech(H, O)
+    for B, T in ((2, 8), (2, 200)):
+        x, wgt = helpers.speech_case(B, T, O, seed=100 + T)
+        masks = onets.keep_scales(onets.draw_keeps(onets.speech_mask_shapes(B, T, H, O), onets.SPEECH_P, 7), onets.SPEECH_P)
+        run = lambda m: (lambda o, gr: ((o,), gr))(*helpers.oracle_speech(se, x, wgt, m))  # noqa: E731
+        out, grads = run(masks)
+        so, sg = _control(f"speech {H}/{O} T={T}", out, grads, run, masks, onets.SPEECH_P, 8, helpers.SPEECH_OUT_BOUND,
+                          max(helpers.SPEECH_GRAD_BOUND, helpers.ENGINE_GRAD_BOUND))
+        print(f"\nspeech {H}/{O} B={B} T={T}: smallest separation {so:.0f}x the output bound, {sg:.0f}x the gradient bound")
+
+
+@pytest.mark.parametrize("HE,lengths", helpers.STYLE_MATRIX + (helpers.STYLE_REFUSED,),
+                         ids=[f"{h}-{e}" for (h, e), _ in helpers.STYLE_MATRIX + (helpers.STYLE_REFUSED,)])
+def test_negative_control_style_mask_errors_exceed_the_gpu_bounds(HE, lengths):
+    """the same for the five sites of the style encoder at the shortest and the longest length of every (H, E) of the GPU matrix
+    (mean pooling over L averages one mask's effect down: the longest length is the hard end), against 10x the output bound 2e-5
+    and 10x the larger of the gradient bounds (3e-4 encoder, 5e-4 engine step)."""
+    H, E = HE
+    st = helpers.build_style(H, E // 2)
+    for L in sorted({min(lengths), max(lengths)}):
+        B = helpers.style_batch(H, E, L)
+        x, eps, wts = helpers.style_case(B, L, E // 2, seed=200 + L)
+        masks = onets.keep_scales(onets.draw_keeps(onets.style_mask_shapes(B, L, H, E), onets.STYLE_P, 17), onets.STYLE_P)
+        run = lambda m: helpers.oracle_style(st, x, eps, wts, m)  # noqa: E731
+        out, grads = run(masks)
+        so, sg = _control(f"style {H}/{E} L={L}", out, grads, run, masks, onets.STYLE_P, 18, helpers.STYLE_OUT_BOUND,
+                          max(helpers.STYLE_GRAD_BOUND, helpers.ENGINE_GRAD_BOUND))
+        print(f"\nstyle {H}/{E} B={B} L={L}: smallest separation {so:.0f}x the output bound, {sg:.0f}x the gradient bound")
+
+
+@pytest.mark.parametrize("case", helpers.ENGINE_CASES, ids=lambda c: f"B{c['B']}-L{c['L']}")
+def test_negative_control_engine_step_mask_errors_exceed_the_gpu_bounds(case):
+    """... and through the whole iteration (the engine-step cases of the GPU test: B = 2 / example 16, B = 5 / example 33, window
+    8): each of the seven corruptions moves the worst of the 44 gradient tensors by more than 10x the 5e-4 the GPU test allows.
+    (The scalar loss is NOT a discriminator here and is not claimed to be one: with seeded, untrained nets it moves by 2e-6 when a
+    mask is redrawn -- below its own 1e-5 bound.  In the engine step the gradients carry the mask check, the loss does not.)"""
+    B, L = case["B"], case["L"]
+    from zeggs import engine
+    data = helpers.engine_case_data(case)
+    n_win = len(engine.DeviceDataset(data, case["window"], torch.device("cpu")))
+    idx = helpers.engine_case_idx(case, n_win)
+    audio_n, target, gaze, example_n, ds = helpers.host_batch(data, case["window"], idx, L)
+    eps = torch.as_tensor(np.random.default_rng(3).standard_normal((B, 64)))
+    ps = onets.SPEECH_P + onets.STYLE_P
+    masks = onets.keep_scales(onets.draw_keeps(onets.speech_mask_shapes(B, case["window"]) + onets.style_mask_shapes(B, L), ps, 27), ps)
+    nets = helpers.build_nets()
+
+    def run(m):
+        ws = [helpers.f64_weights(n) for n in nets]
+        loss, terms, ws = helpers.oracle_iteration_core(ws, audio_n, target, gaze, example_n, eps, 0, masks=m)
+        return (loss.detach().reshape(1),), {f"{i}.{k}": v.grad for i, w in enumerate(ws) for k, v in w.items()}
+    out, grads = run(masks)
+    assert len(grads) == 44
+    so, sg = _control(f"engine step B={B} L={L}", out, grads, run, masks, ps, 28, None, helpers.ENGINE_GRAD_BOUND)
+    print(f"\nengine step B={B} L={L}: smallest separation {sg:.0f}x the gradient bound")

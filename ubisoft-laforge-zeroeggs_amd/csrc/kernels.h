@@ -22,6 +22,7 @@ int k_act_bwd_v(RowView dx, RowView dy, RowView y, long R, int C, int act, float
 //   out  = dx * mask(seed_post) * act'(ysave);  dbias[c] += sum_rows out   (atomics; the gradient of the bias that produced the
 //          LayerNorm's input);  pad_L > 0: `out` is the interior of a [B, pad_L + 2, C] buffer whose edge rows are zeroed here
 // Element index of the masks: row * C + c (k_dropout over the contiguous [R, C] array).  In-place use is fine row by row.
+// C <= 1024 (16-byte lanes up to 512, scalar lanes above).
 struct LnBwdFused {
   RowView dyA, dyB;
   const float* dy_pool;

@@ -796,12 +796,12 @@ LnBwdFused ln_bwd_fused_args(int R, int C) {
 int g_ln_bwd4 = 1;      // zeggs_set_option("ln_bwd4", 0/1): the 16-byte-lane form of the fused LayerNorm backward pass (A/B switch)
 static bool rv_al16(const RowView& v) { return v.p == nullptr || ((((size_t)v.p) & 15) == 0 && (v.rpb == 0 || v.bstride % 4 == 0)); }
 int k_ln_bwd_fused(const LnBwdFused& a, hipStream_t s) {
-  ZCHECK(a.C <= 512, "ln_bwd_fused: C=%d > 512 unsupported", a.C);
+  ZCHECK(a.C <= 1024, "ln_bwd_fused: C=%d > 1024 unsupported", a.C);
   ZCHECK(a.out.p != nullptr && (a.dy_pool != nullptr || a.dyA.p != nullptr), "ln_bwd_fused: missing operand");
   const bool al = a.C % 4 == 0 && rv_al16(a.dyA) && rv_al16(a.dyB) && rv_al16(a.x) && rv_al16(a.res) && rv_al16(a.dx_raw) &&
                   rv_al16(a.out) && rv_al16(a.ysave) && (((size_t)a.dy_pool) & 15) == 0 &&
                   a.R > 0 && (long)a.R * a.C < (1L << 31);
-  if (g_ln_bwd4 && al) {
+  if (g_ln_bwd4 && al && a.C <= 512) {
     // 16-wave blocks, ~1 per CU (the column sums of a block end in 3 C atomics: with 512 four-wave blocks those 196 k atomics onto
     // 24 cache lines were half of the kernel's 20 us), whole passes per block
     // (wider rows keep 4-wave blocks: two pipelined passes of 8 float4 operands do not fit 16 waves' register budget)
@@ -815,7 +815,10 @@ int k_ln_bwd_fused(const LnBwdFused& a, hipStream_t s) {
   }
   const int rpb = 16;
   if (a.C <= 128) hipLaunchKernelGGL((ln_bwd_fused_k<2>), dim3(cdiv(a.R, rpb)), dim3(256), 0, s, a, rpb);
-  else hipLaunchKernelGGL((ln_bwd_fused_k<8>), dim3(cdiv(a.R, rpb)), dim3(256), 0, s, a, rpb);
+  else if (a.C <= 512) hipLaunchKernelGGL((ln_bwd_fused_k<8>), dim3(cdiv(a.R, rpb)), dim3(256), 0, s, a, rpb);
+  // 512 < C <= 1024 (a style encoder wider than the fused forward serves: encoders.hip runs its unfused forward chain there, whose
+  // saved tensors are the ones this pass reads): the scalar-lane form with the row in 16 registers per lane, 48 KB of LDS
+  else hipLaunchKernelGGL((ln_bwd_fused_k<16>), dim3(cdiv(a.R, rpb)), dim3(256), 0, s, a, rpb);
   ZLAUNCH_CHECK("ln_bwd_fused");
   return 0;
 }
