@@ -334,7 +334,9 @@ int zeggs_side_stream(void** out /* hipStream_t */);
  * ZEGGS/anim/txform.py:10-34, 17 weighted L1 terms + KL, sum/18) and its backward.
  * O = prediction (pose/rpos/rrot as produced by zeggs_decoder_fwd), W = ground truth in the same layout.
  * terms[18] (weighted, as logged by the reference), loss = sum(terms)/18 in terms[18].
- * kl_weight <= 0 or mu == NULL disables the KL term.  Gradients are scaled by `gscale` (1/world_size). */
+ * kl_weight <= 0 or mu == NULL disables the KL term.  Gradients are scaled by `gscale` (1/world_size).
+ * 1 <= J <= 256, B >= 1, T >= 1 (T == 1: the four finite-difference terms are 0), ws_bytes >= zeggs_loss_workspace_bytes:
+ * checked before anything is launched (-1 + zeggs_last_error()). */
 typedef struct {
   int B, T, J, S;
   float dt;

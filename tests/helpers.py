@@ -491,3 +491,238 @@ def oracle_at_kinks(run, got):
         if e < best:
             best, grads, flips = e, alt, flips | {unit}
     return outs, grads, near, sorted(flips)
+
+
+# ----------------------------------------------------------------------------- loss kernels (tests/test_gpu_loss.py)
+# Fixtures for ANY parent table, the L1 kinks, and the per-slice gradient comparison.  tests/test_loss_oracle_cpu.py proves on the
+# CPU that every case below meets the near-kink condition and that the comparison is sharp (negative controls).
+LOSS_GROUPS = ("root_pos", "root_rot", "root_vel", "root_vrt", "lpos", "ltxy", "lvel", "lvrt")
+LOSS_TERM_BOUND = dict(rtol=3e-5, atol=1e-7)          # tests/test_gpu_parity.py::test_loss_forward_backward_vs_oracle
+LOSS_BOUND, LOSS_GRAD_BOUND, LOSS_KL_BOUND = 3e-5, 3e-4, 1e-5
+LOSS_NEAR_MARGIN, LOSS_NEAR_MAX = 16, 16
+LOSS_KL_ITERATION = 9000
+
+
+def _tree40():
+    rng = np.random.default_rng(40)
+    return [-1] + [int(rng.integers(0, i)) for i in range(1, 40)]
+
+
+LOSS_SKELETONS = {
+    "rig": list(synth.PARENTS),                                     # 75 joints, 13 levels, widths 1 3 3 5 5 5 3 3 5 12 10 10 10
+    "j1": [-1],                                                     # one level, no message
+    "chain12": [-1] + list(range(11)),                              # every level one joint: seven idle waves at every barrier
+    "star16": [-1] + [0] * 16,                                      # a level of exactly LOSS_LW joints: message slots 12-15
+    "star17": [-1] + [0] * 17,                                      # wider than LOSS_LW: the table walk, chosen by maxw
+    "star20": [-1] + [0] * 20,
+    "tree40": _tree40(),                                            # seeded random tree, parents[i] < i
+    "j256": [-1] + [0 if k == 0 else 1 + c * 17 + k - 1 for c in range(15) for k in range(17)],   # MAXJ; 17 levels of 15
+}
+# (skeleton, B, T, root rotations); ids "rig-3x7-general" ...
+LOSS_CASES = ([("rig", 3, 7, "yaw")] +
+              [("rig", B, T, "general") for B, T in ((3, 7), (2, 8), (1, 4), (1, 12), (2, 2), (10, 7), (5, 28), (3, 1))] +
+              [(s, B, T, "general") for s in ("j1", "chain12", "star16", "star17", "star20", "tree40")
+               for B, T in ((3, 7), (2, 8), (10, 7))] + [("j256", 2, 4, "general")])
+LOSS_MOVED_CASES = [("rig", B, T, "general", grp) for B, T in ((3, 7), (2, 8)) for grp in LOSS_GROUPS]
+# the terms a moved group reaches (every other term is exactly 0 when the rest of the prediction IS the ground truth)
+LOSS_REACH = dict(root_pos={0, 4, 8, 12, 14, 16}, root_rot={1, 2, 3, 4, 6, 7, 8, 9, 10, 11, 12, 14, 15, 16}, root_vel={2, 6, 10},
+                  root_vrt={3, 6, 7, 10, 11}, lpos={4, 6, 8, 10, 12, 14}, ltxy={5, 8, 9, 10, 11, 13, 14, 15}, lvel={6, 10},
+                  lvrt={7, 10, 11})
+
+
+def loss_case_id(case):
+    return "-".join([case[0], f"{case[1]}x{case[2]}", case[3]] + list(case[4:]))
+
+
+def loss_case_seed(case):
+    """one seed per case (chosen so that at most LOSS_NEAR_MAX elements are near a kink: tests/test_loss_oracle_cpu.py)"""
+    s, B, T, root = case[:4]
+    return 1000 * sorted(LOSS_SKELETONS).index(s) + 31 * B + T + (500 if root == "yaw" else 0)
+
+
+def tree_clip(parents, nframes, seed, root="general"):
+    """synth.make_clip for an arbitrary parent table: smooth motion of len(parents) joints, float32 arrays under the Y_* keys.
+    root = "yaw": rotations (cos, 0, sin, 0) as synth.make_clip; "general": unit quaternions drifting around a random point of the
+    sphere, w < 0 for odd seeds."""
+    rng = np.random.default_rng(seed)
+    J, n, S, DT = len(parents), nframes + 1, synth._smooth, synth.DT
+    if root == "yaw":
+        yaw = S(rng, n, 1, 0.4)[:, 0]
+        root_rot = np.stack([np.cos(yaw / 2), np.zeros(n), np.sin(yaw / 2), np.zeros(n)], axis=1)
+    else:
+        c = rng.standard_normal(4)
+        c[0] = -abs(c[0]) if seed % 2 else abs(c[0])
+        q = c / np.linalg.norm(c) + S(rng, n, 4, 0.15)
+        root_rot = q / np.linalg.norm(q, axis=1, keepdims=True)
+    root_pos = np.cumsum(S(rng, n, 3, 0.5) * DT * 30, axis=0)
+    root_vel = S(rng, n, 3, 6.0)
+    root_vrt = S(rng, n, 3, 0.2)
+    hel = S(rng, n, J * 3, 0.35).reshape(n, J, 3)               # smooth along TIME (angular velocities of a few rad / s)
+    lrot = synth._quat_exp(hel / 2.0)
+    ex = np.zeros((n, J, 3)); ex[..., 0] = 1.0
+    ey = np.zeros((n, J, 3)); ey[..., 1] = 1.0
+    ltxy = np.stack([synth._quat_mul_vec(lrot, ex), synth._quat_mul_vec(lrot, ey)], axis=2)
+    lpos = rng.normal(0, 8.0, (1, J, 3)) + S(rng, n, J * 3, 0.05).reshape(n, J, 3)
+    lvel = (lpos[1:] - lpos[:-1]) / DT
+    lvrt = (hel[1:] - hel[:-1]) / DT
+    gaze = np.array([[10.0, 150.0, 100.0]]) + rng.normal(0, 1.0, (1, 3)) + S(rng, n, 3, 2.0)
+    f, m = np.float32, nframes
+    return dict(Y_root_pos=root_pos[:m].astype(f), Y_root_rot=root_rot[:m].astype(f), Y_root_vel=root_vel[:m].astype(f),
+                Y_root_vrt=root_vrt[:m].astype(f), Y_lpos=lpos[:m].astype(f), Y_ltxy=ltxy[:m].astype(f), Y_lvel=lvel.astype(f),
+                Y_lvrt=lvrt.astype(f), Y_gaze_pos=gaze[:m].astype(f))
+
+
+def loss_case(case):
+    """-> dict(O, W: 8 float32 tensors [B, T, ...] (LOSS_GROUPS order), gaze, mu, logvar, parents, T).  Prediction O = W + 0.3 (O' -
+    W) with O' another clip; "general" root rotations: the truth's, perturbed and scaled to norms 0.7 ... 1.3 (the decoder emits
+    non-unit quaternions); "yaw": the fixture of test_gpu_parity.py::test_loss_forward_backward_vs_oracle (synth.make_clip).
+    A fifth entry of the case names the ONE group that moves: every other group of the prediction is the truth bit for bit."""
+    skel, B, T, root = case[:4]
+    parents, seed = LOSS_SKELETONS[skel], loss_case_seed(case)
+    rng = np.random.default_rng(seed + 7)
+    keys = ["Y_" + n for n in LOSS_GROUPS]
+    tt = lambda cl, k: torch.as_tensor(np.stack([c[k] for c in cl]))  # noqa: E731
+    if root == "yaw":
+        assert skel == "rig"
+        stats = synth.make_stats()
+        Wc = [synth.make_clip(T, seed=90 + b, stats=stats) for b in range(B)]
+        Oc = [synth.make_clip(T, seed=190 + b, stats=stats) for b in range(B)]
+    else:
+        Wc = [tree_clip(parents, T, seed + 3 * b, root) for b in range(B)]            # seeds of both parities: w > 0 and w < 0
+        Oc = [tree_clip(parents, T, seed + 100 + 3 * b, root) for b in range(B)]
+    W = [tt(Wc, k) for k in keys]
+    step = 1.0 if len(case) > 4 else 0.3          # (a group that moves alone moves all the way to the other clip)
+    O = [w + step * (o - w) for o, w in zip([tt(Oc, k) for k in keys], W)]
+    if root != "yaw":
+        q = W[1].double() + 0.1 * torch.as_tensor(rng.standard_normal((B, T, 4)))
+        q = q / q.norm(dim=-1, keepdim=True) * torch.as_tensor(rng.uniform(0.7, 1.3, (B, T, 1)))
+        O[1] = q.float()
+    if len(case) > 4:
+        O = [o if n == case[4] else w.clone() for n, o, w in zip(LOSS_GROUPS, O, W)]
+    mu = torch.as_tensor(rng.standard_normal((B, 64)), dtype=torch.float32)
+    lv = torch.as_tensor(0.3 * rng.standard_normal((B, 64)), dtype=torch.float32)
+    return dict(O=O, W=W, gaze=tt(Wc, "Y_gaze_pos"), mu=mu, logvar=lv, parents=parents, T=T)
+
+
+def unpack_pose_tree(pose, J):
+    B, T = pose.shape[:2]
+    vel, vrt, lpos, ltxy, lvel, lvrt = torch.split(pose, (3, 3, 3 * J, 6 * J, 3 * J, 3 * J), dim=-1)
+    return vel, vrt, lpos.reshape(B, T, J, 3), ltxy.reshape(B, T, J, 2, 3), lvel.reshape(B, T, J, 3), lvrt.reshape(B, T, J, 3)
+
+
+def loss_slices(grads):
+    """8 gradient tensors (LOSS_GROUPS order) -> {slice name: tensor}: the four root groups whole, the joint groups per joint."""
+    out = {}
+    for n, t in zip(LOSS_GROUPS, grads):
+        if n.startswith("root"):
+            out[n] = t
+        else:
+            for j in range(t.shape[2]):
+                out[f"{n}[{j}]"] = t[:, :, j]
+    return out
+
+
+def slice_errors(got, ref):
+    """per slice: max |got - ref| / max |ref| (each slice against its OWN largest entry); a slice whose reference is exactly zero
+    must be exactly zero: its error is 0 or inf"""
+    errs = {}
+    for k, r in loss_slices(ref).items():
+        gk = loss_slices_get(got, k)
+        m = float(r.abs().max())
+        if m == 0.0:
+            errs[k] = 0.0 if float(gk.abs().max()) == 0.0 else float("inf")
+        else:
+            errs[k] = float((gk.double() - r.double()).abs().max()) / m
+    return errs
+
+
+def loss_slices_get(grads, key):
+    n, _, j = key.partition("[")
+    t = grads[LOSS_GROUPS.index(n)]
+    return t if not j else t[:, :, int(j[:-1])]
+
+
+def packed_error(got, ref):
+    """the OLD view: one max-norm over the packed pose gradient, root_pos, root_rot (test_loss_forward_backward_vs_oracle)"""
+    return max(relerr(pack_pose(*got[2:]), pack_pose(*ref[2:])), relerr(got[0], ref[0]), relerr(got[1], ref[1]))
+
+
+def loss_term_args(data, dtype, bug=None):
+    from oracle import loss as oloss
+    with torch.no_grad():
+        return oloss.term_arguments([o.to(dtype) for o in data["O"]], [w.to(dtype) for w in data["W"]], data["gaze"].to(dtype),
+                                    data["parents"], synth.DT, bug=bug)
+
+
+def loss_near_elements(data, x64=None):
+    """L1 kinks.  |x| has two one-sided derivatives at 0: an element of a term's argument whose float64 value is below what float32
+    forward kinematics can resolve gets either sign in a float32 implementation, and one flipped sign moves an input gradient by
+    2 w / n.  The criterion is a MEASURED envelope taken from the oracle alone: per term and per joint (per term for the root and
+    gaze terms) E = max |x32 - x64| over batch, frames and components, x32 / x64 the term arguments of the oracle run in float32 /
+    float64 on the same float32 inputs; an element is near iff 0 < |x64| <= LOSS_NEAR_MARGIN E (exact zeros give sign 0 on both
+    sides).  -> [(term, flat index)], {term: E}."""
+    x32 = loss_term_args(data, torch.float32)
+    x64 = loss_term_args(data, torch.float64) if x64 is None else [x.detach() for x in x64]
+    near, env = [], {}
+    for k, (a, b) in enumerate(zip(x32, x64)):
+        if k in (12, 13, 14, 15) and data["T"] == 1:
+            continue
+        dev = (a.double() - b).abs()
+        if 4 <= k <= 15:
+            dims = [d for d in range(dev.dim()) if d != 2]
+            E = dev.amax(dim=dims, keepdim=True)
+        else:
+            E = dev.amax().reshape([1] * dev.dim())
+        env[k] = float(E.max())
+        hit = ((b.abs() > 0) & (b.abs() <= LOSS_NEAR_MARGIN * E)).flatten().nonzero().flatten()
+        near += [(k, int(j)) for j in hit]
+    return near, env
+
+
+def loss_oracle(data, dtype=torch.float64, bug=None, sides=None):
+    """oracle of one case in `dtype`: -> (loss, terms[18], [the 8 input gradients in LOSS_GROUPS order, dmu, dlogvar]); T = 1: without
+    the four finite-difference terms"""
+    from oracle import loss as oloss
+    O = [o.to(dtype).requires_grad_(True) for o in data["O"]]
+    mu, lv = data["mu"].to(dtype).requires_grad_(True), data["logvar"].to(dtype).requires_grad_(True)
+    skip = oloss.DIFF_TERMS if data["T"] == 1 else ()
+    loss, terms = oloss.training_loss(O, [w.to(dtype) for w in data["W"]], data["gaze"].to(dtype), data["parents"], synth.DT, mu,
+                                      lv, iteration=LOSS_KL_ITERATION, sides=sides, skip=skip, bug=bug)
+    grads = torch.autograd.grad(loss, O + [mu, lv], allow_unused=True)
+    grads = [torch.zeros_like(t) if g is None else g for g, t in zip(grads, O + [mu, lv])]
+    return loss.detach(), terms, grads
+
+
+def worst_slice(errs):
+    k = max(errs, key=lambda n: errs[n])
+    return k, errs[k]
+
+
+def loss_oracle_at_kinks(data, got):
+    """The float64 oracle with, for every near-kink element in turn, the side (-1, 0, +1) that brings its input gradients closest
+    to `got` (8 tensors, LOSS_GROUPS order) in the worst slice.  The gradient is linear in the sides -- d loss / d input = base +
+    sum over near elements (side - sign) / (18 n_term) d x_e / d input -- so one extra backward per near element is all it takes.
+    -> (loss, terms, grads (8 + dmu, dlogvar), near, chosen: [((term, index), oracle's sign, side taken)])"""
+    from oracle import loss as oloss
+    O = [o.double().requires_grad_(True) for o in data["O"]]
+    Wd, gz = [w.double() for w in data["W"]], data["gaze"].double()
+    x = oloss.term_arguments(O, Wd, gz, data["parents"], synth.DT)
+    near, _ = loss_near_elements(data, x)
+    assert len(near) <= LOSS_NEAR_MAX, f"{len(near)} term elements within {LOSS_NEAR_MARGIN} x the float32 envelope of their kink"
+    loss, terms, grads = loss_oracle(data)
+    base, chosen = [g.clone() for g in grads[:8]], []
+    for k, j in near:
+        xe = x[k].flatten()[j]
+        D = torch.autograd.grad(xe, O, retain_graph=True, allow_unused=True)
+        D = [torch.zeros_like(o) if d is None else d / (18.0 * x[k].numel()) for d, o in zip(D, O)]
+        s0 = float(torch.sign(xe.detach()))
+        best = (worst_slice(slice_errors(got, base))[1], s0, base)
+        for s in (-1.0, 0.0, 1.0):
+            if s != s0:
+                cand = [b + (s - s0) * d for b, d in zip(base, D)]
+                e = worst_slice(slice_errors(got, cand))[1]
+                if e < best[0]:
+                    best = (e, s, cand)
+        base = best[2]
+        chosen.append(((k, j), s0, best[1]))
+    return loss, terms, base + list(grads[8:]), near, chosen

@@ -2042,6 +2042,22 @@ def test_c_abi_rejects_bad_arguments_loudly():
                                  p(dev_buf), p(dev_buf), p(dev_buf), p(dev_buf), p(dev_buf), 0, p(dev_buf), C.c_size_t(16),
                                  stream)
         assert rc == -1 and msg in L.zeggs_last_error().decode(), (msg, L.zeggs_last_error())
+    # loss: at most 256 joints, a non-empty batch, the workspace zeggs_loss_workspace_bytes states -- refused before any launch
+    for (B, T, J), short, msg in (((2, 4, 257), 0, "more than 256 joints"), ((0, 4, 75), 0, "bad dims"),
+                                  ((2, 4, 75), 1, "workspace too small")):
+        ld = ops.LossDims(B, T, J, 64, 0.016)
+        need = L.zeggs_loss_workspace_bytes(C.byref(ld))
+        ws = torch.zeros(need, dtype=torch.uint8, device=DEV)
+        big = torch.zeros(max(1, B) * T * (6 + 15 * J), device=DEV)
+        par = torch.zeros(J, dtype=torch.int32, device=DEV)
+        rc = L.zeggs_loss_fwd_bwd(C.byref(ld), p(par), p(big), p(big), p(big), p(big), p(big), p(big), p(big), p(big), p(big),
+                                  C.c_float(0.1), p(big), p(big), p(big), p(big), p(big), p(big), C.c_float(1.0), p(ws),
+                                  C.c_size_t(need - short), stream)
+        assert rc == -1 and msg in L.zeggs_last_error().decode(), (msg, L.zeggs_last_error())
+        if not short:
+            continue
+        rc = L.zeggs_loss_prepare_truth(C.byref(ld), p(par), p(big), p(big), p(big), p(big), p(ws), C.c_size_t(need - short), stream)
+        assert rc == -1 and msg in L.zeggs_last_error().decode(), (msg, L.zeggs_last_error())
     # unknown option, bad mel dims, streaming range ahead of the received samples
     assert L.zeggs_set_option(b"no_such_option", 1) == -1 and b"unknown option" in L.zeggs_last_error()
     from zeggs import audio

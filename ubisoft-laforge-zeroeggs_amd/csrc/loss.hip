@@ -356,9 +356,9 @@ __device__ __forceinline__ void term_of(int e, int J, int& id, float& w, int& id
 __device__ __forceinline__ float sgn(float x) { return x > 0.f ? 1.f : (x < 0.f ? -1.f : 0.f); }
 
 // one block = one feature row e, looping over all frames (coalesced along the frame axis);
-// writes G = dLoss/dF_O and accumulates the row's share of its (one or two) loss terms
+// writes G = dLoss/dF_O and leaves the row's share of its (one or two) loss terms in the partials table
 __global__ __launch_bounds__(256) void loss_terms_k(ZeggsLossDims d, const float* FO, const float* FW, float* G,
-                                                     float* terms, float gscale) {
+                                                     float* partial, float gscale) {
   __shared__ float red[16];
   const long NF = (long)d.B * d.T;
   const int e = blockIdx.x;
@@ -389,17 +389,20 @@ __global__ __launch_bounds__(256) void loss_terms_k(ZeggsLossDims d, const float
   }
   s1 = block_sum(s1, red);
   if (id2 >= 0) s2 = block_sum(s2, red);
-  if (threadIdx.x == 0) {
-    atomicAdd(terms + id, s1 / n1);
-    if (id2 >= 0 && d.T > 1) atomicAdd(terms + id2, s2 / n2);
+  if (threadIdx.x == 0) {      // the row's sums to the partials table (slot 0 of its LOSS_TSPLIT): loss_kl_final_k adds them up in a fixed order
+    float* ps = partial + (long)e * LOSS_TSPLIT * 2;
+    for (int k = 0; k < 2 * LOSS_TSPLIT; ++k) ps[k] = 0.f;
+    ps[0] = s1 / n1;
+    if (id2 >= 0 && d.T > 1) ps[1] = s2 / n2;
   }
 }
 
 // The same, four consecutive frames per thread (16-byte loads / stores; T % 4 == 0, so a thread's frames lie in one window) and
 // LOSS_TSPLIT workgroups per feature row: the scalar form moved 245 MB in 110 us (2.2x its HBM bound: 2 496 workgroups are 1.2
 // rounds of the chip, 4-byte accesses); identical G (same expression per element).  The workgroups' term sums go to a partials
-// table that loss_kl_final_k adds up in LDS: 5 000 float atomics onto the 18 words of ONE cache line were what the first version
-// of this kernel spent its time on (122 us, no faster than the scalar form).
+// table that loss_kl_final_k adds up in LDS, in a fixed order: 5 000 float atomics onto the 18 words of ONE cache line were what
+// the first version of this kernel spent its time on (122 us, no faster than the scalar form), and made the terms differ from call
+// to call.
 __global__ __launch_bounds__(256) void loss_terms4_k(ZeggsLossDims d, const float* FO, const float* FW, float* G,
                                                       float* partial, float gscale) {
   __shared__ float red[16];
@@ -724,20 +727,25 @@ __global__ __launch_bounds__(1024) void loss_kl_final_k(const float* mu, const f
                                                         const float* partial, int nrows, int J) {
   __shared__ float red[16];
   __shared__ float tsum[18];
-  if (partial) {        // term sums of loss_terms4_k's workgroups (LDS atomics: 18 words, one workgroup)
-    if (threadIdx.x < 18) tsum[threadIdx.x] = 0.f;
+  // the term sums of the terms kernels' workgroups.  Bitwise reproducible from call to call (tests/test_gpu_loss.py: a prepared
+  // truth half, gscale, unit_grad must not move the terms): no float atomics.  Pass 1: a wave's 64 consecutive partials ("chunk")
+  // are summed per term -- consecutive rows belong to the same term, a wave sees one to three of them -- into the chunk's row of
+  // csum; pass 2: one wave per term adds the chunks up, lanes striding over them, in an order that depends on nothing but J.
+  constexpr int MAXCHUNK = ((21 + 33 * MAXJ) * LOSS_TSPLIT + 63) / 64;
+  __shared__ float csum[MAXCHUNK][17];
+  {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nwaves = blockDim.x >> 6, total = nrows * LOSS_TSPLIT;
+    const int nchunks = (total + 63) / 64;
+    for (int i = threadIdx.x; i < nchunks * 17; i += blockDim.x) (&csum[0][0])[i] = 0.f;
     __syncthreads();
-    // consecutive rows belong to the same term (a wave sees one to three of them): summed per term across the wave first -- 64 lanes'
-    // atomics onto ONE LDS word serialise, which made this reduction 13 of the kernel's 18 us
-    const int lane = threadIdx.x & 63, total = nrows * LOSS_TSPLIT;
-    auto add_by_key = [&](int key, float v) {       // key < 0: lane takes no part
+    auto add_by_key = [&](int chunk, int key, float v) {       // key < 0: lane takes no part
       unsigned long long todo = __ballot(key >= 0);
       while (todo) {
         const int leader = __ffsll((long long)todo) - 1;
         const int k = __shfl(key, leader, 64);
         const bool mine = key == k;
         const float sum = wave_sum(mine ? v : 0.f);
-        if (lane == leader) atomicAdd(&tsum[k], sum);
+        if (lane == leader) csum[chunk][k] = sum;              // (a term appears once per chunk: plain ids 0-11, 16, differences 12-15)
         todo &= ~__ballot(mine);
       }
     };
@@ -745,8 +753,15 @@ __global__ __launch_bounds__(1024) void loss_kl_final_k(const float* mu, const f
       const int i = i0 + lane;
       int id = -1, id2 = -1, size; float w, w2;
       if (i < total) term_of(i / LOSS_TSPLIT, J, id, w, id2, w2, size);
-      add_by_key(id, i < total ? partial[2 * i] : 0.f);
-      add_by_key(id2, id2 >= 0 ? partial[2 * i + 1] : 0.f);
+      add_by_key(i0 >> 6, id, i < total ? partial[2 * i] : 0.f);
+      add_by_key(i0 >> 6, id2, id2 >= 0 ? partial[2 * i + 1] : 0.f);
+    }
+    __syncthreads();
+    for (int k = wave; k < 17; k += nwaves) {
+      float v = 0.f;
+      for (int c = lane; c < nchunks; c += 64) v += csum[c][k];
+      v = wave_sum(v);
+      if (lane == 0) tsum[k] = v;
     }
     __syncthreads();
     if (threadIdx.x < 17) terms[threadIdx.x] += tsum[threadIdx.x];
@@ -796,6 +811,11 @@ extern "C" size_t zeggs_loss_workspace_bytes(const ZeggsLossDims* d) {
   carve_loss(*d, a);
   return a.off + 256;
 }
+// the argument checks of both entry points, ahead of any launch: the workspace is the size zeggs_loss_workspace_bytes states
+#define LOSS_CHECK_ARGS(d, a, ws_bytes)                                                                                    \
+  ZCHECK((d).J <= MAXJ, "loss: more than %d joints", MAXJ);                                                                \
+  ZCHECK((d).J >= 1 && (d).T >= 1 && (d).B >= 1, "loss: bad dims");                                                        \
+  ZCHECK((a).ok() && (ws_bytes) >= (a).off + 256, "loss: workspace too small (%zu < %zu)", (size_t)(ws_bytes), (a).off + 256)
 
 // The ground-truth half of the feature pass (pose rows transposed, forward kinematics of the truth side) depends on the batch
 // only: a training loop may run it ahead of the step, on any stream, into the workspace the loss call of that batch will be
@@ -806,8 +826,7 @@ extern "C" int zeggs_loss_prepare_truth(const ZeggsLossDims* dp, const int* pare
   hipStream_t s = (hipStream_t)stream;
   Arena a(ws, ws_bytes);
   LossWs w = carve_loss(d, a);
-  ZCHECK(a.ok(), "loss: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  ZCHECK(d.J >= 1 && d.J <= MAXJ && d.T >= 1 && d.B >= 1, "loss: bad dims");
+  LOSS_CHECK_ARGS(d, a, ws_bytes);
   const int lds_ok = g_loss_lds ? loss_lds_ready() : 0;
   const long NF = (long)d.B * d.T;
   const int PO = 6 + 15 * d.J;
@@ -836,8 +855,7 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
   hipStream_t s = (hipStream_t)stream;
   Arena a(ws, ws_bytes);
   LossWs w = carve_loss(d, a);
-  ZCHECK(a.ok(), "loss: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  ZCHECK(d.J >= 1 && d.T >= 1 && d.B >= 1, "loss: bad dims");
+  LOSS_CHECK_ARGS(d, a, ws_bytes);
   const int lds_ok = g_loss_lds ? loss_lds_ready() : 0;
   const long NF = (long)d.B * d.T;
   const Off o = offsets(d.J);
@@ -847,7 +865,6 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
   const dim3 tg((unsigned)cdiv(NF, 64), (unsigned)cdiv(PO, 64));
   hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT0, o_pose, NF, PO);
   if (!truth_prepared) hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT1, w_pose, NF, PO);
-  ZCHECK(d.J <= MAXJ, "loss: more than %d joints", MAXJ);
   // (truth_prepared: zeggs_loss_prepare_truth has filled PT1 / FW of THIS workspace; only the prediction side is left)
   const long gend = truth_prepared ? NF : 2 * NF;
   hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(gend, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
@@ -856,11 +873,10 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
   if (d.T % 4 == 0 && ((uintptr_t)w.FO % 16 == 0) && ((uintptr_t)w.FW % 16 == 0) && ((uintptr_t)w.G % 16 == 0))      // (= vec4 below)
     hipLaunchKernelGGL(loss_terms4_k, dim3(o.n, LOSS_TSPLIT), dim3(256), 0, s, d, w.FO, w.FW, w.G, w.PS, gscale);
   else
-    hipLaunchKernelGGL(loss_terms_k, dim3(o.n), dim3(256), 0, s, d, w.FO, w.FW, w.G, terms, gscale);
+    hipLaunchKernelGGL(loss_terms_k, dim3(o.n), dim3(256), 0, s, d, w.FO, w.FW, w.G, w.PS, gscale);
   ZLAUNCH_CHECK("loss_terms");
-  const bool vec4 = d.T % 4 == 0 && ((uintptr_t)w.FO % 16 == 0) && ((uintptr_t)w.FW % 16 == 0) && ((uintptr_t)w.G % 16 == 0);
   hipLaunchKernelGGL(loss_kl_final_k, dim3(1), dim3(1024), 0, s, mu, logvar, d.B * d.S, d.B, kl_weight, terms, dmu, dlogvar,
-                     gscale, vec4 ? w.PS : (const float*)nullptr, o.n, d.J);
+                     gscale, (const float*)w.PS, o.n, d.J);
   ZLAUNCH_CHECK("loss_kl_final");
   if (dpose) {
     hipLaunchKernelGGL(loss_frame_bwd_k, dim3(cdiv(NF, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, gaze, w.PT0, w.FO, w.LM, w.G,
