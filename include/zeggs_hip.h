@@ -290,6 +290,7 @@ int zeggs_decoder_bwd(const ZeggsDecDims*, const ZeggsDecParams*, const ZeggsDec
 #define ZEGGS_GAVE_UP_DECODE 1u    /* decode_persistent_k   (B = 1 inference rollout) */
 #define ZEGGS_GAVE_UP_TRAIN_FWD 2u /* train_fwd_persistent_k (training rollout) */
 #define ZEGGS_GAVE_UP_BPTT 4u      /* train_bwd_persistent_k (BPTT sweep) */
+#define ZEGGS_GAVE_UP_BATCH_FWD 8u /* train_fwd_persistent_k, inference form (zeggs_decoder_fwd_batch) */
 typedef struct {
   int prepared;
   int defer_wgrads;
@@ -316,6 +317,41 @@ int zeggs_decoder_fwd_state_ex(const ZeggsDecDims*, const ZeggsDecParams*, const
                                const float* rpos0, const float* rrot0, const float* gaze, const float* speech,
                                const float* style, float* pose, float* rpos, float* rrot, const float* h_in,
                                float* h_out, void* ws, size_t ws_bytes, void* stream, const ZeggsDecCall* call);
+/* Batch decode (zeggs_version() >= 102): B = 2..64 rows of INFERENCE advance together on the weight-stationary sweep of the
+ * training rollout (csrc/train_persistent.hip, inference form: no saved gates, no per-step canonical rows) -- many clips per
+ * decode instead of one B = 1 rollout each (the reference's generate.py --csv loop).  Non-FiLM, H = 1024; everything else, and a
+ * sweep that is switched off ("train_persistent") or failed its validation, runs on the stage launches.
+ *   zeggs_decoder_batch_workspace_bytes   the inference workspace of zeggs_decoder_workspace_bytes(d, 0) + the sweep's packs + the
+ *                                         write-once operand buffers of ONE chunk of d.T frames (no backward buffers).  A
+ *                                         workspace sized for d.T serves every chunk length <= d.T.
+ *   zeggs_decoder_batch_prepare           the weight-only work (folded matrices, per-workgroup packs), once per job list; returns
+ *                                         the mask for ZeggsDecCall.prepared of the zeggs_decoder_fwd_batch calls on this
+ *                                         workspace (0: nothing done, these dimensions go to the stage launches; < 0: error).
+ *   zeggs_decoder_state_init              the CellStateEncoder alone: pose0 [B,PO], rpos0 [B,3], rrot0 [B,4], gaze0 [B,3] and
+ *                                         style0 [B,ST] of frame 0 -> h_out [2,B,H], the state a clip starts from (rows of h_in
+ *                                         for the rows that begin a clip in the next chunk).  Any decoder workspace.
+ *   zeggs_decoder_fwd_batch               one chunk, arguments as zeggs_decoder_fwd_state_ex (h_in and h_out required, d.T >= 2;
+ *                                         the sweep needs d.T >= 4).  Rows are independent: whatever an idle row holds, NaN
+ *                                         included, reaches no other row, and on the sweep what a
+ *                                         row holds in speech / style / gaze PAST its last valid frame does not reach that
+ *                                         frame either (on the stage launches keep those frames finite).  mode 0: the sweep.  Its first use on a process is
+ *                                         validated (device sync + error word; never inside a stream capture); later give-ups
+ *                                         OR ZEGGS_GAVE_UP_BATCH_FWD into call->status (and NaN into the last frame): the caller
+ *                                         looks at the word and redoes the chunk with mode 1 = the stage launches.
+ *   zeggs_decoder_batch_last_path         which path the calling thread's last zeggs_decoder_fwd_batch took: 1 the persistent
+ *                                         sweep, 2 not the sweep: the inference dispatch of zeggs_decoder_fwd_state (the stage
+ *                                         launches; for B = 1 the B = 1 persistent kernel) (0: none yet). */
+size_t zeggs_decoder_batch_workspace_bytes(const ZeggsDecDims*);
+int zeggs_decoder_batch_prepare(const ZeggsDecDims*, const ZeggsDecParams*, const ZeggsDecStats*, void* ws, size_t ws_bytes,
+                                void* stream);
+int zeggs_decoder_state_init(const ZeggsDecDims*, const ZeggsDecParams*, const ZeggsDecStats*, const float* pose0,
+                             const float* rpos0, const float* rrot0, const float* gaze0, const float* style0, float* h_out,
+                             void* ws, size_t ws_bytes, void* stream);
+int zeggs_decoder_fwd_batch(const ZeggsDecDims*, const ZeggsDecParams*, const ZeggsDecStats*, const float* pose0,
+                            const float* rpos0, const float* rrot0, const float* gaze, const float* speech,
+                            const float* style, float* pose, float* rpos, float* rrot, const float* h_in, float* h_out,
+                            void* ws, size_t ws_bytes, void* stream, const ZeggsDecCall* call, int mode);
+int zeggs_decoder_batch_last_path(void);
 /* second half of the deferred weight gradients (ZeggsDecCall.defer_wgrads = 2): what = 4 -> GRU layer 0 and layer0;
  * what | 8: the gradient outputs are zero on entry (as ZeggsDecCall.grads_zeroed of the backward it completes) */
 int zeggs_decoder_wgrads(const ZeggsDecDims*, const ZeggsDecGrads*, void* ws, size_t ws_bytes, int what, void* stream);

@@ -727,6 +727,119 @@ static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, con
   return save_state();
 }
 
+// ---------------------------------------------------------------- batch decode: many clips per weight-stationary rollout
+// N rows of inference advance together, chunk by chunk, on the training rollout's sweep (train_persistent.hip, inference form): the
+// weights stay in the register files and a step costs about what ONE row costs the B = 1 kernel.  The rollout is chunked and
+// resumable exactly like zeggs_decoder_fwd_state (frame 0 of a chunk = the last frame already produced, h_in / h_out [2,B,H]); a
+// row starts a new clip at a chunk boundary by taking its h_in rows from zeggs_decoder_state_init.  Reached only through these
+// entry points: what the existing ones dispatch to is unchanged.
+static thread_local int t_batch_last_path = 0;
+extern "C" int zeggs_decoder_batch_last_path(void) { return t_batch_last_path; }
+
+extern "C" size_t zeggs_decoder_batch_workspace_bytes(const ZeggsDecDims* d) {
+  Arena a(nullptr, 0);
+  carve_dec_batch(*d, a);
+  return a.off + 256;
+}
+
+// bit 0: the sweep takes these dimensions; bit 1 (with bit 0): its GRU packs are 4-row tiles
+static int batch_sweep_mask(const ZeggsDecDims& d, const DecWs& w) {
+  if (!(g_decoder_fast && dec_fast_supported(d) && g_train_persistent && dec_tp_state() != 0 && dec_tb_supported(d, w))) return 0;
+  return 1 | (dec_tb_t4(w) ? 2 : 0);
+}
+
+extern "C" int zeggs_decoder_batch_prepare(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st, void* ws,
+                                           size_t ws_bytes, void* stream) {
+  const ZeggsDecDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  Arena a(ws, ws_bytes);
+  DecWs w = carve_dec_batch(d, a);
+  ZCHECK(a.ok(), "decoder batch prepare: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const int mask = batch_sweep_mask(d, w);
+  if (!mask) return 0;
+  ZTRY(dec_fast_merge_prep(d, P, st, w, s));
+  ZTRY(dec_tp_pack(d, P, st, w, s, (mask & 2) ? 1 : 0));
+  return mask;
+}
+
+// the CellStateEncoder alone: GRU state [2,B,H] a clip starts from, given its first pose and the gaze target / style of frame 0
+extern "C" int zeggs_decoder_state_init(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                        const float* pose0, const float* rpos0, const float* rrot0, const float* gaze0,
+                                        const float* style0, float* h_out, void* ws, size_t ws_bytes, void* stream) {
+  ZeggsDecDims d = *dp;
+  d.T = 1;                                        // gaze0 [B,3], style0 [B,ST]: one frame per row
+  hipStream_t s = (hipStream_t)stream;
+  ZCHECK(d.PI == d.PO + 3, "decoder: pose_input_size must be pose_output_size + 3 (gaze)");
+  ZCHECK(d.B >= 1, "decoder: empty batch");
+  Arena a(ws, ws_bytes);
+  DecWs w = carve_dec(d, 0, a);
+  ZCHECK(a.ok(), "decoder state init: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const int B = d.B, H = d.H, CI = d.PI + d.ST;
+  const long sH = (long)B * H;
+  // (frame-0 copies of the outputs land in step scratch: Y [B,POL], gi [B,3H])
+  hipLaunchKernelGGL(dec_init_k, dim3(B), dim3(256), 0, s, d, *st, pose0, rpos0, rrot0, gaze0, style0, w.Y, w.gi, w.gi + 4L * B,
+                     w.cse_in, w.Gin, w.GL);
+  ZLAUNCH_CHECK("dec_init");
+  ZTRY(gemm_nt(w.cse_in, CI, P->c0_w, CI, w.cse_a, H, P->c0_b, B, H, CI, ACT_ELU, 0.f, s));
+  ZTRY(gemm_nt(w.cse_a, H, P->c1_w, H, w.cse_b, H, P->c1_b, B, H, H, ACT_ELU, 0.f, s));
+  ZTRY(gemm_nt(w.cse_b, H, P->c2_w, H, h_out, H, P->c2_b, B, H, H, ACT_NONE, 0.f, s));
+  ZTRY(gemm_nt(w.cse_b, H, P->c2_w + (long)H * H, H, h_out + sH, H, P->c2_b + H, B, H, H, ACT_NONE, 0.f, s));
+  return 0;
+}
+
+// mode 0: the sweep (first use on a process validated by a device sync and the error word -- never inside a stream capture --,
+// later give-ups OR ZEGGS_GAVE_UP_BATCH_FWD into call->status and the caller redoes the chunk with mode 1); dimensions the sweep
+// does not take, a disabled sweep, a failed validation: the stage launches.  mode 1: the stage launches.
+extern "C" int zeggs_decoder_fwd_batch(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                       const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
+                                       const float* speech, const float* style, float* pose, float* rpos, float* rrot,
+                                       const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
+                                       const ZeggsDecCall* call, int mode) {
+  const ZeggsDecDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  ZCHECK(d.PI == d.PO + 3, "decoder: pose_input_size must be pose_output_size + 3 (gaze)");
+  ZCHECK(d.B >= 1 && d.T >= 2, "decoder batch: empty batch or chunk");
+  ZCHECK(h_in && h_out, "decoder batch: h_in and h_out are required (zeggs_decoder_state_init gives the state a clip starts from)");
+  Arena a(ws, ws_bytes);
+  DecWs w = carve_dec_batch(d, a);
+  ZCHECK(a.ok(), "decoder batch: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  unsigned* status = call ? call->status : nullptr;
+  int mask = mode == 0 ? batch_sweep_mask(d, w) : 0;
+  if (mask) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;
+    if (!(cap == hipStreamCaptureStatusNone || dec_tp_state() == 1)) mask = 0;
+  }
+  if (mask) {
+    const int B = d.B, H = d.H, GL = w.GL, XD = w.XD;
+    const long sG = (long)B * GL;
+    float* gin1 = w.Gin + sG;
+    ZTRY(k_fill(w.Gin, 2 * sG, 0.f, s));
+    hipLaunchKernelGGL(dec_init_k, dim3(B), dim3(256), 0, s, d, *st, pose0, rpos0, rrot0, gaze, style, pose, rpos, rrot, w.cse_in,
+                       gin1, GL);
+    hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1, 1, sG, 1);
+    ZLAUNCH_CHECK("dec_fill_cond");
+    ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
+    if (!(call && (call->prepared & 1) && (call->prepared & 2) == (mask & 2))) {
+      ZTRY(dec_fast_merge_prep(d, P, st, w, s));
+      ZTRY(dec_tp_pack(d, P, st, w, s, (mask & 2) ? 1 : 0));
+    }
+    const bool validated = dec_tp_state() == 1;
+    ZTRY(dec_tb_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, h_in, h_out, s, validated ? status : nullptr));
+    t_batch_last_path = 1;
+    if (validated) return 0;
+    unsigned perr = 1;
+    ZCHECK(hipStreamSynchronize(s) == hipSuccess, "persistent batch decode: stream sync failed");
+    ZTRY(dec_tp_errors(w, &perr));
+    dec_tp_set_state(perr == 0 ? 1 : 0);
+    if (perr == 0) return 0;
+    // a bounded wait gave up (not every workgroup resident?): disabled for this process, the stage launches redo the chunk
+  }
+  t_batch_last_path = 2;
+  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, 0, h_in, h_out, ws, ws_bytes,
+                          stream, nullptr);
+}
+
 // error word of the chained (run-ahead) stage launches of the last rollout that used `ws`: 0 = every hand-off wait was
 // satisfied; non-zero = a bounded spin gave up (the results of that rollout are invalid).  Synchronises the device.
 extern "C" int zeggs_decoder_chain_errors(const ZeggsDecDims* dp, int training, void* ws, size_t ws_bytes, int* out) {

@@ -155,6 +155,23 @@ inline DecWs carve_dec(const ZeggsDecDims& d, int training, Arena& a) {
   return w;
 }
 
+// Workspace of the batch decode (zeggs_decoder_fwd_batch): the inference ring and stage-launch packs of carve_dec(d, 0) -- the
+// fall-back runs on them --, then what the weight-stationary sweep needs: its packs and folded matrices first (weights only, made
+// once per job: their offsets must not depend on the chunk length), then the write-once operand buffers of ONE chunk of d.T frames.
+// None of the backward buffers of carve_dec(d, 1).
+inline DecWs carve_dec_batch(const ZeggsDecDims& d, Arena& a) {
+  DecWs w = carve_dec(d, 0, a);
+  if (d.H == 1024 && d.B <= 64 && !d.film) {
+    const long BLK = 256, T = d.T, H = d.H, XB = 256L * w.NB;
+    const long KB0 = 64 + w.KBX + 64 > 201 ? 64 + w.KBX + 64 : 201, KB3 = 64 + w.KBC;      // (the sweep walks zeggs_tp::TKB0 = 201 blocks)
+    w.tp_w0 = a.f(256L * 8 * 26 * BLK); w.tp_w1 = a.f(256L * 8 * 16 * BLK); w.tp_w3 = a.f(256L * 8 * 9 * BLK);   // [wg][wave][block]
+    w.tp_n0s = a.f(3 * H * (long)w.POL); w.tp_n0 = a.f(3 * H * H); w.tp_cv0 = a.f(3 * H); w.tp_p1x = a.f((long)d.B * 3 * H);
+    w.tp_cnt = (unsigned*)a.f(8192);
+    w.G0xf = a.f(T * KB0 * XB); w.G1xf = a.f(T * 128 * XB); w.G3xf = a.f(T * KB3 * XB);
+  }
+  return w;
+}
+
 extern int g_poll_sleep;           // s_sleep units (64 clocks) between two polls of the arrival slots (option "poll_sleep")
 extern int g_poll_stagger;         // != 0: two polls of the arrival slots in flight, this many s_sleep units apart (option "poll_stagger")
 extern int g_persistent_spin;      // bound of the device-side waits of the persistent kernels (option "persistent_spin")
@@ -172,7 +189,13 @@ int dec_persistent_errptr(const DecWs& w, unsigned** out);
 int dec_tp_supported(const ZeggsDecDims& d, const DecWs& w);
 int dec_tp_state();
 void dec_tp_set_state(int v);
-int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s);
+int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4 = -1);
+// batch decode on the same sweep (inference form of the kernel; zeggs_decoder_fwd_batch)
+int dec_tb_t4(const DecWs& w);
+int dec_tb_supported(const ZeggsDecDims& d, const DecWs& w);
+int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
+               const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* h_in, float* h_out,
+               hipStream_t s, unsigned* status);
 int dec_tp_zero(const ZeggsDecDims& d, DecWs& w, hipStream_t s);
 int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
                const float* speech, const float* style, float* pose, float* rpos, float* rrot, hipStream_t s,

@@ -48,6 +48,7 @@ struct TArgs {
   const f4 *PW0, *PW1, *PW3;                 // per-workgroup fragment packs [256][KB][64]
   float *G0, *G1, *G3;                       // operand fragments, time-major [T][KB*][NB][64][4]
   float *Gin, *H0, *H1, *GT0, *GT1;          // canonical saves (time-major)
+  float *Hout0, *Hout1;                      // inference form: GRU state after the chunk's last frame, [B,H] each (H0 / H1: the state it starts from)
   const float *b_ih0, *b_hh0, *b_ih1, *b_hh1, *cvec, *l0_w, *l2_b;
   const float* w_ih0;                        // [3H][H + XD]: its three gaze columns (H + PO ..) are applied by the gate threads
   const float *cv0, *p1x;                    // folded pose term of GRU layer 0: constant [3H], step-1 product [B][3H]

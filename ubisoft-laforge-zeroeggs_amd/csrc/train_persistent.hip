@@ -223,7 +223,10 @@ __device__ __forceinline__ void tp_mma4(const float (&wq)[NW], const float* wl, 
 #endif
 template <bool C, typename A, typename B> struct tp_pick { typedef A type; };
 template <typename A, typename B> struct tp_pick<false, A, B> { typedef B type; };
-template <int NB, bool T4 = false>
+// INF: the inference form (zeggs_decoder_fwd_batch) -- the same rollout of one CHUNK resumed from a given state: a.H0 / a.H1 are the
+// caller's state after frame 0 of the chunk ([B,H] each), a.Hout0 / a.Hout1 receive the state after its last frame, a.Gin is the
+// 2-slot inference ring (slot 1 = [hid_1 | x_1]); nothing that only BPTT reads is written (saved gates, per-step canonical rows).
+template <int NB, bool T4 = false, bool INF = false>
 __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
   constexpr int BP = 16 * NB;
   constexpr int NT = NB >= 2 ? NB / 2 : 1;     // 32-row batch tiles of the 4-row form (T4: NB is even)
@@ -593,10 +596,13 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
           const long o = xf4(gb, 4 * c, NT);
           stp4(a.G1 + (long)t * 128 * XB + o, hv);                                                // [h0_t | .] of layer 1
           if (next) stp4(a.G0 + (long)(t + 1) * a.KB0 * XB + (long)TKH0 * XB + o, hv);            // h0 slot of layer 0, step t+1
-          *(f4*)(a.H0 + (long)t * sH + (long)gb * H + 4 * c) = hv;
+          if constexpr (INF) { if (!next) *(f4*)(a.Hout0 + (long)gb * H + 4 * c) = hv; }
+          else *(f4*)(a.H0 + (long)t * sH + (long)gb * H + 4 * c) = hv;
         }
-        f4* gts = (f4*)a.GT0 + (long)t * sH + (long)gb * H + 4 * c + u0;
-        gts[0] = gt[0]; gts[1] = gt[1];
+        if constexpr (!INF) {
+          f4* gts = (f4*)a.GT0 + (long)t * sH + (long)gb * H + 4 * c + u0;
+          gts[0] = gt[0]; gts[1] = gt[1];
+        }
       }
     } else {
     if (gact) {
@@ -619,7 +625,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       const float h = (1.f - z) * nn + z * hp0;
       hp0 = h;
       const long i = (long)t * sH + (long)eb * H + EU;
-      ((f4*)a.GT0)[i] = f4{r, z, nn, nh};
+      if constexpr (!INF) ((f4*)a.GT0)[i] = f4{r, z, nn, nh};
       ((float*)&ex[eb])[eu] = h;
     }
     __syncthreads();
@@ -628,7 +634,8 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       const long o = xfi(tb, 4 * c, NB);
       stp4(a.G1 + (long)t * 128 * XB + o, v);                                                // [h0_t | .] of layer 1
       if (next) stp4(a.G0 + (long)(t + 1) * a.KB0 * XB + (long)TKH0 * XB + o, v);            // h0 slot of layer 0, step t+1
-      *(f4*)(a.H0 + (long)t * sH + (long)tb * H + 4 * c) = v;
+      if constexpr (INF) { if (!next) *(f4*)(a.Hout0 + (long)tb * H + 4 * c) = v; }
+      else *(f4*)(a.H0 + (long)t * sH + (long)tb * H + 4 * c) = v;
     }
     }
     TPT(4);
@@ -689,10 +696,13 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
             stp4(a.G1 + (long)(t + 1) * 128 * XB + 64 * XB + o, hv);                              // [. | h1_t] of t+1
             stp4(a.G0 + (long)(t + 1) * a.KB0 * XB + (long)TKH1 * XB + o, hv);                    // h1 slot of layer 0, step t+1 (fold)
           }
-          *(f4*)(a.H1 + (long)t * sH + (long)gb * H + 4 * c) = hv;
+          if constexpr (INF) { if (!next) *(f4*)(a.Hout1 + (long)gb * H + 4 * c) = hv; }
+          else *(f4*)(a.H1 + (long)t * sH + (long)gb * H + 4 * c) = hv;
         }
-        f4* gts = (f4*)a.GT1 + (long)t * sH + (long)gb * H + 4 * c + u0;
-        gts[0] = gt[0]; gts[1] = gt[1];
+        if constexpr (!INF) {
+          f4* gts = (f4*)a.GT1 + (long)t * sH + (long)gb * H + 4 * c + u0;
+          gts[0] = gt[0]; gts[1] = gt[1];
+        }
       }
     } else {
     if (gact) {
@@ -704,7 +714,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       const float h = (1.f - z) * nn + z * hp1;
       hp1 = h;
       const long i = (long)t * sH + (long)eb * H + EU;
-      ((f4*)a.GT1)[i] = f4{r, z, nn, nh};
+      if constexpr (!INF) ((f4*)a.GT1)[i] = f4{r, z, nn, nh};
       ((float*)&ex[eb])[eu] = h;
     }
     __syncthreads();
@@ -716,7 +726,8 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
         stp4(a.G1 + (long)(t + 1) * 128 * XB + 64 * XB + o, v);                              // [. | h1_t] of t+1
         stp4(a.G0 + (long)(t + 1) * a.KB0 * XB + (long)TKH1 * XB + o, v);                    // h1 slot of layer 0, step t+1 (fold)
       }
-      *(f4*)(a.H1 + (long)t * sH + (long)tb * H + 4 * c) = v;
+      if constexpr (INF) { if (!next) *(f4*)(a.Hout1 + (long)tb * H + 4 * c) = v; }
+      else *(f4*)(a.H1 + (long)t * sH + (long)tb * H + 4 * c) = v;
     }
     }
     TPT(9);
@@ -785,7 +796,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
           oq[0] = nq.w; oq[1] = nq.x; oq[2] = nq.y; oq[3] = nq.z;
           if (next)
             for (int k = 0; k < 3; ++k) {
-              gnext[(long)b * GL + H + PO + k] = genc[k];
+              if constexpr (!INF) gnext[(long)b * GL + H + PO + k] = genc[k];
               stp(xnext + 64 * XB + xfi(b, k, NB), genc[k]);                 // the gaze block of layer 0's operand
             }
         }
@@ -797,9 +808,11 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
           const int col = c + TNCU * (vc - 4);
           const float pv = (FV(vc, b) + k_[0]) * k_[1] + k_[2];
           a.pose[((long)b * T + t) * PO + col] = pv;
-          if (next) {
-            const float e = (pv - k_[3]) / k_[4];
-            gnext[(long)b * GL + H + col] = e;        // (canonical only: the products take the pose columns through the fold)
+          if constexpr (!INF) {
+            if (next) {
+              const float e = (pv - k_[3]) / k_[4];
+              gnext[(long)b * GL + H + col] = e;        // (canonical only: the products take the pose columns through the fold)
+            }
           }
         }
       }
@@ -816,7 +829,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       if (next && tb < B) {
         const f4 v = ex[tb];
         stp4(xnext + (T4 ? xf4(tb, 4 * c, NT) : xfi(tb, 4 * c, NB)), v);
-        *(f4*)(gnext + (long)tb * GL + 4 * c) = v;
+        if constexpr (!INF) *(f4*)(gnext + (long)tb * GL + 4 * c) = v;
       }
     }
     TPT(14);
@@ -832,7 +845,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
   if (fail) {     // a bounded wait gave up: error word, the caller's sticky status, NaN in the last frame of every output row
     if (tid == 0) {
       atomicOr(a.err, 1u);
-      if (a.status) atomicOr(a.status, ZEGGS_GAVE_UP_TRAIN_FWD);
+      if (a.status) atomicOr(a.status, INF ? ZEGGS_GAVE_UP_BATCH_FWD : ZEGGS_GAVE_UP_TRAIN_FWD);
     }
     const float qnan = __uint_as_float(0x7fc00000u);
     for (int i = c * TTHR + tid; i < B * PO; i += TNCU * TTHR) a.pose[((long)(i / PO) * T + T - 1) * PO + i % PO] = qnan;
@@ -930,7 +943,7 @@ __global__ void tp_xfrag_k(TXfrag x, int K, int B, int NB, int t4) {
 }
 // speech / style columns of every step: x part of G0[t] (t >= 1) and the cond part of G3[t] (cond_{t+1}); block `bid` of `nblocks`
 __device__ __forceinline__ void tp_cond_body(long bid, long nblocks, const ZeggsDecDims& d, const float* speech, const float* style,
-                                             float* G0, float* G3, int KB0, int KB3, int NB, int t4) {
+                                             float* G0, float* G3, int KB0, int KB3, int NB, int t4, int clean = 0) {
   const int XC = d.SP + d.ST;
   const long XB = 256L * NB, n = (long)(d.T - 1) * d.B * XC;
   for (long i = bid * blockDim.x + threadIdx.x; i < n; i += nblocks * blockDim.x) {
@@ -939,12 +952,15 @@ __device__ __forceinline__ void tp_cond_body(long bid, long nblocks, const Zeggs
     const int b = (int)(r % d.B), t = 1 + (int)(r / d.B);
     const float v = cc < d.SP ? speech[((long)b * d.T + t) * d.SP + cc] : style[((long)b * d.T + t) * d.ST + (cc - d.SP)];
     G0[(long)t * KB0 * XB + (long)TFR0 * XB + (t4 ? xf4(b, cc, NB / 2) : xfi(b, cc, NB))] = v;      // (G3 keeps the 16-row form)
-    if (t >= 2) G3[(long)(t - 1) * KB3 * XB + 64 * XB + xfi(b, cc, NB)] = v;
+    // clean (batch decode): the output stage of step t - 1 multiplies cond_t into the tile that also holds pose_{t-1} -- by ZERO
+    // weights, but 0 * NaN is NaN: what a row holds PAST its last valid frame must not reach that frame.  (x_t itself keeps the
+    // value: a live frame with a non-finite input still comes out non-finite.)
+    if (t >= 2) G3[(long)(t - 1) * KB3 * XB + 64 * XB + xfi(b, cc, NB)] = (clean && !(fabsf(v) <= 3.402823466e38f)) ? 0.f : v;
   }
 }
 __global__ void tp_cond_k(ZeggsDecDims d, const float* speech, const float* style, float* G0, float* G3, int KB0, int KB3,
-                          int NB, int t4) {
-  tp_cond_body(blockIdx.x, gridDim.x, d, speech, style, G0, G3, KB0, KB3, NB, t4);
+                          int NB, int t4, int clean) {
+  tp_cond_body(blockIdx.x, gridDim.x, d, speech, style, G0, G3, KB0, KB3, NB, t4, clean);
 }
 // Round 6: everything elementwise in front of the training rollout in ONE launch -- frame 0 + CellStateEncoder input + the pose part
 // of x_1 (dec_init: blocks [0, B)), the speech / style columns of every canonical input row (dec_fill_cond: the next nfill blocks)
@@ -1000,8 +1016,9 @@ int dec_tp_state() { return g_tp_ok; }
 void dec_tp_set_state(int v) { g_tp_ok = v; }
 
 // once per optimizer step: the per-workgroup fragment packs (needs Mc / cvec: dec_fast_merge_prep)
-int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s) {
+int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4) {
   const int H = d.H, KIN = H + w.XD;
+  if (t4 < 0) t4 = tp_pack_t4(w) ? 1 : 0;      // (the training rollout's choice; the batch decode passes its own)
   // the fold of GRU layer 0's pose columns: N0 = W_ih0[:, pose] diag(sigma_o/sigma_i) W2 [3H, H], cv0 = W_ih0[:, pose] v [3H]
   // (v = (b2 sigma_o + mu_o - mu_i) / sigma_i: dec_fast_merge_prep)
   {
@@ -1012,7 +1029,7 @@ int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSt
     ZTRY(gemm_nn(w.tp_n0s, w.POL, P->l2_w, H, w.tp_n0, H, 3 * H, d.PO, H, 0.f, s));
     ZTRY(gemm_nt(w.vvec, w.POL, P->w_ih0 + H, KIN, w.tp_cv0, 3 * H, nullptr, 1, 3 * H, d.PO, ACT_NONE, 0.f, s));
   }
-  TPackArgs p{tp_pack_t4(w) ? 1 : 0, (f4*)w.tp_w0, (f4*)w.tp_w1, (f4*)w.tp_w3, P->w_ih0, P->w_hh0, P->w_ih1, P->w_hh1, P->l2_w, P->l0_w, w.Mc, w.tp_n0,
+  TPackArgs p{t4, (f4*)w.tp_w0, (f4*)w.tp_w1, (f4*)w.tp_w3, P->w_ih0, P->w_hh0, P->w_ih1, P->w_hh1, P->l2_w, P->l0_w, w.Mc, w.tp_n0,
               w.XD, w.KBX, w.KBC, TKB0, 64 + w.KBC, d.PO, d.PI, d.SP + d.ST};
   hipLaunchKernelGGL(tp_pack_k, dim3(8192), dim3(256), 0, s, p);
   ZLAUNCH_CHECK("tp_pack");
@@ -1055,6 +1072,21 @@ GemmNtItem dec_tp_p1x_item(const ZeggsDecDims& d, const ZeggsDecParams* P, const
   const float* gin1 = w.Gin + (long)d.B * w.GL;
   return GemmNtItem{gin1 + d.H, (long)w.GL, P->w_ih0 + d.H, (long)(d.H + w.XD), w.tp_p1x, 3L * d.H, nullptr, 3 * d.H, d.PO, ACT_NONE};
 }
+template <bool INF>
+static void tp_launch(const TArgs& a, int NB, int t4, hipStream_t s) {
+  switch (NB) {
+    case 1: hipLaunchKernelGGL((train_fwd_persistent_k<1, false, INF>), dim3(TNCU), dim3(TTHR), 0, s, a); break;
+    case 2:
+      if (t4) hipLaunchKernelGGL((train_fwd_persistent_k<2, true, INF>), dim3(TNCU), dim3(TTHR), 0, s, a);
+      else hipLaunchKernelGGL((train_fwd_persistent_k<2, false, INF>), dim3(TNCU), dim3(TTHR), 0, s, a);
+      break;
+    case 3: hipLaunchKernelGGL((train_fwd_persistent_k<3, false, INF>), dim3(TNCU), dim3(TTHR), 0, s, a); break;
+    default:
+      if (t4) hipLaunchKernelGGL((train_fwd_persistent_k<4, true, INF>), dim3(TNCU), dim3(TTHR), 0, s, a);
+      else hipLaunchKernelGGL((train_fwd_persistent_k<4, false, INF>), dim3(TNCU), dim3(TTHR), 0, s, a);
+      break;
+  }
+}
 int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
                const float* speech, const float* style, float* pose, float* rpos, float* rrot, hipStream_t s, bool zeroed,
                unsigned* status, bool prologue_done) {
@@ -1068,7 +1100,7 @@ int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
   // (only the blocks with pad columns: the gaze + speech / style blocks of G0, the cond blocks of G3, the h1 slot of step 1)
   if (!zeroed && !prologue_done) ZTRY(dec_tp_zero(d, w, s));
   const int t4 = tp_use_t4(w) ? 1 : 0;
-  if (!prologue_done) hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4);
+  if (!prologue_done) hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4, 0);
   const float* gin1 = w.Gin + sG;
   {   // hid_1, h0_0 -> operand of GRU layer 0, step 1 (its h1 slot stays zero: the pose columns of x_1 are the given first pose; its
       // gaze block is not an operand any more: the gate threads read the gaze direction of x_1 from the canonical row); h1_0 -> layer 1
@@ -1097,19 +1129,54 @@ int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
     ZLAUNCH_CHECK("train_fwd_dual");
     return 0;
   }
-  switch (NB) {
-    case 1: hipLaunchKernelGGL((train_fwd_persistent_k<1>), dim3(TNCU), dim3(TTHR), 0, s, a); break;
-    case 2:
-      if (t4) hipLaunchKernelGGL((train_fwd_persistent_k<2, true>), dim3(TNCU), dim3(TTHR), 0, s, a);
-      else hipLaunchKernelGGL((train_fwd_persistent_k<2>), dim3(TNCU), dim3(TTHR), 0, s, a);
-      break;
-    case 3: hipLaunchKernelGGL((train_fwd_persistent_k<3>), dim3(TNCU), dim3(TTHR), 0, s, a); break;
-    default:
-      if (t4) hipLaunchKernelGGL((train_fwd_persistent_k<4, true>), dim3(TNCU), dim3(TTHR), 0, s, a);
-      else hipLaunchKernelGGL((train_fwd_persistent_k<4>), dim3(TNCU), dim3(TTHR), 0, s, a);
-      break;
-  }
+  tp_launch<false>(a, NB, t4, s);
   ZLAUNCH_CHECK("train_fwd_persistent");
+  return 0;
+}
+
+// ---------------------------------------------------------------- batch decode (zeggs_decoder_fwd_batch): the inference form
+// tile form of the batch decode's packs and operands: the 4-row GRU tiles wherever the batch tiles come in pairs (the dual-chain
+// kernel has no inference form)
+int dec_tb_t4(const DecWs& w) { return g_tp_tiles4 && w.NB % 2 == 0; }
+int dec_tb_supported(const ZeggsDecDims& d, const DecWs& w) { return d.B >= 2 && dec_tp_supported(d, w); }
+// One chunk of d.T frames on the sweep.  The caller has prepared, as for the training rollout: Gin slot 1 (= [hid_1 | x_1] of the
+// 2-slot ring), frame 0 of pose / rpos / rrot, the packs (dec_tp_pack with dec_tb_t4).  h_in / h_out: [2,B,H].  The operand buffers
+// are write-once inside this launch only: pad blocks and arrival slots are zeroed again for every chunk.
+int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
+               const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* h_in, float* h_out,
+               hipStream_t s, unsigned* status) {
+  const int B = d.B, H = d.H, NB = w.NB, KB0 = TKB0, KB3 = 64 + w.KBC;
+  const long XB = 256L * NB, sG = (long)B * w.GL, sH = (long)B * H;
+  int dev = 0, ncu = 0;
+  ZCHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
+  ZCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess, "device query failed");
+  ZCHECK(ncu >= TNCU, "persistent batch decode needs %d CUs (device has %d)", TNCU, ncu);
+  const int t4 = dec_tb_t4(w);
+  ZTRY(dec_tp_zero(d, w, s));
+  hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4, 1);
+  const float* gin1 = w.Gin + sG;
+  {
+    TXfrag x;
+    x.xf[0] = w.G0xf + (long)KB0 * XB; x.src[0] = gin1;       x.ld[0] = w.GL; x.kofs[0] = 0;
+    x.xf[1] = w.G0xf + (long)KB0 * XB; x.src[1] = h_in;       x.ld[1] = H;    x.kofs[1] = 16 * TKH0;
+    x.xf[2] = w.G1xf + 128 * XB;       x.src[2] = h_in + sH;  x.ld[2] = H;    x.kofs[2] = 16 * 64;
+    const long g = (3L * B * H + 255) / 256;
+    hipLaunchKernelGGL(tp_xfrag_k, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, x, H, B, NB, t4);
+  }
+  ZTRY(gemm_nt(gin1 + H, w.GL, P->w_ih0 + H, H + w.XD, w.tp_p1x, 3 * H, nullptr, B, 3 * H, d.PO, ACT_NONE, 0.f, s));
+  ZLAUNCH_CHECK("tb_prologue");
+  TArgs a;
+  memset(&a, 0, sizeof(a));
+  a.d = d; a.st = *st; a.XD = w.XD; a.GL = w.GL; a.KBX = w.KBX; a.KBC = w.KBC; a.KB0 = KB0; a.KB3 = KB3; a.POL = w.POL;
+  a.PW0 = (const f4*)w.tp_w0; a.PW1 = (const f4*)w.tp_w1; a.PW3 = (const f4*)w.tp_w3;
+  a.G0 = w.G0xf; a.G1 = w.G1xf; a.G3 = w.G3xf;
+  a.Gin = w.Gin; a.H0 = (float*)h_in; a.H1 = (float*)h_in + sH; a.Hout0 = h_out; a.Hout1 = h_out + sH;
+  a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1; a.cvec = w.cvec; a.l0_w = P->l0_w;
+  a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x; a.gaze = gaze; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
+  a.cnt = w.tp_cnt; a.err = w.tp_cnt + TRING * TSH * TSTR;
+  a.status = status; a.spin = (unsigned)g_persistent_spin; a.nap = (unsigned)g_poll_sleep; a.stag = (unsigned)g_poll_stagger;
+  tp_launch<true>(a, NB, t4, s);
+  ZLAUNCH_CHECK("batch_fwd_persistent");
   return 0;
 }
 extern "C" int zeggs_tp_stamps(const ZeggsDecDims* dp, void* ws, size_t ws_bytes, unsigned long long* out /* [4][2][32] */) {

@@ -3,6 +3,7 @@
     python -m zeggs.cli train    -o options.json [-n NAME]                     (ZEGGS/main.py:10-74)
     python -m zeggs.cli generate -o options.json -s style.bvh -a speech.wav ... (ZEGGS/generate.py:414-525)
     python -m zeggs.cli generate -o options.json -c pairs.csv                   (batch mode, same CSV columns)
+    python -m zeggs.cli generate -o options.json -c pairs.csv -b 32             (the job list decoded 32 clips at a time)
 
 `options.json` is the reference's file (configs/configs_v*.json before training, <output_dir>/options.json after): keys
 `train_opt`, `net_opt`, `paths` {base_path, path_processed_data, output_dir, models_dir}.  Differences from the reference's
@@ -73,6 +74,13 @@ def cmd_generate(a):
         jobs.append(dict(audio=Path(a.audio), style=(Path(a.style), a.frames) if kind == "example" else a.style,
                          file_name=a.file_name, first_pose=Path(a.first_pose) if a.first_pose else None,
                          temperature=a.temperature, seed=a.seed))
+    if a.batch:     # the whole list in one call: networks loaded once, the clips decoded a.batch rows at a time (zeggs.generate)
+        from .generate import Job, generate_gestures
+        print(f"{len(jobs)} jobs, {a.batch} clips per decode", flush=True)
+        generate_gestures([Job(j["audio"], [j["style"]], file_name=j["file_name"], first_pose=j["first_pose"],
+                               temperature=j["temperature"], seed=j["seed"]) for j in jobs],
+                          network_path=network, data_path=data, results_path=results, style_encoding_type=kind, batch=a.batch)
+        return 0
     for k, j in enumerate(jobs):
         print(f"[{k + 1}/{len(jobs)}] {j['audio']}  style {j['style']}", flush=True)
         generate_gesture(audio_file=j["audio"], styles=[j["style"]], network_path=network, data_path=data, results_path=results,
@@ -101,6 +109,8 @@ def main(argv=None):
     g.add_argument("-g", "--use_gpu", action="store_true", help="accepted for compatibility: the engine always runs on the GPU")
     g.add_argument("-f", "--frames", type=int, nargs=2, help="start and end frame of the exemplar")
     g.add_argument("-c", "--csv", help="CSV with one audio / style pair per row (evaluation_example_based.csv layout)")
+    g.add_argument("-b", "--batch", type=int, default=0, metavar="N",
+                   help="decode the jobs N clips at a time on the weight-stationary batch sweep (default: one clip per decode)")
     g.set_defaults(fn=cmd_generate)
     a = ap.parse_args(argv)
     return a.fn(a)

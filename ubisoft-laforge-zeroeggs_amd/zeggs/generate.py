@@ -244,6 +244,215 @@ def _pinned_release(ring):
         del free[1:]
 
 
+class _Loaded:
+    """what a call needs from disk besides the job itself: data definition, statistics and the networks, loaded ONCE"""
+
+    def __init__(self, network_path, data_path, style_encoding_type, device):
+        network_path, data_path = Path(network_path), Path(data_path)
+        self.device = device
+        with open(data_path / "data_pipeline_conf.json") as f:
+            self.pipe_conf = json.load(f)
+        with open(data_path / "data_definition.json") as f:
+            details = json.load(f)
+        self.nlabels, self.label_names, self.bone_names = len(details["label_names"]), details["label_names"], details["bone_names"]
+        self.parents, self.dt = np.asarray(details["parents"]), details["dt"]
+        stat = np.load(data_path / "stats.npz")
+        tt = lambda k: torch.as_tensor(np.asarray(stat[k]), dtype=torch.float32, device=device)  # noqa: E731
+        self.audio_mean, self.audio_std = tt("audio_input_mean"), tt("audio_input_std")
+        self.stats = (tt("anim_input_mean"), tt("anim_input_std"), tt("anim_output_mean"), tt("anim_output_std"))
+        if (network_path / "decoder.pt").exists():      # the reference's whole-module pickles
+            self.speech_net = compat.load_module(network_path / "speech_encoder.pt", device).to(device).eval()
+            self.decoder = compat.load_module(network_path / "decoder.pt", device).to(device).eval()
+            self.style_net = None
+            if style_encoding_type == "example":
+                self.style_net = compat.load_module(network_path / "style_encoder.pt", device).to(device).eval()
+        else:                                           # pickle-free twin written by zeggs.train (safetensors + arch.json)
+            speech_net, decoder, style_net, _ = compat.load_state(network_path, device)
+            self.speech_net, self.decoder = speech_net.eval(), decoder.eval()
+            self.style_net = style_net.eval() if style_net is not None else None
+            assert self.style_net is not None or style_encoding_type != "example", "checkpoint has no style encoder"
+        self.film = hasattr(self.decoder.recurrent_decoder, "gammas_predictor")
+
+
+def _seed_all(seed):
+    from . import ops
+    np.random.seed(seed)
+    torch.manual_seed(seed)
+    ops.manual_seed(seed)       # the VAE noise comes from the library's counter-hash stream: the same seed gives the same clip,
+                                # as `torch.manual_seed(seed)` does for the reference's randn_like (generate.py:86-87)
+
+
+def _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature,
+               cache=None):
+    """Everything of generate_gesture() in front of the decoder: WAV read, loudness + mel, speech encoder, exemplar parse, style
+    encoder, blend.  -> dict(final, speech, feat, file_name).  `cache` (generate_gestures: a dict shared by the jobs of a list)
+    keeps parsed BVH files and exemplar features across calls; without it files are parsed on a host thread beside the audio
+    front-end, every distinct file once per call."""
+    device = ld.device
+    in_mean, in_std = ld.stats[0], ld.stats[1]
+    # exemplar / first-pose BVH files are parsed on a host thread (the C parser releases the GIL) while this thread reads the WAV
+    # and enqueues the audio front-end: every distinct file once
+    from concurrent.futures import ThreadPoolExecutor
+    bvh_paths = [str(Path(s_[0])) for s_ in styles
+                 if style_encoding_type == "example" and isinstance(s_, (tuple, list)) and isinstance(s_[0], (pathlib.PurePath, str))]
+    if audio_file is not None and isinstance(first_pose, (pathlib.PurePath, str)):
+        bvh_paths.append(str(Path(first_pose)))
+    clips = cache.setdefault("clips", {}) if cache is not None else None
+    if clips is not None:
+        bvh_paths = [p_ for p_ in bvh_paths if p_ not in clips]
+    loader = ThreadPoolExecutor(max_workers=1) if (audio_file is not None and bvh_paths) else None
+    loading = {}
+    if loader is not None:
+        for pth in dict.fromkeys(bvh_paths):
+            loading[pth] = loader.submit(anim.bvh_load, pth)
+        loader.shutdown(wait=False)
+
+    def load_bvh(pth):
+        """parsed clip of a BVH path (a private copy: callers trim / modify it)"""
+        key = str(Path(pth))
+        if clips is not None and key in clips:
+            clip = clips[key]
+        else:
+            fut = loading.get(key)
+            clip = fut.result() if fut is not None else anim.bvh_load(pth)
+            if clips is not None:
+                clips[key] = clip
+        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in clip.items()}
+
+    speech, n_frames = None, None
+    if audio_file is not None:
+        with _stage("wav_read_host"):
+            _, wav = read_wav_mono16k(audio_file)
+        n_frames = audio.n_anim_frames(len(wav))
+        with _stage("loudness+mel_device"):
+            feats = audio.preprocess_audio_device(wav, 60, n_frames, ld.pipe_conf["audio_conf"],
+                                                  ld.pipe_conf["audio_feature_type"], device)
+        with _stage("speech_encoder_device"):
+            speech = ld.speech_net(((feats[None] - ld.audio_mean) / ld.audio_std).contiguous())
+
+    encodings, feat = [], None
+    anim_name = "style"
+    parsed = cache.setdefault("feats", {}) if cache is not None else {}   # exemplar files already parsed: (path, trim) -> feature arrays
+    for style in styles:
+        if style_encoding_type == "example":
+            if isinstance(style[0], (pathlib.PurePath, str)):
+                anim_name = Path(style[0]).stem
+                fkey = (str(Path(style[0]).resolve()), None if style[1] is None else tuple(style[1]))
+                if cache is not None and fkey in parsed:
+                    feat = parsed[fkey]
+                else:
+                    with _stage("exemplar_bvh_parse_host"):
+                        clip = load_bvh(style[0])
+                    if style[1] is not None:
+                        clip["rotations"] = clip["rotations"][style[1][0]:style[1][1]]
+                        clip["positions"] = clip["positions"][style[1][0]:style[1][1]]
+                    assert int(np.ceil(1 / clip["frametime"])) == 60
+                    with _stage("exemplar_features_device"):
+                        feat = anim.preprocess_animation(clip, device)
+                        parsed[fkey] = feat
+                with _stage("exemplar_features_device"):
+                    ex = (_example_features(feat) - in_mean) / in_std
+                with _stage("style_encoder_device"):
+                    z, _, _ = ld.style_net(ex[None].contiguous(), temperature)
+                encodings.append(z)
+            elif isinstance(style[0], np.ndarray):
+                anim_name = style[1]
+                encodings.append(torch.as_tensor(style[0], dtype=torch.float32, device=device)[None])
+        elif style_encoding_type == "label":
+            onehot = torch.zeros((1, ld.nlabels), device=device)
+            onehot[0, ld.label_names.index(style)] = 1.0
+            encodings.append(onehot)
+            anim_name = style
+            assert first_pose is not None
+        else:
+            raise ValueError("Unknown style encoding type")
+
+    if blend_type == "stitch" and len(encodings) > 1:
+        if audio_file is None:
+            final = encodings
+        else:
+            assert len(styles) == len(blend_ratio)
+            se = split_by_ratio(n_frames, blend_ratio)
+            final = torch.cat([z.unsqueeze(1).repeat(1, e - s, 1) for z, (s, e) in zip(encodings, se)], dim=1)
+    elif blend_type == "add" and len(encodings) > 1:
+        assert len(encodings) == len(blend_ratio)
+        final = torch.matmul(torch.stack(encodings, dim=1).transpose(2, 1),
+                             torch.tensor(blend_ratio, device=device, dtype=torch.float32))
+    else:
+        final = encodings[0]
+
+    if audio_file is not None:
+        if first_pose is not None:
+            key = (str(Path(first_pose).resolve()), None) if isinstance(first_pose, (pathlib.PurePath, str)) else None
+            if key in parsed:       # the first pose is an (untrimmed) style exemplar: parsed already
+                feat = parsed[key]
+            else:
+                with _stage("first_pose_bvh_parse_host"):
+                    clip = load_bvh(first_pose) if key is not None else dict(first_pose)
+                with _stage("first_pose_features_device"):
+                    feat = anim.preprocess_animation(clip, device)
+                if cache is not None and key is not None:
+                    parsed[key] = feat
+        if final.dim() == 2:
+            final = final.unsqueeze(1).repeat(1, speech.shape[1], 1)
+        if file_name is None:
+            file_name = f"audio_{Path(audio_file).stem}_label_{anim_name}"
+    return dict(final=final, speech=speech, feat=feat, file_name=file_name)
+
+
+def _first_frame(feat):
+    """-> pose0 [1,PO], rpos0 [1,3], rrot0 [1,4], gaze [1,3] of the frame a clip starts from"""
+    g = lambda a: a[0:1].to(torch.float32).contiguous()  # noqa: E731
+    root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = feat[:9]
+    pose0 = torch.cat([g(x).reshape(1, -1) for x in (root_vel, root_vrt, lpos, ltxy, lvel, lvrt)], dim=1)
+    return pose0, g(root_pos), g(root_rot), g(feat[14])
+
+
+def _decode_one(ld, fe, audio_file, results_path, return_poses=False):
+    """decoder rollout of ONE clip (B = 1) + BVH / WAV files: the tail of generate_gesture()"""
+    in_mean, in_std, out_mean, out_std = ld.stats
+    decoder, dt, parents, bone_names = ld.decoder, ld.dt, ld.parents, ld.bone_names
+    speech, final, feat, file_name = fe["speech"], fe["final"], fe["feat"], fe["file_name"]
+    g = lambda a: a[0:1].to(torch.float32).contiguous()  # noqa: E731
+    root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = feat[:9]
+    gaze_pos = feat[14]
+    T = speech.shape[1]
+    if T > STREAM_MIN_FRAMES and not ld.film and not return_poses:
+        # long clip: chunked persistent decode with the BVH text formatted and written underneath it
+        pose0 = torch.cat([g(x).reshape(1, -1) for x in (root_vel, root_vrt, lpos, ltxy, lvel, lvrt)], dim=1)
+        # the WAV copy runs beside the decode; its errors surface where the one-launch path's do (ADVICE r4: a bare Thread
+        # sent a PermissionError to threading.excepthook instead of the `except` below)
+        from concurrent.futures import ThreadPoolExecutor as _TPE
+        with _TPE(max_workers=1) as copy_pool:
+            try:
+                copier = copy_pool.submit(copyfile, audio_file, str(results_path / (file_name + ".wav")))
+                with _stage("decode+pose_to_bvh_device_with_bvh_text_write_host_underneath"):
+                    _decode_to_bvh_streaming(decoder, pose0, g(root_pos), g(root_rot), g(gaze_pos), speech,
+                                             final.contiguous(), (in_mean, in_std, out_mean, out_std), dt,
+                                             str(results_path / (file_name + ".bvh")), parents, bone_names)
+                copier.result()
+            except (PermissionError, OSError) as e:
+                print(e)
+        return None
+    gaze = g(gaze_pos).repeat(T, 1)[None]
+    with _stage("decode_device"):
+        out = decoder(g(root_pos), g(root_rot), g(root_vel), g(root_vrt), g(lpos), g(ltxy), g(lvel), g(lvrt),
+                      gaze.contiguous(), speech, final.contiguous(), None, in_mean, in_std, out_mean, out_std, dt)
+    V_root_pos, V_root_rot, _, _, V_lpos, V_ltxy = out[0], out[1], out[2], out[3], out[4], out[5]
+    try:
+        with _stage("pose_to_bvh_device"):
+            channels = anim.bvh_channels(V_root_pos[0], V_root_rot[0], V_lpos[0], V_ltxy[0], np.array([0, 0, 0]),
+                                         np.array([1, 0, 0, 0]))
+        with _stage("bvh_text_write_host"):
+            anim.write_bvh_channels(str(results_path / (file_name + ".bvh")), *channels, parents=parents,
+                                    names=bone_names, order="zyx", dt=dt)
+        with _stage("wav_copy_host"):
+            copyfile(audio_file, str(results_path / (file_name + ".wav")))
+    except (PermissionError, OSError) as e:
+        print(e)
+    return (V_root_pos[0], V_root_rot[0], V_lpos[0], V_ltxy[0]) if return_poses else None
+
+
 def generate_gesture(audio_file, styles, network_path, data_path, results_path, style_encoding_type="example",
                      blend_type="add", blend_ratio=[0.5, 0.5], file_name=None, first_pose=None, temperature=1.0,
                      seed=1234, use_gpu=True, use_script=False):
@@ -254,163 +463,290 @@ def generate_gesture(audio_file, styles, network_path, data_path, results_path, 
     assert (audio_file is None) == (results_path is None)
     if not (use_gpu and torch.cuda.is_available()):
         raise RuntimeError("the ZeroEGGS MI355X engine has no CPU path (use_gpu=False / no GPU visible)")
-    np.random.seed(seed)
-    torch.manual_seed(seed)
-    from . import ops
-    ops.manual_seed(seed)       # the VAE noise comes from the library's counter-hash stream: the same seed gives the same clip,
-                                # as `torch.manual_seed(seed)` does for the reference's randn_like (generate.py:86-87)
-    device = torch.device("cuda")
-
-    with open(data_path / "data_pipeline_conf.json") as f:
-        pipe_conf = json.load(f)
-    with open(data_path / "data_definition.json") as f:
-        details = json.load(f)
-    nlabels, label_names, bone_names = len(details["label_names"]), details["label_names"], details["bone_names"]
-    parents, dt = np.asarray(details["parents"]), details["dt"]
-    stat = np.load(data_path / "stats.npz")
-    tt = lambda k: torch.as_tensor(np.asarray(stat[k]), dtype=torch.float32, device=device)  # noqa: E731
-    audio_mean, audio_std = tt("audio_input_mean"), tt("audio_input_std")
-    in_mean, in_std, out_mean, out_std = (tt("anim_input_mean"), tt("anim_input_std"), tt("anim_output_mean"),
-                                          tt("anim_output_std"))
-    if (network_path / "decoder.pt").exists():      # the reference's whole-module pickles
-        speech_net = compat.load_module(network_path / "speech_encoder.pt", device).to(device).eval()
-        decoder = compat.load_module(network_path / "decoder.pt", device).to(device).eval()
-        style_net = None
-        if style_encoding_type == "example":
-            style_net = compat.load_module(network_path / "style_encoder.pt", device).to(device).eval()
-    else:                                           # pickle-free twin written by zeggs.train (safetensors + arch.json)
-        speech_net, decoder, style_net, _ = compat.load_state(network_path, device)
-        speech_net, decoder = speech_net.eval(), decoder.eval()
-        style_net = style_net.eval() if style_net is not None else None
-        assert style_net is not None or style_encoding_type != "example", "checkpoint has no style encoder"
-
-    # exemplar / first-pose BVH files are parsed on a host thread (the C parser releases the GIL) while this thread reads the WAV
-    # and enqueues the audio front-end: every distinct file once
-    from concurrent.futures import ThreadPoolExecutor
-    bvh_paths = [str(Path(s_[0])) for s_ in styles
-                 if style_encoding_type == "example" and isinstance(s_, (tuple, list)) and isinstance(s_[0], (pathlib.PurePath, str))]
-    if audio_file is not None and isinstance(first_pose, (pathlib.PurePath, str)):
-        bvh_paths.append(str(Path(first_pose)))
-    loader = ThreadPoolExecutor(max_workers=1) if (audio_file is not None and bvh_paths) else None
-    loading = {}
-    if loader is not None:
-        for pth in dict.fromkeys(bvh_paths):
-            loading[pth] = loader.submit(anim.bvh_load, pth)
-        loader.shutdown(wait=False)
-
-    def load_bvh(pth):
-        """parsed clip of a BVH path (a private copy: callers trim / modify it)"""
-        fut = loading.get(str(Path(pth)))
-        clip = fut.result() if fut is not None else anim.bvh_load(pth)
-        return {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in clip.items()}
-
+    _seed_all(seed)
+    ld = _Loaded(network_path, data_path, style_encoding_type, torch.device("cuda"))
     with torch.no_grad():
+        fe = _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature)
         if audio_file is not None:
-            with _stage("wav_read_host"):
-                _, wav = read_wav_mono16k(audio_file)
-            n_frames = audio.n_anim_frames(len(wav))
-            with _stage("loudness+mel_device"):
-                feats = audio.preprocess_audio_device(wav, 60, n_frames, pipe_conf["audio_conf"],
-                                                      pipe_conf["audio_feature_type"], device)
-            with _stage("speech_encoder_device"):
-                speech = speech_net(((feats[None] - audio_mean) / audio_std).contiguous())
+            _decode_one(ld, fe, audio_file, results_path)
+    return fe["final"]
 
-        encodings, feat = [], None
-        anim_name = "style"
-        parsed = {}                     # exemplar files already parsed in this call: (path, trim) -> feature arrays
-        for style in styles:
-            if style_encoding_type == "example":
-                if isinstance(style[0], (pathlib.PurePath, str)):
-                    anim_name = Path(style[0]).stem
-                    with _stage("exemplar_bvh_parse_host"):
-                        clip = load_bvh(style[0])
-                    if style[1] is not None:
-                        clip["rotations"] = clip["rotations"][style[1][0]:style[1][1]]
-                        clip["positions"] = clip["positions"][style[1][0]:style[1][1]]
-                    assert int(np.ceil(1 / clip["frametime"])) == 60
-                    with _stage("exemplar_features_device"):
-                        feat = anim.preprocess_animation(clip, device)
-                        parsed[(str(Path(style[0]).resolve()), None if style[1] is None else tuple(style[1]))] = feat
-                        ex = (_example_features(feat) - in_mean) / in_std
-                    with _stage("style_encoder_device"):
-                        z, _, _ = style_net(ex[None].contiguous(), temperature)
-                    encodings.append(z)
-                elif isinstance(style[0], np.ndarray):
-                    anim_name = style[1]
-                    encodings.append(torch.as_tensor(style[0], dtype=torch.float32, device=device)[None])
-            elif style_encoding_type == "label":
-                onehot = torch.zeros((1, nlabels), device=device)
-                onehot[0, label_names.index(style)] = 1.0
-                encodings.append(onehot)
-                anim_name = style
-                assert first_pose is not None
-            else:
-                raise ValueError("Unknown style encoding type")
 
-        if blend_type == "stitch" and len(encodings) > 1:
-            if audio_file is None:
-                final = encodings
-            else:
-                assert len(styles) == len(blend_ratio)
-                se = split_by_ratio(n_frames, blend_ratio)
-                final = torch.cat([z.unsqueeze(1).repeat(1, e - s, 1) for z, (s, e) in zip(encodings, se)], dim=1)
-        elif blend_type == "add" and len(encodings) > 1:
-            assert len(encodings) == len(blend_ratio)
-            final = torch.matmul(torch.stack(encodings, dim=1).transpose(2, 1),
-                                 torch.tensor(blend_ratio, device=device, dtype=torch.float32))
-        else:
-            final = encodings[0]
+# ----------------------------------------------------------------------------- many clips per decode
+def plan_slots(lengths, batch, chunk):
+    """Slot plan of the batch decode: clips of `lengths` frames (frame 0 = the given first pose, frames 1 .. L-1 are generated)
+    on `batch` rows, decoded in chunks of at most `chunk` frames (frame 0 of a chunk = the last frame already produced, so a
+    chunk yields at most chunk - 1 new frames per row).  -> one list per chunk of pieces (row, clip, start, count): row `row`
+    starts from frame `start` of clip `clip` and produces frames start + 1 .. start + count (a piece with start == 0 also
+    delivers the given frame 0).  Clips enter in job order as rows free up; a row whose clip ends inside a chunk idles until the
+    next boundary; a one-frame clip is a piece with count == 0.  The launch length of a chunk is max(4, max count + 1): shorter
+    rows are padded and their surplus frames discarded (the sweep needs 4 frames)."""
+    batch, chunk = int(batch), int(chunk)
+    if batch < 1 or chunk < 4:
+        raise ValueError("plan_slots: batch >= 1 and chunk >= 4")
+    lengths = [int(n) for n in lengths]
+    if any(n < 1 for n in lengths):
+        raise ValueError("plan_slots: every clip has at least its first frame")
+    rows = [None] * batch            # per row: [clip, last frame produced]
+    nxt, chunks = 0, []
+    while True:
+        pieces = []
+        for r in range(batch):
+            if rows[r] is None and nxt < len(lengths):
+                rows[r] = [nxt, 0]
+                nxt += 1
+            if rows[r] is not None:
+                clip, k = rows[r]
+                n = min(chunk - 1, lengths[clip] - 1 - k)
+                pieces.append((r, clip, k, n))
+                rows[r] = [clip, k + n] if k + n < lengths[clip] - 1 else None
+        if not pieces:
+            return chunks
+        chunks.append(pieces)
 
-        if audio_file is not None:
-            if first_pose is not None:
-                key = (str(Path(first_pose).resolve()), None) if isinstance(first_pose, (pathlib.PurePath, str)) else None
-                if key in parsed:       # the first pose is an (untrimmed) style exemplar of this call: parsed already
-                    feat = parsed[key]
-                else:
-                    with _stage("first_pose_bvh_parse_host"):
-                        clip = load_bvh(first_pose) if key is not None else dict(first_pose)
-                    with _stage("first_pose_features_device"):
-                        feat = anim.preprocess_animation(clip, device)
-            g = lambda a: a[0:1].to(torch.float32).contiguous()  # noqa: E731
-            root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = feat[:9]
-            gaze_pos = feat[14]
-            if final.dim() == 2:
-                final = final.unsqueeze(1).repeat(1, speech.shape[1], 1)
-            if file_name is None:
-                file_name = f"audio_{Path(audio_file).stem}_label_{anim_name}"
-            T = speech.shape[1]
-            film = hasattr(decoder.recurrent_decoder, "gammas_predictor")
-            if T > STREAM_MIN_FRAMES and not film:
-                # long clip: chunked persistent decode with the BVH text formatted and written underneath it
-                pose0 = torch.cat([g(x).reshape(1, -1) for x in (root_vel, root_vrt, lpos, ltxy, lvel, lvrt)], dim=1)
-                # the WAV copy runs beside the decode; its errors surface where the one-launch path's do (ADVICE r4: a bare Thread
-                # sent a PermissionError to threading.excepthook instead of the `except` below)
-                from concurrent.futures import ThreadPoolExecutor as _TPE
-                with _TPE(max_workers=1) as copy_pool:
+
+class Job:
+    """one row of a job list: the arguments of generate_gesture() that vary per clip"""
+
+    def __init__(self, audio_file, styles, file_name=None, first_pose=None, temperature=1.0, seed=1234, blend_type="add",
+                 blend_ratio=(0.5, 0.5)):
+        self.audio_file, self.styles, self.file_name, self.first_pose = audio_file, list(styles), file_name, first_pose
+        self.temperature, self.seed, self.blend_type, self.blend_ratio = temperature, seed, blend_type, list(blend_ratio)
+
+
+BATCH_RING = 4          # chunks whose rows are being downloaded / formatted while the next ones are decoded
+
+
+def decode_plan(bd, firsts, speech, style, plan, status=None, fill=0.0, infos=None):
+    """Run a slot plan (plan_slots) on the batch decode `bd` (ops.BatchDecode).  Per clip j: firsts[j] = (pose0 [1,PO], rpos0 [1,3],
+    rrot0 [1,4], gaze target [1,3]) of its frame 0, speech[j] [L_j,SP], style[j] [L_j,ST].  A generator: per chunk it yields
+    (pieces, pose [B,N,PO], rpos [B,N,3], rrot [B,N,4]); row r of a piece (r, j, start, count) holds frames start .. start + count
+    of clip j at indices 0 .. count (index 0 = the frame the chunk started from).  Rows that begin a clip take their state from
+    the CellStateEncoder (ops.decoder_state_init); `fill` is what idle rows and the frames past a row's last valid one hold
+    (anything on the sweep: rows are independent and a row's frames past its last valid one do not reach it; a chunk that is
+    redone on the stage launches is redone with non-finite inputs replaced by 0, see ops.decoder_batch_chunk).  `infos` (a list) receives one dict per decoded chunk (ops.decoder_batch_chunk's info)."""
+    from . import ops
+    dev = speech[0].device
+    B, H = bd.B, bd.H
+    SP, ST, PO = speech[0].shape[1], style[0].shape[1], firsts[0][0].shape[1]
+    pose_l = torch.zeros(B, PO, device=dev)
+    rpos_l = torch.zeros(B, 3, device=dev)
+    rrot_l = torch.zeros(B, 4, device=dev)
+    rrot_l[:, 0] = 1.0
+    h = torch.zeros(2, B, H, device=dev)
+    # a chunk's inputs are ONE gather each from the clips' rows laid end to end (+ a last row of `fill`), not three copies per row
+    off = np.concatenate([[0], np.cumsum([int(x.shape[0]) for x in speech])]).astype(np.int64)
+    sp_all = torch.cat(list(speech) + [torch.full((1, SP), fill, device=dev)])
+    st_all = torch.cat(list(style) + [torch.full((1, ST), fill, device=dev)])
+    gz_all = torch.cat([f[3] for f in firsts] + [torch.full((1, 3), fill, device=dev)])
+    for pieces in plan:
+        nmax = max(n for _, _, _, n in pieces)
+        N = max(4, nmax + 1)
+        new = [(r, j) for r, j, k, _ in pieces if k == 0]
+        if new:              # rows that begin a clip: first pose and the CellStateEncoder's state
+            idx = torch.as_tensor([r for r, _ in new], device=dev)
+            p0 = torch.cat([firsts[j][0] for _, j in new])
+            rp0 = torch.cat([firsts[j][1] for _, j in new])
+            rr0 = torch.cat([firsts[j][2] for _, j in new])
+            pose_l[idx], rpos_l[idx], rrot_l[idx] = p0, rp0, rr0
+            if nmax > 0:
+                gz0 = torch.cat([firsts[j][3] for _, j in new])
+                st0 = torch.stack([style[j][0] for _, j in new])
+                h[:, idx] = ops.decoder_state_init(bd, p0, rp0, rr0, gz0, st0)
+        if nmax > 0:
+            fidx = np.full((B, N), off[-1], np.int64)
+            gidx = np.full((B, N), len(firsts), np.int64)
+            for r, j, k, n in pieces:
+                fidx[r, :n + 1] = off[j] + k + np.arange(n + 1)
+                gidx[r, :n + 1] = j
+            fidx, gidx = torch.as_tensor(fidx, device=dev), torch.as_tensor(gidx, device=dev)
+            gz, sp, sty = gz_all[gidx], sp_all[fidx], st_all[fidx]
+            info = {} if infos is not None else None
+            pose, rpos, rrot, h = ops.decoder_batch_chunk(bd, pose_l, rpos_l, rrot_l, gz, sp, sty, h, status=status, info=info)
+            if infos is not None:
+                infos.append(info)
+            # (a row that goes on fills its chunk: h is its state after frame start + count)
+            ridx = torch.as_tensor([r for r, _, _, _ in pieces], device=dev)
+            nidx = torch.as_tensor([n for _, _, _, n in pieces], device=dev)
+            pose_l[ridx], rpos_l[ridx], rrot_l[ridx] = pose[ridx, nidx], rpos[ridx, nidx], rrot[ridx, nidx]
+        else:                # only one-frame clips in this chunk
+            pose, rpos, rrot = pose_l[:, None].clone(), rpos_l[:, None].clone(), rrot_l[:, None].clone()
+        yield pieces, pose, rpos, rrot
+
+
+def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, block=None):
+    """The clips of `fes` on `batch` rows of the weight-stationary sweep (ops.decoder_batch_chunk), chunk by chunk through the slot
+    plan; every (row, chunk) piece is converted to BVH motion rows on the device (zeggs_pose_to_bvh_table), downloaded into pinned
+    memory on a copy stream and formatted by host threads underneath the following chunks -- the mechanism of
+    _decode_to_bvh_streaming; this thread writes each clip's text in order.  `paths[j]` None: no file for clip j."""
+    import ctypes as C
+    from concurrent.futures import ThreadPoolExecutor
+    from . import ops
+    dev = ld.device
+    J, dt = len(ld.parents), ld.dt
+    cols = 3 + 3 * J
+    L = ops.lib()
+    firsts = [_first_frame(fe["feat"]) for fe in fes]
+    speech = [fe["speech"][0] for fe in fes]
+    style = [fe["final"].contiguous()[0] for fe in fes]
+    lengths = [int(x.shape[0]) for x in speech]
+    plan = plan_slots(lengths, batch, chunk)
+    # per clip: header + channel order of its file (frame 0's joint positions are the OFFSETs: utils.write_bvh)
+    heads, seqs = [], []
+    for (pose0, rpos0, rrot0, _), n in zip(firsts, lengths):
+        sl = lambda a, b: pose0[:, a:b]  # noqa: E731
+        pos0, _r = anim.bvh_channels(rpos0, rrot0, sl(6, 6 + 3 * J).reshape(1, J, 3), sl(6 + 3 * J, 6 + 9 * J).reshape(1, J, 2, 3),
+                                     np.array([0, 0, 0]), np.array([1, 0, 0, 0]))
+        head, seq = anim.bvh_header(pos0[0].cpu().numpy(), ld.parents, ld.bone_names, "zyx", n, dt)
+        heads.append(head)
+        seqs.append(seq)
+    seq_dev = torch.as_tensor(np.asarray(seqs[0], np.int32), device=dev)      # (the skeleton is the data definition's: one order)
+    d = anim.BvhDims(0, J, 1)
+    d.start_pos[:] = [0.0, 0.0, 0.0]
+    d.start_rot[:] = [1.0, 0.0, 0.0, 0.0]
+    copy_stream = torch.cuda.Stream(device=dev)
+    main = torch.cuda.current_stream()
+    status = ops.new_status(dev)
+    workers = threads or min(16, (__import__("os").cpu_count() or 4))
+    block = block or STREAM_BLOCK
+    ring = _pinned_ring(BATCH_RING, batch * chunk, cols)
+    kept = [[] for _ in fes] if return_poses else None
+    files = {}
+    pending = []                     # per chunk in flight: [(clip, future), ...] in (row, block) order
+    used = 0                         # staging buffers handed out so far
+
+    dead = set()                     # clips whose file could not be opened or written: reported, the other clips go on
+
+    def live(j):
+        return paths[j] is not None and j not in dead
+
+    def drain(keep):
+        while len(pending) > keep:
+            for j, f, last in pending.pop(0):
+                txt = f.result()
+                if live(j):
                     try:
-                        copier = copy_pool.submit(copyfile, audio_file, str(results_path / (file_name + ".wav")))
-                        with _stage("decode+pose_to_bvh_device_with_bvh_text_write_host_underneath"):
-                            _decode_to_bvh_streaming(decoder, pose0, g(root_pos), g(root_rot), g(gaze_pos), speech,
-                                                     final.contiguous(), (in_mean, in_std, out_mean, out_std), dt,
-                                                     str(results_path / (file_name + ".bvh")), parents, bone_names)
-                        copier.result()
+                        files[j].write(txt)
+                    except OSError as e:
+                        print(e)
+                        dead.add(j)
+                if last and j in files:          # the clip's last rows: its file is complete (a long job list must not hold
+                    files.pop(j).close()         # every file open until the end)
+
+    try:
+        with ThreadPoolExecutor(max_workers=workers) as pool:
+            for pieces, pose, rpos, rrot in decode_plan(bd, firsts, speech, style, plan, status=status):
+                for r, j, k, n in pieces:
+                    if k == 0 and paths[j] is not None:
+                        try:
+                            files[j] = open(paths[j], "wb")
+                            files[j].write(heads[j].encode())
+                        except OSError as e:     # (PermissionError included) this clip has no file; generate_gesture prints too
+                            print(e)
+                            dead.add(j)
+                total = sum(n + (1 if k == 0 else 0) for _, _, k, n in pieces)
+                table = torch.empty(total, cols, dtype=torch.float64, device=dev)
+                spans, r0 = [], 0
+                for r, j, k, n in pieces:
+                    lo = 0 if k == 0 else 1          # (frame 0 of a later chunk was written with the chunk before)
+                    rows = n + 1 - lo
+                    if rows == 0:
+                        continue
+                    P = pose[r, lo:n + 1]
+                    a_rpos, a_rrot = rpos[r, lo:n + 1].contiguous(), rrot[r, lo:n + 1].contiguous()
+                    a_lpos, a_ltxy = P[:, 6:6 + 3 * J].contiguous(), P[:, 6 + 3 * J:6 + 9 * J].contiguous()
+                    if kept is not None:
+                        kept[j].append((a_rpos, a_rrot, a_lpos.reshape(rows, J, 3), a_ltxy.reshape(rows, J, 2, 3)))
+                    if live(j):
+                        d.T = rows
+                        out = table[r0:r0 + rows]
+                        ref_pos, ref_rot = firsts[j][1], firsts[j][2]
+                        rc = L.zeggs_pose_to_bvh_table(C.byref(d), C.c_void_p(a_rpos.data_ptr()), C.c_void_p(a_rrot.data_ptr()),
+                                                       C.c_void_p(a_lpos.data_ptr()), C.c_void_p(a_ltxy.data_ptr()),
+                                                       C.c_void_p(ref_pos.data_ptr()), C.c_void_p(ref_rot.data_ptr()),
+                                                       C.c_void_p(seq_dev.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                       C.c_void_p(main.cuda_stream))
+                        if rc != 0:
+                            raise RuntimeError("zeggs_pose_to_bvh_table: " + L.zeggs_last_error().decode())
+                        spans.append((j, r0, rows, k + n == lengths[j] - 1))
+                        r0 += rows
+                    del a_rpos, a_rrot, a_lpos, a_ltxy
+                if not spans:
+                    continue
+                done = torch.cuda.Event()
+                done.record(main)
+                drain(BATCH_RING - 1)            # the staging buffer used BATCH_RING chunks ago has been formatted and written
+                host = ring[used % BATCH_RING][:r0]
+                used += 1
+                with torch.cuda.stream(copy_stream):
+                    copy_stream.wait_event(done)
+                    host.copy_(table[:r0], non_blocking=True)
+                    table.record_stream(copy_stream)
+                    ev = torch.cuda.Event()
+                    ev.record(copy_stream)
+
+                def fmt(host=host, ev=ev, a=0, b=0):
+                    ev.synchronize()
+                    return anim.format_rows(host[a:b].numpy())
+                pending.append([(j, pool.submit(fmt, a=a, b=min(a + block, s0 + rows)), end and a + block >= s0 + rows)
+                                for j, s0, rows, end in spans for a in range(s0, s0 + rows, block)])
+            drain(0)
+    finally:
+        for fh in files.values():
+            fh.close()
+        _pinned_release(ring)
+    if kept is None:
+        return None
+    return [tuple(torch.cat([p[i] for p in ps]) for i in range(4)) for ps in kept]
+
+
+def generate_gestures(jobs, network_path, data_path, results_path, style_encoding_type="example", batch=32, chunk=256,
+                      use_gpu=True, return_poses=False, threads=None):
+    """A whole job list in one call: `jobs` are Job objects (or dicts of Job's arguments); N (audio, style) jobs in, N BVH / WAV
+    pairs out.  Networks and statistics are loaded once, each job's front end runs exactly as generate_gesture() does (same
+    seeding, so a job's style encoding equals what generate_gesture() returns for the same arguments; parsed exemplars are kept
+    across jobs), and the clips are decoded together, `batch` rows at a time, on the weight-stationary sweep
+    (ops.decoder_batch_chunk) in chunks of `chunk` frames: rows of clips that end are handed to the next job at the chunk
+    boundary.  One job, a FiLM decoder or dimensions the sweep does not take: every job runs the per-clip path of
+    generate_gesture(), still on the networks loaded once.  -> the list of style encodings; with return_poses also each clip's
+    (root_pos [T,3], root_rot [T,4], lpos [T,J,3], ltxy [T,J,2,3]) device tensors."""
+    from . import ops
+    jobs = [j if isinstance(j, Job) else Job(**j) for j in jobs]
+    results_path = Path(results_path)
+    results_path.mkdir(exist_ok=True)
+    if not (use_gpu and torch.cuda.is_available()):
+        raise RuntimeError("the ZeroEGGS MI355X engine has no CPU path (use_gpu=False / no GPU visible)")
+    device = torch.device("cuda")
+    if not jobs:
+        return ([], []) if return_poses else []
+    _seed_all(jobs[0].seed)
+    ld = _Loaded(network_path, data_path, style_encoding_type, device)
+    cache, fes = {}, []
+    with torch.no_grad():
+        for j in jobs:
+            _seed_all(j.seed)
+            fes.append(_front_end(ld, j.audio_file, j.styles, style_encoding_type, j.blend_type, j.blend_ratio, j.file_name,
+                                  j.first_pose, j.temperature, cache=cache))
+        bd = None
+        rows = min(int(batch), len(jobs))
+        if rows >= 2 and not ld.film and int(chunk) >= 4:
+            sp, st = fes[0]["speech"], fes[0]["final"]
+            bd = ops.BatchDecode(ld.decoder, rows, min(int(chunk), max(4, max(fe["speech"].shape[1] for fe in fes))),
+                                 sp.shape[2], st.shape[2], *ld.stats, ld.dt)
+            if not bd.sweep:
+                bd = None
+        if bd is None:
+            poses = [_decode_one(ld, fe, j.audio_file, results_path, return_poses) for j, fe in zip(jobs, fes)]
+        else:
+            # a file that cannot be opened, written or copied costs that job's file only (as in the loop over generate_gesture)
+            with _stage("batch_decode+pose_to_bvh_device_with_bvh_text_write_host_underneath"):
+                poses = _decode_batch(ld, fes, [str(results_path / (fe["file_name"] + ".bvh")) for fe in fes], bd, bd.B,
+                                      bd.chunk, return_poses, threads=threads)
+            with _stage("wav_copy_host"):
+                for j, fe in zip(jobs, fes):
+                    try:
+                        copyfile(j.audio_file, str(results_path / (fe["file_name"] + ".wav")))
                     except (PermissionError, OSError) as e:
                         print(e)
-                return final
-            gaze = g(gaze_pos).repeat(T, 1)[None]
-            with _stage("decode_device"):
-                out = decoder(g(root_pos), g(root_rot), g(root_vel), g(root_vrt), g(lpos), g(ltxy), g(lvel), g(lvrt),
-                              gaze.contiguous(), speech, final.contiguous(), None, in_mean, in_std, out_mean, out_std, dt)
-            V_root_pos, V_root_rot, _, _, V_lpos, V_ltxy = out[0], out[1], out[2], out[3], out[4], out[5]
-            try:
-                with _stage("pose_to_bvh_device"):
-                    channels = anim.bvh_channels(V_root_pos[0], V_root_rot[0], V_lpos[0], V_ltxy[0], np.array([0, 0, 0]),
-                                                 np.array([1, 0, 0, 0]))
-                with _stage("bvh_text_write_host"):
-                    anim.write_bvh_channels(str(results_path / (file_name + ".bvh")), *channels, parents=parents,
-                                            names=bone_names, order="zyx", dt=dt)
-                with _stage("wav_copy_host"):
-                    copyfile(audio_file, str(results_path / (file_name + ".wav")))
-            except (PermissionError, OSError) as e:
-                print(e)
-    return final
+    encodings = [fe["final"] for fe in fes]
+    return (encodings, poses) if return_poses else encodings

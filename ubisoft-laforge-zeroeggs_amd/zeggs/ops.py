@@ -64,7 +64,11 @@ class DecCall(C.Structure):       # mirrors ZeggsDecCall: the per-call controls 
 
 COUNTERS = {}                                      # which optional paths ran (tests): "style_in_place"
 STATUS_WORDS = 4                                   # ZEGGS_STATUS_WORDS
-GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep"}     # ZEGGS_GAVE_UP_* bits of status[0]
+GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "batch decode sweep"}     # ZEGGS_GAVE_UP_* bits of status[0]
+# what the binding needs beyond the header's older entry points: checked when the library is loaded, so that a stale
+# libzeggs_hip.so fails with a message instead of an AttributeError in the middle of a job list
+REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
+                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path")
 
 
 def lib():
@@ -78,8 +82,12 @@ def lib():
             "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
     L = C.CDLL(str(_LIB_PATH))
     L.zeggs_last_error.restype = C.c_char_p
+    missing = [n for n in REQUIRED_SYMBOLS if not hasattr(L, n)]
+    if missing:
+        raise HipLibraryMissing(f"{_LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
     for n in ("zeggs_speech_encoder_workspace_bytes", "zeggs_style_encoder_workspace_bytes",
-              "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_style_encoder_input_offset"):
+              "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_style_encoder_input_offset",
+              "zeggs_decoder_batch_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
     _LIB = L
     # tuning switches for experiments, e.g. ZEGGS_OPTIONS="bwd_chunks=4,stage_variant=0" (see zeggs_set_option)
@@ -651,10 +659,10 @@ def decoder_prepare(dec, B, T, SP, ST, in_mean, in_std, out_mean, out_std, dt, s
     return int(mask)
 
 
-def _warn_gave_up(bits, what):
+def _warn_gave_up(bits, what, disabled=True):
     import warnings
     warnings.warn("zeggs: a persistent kernel gave up (" + ", ".join(n for b, n in GAVE_UP.items() if bits & b) +
-                  "; another tenant on the GPU?); it is disabled for this process and " + what +
+                  "; another tenant on the GPU?); " + ("it is disabled for this process and " if disabled else "") + what +
                   " is redone on the stage kernels")
 
 
@@ -860,6 +868,99 @@ def decoder_chunk(dec, pose0, rpos0, rrot0, gaze, speech, style, in_mean, in_std
                                         _p(speech), _p(style), _p(pose), _p(rpos), _p(rrot),
                                         _p(_f32c(h_in)) if h_in is not None else None, _p(h_out), _p(ws),
                                         C.c_size_t(ws.numel()), _stream(), C.byref(call)), "decoder_fwd_state_ex")
+    return pose, rpos, rrot, h_out
+
+
+# ----------------------------------------------------------------------------- batch decode (many clips per rollout)
+BATCH_PATHS = {0: None, 1: "persistent", 2: "stage"}
+
+
+def batch_last_path():
+    """Which path this thread's last decoder_batch_chunk took: "persistent" (the weight-stationary sweep), "stage" (the stage
+    launches: unsupported dimensions, a sweep that is switched off or gave up) or None."""
+    return BATCH_PATHS[int(lib().zeggs_decoder_batch_last_path())]
+
+
+class BatchDecode:
+    """Workspace and weight packs of one job list on the batch decode (zeggs_decoder_batch_prepare: the weight-only work runs
+    here, once, not per chunk).  `B` rows, chunks of at most `chunk` frames (frame 0 of a chunk included).  `sweep` tells
+    whether these dimensions run on the weight-stationary sweep at all (else every chunk takes the stage launches)."""
+
+    def __init__(self, dec, B, chunk, SP, ST, in_mean, in_std, out_mean, out_std, dt):
+        self.stats = [_f32c(t) for t in (in_mean, in_std, out_mean, out_std)]
+        self.params = [_f32c(t) for t in decoder_param_list(dec)]
+        self.B, self.chunk, self.SP, self.ST = int(B), int(chunk), int(SP), int(ST)
+        self.PO, self.H, self.dt = int(self.stats[2].numel()), dec.recurrent_decoder.layer1.hidden_size, float(dt)
+        self.film = 1 if len(self.params) == len(DEC_FIELDS) else 0
+        L = lib()
+        _route(current())
+        d = self.dims(self.chunk)
+        self.ws = _ws(L.zeggs_decoder_batch_workspace_bytes(C.byref(d)), self.params[0].device)
+        self.P = _ptrs(DecPtrs, DEC_FIELDS, self.params)
+        self.S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), self.stats)
+        self.mask = int(L.zeggs_decoder_batch_prepare(C.byref(d), C.byref(self.P), C.byref(self.S), _p(self.ws),
+                                                      C.c_size_t(self.ws.numel()), _stream()))
+        _check(min(self.mask, 0), "decoder_batch_prepare")
+        self.sweep = self.mask != 0
+
+    def dims(self, T, B=None):
+        return DecDims(self.B if B is None else int(B), int(T), self.PO + 3, self.PO, self.SP, self.ST, self.H, self.dt, self.film)
+
+
+def decoder_state_init(bd, pose0, rpos0, rrot0, gaze0, style0):
+    """The CellStateEncoder alone (zeggs_decoder_state_init): first pose [n,PO], root state [n,3] / [n,4], gaze target [n,3] and
+    style [n,ST] of frame 0 of n clips -> the GRU state [2,n,H] they start from (rows of a later decoder_batch_chunk's h_in)."""
+    pose0, rpos0, rrot0, gaze0, style0 = (_f32c(t) for t in (pose0, rpos0, rrot0, gaze0, style0))
+    n = pose0.shape[0]
+    assert 1 <= n <= bd.B
+    h = torch.empty(2, n, bd.H, device=pose0.device, dtype=torch.float32)
+    d = bd.dims(1, n)
+    _check(lib().zeggs_decoder_state_init(C.byref(d), C.byref(bd.P), C.byref(bd.S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze0),
+                                          _p(style0), _p(h), _p(bd.ws), C.c_size_t(bd.ws.numel()), _stream()),
+           "decoder_state_init")
+    return h
+
+
+def decoder_batch_chunk(bd, pose0, rpos0, rrot0, gaze, speech, style, h_in, status=None, info=None, stage=False):
+    """One chunk of the batch decode (zeggs_decoder_fwd_batch), arguments as decoder_chunk with B = bd.B rows and N <= bd.chunk
+    frames: frame 0 of the chunk is the last frame already produced of every row, h_in [2,B,H] the GRU state after it (rows that
+    begin a clip: decoder_state_init).  -> pose [B,N,PO], rpos, rrot, h_out [2,B,H].  Rows are independent; what an idle row
+    holds does not matter.  With `status` (ops.new_status) the word is read back after the chunk once the sweep has been
+    validated on this process -- one 4-byte read per chunk: the next chunk starts from h_out --, and a chunk whose sweep gave up is
+    redone on the stage launches right here (with non-finite gaze / speech / style values replaced by 0: only the sweep isolates a
+    row's last valid frame from what follows it).  `info` (a dict) receives "path" and "gave_up"."""
+    pose0, rpos0, rrot0, gaze, speech, style, h_in = (_f32c(t) for t in (pose0, rpos0, rrot0, gaze, speech, style, h_in))
+    B, N, SP = speech.shape
+    if B != bd.B or N > bd.chunk or N < 2 or SP != bd.SP or style.shape[2] != bd.ST:
+        raise ValueError(f"decoder_batch_chunk: [{B},{N}] rows x frames on a BatchDecode of [{bd.B},<={bd.chunk}]")
+    _route(current())
+    L = lib()
+    dev = pose0.device
+    d = bd.dims(N)
+    pose = torch.empty(B, N, bd.PO, device=dev, dtype=torch.float32)
+    rpos = torch.empty(B, N, 3, device=dev, dtype=torch.float32)
+    rrot = torch.empty(B, N, 4, device=dev, dtype=torch.float32)
+    h_out = torch.empty(2, B, bd.H, device=dev, dtype=torch.float32)
+    watch = status is not None and not stage and not torch.cuda.is_current_stream_capturing() and _persistent_live(1)
+    call = DecCall(bd.mask, 0, None, status.data_ptr() if status is not None else None, 0)
+
+    def run(mode, gaze=gaze, speech=speech, style=style):
+        _check(L.zeggs_decoder_fwd_batch(C.byref(d), C.byref(bd.P), C.byref(bd.S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze),
+                                         _p(speech), _p(style), _p(pose), _p(rpos), _p(rrot), _p(h_in), _p(h_out), _p(bd.ws),
+                                         C.c_size_t(bd.ws.numel()), _stream(), C.byref(call), int(mode)), "decoder_fwd_batch")
+    run(1 if stage else 0)
+    bits = 0
+    if watch and batch_last_path() == "persistent":
+        bits = int(status[0].item())
+        if bits:
+            _warn_gave_up(bits, "this chunk", disabled=False)
+            COUNTERS["batch_chunks_redone"] = COUNTERS.get("batch_chunks_redone", 0) + 1
+            fill_(status.view(torch.float32))
+            # the stage launches do not keep what a row holds past its last valid frame away from that frame (0 * NaN in the
+            # merged stage): the redo sees non-finite padding as 0, which is what the sweep made of it
+            run(1, *(torch.nan_to_num(t, nan=0.0, posinf=0.0, neginf=0.0) for t in (gaze, speech, style)))
+    if info is not None:
+        info["path"], info["gave_up"] = batch_last_path(), bits
     return pose, rpos, rrot, h_out
 
 
