@@ -613,6 +613,35 @@ int zeggs_parse_table_text(const char* text, size_t len, double* table /* host *
  * blocks, the caller writes the blocks in order); *written = bytes produced.  cap >= rows * (cols * 24 + 1) suffices. */
 int zeggs_format_table_text(const double* table /* host */, long rows, int cols, char* out, size_t cap, size_t* written);
 
+/* Dataset preparation (csrc/prepare.hip; zeggs_version() >= 103): the stages of ZEGGS/data_pipeline.py:234-736 around preprocess_audio /
+ * preprocess_animation.  All pointers are device pointers unless marked; workspaces are caller-owned.
+ *
+ * zeggs_spline_resample: y [N, W] float64 -> out [M, W] float64 = the not-a-knot cubic spline over the integer grid 0 .. N-1
+ * (scipy griddata(method = "cubic") on 1-D points = interp1d(kind = "cubic")) evaluated at linspace(0, N-1, M); any W >= 1, M >= 1
+ * (up-sampling included); N < 4 is an error, as in scipy.  zeggs_spline_chunk: the rows per elimination chunk, the halo on either
+ * side and the widest table that takes the thread-per-chunk kernel (what a test needs to place its sizes). */
+int zeggs_spline_chunk(int* chunk, int* halo, int* narrow_width);
+size_t zeggs_spline_resample_workspace_bytes(long N, int W);
+int zeggs_spline_resample(const double* y, long N, int W, long M, double* out, void* ws, size_t ws_bytes, void* stream);
+/* Euler degrees [N, J, 3] in channel order `order` (packed as ZeggsAnimDims.order, "zyx" or "xzy": what quat.to_euler has) ->
+ * [M, J, 3]: from_euler, sign unrolling along time, spline on the four components, normalise, to_euler (data_pipeline.py:423-427). */
+size_t zeggs_rot_stretch_workspace_bytes(long N, int J, long M);
+int zeggs_rot_stretch(const double* euler_deg, long N, int J, long M, int order, double* out_deg, void* ws, size_t ws_bytes, void* stream);
+/* out[i] = wav[start + i] inside the union of the sample intervals [intervals[2j], intervals[2j+1]) (int64 [n, 2]), 0 outside, for
+ * start + i < min(end, n_wav) (data_pipeline.py:306-332, 403); float32 and / or float64 output (either may be NULL). */
+int zeggs_audio_prepare(const float* wav, long n_wav, const long* intervals, int n_intervals, long start, long end, float* out_f32,
+                        double* out_f64, void* stream);
+/* The centring of a trimmed take, in place (data_pipeline.py:449-459): positions / euler_deg [N, J, 3] float64; joint 0 is moved by
+ * frame 0's (x, 0, z) and turned by the inverse of frame 0's (w, 0, y, 0), NOT normalised, as the reference.  round_f32 != 0: the
+ * results are rounded to float32 (a take stored as float32).  ws: >= 64 bytes. */
+int zeggs_center_take(double* positions, double* euler_deg, long N, int J, int order, int round_f32, void* ws, size_t ws_bytes,
+                      void* stream);
+/* x [R, D] float32, mask [R] bytes -> mean [D], population std [D] over the masked rows, pooled [1] = the population std of all masked
+ * elements; float64, bitwise reproducible. */
+size_t zeggs_masked_stats_workspace_bytes(long R, int D);
+int zeggs_masked_stats(const float* x, const unsigned char* mask, long R, int D, double* mean, double* std_, double* pooled, void* ws,
+                       size_t ws_bytes, void* stream);
+
 /* Launch sequences that are replayed as hipGraphs (the frame sweeps of the "gru" style encoder with option "sweep_graphs" = 1; default off):
  * how many were captured and how many replays hit the cache on this process.  No reference counterpart (diagnostics). */
 int zeggs_sweep_graph_stats(long* captures, long* replays);

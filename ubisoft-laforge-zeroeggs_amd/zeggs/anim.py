@@ -203,13 +203,20 @@ def preprocess_animation(anim, device=None):
     (root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt, cpos, crot, ctxy, cvel, cvrt, gaze_pos,
     gaze_dir) as DEVICE tensors (float64; ltxy / ctxy float32)."""
     device = torch.device(device or "cuda")
-    names = list(anim["names"])
     rot = torch.as_tensor(np.ascontiguousarray(anim["rotations"], dtype=np.float64), device=device)
     pos = torch.as_tensor(np.ascontiguousarray(anim["positions"], dtype=np.float64), device=device)
-    parents = torch.as_tensor(np.ascontiguousarray(anim["parents"], dtype=np.int32), device=device)
+    return preprocess_animation_device(rot, pos, anim["parents"], anim["names"], anim["frametime"], anim["order"])
+
+
+def preprocess_animation_device(rot, pos, parents, names, frametime, order):
+    """preprocess_animation on channels that are on the device already: rot / pos float64 [N, J, 3] contiguous (what the
+    dataset builder holds after trimming / stretching / centring a take)"""
+    device = rot.device
+    names = list(names)
+    parents = torch.as_tensor(np.ascontiguousarray(parents, dtype=np.int32), device=device)
     N, J = rot.shape[0], rot.shape[1]
-    d = AnimDims(N, J, names.index("Hips"), names.index("Spine2"), names.index("Head"), float(anim["frametime"]),
-                 order_code(anim["order"]))      # any channel order (quat.from_euler takes any)
+    d = AnimDims(N, J, names.index("Hips"), names.index("Spine2"), names.index("Head"), float(frametime),
+                 order_code(order))      # any channel order (quat.from_euler takes any)
     L = ops.lib()
     L.zeggs_anim_features_workspace_bytes.restype = C.c_size_t
     ws = torch.empty(int(L.zeggs_anim_features_workspace_bytes(C.byref(d))), dtype=torch.uint8, device=device)

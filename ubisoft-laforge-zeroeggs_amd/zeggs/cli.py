@@ -1,5 +1,6 @@
-"""Command line of the drop-in: the option surface of the reference's two scripts on the MI355X engine.
+"""Command line of the drop-in: the option surface of the reference's three scripts on the MI355X engine.
 
+    python -m zeggs.cli prepare  -c data_pipeline_conf.json [--base-path DIR]  (ZEGGS/data_pipeline.py:739-744)
     python -m zeggs.cli train    -o options.json [-n NAME]                     (ZEGGS/main.py:10-74)
     python -m zeggs.cli generate -o options.json -s style.bvh -a speech.wav ... (ZEGGS/generate.py:414-525)
     python -m zeggs.cli generate -o options.json -c pairs.csv                   (batch mode, same CSV columns)
@@ -42,6 +43,15 @@ def cmd_train(a):
     train(models_dir=models, logs_dir=logs, path_processed_data=data / "processed_data.npz",
           path_data_definition=data / "data_definition.json", train_options=options["train_opt"],
           network_options=options["net_opt"])
+    return 0
+
+
+def cmd_prepare(a):
+    from .data_pipeline import data_pipeline
+    conf = json.loads(Path(a.conf).read_text())
+    if a.base_path:
+        conf["base_path"] = a.base_path
+    data_pipeline(conf, log=lambda line: print(line, flush=True))
     return 0
 
 
@@ -90,8 +100,12 @@ def cmd_generate(a):
 
 
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="zeggs", description="ZeroEGGS on the MI355X engine: train / generate")
+    ap = argparse.ArgumentParser(prog="zeggs", description="ZeroEGGS on the MI355X engine: prepare / train / generate")
     sub = ap.add_subparsers(dest="cmd", required=True)
+    d = sub.add_parser("prepare", help="raw takes -> processed_data.npz, stats.npz, data_definition.json (reference: python data_pipeline.py)")
+    d.add_argument("-c", "--conf", required=True, help="pipeline conf (configs/data_pipeline_conf_v*.json layout)")
+    d.add_argument("--base-path", default=None, help="overrides the conf's base_path (the directory that holds original/ and the info CSV)")
+    d.set_defaults(fn=cmd_prepare)
     t = sub.add_parser("train", help="train the networks (reference: python main.py -o ... -n ...)")
     t.add_argument("-o", "--options", required=True, help="options file (configs_v*.json layout)")
     t.add_argument("-n", "--name", help="run name stored in the options")

@@ -202,3 +202,73 @@ def make_bvh_clip(nframes, seed=0):
     pos[:, 0] += (_smooth(rng, nframes, 3, 3.0) * np.array([1.0, 0.1, 1.0])).astype(np.float32)
     return dict(rotations=rot, positions=pos, offsets=offsets, parents=np.asarray(PARENTS, np.int32),
                 names=list(BONE_NAMES), order="zyx", frametime=1.0 / 60.0)
+
+
+# ----------------------------------------------------------------------------- raw corpus (what `zeggs.cli prepare` reads)
+INFO_COLUMNS = ("audio_filename", "audio_start_time", "anim_start_time", "style", "acting_start_time", "acting_end_time", "anim_bvh",
+                "validation")
+
+
+def timecode(sixtieths, fps=60):
+    """sixtieths of a second -> 'HH:MM:SS:FF' at `fps` (the info CSV's audio timecodes run at 30 fps, the others at 60)"""
+    s, f = divmod(int(sixtieths), 60)
+    return "%02d:%02d:%02d:%02d" % (s // 3600, (s // 60) % 60, s % 60, f * fps // 60)
+
+
+def make_raw_take(name, nframes, seed=0, style="Neutral", validation=False, anim=None, fs=16000, lead=(600, 10, 25), tail=5,
+                  audio_seconds=0.0):
+    """One take of a raw corpus: BVH animation dict, int16 speech, the info row and the speaker-timing rows.  The audio recording
+    starts `lead[0]` sixtieths after midnight, the animation `lead[1]` sixtieths later, the acting `lead[2]` sixtieths after the audio;
+    it ends `tail` frames before the animation does; the recording lasts a quarter of a second longer, `audio_seconds` at least.  The speaker rows keep two "R" spans and silence an "L" span between them."""
+    anim = anim or make_bvh_clip(nframes, seed)
+    nframes = len(anim["rotations"])
+    t_audio, t_anim, t_act0 = lead[0], lead[0] + lead[1], lead[0] + lead[2]
+    t_act1 = t_anim + nframes - tail
+    n_audio = max(int(np.ceil((t_act1 - t_audio) * fs / 60.0)) + fs // 4, int(audio_seconds * fs))
+    secs = n_audio / fs
+    cut = lambda x: "%d:%02d.%03d" % (int(x) // 60, int(x) % 60, int(round((x - int(x)) * 1000)) % 1000)  # noqa: E731
+    speaker = [("R1", cut(0.2), cut(0.45 * secs)), ("L1", cut(0.45 * secs), cut(0.6 * secs)), ("R2", cut(0.6 * secs), cut(secs))]
+    row = dict(audio_filename=name + ".wav", audio_start_time=timecode(t_audio, 30), anim_start_time=timecode(t_anim),
+               style=style, acting_start_time=timecode(t_act0), acting_end_time=timecode(t_act1), anim_bvh=name + ".bvh",
+               validation="TRUE" if validation else "FALSE")
+    return dict(name=name, anim=anim, wav=synth_wav(n_audio, seed=seed + 500, fs=fs), fs=fs, info=row, speaker=speaker)
+
+
+def write_raw_corpus(directory, takes, info_name="info.csv"):
+    """takes (make_raw_take) -> <directory>/original/<name>.bvh|.wav|.csv and <directory>/<info_name>: the layout
+    data_pipeline(conf) reads with base_path = directory"""
+    import csv
+    from scipy.io import wavfile
+    from . import anim as zanim
+    d = Path(directory)
+    (d / "original").mkdir(parents=True, exist_ok=True)
+    for t in takes:
+        zanim.bvh_save(d / "original" / (t["name"] + ".bvh"), t["anim"])
+        wavfile.write(str(d / "original" / (t["name"] + ".wav")), t["fs"], t["wav"])
+        with open(d / "original" / (t["name"] + ".csv"), "w", newline="") as fh:
+            w = csv.writer(fh)
+            w.writerow(["#", "Start", "End"])
+            w.writerows(t["speaker"])
+    with open(d / info_name, "w", newline="") as fh:
+        w = csv.DictWriter(fh, fieldnames=INFO_COLUMNS)
+        w.writeheader()
+        w.writerows(t["info"] for t in takes)
+    return d / info_name
+
+
+PIPELINE_CONF = dict(
+    base_path=".", processed_data_path="processed", save_trimmed_audio=True, save_trimmed_animation=True,
+    save_normalized_animations=False, save_final_data=True, info_filename="info.csv",
+    audio_conf=dict(pre_emphasis=False, pre_emph_coeff=0.97, centered=True, real_amplitude=True, normalize_mel_bins=True,
+                    normalize_range=True, min_clipping=1e-5, sampling_rate=16000, mel_fmin=20, mel_fmax=7600, n_mel_channels=80,
+                    filter_length=800, hop_length=200, resample_method="linear", normalize_loudness=False),
+    audio_feature_type=["mel_spec", "energy"], visualize_spectrogram=False, visualize_gaze=False, len_ratios=[0.9, 1.0])
+
+
+def pipeline_conf(base_path, **over):
+    """the reference's configs/data_pipeline_conf_v1.json keys (loudness normalisation off) for a corpus under `base_path`"""
+    import copy
+    conf = copy.deepcopy(PIPELINE_CONF)
+    conf["base_path"] = str(base_path)
+    conf.update(over)
+    return conf
