@@ -212,6 +212,12 @@ typedef struct {
   float *l0_w, *l0_b, *w_ih0, *w_hh0, *b_ih0, *b_hh0, *w_ih1, *w_hh1, *b_ih1, *b_hh1, *l2_w, *l2_b, *c0_w,
       *c0_b, *c1_w, *c1_b, *c2_w, *c2_b, *l3_w, *l3_b, *g_w, *g_b, *be_w, *be_b;
 } ZeggsDecGrads;
+/* The four vectors are INDEPENDENT (the reference's Decoder.forward takes them separately): out_mean need not equal
+ * in_mean[:PO] and out_std may hold exact zeros (constant channels) -- every path folds (b2 out_std + out_mean - in_mean) / in_std
+ * into its weights per call, and zeggs_decoder_prepare / zeggs_decoder_batch_prepare do so for the statistics THEY were given: a
+ * prepared workspace serves calls with those statistics only.  Root integration: the half turn dt / 2 |root_vrt| takes the branch
+ * the reference takes (< 1e-5: normalize([1, x]) with its 1e-5 in the norm); an exactly zero turn gives finite gradients where the
+ * reference's autograd gives NaN (0 * inf behind the sqrt).  tests/test_gpu_decoder_stats.py runs every path at every branch. */
 typedef struct {
   const float *in_mean, *in_std;   /* [PI] */
   const float *out_mean, *out_std; /* [PO] */

@@ -726,3 +726,285 @@ def loss_oracle_at_kinks(data, got):
         base = best[2]
         chosen.append(((k, j), s0, best[1]))
     return loss, terms, base + list(grads[8:]), near, chosen
+
+
+# ----------------------------------------------------------------------------- decoder statistics kinds (tests/test_gpu_decoder_stats.py)
+# The four statistics vectors of the decoder are independent arguments (reference Decoder.forward), but synth.make_stats() and both
+# recorded stats files have out_mean == in_mean[:PO] exactly, and with them the root's half turn per frame h = dt / 2 |root_vrt|
+# stays in [2.8e-3, 6.4e-3]: one of the three branches of every quaternion exponential (dec_math.h) and a zero (mu_o - mu_i) term
+# in every fold of the statistics into the weights.  tests/test_decoder_stats_oracle_cpu.py proves on the CPU that every case below
+# lies in the branch it is meant for and that the comparison is sharp (negative controls).
+DEC_KINDS = ("tied", "untied", "still", "brisk", "spin")
+DEC_TURN = dict(still=(0.0, 0.0, 0.0), brisk=(52.0, -83.0, 58.0), spin=(70.0, -110.0, 60.0))      # out_mean[3:6]: |.| = 0, 113.8, 143.5
+# the open interval of h = dt / 2 |root_vrt| (frames 1 .. T-1 of the float64 oracle) that a kind must keep at every shape; h is at
+# least 2x away from the branch point 1e-5 on either side everywhere (the function is discontinuous there)
+DEC_TURN_RANGE = dict(tied=(1e-3, 0.1), untied=(1e-3, 0.1), still=(0.0, 2e-6), brisk=(0.9, 0.995), spin=(1.05, 1.5), zero=(-1.0, 1e-300))
+DEC_OUT_BOUND, DEC_GRAD_BOUND = 1e-4, 3e-4            # tests/test_gpu_parity.py::test_decoder_backward_vs_oracle
+DEC_SMALL_EPS = 1e-5                                  # reference tquat.py:50-51, 94-99: quat_exp's branch point and quat_normalize's eps
+DEC_NAMES = ("root_pos", "root_rot", "root_vel", "root_vrt", "lpos", "ltxy", "lvel", "lvrt")
+DEC_KEYS = tuple("Y_" + n for n in DEC_NAMES)
+# A slice may have a bound wider than DEC_GRAD_BOUND only if the FLOAT32 ORACLE's own error on it exceeds 3e-5: {slice: 10 x that
+# measured error}.  None does (float32 oracle <= 3.4e-7 on every slice, tests/test_decoder_stats_oracle_cpu.py).
+DEC_SLICE_BOUNDS = {}
+
+
+def decoder_stats(kind, dtype=torch.float32, device="cpu"):
+    """-> dict(in_mean, in_std, out_mean, out_std) derived from synth.make_stats(); float32 values, cast to `dtype`.
+    tied: today's set (out_mean == in_mean[:PO]).  untied: out_mean ~ N(0, 1) from its own generator, out_std[3:6] = (0.8, 1.1,
+    0.6); the 40 zero entries of out_std stay -- constant channels whose (mu_o - mu_i) / sigma_i is not zero.  still / brisk / spin:
+    untied with out_mean[3:6] = DEC_TURN[kind] (still: out_std[3:6] = 1e-4) -- the small-angle branch, the top of the polynomial
+    range, the libm branch.  zero: still with out_std[3:6] = 0, a half turn of exactly 0 (forward only: the reference's own
+    gradient is NaN there, 0 * inf behind the sqrt)."""
+    s = synth.make_stats()
+    im, isd = np.asarray(s["anim_input_mean"], np.float32), np.asarray(s["anim_input_std"], np.float32)
+    om, osd = np.asarray(s["anim_output_mean"], np.float32).copy(), np.asarray(s["anim_output_std"], np.float32).copy()
+    assert kind in DEC_KINDS + ("zero",), kind
+    if kind != "tied":
+        assert int((osd == 0).sum()) == 40 and not bool((osd[:6] == 0).any())
+        om = np.random.default_rng(2024).standard_normal(synth.POSE_OUT).astype(np.float32)
+        osd[3:6] = (0.8, 1.1, 0.6)
+        if kind in ("still", "zero"):
+            om[3:6], osd[3:6] = 0.0, (1e-4 if kind == "still" else 0.0)
+        elif kind != "untied":
+            om[3:6] = DEC_TURN[kind]
+    t = lambda a: torch.as_tensor(a).to(dtype).to(device)  # noqa: E731
+    return dict(in_mean=t(im), in_std=t(isd), out_mean=t(om), out_std=t(osd))
+
+
+_DEC_NETS, _DEC_CASES = {}, {}
+
+
+def decoder_net(tag):
+    """(cached; callers move a deepcopy to the device) the seeded decoders of the statistics tests: "main" (build_nets), "film" (rnn_cond="film", the construction of
+    test_gpu_parity._variant_nets), "h512" (nhidden = 512)"""
+    if tag not in _DEC_NETS:
+        if tag == "main":
+            _DEC_NETS[tag] = build_nets()[1]
+        else:
+            assert tag in ("film", "h512"), tag
+            torch.manual_seed(4321 if tag == "film" else 77)
+            _DEC_NETS[tag] = (modules.Decoder(synth.POSE_IN, synth.POSE_OUT, 64, 64, 1024, 2, rnn_cond="film") if tag == "film"
+                              else modules.Decoder(synth.POSE_IN, synth.POSE_OUT, 64, 64, 512, 2))
+    return _DEC_NETS[tag]
+
+
+def decoder_case(B, T):
+    """float32 inputs of a [B, T] rollout: clips of synth.make_clip, speech / style seeded as test_gpu_parity._oracle_vs_hip_rollout
+    -> dict(fp: the 8 first-pose tensors (DEC_NAMES order), gaze [B, T, 3], speech, style [B, T, 64]); cached, read-only"""
+    if (B, T) in _DEC_CASES:
+        return _DEC_CASES[(B, T)]
+    stats = synth.make_stats()
+    clips = [synth.make_clip(max(T, 4), seed=700 + b, stats=stats) for b in range(B)]
+    tt = lambda k: torch.as_tensor(np.stack([c[k][:T] for c in clips]))  # noqa: E731
+    gen = torch.Generator().manual_seed(4)
+    speech, style = torch.randn(B, T, 64, generator=gen) * 0.5, torch.randn(B, T, 64, generator=gen) * 0.5
+    _DEC_CASES[(B, T)] = dict(fp=[tt(k)[:, 0] for k in DEC_KEYS], gaze=tt("Y_gaze_pos"), speech=speech, style=style, B=B, T=T)
+    return _DEC_CASES[(B, T)]
+
+
+def decoder_weighting(name, B, T):
+    """weights of the differentiated sum over the 8 outputs.  "all": seeded normal weights on everything; "root": on root_pos and
+    root_rot of the LAST frame only -- every gradient then arrives through the root adjoint carried over T - 1 steps and through the
+    gaze direction."""
+    J = synth.NJ
+    shapes = [(B, T, 3), (B, T, 4), (B, T, 3), (B, T, 3), (B, T, J, 3), (B, T, J, 2, 3), (B, T, J, 3), (B, T, J, 3)]
+    gen = torch.Generator().manual_seed(11)
+    wts = [torch.randn(*sh, generator=gen) for sh in shapes]
+    if name == "root":
+        for i, w in enumerate(wts):
+            if i >= 2:
+                w.zero_()
+            else:
+                w[:, :-1] = 0.0
+    else:
+        assert name == "all", name
+    return wts
+
+
+class oracle_bug:
+    """Context manager around an ORACLE evaluation: one of the bug models of the negative controls.
+    "eps0": quat_exp(x, eps=0) in the root integration -- the polynomial / libm formula where the small branch is due;
+    "gaze_detached": the gaze direction's gradient to root_pos / root_rot cut (detach inside vectorize_input);
+    ("stale_fold", stats A): the pose fed back to the next step is de-normalised with the out_mean / out_std of A while the outputs
+    use the call's own -- what a fold of A into the weight packs gives under a call with other statistics."""
+
+    def __init__(self, model):
+        self.model = model
+
+    def __enter__(self):
+        from oracle import nets as onets
+        self.onets, self.saved = onets, (onets.quat_from_helical, onets.vectorize_input, onets.devectorize_output)
+        qfh, vec, dev = self.saved
+        model = self.model
+        if model == "eps0":
+            onets.quat_from_helical = lambda x, eps=0.0: onets.quat_exp(x / 2.0, 0.0)
+        elif model == "gaze_detached":
+            onets.vectorize_input = lambda rp, rr, *rest: vec(rp.detach(), rr.detach(), *rest)
+        elif isinstance(model, tuple) and model[0] == "stale_fold":
+            A, last = model[1], [None]
+
+            def dev_(pred, *a):
+                last[0] = pred
+                return dev(pred, *a)
+
+            def vec_(*a):
+                v = vec(*a)
+                if last[0] is None:
+                    return v
+                im, isd = a[-2], a[-1]
+                PO = last[0].shape[1]
+                fb = (last[0] * A["out_std"].to(v.dtype) + A["out_mean"].to(v.dtype) - im[:PO]) / isd[:PO]
+                return torch.cat([fb, v[:, PO:]], dim=1)
+            onets.devectorize_output, onets.vectorize_input = dev_, vec_
+        elif model is not None:
+            raise ValueError(model)
+        return self
+
+    def __exit__(self, *exc):
+        self.onets.quat_from_helical, self.onets.vectorize_input, self.onets.devectorize_output = self.saved
+        return False
+
+
+def decoder_oracle(de, case, stats, wts=None, dtype=torch.float64, bug=None):
+    """oracle.nets.decoder_rollout of one case in `dtype` -> (8 outputs, {name: gradient} or None).  Gradients (wts given) of
+    sum(out * wts) w.r.t. every parameter, "speech" and "style"."""
+    from oracle import nets as onets
+    w = {k: v.detach().cpu().to(dtype).clone().requires_grad_(wts is not None) for k, v in de.state_dict().items()}
+    sp = case["speech"].detach().clone().to(dtype).requires_grad_(wts is not None)
+    sy = case["style"].detach().clone().to(dtype).requires_grad_(wts is not None)
+    s = {k: v.to(dtype) for k, v in stats.items()}
+    with oracle_bug(bug), torch.set_grad_enabled(wts is not None):
+        O = onets.decoder_rollout(w, *[t.to(dtype) for t in case["fp"]], case["gaze"].to(dtype), sp, sy, s["in_mean"], s["in_std"],
+                                  s["out_mean"], s["out_std"], synth.DT)
+        if wts is None:
+            return [o.detach() for o in O], None
+        sum((o * wt.to(dtype)).sum() for o, wt in zip(O, wts)).backward()
+    grads = {k: v.grad for k, v in w.items()}
+    grads["speech"], grads["style"] = sp.grad, sy.grad
+    return [o.detach() for o in O], grads
+
+
+_DEC_ORACLE = {}
+
+
+def decoder_oracle_cached(net, B, T, kind, weighting=None, dtype=torch.float64, bug=None):
+    """decoder_oracle of (decoder_net(net), decoder_case(B, T), decoder_stats(kind), decoder_weighting(weighting)), computed once
+    per process and left unchanged: the paths of one shape share it"""
+    key = (net, B, T, kind, weighting, dtype, bug if not isinstance(bug, tuple) else None)
+    if isinstance(bug, tuple) or key not in _DEC_ORACLE:
+        wts = None if weighting is None else decoder_weighting(weighting, B, T)
+        res = decoder_oracle(decoder_net(net), decoder_case(B, T), decoder_stats(kind), wts, dtype, bug)
+        if isinstance(bug, tuple):
+            return res
+        _DEC_ORACLE[key] = res
+    return _DEC_ORACLE[key]
+
+
+def half_turns(outs):
+    """h = dt / 2 |root_vrt| of the generated frames 1 .. T-1 (what the root integration exponentiates) -> (min, max)"""
+    h = 0.5 * synth.DT * outs[3][:, 1:].double().norm(dim=-1)
+    return float(h.min()), float(h.max())
+
+
+def assert_half_turns(kind, outs):
+    """the branch condition of a kind, from the float64 oracle's own root_vrt"""
+    lo, hi = half_turns(outs)
+    a, b = DEC_TURN_RANGE[kind]
+    assert a < lo and hi < b, (kind, lo, hi)
+    assert hi < DEC_SMALL_EPS / 2 or lo > 2 * DEC_SMALL_EPS, (kind, lo, hi)
+    return lo, hi
+
+
+def decoder_grad_slices(grads):
+    """{name: gradient} of a decoder -> {slice: tensor}: every tensor whole, and the parts of the three matrices whose blocks see
+    different shares of the root chain -- output layer (layer2, FiLM: layer3) rows [0:3] root_vel, [3:6] root_vrt, [6:] joints;
+    layer0 columns: pose [0:6], [6:PO], gaze, speech, style; GRU layer 0 input columns: hid [:H] and the same groups behind it."""
+    out = dict(grads)
+    p = "recurrent_decoder."
+    last = p + ("layer3" if p + "layer3.weight" in grads else "layer2")
+    for a, b in ((0, 3), (3, 6), (6, None)):
+        out[f"{last}.weight[{a}:{b}]"] = grads[last + ".weight"][a:b]
+        out[f"{last}.bias[{a}:{b}]"] = grads[last + ".bias"][a:b]
+    PO = grads[last + ".bias"].shape[0]
+    SP = grads["speech"].shape[-1]
+    XD = grads[p + "layer0.weight"].shape[1]
+    cols = [("pose[0:6]", 0, 6), ("pose[6:]", 6, PO), ("gaze", PO, PO + 3), ("speech", PO + 3, PO + 3 + SP)]
+    if XD > PO + 3 + SP:
+        cols.append(("style", PO + 3 + SP, XD))
+    H = grads[p + "layer1.weight_hh_l0"].shape[1]
+    for n, a, b in cols:
+        out[f"{p}layer0.weight[:, {n}]"] = grads[p + "layer0.weight"][:, a:b]
+        out[f"{p}layer1.weight_ih_l0[:, {n}]"] = grads[p + "layer1.weight_ih_l0"][:, H + a:H + b]
+    out[f"{p}layer1.weight_ih_l0[:, hid]"] = grads[p + "layer1.weight_ih_l0"][:, :H]
+    return out
+
+
+def decoder_slice_errors(got, ref):
+    """per slice of decoder_grad_slices: max |got - ref| / max |ref| (each slice against its OWN largest entry); a slice whose
+    reference is exactly zero must be exactly zero: its error is 0 or inf (the shape of slice_errors above)"""
+    gs, rs = decoder_grad_slices(got), decoder_grad_slices(ref)
+    errs = {}
+    for k, r in rs.items():
+        gk = gs[k].detach().double().cpu()
+        m = float(r.abs().max())
+        if m == 0.0:
+            errs[k] = 0.0 if float(gk.abs().max()) == 0.0 else float("inf")
+        else:
+            errs[k] = float((gk - r.double()).abs().max()) / m
+    return errs
+
+
+def decoder_output_errors(got, ref):
+    """per output group: max |got - ref|"""
+    return {n: float((o.detach().double().cpu().reshape(r.shape) - r.double()).abs().max()) for n, o, r in zip(DEC_NAMES, got, ref)}
+
+
+def root_norm_change(outs):
+    """|root_rot[:, -1]| - |root_rot[:, 0]| per row"""
+    q = outs[1].detach().double().cpu()
+    return q[:, -1].norm(dim=-1) - q[:, 0].norm(dim=-1)
+
+
+def assert_decoder_outputs(kind, got, ref, T):
+    """The output assertions of one case against the float64 oracle `ref`: every group within DEC_OUT_BOUND; still / zero: root_rot
+    within (T - 1) 1e-6 -- a tenth of the norm deficit (T - 1) 1e-5 that the small branch's division by (|.| + 1e-5) produces and
+    the other branches would not -- and the norm of root_rot loses (T - 1) 1e-5 within (T - 1) 1e-6; the other kinds keep the norm
+    within 2e-6.  -> the errors per group."""
+    errs = decoder_output_errors(got, ref)
+    for o in got:
+        assert bool(torch.isfinite(o).all()), kind
+    for n, e in errs.items():
+        assert e < DEC_OUT_BOUND, (kind, n, e)
+    dn = root_norm_change(got)
+    if kind in ("still", "zero"):
+        assert errs["root_rot"] < (T - 1) * 1e-6, (kind, errs["root_rot"])
+        assert float((dn + (T - 1) * DEC_SMALL_EPS).abs().max()) < (T - 1) * 1e-6, (kind, dn)
+    elif kind != "tied":
+        assert float(dn.abs().max()) < 2e-6, (kind, dn)
+    return errs
+
+
+def assert_decoder_grads(got, ref, tag=""):
+    """every parameter tensor, dspeech, dstyle and every slice of decoder_grad_slices within its bound of the float64 oracle, each
+    relative to its own largest oracle entry -> the errors per slice"""
+    errs = decoder_slice_errors(got, ref)
+    bad = {k: e for k, e in errs.items() if not e < DEC_SLICE_BOUNDS.get(k, DEC_GRAD_BOUND)}
+    assert not bad, (tag, bad)
+    return errs
+
+
+# (path, decoder, B, T) of tests/test_gpu_decoder_stats.py: the smallest shapes at which each path runs -- T >= 4 for the persistent
+# forward, T >= 3 for the persistent sweep; B = 5: one 16-row tile, 17: two tiles (4-row form / dual chain), 33 / 40: three tiles
+# and the two-sweep BPTT
+DEC_TRAIN_CASES = (("generic", "main", 2, 6), ("stage", "main", 5, 6), ("stage", "main", 33, 4), ("tp16-tiles4=0", "main", 5, 6),
+                   ("tp16-tiles4=1", "main", 5, 6), ("tp4", "main", 17, 5), ("dual", "main", 17, 5), ("bptt", "main", 5, 6),
+                   ("bptt", "main", 17, 5), ("bptt", "main", 40, 4), ("film", "film", 5, 6), ("h512", "h512", 2, 6))
+DEC_TRAIN_KINDS = (("tied", "all"),) + tuple((k, w) for k in ("untied", "still", "brisk", "spin") for w in ("all", "root"))
+DEC_INFER_CASES = (("ring", 3, 7), ("b1-persistent", 1, 6), ("b1-persistent", 1, 37), ("b1-stage-gemv", 1, 6), ("b1-stage-gemv", 1, 37),
+                   ("b1-stage-mfma", 1, 6), ("b1-stage-mfma", 1, 37), ("batch-chunk4", 3, 9))
+DEC_INFER_KINDS = ("tied", "untied", "still", "brisk", "spin", "zero")
+
+
+def decoder_shapes():
+    """every (decoder, B, T) the GPU file runs"""
+    return sorted({c[1:] for c in DEC_TRAIN_CASES} | {("main", B, T) for _, B, T in DEC_INFER_CASES})

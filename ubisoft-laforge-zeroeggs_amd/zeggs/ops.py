@@ -626,6 +626,14 @@ def _versions(params):
     return tuple(int(t._version) for t in params)
 
 
+def _prepared_key(d, params, stats):
+    """What a preparation is valid for: the dimensions, the weights AND the four statistics vectors -- the packs fold in_mean,
+    in_std, out_mean, out_std into the weights (dec_fast_merge_prep, dec_tp_pack), so a call with other statistics must not pick
+    them up."""
+    return (d.B, d.T, d.PI, d.PO, d.SP, d.ST, d.H, d.film, tuple(t.data_ptr() for t in params), _versions(params),
+            tuple(t.data_ptr() for t in stats), _versions(stats))
+
+
 def decoder_prepare(dec, B, T, SP, ST, in_mean, in_std, out_mean, out_std, dt, stream, after=None):
     """Weight-only preparation of the NEXT training-mode decoder_core call of THIS context (ops.use) with these dimensions
     (zeggs_decoder_prepare) on `stream`, beside whatever the current stream does meanwhile (the encoders' forward); that
@@ -654,8 +662,7 @@ def decoder_prepare(dec, B, T, SP, ST, in_mean, in_std, out_mean, out_std, dt, s
         if after is not None:       # (more work of the caller for `stream`, behind the packs and outside what the forward waits for)
             after()
     if mask > 0:
-        key = (d.B, d.T, d.PI, d.PO, d.SP, d.ST, d.H, d.film, tuple(t.data_ptr() for t in params), _versions(params))
-        ectx.prepared = (key, ws, ev, int(mask))
+        ectx.prepared = (_prepared_key(d, params, stats), ws, ev, int(mask))
     return int(mask)
 
 
@@ -685,8 +692,7 @@ class _DecoderFn(torch.autograd.Function):
         dev = pose0.device
         prep = ectx.prepared
         mask = 0
-        if prep is not None and training and prep[0] == (d.B, d.T, d.PI, d.PO, d.SP, d.ST, d.H, d.film,
-                                                         tuple(t.data_ptr() for t in params), _versions(params)):
+        if prep is not None and training and prep[0] == _prepared_key(d, params, stats):
             ectx.prepared = None
             _, ws, ev, mask = prep                          # packs of this step's weights, made on a second stream
             ectx.prepared_hits += 1
