@@ -74,6 +74,33 @@ def test_gemm_routing_is_per_thread_not_per_process():
     assert list(out) == base
 
 
+_SWEEP_STATE_CHILD = """
+import ctypes, json, sys
+L = ctypes.CDLL(sys.argv[1])
+L.zeggs_last_error.restype = ctypes.c_char_p
+out = {"fresh": [L.zeggs_persistent_state(w) for w in range(3)], "toggle": []}
+for w, name in ((0, b"persistent"), (1, b"train_persistent"), (2, b"bwd_persistent")):
+    out["toggle"].append([L.zeggs_set_option(name, 0), L.zeggs_set_option(name, 1), L.zeggs_persistent_state(w)])
+out["unknown"] = [L.zeggs_set_option(b"no_such_option", 1), L.zeggs_last_error().decode()]
+print(json.dumps(out))
+"""
+
+
+def test_persistent_sweep_state_before_any_launch():
+    """The owner of the persistent kernels' option / first-use state, host only, in a process that has launched nothing: every
+    kernel starts unused (-1); switching its option off and on again succeeds and leaves it unused (re-enabling re-arms only a
+    kernel that FAILED its validation, state 0); an unknown option is still refused by name."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _SWEEP_STATE_CHILD, str(ops._LIB_PATH)], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["fresh"] == [-1, -1, -1]
+    assert out["toggle"] == [[0, 0, -1]] * 3
+    assert out["unknown"][0] != 0 and "no_such_option" in out["unknown"][1]
+
+
 def test_no_cpu_fallback():
     se = modules.SpeechEncoder(synth.N_AUDIO, 64, 64)
     with pytest.raises(RuntimeError, match="GPU"):

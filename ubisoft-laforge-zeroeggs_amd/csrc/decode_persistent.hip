@@ -28,16 +28,10 @@
 #include "dec_math.h"
 #include "gemm.h"
 #include "kernels.h"
-
-int g_persistent = 1;           // zeggs_set_option("persistent", 0/1)
-int g_poll_sleep = 0;
-int g_poll_stagger = 0;
-int g_persistent_spin = 1 << 21;   // bound of every device-side wait of the three persistent kernels ("persistent_spin")
-static int g_persistent_ok = -1;   // -1 not validated yet, 0 failed once (disabled), 1 validated on this process
+#include "sweep_sync.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) unsigned long long gu64;
 constexpr int PH = 1024, PTHR = 512, PNCU = 256, J0 = 26, J1 = 16, J3 = 18;
 
 struct PArgs {
@@ -50,14 +44,15 @@ struct PArgs {
   const float *h0_init, *h1_init;
   float *h0_fin, *h1_fin;      // state after the last frame (streaming), may be null
   unsigned long long *g_h0, *g_h1, *g_hid, *g_xp;
-  unsigned* err;
-  unsigned* status;         // caller-owned sticky give-up flags (ZeggsDecCall.status), may be null
-  unsigned spin;            // bound of every sweep (option "persistent_spin")
+  // the SweepSync members this kernel reads, flat: embedding the struct moves XD away from spin, and the register allocation that
+  // follows from the other argument loads spills four more SGPRs (profiles/sweep_sync_refactor.txt)
+  unsigned *err, *status;
+  unsigned spin;
   int XD;
 };
 
 __device__ __forceinline__ void publish(unsigned long long* g, unsigned epoch, float v) {
-  __hip_atomic_store((gu64*)g, ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED,
+  __hip_atomic_store((gu64t*)g, ((unsigned long long)epoch << 32) | (unsigned long long)__float_as_uint(v), __ATOMIC_RELAXED,
                      __HIP_MEMORY_SCOPE_AGENT);
 }
 
@@ -72,7 +67,7 @@ __device__ __forceinline__ bool gather(const unsigned long long* g, int lo, int 
 #pragma unroll
     for (int q = 0; q < PER; ++q) {
       const int i = lo + lane + 64 * q;
-      v[q] = i < hi ? __hip_atomic_load((gu64*)(g + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+      v[q] = i < hi ? __hip_atomic_load((gu64t*)(g + i), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                     : ((unsigned long long)epoch << 32);
     }
 #pragma unroll
@@ -313,10 +308,7 @@ __global__ __launch_bounds__(PTHR, 2) void decode_persistent_k(PArgs a) {
               d_elu(rs[tq] + cst[tq][12] + cst[tq][13] * rootst[7] + cst[tq][14] * rootst[8] + cst[tq][15] * rootst[9]));
   }
   if (fail) {     // a bounded sweep gave up: error word, the caller's sticky status, and NaN in what a consumer reads first
-    if (tid == 0) {
-      atomicOr(a.err, 1u);
-      if (a.status) atomicOr(a.status, ZEGGS_GAVE_UP_DECODE);
-    }
+    if (tid == 0) sweep_gave_up(SweepSync{nullptr, a.err, a.status, 0, 0, 0}, ZEGGS_GAVE_UP_DECODE);
     if (c == 0) {
       const float qnan = __uint_as_float(0x7fc00000u);
       for (int i = tid; i < PO; i += PTHR) a.pose[(long)(T - 1) * PO + i] = qnan;
@@ -343,10 +335,7 @@ int dec_persistent_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
                        const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* gin1,
                        const float* h0_init, const float* h1_init, float* h0_fin, float* h1_fin, hipStream_t s,
                        unsigned* status) {
-  int dev = 0, ncu = 0;
-  ZCHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
-  ZCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess, "device query failed");
-  ZCHECK(ncu >= PNCU, "persistent decode needs %d CUs (device has %d)", PNCU, ncu);
+  ZTRY(require_cus(PNCU, "persistent decode"));
   ZTRY(k_fill((float*)w.pgran, (long)(w.pgran_bytes / 4), 0.f, s));      // tags 0 = nothing published
   PArgs a;
   memset(&a, 0, sizeof(a));
@@ -358,24 +347,10 @@ int dec_persistent_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
   a.gin1 = gin1; a.h0_init = h0_init; a.h1_init = h1_init; a.h0_fin = h0_fin; a.h1_fin = h1_fin;
   unsigned long long* g = (unsigned long long*)w.pgran;
   a.g_h0 = g; a.g_h1 = g + PH; a.g_hid = g + 2 * PH; a.g_xp = g + 3 * PH;
-  a.err = (unsigned*)(g + 3 * PH + 5 * PNCU);
   a.XD = w.XD;
-  a.status = status; a.spin = (unsigned)g_persistent_spin;
+  const SweepSync y = sweep_sync_args(nullptr, dp_errword(w), status);
+  a.err = y.err; a.status = y.status; a.spin = y.spin;
   hipLaunchKernelGGL(decode_persistent_k, dim3(PNCU), dim3(PTHR), 0, s, a);
   ZLAUNCH_CHECK("decode_persistent");
-  return 0;
-}
-
-// 1: validated on this process, 0: failed (disabled), -1: unknown
-int dec_persistent_state() { return g_persistent_ok; }
-void dec_persistent_set_state(int v) { g_persistent_ok = v; }
-int dec_persistent_errptr(const DecWs& w, unsigned** out) {
-  *out = (unsigned*)((unsigned long long*)w.pgran + 3 * PH + 5 * PNCU);
-  return 0;
-}
-int dec_persistent_errors(const DecWs& w, unsigned* out) {
-  const unsigned long long* g = (const unsigned long long*)w.pgran;
-  ZCHECK(hipMemcpy(out, (const void*)(g + 3 * PH + 5 * PNCU), sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess,
-         "persistent decode: error word copy failed");
   return 0;
 }

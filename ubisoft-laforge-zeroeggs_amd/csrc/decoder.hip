@@ -24,9 +24,6 @@ extern int g_timing;
 extern int g_chain;
 extern int g_sweep_graphs;
 extern int g_launch_window;
-extern int g_persistent;
-extern int g_train_persistent;
-extern int g_bwd_persistent;
 extern int g_fused_attention;
 extern int g_gemm_streamk;
 extern int g_gemm_skinny;
@@ -64,22 +61,9 @@ extern "C" int zeggs_set_option(const char* name, int value) {
   }
   if (strcmp(name, "sweep_graphs") == 0) { g_sweep_graphs = value != 0; return 0; }
   if (strcmp(name, "launch_window") == 0) { g_launch_window = value < 0 ? 0 : value; return 0; }
-  // (re-)enabling gives a kernel that was disabled after a failed validation another chance
-  if (strcmp(name, "train_persistent") == 0) {
-    g_train_persistent = value;
-    if (value && dec_tp_state() == 0) dec_tp_set_state(-1);
-    return 0;
-  }
-  if (strcmp(name, "bwd_persistent") == 0) {
-    g_bwd_persistent = value;
-    if (value && dec_bp_state() == 0) dec_bp_set_state(-1);
-    return 0;
-  }
-  if (strcmp(name, "persistent") == 0) {
-    g_persistent = value;
-    if (value && dec_persistent_state() == 0) dec_persistent_set_state(-1);
-    return 0;
-  }
+  if (strcmp(name, "train_persistent") == 0) { g_sweep_kernels[SWEEP_ROLLOUT].set_enabled(value); return 0; }
+  if (strcmp(name, "bwd_persistent") == 0) { g_sweep_kernels[SWEEP_BPTT].set_enabled(value); return 0; }
+  if (strcmp(name, "persistent") == 0) { g_sweep_kernels[SWEEP_DECODE].set_enabled(value); return 0; }
   if (strcmp(name, "mel_mfma") == 0) { g_mel_mfma = value != 0; return 0; }
   if (strcmp(name, "mel_fft") == 0) { g_mel_fft = value != 0; return 0; }
   if (strcmp(name, "gemm_streamk_wgs") == 0) { g_gemm_streamk_wgs = value; return 0; }
@@ -95,8 +79,6 @@ extern "C" int zeggs_set_option(const char* name, int value) {
   if (strcmp(name, "gemm_streamk") == 0) { g_gemm_streamk = value != 0; return 0; }
   if (strcmp(name, "fused_attention") == 0) { g_fused_attention = value != 0; return 0; }
   if (strcmp(name, "bwd_chunks") == 0) { g_bwd_chunks = value < 1 ? 1 : value; return 0; }
-  // bound of every device-side wait of the persistent kernels (polls); 0 makes the first unsatisfied wait give up: the
-  // tests use it to drive the give-up path (tests/test_gpu_giveup.py)
   if (strcmp(name, "tp_tiles4") == 0) { g_tp_tiles4 = value != 0; return 0; }
   if (strcmp(name, "tp_dual") == 0) { g_tp_dual = value != 0; return 0; }
   if (strcmp(name, "tp_prologue") == 0) { g_tp_prologue = value != 0; return 0; }
@@ -105,6 +87,8 @@ extern "C" int zeggs_set_option(const char* name, int value) {
   if (strcmp(name, "gemm_split_bf16") == 0) { g_gemm_split_bf16 = (value == 3 || value == 6 || value == 9) ? value : 0; return 0; }
   if (strcmp(name, "poll_stagger") == 0) { g_poll_stagger = value < 0 ? 0 : value; return 0; }
   if (strcmp(name, "poll_sleep") == 0) { g_poll_sleep = value < 0 ? 0 : value; return 0; }
+  // bound of every device-side wait of the persistent kernels (polls); 0 makes the first unsatisfied wait give up: the
+  // tests use it to drive the give-up path (tests/test_gpu_giveup.py)
   if (strcmp(name, "persistent_spin") == 0) { g_persistent_spin = value < 0 ? 0 : value; return 0; }
   if (strcmp(name, "ln_bwd4") == 0) { g_ln_bwd4 = value; return 0; }
   if (strcmp(name, "mel_exact_log") == 0) { g_mel_exact_log = value; return 0; }
@@ -120,7 +104,7 @@ extern "C" int zeggs_set_option(const char* name, int value) {
 // watch state of its own.
 // 1: the persistent kernel was validated on this process, 0: it failed once and is disabled, -1: not used yet
 extern "C" int zeggs_persistent_state(int which /* 0 decode (B=1), 1 training forward, 2 BPTT sweep */) {
-  return which == 0 ? dec_persistent_state() : which == 1 ? dec_tp_state() : dec_bp_state();
+  return g_sweep_kernels[which == 0 ? SWEEP_DECODE : which == 1 ? SWEEP_ROLLOUT : SWEEP_BPTT].state;
 }
 
 namespace {
@@ -560,12 +544,8 @@ static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, con
   // five launches instead of ten (round 6; option "tp_prologue", default on): [dec_init | dec_fill_cond | tp_cond] in one,
   // [CellStateEncoder layer 0 | hid_1 | the step-1 pose product] in one, CellStateEncoder layer 1, the two halves of its last layer
   // in one, and the rollout's own operand fragments (dec_tp_run) -- every one of them was launch latency on an idle chip
-  bool tp_path = false;
-  if (fast && training && g_train_persistent && dec_tp_state() != 0 && dec_tp_supported(d, w)) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;   // a failed query must not read as "not capturing"
-    tp_path = cap == hipStreamCaptureStatusNone || dec_tp_state() == 1;
-  }
+  SweepKernel& tpk = g_sweep_kernels[SWEEP_ROLLOUT];
+  const bool tp_path = fast && training && dec_tp_supported(d, w) && tpk.may_run(s);
   const bool tp_pro = tp_path && g_tp_prologue && !h_in && T > 1 && !d.film;
   if (tp_pro) {
     float* gin1 = w.Gin + sG;
@@ -615,52 +595,37 @@ static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, con
     }
   }
   // ---- batch-1 inference: the weight-stationary persistent kernel (one launch for all frames, decode_persistent.hip)
-  if (fast && !training && g_persistent && dec_persistent_state() != 0 && dec_persistent_supported(d, w)) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;   // a failed query must not read as "not capturing"
-    // the first use on a process is validated (device sync + error word); never inside a stream capture
-    if (cap == hipStreamCaptureStatusNone || dec_persistent_state() == 1) {
-      float* gin1 = w.Gin + slot(1) * sG;
-      hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1, 1,
-                         sG, 1);
-      ZLAUNCH_CHECK("dec_fill_cond");
-      ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
-      ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-      dec_timing_mark(0, s);
-      ZTRY(dec_persistent_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, gin1, w.H0 + slot(0) * sH,
-                              w.H1 + slot(0) * sH, w.H0 + slot(T - 1) * sH, w.H1 + slot(T - 1) * sH, s,
-                              dec_persistent_state() == 1 ? status : nullptr));
-      dec_timing_mark(1, s);
-      if (dec_persistent_state() == 1) return save_state();
-      unsigned perr = 1;
-      ZCHECK(hipStreamSynchronize(s) == hipSuccess, "persistent decode: stream sync failed");
-      ZTRY(dec_persistent_errors(w, &perr));
-      dec_persistent_set_state(perr == 0 ? 1 : 0);
-      if (perr == 0) return save_state();
-      // a bounded sweep gave up (not every workgroup resident?): disabled for this process, the stage kernels redo the rollout
-    }
+  SweepKernel& dpk = g_sweep_kernels[SWEEP_DECODE];
+  if (fast && !training && dec_persistent_supported(d, w) && dpk.may_run(s)) {
+    float* gin1 = w.Gin + slot(1) * sG;
+    hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1, 1,
+                       sG, 1);
+    ZLAUNCH_CHECK("dec_fill_cond");
+    ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
+    ZTRY(dec_fast_merge_prep(d, P, st, w, s));
+    dec_timing_mark(0, s);
+    ZTRY(dec_persistent_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, gin1, w.H0 + slot(0) * sH,
+                            w.H1 + slot(0) * sH, w.H0 + slot(T - 1) * sH, w.H1 + slot(T - 1) * sH, s, dpk.status_arg(status)));
+    dec_timing_mark(1, s);
+    bool ok = false;
+    ZTRY(dpk.settle(s, dp_errword(w), &ok));
+    if (ok) return save_state();
+    // a bounded sweep gave up: disabled for this process, the stage kernels redo the rollout
   }
   // ---- training, batch <= 32: the forward rollout as one persistent launch (train_persistent.hip)
   if (tp_path) {
-    {
-      float* gin1 = w.Gin + sG;
-      if (!tp_pro) ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
-      if (!fwd_prepared) {
-        ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-        ZTRY(dec_tp_pack(d, P, st, w, s));
-      }
-      dec_timing_mark(0, s);
-      // (the first, validated use reports through the workspace's own error word: a give-up there is handled right below)
-      ZTRY(dec_tp_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, s, fwd_prepared,
-                      dec_tp_state() == 1 ? status : nullptr, tp_pro));
-      dec_timing_mark(1, s);
-      if (dec_tp_state() == 1) return save_state();
-      unsigned perr = 1;
-      ZCHECK(hipStreamSynchronize(s) == hipSuccess, "persistent training rollout: stream sync failed");
-      ZTRY(dec_tp_errors(w, &perr));
-      dec_tp_set_state(perr == 0 ? 1 : 0);
-      if (perr == 0) return save_state();
+    float* gin1 = w.Gin + sG;
+    if (!tp_pro) ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
+    if (!fwd_prepared) {
+      ZTRY(dec_fast_merge_prep(d, P, st, w, s));
+      ZTRY(dec_tp_pack(d, P, st, w, s));
     }
+    dec_timing_mark(0, s);
+    ZTRY(dec_tp_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, s, fwd_prepared, tpk.status_arg(status), tp_pro));
+    dec_timing_mark(1, s);
+    bool ok = false;
+    ZTRY(tpk.settle(s, tp_errword(w), &ok));
+    if (ok) return save_state();
   }
   if (fast) {
     if (!training && T > 1) {
@@ -744,7 +709,8 @@ extern "C" size_t zeggs_decoder_batch_workspace_bytes(const ZeggsDecDims* d) {
 
 // bit 0: the sweep takes these dimensions; bit 1 (with bit 0): its GRU packs are 4-row tiles
 static int batch_sweep_mask(const ZeggsDecDims& d, const DecWs& w) {
-  if (!(g_decoder_fast && dec_fast_supported(d) && g_train_persistent && dec_tp_state() != 0 && dec_tb_supported(d, w))) return 0;
+  const SweepKernel& k = g_sweep_kernels[SWEEP_ROLLOUT];
+  if (!(g_decoder_fast && dec_fast_supported(d) && k.enabled && k.state != 0 && dec_tb_supported(d, w))) return 0;
   return 1 | (dec_tb_t4(w) ? 2 : 0);
 }
 
@@ -804,12 +770,8 @@ extern "C" int zeggs_decoder_fwd_batch(const ZeggsDecDims* dp, const ZeggsDecPar
   DecWs w = carve_dec_batch(d, a);
   ZCHECK(a.ok(), "decoder batch: workspace too small (%zu < %zu)", ws_bytes, a.off);
   unsigned* status = call ? call->status : nullptr;
-  int mask = mode == 0 ? batch_sweep_mask(d, w) : 0;
-  if (mask) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;
-    if (!(cap == hipStreamCaptureStatusNone || dec_tp_state() == 1)) mask = 0;
-  }
+  SweepKernel& tpk = g_sweep_kernels[SWEEP_ROLLOUT];
+  const int mask = mode == 0 && tpk.may_run(s) ? batch_sweep_mask(d, w) : 0;
   if (mask) {
     const int B = d.B, H = d.H, GL = w.GL, XD = w.XD;
     const long sG = (long)B * GL;
@@ -824,16 +786,12 @@ extern "C" int zeggs_decoder_fwd_batch(const ZeggsDecDims* dp, const ZeggsDecPar
       ZTRY(dec_fast_merge_prep(d, P, st, w, s));
       ZTRY(dec_tp_pack(d, P, st, w, s, (mask & 2) ? 1 : 0));
     }
-    const bool validated = dec_tp_state() == 1;
-    ZTRY(dec_tb_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, h_in, h_out, s, validated ? status : nullptr));
+    ZTRY(dec_tb_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, h_in, h_out, s, tpk.status_arg(status)));
     t_batch_last_path = 1;
-    if (validated) return 0;
-    unsigned perr = 1;
-    ZCHECK(hipStreamSynchronize(s) == hipSuccess, "persistent batch decode: stream sync failed");
-    ZTRY(dec_tp_errors(w, &perr));
-    dec_tp_set_state(perr == 0 ? 1 : 0);
-    if (perr == 0) return 0;
-    // a bounded wait gave up (not every workgroup resident?): disabled for this process, the stage launches redo the chunk
+    bool ok = false;
+    ZTRY(tpk.settle(s, tp_errword(w), &ok));
+    if (ok) return 0;
+    // a bounded wait gave up: disabled for this process, the stage launches redo the chunk
   }
   t_batch_last_path = 2;
   return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, 0, h_in, h_out, ws, ws_bytes,
@@ -888,12 +846,13 @@ extern "C" int zeggs_decoder_prepare(const ZeggsDecDims* dp, const ZeggsDecParam
   ZCHECK(a.ok(), "decoder prepare: workspace too small");
   const bool fast = g_decoder_fast && dec_fast_supported(d);
   // only once the kernels have been validated on this process (the first use takes the ordinary path)
-  if (!(fast && d.T > 1 && g_train_persistent && dec_tp_state() == 1 && dec_tp_supported(d, w))) return 0;
+  const SweepKernel &tpk = g_sweep_kernels[SWEEP_ROLLOUT], &bpk = g_sweep_kernels[SWEEP_BPTT];
+  if (!(fast && d.T > 1 && tpk.enabled && tpk.state == 1 && dec_tp_supported(d, w))) return 0;
   ZTRY(dec_fast_merge_prep(d, P, st, w, s));
   ZTRY(dec_tp_pack(d, P, st, w, s));
   ZTRY(dec_tp_zero(d, w, s));
   int mask = 1;
-  if (g_bwd_persistent && dec_bp_state() == 1 && dec_bp_supported(d, w)) {
+  if (bpk.enabled && bpk.state == 1 && dec_bp_supported(d, w)) {
     ZTRY(dec_bp_pack(d, P, w, s));
     // ... and the zero state the backward starts from (carries, frame-0 slot of DX, arrival slots + error word)
     ZTRY(k_fill(w.dH0c, (long)d.B * d.H, 0.f, s));
@@ -949,25 +908,14 @@ extern "C" int zeggs_decoder_bwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams
   const bool fast_path = g_decoder_fast && dec_fast_supported(d);
   // ---- batch <= 32: the whole sweep as one persistent launch (train_bwd_persistent.hip)
   bool swept = false;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess) cap = hipStreamCaptureStatusActive;   // a failed query must not read as "not capturing"
-  if (fast_path && g_bwd_persistent && dec_bp_state() != 0 && dec_bp_supported(d, w) &&
-      (cap == hipStreamCaptureStatusNone || dec_bp_state() == 1)) {
-    ZTRY(dec_bp_run(d, P, st, w, gaze, pose, rpos, rrot, dpose, drpos, drrot, s, bwd_prepared,
-                    dec_bp_state() == 1 ? status : nullptr));
-    if (dec_bp_state() == 1) {
-      swept = true;
-    } else {      // first use on this process: validate (a bounded wait that gave up means not every workgroup was resident)
-      unsigned perr = 1;
-      ZCHECK(hipStreamSynchronize(s) == hipSuccess, "persistent BPTT sweep: stream sync failed");
-      ZTRY(dec_bp_errors(w, &perr));
-      dec_bp_set_state(perr == 0 ? 1 : 0);
-      swept = perr == 0;
-      if (!swept) {   // the stage kernels redo the sweep from clean carries
-        ZTRY(k_fill(w.dH0c, sH, 0.f, s));
-        ZTRY(k_fill(w.dH1c, sH, 0.f, s));
-        ZTRY(k_fill(w.carry, (long)2 * B * 8, 0.f, s));
-      }
+  SweepKernel& bpk = g_sweep_kernels[SWEEP_BPTT];
+  if (fast_path && dec_bp_supported(d, w) && bpk.may_run(s)) {
+    ZTRY(dec_bp_run(d, P, st, w, gaze, pose, rpos, rrot, dpose, drpos, drrot, s, bwd_prepared, bpk.status_arg(status)));
+    ZTRY(bpk.settle(s, bp_errword(w), &swept));
+    if (!swept) {   // the stage kernels redo the sweep from clean carries
+      ZTRY(k_fill(w.dH0c, sH, 0.f, s));
+      ZTRY(k_fill(w.dH1c, sH, 0.f, s));
+      ZTRY(k_fill(w.carry, (long)2 * B * 8, 0.f, s));
     }
   }
   if (swept) {
@@ -1040,7 +988,8 @@ extern "C" int zeggs_decoder_bwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams
   // what the sweep saved) start NOW on the library's second stream, beside the CellStateEncoder backward below and whatever the
   // caller enqueues on `s` after this call (the encoders' backward).  No join here: the caller makes every consumer of the
   // decoder gradients wait for zeggs_side_stream.
-  if (!wgrads_done && defer_wgrads && cap == hipStreamCaptureStatusNone) {
+  const bool deferred = !wgrads_done && defer_wgrads && !stream_capturing(s);
+  if (deferred) {
     hipStream_t gs = (hipStream_t)call->wgrad_stream;
     hipEvent_t fork = nullptr;
     ZTRY(fork_event(&fork));
@@ -1067,7 +1016,7 @@ extern "C" int zeggs_decoder_bwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams
     ZTRY(gemm_nn_actbwd(db, H, P->c1_w, H, da, H, B, H, H, 0.f, w.cse_a, H, ACT_ELU, s));
     ZTRY(gemm_nn(da, H, P->c0_w, CI, w.t1, CI, B, H, CI, 0.f, s));   // t1 = d cse_in [B, PI+ST]
     hipStream_t ws_ = s;
-    if (!wgrads_done && defer_wgrads && cap == hipStreamCaptureStatusNone) {
+    if (deferred) {
       ws_ = (hipStream_t)call->wgrad_stream;
       hipEvent_t fork = nullptr;
       ZTRY(fork_event(&fork, 1));

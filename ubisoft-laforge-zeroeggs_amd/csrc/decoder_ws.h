@@ -142,14 +142,14 @@ inline DecWs carve_dec(const ZeggsDecDims& d, int training, Arena& a) {
       w.tp_w0 = a.f(256L * 8 * 26 * BLK); w.tp_w1 = a.f(256L * 8 * 16 * BLK); w.tp_w3 = a.f(256L * 8 * 9 * BLK);   // [wg][wave][block]
       w.G0xf = a.f(T * KB0 * XB); w.G1xf = a.f(T * 128 * XB); w.G3xf = a.f(T * KB3 * XB);
       w.tp_n0s = a.f(3 * H * (long)w.POL); w.tp_n0 = a.f(3 * H * H); w.tp_cv0 = a.f(3 * H); w.tp_p1x = a.f(B * 3 * H);
-      w.tp_cnt = (unsigned*)a.f(8192);      // arrival slots | error word (+1024) | stamps | wait statistics (+1536)
+      w.tp_cnt = (unsigned*)a.f(8192);      // arrival slots | error word (tp_errword) | stamps | wait statistics
     }
     if (d.H == 1024 && d.B <= 64 && !d.film) {
       w.bp_wr = a.f(256L * 8 * 113 * 64); w.bp_wl = a.f(256L * 8 * 64 * 64);
       w.bp_opy = a.f(T * (long)((d.PO + 15) / 16) * 512);
       w.bp_op1 = a.f(T * 4 * H * 32); w.bp_op0 = a.f(T * 4 * H * 32); w.bp_opd = a.f(T * H * 32);
       w.bp_sp = a.f(T * 9 * 32);
-      w.bp_cnt = (unsigned*)a.f(16384);      // arrival slots | error word (+1024) | stamps | per-workgroup wait statistics (+1536)
+      w.bp_cnt = (unsigned*)a.f(16384);      // arrival slots | error word (bp_errword) | stamps | per-workgroup wait statistics
     }
   }
   return w;
@@ -172,23 +172,46 @@ inline DecWs carve_dec_batch(const ZeggsDecDims& d, Arena& a) {
   return w;
 }
 
+// ---------------------------------------------------------------- the persistent sweeps' contract, host side
+// Every persistent kernel polls with a bounded wait and, on give-up, writes its workspace error word, ORs its bit into the caller's
+// sticky status word and poisons its outputs (sweep_sync.h).  Here: the option, the first-use state and the error word of each.
+// error words: behind the granule vectors h0 | h1 | hid (1024 each) | x pose columns (5 x 256) of the decode kernel; behind the
+// 1024 arrival slots of the rollout / the BPTT sweep, followed by the stamps (+32) and the wait statistics (+512) of measurement builds
+inline unsigned* dp_errword(const DecWs& w) { return (unsigned*)((unsigned long long*)w.pgran + 3 * 1024 + 5 * 256); }
+inline unsigned* tp_errword(const DecWs& w) { return w.tp_cnt + 1024; }
+inline unsigned* bp_errword(const DecWs& w) { return w.bp_cnt + 1024; }
+
+struct SweepKernel {
+  int enabled;            // the kernel's zeggs_set_option switch
+  int state;              // 1: validated on this process, 0: it failed once and is disabled, -1: not used yet
+  const char* what;       // its name in error messages
+  // (re-)enabling gives a kernel that was disabled after a failed validation another chance
+  void set_enabled(int v) { enabled = v; if (v && state == 0) state = -1; }
+  // The first use on a process is validated (stream sync + error word: settle), never inside a stream capture.
+  bool may_run(hipStream_t s) const;
+  // the first, validated use reports through the workspace's own error word; the caller's status word is for the later ones
+  unsigned* status_arg(unsigned* status) const { return state == 1 ? status : nullptr; }
+  // after the launch.  Validated: *ok = true, no host work.  First use: synchronise, read the error word; a bounded wait that gave
+  // up (not every workgroup resident?) disables the kernel for this process and the caller redoes the work on the stage kernels.
+  int settle(hipStream_t s, const unsigned* errword, bool* ok);
+};
+enum { SWEEP_DECODE = 0, SWEEP_ROLLOUT = 1, SWEEP_BPTT = 2 };      // the order of zeggs_persistent_state(which)
+extern SweepKernel g_sweep_kernels[3];    // options "persistent", "train_persistent" (training rollout and batch decode), "bwd_persistent"
+bool stream_capturing(hipStream_t s);      // a failed query reads as capturing
 extern int g_poll_sleep;           // s_sleep units (64 clocks) between two polls of the arrival slots (option "poll_sleep")
 extern int g_poll_stagger;         // != 0: two polls of the arrival slots in flight, this many s_sleep units apart (option "poll_stagger")
 extern int g_persistent_spin;      // bound of the device-side waits of the persistent kernels (option "persistent_spin")
+struct SweepSync;                  // sweep_sync.h
+SweepSync sweep_sync_args(unsigned* cnt, unsigned* err, unsigned* status);      // + the three tuning options above
+int require_cus(int n, const char* what);      // the sweeps are one workgroup per CU, all resident
 // persistent weight-stationary decode (decode_persistent.hip)
 int dec_persistent_supported(const ZeggsDecDims& d, const DecWs& w);
 int dec_persistent_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
                        const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* gin1,
                        const float* h0_init, const float* h1_init, float* h0_fin, float* h1_fin, hipStream_t s,
                        unsigned* status = nullptr);
-int dec_persistent_state();
-void dec_persistent_set_state(int v);
-int dec_persistent_errors(const DecWs& w, unsigned* out);
-int dec_persistent_errptr(const DecWs& w, unsigned** out);
 // persistent training rollout (train_persistent.hip)
 int dec_tp_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_tp_state();
-void dec_tp_set_state(int v);
 int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4 = -1);
 // batch decode on the same sweep (inference form of the kernel; zeggs_decoder_fwd_batch)
 int dec_tb_t4(const DecWs& w);
@@ -205,19 +228,13 @@ int dec_tp_prologue(const ZeggsDecDims& d, const ZeggsDecStats* st, DecWs& w, co
                     float* rrot, hipStream_t s, bool zeroed);
 struct GemmNtItem;
 GemmNtItem dec_tp_p1x_item(const ZeggsDecDims& d, const ZeggsDecParams* P, const DecWs& w);
-int dec_tp_errors(const DecWs& w, unsigned* out);
-int dec_tp_errptr(const DecWs& w, unsigned** out);
 // persistent BPTT sweep (train_bwd_persistent.hip)
 int dec_bp_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_bp_state();
-void dec_bp_set_state(int v);
 int dec_bp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStream_t s);
 int dec_bp_zero_slots(DecWs& w, hipStream_t s);      // weight tiles + operand pads (weights only)
 int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
                const float* pose, const float* rpos, const float* rrot, const float* dpose, const float* drpos,
                const float* drrot, hipStream_t s, bool packed = false, unsigned* status = nullptr);
-int dec_bp_errors(const DecWs& w, unsigned* out);
-int dec_bp_errptr(const DecWs& w, unsigned** out);
 // fast path entry points (decoder_fast.hip)
 int dec_fast_merge_prep(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s);
 void dec_timing_mark(int i, hipStream_t s);

@@ -4,10 +4,10 @@
 #pragma once
 #include "decoder_ws.h"
 #include "dec_math.h"
+#include "sweep_sync.h"
 
 namespace zeggs_tp {
 
-typedef __attribute__((address_space(1))) unsigned gu32;
 constexpr int TH = 1024, TTHR = 512, TNCU = 256;
 // k-blocks of a wave per phase: first the OLD part of the operand (known one phase earlier: previous hidden state,
 // speech / style columns), then the FRESH part (produced by the preceding phase).  Block j of a part is k-block
@@ -39,7 +39,6 @@ __host__ __device__ inline int tp_kb(int i, int wave, int NO, int old_lo, int ol
   const int kb = wave + 8 * (i - NO);
   return kb < fresh_hi ? kb : -1;
 }
-constexpr int TSH = 8, TSTR = 32, TRING = 4;
 
 struct TArgs {
   ZeggsDecDims d;
@@ -54,31 +53,13 @@ struct TArgs {
   const float *cv0, *p1x;                    // folded pose term of GRU layer 0: constant [3H], step-1 product [B][3H]
   const float* gaze;
   float *pose, *rpos, *rrot;
-  unsigned *cnt, *err;
-  unsigned* status;                          // caller-owned sticky give-up flags (ZeggsDecCall.status), may be null
-  unsigned spin;                             // bound of every wait (option "persistent_spin")
-  unsigned nap;                              // s_sleep units between two polls (option "poll_sleep")
-  unsigned stag;                             // != 0: two staggered polls in flight (option "poll_stagger")
+  SweepSync sync;
 };
 
-__device__ __forceinline__ void stp(float* p, float v) {       // published: write-through
-  __hip_atomic_store((gu32*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// 16 bytes, write-through: the four hidden units of this workgroup are four consecutive k of one batch row = one float4 of the
-// operand layout.  The "memory" clobber is required (results are corrupted without it) and makes the compiler drain the stores
-// it knows about first, so stp4 goes BEFORE the plain stores of an epilogue (train_bwd_persistent.hip).
-__device__ __forceinline__ void stp4(float* p, f4 v) {
-#ifdef ZEGGS_TP_NOSTP      // (timing experiment, results wrong: nothing is published)
-  asm volatile("" ::"v"(p), "v"(v) : "memory");
-#else
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#endif
-}
 __device__ __forceinline__ long xfi(int b, int k, int NB) {   // B-fragment position of (batch row, k)
   return ((((long)(k >> 4) * NB + (b >> 4)) * 64 + ((((k >> 2) & 3) << 4) | (b & 15))) << 2) | (k & 3);
 }
 
-typedef __attribute__((address_space(1))) unsigned long long gu64t;
 // Operand position of (batch row, k) for that instruction form: lane 32 * ((k >> 3) & 1) + (b & 31) reads float4 q = (k >> 2) & 1
 // of block k >> 4 (batch tile b >> 5), element k & 3 = abid & 3.  A block is 512 floats per 32 batch rows: the same size as two
 // 16-row tiles of the 16x16x4 layout, so the block offsets of the operand buffers do not change.

@@ -30,14 +30,10 @@
 #include "decoder_ws.h"
 #include "dec_math.h"
 #include "kernels.h"
-
-int g_bwd_persistent = 1;        // zeggs_set_option("bwd_persistent", 0/1)
-static int g_bp_ok = -1;
+#include "sweep_sync.h"
 
 namespace {
 
-typedef __attribute__((address_space(1))) unsigned gu32;
-typedef __attribute__((address_space(1))) unsigned long long gu64t;
 constexpr int BH = 1024, BTHR = 512, BNCU = 256;
 // blocks (16 k each) per wave and part; block j of a wave is enumeration index e = wave + 8 j of the part.  Every workgroup
 // streams the whole operand of a part through its CU (2 KB per block, ~90 GB/s per CU when all CUs read the same lines),
@@ -68,61 +64,13 @@ struct BArgs {
   float *DY, *DI1, *DH1, *DI0, *DH0, *D0, *DX, *dH0c, *dH1c;
   const float *dpose, *drpos, *drrot, *gaze, *pose, *rpos, *rrot;
   const float* carry;                        // root adjoint after frame T-1 [B][8]
-  unsigned *cnt, *err;
-  unsigned* status;                          // caller-owned sticky give-up flags (ZeggsDecCall.status), may be null
-  unsigned spin;                             // bound of every wait (option "persistent_spin")
-  unsigned nap;                              // s_sleep units between two polls (option "poll_sleep")
-  unsigned stag;                             // != 0: two staggered polls in flight (option "poll_stagger")
+  SweepSync sync;
 };
 
-__device__ __forceinline__ void stp(float* p, float v) {       // published: write-through
-  __hip_atomic_store((gu32*)p, __float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-// 16 bytes, write-through: one lane publishes 4 consecutive contraction indices (k % 4 == 0) of its batch row, a half-wave
-// of batch rows 512 contiguous bytes -- whole lines instead of byte-masked partial writes
-__device__ __forceinline__ void stp4(float* p, f4 v) {
-  // NOTE the "memory" clobber is required (without it the results are corrupted), and with it the compiler drains every store
-  // it knows to be in flight (s_waitcnt vmcnt(0): about a microsecond) before this one: call stp4 BEFORE the plain stores of an
-  // epilogue, never after them
-  asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-}
 // position of (batch row b, contraction index k) in an operand buffer: lane 32 * ((k >> 3) & 1) + b reads
 // float4 q = (k >> 2) & 1 of block k >> 4, element k & 3 (= abid & 3 of the instruction that consumes it)
 __host__ __device__ inline long op_idx(int b, int k) {
   return ((((long)(k >> 4) * 2 + ((k >> 2) & 1)) * 64 + ((((k >> 3) & 1) << 5) | b)) << 2) | (k & 3);
-}
-
-__device__ __forceinline__ bool bp_wait(const unsigned* slots, unsigned expect, unsigned limit, unsigned nap = 0) {
-  const int lane = threadIdx.x & 63;
-  const gu64t* q = (const gu64t*)(slots + 4 * lane);
-  for (unsigned spins = 0;; ++spins) {
-    const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool ok = (unsigned)a >= expect && (unsigned)(a >> 32) >= expect && (unsigned)b >= expect && (unsigned)(b >> 32) >= expect;
-    if (__all(ok)) return true;
-    if (spins >= limit) return false;
-    for (unsigned i = 0; i < nap; ++i) __builtin_amdgcn_s_sleep(1);
-  }
-}
-// two staggered samples in flight (train_persistent.hip: tp_wait2)
-__device__ __forceinline__ bool bp_wait2(const unsigned* slots, unsigned expect, unsigned limit, unsigned stagger) {
-  const int lane = threadIdx.x & 63;
-  const gu64t* q = (const gu64t*)(slots + 4 * lane);
-  auto all_in = [&](unsigned long long a, unsigned long long b) {
-    return __all((unsigned)a >= expect && (unsigned)(a >> 32) >= expect && (unsigned)b >= expect && (unsigned)(b >> 32) >= expect);
-  };
-  unsigned long long a0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  unsigned long long b0 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (unsigned i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(1);
-  for (unsigned spins = 0;; spins += 2) {
-    const unsigned long long a1 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (all_in(a0, b0)) return true;
-    a0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    b0 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (all_in(a1, b1)) return true;
-    if (spins >= limit) return false;
-  }
 }
 
 // products of one part: slot j = 0..NJ-1 of this wave is k-block kb0 + wave + 8 j (< kb0 + nblk) of the operand, NRG row groups;
@@ -350,7 +298,7 @@ __host__ __device__ inline int p4_row(int c, int s, int PO, int XD) {      // dx
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                             \
     __builtin_amdgcn_sched_barrier(0);                                                                      \
     if (t <= 3 && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1))                      \
-      ((unsigned long long*)(a.err + 32))[((3 - t) * 2 + (blockIdx.x != 0)) * 32 + (i)] = wall_clock64();     \
+      ((unsigned long long*)(a.sync.err + 32))[((3 - t) * 2 + (blockIdx.x != 0)) * 32 + (i)] = wall_clock64();     \
   } while (0)
 #else
 #define BPT(i) do {} while (0)
@@ -436,7 +384,7 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
       const unsigned long long w0 = wall_clock64();
 #endif
 #ifndef ZEGGS_BP_NOPOLL      // (timing experiment, results wrong: nobody waits for anybody -- the step as pure per-CU work)
-      if (wave == 1 && !(a.stag ? bp_wait2(a.cnt, (unsigned)(p + 1), a.spin, a.stag) : bp_wait(a.cnt, (unsigned)(p + 1), a.spin, a.nap))) fail = 1;     // (wave 0 of workgroup 0 prepares the root frame meanwhile)
+      if (wave == 1 && !(a.sync.stag ? slots_wait2(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, a.sync.stag) : slots_wait(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, true, a.sync.nap))) fail = 1;     // (wave 0 of workgroup 0 prepares the root frame meanwhile)
 #endif
 #ifdef ZEGGS_BPSTAT
       wsum[(p + 1) & 3] += wall_clock64() - w0;
@@ -447,7 +395,7 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
   auto arrive = [&](long p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) __hip_atomic_store((gu32*)(a.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store((gu32*)(a.sync.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   // wave partial sums -> red[wave][row0 + 4 rg + i][batch]  (the two k-halves of the accumulator lanes are added first)
   auto put = [&](const f4& v, int row0) {
@@ -737,21 +685,18 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
   }
 #ifdef ZEGGS_BPSTAT
   if (tid == 64) {      // wave 1 polls
-    unsigned long long* o = (unsigned long long*)(a.err + 512) + 4 * c;
+    unsigned long long* o = (unsigned long long*)(a.sync.err + 512) + 4 * c;
     for (int i = 0; i < 4; ++i) o[i] = wsum[i];
-    unsigned long long* o2 = (unsigned long long*)(a.err + 512) + 4 * 256 + 4 * c;
+    unsigned long long* o2 = (unsigned long long*)(a.sync.err + 512) + 4 * 256 + 4 * c;
     for (int i = 0; i < 4; ++i) o2[i] = esum[i];
   }
   if (tid == 0) {
-    unsigned long long* o3 = (unsigned long long*)(a.err + 512) + 8 * 256 + 8 * c;
+    unsigned long long* o3 = (unsigned long long*)(a.sync.err + 512) + 8 * 256 + 8 * c;
     for (int i = 0; i < 6; ++i) o3[i] = q4[i];
   }
 #endif
   if (fail) {     // a bounded wait gave up: error word, the caller's sticky status, NaN in the carries the CellStateEncoder backward reads
-    if (tid == 0) {
-      atomicOr(a.err, 1u);
-      if (a.status) atomicOr(a.status, ZEGGS_GAVE_UP_BPTT);
-    }
+    if (tid == 0) sweep_gave_up(a.sync, ZEGGS_GAVE_UP_BPTT);
     if (er < 4 && bact) {
       const float qnan = __uint_as_float(0x7fc00000u);
       a.dH1c[(long)eb * H + U] = qnan;
@@ -848,8 +793,6 @@ int dec_bp_supported(const ZeggsDecDims& d, const DecWs& w) {
   return !d.film && d.H == BH && d.B <= 64 && d.T >= 3 && d.PI == d.PO + 3 && d.PO >= 16 && (d.PO + 15) / 16 <= 8 * NJ1 &&
          w.XD <= 8 * BNCU && w.bp_wr != nullptr;
 }
-int dec_bp_state() { return g_bp_ok; }
-void dec_bp_set_state(int v) { g_bp_ok = v; }
 
 // the whole sweep t = T-1 .. 1; leaves DY, DI*, DH*, D0, DX (speech / style columns), dH0c, dH1c as the stage sweep does
 // what depends on the weights and the dimensions only (zeggs_decoder_prepare runs it ahead of the forward, on a second stream)
@@ -863,17 +806,14 @@ int dec_bp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStr
   ZTRY(k_fill(w.bp_opy, (long)T * KBY * 512, 0.f, s));
   return 0;
 }
-int dec_bp_zero_slots(DecWs& w, hipStream_t s) {        // arrival slots + error word
-  return k_fill((float*)w.bp_cnt, 2048, 0.f, s);
+int dec_bp_zero_slots(DecWs& w, hipStream_t s) {        // arrival slots + error word (and the stamps behind it)
+  return k_fill((float*)w.bp_cnt, bp_errword(w) - w.bp_cnt + 1024, 0.f, s);
 }
 int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
                const float* pose, const float* rpos, const float* rrot, const float* dpose, const float* drpos,
                const float* drrot, hipStream_t s, bool packed, unsigned* status) {
   const int B = d.B, T = d.T, H = d.H, KBY = (d.PO + 15) / 16;
-  int dev = 0, ncu = 0;
-  ZCHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
-  ZCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess, "device query failed");
-  ZCHECK(ncu >= BNCU, "persistent BPTT sweep needs %d CUs (device has %d)", BNCU, ncu);
+  ZTRY(require_cus(BNCU, "persistent BPTT sweep"));
   if (!packed) ZTRY(dec_bp_pack(d, P, w, s));
   float* dyl = w.DY + (long)(T - 1) * B * w.POL;
   hipLaunchKernelGGL(bp_dy_last_k, dim3(B), dim3(256), 0, s, d, *st, dpose, drpos, drrot, gaze, pose, rpos, rrot, w.carry,
@@ -900,8 +840,7 @@ int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
     a.dpose = dpose + o * T * d.PO; a.drpos = drpos + o * T * 3; a.drrot = drrot + o * T * 4; a.gaze = gaze + o * T * 3;
     a.pose = pose + o * T * d.PO; a.rpos = rpos + o * T * 3; a.rrot = rrot + o * T * 4;
     a.carry = w.carry + o * 8;
-    a.cnt = w.bp_cnt; a.err = w.bp_cnt + 1024;
-    a.status = status; a.spin = (unsigned)g_persistent_spin; a.nap = (unsigned)g_poll_sleep; a.stag = (unsigned)g_poll_stagger;
+    a.sync = sweep_sync_args(w.bp_cnt, bp_errword(w), status);
     hipLaunchKernelGGL(train_bwd_persistent_k, dim3(BNCU), dim3(BTHR), 0, s, a);
     ZLAUNCH_CHECK("train_bwd_persistent");
   }
@@ -913,7 +852,7 @@ extern "C" int zeggs_bp_stamps(const ZeggsDecDims* dp, void* ws, size_t ws_bytes
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(*dp, 1, a);
   ZCHECK(a.ok() && w.bp_cnt, "bp_stamps: workspace");
-  ZCHECK(hipMemcpy(out, w.bp_cnt + 1024 + 32, 3 * 2 * 32 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
+  ZCHECK(hipMemcpy(out, bp_errword(w) + 32, 3 * 2 * 32 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
   return 0;
 }
 // -DZEGGS_BPSTAT builds: 100 MHz ticks every workgroup spent polling for the hand-off INTO phase P1..P4, summed over the sweep
@@ -921,15 +860,6 @@ extern "C" int zeggs_bp_waits(const ZeggsDecDims* dp, void* ws, size_t ws_bytes,
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(*dp, 1, a);
   ZCHECK(a.ok() && w.bp_cnt, "bp_waits: workspace");
-  ZCHECK(hipMemcpy(out, w.bp_cnt + 1024 + 512, 4 * 256 * 4 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
-  return 0;
-}
-int dec_bp_errptr(const DecWs& w, unsigned** out) {
-  *out = w.bp_cnt + 1024;
-  return 0;
-}
-int dec_bp_errors(const DecWs& w, unsigned* out) {
-  ZCHECK(hipMemcpy(out, w.bp_cnt + 1024, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess,
-         "persistent BPTT sweep: error word copy failed");
+  ZCHECK(hipMemcpy(out, bp_errword(w) + 512, 4 * 256 * 4 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
   return 0;
 }

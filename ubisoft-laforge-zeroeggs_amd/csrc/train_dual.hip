@@ -110,7 +110,7 @@ __device__ __forceinline__ f4 dc_fold(const f4 (&acc)[4]) {
   do {                                                                                                                    \
     __builtin_amdgcn_sched_barrier(0);                                                                                    \
     if (t == T - 2 && lane == 0 && (c == 0 || c == TNCU - 1))                                                             \
-      ((unsigned long long*)(a.cnt + 4096))[(((c != 0) * 8 + wave) * 6 + (SLOT)) * 6 + (I)] = wall_clock64();            \
+      ((unsigned long long*)(a.sync.cnt + 4096))[(((c != 0) * 8 + wave) * 6 + (SLOT)) * 6 + (I)] = wall_clock64();            \
     __builtin_amdgcn_sched_barrier(0);                                                                                    \
   } while (0)
 #else
@@ -210,8 +210,8 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
       const bool ok = (unsigned)fa >= expect && (unsigned)(fa >> 32) >= expect && (unsigned)fb >= expect && (unsigned)(fb >> 32) >= expect &&
                       *ve >= expect;
       if (__all(ok)) return true;
-      if (spins >= a.spin || *vfail) return false;
-      for (unsigned i = 0; i < a.nap; ++i) __builtin_amdgcn_s_sleep(1);
+      if (spins >= a.sync.spin || *vfail) return false;
+      for (unsigned i = 0; i < a.sync.nap; ++i) __builtin_amdgcn_s_sleep(1);
       ld_flags(q, fa, fb);
     }
   };
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
   auto arrive = [&](int X, long p) {         // everything this wave published is on its way past the L2: raise the chain's flag
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     if (lane == 0)
-      __hip_atomic_store((gu32*)(a.cnt + X * 256 + fcls * 32 + fidx), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store((gu32*)(a.sync.cnt + X * 256 + fcls * 32 + fidx), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
 
   // operand of (phase, step, chain) as a uniform byte address
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
     asm volatile("" : "+v"(loff));
     int wv = wave;                       // (opaque copies: the block offsets are cheap scalar arithmetic, not live scalar pairs)
     asm volatile("" : "+s"(wv));
-    const gu64t* q = (const gu64t*)(a.cnt + X * 256 + wv * 32 + 4 * (loff >> 4 & 7));
+    const gu64t* q = (const gu64t*)(a.sync.cnt + X * 256 + wv * 32 + 4 * (loff >> 4 & 7));
     DCT(SL, 1);
     if (p > 0 && !wait_arrival(X, q, p - 1, fa, fb)) return false;
     DCT(SL, 2);
@@ -274,7 +274,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
       constexpr int J = decltype(JC)::value;
       dc_issue<PH, NO + J>(xr[J], base, loff, wv, a.KB3);
     });
-    const gu64t* qn = (const gu64t*)(a.cnt + XN * 256 + wv * 32 + 4 * (loff >> 4 & 7));
+    const gu64t* qn = (const gu64t*)(a.sync.cnt + XN * 256 + wv * 32 + 4 * (loff >> 4 & 7));
     ld_flags(qn, fa, fb);
     __builtin_amdgcn_sched_barrier(0);
     return true;
@@ -540,10 +540,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
   if (!okrun) *vfail = 1;
   __syncthreads();
   if (fail) {     // a bounded wait gave up: error word, the caller's sticky status, NaN in the last frame of every output row
-    if (tid == 0) {
-      atomicOr(a.err, 1u);
-      if (a.status) atomicOr(a.status, ZEGGS_GAVE_UP_TRAIN_FWD);
-    }
+    if (tid == 0) sweep_gave_up(a.sync, ZEGGS_GAVE_UP_TRAIN_FWD);
     const float qnan = __uint_as_float(0x7fc00000u);
     for (int i = c * TTHR + tid; i < B * PO; i += TNCU * TTHR) a.pose[((long)(i / PO) * T + T - 1) * PO + i % PO] = qnan;
     if (c == 0 && tid < B) { a.rpos[((long)tid * T + T - 1) * 3] = qnan; a.rrot[((long)tid * T + T - 1) * 4] = qnan; }

@@ -24,54 +24,10 @@
 #include "gemm.h"
 #include "kernels.h"
 
-int g_train_persistent = 1;      // zeggs_set_option("train_persistent", 0/1)
 int g_tp_tiles4 = 1;             // zeggs_set_option("tp_tiles4", 0/1): the GRU phases of the training rollout on 4-row tiles (even batch-tile counts)
-static int g_tp_ok = -1;
 
 using namespace zeggs_tp;
 namespace {
-
-// Arrival slots: workgroup c publishes "I have finished phase instance p" by storing p + 1 into slot[c] (a write-through
-// store, no read-modify-write to serialise); a consumer's wave 0 loads all 256 slots with one 16-byte load per lane and
-// waits until every slot has reached p + 1.  Epochs are monotonic and a workgroup can run at most one phase ahead of the
-// slowest one, so one 1 KB array serves every phase.  Returns false on give-up.
-// `mine` (per lane): this lane's four slots = the four workgroups that produce k-block `lane` of every exchanged vector (workgroup c
-// owns hidden units 4c .. 4c+3 = a quarter of block c / 4) matter to the calling wave; a wave waits for the producers of ITS
-// k-blocks only (wave + 8 j: the lanes with lane % 8 == wave), the eight waves of a workgroup together for everybody.
-__device__ __forceinline__ bool tp_wait(const unsigned* slots, unsigned expect, unsigned limit, bool mine = true, unsigned nap = 0) {
-  const int lane = threadIdx.x & 63;
-  const gu64t* q = (const gu64t*)(slots + 4 * lane);
-  for (unsigned spins = 0;; ++spins) {
-    const unsigned long long a = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool ok = !mine || ((unsigned)a >= expect && (unsigned)(a >> 32) >= expect && (unsigned)b >= expect && (unsigned)(b >> 32) >= expect);
-    if (__all(ok)) return true;
-    if (spins >= limit) return false;
-    for (unsigned i = 0; i < nap; ++i) __builtin_amdgcn_s_sleep(1);
-  }
-}
-// Two samples of the slots in flight, half a round trip apart (option "poll_stagger" = that half in s_sleep units, 0 = off): a
-// producer's flag is seen by the first sample issued after it landed, i.e. after a quarter of a round trip on average instead of
-// half of one (the round trip of a load that misses every cache is ~0.9 us: the dominant term of a hand-off).
-__device__ __forceinline__ bool tp_wait2(const unsigned* slots, unsigned expect, unsigned limit, unsigned stagger) {
-  const int lane = threadIdx.x & 63;
-  const gu64t* q = (const gu64t*)(slots + 4 * lane);
-  auto all_in = [&](unsigned long long a, unsigned long long b) {
-    return __all((unsigned)a >= expect && (unsigned)(a >> 32) >= expect && (unsigned)b >= expect && (unsigned)(b >> 32) >= expect);
-  };
-  unsigned long long a0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  unsigned long long b0 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  for (unsigned i = 0; i < stagger; ++i) __builtin_amdgcn_s_sleep(1);
-  for (unsigned spins = 0;; spins += 2) {
-    const unsigned long long a1 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long b1 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (all_in(a0, b0)) return true;
-    a0 = __hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    b0 = __hip_atomic_load(q + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (all_in(a1, b1)) return true;
-    if (spins >= limit) return false;
-  }
-}
 
 // products of one part of a phase: blocks j = 0..NJ-1 of this wave are k-blocks kb0 + 8 j (< hi), their weights wr[OFF + j]
 // (registers) or wl[(OFF + j) * 64] (LDS).  Two blocks per group, the next group's activation loads in flight while this
@@ -199,7 +155,7 @@ __device__ __forceinline__ void tp_mma4(const float (&wq)[NW], const float* wl, 
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                             \
     __builtin_amdgcn_sched_barrier(0);                                                                      \
     if (t >= T - 4 && threadIdx.x == 0 && (blockIdx.x == 0 || blockIdx.x == gridDim.x - 1)) {                \
-      unsigned long long* sl_ = (unsigned long long*)(a.err + 32) + ((t - (T - 4)) * 2 + (blockIdx.x != 0)) * 32; \
+      unsigned long long* sl_ = (unsigned long long*)(a.sync.err + 32) + ((t - (T - 4)) * 2 + (blockIdx.x != 0)) * 32; \
       sl_[(i)] = wall_clock64();                                                                            \
       if ((i) == 0 || (i) == 15) sl_[16 + ((i) == 15)] = clock64();   /* shader-clock cycles of the step */  \
     }                                                                                                       \
@@ -468,10 +424,10 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
 #if ZEGGS_TP_WAVEWAIT
       // every wave for the producers of its own k-blocks: no barrier, no broadcast; a give-up is noticed by everybody behind the
       // phase's reduction barrier (`fail` is checked there: all waves of a workgroup must meet the same barriers)
-      if (!tp_wait(a.cnt, (unsigned)(p + 1), a.spin, (lane & 7) == wave)) fail = 1;
+      if (!slots_wait(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, (lane & 7) == wave)) fail = 1;
 #else
 #ifndef ZEGGS_TP_NOPOLL      // (timing experiment, results wrong: nobody waits for anybody -- the step as pure per-CU work)
-      if (wave == 0 && !(a.stag ? tp_wait2(a.cnt, (unsigned)(p + 1), a.spin, a.stag) : tp_wait(a.cnt, (unsigned)(p + 1), a.spin, true, a.nap))) fail = 1;
+      if (wave == 0 && !(a.sync.stag ? slots_wait2(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, a.sync.stag) : slots_wait(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, true, a.sync.nap))) fail = 1;
 #endif
 #endif
 #ifdef ZEGGS_TPSTAT
@@ -485,7 +441,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
   auto arrive = [&](long p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (tid == 0) __hip_atomic_store((gu32*)(a.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 0) __hip_atomic_store((gu32*)(a.sync.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   };
   // GRU phases in the 4-row form with one batch tile: wave 0 is the only publisher.  Experiment (-DZEGGS_TP_W0ARRIVE=1 / 2): it raises
   // the flag alone, without the workgroup barrier, so that the other seven waves run the next phase's old-operand products beside
@@ -494,7 +450,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     if constexpr (ZEGGS_TP_W0ARRIVE != 0 && T4 && NT == 1) {
       if (wave == 0) {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) __hip_atomic_store((gu32*)(a.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) __hip_atomic_store((gu32*)(a.sync.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (ZEGGS_TP_W0ARRIVE == 2) __builtin_amdgcn_s_setprio(0);
       }
     } else arrive(p);
@@ -838,15 +794,12 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
   }
 #ifdef ZEGGS_TPSTAT
   if (tid == 0) {
-    unsigned long long* o = (unsigned long long*)(a.err + 512) + 4 * c;
+    unsigned long long* o = (unsigned long long*)(a.sync.err + 512) + 4 * c;
     for (int i = 0; i < 3; ++i) o[i] = wsum[i];
   }
 #endif
   if (fail) {     // a bounded wait gave up: error word, the caller's sticky status, NaN in the last frame of every output row
-    if (tid == 0) {
-      atomicOr(a.err, 1u);
-      if (a.status) atomicOr(a.status, INF ? ZEGGS_GAVE_UP_BATCH_FWD : ZEGGS_GAVE_UP_TRAIN_FWD);
-    }
+    if (tid == 0) sweep_gave_up(a.sync, INF ? ZEGGS_GAVE_UP_BATCH_FWD : ZEGGS_GAVE_UP_TRAIN_FWD);
     const float qnan = __uint_as_float(0x7fc00000u);
     for (int i = c * TTHR + tid; i < B * PO; i += TNCU * TTHR) a.pose[((long)(i / PO) * T + T - 1) * PO + i % PO] = qnan;
     if (c == 0 && tid < B) { a.rpos[((long)tid * T + T - 1) * 3] = qnan; a.rrot[((long)tid * T + T - 1) * 4] = qnan; }
@@ -1012,8 +965,6 @@ void tp_dual_launch(const TArgs& a, hipStream_t s);
 // 32-row layout (the dual-chain kernel reads 16-row tiles: tile = chain)
 static bool tp_pack_t4(const DecWs& w) { return tp_dual_supported(w.NB) || (g_tp_tiles4 && w.NB % 2 == 0); }
 static bool tp_use_t4(const DecWs& w) { return !tp_dual_supported(w.NB) && g_tp_tiles4 && w.NB % 2 == 0; }
-int dec_tp_state() { return g_tp_ok; }
-void dec_tp_set_state(int v) { g_tp_ok = v; }
 
 // once per optimizer step: the per-workgroup fragment packs (needs Mc / cvec: dec_fast_merge_prep)
 int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4) {
@@ -1092,10 +1043,7 @@ int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
                unsigned* status, bool prologue_done) {
   const int B = d.B, H = d.H, NB = w.NB, KB0 = TKB0, KB3 = 64 + w.KBC;
   const long XB = 256L * NB, sG = (long)B * w.GL;
-  int dev = 0, ncu = 0;
-  ZCHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
-  ZCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess, "device query failed");
-  ZCHECK(ncu >= TNCU, "persistent training rollout needs %d CUs (device has %d)", TNCU, ncu);
+  ZTRY(require_cus(TNCU, "persistent training rollout"));
   // operand buffers: zero (pad rows / pad columns must be finite), then the inputs that do not depend on the rollout
   // (only the blocks with pad columns: the gaze + speech / style blocks of G0, the cond blocks of G3, the h1 slot of step 1)
   if (!zeroed && !prologue_done) ZTRY(dec_tp_zero(d, w, s));
@@ -1122,8 +1070,7 @@ int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
   a.Gin = w.Gin; a.H0 = w.H0; a.H1 = w.H1; a.GT0 = w.GT0; a.GT1 = w.GT1;
   a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1; a.cvec = w.cvec; a.l0_w = P->l0_w;
   a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x; a.gaze = gaze; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
-  a.cnt = w.tp_cnt; a.err = w.tp_cnt + TRING * TSH * TSTR;
-  a.status = status; a.spin = (unsigned)g_persistent_spin; a.nap = (unsigned)g_poll_sleep; a.stag = (unsigned)g_poll_stagger;
+  a.sync = sweep_sync_args(w.tp_cnt, tp_errword(w), status);
   if (tp_dual_supported(NB)) {
     tp_dual_launch(a, s);
     ZLAUNCH_CHECK("train_fwd_dual");
@@ -1147,10 +1094,7 @@ int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
                hipStream_t s, unsigned* status) {
   const int B = d.B, H = d.H, NB = w.NB, KB0 = TKB0, KB3 = 64 + w.KBC;
   const long XB = 256L * NB, sG = (long)B * w.GL, sH = (long)B * H;
-  int dev = 0, ncu = 0;
-  ZCHECK(hipGetDevice(&dev) == hipSuccess, "hipGetDevice failed");
-  ZCHECK(hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess, "device query failed");
-  ZCHECK(ncu >= TNCU, "persistent batch decode needs %d CUs (device has %d)", TNCU, ncu);
+  ZTRY(require_cus(TNCU, "persistent batch decode"));
   const int t4 = dec_tb_t4(w);
   ZTRY(dec_tp_zero(d, w, s));
   hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4, 1);
@@ -1173,8 +1117,7 @@ int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
   a.Gin = w.Gin; a.H0 = (float*)h_in; a.H1 = (float*)h_in + sH; a.Hout0 = h_out; a.Hout1 = h_out + sH;
   a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1; a.cvec = w.cvec; a.l0_w = P->l0_w;
   a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x; a.gaze = gaze; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
-  a.cnt = w.tp_cnt; a.err = w.tp_cnt + TRING * TSH * TSTR;
-  a.status = status; a.spin = (unsigned)g_persistent_spin; a.nap = (unsigned)g_poll_sleep; a.stag = (unsigned)g_poll_stagger;
+  a.sync = sweep_sync_args(w.tp_cnt, tp_errword(w), status);
   tp_launch<true>(a, NB, t4, s);
   ZLAUNCH_CHECK("batch_fwd_persistent");
   return 0;
@@ -1183,7 +1126,7 @@ extern "C" int zeggs_tp_stamps(const ZeggsDecDims* dp, void* ws, size_t ws_bytes
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(*dp, 1, a);
   ZCHECK(a.ok() && w.tp_cnt, "tp_stamps: workspace");
-  ZCHECK(hipMemcpy(out, w.tp_cnt + TRING * TSH * TSTR + 32, 4 * 2 * 32 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
+  ZCHECK(hipMemcpy(out, tp_errword(w) + 32, 4 * 2 * 32 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
   return 0;
 }
 // -DZEGGS_TPSTAT builds: 100 MHz ticks every workgroup spent polling for the hand-off into phase 1..3, summed over the rollout
@@ -1191,15 +1134,6 @@ extern "C" int zeggs_tp_waits(const ZeggsDecDims* dp, void* ws, size_t ws_bytes,
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(*dp, 1, a);
   ZCHECK(a.ok() && w.tp_cnt, "tp_waits: workspace");
-  ZCHECK(hipMemcpy(out, w.tp_cnt + TRING * TSH * TSTR + 512, 256 * 4 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
-  return 0;
-}
-int dec_tp_errptr(const DecWs& w, unsigned** out) {
-  *out = w.tp_cnt + TRING * TSH * TSTR;
-  return 0;
-}
-int dec_tp_errors(const DecWs& w, unsigned* out) {
-  ZCHECK(hipMemcpy(out, w.tp_cnt + TRING * TSH * TSTR, sizeof(unsigned), hipMemcpyDeviceToHost) == hipSuccess,
-         "persistent training rollout: error word copy failed");
+  ZCHECK(hipMemcpy(out, tp_errword(w) + 512, 256 * 4 * 8, hipMemcpyDeviceToHost) == hipSuccess, "copy");
   return 0;
 }
