@@ -433,6 +433,13 @@ int zeggs_radam_step_guarded_part(float* p, const float* g, float* m, float* v, 
 int zeggs_radam_step_wd(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float eps,
                         float step_scale, int rectified, float decay, unsigned* status, const float* gflag, int count_skip,
                         void* stream);
+/* the general form with the complements from the caller: comp1 = (float)(1 - beta1), comp2 = (float)(1 - beta2) formed in DOUBLE,
+ * as the reference forms them (optimizers.py:61-62 passes the Python double 1 - beta2 = 0.001 as the kernel scalar; formed in
+ * float, 1.f - 0.999f = 0.00099998713 is 1.3e-5 relative off in exp_avg_sq at every step).  The four entry points above keep
+ * their signatures and forward 1.f - beta; a caller that compares moments or checkpoints with the reference uses this one. */
+int zeggs_radam_step_c(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float comp1, float comp2,
+                       float eps, float step_scale, int rectified, float decay, unsigned* status, const float* gflag,
+                       int count_skip, void* stream);
 int zeggs_status_flag(const unsigned* status, float* dst /* device float */, void* stream);
 /* measurement / test hook (no reference counterpart): `workgroups` x `threads` resident for `ms` milliseconds of wall clock on
  * `stream`, touching `scratch[0..n)` lightly (may be NULL) -- the stand-in for a collective's resident workgroups that

@@ -371,6 +371,61 @@ def gold_radam(ref):
     print("radam_wd.npz")
 
 
+RADAM_STEPS_SHAPES = ((7,), (12, 31), (257,))
+RADAM_STEPS_CONFIGS = (dict(lr=(1e-4,)), dict(lr=(1e-2,), weight_decay=0.05), dict(lr=(1e-2,), degenerated_to_sgd=False),
+                       dict(lr=(1e-2, 3e-3), betas=((0.9, 0.999), (0.8, 0.99)), group_of=(0, 1, 0)))
+
+
+def gold_radam_steps(ref):
+    """The unmodified reference RAdam over 12 steps -- past the rectification boundary (step 6) -- on three tensors with the
+    gradients of oracle.radam.recipe (|g| log-uniform in 1e-9 ... 10, eight elements never touched, eight more missing one
+    step), eps = 1e-5 as training runs it, lr x 0.995 before step 9 set on param_groups as train.py:166-172 does; four
+    configurations (plain, weight_decay, degenerated_to_sgd=False, two parameter groups with their own lr and betas).
+    p, exp_avg and exp_avg_sq after every step."""
+    from oracle import radam as oradam
+    steps, eps, decay_before, decay = 12, 1e-5, 9, 0.995
+    sizes = [int(np.prod(s)) for s in RADAM_STEPS_SHAPES]
+    p0, grads, never, once = oradam.recipe(sum(sizes), steps, seed=20)
+    offs = np.concatenate([[0], np.cumsum(sizes)])
+    cut = lambda a, t: a[..., offs[t]:offs[t + 1]].reshape(a.shape[:-1] + RADAM_STEPS_SHAPES[t])  # noqa: E731
+    assert (never < sizes[0]).any() and (never >= offs[2]).any()
+    out = dict(steps=np.int64(steps), eps=np.float64(eps), decay_before_step=np.int64(decay_before), lr_decay=np.float64(decay),
+               never=never, once=np.array(once, dtype=np.int64), n_configs=np.int64(len(RADAM_STEPS_CONFIGS)))
+    for t in range(len(sizes)):
+        out[f"p0_{t}"], out[f"g_{t}"] = cut(p0, t), cut(grads, t)
+    for c, conf in enumerate(RADAM_STEPS_CONFIGS):
+        group_of = conf.get("group_of", (0,) * len(sizes))
+        betas = conf.get("betas", ((0.9, 0.999),) * len(conf["lr"]))
+        ps = [torch.nn.Parameter(torch.as_tensor(out[f"p0_{t}"].copy())) for t in range(len(sizes))]
+        groups = [dict(params=[q for q, gi in zip(ps, group_of) if gi == k], lr=conf["lr"][k], betas=betas[k])
+                  for k in range(len(conf["lr"]))]
+        opt = ref.optimizers.RAdam(groups, eps=eps, weight_decay=conf.get("weight_decay", 0),
+                                   degenerated_to_sgd=conf.get("degenerated_to_sgd", True))
+        rec = {k: [[] for _ in ps] for k in "pmv"}
+        for s in range(steps):
+            if s + 1 == decay_before:
+                for grp in opt.param_groups:
+                    grp["lr"] *= decay
+            for t, q in enumerate(ps):
+                q.grad = torch.as_tensor(out[f"g_{t}"][s].copy())
+            opt.step()
+            for t, q in enumerate(ps):
+                rec["p"][t].append(q.detach().clone().numpy())
+                rec["m"][t].append(opt.state[q]["exp_avg"].clone().numpy())
+                rec["v"][t].append(opt.state[q]["exp_avg_sq"].clone().numpy())
+        out[f"c{c}_lr"], out[f"c{c}_betas"] = np.array(conf["lr"], dtype=np.float64), np.array(betas, dtype=np.float64)
+        out[f"c{c}_group_of"] = np.array(group_of, dtype=np.int64)
+        out[f"c{c}_weight_decay"] = np.float64(conf.get("weight_decay", 0))
+        out[f"c{c}_degenerated_to_sgd"] = np.bool_(conf.get("degenerated_to_sgd", True))
+        for k in "pmv":
+            for t in range(len(sizes)):
+                out[f"c{c}_{k}_{t}"] = np.stack(rec[k][t])
+    np.savez_compressed(GOLD / "radam_steps.npz", **out)
+    size = (GOLD / "radam_steps.npz").stat().st_size
+    assert size < 500_000, size
+    print("radam_steps.npz", size)
+
+
 def gold_generate(ref):
     """Reference generate_gesture() end to end (CPU): 2 s synthetic wav, synthetic 75-joint exemplar BVH written by
     the reference's bvh.save, random-init nets (seed 1234) pickled as whole modules.  temperature = 1e8 makes the
@@ -1008,6 +1063,8 @@ def main():
         gold_dataset(ref)
     if "radam" in which:
         gold_radam(ref)
+    if "radam" in which or "radam_steps" in which:
+        gold_radam_steps(ref)
     if "anim_orders" in which:
         gold_anim_orders(ref)
     if "generate" in which:

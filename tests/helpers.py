@@ -1008,3 +1008,148 @@ DEC_INFER_KINDS = ("tied", "untied", "still", "brisk", "spin", "zero")
 def decoder_shapes():
     """every (decoder, B, T) the GPU file runs"""
     return sorted({c[1:] for c in DEC_TRAIN_CASES} | {("main", B, T) for _, B, T in DEC_INFER_CASES})
+
+
+# ---- RAdam (tests/test_radam_oracle_cpu.py measures and proves on the CPU, tests/test_gpu_radam.py runs the device).
+# Errors are counted in float32 ROUNDINGS: |got - float64 oracle| / (2^-24 * scale), per element and step, every scale taken from
+# the float64 oracle -- v: v itself; m: the same moving average taken over |g|; p: |p0| + sum_t |p_t - p_{t-1}| (+ RADAM_UNDERFLOW,
+# below).  Where a scale is zero (an element that never saw a gradient) the value must be EXACTLY the oracle's.
+# RADAM_REF_ROUNDINGS: the worst distance of the reference's own float32 run (tests/golden/radam_steps.npz: 4 configurations, 3
+# tensors, 12 steps) from the float64 oracle, as test_radam_oracle_cpu.py::test_yardstick_reference_float32_run_vs_float64_oracle
+# measures it on the committed fixture.  RADAM_BOUND = 4 x that, per array, is what every device comparison allows: the margin
+# covers the kernel's FMA contraction and its other order of the same few operations per step (division and sqrtf are correctly
+# rounded on both sides).
+# RADAM_UNDERFLOW: float32 has no rounding finer than its smallest normal number, 2^-126 -- below it results lose bits or (on the
+# device, which flushes denormals) become zero, so (1 - beta2) g g carries an absolute error of up to 2^-126 however small v is.
+# Every non-zero scale therefore gets 2^-126 * 2^24 added: one "rounding" is never less than 2^-126.  That reaches only v < 2e-31,
+# |g| < 1e-14 -- real gradients have such entries (the engine test met v = 0 against 1e-50), the recipe's (|g| >= 1e-9, v >= 1e-21)
+# do not, and sqrt(v) there is 1e-10 of eps.
+RADAM_UNDERFLOW = 2.0 ** -102
+RADAM_REF_ROUNDINGS = dict(p=6.5, m=4.2, v=7.0)            # measured 6.48, 4.17, 6.91 -> RADAM_BOUND 26, 16.8, 28
+RADAM_BOUND = {k: 4.0 * r for k, r in RADAM_REF_ROUNDINGS.items()}
+RADAM_BUGS = ("eps_dropped", "eps_inside_sqrt", "eps_squared", "step_one_behind", "lr_decay_one_step_late", "weight_decay_after_update",
+              "betas_exchanged", "update_in_the_no_update_branch")
+RADAM_F32_COMPLEMENTS = "float32_complements"        # 1.f - beta formed in float32 (what radam_k did): recorded, not a control
+_RADAM_FIXTURE = {}
+
+
+def radam_fixture():
+    """radam_steps.npz -> (gd, configs): configs[c] = one dict per tensor (p0, g [steps, n], lr, betas, weight_decay,
+    degenerated_to_sgd and the reference's p, m, v [steps, n]).  Loaded once, read-only."""
+    if not _RADAM_FIXTURE:
+        gd = np.load(GOLDEN / "radam_steps.npz")
+        configs = []
+        for c in range(int(gd["n_configs"])):
+            per = []
+            for t, grp in enumerate(gd[f"c{c}_group_of"]):
+                steps = int(gd["steps"])
+                d = dict(p0=gd[f"p0_{t}"].reshape(-1), g=gd[f"g_{t}"].reshape(steps, -1), shape=gd[f"p0_{t}"].shape,
+                         lr=float(gd[f"c{c}_lr"][grp]), betas=tuple(float(b) for b in gd[f"c{c}_betas"][grp]),
+                         weight_decay=float(gd[f"c{c}_weight_decay"]), degenerated_to_sgd=bool(gd[f"c{c}_degenerated_to_sgd"]),
+                         group=int(grp))
+                d.update({k: gd[f"c{c}_{k}_{t}"].reshape(steps, -1) for k in "pmv"})
+                for a in d.values():
+                    if isinstance(a, np.ndarray):
+                        a.setflags(write=False)
+                per.append(d)
+            configs.append(per)
+        _RADAM_FIXTURE["v"] = (gd, configs)
+    return _RADAM_FIXTURE["v"]
+
+
+def radam_lr(lr, step, decay_before=9, decay=0.995):
+    """the fixture's schedule: lr x 0.995 before step 9 (1-based), as train.py:166-172 sets it on param_groups"""
+    return lr * decay if step >= decay_before else lr
+
+
+def radam_step64(p, g, m, v, step, lr, eps, beta1, beta2, weight_decay, degenerated_to_sgd, bug=None):
+    """oracle/radam.py's float64 step restated with a switch for ONE wrong line (bug=None: bit-equal to oracle.radam.radam_step,
+    which test_radam_oracle_cpu.py asserts) -- the negative controls of the RAdam bound."""
+    from oracle import radam as oradam
+    b1, b2 = (beta2, beta1) if bug == "betas_exchanged" else (beta1, beta2)
+    c1, c2 = 1 - b1, 1 - b2
+    if bug == RADAM_F32_COMPLEMENTS:
+        c1, c2 = float(np.float32(1) - np.float32(b1)), float(np.float32(1) - np.float32(b2))
+    v *= b2
+    v += c2 * g * g
+    m *= b1
+    m += c1 * g
+    rect, scale = oradam.radam_scalars(max(step - 1, 1) if bug == "step_one_behind" else step, lr, beta1, beta2, degenerated_to_sgd)
+    if scale is None:
+        if bug != "update_in_the_no_update_branch":
+            return
+        scale = lr / (1 - beta1 ** step)
+    if weight_decay != 0 and bug != "weight_decay_after_update":
+        p += (-weight_decay * lr) * p
+    if rect:
+        den = np.sqrt(v + eps) if bug == "eps_inside_sqrt" else np.sqrt(v) + (0.0 if bug == "eps_dropped" else eps * eps if bug == "eps_squared" else eps)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            p += (-scale) * (m / den)
+    else:
+        p += (-scale) * m
+    if weight_decay != 0 and bug == "weight_decay_after_update":
+        p += (-weight_decay * lr) * p
+
+
+def radam_oracle_run(p0, grads, steps, lr, eps, betas=(0.9, 0.999), weight_decay=0.0, degenerated_to_sgd=True, bug=None, lr_of=radam_lr):
+    """The float64 trajectory from (p0, m = v = 0) over the 1-based step numbers `steps` (grads[i] at steps[i]).
+    -> dict of [len(steps), n] float64 arrays: p, m, v and their rounding scales sp, sm, sv."""
+    p, m, v = p0.astype(np.float64), np.zeros(p0.shape, np.float64), np.zeros(p0.shape, np.float64)
+    mabs, path = np.zeros_like(p), np.abs(p)
+    out = {k: [] for k in ("p", "m", "v", "sp", "sm", "sv")}
+    for g, step in zip(grads, steps):
+        g = g.astype(np.float64)
+        before = p.copy()
+        lr_t = lr_of(lr, step - 1 if bug == "lr_decay_one_step_late" else step)
+        radam_step64(p, g, m, v, step, lr_t, eps, betas[0], betas[1], weight_decay, degenerated_to_sgd, bug)
+        mabs = betas[0] * mabs + (1 - betas[0]) * np.abs(g)
+        path = path + np.abs(p - before)
+        for k, a in zip(("p", "m", "v", "sp", "sm", "sv"), (p, m, v, path, mabs, v)):
+            out[k].append(a.copy())
+    return {k: np.stack(a) for k, a in out.items()}
+
+
+def radam_roundings(got, ref, scale, finite_only=False):
+    """worst |got - ref| / (2^-24 scale) over all elements; where scale == 0 the value must be exactly ref's (inf otherwise).
+    finite_only (the negative controls, whose wrong line may divide 0 by 0): the worst over the elements where `got` is finite."""
+    got = np.asarray(got, dtype=np.float64)
+    err = np.abs(got - ref)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        r = np.where(scale > 0, err / (2.0 ** -24 * (scale + RADAM_UNDERFLOW)), np.where(err == 0, 0.0, np.inf))
+    r = np.where(np.isfinite(got), r, 0.0 if finite_only else np.inf)
+    return float(r.max()) if r.size else 0.0
+
+
+def radam_worst(got, ref):
+    """got: dict p, m, v [steps, n] (float32); ref: radam_oracle_run's dict -> worst roundings per array"""
+    return {k: radam_roundings(got[k], ref[k], ref["s" + k]) for k in "pmv"}
+
+
+def assert_radam(got, ref, tag=""):
+    worst = radam_worst(got, ref)
+    for k in "pmv":
+        assert worst[k] <= RADAM_BOUND[k], f"{tag}: {k} is {worst[k]:.1f} float32 roundings from the float64 oracle (bound {RADAM_BOUND[k]:.1f})"
+    return worst
+
+
+def radam_roundings_torch(got, ref, scale):
+    """radam_roundings for torch tensors on any device (the engine's flat buffer: 25 M elements, compared where they live)"""
+    err = (got.double() - ref).abs()
+    r = torch.where(scale > 0, err / (2.0 ** -24 * (scale + RADAM_UNDERFLOW)), torch.where(err == 0, 0.0, float("inf")).to(err.dtype))
+    r = torch.where(torch.isfinite(got), r, torch.full_like(r, float("inf")))
+    return float(r.max()) if r.numel() else 0.0
+
+
+def radam_teacher_forced(before, g, after, step, lr, eps, betas=(0.9, 0.999), weight_decay=0.0, degenerated_to_sgd=True):
+    """One step judged on its own: the float64 oracle's step `step` applied to float64 copies of the state BEFORE the step
+    (before = (p, m, v) float32 tensors) with the gradient the step used, against the state after it.  The scales are the
+    trajectory's restricted to this step -- v: v; m: beta1 |m_before| + (1 - beta1) |g|; p: |p_before| + |p - p_before| -- never
+    larger than the trajectory's, so RADAM_BOUND holds a fortiori.  -> worst roundings per array"""
+    from oracle import radam as oradam
+    p, m, v = (t.double().clone() for t in before)
+    g = g.double()
+    sm = betas[0] * m.abs() + (1 - betas[0]) * g.abs()
+    sp = p.abs()
+    oradam.radam_step(p, g, m, v, step, lr, eps, betas[0], betas[1], weight_decay, degenerated_to_sgd)
+    sp = sp + (p - before[0].double()).abs()
+    return {k: radam_roundings_torch(a, r, s) for k, a, r, s in zip("pmv", after, (p, m, v), (sp, sm, v))}

@@ -68,7 +68,7 @@ GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "b
 # what the binding needs beyond the header's older entry points: checked when the library is loaded, so that a stale
 # libzeggs_hip.so fails with a message instead of an AttributeError in the middle of a job list
 REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
-                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path")
+                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c")
 
 
 def lib():
@@ -1177,20 +1177,13 @@ def radam_step(p, g, m, v, beta1, beta2, eps, step_scale, rectified, status=None
     persistent sweep of the iteration gave up here (status[0]) or on another rank (gflag, a device float).  A step applied in
     pieces (slices of the flat buffers) counts its skip in ONE of them: count=False for the others.
     decay = weight_decay * lr (reference optimizers.py:88-95), 0 when the step is not applied."""
-    if decay != 0.0:
-        _check(lib().zeggs_radam_step_wd(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_float(beta1), C.c_float(beta2),
-                                         C.c_float(eps), C.c_float(step_scale), int(rectified), C.c_float(decay),
-                                         C.c_void_p(status.data_ptr()) if status is not None else None,
-                                         _p(gflag) if gflag is not None else None, int(bool(count)), _stream()), "radam_step_wd")
-    elif status is None:
-        _check(lib().zeggs_radam_step(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_float(beta1),
-                                      C.c_float(beta2), C.c_float(eps), C.c_float(step_scale), int(rectified),
-                                      _stream()), "radam_step")
-    else:
-        _check(lib().zeggs_radam_step_guarded_part(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_float(beta1),
-                                                   C.c_float(beta2), C.c_float(eps), C.c_float(step_scale), int(rectified),
-                                                   C.c_void_p(status.data_ptr()), _p(gflag) if gflag is not None else None,
-                                                   int(bool(count)), _stream()), "radam_step_guarded")
+    # the complements in double, as the reference forms them: float(1 - 0.999) = 0.001f, while 1.f - 0.999f = 0.00099998713
+    _check(lib().zeggs_radam_step_c(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_float(beta1), C.c_float(beta2),
+                                    C.c_float(1 - beta1), C.c_float(1 - beta2), C.c_float(eps), C.c_float(step_scale),
+                                    int(rectified), C.c_float(decay),
+                                    C.c_void_p(status.data_ptr()) if status is not None else None,
+                                    _p(gflag) if gflag is not None and status is not None else None, int(bool(count)), _stream()),
+           "radam_step")
 
 
 def status_flag(status, dst):

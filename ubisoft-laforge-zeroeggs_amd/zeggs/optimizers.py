@@ -62,7 +62,12 @@ class RAdam(Optimizer):
 
     def attach_flat(self, flat_p, flat_g, keep_state=False):
         """Run the step as ONE kernel over flat buffers (all params must be views of flat_p in order).
-        keep_state=True copies already-loaded per-tensor moments (resume) into the flat moment buffers."""
+        keep_state=True copies already-loaded per-tensor moments (resume) into the flat moment buffers.
+        One parameter group only: the flat step applies ONE set of scalars (lr, betas, eps, weight_decay) to the whole buffer --
+        with more groups step() would run the whole buffer once per group; those stay on the per-tensor path."""
+        if len(self.param_groups) != 1:
+            raise ValueError("RAdam.attach_flat: the flat step takes one parameter group, not {} (per-group lr / betas need "
+                             "the per-tensor path)".format(len(self.param_groups)))
         self._flat = (flat_p, flat_g, torch.zeros_like(flat_p), torch.zeros_like(flat_p))
         off = 0
         for group in self.param_groups:
