@@ -101,6 +101,73 @@ def test_persistent_sweep_state_before_any_launch():
     assert out["unknown"][0] != 0 and "no_such_option" in out["unknown"][1]
 
 
+# (B, T, SP = ST, H, film) at the synthetic skeleton's PI / PO -> zeggs_decoder_workspace_bytes(d, 0), (d, 1),
+# zeggs_decoder_batch_workspace_bytes(d), recorded from the library before the decoder's host code was reorganised
+_WORKSPACE_BYTES = {
+    (1, 1801, 64, 1024, 0): (98534400, 3748302080, 982638592),
+    (32, 256, 64, 1024, 0): (101411840, 1888559360, 448683008),
+    (64, 256, 64, 1024, 0): (104864000, 3033404160, 665913600),
+    (17, 4, 64, 1024, 0): (100260608, 425267200, 237296384),
+    (19, 12, 64, 1024, 1): (123731200, 225796520, 123731200),
+    (2, 5, 16, 64, 0): (2396416, 4514928, 2396416),
+    (65, 4, 64, 1024, 0): (105438720, 220587192, 105438720),
+    (4, 1, 64, 1024, 0): (98764544, 408307712, 232723200),
+}
+
+
+@pytest.mark.parametrize("dims", sorted(_WORKSPACE_BYTES))
+def test_decoder_workspace_bytes_are_pinned(dims):
+    """The carve of the decoder's workspace is an ABI of its own (a caller sizes its buffer by these queries, the prepare /
+    forward / backward calls of one step must agree on every offset): the byte counts at the shapes that take each path --
+    B = 1 decode, the persistent sweeps at 32 and 64 rows, an odd batch, FiLM, H = 64, the generic path at 65 rows, T = 1."""
+    B, T, S, H, film = dims
+    L = ops.lib()
+    d = ops.DecDims(B, T, synth.POSE_IN, synth.POSE_OUT, S, S, H, synth.DT)
+    d.film = film
+    got = (L.zeggs_decoder_workspace_bytes(ctypes.byref(d), 0), L.zeggs_decoder_workspace_bytes(ctypes.byref(d), 1),
+           L.zeggs_decoder_batch_workspace_bytes(ctypes.byref(d)))
+    assert got == _WORKSPACE_BYTES[dims]
+
+
+# every option name the library accepts, with its default
+_OPTIONS = {
+    "attn_bwd_one_launch": 1, "decoder_fast": 1, "stage_variant": 0, "gemm_wg_target": 6144, "timing": 0, "chain": 0,
+    "sweep_graphs": 0, "launch_window": 8, "train_persistent": 1, "bwd_persistent": 1, "persistent": 1, "mel_mfma": 1,
+    "mel_fft": 1, "gemm_streamk_wgs": 0, "gemm_mid_split": 1, "gemm_dma": 0, "gemm_direct": 1, "gemm_direct_wgs": 0,
+    "gemm_direct_depth": 4, "gemm_direct_shield": 0, "gemm_direct_reserve": 0, "gemm_asum": 1, "gemm_skinny": 1,
+    "gemm_streamk": 1, "fused_attention": 1, "bwd_chunks": 1, "tp_tiles4": 1, "tp_dual": 0, "tp_prologue": 1, "loss_lds": 1,
+    "wgrad_order": 0, "gemm_split_bf16": 0, "poll_stagger": 0, "poll_sleep": 0, "persistent_spin": 1 << 21, "ln_bwd4": 1,
+    "mel_exact_log": 2,
+}
+
+_OPTIONS_CHILD = """
+import ctypes, json, sys
+L = ctypes.CDLL(sys.argv[1])
+L.zeggs_last_error.restype = ctypes.c_char_p
+opts = json.loads(sys.argv[2])
+out = {"set": {k: [L.zeggs_set_option(k.encode(), 0), L.zeggs_set_option(k.encode(), v)] for k, v in opts.items()}}
+out["chain"] = [L.zeggs_set_option(b"chain", 1), L.zeggs_last_error().decode()]
+out["unknown"] = [L.zeggs_set_option(b"no_such_option", 1), L.zeggs_last_error().decode()]
+print(json.dumps(out))
+"""
+
+
+def test_every_option_is_still_accepted():
+    """zeggs_set_option, host only, in a process of its own (the switches are process-wide): every name is accepted with 0 and
+    with its default, `chain` is refused outside measurement builds with the build flag in the message, an unknown name is
+    refused by name."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _OPTIONS_CHILD, str(ops._LIB_PATH), json.dumps(_OPTIONS)], capture_output=True,
+                       text=True, timeout=60)
+    assert r.returncode == 0, r.stderr
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    assert out["set"] == {k: [0, 0] for k in _OPTIONS}
+    assert out["chain"][0] != 0 and "ZEGGS_CHAIN" in out["chain"][1]
+    assert out["unknown"][0] != 0 and "no_such_option" in out["unknown"][1]
+
+
 def test_no_cpu_fallback():
     se = modules.SpeechEncoder(synth.N_AUDIO, 64, 64)
     with pytest.raises(RuntimeError, match="GPU"):

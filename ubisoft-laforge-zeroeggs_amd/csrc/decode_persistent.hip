@@ -331,19 +331,18 @@ int dec_persistent_supported(const ZeggsDecDims& d, const DecWs& w) {
 
 // hid_1 / x_1 / the initial state are in the workspace (decoder.hip: dec_init_k, CellStateEncoder or h_in, layer0 of
 // the first frame); Mc / cvec are the folded layer0 operands (dec_fast_merge_prep).
-int dec_persistent_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-                       const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* gin1,
-                       const float* h0_init, const float* h1_init, float* h0_fin, float* h1_fin, hipStream_t s,
-                       unsigned* status) {
+int dec_persistent_run(const DecCtx& c, const DecFwdIO& io, const float* gin1, const float* h0_init, const float* h1_init,
+                       float* h0_fin, float* h1_fin, unsigned* status) {
+  const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
   ZTRY(require_cus(PNCU, "persistent decode"));
   ZTRY(k_fill((float*)w.pgran, (long)(w.pgran_bytes / 4), 0.f, s));      // tags 0 = nothing published
   PArgs a;
   memset(&a, 0, sizeof(a));
-  a.d = d; a.st = *st;
+  a.d = c.d; a.st = *c.st;
   a.w_ih0 = P->w_ih0; a.w_hh0 = P->w_hh0; a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0;
   a.w_ih1 = P->w_ih1; a.w_hh1 = P->w_hh1; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1;
   a.l2_w = P->l2_w; a.l2_b = P->l2_b; a.l0_w = P->l0_w; a.Mc = w.Mc; a.cvec = w.cvec;
-  a.gaze = gaze; a.speech = speech; a.style = style; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
+  a.gaze = io.gaze; a.speech = io.speech; a.style = io.style; a.pose = io.pose; a.rpos = io.rpos; a.rrot = io.rrot;
   a.gin1 = gin1; a.h0_init = h0_init; a.h1_init = h1_init; a.h0_fin = h0_fin; a.h1_fin = h1_fin;
   unsigned long long* g = (unsigned long long*)w.pgran;
   a.g_h0 = g; a.g_h1 = g + PH; a.g_hid = g + 2 * PH; a.g_xp = g + 3 * PH;

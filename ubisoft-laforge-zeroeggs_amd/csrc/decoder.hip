@@ -17,84 +17,9 @@
 #include "decoder_ws.h"
 
 int g_decoder_fast = 1;      // option "decoder_fast": 0 = generic per-step GEMM path everywhere (A/B reference of the stage kernels)
-static int g_bwd_chunks = 1;   // BPTT sweep chunks whose weight-gradient GEMMs overlap the rest of the sweep (1: serial)
-extern int g_stage_variant;
-extern int g_gemm_wg_target;
-extern int g_timing;
-extern int g_chain;
-extern int g_sweep_graphs;
-extern int g_launch_window;
-extern int g_fused_attention;
-extern int g_gemm_streamk;
-extern int g_gemm_skinny;
-extern int g_tp_tiles4;
-extern int g_tp_dual;
-extern int g_loss_lds;
-extern int g_gemm_split_bf16;
-int g_tp_prologue = 1;      // zeggs_set_option("tp_prologue", 0 / 1): the training rollout's prologue in five launches instead of ten
-int g_wgrad_order = 0;      // zeggs_set_option("wgrad_order", 0 / 1 / 2): see dec_recurrent_wgrads
-void zeggs_gemm_set_dma(int on);
-void zeggs_gemm_set_direct(int mode, int wgs);
-void zeggs_gemm_set_direct_depth(int d);
-void zeggs_gemm_set_direct_shield(int on);
-void zeggs_gemm_set_direct_reserve(int n);
-void zeggs_gemm_set_asum(int on);
-extern int g_gemm_mid_split;
-extern int g_gemm_streamk_wgs;
-extern int g_mel_mfma;
-extern int g_mel_fft;
-extern int g_ln_bwd4;
-extern int g_mel_exact_log;
-extern int g_attn_bwd_one_launch;
-extern "C" int zeggs_set_option(const char* name, int value) {
-  if (strcmp(name, "attn_bwd_one_launch") == 0) { g_attn_bwd_one_launch = value != 0; return 0; }
-  if (strcmp(name, "decoder_fast") == 0) { g_decoder_fast = value; return 0; }
-  if (strcmp(name, "stage_variant") == 0) { g_stage_variant = value; return 0; }
-  if (strcmp(name, "gemm_wg_target") == 0) { g_gemm_wg_target = value; return 0; }
-  if (strcmp(name, "timing") == 0) { g_timing = value; return 0; }
-  if (strcmp(name, "chain") == 0) {
-#ifndef ZEGGS_CHAIN
-    if (value) { zeggs_set_error("option chain: the chained (run-ahead) stage launches lost to the persistent decode kernel and are "
-                                 "compiled in measurement builds only (-DZEGGS_CHAIN)"); return -1; }
-#endif
-    g_chain = value; return 0;
-  }
-  if (strcmp(name, "sweep_graphs") == 0) { g_sweep_graphs = value != 0; return 0; }
-  if (strcmp(name, "launch_window") == 0) { g_launch_window = value < 0 ? 0 : value; return 0; }
-  if (strcmp(name, "train_persistent") == 0) { g_sweep_kernels[SWEEP_ROLLOUT].set_enabled(value); return 0; }
-  if (strcmp(name, "bwd_persistent") == 0) { g_sweep_kernels[SWEEP_BPTT].set_enabled(value); return 0; }
-  if (strcmp(name, "persistent") == 0) { g_sweep_kernels[SWEEP_DECODE].set_enabled(value); return 0; }
-  if (strcmp(name, "mel_mfma") == 0) { g_mel_mfma = value != 0; return 0; }
-  if (strcmp(name, "mel_fft") == 0) { g_mel_fft = value != 0; return 0; }
-  if (strcmp(name, "gemm_streamk_wgs") == 0) { g_gemm_streamk_wgs = value; return 0; }
-  if (strcmp(name, "gemm_mid_split") == 0) { g_gemm_mid_split = value != 0; return 0; }
-  if (strcmp(name, "gemm_dma") == 0) { zeggs_gemm_set_dma(value != 0); return 0; }
-  if (strcmp(name, "gemm_direct") == 0) { zeggs_gemm_set_direct(value, -1); return 0; }
-  if (strcmp(name, "gemm_direct_wgs") == 0) { zeggs_gemm_set_direct(-1, value); return 0; }
-  if (strcmp(name, "gemm_direct_depth") == 0) { zeggs_gemm_set_direct_depth(value); return 0; }
-  if (strcmp(name, "gemm_direct_shield") == 0) { zeggs_gemm_set_direct_shield(value); return 0; }
-  if (strcmp(name, "gemm_direct_reserve") == 0) { zeggs_gemm_set_direct_reserve(value); return 0; }
-  if (strcmp(name, "gemm_asum") == 0) { zeggs_gemm_set_asum(value); return 0; }
-  if (strcmp(name, "gemm_skinny") == 0) { g_gemm_skinny = value != 0; return 0; }
-  if (strcmp(name, "gemm_streamk") == 0) { g_gemm_streamk = value != 0; return 0; }
-  if (strcmp(name, "fused_attention") == 0) { g_fused_attention = value != 0; return 0; }
-  if (strcmp(name, "bwd_chunks") == 0) { g_bwd_chunks = value < 1 ? 1 : value; return 0; }
-  if (strcmp(name, "tp_tiles4") == 0) { g_tp_tiles4 = value != 0; return 0; }
-  if (strcmp(name, "tp_dual") == 0) { g_tp_dual = value != 0; return 0; }
-  if (strcmp(name, "tp_prologue") == 0) { g_tp_prologue = value != 0; return 0; }
-  if (strcmp(name, "loss_lds") == 0) { g_loss_lds = value != 0; return 0; }
-  if (strcmp(name, "wgrad_order") == 0) { g_wgrad_order = value; return 0; }
-  if (strcmp(name, "gemm_split_bf16") == 0) { g_gemm_split_bf16 = (value == 3 || value == 6 || value == 9) ? value : 0; return 0; }
-  if (strcmp(name, "poll_stagger") == 0) { g_poll_stagger = value < 0 ? 0 : value; return 0; }
-  if (strcmp(name, "poll_sleep") == 0) { g_poll_sleep = value < 0 ? 0 : value; return 0; }
-  // bound of every device-side wait of the persistent kernels (polls); 0 makes the first unsatisfied wait give up: the
-  // tests use it to drive the give-up path (tests/test_gpu_giveup.py)
-  if (strcmp(name, "persistent_spin") == 0) { g_persistent_spin = value < 0 ? 0 : value; return 0; }
-  if (strcmp(name, "ln_bwd4") == 0) { g_ln_bwd4 = value; return 0; }
-  if (strcmp(name, "mel_exact_log") == 0) { g_mel_exact_log = value; return 0; }
-  zeggs_set_error("unknown option %s", name);
-  return -1;
-}
+int g_bwd_chunks = 1;        // option "bwd_chunks": BPTT sweep chunks whose weight-gradient GEMMs overlap the rest of the sweep (1: serial)
+int g_tp_prologue = 1;       // option "tp_prologue", 0 / 1: the training rollout's prologue in five launches instead of ten
+int g_wgrad_order = 0;       // option "wgrad_order", 0 / 1 / 2: see dec_recurrent_wgrads
 
 // What tells a caller that a persistent kernel gave up AFTER its first (validated) use -- e.g. a co-tenant took CUs, so not
 // every workgroup was resident and a bounded wait ran out: (1) the kernel ORs its bit into the caller-owned sticky status word
@@ -435,7 +360,7 @@ int dec_recurrent_wgrads(const ZeggsDecDims& d, const DecWs& w, const ZeggsDecGr
 }
 
 // Side stream (lowest priority) + events for the overlapped weight-gradient GEMMs, one set per device.
-struct SideStream { hipStream_t s; hipEvent_t chunk, done; };
+struct SideStream { hipStream_t s; hipEvent_t done; };
 int side_stream(SideStream** out) {
   static SideStream pool[16];
   static bool ready[16] = {};
@@ -445,7 +370,6 @@ int side_stream(SideStream** out) {
     int lo = 0, hi = 0;
     ZCHECK(hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess, "hipDeviceGetStreamPriorityRange failed");
     ZCHECK(hipStreamCreateWithPriority(&pool[dev].s, hipStreamNonBlocking, lo) == hipSuccess, "side stream creation failed");
-    ZCHECK(hipEventCreateWithFlags(&pool[dev].chunk, hipEventDisableTiming) == hipSuccess, "event creation failed");
     ZCHECK(hipEventCreateWithFlags(&pool[dev].done, hipEventDisableTiming) == hipSuccess, "event creation failed");
     ready[dev] = true;
   }
@@ -453,208 +377,150 @@ int side_stream(SideStream** out) {
   return 0;
 }
 
-// fork event of a deferred-GEMM hand-over: stream-ordered use only (record on one stream, wait on another, both enqueued
-// before this returns), so one event per device and hand-over point (`which`) is enough; events carry no data and are created once
-int fork_event(hipEvent_t* out, int which = 0) {
-  static hipEvent_t pool[16][2];
-  static bool ready[16][2] = {};
+// `to` continues behind what `from` holds now.  The event of such a hand-over: stream-ordered use only (record on one stream, wait
+// on another, both enqueued before this returns), so one event per device and hand-over point (`which`: 0 / 1 the deferred weight
+// gradients of the recurrent layers / the CellStateEncoder, 2 a chunk of the stage sweep) is enough; events carry no data and are
+// created once
+int stream_fork(hipStream_t from, hipStream_t to, int which) {
+  static hipEvent_t pool[16][3];
+  static bool ready[16][3] = {};
   int dev = 0;
   ZCHECK(hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16, "decoder bwd: unsupported device index");
   if (!ready[dev][which]) {
     ZCHECK(hipEventCreateWithFlags(&pool[dev][which], hipEventDisableTiming) == hipSuccess, "event creation failed");
     ready[dev][which] = true;
   }
-  *out = pool[dev][which];
+  ZCHECK(hipEventRecord(pool[dev][which], from) == hipSuccess, "hipEventRecord failed");
+  ZCHECK(hipStreamWaitEvent(to, pool[dev][which], 0) == hipSuccess, "hipStreamWaitEvent failed");
   return 0;
 }
 
 inline dim3 g1(long n) { long g = (n + 255) / 256; return dim3((unsigned)(g > 4096 ? 4096 : (g < 1 ? 1 : g))); }
 
-}  // namespace
-
-extern "C" size_t zeggs_decoder_workspace_bytes(const ZeggsDecDims* d, int training) {
-  Arena a(nullptr, 0);
-  carve_dec(*d, training, a);
-  return a.off + 256;
+// ------------------------------------------------------------------ the head of a rollout, piece by piece
+// frame 0 of the outputs, the CellStateEncoder's input and the pose part of x_1 (the caller checks the launch)
+void dec_init(const DecCtx& c, const DecFwdIO& io, float* gin1) {
+  hipLaunchKernelGGL(dec_init_k, dim3(c.d.B), dim3(256), 0, c.s, c.d, *c.st, io.pose0, io.rpos0, io.rrot0, io.gaze, io.style, io.pose,
+                     io.rpos, io.rrot, c.w.cse_in, gin1, c.w.GL);
 }
-
-static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                            const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                            const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                            int training, const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
-                            const ZeggsDecCall* call);
-
-extern "C" int zeggs_decoder_fwd(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                                 const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                                 const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                                 int training, void* ws, size_t ws_bytes, void* stream) {
-  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, training, nullptr,
-                          nullptr, ws, ws_bytes, stream, nullptr);
+// speech / style columns of x_t, t = t0 .. t0 + nt - 1, in the canonical input rows (ring: the 2-slot ring of inference)
+int dec_fill_cond(const DecCtx& c, const DecFwdIO& io, int t0, int nt, int ring) {
+  const ZeggsDecDims& d = c.d;
+  hipLaunchKernelGGL(dec_fill_cond_k, g1((long)nt * d.B * (d.SP + d.ST)), dim3(256), 0, c.s, d, io.speech, io.style, c.w.Gin, c.w.GL,
+                     t0, nt, (long)d.B * c.w.GL, ring);
+  ZLAUNCH_CHECK("dec_fill_cond");
+  return 0;
 }
-extern "C" int zeggs_decoder_fwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                                    const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                                    const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                                    int training, void* ws, size_t ws_bytes, void* stream, const ZeggsDecCall* call) {
-  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, training, nullptr,
-                          nullptr, ws, ws_bytes, stream, call);
+int gemm_nt_item(const GemmNtItem& i, int M, hipStream_t s) {
+  return gemm_nt(i.x, i.ldx, i.W, i.ldw, i.y, i.ldy, i.bias, M, i.N, i.K, i.act, 0.f, s);
 }
-
-// Chunked (streaming) decode: frame 0 of the chunk is the last frame already produced (its pose / root state come in as
-// pose0 / rpos0 / rrot0), h_in [2,B,H] is the GRU state after that frame (NULL: first chunk, CellStateEncoder), h_out
-// receives the state after the chunk's last frame.  Inference only (2-slot rings).
-extern "C" int zeggs_decoder_fwd_state(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                                       const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                                       const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                                       const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream) {
-  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, 0, h_in, h_out, ws,
-                          ws_bytes, stream, nullptr);
+// hid_1 = ELU(W0 x_1 + b0) in slot 1 of the canonical input rows
+GemmNtItem dec_hid1_item(const DecCtx& c) {
+  float* gin1 = c.w.Gin + (long)c.d.B * c.w.GL;
+  return GemmNtItem{gin1 + c.d.H, c.w.GL, c.P->l0_w, c.w.XD, gin1, c.w.GL, c.P->l0_b, c.d.H, c.w.XD, ACT_ELU};
 }
-// the same with per-call controls: ZeggsDecCall.status receives the give-up bit of the B = 1 persistent kernel, so that a caller
-// that feeds the returned state into the NEXT chunk (zeggs/stream.py) can notice a rollout that did not complete and redo it
-extern "C" int zeggs_decoder_fwd_state_ex(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                                          const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                                          const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                                          const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
-                                          const ZeggsDecCall* call) {
-  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, 0, h_in, h_out, ws,
-                          ws_bytes, stream, call);
+int dec_hid1(const DecCtx& c) { return gemm_nt_item(dec_hid1_item(c), c.d.B, c.s); }
+// the CellStateEncoder's four products: two layers, then the halves of the last one, which are the initial states of the GRU layers
+struct CseItems { GemmNtItem it[4]; };
+CseItems dec_cse_items(const DecCtx& c, float* h0_dst, float* h1_dst) {
+  const ZeggsDecParams* P = c.P; const DecWs& w = c.w;
+  const int H = c.d.H, CI = c.d.PI + c.d.ST;
+  return CseItems{{{w.cse_in, CI, P->c0_w, CI, w.cse_a, H, P->c0_b, H, CI, ACT_ELU},
+                   {w.cse_a, H, P->c1_w, H, w.cse_b, H, P->c1_b, H, H, ACT_ELU},
+                   {w.cse_b, H, P->c2_w, H, h0_dst, H, P->c2_b, H, H, ACT_NONE},
+                   {w.cse_b, H, P->c2_w + (long)H * H, H, h1_dst, H, P->c2_b + H, H, H, ACT_NONE}}};
 }
-
-static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
-                            const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
-                            const float* speech, const float* style, float* pose, float* rpos, float* rrot,
-                            int training, const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
-                            const ZeggsDecCall* call) {
-  const ZeggsDecDims& d = *dp;
-  hipStream_t s = (hipStream_t)stream;
-  const bool fwd_prepared = call && (call->prepared & 1);
-  unsigned* status = call ? call->status : nullptr;
-  ZCHECK(d.PI == d.PO + 3, "decoder: pose_input_size must be pose_output_size + 3 (gaze)");
-  ZCHECK(d.B >= 1 && d.T >= 1, "decoder: empty batch or sequence");
-  Arena a(ws, ws_bytes);
-  DecWs w = carve_dec(d, training, a);
-  ZCHECK(a.ok(), "decoder: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  const int B = d.B, T = d.T, H = d.H, GL = w.GL, XD = w.XD, CI = d.PI + d.ST;
-  const long sG = (long)B * GL, sH = (long)B * H;
-  const int ring = training ? 0 : 1;
-  auto slot = [&](int t) { return ring ? (t & 1) : t; };
-  if (!training) ZTRY(k_fill(w.Gin, 2 * sG, 0.f, s));   // ring slots: pad columns must be finite (GEMV decode path)
-  const bool fast = g_decoder_fast && dec_fast_supported(d);
-  // ---- training, batch <= 64: will the forward rollout run as one persistent launch (train_persistent.hip)?  Then its whole prologue is
-  // five launches instead of ten (round 6; option "tp_prologue", default on): [dec_init | dec_fill_cond | tp_cond] in one,
-  // [CellStateEncoder layer 0 | hid_1 | the step-1 pose product] in one, CellStateEncoder layer 1, the two halves of its last layer
-  // in one, and the rollout's own operand fragments (dec_tp_run) -- every one of them was launch latency on an idle chip
-  SweepKernel& tpk = g_sweep_kernels[SWEEP_ROLLOUT];
-  const bool tp_path = fast && training && dec_tp_supported(d, w) && tpk.may_run(s);
-  const bool tp_pro = tp_path && g_tp_prologue && !h_in && T > 1 && !d.film;
-  if (tp_pro) {
-    float* gin1 = w.Gin + sG;
-    ZTRY(dec_tp_prologue(d, st, w, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, s, fwd_prepared));
-    const GemmNtItem l1[3] = {{w.cse_in, CI, P->c0_w, CI, w.cse_a, H, P->c0_b, H, CI, ACT_ELU},
-                              {gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, H, XD, ACT_ELU},          // hid_1 = ELU(W0 x_1 + b0)
-                              dec_tp_p1x_item(d, P, w)};
-    ZTRY(gemm_nt_multi(l1, 3, B, s));
-    ZTRY(gemm_nt(w.cse_a, H, P->c1_w, H, w.cse_b, H, P->c1_b, B, H, H, ACT_ELU, 0.f, s));
-    const GemmNtItem l3[2] = {{w.cse_b, H, P->c2_w, H, w.H0, H, P->c2_b, H, H, ACT_NONE},
-                              {w.cse_b, H, P->c2_w + (long)H * H, H, w.H1, H, P->c2_b + H, H, H, ACT_NONE}};
-    ZTRY(gemm_nt_multi(l3, 2, B, s));
-  } else {
-  // frame 0 + CellStateEncoder
-  hipLaunchKernelGGL(dec_init_k, dim3(B), dim3(256), 0, s, d, *st, pose0, rpos0, rrot0, gaze, style, pose, rpos, rrot,
-                     w.cse_in, w.Gin + slot(1) * sG, GL);
+int dec_cse(const DecCtx& c, float* h0_dst, float* h1_dst) {
+  const CseItems q = dec_cse_items(c, h0_dst, h1_dst);
+  for (const GemmNtItem& i : q.it) ZTRY(gemm_nt_item(i, c.d.B, c.s));
+  return 0;
+}
+// frame 0, then the recurrent state before step 1: given (resumed rollout) or the CellStateEncoder's
+int dec_head(const DecCtx& c, const DecFwdIO& io, const float* h_in) {
+  const long sH = (long)c.d.B * c.d.H;
+  dec_init(c, io, c.w.Gin + (long)c.d.B * c.w.GL);
   ZLAUNCH_CHECK("dec_init");
-  if (h_in) {   // resumed rollout: the recurrent state is given
-    ZTRY(k_copy(w.H0 + slot(0) * sH, h_in, sH, s));
-    ZTRY(k_copy(w.H1 + slot(0) * sH, h_in + sH, sH, s));
-  } else {
-    ZTRY(gemm_nt(w.cse_in, CI, P->c0_w, CI, w.cse_a, H, P->c0_b, B, H, CI, ACT_ELU, 0.f, s));
-    ZTRY(gemm_nt(w.cse_a, H, P->c1_w, H, w.cse_b, H, P->c1_b, B, H, H, ACT_ELU, 0.f, s));
-    ZTRY(gemm_nt(w.cse_b, H, P->c2_w, H, w.H0 + slot(0) * sH, H, P->c2_b, B, H, H, ACT_NONE, 0.f, s));
-    ZTRY(gemm_nt(w.cse_b, H, P->c2_w + (long)H * H, H, w.H1 + slot(0) * sH, H, P->c2_b + H, B, H, H, ACT_NONE, 0.f, s));
-  }
-  }
-  auto save_state = [&]() -> int {
-    if (h_out) {
-      ZTRY(k_copy(h_out, w.H0 + slot(T - 1) * sH, sH, s));
-      ZTRY(k_copy(h_out + sH, w.H1 + slot(T - 1) * sH, sH, s));
-    }
-    return 0;
-  };
-  if (training && T > 1) {
-    if (!tp_pro) {
-      hipLaunchKernelGGL(dec_fill_cond_k, g1((long)(T - 1) * B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin,
-                         GL, 1, T - 1, sG, 0);
-      ZLAUNCH_CHECK("dec_fill_cond");
-    }
-    if (d.film) {   // modulation vectors of every step in two GEMMs over the time-major style
-      ZCHECK(P->l3_w && P->l3_b && P->g_w && P->g_b && P->be_w && P->be_b, "decoder: film parameters missing");
-      hipLaunchKernelGGL(style_time_major_k, g1((long)T * B * d.ST), dim3(256), 0, s, d, style, w.STm);
-      ZLAUNCH_CHECK("style_time_major");
-      ZTRY(gemm_nt(w.STm, d.ST, P->g_w, d.ST, w.GAM, 2 * H, P->g_b, T * B, 2 * H, d.ST, ACT_NONE, 0.f, s));
-      ZTRY(gemm_nt(w.STm, d.ST, P->be_w, d.ST, w.BET, 2 * H, P->be_b, T * B, 2 * H, d.ST, ACT_NONE, 0.f, s));
-    }
-  }
-  // ---- batch-1 inference: the weight-stationary persistent kernel (one launch for all frames, decode_persistent.hip)
-  SweepKernel& dpk = g_sweep_kernels[SWEEP_DECODE];
-  if (fast && !training && dec_persistent_supported(d, w) && dpk.may_run(s)) {
-    float* gin1 = w.Gin + slot(1) * sG;
-    hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1, 1,
-                       sG, 1);
-    ZLAUNCH_CHECK("dec_fill_cond");
-    ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
-    ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-    dec_timing_mark(0, s);
-    ZTRY(dec_persistent_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, gin1, w.H0 + slot(0) * sH,
-                            w.H1 + slot(0) * sH, w.H0 + slot(T - 1) * sH, w.H1 + slot(T - 1) * sH, s, dpk.status_arg(status)));
-    dec_timing_mark(1, s);
-    bool ok = false;
-    ZTRY(dpk.settle(s, dp_errword(w), &ok));
-    if (ok) return save_state();
-    // a bounded sweep gave up: disabled for this process, the stage kernels redo the rollout
-  }
-  // ---- training, batch <= 32: the forward rollout as one persistent launch (train_persistent.hip)
-  if (tp_path) {
-    float* gin1 = w.Gin + sG;
-    if (!tp_pro) ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
-    if (!fwd_prepared) {
-      ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-      ZTRY(dec_tp_pack(d, P, st, w, s));
-    }
-    dec_timing_mark(0, s);
-    ZTRY(dec_tp_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, s, fwd_prepared, tpk.status_arg(status), tp_pro));
-    dec_timing_mark(1, s);
-    bool ok = false;
-    ZTRY(tpk.settle(s, tp_errword(w), &ok));
-    if (ok) return save_state();
-  }
-  if (fast) {
-    if (!training && T > 1) {
-      hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1,
-                         1, sG, 1);
-      ZLAUNCH_CHECK("dec_fill_cond");
-    }
-    ZTRY(dec_fast_pack_fwd(d, P, w, s));
-    ZTRY(dec_fast_fwd_steps(d, P, st, w, gaze, speech, style, pose, rpos, rrot, training, s));
-    return save_state();
-  }
+  if (!h_in) return dec_cse(c, c.w.H0, c.w.H1);
+  ZTRY(k_copy(c.w.H0, h_in, sH, c.s));
+  return k_copy(c.w.H1, h_in + sH, sH, c.s);
+}
+// The same head in front of the persistent training rollout (train_persistent.hip), five launches instead of ten (round 6; option
+// "tp_prologue", default on): [dec_init | dec_fill_cond | tp_cond] in one, [CellStateEncoder layer 0 | hid_1 | the step-1 pose
+// product] in one, CellStateEncoder layer 1, the two halves of its last layer in one, and the rollout's own operand fragments
+// (dec_tp_run) -- every one of them was launch latency on an idle chip
+int dec_head_prologue(const DecCtx& c, const DecFwdIO& io, bool zeroed) {
+  ZTRY(dec_tp_prologue(c, io, zeroed));
+  const CseItems q = dec_cse_items(c, c.w.H0, c.w.H1);
+  const GemmNtItem l1[3] = {q.it[0], dec_hid1_item(c), dec_tp_p1x_item(c)};
+  ZTRY(gemm_nt_multi(l1, 3, c.d.B, c.s));
+  ZTRY(gemm_nt_item(q.it[1], c.d.B, c.s));
+  return gemm_nt_multi(q.it + 2, 2, c.d.B, c.s);
+}
+// training: the speech / style columns of every step (unless the prologue launch has filled them) and, with FiLM, the modulation
+// vectors of every step in two GEMMs over the time-major style
+int dec_train_inputs(const DecCtx& c, const DecFwdIO& io, bool cond_filled) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
+  if (!cond_filled) ZTRY(dec_fill_cond(c, io, 1, d.T - 1, 0));
+  if (!d.film) return 0;
+  ZCHECK(P->l3_w && P->l3_b && P->g_w && P->g_b && P->be_w && P->be_b, "decoder: film parameters missing");
+  hipLaunchKernelGGL(style_time_major_k, g1((long)d.T * d.B * d.ST), dim3(256), 0, s, d, io.style, w.STm);
+  ZLAUNCH_CHECK("style_time_major");
+  ZTRY(gemm_nt(w.STm, d.ST, P->g_w, d.ST, w.GAM, 2 * d.H, P->g_b, d.T * d.B, 2 * d.H, d.ST, ACT_NONE, 0.f, s));
+  return gemm_nt(w.STm, d.ST, P->be_w, d.ST, w.BET, 2 * d.H, P->be_b, d.T * d.B, 2 * d.H, d.ST, ACT_NONE, 0.f, s);
+}
+
+// ------------------------------------------------------------------ the paths of a rollout, in the order they are tried.  A persistent
+// sweep that gave up on its first use leaves *done false (the kernel is then disabled for this process): the next path redoes the rollout.
+// batch-1 inference: the weight-stationary persistent kernel (one launch for all frames, decode_persistent.hip)
+int fwd_persistent_decode(const DecCtx& c, const DecFwdIO& io, unsigned* status, bool* done) {
+  const ZeggsDecDims& d = c.d; DecWs& w = c.w;
+  SweepKernel& k = g_sweep_kernels[SWEEP_DECODE];
+  if (!(dec_persistent_supported(d, w) && k.may_run(c.s))) return 0;
+  const long fin = (long)((d.T - 1) & 1) * d.B * d.H;
+  ZTRY(dec_fill_cond(c, io, 1, 1, 1));
+  ZTRY(dec_hid1(c));
+  ZTRY(dec_fast_merge_prep(c));
+  dec_timing_mark(0, c.s);
+  ZTRY(dec_persistent_run(c, io, w.Gin + (long)d.B * w.GL, w.H0, w.H1, w.H0 + fin, w.H1 + fin, k.status_arg(status)));
+  dec_timing_mark(1, c.s);
+  return k.settle(c.s, dp_errword(w), done);
+}
+// training, batch <= 64: the forward rollout as one persistent launch (train_persistent.hip)
+int fwd_persistent_rollout(const DecCtx& c, const DecFwdIO& io, bool prepared, bool prologue_done, unsigned* status, bool* done) {
+  SweepKernel& k = g_sweep_kernels[SWEEP_ROLLOUT];
+  if (!prologue_done) ZTRY(dec_hid1(c));
+  if (!prepared) ZTRY(dec_tp_pack(c));
+  dec_timing_mark(0, c.s);
+  ZTRY(dec_tp_run(c, io, prepared, k.status_arg(status), prologue_done));
+  dec_timing_mark(1, c.s);
+  return k.settle(c.s, tp_errword(c.w), done);
+}
+// the stage kernels, three or four launches per step (decoder_fast.hip)
+int fwd_stage_launches(const DecCtx& c, const DecFwdIO& io, int training) {
+  if (!training && c.d.T > 1) ZTRY(dec_fill_cond(c, io, 1, 1, 1));
+  ZTRY(dec_fast_pack_fwd(c));
+  return dec_fast_fwd_steps(c, io, training);
+}
+// generic GEMMs and elementwise kernels, step by step
+int fwd_generic_steps(const DecCtx& c, const DecFwdIO& io, int training) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
+  const int B = d.B, T = d.T, H = d.H, GL = w.GL, XD = w.XD;
+  const long sG = (long)B * GL, sH = (long)B * H;
+  auto slot = [&](int t) { return training ? t : (t & 1); };
   for (int t = 1; t < T; ++t) {
     float* gin = w.Gin + slot(t) * sG;
     float* gin_next = (t + 1 < T) ? w.Gin + slot(t + 1) * sG : nullptr;
     const float *h0p = w.H0 + slot(t - 1) * sH, *h1p = w.H1 + slot(t - 1) * sH;
     float *h0 = w.H0 + slot(t) * sH, *h1 = w.H1 + slot(t) * sH;
-    if (!training) {
-      hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, t,
-                         1, sG, 1);
-      ZLAUNCH_CHECK("dec_fill_cond");
-    }
+    if (!training) ZTRY(dec_fill_cond(c, io, t, 1, 1));
     // hid = ELU(layer0(x))   [film: modulated by the style]
     const float *gam = nullptr, *bet = nullptr;
     if (d.film) {
       if (!training) {   // ring path: this step's modulation vectors from style[:, t]
         ZCHECK(P->l3_w && P->l3_b && P->g_w && P->g_b && P->be_w && P->be_b, "decoder: film parameters missing");
-        ZTRY(gemm_nt(style + (long)t * d.ST, (long)T * d.ST, P->g_w, d.ST, w.GAM, 2 * H, P->g_b, B, 2 * H, d.ST, ACT_NONE,
+        ZTRY(gemm_nt(io.style + (long)t * d.ST, (long)T * d.ST, P->g_w, d.ST, w.GAM, 2 * H, P->g_b, B, 2 * H, d.ST, ACT_NONE,
                      0.f, s));
-        ZTRY(gemm_nt(style + (long)t * d.ST, (long)T * d.ST, P->be_w, d.ST, w.BET, 2 * H, P->be_b, B, 2 * H, d.ST, ACT_NONE,
+        ZTRY(gemm_nt(io.style + (long)t * d.ST, (long)T * d.ST, P->be_w, d.ST, w.BET, 2 * H, P->be_b, B, 2 * H, d.ST, ACT_NONE,
                      0.f, s));
       }
       gam = w.GAM + (training ? (long)t * B * 2 * H : 0);
@@ -685,11 +551,210 @@ static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, con
     } else {
       ZTRY(gemm_nt(h1, H, P->l2_w, H, w.Y, w.POL, P->l2_b, B, d.PO, H, ACT_NONE, 0.f, s));
     }
-    hipLaunchKernelGGL(dec_devec_k, dim3(B), dim3(256), 0, s, d, *st, w.Y, w.POL, gaze, pose, rpos, rrot, gin_next, GL,
-                       t);
+    hipLaunchKernelGGL(dec_devec_k, dim3(B), dim3(256), 0, s, d, *st, w.Y, w.POL, io.gaze, io.pose, io.rpos, io.rrot,
+                       gin_next, GL, t);
     ZLAUNCH_CHECK("dec_step");
   }
-  return save_state();
+  return 0;
+}
+
+// ------------------------------------------------------------------ the pieces of the backward
+// the zero state a sweep starts from: the carries and (with_dx) the frame-0 slot of DX, unused but read by the scatter
+int dec_bwd_zero_state(const DecCtx& c, bool with_dx) {
+  const ZeggsDecDims& d = c.d;
+  ZTRY(k_fill(c.w.dH0c, (long)d.B * d.H, 0.f, c.s));
+  ZTRY(k_fill(c.w.dH1c, (long)d.B * d.H, 0.f, c.s));
+  ZTRY(k_fill(c.w.carry, (long)2 * d.B * 8, 0.f, c.s));
+  if (with_dx) ZTRY(k_fill(c.w.DX, (long)d.B * c.w.XD, 0.f, c.s));
+  return 0;
+}
+// The stage launches (decoder_fast.hip).  The sweep is a chain of small dependent launches that leaves most of the chip idle; with
+// option "bwd_chunks" > 1 the weight-gradient GEMMs of the steps already swept run beside it on a low-priority stream, chunk by
+// chunk: *ss is then the side stream the caller joins.
+int bwd_stage_sweep(const DecCtx& c, const DecBwdIO& io, const ZeggsDecGrads* G, float gb, SideStream** ss) {
+  const int T = c.d.T;
+  ZTRY(dec_fast_pack_bwd(c));
+  const int nch = g_bwd_chunks < T - 1 ? g_bwd_chunks : T - 1;
+  if (nch > 1) ZTRY(side_stream(ss));
+  for (int k = 0; k < nch; ++k) {
+    const int t_hi = T - 1 - (int)((long)(T - 1) * k / nch), t_lo = T - (int)((long)(T - 1) * (k + 1) / nch);
+    ZTRY(dec_fast_bwd_steps(c, io, t_hi, t_lo));
+    if (nch > 1) {
+      ZTRY(stream_fork(c.s, (*ss)->s, 2));
+      ZTRY(dec_recurrent_wgrads(c.d, c.w, G, t_lo, t_hi, k == 0 ? gb : 1.f, 1, (*ss)->s));
+    }
+  }
+  if (nch > 1) ZCHECK(hipEventRecord((*ss)->done, (*ss)->s) == hipSuccess, "hipEventRecord failed");
+  return 0;
+}
+// generic GEMMs and elementwise kernels, step by step
+int bwd_generic_steps(const DecCtx& c, const DecBwdIO& io) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
+  const int B = d.B, T = d.T, H = d.H, GL = w.GL, XD = w.XD, POL = w.POL;
+  const long sG = (long)B * GL, sH = (long)B * H, s3 = 3 * sH;
+  for (int t = T - 1; t >= 1; --t) {
+    const float* gin = w.Gin + t * sG;
+    const long o = (long)t * sH;
+    float* dy = w.DY + (long)t * B * POL;
+    const float* dxn = (t + 1 < T) ? w.DX + (long)(t + 1) * B * XD : nullptr;
+    hipLaunchKernelGGL(dec_devec_bwd_k, dim3(B), dim3(256), 0, s, d, *st, io.dpose, io.drpos, io.drrot, dxn, XD, io.gaze,
+                       io.pose, io.rpos, io.rrot, w.carry, dy, POL, t);
+    ZLAUNCH_CHECK("dec_devec_bwd");
+    // dH1 total = dy W2 + carried   [film: through layer3, the modulation and layer2]
+    if (d.film) {
+      const long og = (long)t * B * 2 * H;
+      ZTRY(gemm_nn(dy, POL, P->l3_w, H, w.dF2, H, B, d.PO, H, 0.f, s));
+      hipLaunchKernelGGL(film_bwd_k, g1(sH), dim3(256), 0, s, w.dF2, (long)H, w.A2 + o, w.GAM + og + H, (long)2 * H,
+                         w.D2 + o, w.DGAM + og + H, w.DBET + og + H, B, H);
+      ZTRY(gemm_nn(w.D2 + o, H, P->l2_w, H, w.dH1c, H, B, H, H, 1.f, s));
+    } else {
+      ZTRY(gemm_nn(dy, POL, P->l2_w, H, w.dH1c, H, B, d.PO, H, 1.f, s));
+    }
+    hipLaunchKernelGGL(gru_gate_bwd_k, g1(sH), dim3(256), 0, s, w.dH1c, (const f4*)w.GT1 + o,
+                       w.H1 + o - sH, w.DI1 + t * s3, w.DH1 + t * s3, w.t0, B, H);
+    // t0 = dH1 * z (direct path); dH1c <- t0 + DH1 W_hh1 ; dH0 total = dH0c + DI1 W_ih1
+    ZTRY(k_copy(w.dH1c, w.t0, sH, s));
+    ZTRY(gemm_nn(w.DH1 + t * s3, 3 * H, P->w_hh1, H, w.dH1c, H, B, 3 * H, H, 1.f, s));
+    ZTRY(gemm_nn(w.DI1 + t * s3, 3 * H, P->w_ih1, H, w.dH0c, H, B, 3 * H, H, 1.f, s));
+    hipLaunchKernelGGL(gru_gate_bwd_k, g1(sH), dim3(256), 0, s, w.dH0c, (const f4*)w.GT0 + o,
+                       w.H0 + o - sH, w.DI0 + t * s3, w.DH0 + t * s3, w.t0, B, H);
+    ZTRY(k_copy(w.dH0c, w.t0, sH, s));
+    ZTRY(gemm_nn(w.DH0 + t * s3, 3 * H, P->w_hh0, H, w.dH0c, H, B, 3 * H, H, 1.f, s));
+    // dGin = DI0 W_ih0 -> [dhid | dx]
+    ZTRY(gemm_nn(w.DI0 + t * s3, 3 * H, P->w_ih0, H + XD, w.dGin, GL, B, 3 * H, H + XD, 0.f, s));
+    if (d.film) {
+      const long og = (long)t * B * 2 * H;
+      hipLaunchKernelGGL(film_bwd_k, g1(sH), dim3(256), 0, s, w.dGin, (long)GL, w.A0 + o, w.GAM + og, (long)2 * H,
+                         w.D0 + o, w.DGAM + og, w.DBET + og, B, H);
+    } else {
+      hipLaunchKernelGGL(elu_bwd_rows_k, g1(sH), dim3(256), 0, s, w.D0 + o, w.dGin, gin, B, H, GL);
+    }
+    // dx_t = dGin[:, H:] + D0 W0
+    float* dx = w.DX + (long)t * B * XD;
+    hipLaunchKernelGGL(copy_cols_k, g1((long)B * XD), dim3(256), 0, s, dx, (long)XD, w.dGin, (long)GL, H, XD, B);
+    ZLAUNCH_CHECK("dec_bwd_step");
+    ZTRY(gemm_nn(w.D0 + o, H, P->l0_w, XD, dx, XD, B, H, XD, 1.f, s));
+  }
+  return 0;
+}
+// CellStateEncoder backward: dH0c / dH1c are the grads wrt its two output halves.  The input-gradient chain (four batch-sized
+// products, the ELU' factors in their epilogues) is what the caller's next kernels wait for (dstyle -> the style encoder's
+// backward): it goes first; the weight / bias gradients need only its intermediates and, with deferred GEMMs (gs != null), join
+// the recurrent layers' on the weight-gradient stream.
+int dec_cse_bwd(const DecCtx& c, const ZeggsDecGrads* G, float gb, hipStream_t gs) {
+  const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
+  const int B = c.d.B, H = c.d.H, CI = c.d.PI + c.d.ST;
+  // out = [H0_init | H1_init] = cse_b W2^T + b2
+  float* db = w.t0;                       // [B,H] grad wrt cse_b
+  float* da = w.t0 + (long)B * H;         // [B,H] grad wrt cse_a
+  ZTRY(gemm_nn(w.dH0c, H, P->c2_w, H, db, H, B, H, H, 0.f, s));
+  ZTRY(gemm_nn_actbwd(w.dH1c, H, P->c2_w + (long)H * H, H, db, H, B, H, H, 1.f, w.cse_b, H, ACT_ELU, s));
+  ZTRY(gemm_nn_actbwd(db, H, P->c1_w, H, da, H, B, H, H, 0.f, w.cse_a, H, ACT_ELU, s));
+  ZTRY(gemm_nn(da, H, P->c0_w, CI, w.t1, CI, B, H, CI, 0.f, s));   // t1 = d cse_in [B, PI+ST]
+  if (gs) ZTRY(stream_fork(s, gs, 1));
+  else gs = s;
+  ZTRY(gemm_tn(w.dH0c, H, w.cse_b, H, G->c2_w, H, B, H, H, gb, gs));
+  ZTRY(gemm_tn(w.dH1c, H, w.cse_b, H, G->c2_w + (long)H * H, H, B, H, H, gb, gs));
+  ZTRY(k_colsum(G->c2_b, w.dH0c, B, H, H, gb, gs));
+  ZTRY(k_colsum(G->c2_b + H, w.dH1c, B, H, H, gb, gs));
+  ZTRY(gemm_tn(db, H, w.cse_a, H, G->c1_w, H, B, H, H, gb, gs));
+  ZTRY(k_colsum(G->c1_b, db, B, H, H, gb, gs));
+  ZTRY(gemm_tn(da, H, w.cse_in, CI, G->c0_w, CI, B, H, CI, gb, gs));
+  return k_colsum(G->c0_b, da, B, H, H, gb, gs);
+}
+// the gradients of the conditioning inputs: DX's speech / style columns, the style through FiLM's predictors, the style of frame 0
+int dec_cond_grads(const DecCtx& c, float* dspeech, float* dstyle) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
+  const int B = d.B, T = d.T, H = d.H;
+  hipLaunchKernelGGL(dec_scatter_cond_grad_k, g1((long)T * B * (d.SP + d.ST)), dim3(256), 0, s, d, w.DX, w.XD, dspeech, dstyle);
+  if (d.film) {   // the style reaches the steps through the two predictors only
+    const long M1 = (long)(T - 1) * B, sg = (long)B * 2 * H, sS = (long)B * d.ST;
+    ZTRY(gemm_nn(w.DGAM + sg, 2 * H, P->g_w, d.ST, w.dSTm + sS, d.ST, (int)M1, 2 * H, d.ST, 0.f, s));
+    ZTRY(gemm_nn(w.DBET + sg, 2 * H, P->be_w, d.ST, w.dSTm + sS, d.ST, (int)M1, 2 * H, d.ST, 1.f, s));
+    hipLaunchKernelGGL(style_grad_from_time_major_k, g1((long)T * B * d.ST), dim3(256), 0, s, d, w.dSTm, dstyle);
+  }
+  hipLaunchKernelGGL(add_style0_grad_k, g1((long)B * d.ST), dim3(256), 0, s, d, w.t1, dstyle);
+  ZLAUNCH_CHECK("dec_bwd_tail");
+  return 0;
+}
+
+}  // namespace
+
+extern "C" size_t zeggs_decoder_workspace_bytes(const ZeggsDecDims* d, int training) {
+  Arena a(nullptr, 0);
+  carve_dec(*d, training, a);
+  return a.off + 256;
+}
+
+// every forward entry point: validation, carve, head, the paths in the order they are tried, the state after the last frame
+static int decoder_fwd_impl(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st, const DecFwdIO& io,
+                            int training, const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
+                            const ZeggsDecCall* call) {
+  const ZeggsDecDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  const bool fwd_prepared = call && (call->prepared & 1);
+  unsigned* status = call ? call->status : nullptr;
+  ZCHECK(d.PI == d.PO + 3, "decoder: pose_input_size must be pose_output_size + 3 (gaze)");
+  ZCHECK(d.B >= 1 && d.T >= 1, "decoder: empty batch or sequence");
+  Arena a(ws, ws_bytes);
+  DecWs w = carve_dec(d, training, a);
+  ZCHECK(a.ok(), "decoder: workspace too small (%zu < %zu)", ws_bytes, a.off);
+  const DecCtx c{d, P, st, w, s};
+  const long sH = (long)d.B * d.H;
+  if (!training) ZTRY(k_fill(w.Gin, 2L * d.B * w.GL, 0.f, s));   // ring slots: pad columns must be finite (GEMV decode path)
+  const bool fast = g_decoder_fast && dec_fast_supported(d);
+  // training, batch <= 64: will the rollout run as one persistent launch?  Then its head is the five-launch prologue
+  const bool tp_path = fast && training && dec_tp_supported(d, w) && g_sweep_kernels[SWEEP_ROLLOUT].may_run(s);
+  const bool tp_pro = tp_path && g_tp_prologue && !h_in && d.T > 1 && !d.film;
+  ZTRY(tp_pro ? dec_head_prologue(c, io, fwd_prepared) : dec_head(c, io, h_in));
+  if (training && d.T > 1) ZTRY(dec_train_inputs(c, io, tp_pro));
+  bool done = false;
+  if (fast && !training) ZTRY(fwd_persistent_decode(c, io, status, &done));
+  if (!done && tp_path) ZTRY(fwd_persistent_rollout(c, io, fwd_prepared, tp_pro, status, &done));
+  if (!done && fast) ZTRY(fwd_stage_launches(c, io, training));
+  else if (!done) ZTRY(fwd_generic_steps(c, io, training));
+  if (h_out) {      // the state after the last frame (inference: its ring slot)
+    const long last = (training ? d.T - 1 : (d.T - 1) & 1) * sH;
+    ZTRY(k_copy(h_out, w.H0 + last, sH, s));
+    ZTRY(k_copy(h_out + sH, w.H1 + last, sH, s));
+  }
+  return 0;
+}
+
+extern "C" int zeggs_decoder_fwd(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                 const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
+                                 const float* speech, const float* style, float* pose, float* rpos, float* rrot,
+                                 int training, void* ws, size_t ws_bytes, void* stream) {
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot};
+  return decoder_fwd_impl(dp, P, st, io, training, nullptr, nullptr, ws, ws_bytes, stream, nullptr);
+}
+extern "C" int zeggs_decoder_fwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                    const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
+                                    const float* speech, const float* style, float* pose, float* rpos, float* rrot,
+                                    int training, void* ws, size_t ws_bytes, void* stream, const ZeggsDecCall* call) {
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot};
+  return decoder_fwd_impl(dp, P, st, io, training, nullptr, nullptr, ws, ws_bytes, stream, call);
+}
+
+// Chunked (streaming) decode: frame 0 of the chunk is the last frame already produced (its pose / root state come in as
+// pose0 / rpos0 / rrot0), h_in [2,B,H] is the GRU state after that frame (NULL: first chunk, CellStateEncoder), h_out
+// receives the state after the chunk's last frame.  Inference only (2-slot rings).
+extern "C" int zeggs_decoder_fwd_state(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                       const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
+                                       const float* speech, const float* style, float* pose, float* rpos, float* rrot,
+                                       const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream) {
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot};
+  return decoder_fwd_impl(dp, P, st, io, 0, h_in, h_out, ws, ws_bytes, stream, nullptr);
+}
+// the same with per-call controls: ZeggsDecCall.status receives the give-up bit of the B = 1 persistent kernel, so that a caller
+// that feeds the returned state into the NEXT chunk (zeggs/stream.py) can notice a rollout that did not complete and redo it
+extern "C" int zeggs_decoder_fwd_state_ex(const ZeggsDecDims* dp, const ZeggsDecParams* P, const ZeggsDecStats* st,
+                                          const float* pose0, const float* rpos0, const float* rrot0, const float* gaze,
+                                          const float* speech, const float* style, float* pose, float* rpos, float* rrot,
+                                          const float* h_in, float* h_out, void* ws, size_t ws_bytes, void* stream,
+                                          const ZeggsDecCall* call) {
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot};
+  return decoder_fwd_impl(dp, P, st, io, 0, h_in, h_out, ws, ws_bytes, stream, call);
 }
 
 // ---------------------------------------------------------------- batch decode: many clips per weight-stationary rollout
@@ -723,8 +788,8 @@ extern "C" int zeggs_decoder_batch_prepare(const ZeggsDecDims* dp, const ZeggsDe
   ZCHECK(a.ok(), "decoder batch prepare: workspace too small (%zu < %zu)", ws_bytes, a.off);
   const int mask = batch_sweep_mask(d, w);
   if (!mask) return 0;
-  ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-  ZTRY(dec_tp_pack(d, P, st, w, s, (mask & 2) ? 1 : 0));
+  const DecCtx c{d, P, st, w, s};
+  ZTRY(dec_tp_pack(c, (mask & 2) ? 1 : 0));
   return mask;
 }
 
@@ -734,23 +799,17 @@ extern "C" int zeggs_decoder_state_init(const ZeggsDecDims* dp, const ZeggsDecPa
                                         const float* style0, float* h_out, void* ws, size_t ws_bytes, void* stream) {
   ZeggsDecDims d = *dp;
   d.T = 1;                                        // gaze0 [B,3], style0 [B,ST]: one frame per row
-  hipStream_t s = (hipStream_t)stream;
   ZCHECK(d.PI == d.PO + 3, "decoder: pose_input_size must be pose_output_size + 3 (gaze)");
   ZCHECK(d.B >= 1, "decoder: empty batch");
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(d, 0, a);
   ZCHECK(a.ok(), "decoder state init: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  const int B = d.B, H = d.H, CI = d.PI + d.ST;
-  const long sH = (long)B * H;
+  const DecCtx c{d, P, st, w, (hipStream_t)stream};
   // (frame-0 copies of the outputs land in step scratch: Y [B,POL], gi [B,3H])
-  hipLaunchKernelGGL(dec_init_k, dim3(B), dim3(256), 0, s, d, *st, pose0, rpos0, rrot0, gaze0, style0, w.Y, w.gi, w.gi + 4L * B,
-                     w.cse_in, w.Gin, w.GL);
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze0, nullptr, style0, w.Y, w.gi, w.gi + 4L * d.B};
+  dec_init(c, io, w.Gin);
   ZLAUNCH_CHECK("dec_init");
-  ZTRY(gemm_nt(w.cse_in, CI, P->c0_w, CI, w.cse_a, H, P->c0_b, B, H, CI, ACT_ELU, 0.f, s));
-  ZTRY(gemm_nt(w.cse_a, H, P->c1_w, H, w.cse_b, H, P->c1_b, B, H, H, ACT_ELU, 0.f, s));
-  ZTRY(gemm_nt(w.cse_b, H, P->c2_w, H, h_out, H, P->c2_b, B, H, H, ACT_NONE, 0.f, s));
-  ZTRY(gemm_nt(w.cse_b, H, P->c2_w + (long)H * H, H, h_out + sH, H, P->c2_b + H, B, H, H, ACT_NONE, 0.f, s));
-  return 0;
+  return dec_cse(c, h_out, h_out + (long)d.B * d.H);
 }
 
 // mode 0: the sweep (first use on a process validated by a device sync and the error word -- never inside a stream capture --,
@@ -769,24 +828,17 @@ extern "C" int zeggs_decoder_fwd_batch(const ZeggsDecDims* dp, const ZeggsDecPar
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec_batch(d, a);
   ZCHECK(a.ok(), "decoder batch: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  unsigned* status = call ? call->status : nullptr;
+  const DecCtx c{d, P, st, w, s};
+  const DecFwdIO io{pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot};
   SweepKernel& tpk = g_sweep_kernels[SWEEP_ROLLOUT];
   const int mask = mode == 0 && tpk.may_run(s) ? batch_sweep_mask(d, w) : 0;
   if (mask) {
-    const int B = d.B, H = d.H, GL = w.GL, XD = w.XD;
-    const long sG = (long)B * GL;
-    float* gin1 = w.Gin + sG;
-    ZTRY(k_fill(w.Gin, 2 * sG, 0.f, s));
-    hipLaunchKernelGGL(dec_init_k, dim3(B), dim3(256), 0, s, d, *st, pose0, rpos0, rrot0, gaze, style, pose, rpos, rrot, w.cse_in,
-                       gin1, GL);
-    hipLaunchKernelGGL(dec_fill_cond_k, g1((long)B * (d.SP + d.ST)), dim3(256), 0, s, d, speech, style, w.Gin, GL, 1, 1, sG, 1);
-    ZLAUNCH_CHECK("dec_fill_cond");
-    ZTRY(gemm_nt(gin1 + H, GL, P->l0_w, XD, gin1, GL, P->l0_b, B, H, XD, ACT_ELU, 0.f, s));   // hid_1 = ELU(W0 x_1 + b0)
-    if (!(call && (call->prepared & 1) && (call->prepared & 2) == (mask & 2))) {
-      ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-      ZTRY(dec_tp_pack(d, P, st, w, s, (mask & 2) ? 1 : 0));
-    }
-    ZTRY(dec_tb_run(d, P, st, w, gaze, speech, style, pose, rpos, rrot, h_in, h_out, s, tpk.status_arg(status)));
+    ZTRY(k_fill(w.Gin, 2L * d.B * w.GL, 0.f, s));
+    dec_init(c, io, w.Gin + (long)d.B * w.GL);
+    ZTRY(dec_fill_cond(c, io, 1, 1, 1));
+    ZTRY(dec_hid1(c));
+    if (!(call && (call->prepared & 1) && (call->prepared & 2) == (mask & 2))) ZTRY(dec_tp_pack(c, (mask & 2) ? 1 : 0));
+    ZTRY(dec_tb_run(c, io, h_in, h_out, tpk.status_arg(call ? call->status : nullptr)));
     t_batch_last_path = 1;
     bool ok = false;
     ZTRY(tpk.settle(s, tp_errword(w), &ok));
@@ -794,8 +846,7 @@ extern "C" int zeggs_decoder_fwd_batch(const ZeggsDecDims* dp, const ZeggsDecPar
     // a bounded wait gave up: disabled for this process, the stage launches redo the chunk
   }
   t_batch_last_path = 2;
-  return decoder_fwd_impl(dp, P, st, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, 0, h_in, h_out, ws, ws_bytes,
-                          stream, nullptr);
+  return decoder_fwd_impl(dp, P, st, io, 0, h_in, h_out, ws, ws_bytes, stream, nullptr);
 }
 
 // error word of the chained (run-ahead) stage launches of the last rollout that used `ws`: 0 = every hand-off wait was
@@ -848,17 +899,14 @@ extern "C" int zeggs_decoder_prepare(const ZeggsDecDims* dp, const ZeggsDecParam
   // only once the kernels have been validated on this process (the first use takes the ordinary path)
   const SweepKernel &tpk = g_sweep_kernels[SWEEP_ROLLOUT], &bpk = g_sweep_kernels[SWEEP_BPTT];
   if (!(fast && d.T > 1 && tpk.enabled && tpk.state == 1 && dec_tp_supported(d, w))) return 0;
-  ZTRY(dec_fast_merge_prep(d, P, st, w, s));
-  ZTRY(dec_tp_pack(d, P, st, w, s));
+  const DecCtx c{d, P, st, w, s};
+  ZTRY(dec_tp_pack(c));
   ZTRY(dec_tp_zero(d, w, s));
   int mask = 1;
   if (bpk.enabled && bpk.state == 1 && dec_bp_supported(d, w)) {
-    ZTRY(dec_bp_pack(d, P, w, s));
+    ZTRY(dec_bp_pack(c));
     // ... and the zero state the backward starts from (carries, frame-0 slot of DX, arrival slots + error word)
-    ZTRY(k_fill(w.dH0c, (long)d.B * d.H, 0.f, s));
-    ZTRY(k_fill(w.dH1c, (long)d.B * d.H, 0.f, s));
-    ZTRY(k_fill(w.carry, (long)2 * d.B * 8, 0.f, s));
-    ZTRY(k_fill(w.DX, (long)d.B * w.XD, 0.f, s));
+    ZTRY(dec_bwd_zero_state(c, true));
     ZTRY(dec_bp_zero_slots(w, s));
     mask |= 2;
   }
@@ -894,154 +942,38 @@ extern "C" int zeggs_decoder_bwd_ex(const ZeggsDecDims* dp, const ZeggsDecParams
   Arena a(ws, ws_bytes);
   DecWs w = carve_dec(d, 1, a);
   ZCHECK(a.ok(), "decoder bwd: workspace too small (was the forward run with training=1?)");
-  const int B = d.B, T = d.T, H = d.H, GL = w.GL, XD = w.XD, CI = d.PI + d.ST, POL = w.POL;
-  const long sG = (long)B * GL, sH = (long)B * H, s3 = 3 * sH;
-  if (!bwd_prepared) {      // (zeggs_decoder_prepare has done it)
-    ZTRY(k_fill(w.dH0c, sH, 0.f, s));
-    ZTRY(k_fill(w.dH1c, sH, 0.f, s));
-    ZTRY(k_fill(w.carry, (long)2 * B * 8, 0.f, s));
-    ZTRY(k_fill(w.DX, (long)B * XD, 0.f, s));          // slot t = 0 unused but read by the scatter
-  }
-  ZCHECK(T > 1, "decoder bwd: T must be > 1");
-  bool wgrads_done = false;
-  SideStream* ss = nullptr;
+  const DecCtx c{d, P, st, w, s};
+  const DecBwdIO io{gaze, pose, rpos, rrot, dpose, drpos, drrot};
+  if (!bwd_prepared) ZTRY(dec_bwd_zero_state(c, true));      // (zeggs_decoder_prepare has done it)
+  ZCHECK(d.T > 1, "decoder bwd: T must be > 1");
   const bool fast_path = g_decoder_fast && dec_fast_supported(d);
-  // ---- batch <= 32: the whole sweep as one persistent launch (train_bwd_persistent.hip)
+  // ---- the sweep t = T-1 .. 1 leaves DY, DI*, DH*, D0, DX and the final carries.  Batch <= 64: as one persistent launch
+  // (train_bwd_persistent.hip); if it gave up on its first use, the stage kernels redo it from clean carries
   bool swept = false;
+  SideStream* ss = nullptr;      // set where the sweep has started the weight gradients beside itself
   SweepKernel& bpk = g_sweep_kernels[SWEEP_BPTT];
   if (fast_path && dec_bp_supported(d, w) && bpk.may_run(s)) {
-    ZTRY(dec_bp_run(d, P, st, w, gaze, pose, rpos, rrot, dpose, drpos, drrot, s, bwd_prepared, bpk.status_arg(status)));
+    ZTRY(dec_bp_run(c, io, bwd_prepared, bpk.status_arg(status)));
     ZTRY(bpk.settle(s, bp_errword(w), &swept));
-    if (!swept) {   // the stage kernels redo the sweep from clean carries
-      ZTRY(k_fill(w.dH0c, sH, 0.f, s));
-      ZTRY(k_fill(w.dH1c, sH, 0.f, s));
-      ZTRY(k_fill(w.carry, (long)2 * B * 8, 0.f, s));
-    }
+    if (!swept) ZTRY(dec_bwd_zero_state(c, false));
   }
-  if (swept) {
-    // nothing left to do here: DY, DI*, DH*, D0, DX and the final carries are in place
-  } else if (fast_path) {
-    ZTRY(dec_fast_pack_bwd(d, P, st, w, s));
-    // The sweep is a chain of small dependent launches that leaves most of the chip idle; the weight-gradient
-    // GEMMs of the steps already swept run beside it on a low-priority stream, chunk by chunk.
-    const int nch = g_bwd_chunks < T - 1 ? g_bwd_chunks : T - 1;
-    if (nch > 1) ZTRY(side_stream(&ss));
-    for (int c = 0; c < nch; ++c) {
-      const int t_hi = T - 1 - (int)((long)(T - 1) * c / nch), t_lo = T - (int)((long)(T - 1) * (c + 1) / nch);
-      ZTRY(dec_fast_bwd_steps(d, P, st, w, gaze, pose, rpos, rrot, dpose, drpos, drrot, t_hi, t_lo, s));
-      if (nch > 1) {
-        ZCHECK(hipEventRecord(ss->chunk, s) == hipSuccess, "hipEventRecord failed");
-        ZCHECK(hipStreamWaitEvent(ss->s, ss->chunk, 0) == hipSuccess, "hipStreamWaitEvent failed");
-        ZTRY(dec_recurrent_wgrads(d, w, G, t_lo, t_hi, c == 0 ? gb : 1.f, 1, ss->s));
-      }
-    }
-    if (nch > 1) {
-      ZCHECK(hipEventRecord(ss->done, ss->s) == hipSuccess, "hipEventRecord failed");
-      wgrads_done = true;
-    }
-  } else {
-  for (int t = T - 1; t >= 1; --t) {
-    const float* gin = w.Gin + t * sG;
-    const long o = (long)t * sH;
-    float* dy = w.DY + (long)t * B * POL;
-    const float* dxn = (t + 1 < T) ? w.DX + (long)(t + 1) * B * XD : nullptr;
-    hipLaunchKernelGGL(dec_devec_bwd_k, dim3(B), dim3(256), 0, s, d, *st, dpose, drpos, drrot, dxn, XD, gaze, pose, rpos,
-                       rrot, w.carry, dy, POL, t);
-    ZLAUNCH_CHECK("dec_devec_bwd");
-    // dH1 total = dy W2 + carried   [film: through layer3, the modulation and layer2]
-    if (d.film) {
-      const long og = (long)t * B * 2 * H;
-      ZTRY(gemm_nn(dy, POL, P->l3_w, H, w.dF2, H, B, d.PO, H, 0.f, s));
-      hipLaunchKernelGGL(film_bwd_k, g1(sH), dim3(256), 0, s, w.dF2, (long)H, w.A2 + o, w.GAM + og + H, (long)2 * H,
-                         w.D2 + o, w.DGAM + og + H, w.DBET + og + H, B, H);
-      ZTRY(gemm_nn(w.D2 + o, H, P->l2_w, H, w.dH1c, H, B, H, H, 1.f, s));
-    } else {
-      ZTRY(gemm_nn(dy, POL, P->l2_w, H, w.dH1c, H, B, d.PO, H, 1.f, s));
-    }
-    hipLaunchKernelGGL(gru_gate_bwd_k, g1(sH), dim3(256), 0, s, w.dH1c, (const f4*)w.GT1 + o,
-                       w.H1 + o - sH, w.DI1 + t * s3, w.DH1 + t * s3, w.t0, B, H);
-    // t0 = dH1 * z (direct path); dH1c <- t0 + DH1 W_hh1 ; dH0 total = dH0c + DI1 W_ih1
-    ZTRY(k_copy(w.dH1c, w.t0, sH, s));
-    ZTRY(gemm_nn(w.DH1 + t * s3, 3 * H, P->w_hh1, H, w.dH1c, H, B, 3 * H, H, 1.f, s));
-    ZTRY(gemm_nn(w.DI1 + t * s3, 3 * H, P->w_ih1, H, w.dH0c, H, B, 3 * H, H, 1.f, s));
-    hipLaunchKernelGGL(gru_gate_bwd_k, g1(sH), dim3(256), 0, s, w.dH0c, (const f4*)w.GT0 + o,
-                       w.H0 + o - sH, w.DI0 + t * s3, w.DH0 + t * s3, w.t0, B, H);
-    ZTRY(k_copy(w.dH0c, w.t0, sH, s));
-    ZTRY(gemm_nn(w.DH0 + t * s3, 3 * H, P->w_hh0, H, w.dH0c, H, B, 3 * H, H, 1.f, s));
-    // dGin = DI0 W_ih0 -> [dhid | dx]
-    ZTRY(gemm_nn(w.DI0 + t * s3, 3 * H, P->w_ih0, H + XD, w.dGin, GL, B, 3 * H, H + XD, 0.f, s));
-    if (d.film) {
-      const long og = (long)t * B * 2 * H;
-      hipLaunchKernelGGL(film_bwd_k, g1(sH), dim3(256), 0, s, w.dGin, (long)GL, w.A0 + o, w.GAM + og, (long)2 * H,
-                         w.D0 + o, w.DGAM + og, w.DBET + og, B, H);
-    } else {
-      hipLaunchKernelGGL(elu_bwd_rows_k, g1(sH), dim3(256), 0, s, w.D0 + o, w.dGin, gin, B, H, GL);
-    }
-    // dx_t = dGin[:, H:] + D0 W0
-    float* dx = w.DX + (long)t * B * XD;
-    hipLaunchKernelGGL(copy_cols_k, g1((long)B * XD), dim3(256), 0, s, dx, (long)XD, w.dGin, (long)GL, H, XD, B);
-    ZLAUNCH_CHECK("dec_bwd_step");
-    ZTRY(gemm_nn(w.D0 + o, H, P->l0_w, XD, dx, XD, B, H, XD, 1.f, s));
-  }
-  }
+  if (!swept && fast_path) ZTRY(bwd_stage_sweep(c, io, G, gb, &ss));
+  else if (!swept) ZTRY(bwd_generic_steps(c, io));
   // ---- weight gradients of the recurrent layers.  Option "defer_wgrads": the seven large GEMMs (K = B (T-1), they read only
   // what the sweep saved) start NOW on the library's second stream, beside the CellStateEncoder backward below and whatever the
   // caller enqueues on `s` after this call (the encoders' backward).  No join here: the caller makes every consumer of the
   // decoder gradients wait for zeggs_side_stream.
-  const bool deferred = !wgrads_done && defer_wgrads && !stream_capturing(s);
-  if (deferred) {
-    hipStream_t gs = (hipStream_t)call->wgrad_stream;
-    hipEvent_t fork = nullptr;
-    ZTRY(fork_event(&fork));
-    ZCHECK(hipEventRecord(fork, s) == hipSuccess, "hipEventRecord failed");
-    ZCHECK(hipStreamWaitEvent(gs, fork, 0) == hipSuccess, "hipStreamWaitEvent failed");
-    // (value 2: only the first half of the parameter order here -- the caller all-reduces it while zeggs_decoder_wgrads
-    //  computes the second half)
-    // The bias sums (a dozen column sums over the same saves) go with them: since the split-K retune the GEMMs are the shorter
-    // of the two queues.
-    ZTRY(dec_recurrent_wgrads(d, w, G, 1, T - 1, gb, fast_path ? 1 : 0, gs, (defer_wgrads == 2 ? 1 : 5) | 2));
-  } else if (!wgrads_done) {
-    ZTRY(dec_recurrent_wgrads(d, w, G, 1, T - 1, gb, fast_path ? 1 : 0, s));
-  }
-  // ---- CellStateEncoder backward: dH0c / dH1c are the grads wrt its two output halves.  The input-gradient chain (four
-  // batch-sized products, the ELU' factors in their epilogues) is what the caller's next kernels wait for (dstyle -> the style
-  // encoder's backward): it goes first; the weight / bias gradients need only its intermediates and, with deferred GEMMs, join
-  // the recurrent layers' on the weight-gradient stream.
-  {
-    // out = [H0_init | H1_init] = cse_b W2^T + b2
-    float* db = w.t0;                       // [B,H] grad wrt cse_b
-    float* da = w.t0 + sH;                  // [B,H] grad wrt cse_a
-    ZTRY(gemm_nn(w.dH0c, H, P->c2_w, H, db, H, B, H, H, 0.f, s));
-    ZTRY(gemm_nn_actbwd(w.dH1c, H, P->c2_w + (long)H * H, H, db, H, B, H, H, 1.f, w.cse_b, H, ACT_ELU, s));
-    ZTRY(gemm_nn_actbwd(db, H, P->c1_w, H, da, H, B, H, H, 0.f, w.cse_a, H, ACT_ELU, s));
-    ZTRY(gemm_nn(da, H, P->c0_w, CI, w.t1, CI, B, H, CI, 0.f, s));   // t1 = d cse_in [B, PI+ST]
-    hipStream_t ws_ = s;
-    if (deferred) {
-      ws_ = (hipStream_t)call->wgrad_stream;
-      hipEvent_t fork = nullptr;
-      ZTRY(fork_event(&fork, 1));
-      ZCHECK(hipEventRecord(fork, s) == hipSuccess, "hipEventRecord failed");
-      ZCHECK(hipStreamWaitEvent(ws_, fork, 0) == hipSuccess, "hipStreamWaitEvent failed");
-    }
-    ZTRY(gemm_tn(w.dH0c, H, w.cse_b, H, G->c2_w, H, B, H, H, gb, ws_));
-    ZTRY(gemm_tn(w.dH1c, H, w.cse_b, H, G->c2_w + (long)H * H, H, B, H, H, gb, ws_));
-    ZTRY(k_colsum(G->c2_b, w.dH0c, B, H, H, gb, ws_));
-    ZTRY(k_colsum(G->c2_b + H, w.dH1c, B, H, H, gb, ws_));
-    ZTRY(gemm_tn(db, H, w.cse_a, H, G->c1_w, H, B, H, H, gb, ws_));
-    ZTRY(k_colsum(G->c1_b, db, B, H, H, gb, ws_));
-    ZTRY(gemm_tn(da, H, w.cse_in, CI, G->c0_w, CI, B, H, CI, gb, ws_));
-    ZTRY(k_colsum(G->c0_b, da, B, H, H, gb, ws_));
-  }
-  hipLaunchKernelGGL(dec_scatter_cond_grad_k, g1((long)T * B * (d.SP + d.ST)), dim3(256), 0, s, d, w.DX, XD, dspeech,
-                     dstyle);
-  if (d.film) {   // the style reaches the steps through the two predictors only
-    const long M1 = (long)(T - 1) * B, sg = (long)B * 2 * H, sS = (long)B * d.ST;
-    ZTRY(gemm_nn(w.DGAM + sg, 2 * H, P->g_w, d.ST, w.dSTm + sS, d.ST, (int)M1, 2 * H, d.ST, 0.f, s));
-    ZTRY(gemm_nn(w.DBET + sg, 2 * H, P->be_w, d.ST, w.dSTm + sS, d.ST, (int)M1, 2 * H, d.ST, 1.f, s));
-    hipLaunchKernelGGL(style_grad_from_time_major_k, g1((long)T * B * d.ST), dim3(256), 0, s, d, w.dSTm, dstyle);
-  }
-  hipLaunchKernelGGL(add_style0_grad_k, g1((long)B * d.ST), dim3(256), 0, s, d, w.t1, dstyle);
-  ZLAUNCH_CHECK("dec_bwd_tail");
-  if (wgrads_done) ZCHECK(hipStreamWaitEvent(s, ss->done, 0) == hipSuccess, "hipStreamWaitEvent failed");   // join
+  const bool deferred = !ss && defer_wgrads && !stream_capturing(s);
+  hipStream_t gs = deferred ? (hipStream_t)call->wgrad_stream : nullptr;
+  // (value 2: only the first half of the parameter order here -- the caller all-reduces it while zeggs_decoder_wgrads
+  //  computes the second half)
+  // The bias sums (a dozen column sums over the same saves) go with them: since the split-K retune the GEMMs are the shorter
+  // of the two queues.
+  const int what = deferred ? (defer_wgrads == 2 ? 1 : 5) | 2 : 7;
+  if (deferred) ZTRY(stream_fork(s, gs, 0));
+  if (!ss) ZTRY(dec_recurrent_wgrads(d, w, G, 1, d.T - 1, gb, fast_path ? 1 : 0, deferred ? gs : s, what));
+  ZTRY(dec_cse_bwd(c, G, gb, gs));
+  ZTRY(dec_cond_grads(c, dspeech, dstyle));
+  if (ss) ZCHECK(hipStreamWaitEvent(s, ss->done, 0) == hipSuccess, "hipStreamWaitEvent failed");   // join
   return 0;
 }

@@ -1172,7 +1172,8 @@ StageArgs base_args(const ZeggsDecDims& d, const ZeggsDecStats* st, const DecWs&
 // H = 1024 kernels decline it.
 int dec_fast_supported(const ZeggsDecDims& d) { return d.H % 16 == 0 && d.B <= 64 && d.PI == d.PO + 3 && d.PO >= 16; }
 
-int dec_fast_pack_fwd(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStream_t s) {
+int dec_fast_pack_fwd(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
   const int H = d.H, XD = w.XD;
   ZTRY(pack(w.pw_l0, P->l0_w, w.nTH, w.KBX, 0, XD, H, H, d.PO, XD, 0, s));
   ZTRY(pack(w.pw_ih0h, P->w_ih0, w.nT5, w.KBH, 1, H, 3 * H, H, d.PO, H + XD, 0, s, w.TG0));
@@ -1197,7 +1198,8 @@ int dec_fast_pack_fwd(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, 
 void dec_timing_mark(int i, hipStream_t s) { timing_mark(i, s); }
 
 // canonical operands of the folded stage: Mc = W0[:, :PO] diag(sigma_o/sigma_i) W2 [H,H], cvec [H]
-int dec_fast_merge_prep(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s) {
+int dec_fast_merge_prep(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
   const int H = d.H, XD = w.XD;
   const long n = (long)H * w.POL;
   const float *ow = d.film ? P->l3_w : P->l2_w, *ob = d.film ? P->l3_b : P->l2_b;     // the output layer [PO,H]
@@ -1209,16 +1211,18 @@ int dec_fast_merge_prep(const ZeggsDecDims& d, const ZeggsDecParams* P, const Ze
   return 0;
 }
 
-int dec_fast_pack_merged(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s) {
+int dec_fast_pack_merged(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
   const int H = d.H, XD = w.XD;
-  ZTRY(dec_fast_merge_prep(d, P, st, w, s));
+  ZTRY(dec_fast_merge_prep(c));
   ZTRY(pack(w.pw_m, w.Mc, w.nTH, w.KBH, 0, H, H, H, d.PO, H, 0, s, w.TMC));
   ZTRY(pack(w.pw_c, P->l0_w, w.nTH, w.KBC, 0, d.SP + (d.film ? 0 : d.ST), H, H, d.PO, XD, d.PI, s, w.TMC));
   ZTRY(pack(w.pw_l2c, d.film ? P->l3_w : P->l2_w, w.nTH, w.KBH, 4, H, 16, H, d.PO, H, 0, s, w.TMC));   // the output layer's root tile, per tile
   return 0;
 }
 
-int dec_fast_pack_bwd(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s) {
+int dec_fast_pack_bwd(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
   const int H = d.H, XD = w.XD;
   if (d.film) {
     ZTRY(pack(w.pb_l3, P->l3_w, w.nTH, w.KBPO, 2, d.PO, H, H, d.PO, H, 0, s));         // V[U][c] = W3[c][U]
@@ -1244,9 +1248,8 @@ int dec_fast_pack_bwd(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zegg
   return 0;
 }
 
-int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w,
-                       const float* gaze, const float* speech, const float* style, float* pose, float* rpos,
-                       float* rrot, int training, hipStream_t s) {
+int dec_fast_fwd_steps(const DecCtx& c, const DecFwdIO& io, int training) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
   const int B = d.B, T = d.T, H = d.H, NB = w.NB;
   const long sG = (long)B * w.GL, sH = (long)B * H;
   const long XB = 256L * NB;
@@ -1271,7 +1274,7 @@ int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
   const bool gemv = !training && B <= 2 && !(g_stage_variant & 1024);
   // 3 launches per step: layer2 of step t and layer0 of step t+1 run in ONE launch (variant 4096: 4 launches)
   const bool merged = !(g_stage_variant & 4096);
-  if (merged && T > 2) ZTRY(dec_fast_pack_merged(d, P, st, w, s));
+  if (merged && T > 2) ZTRY(dec_fast_pack_merged(c));
   Chain ch;
   ch.s[0] = ch.s[1] = s;
   {
@@ -1297,7 +1300,7 @@ int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
     const long o = (long)t * sH;
     const bool next = t + 1 < T;
     StageArgs a = base_args(d, st, w);
-    a.t = t; a.gaze = gaze; a.speech = speech; a.style = style; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
+    a.t = t; a.gaze = io.gaze; a.speech = io.speech; a.style = io.style; a.pose = io.pose; a.rpos = io.rpos; a.rrot = io.rrot;
     a.gemv = gemv;
     const float* gin_c = w.Gin + cs(t) * sG;
     float* gin_n = w.Gin + cs(t + 1) * sG;
@@ -1315,7 +1318,7 @@ int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
         const int f0 = t == 1 ? 1 : t + 1;                 // first frame of the block to compute
         const int nfr = (T - f0) < FILM_GB ? (T - f0) : FILM_GB;
         for (int which = 0; which < 2 && nfr > 0; ++which) {
-          GemmArgs g = gemm_args(style + (long)f0 * d.ST, which ? P->be_w : P->g_w, (which ? w.BET : w.GAM) + gslot(f0) * sg, nfr, 2 * H, d.ST);
+          GemmArgs g = gemm_args(io.style + (long)f0 * d.ST, which ? P->be_w : P->g_w, (which ? w.BET : w.GAM) + gslot(f0) * sg, nfr, 2 * H, d.ST);
           g.sam = d.ST; g.sak = 1; g.sbk = 1; g.sbn = d.ST; g.scm = sg; g.scn = 1;
           g.bsA0 = (long)T * d.ST; g.bsC0 = 2 * H; g.nb1 = 1; g.bias = which ? P->be_b : P->g_b;
           ZTRY(launch_gemm(g, B, s));
@@ -1415,16 +1418,15 @@ int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
   return 0;
 }
 
-int dec_fast_bwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w,
-                       const float* gaze, const float* pose, const float* rpos, const float* rrot,
-                       const float* dpose, const float* drpos, const float* drrot, int t_hi, int t_lo, hipStream_t s) {
+int dec_fast_bwd_steps(const DecCtx& c, const DecBwdIO& io, int t_hi, int t_lo) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
   const int B = d.B, T = d.T, H = d.H, NB = w.NB;
   const long sG = (long)B * w.GL, sH = (long)B * H, s3 = 3 * sH;
   if (T < 2) return 0;
   if (t_hi == T - 1) {   // first chunk of the sweep
     ZTRY(k_fill(w.xf_base_bwd, (long)(w.xf_bytes_bwd / 4), 0.f, s));
     const bool merged0 = !(g_stage_variant & 8192) && T > 2;   // carry slot read by the first dx stage (see below)
-    hipLaunchKernelGGL(dy_last_k, dim3(B), dim3(256), 0, s, d, *st, dpose, drpos, drrot, gaze, pose, rpos, rrot,
+    hipLaunchKernelGGL(dy_last_k, dim3(B), dim3(256), 0, s, d, *st, io.dpose, io.drpos, io.drrot, io.gaze, io.pose, io.rpos, io.rrot,
                        w.carry + (merged0 ? (long)((T - 1) & 1) * B * 8 : 0), w.DY + (long)(T - 1) * B * w.POL, w.POL,
                        w.DYxf, NB);
     ZLAUNCH_CHECK("dy_last");
@@ -1438,8 +1440,8 @@ int dec_fast_bwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const Zeg
     ZTRY(t_window.tick(s));
     const long o = (long)t * sH;
     StageArgs a = base_args(d, st, w);
-    a.t = t; a.gaze = gaze; a.cpose = pose; a.crpos = rpos; a.crrot = rrot; a.dpose = dpose; a.drpos = drpos;
-    a.drrot = drrot;
+    a.t = t; a.gaze = io.gaze; a.cpose = io.pose; a.crpos = io.rpos; a.crrot = io.rrot; a.dpose = io.dpose; a.drpos = io.drpos;
+    a.drrot = io.drrot;
     float* c_in = w.carry + (merged ? (long)(t & 1) * B * 8 : 0);
     float* c_out = w.carry + (merged ? (long)((t - 1) & 1) * B * 8 : 0);
     a.carry = c_in; a.carry_out = c_out;

@@ -143,8 +143,6 @@ inline DecWs carve_dec(const ZeggsDecDims& d, int training, Arena& a) {
       w.G0xf = a.f(T * KB0 * XB); w.G1xf = a.f(T * 128 * XB); w.G3xf = a.f(T * KB3 * XB);
       w.tp_n0s = a.f(3 * H * (long)w.POL); w.tp_n0 = a.f(3 * H * H); w.tp_cv0 = a.f(3 * H); w.tp_p1x = a.f(B * 3 * H);
       w.tp_cnt = (unsigned*)a.f(8192);      // arrival slots | error word (tp_errword) | stamps | wait statistics
-    }
-    if (d.H == 1024 && d.B <= 64 && !d.film) {
       w.bp_wr = a.f(256L * 8 * 113 * 64); w.bp_wl = a.f(256L * 8 * 64 * 64);
       w.bp_opy = a.f(T * (long)((d.PO + 15) / 16) * 512);
       w.bp_op1 = a.f(T * 4 * H * 32); w.bp_op0 = a.f(T * 4 * H * 32); w.bp_opd = a.f(T * H * 32);
@@ -204,46 +202,37 @@ extern int g_persistent_spin;      // bound of the device-side waits of the pers
 struct SweepSync;                  // sweep_sync.h
 SweepSync sweep_sync_args(unsigned* cnt, unsigned* err, unsigned* status);      // + the three tuning options above
 int require_cus(int n, const char* what);      // the sweeps are one workgroup per CU, all resident
+// ---------------------------------------------------------------- call records of the host entry points
+// the callee's world (dimensions, parameters, statistics, carved workspace, stream) and the caller's arrays of one forward / backward call
+struct DecCtx { const ZeggsDecDims& d; const ZeggsDecParams* P; const ZeggsDecStats* st; DecWs& w; hipStream_t s; };
+struct DecFwdIO { const float *pose0, *rpos0, *rrot0, *gaze, *speech, *style; float *pose, *rpos, *rrot; };
+struct DecBwdIO { const float *gaze, *pose, *rpos, *rrot, *dpose, *drpos, *drrot; };
 // persistent weight-stationary decode (decode_persistent.hip)
 int dec_persistent_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_persistent_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-                       const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* gin1,
-                       const float* h0_init, const float* h1_init, float* h0_fin, float* h1_fin, hipStream_t s,
-                       unsigned* status = nullptr);
+int dec_persistent_run(const DecCtx& c, const DecFwdIO& io, const float* gin1, const float* h0_init, const float* h1_init,
+                       float* h0_fin, float* h1_fin, unsigned* status = nullptr);
 // persistent training rollout (train_persistent.hip)
 int dec_tp_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4 = -1);
+int dec_tp_pack(const DecCtx& c, int t4 = -1);
 // batch decode on the same sweep (inference form of the kernel; zeggs_decoder_fwd_batch)
 int dec_tb_t4(const DecWs& w);
 int dec_tb_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* h_in, float* h_out,
-               hipStream_t s, unsigned* status);
+int dec_tb_run(const DecCtx& c, const DecFwdIO& io, const float* h_in, float* h_out, unsigned* status);
 int dec_tp_zero(const ZeggsDecDims& d, DecWs& w, hipStream_t s);
-int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* speech, const float* style, float* pose, float* rpos, float* rrot, hipStream_t s,
-               bool zeroed = false, unsigned* status = nullptr, bool prologue_done = false);
-int dec_tp_prologue(const ZeggsDecDims& d, const ZeggsDecStats* st, DecWs& w, const float* pose0, const float* rpos0,
-                    const float* rrot0, const float* gaze, const float* speech, const float* style, float* pose, float* rpos,
-                    float* rrot, hipStream_t s, bool zeroed);
+int dec_tp_run(const DecCtx& c, const DecFwdIO& io, bool zeroed = false, unsigned* status = nullptr, bool prologue_done = false);
+int dec_tp_prologue(const DecCtx& c, const DecFwdIO& io, bool zeroed);
 struct GemmNtItem;
-GemmNtItem dec_tp_p1x_item(const ZeggsDecDims& d, const ZeggsDecParams* P, const DecWs& w);
+GemmNtItem dec_tp_p1x_item(const DecCtx& c);
 // persistent BPTT sweep (train_bwd_persistent.hip)
 int dec_bp_supported(const ZeggsDecDims& d, const DecWs& w);
-int dec_bp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStream_t s);
+int dec_bp_pack(const DecCtx& c);
 int dec_bp_zero_slots(DecWs& w, hipStream_t s);      // weight tiles + operand pads (weights only)
-int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* pose, const float* rpos, const float* rrot, const float* dpose, const float* drpos,
-               const float* drrot, hipStream_t s, bool packed = false, unsigned* status = nullptr);
+int dec_bp_run(const DecCtx& c, const DecBwdIO& io, bool packed = false, unsigned* status = nullptr);
 // fast path entry points (decoder_fast.hip)
-int dec_fast_merge_prep(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s);
+int dec_fast_merge_prep(const DecCtx& c);
 void dec_timing_mark(int i, hipStream_t s);
 int dec_fast_supported(const ZeggsDecDims& d);
-int dec_fast_pack_fwd(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStream_t s);
-int dec_fast_pack_bwd(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s);
-int dec_fast_fwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w,
-                       const float* gaze, const float* speech, const float* style, float* pose, float* rpos,
-                       float* rrot, int training, hipStream_t s);
-int dec_fast_bwd_steps(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w,
-                       const float* gaze, const float* pose, const float* rpos, const float* rrot,
-                       const float* dpose, const float* drpos, const float* drrot, int t_hi, int t_lo, hipStream_t s);
+int dec_fast_pack_fwd(const DecCtx& c);
+int dec_fast_pack_bwd(const DecCtx& c);
+int dec_fast_fwd_steps(const DecCtx& c, const DecFwdIO& io, int training);
+int dec_fast_bwd_steps(const DecCtx& c, const DecBwdIO& io, int t_hi, int t_lo);

@@ -796,7 +796,8 @@ int dec_bp_supported(const ZeggsDecDims& d, const DecWs& w) {
 
 // the whole sweep t = T-1 .. 1; leaves DY, DI*, DH*, D0, DX (speech / style columns), dH0c, dH1c as the stage sweep does
 // what depends on the weights and the dimensions only (zeggs_decoder_prepare runs it ahead of the forward, on a second stream)
-int dec_bp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStream_t s) {
+int dec_bp_pack(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; DecWs& w = c.w; hipStream_t s = c.s;
   const int T = d.T, KBY = (d.PO + 15) / 16;
   BPackArgs p{w.bp_wr, w.bp_wl, P->w_ih0, P->w_hh0, P->w_ih1, P->w_hh1, P->l2_w, P->l0_w, w.XD, d.PO, KBY};
   hipLaunchKernelGGL(bp_pack_k, dim3(8192), dim3(256), 0, s, p);
@@ -809,15 +810,14 @@ int dec_bp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, DecWs& w, hipStr
 int dec_bp_zero_slots(DecWs& w, hipStream_t s) {        // arrival slots + error word (and the stamps behind it)
   return k_fill((float*)w.bp_cnt, bp_errword(w) - w.bp_cnt + 1024, 0.f, s);
 }
-int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* pose, const float* rpos, const float* rrot, const float* dpose, const float* drpos,
-               const float* drrot, hipStream_t s, bool packed, unsigned* status) {
+int dec_bp_run(const DecCtx& c, const DecBwdIO& io, bool packed, unsigned* status) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
   const int B = d.B, T = d.T, H = d.H, KBY = (d.PO + 15) / 16;
   ZTRY(require_cus(BNCU, "persistent BPTT sweep"));
-  if (!packed) ZTRY(dec_bp_pack(d, P, w, s));
+  if (!packed) ZTRY(dec_bp_pack(c));
   float* dyl = w.DY + (long)(T - 1) * B * w.POL;
-  hipLaunchKernelGGL(bp_dy_last_k, dim3(B), dim3(256), 0, s, d, *st, dpose, drpos, drrot, gaze, pose, rpos, rrot, w.carry,
-                     dyl, w.POL);
+  hipLaunchKernelGGL(bp_dy_last_k, dim3(B), dim3(256), 0, s, d, *st, io.dpose, io.drpos, io.drrot, io.gaze, io.pose, io.rpos, io.rrot,
+                     w.carry, dyl, w.POL);
   ZLAUNCH_CHECK("bp_dy_last");
   if (!packed) ZTRY(dec_bp_zero_slots(w, s));         // (prepared: zeggs_decoder_prepare has zeroed them)
   dec_timing_mark(2, s);
@@ -837,15 +837,14 @@ int dec_bp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecSta
     a.Gin = w.Gin + o * w.GL; a.H0 = w.H0 + o * H; a.H1 = w.H1 + o * H; a.GT0 = w.GT0 + o * H * 4; a.GT1 = w.GT1 + o * H * 4;
     a.DY = w.DY + o * w.POL; a.DI1 = w.DI1 + o * 3 * H; a.DH1 = w.DH1 + o * H; a.DI0 = w.DI0 + o * 3 * H; a.DH0 = w.DH0 + o * H;
     a.D0 = w.D0 + o * H; a.DX = w.DX + o * w.XD; a.dH0c = w.dH0c + o * H; a.dH1c = w.dH1c + o * H;
-    a.dpose = dpose + o * T * d.PO; a.drpos = drpos + o * T * 3; a.drrot = drrot + o * T * 4; a.gaze = gaze + o * T * 3;
-    a.pose = pose + o * T * d.PO; a.rpos = rpos + o * T * 3; a.rrot = rrot + o * T * 4;
+    a.dpose = io.dpose + o * T * d.PO; a.drpos = io.drpos + o * T * 3; a.drrot = io.drrot + o * T * 4; a.gaze = io.gaze + o * T * 3;
+    a.pose = io.pose + o * T * d.PO; a.rpos = io.rpos + o * T * 3; a.rrot = io.rrot + o * T * 4;
     a.carry = w.carry + o * 8;
     a.sync = sweep_sync_args(w.bp_cnt, bp_errword(w), status);
     hipLaunchKernelGGL(train_bwd_persistent_k, dim3(BNCU), dim3(BTHR), 0, s, a);
     ZLAUNCH_CHECK("train_bwd_persistent");
   }
   dec_timing_mark(3, s);
-  (void)H;
   return 0;
 }
 extern "C" int zeggs_bp_stamps(const ZeggsDecDims* dp, void* ws, size_t ws_bytes, unsigned long long* out /* [3][2][32] */) {

@@ -966,8 +966,10 @@ void tp_dual_launch(const TArgs& a, hipStream_t s);
 static bool tp_pack_t4(const DecWs& w) { return tp_dual_supported(w.NB) || (g_tp_tiles4 && w.NB % 2 == 0); }
 static bool tp_use_t4(const DecWs& w) { return !tp_dual_supported(w.NB) && g_tp_tiles4 && w.NB % 2 == 0; }
 
-// once per optimizer step: the per-workgroup fragment packs (needs Mc / cvec: dec_fast_merge_prep)
-int dec_tp_pack(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, hipStream_t s, int t4) {
+// once per optimizer step: the merged matrices Mc / cvec (dec_fast_merge_prep), then the per-workgroup fragment packs made of them
+int dec_tp_pack(const DecCtx& c, int t4) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const ZeggsDecStats* st = c.st; DecWs& w = c.w; hipStream_t s = c.s;
+  ZTRY(dec_fast_merge_prep(c));
   const int H = d.H, KIN = H + w.XD;
   if (t4 < 0) t4 = tp_pack_t4(w) ? 1 : 0;      // (the training rollout's choice; the batch decode passes its own)
   // the fold of GRU layer 0's pose columns: N0 = W_ih0[:, pose] diag(sigma_o/sigma_i) W2 [3H, H], cv0 = W_ih0[:, pose] v [3H]
@@ -1002,14 +1004,13 @@ int dec_tp_zero(const ZeggsDecDims& d, DecWs& w, hipStream_t s) {
 }
 // the elementwise prologue as one launch (tp_prologue_k); the caller then runs the CellStateEncoder, hid_1 and the step-1 pose product
 // (dec_tp_p1x_item) and calls dec_tp_run(..., prologue_done = true)
-int dec_tp_prologue(const ZeggsDecDims& d, const ZeggsDecStats* st, DecWs& w, const float* pose0, const float* rpos0,
-                    const float* rrot0, const float* gaze, const float* speech, const float* style, float* pose, float* rpos,
-                    float* rrot, hipStream_t s, bool zeroed) {
+int dec_tp_prologue(const DecCtx& c, const DecFwdIO& io, bool zeroed) {
+  const ZeggsDecDims& d = c.d; DecWs& w = c.w; hipStream_t s = c.s;
   if (!zeroed) ZTRY(dec_tp_zero(d, w, s));
   TProArgs a;
   memset(&a, 0, sizeof(a));
-  a.d = d; a.st = *st; a.pose0 = pose0; a.rp0 = rpos0; a.rr0 = rrot0; a.gaze = gaze; a.speech = speech; a.style = style;
-  a.pose = pose; a.rpos = rpos; a.rrot = rrot; a.cse_in = w.cse_in; a.gin = w.Gin; a.GL = w.GL; a.sG = (long)d.B * w.GL;
+  a.d = d; a.st = *c.st; a.pose0 = io.pose0; a.rp0 = io.rpos0; a.rr0 = io.rrot0; a.gaze = io.gaze; a.speech = io.speech; a.style = io.style;
+  a.pose = io.pose; a.rpos = io.rpos; a.rrot = io.rrot; a.cse_in = w.cse_in; a.gin = w.Gin; a.GL = w.GL; a.sG = (long)d.B * w.GL;
   a.G0 = w.G0xf; a.G3 = w.G3xf; a.KB0 = TKB0; a.KB3 = 64 + w.KBC; a.NB = w.NB; a.t4 = tp_use_t4(w) ? 1 : 0;
   const long nf = ((long)(d.T - 1) * d.B * (d.SP + d.ST) + 255) / 256;
   a.nfill = (int)(nf > 2048 ? 2048 : (nf < 1 ? 1 : nf));
@@ -1019,7 +1020,8 @@ int dec_tp_prologue(const ZeggsDecDims& d, const ZeggsDecStats* st, DecWs& w, co
   return 0;
 }
 // the step-1 pose product p1x[b][3H] = x_1[b][pose] W_ih0[:, pose]^T as an item of a multi-product launch
-GemmNtItem dec_tp_p1x_item(const ZeggsDecDims& d, const ZeggsDecParams* P, const DecWs& w) {
+GemmNtItem dec_tp_p1x_item(const DecCtx& c) {
+  const ZeggsDecDims& d = c.d; const ZeggsDecParams* P = c.P; const DecWs& w = c.w;
   const float* gin1 = w.Gin + (long)d.B * w.GL;
   return GemmNtItem{gin1 + d.H, (long)w.GL, P->w_ih0 + d.H, (long)(d.H + w.XD), w.tp_p1x, 3L * d.H, nullptr, 3 * d.H, d.PO, ACT_NONE};
 }
@@ -1038,46 +1040,56 @@ static void tp_launch(const TArgs& a, int NB, int t4, hipStream_t s) {
       break;
   }
 }
-int dec_tp_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* speech, const float* style, float* pose, float* rpos, float* rrot, hipStream_t s, bool zeroed,
-               unsigned* status, bool prologue_done) {
-  const int B = d.B, H = d.H, NB = w.NB, KB0 = TKB0, KB3 = 64 + w.KBC;
-  const long XB = 256L * NB, sG = (long)B * w.GL;
-  ZTRY(require_cus(TNCU, "persistent training rollout"));
-  // operand buffers: zero (pad rows / pad columns must be finite), then the inputs that do not depend on the rollout
-  // (only the blocks with pad columns: the gaze + speech / style blocks of G0, the cond blocks of G3, the h1 slot of step 1)
-  if (!zeroed && !prologue_done) ZTRY(dec_tp_zero(d, w, s));
-  const int t4 = tp_use_t4(w) ? 1 : 0;
-  if (!prologue_done) hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4, 0);
-  const float* gin1 = w.Gin + sG;
-  {   // hid_1, h0_0 -> operand of GRU layer 0, step 1 (its h1 slot stays zero: the pose columns of x_1 are the given first pose; its
-      // gaze block is not an operand any more: the gate threads read the gaze direction of x_1 from the canonical row); h1_0 -> layer 1
-    TXfrag x;
-    x.xf[0] = w.G0xf + (long)KB0 * XB; x.src[0] = gin1; x.ld[0] = w.GL; x.kofs[0] = 0;
-    x.xf[1] = w.G0xf + (long)KB0 * XB; x.src[1] = w.H0; x.ld[1] = H;    x.kofs[1] = 16 * TKH0;
-    x.xf[2] = w.G1xf + 128 * XB;       x.src[2] = w.H1; x.ld[2] = H;    x.kofs[2] = 16 * 64;
-    const long g = (3L * B * H + 255) / 256;
-    hipLaunchKernelGGL(tp_xfrag_k, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, x, H, B, NB, t4);
-  }
-  // ... whose product with W_ih0 is one small GEMM: p1x[b][3H] = x_1[b][pose] W_ih0[:, pose]^T
-  if (!prologue_done) ZTRY(gemm_nt(gin1 + H, w.GL, P->w_ih0 + H, H + w.XD, w.tp_p1x, 3 * H, nullptr, B, 3 * H, d.PO, ACT_NONE, 0.f, s));
-  ZLAUNCH_CHECK("tp_prologue");
+// what dec_tp_run and dec_tb_run share.  (1) the operands of step 1 that the caller prepared in canonical form: hid_1, h0_0 ->
+// operand of GRU layer 0 (its h1 slot stays zero: the pose columns of x_1 are the given first pose; its gaze block is not an
+// operand any more: the gate threads read the gaze direction of x_1 from the canonical row), h1_0 -> layer 1; then, unless a
+// multi-product launch of the caller has done it (dec_tp_p1x_item), the step-1 pose product p1x[b][3H] = x_1[b][pose] W_ih0[:, pose]^T
+static int tp_step1_operands(const DecCtx& c, const float* h0, const float* h1, int t4, bool p1x_done) {
+  const ZeggsDecDims& d = c.d; DecWs& w = c.w;
+  const int B = d.B, H = d.H, NB = w.NB;
+  const long XB = 256L * NB;
+  const float* gin1 = w.Gin + (long)B * w.GL;
+  TXfrag x;
+  x.xf[0] = w.G0xf + (long)TKB0 * XB; x.src[0] = gin1; x.ld[0] = w.GL; x.kofs[0] = 0;
+  x.xf[1] = w.G0xf + (long)TKB0 * XB; x.src[1] = h0;   x.ld[1] = H;    x.kofs[1] = 16 * TKH0;
+  x.xf[2] = w.G1xf + 128 * XB;        x.src[2] = h1;   x.ld[2] = H;    x.kofs[2] = 16 * 64;
+  const long g = (3L * B * H + 255) / 256;
+  hipLaunchKernelGGL(tp_xfrag_k, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, c.s, x, H, B, NB, t4);
+  if (!p1x_done) ZTRY(gemm_nt(gin1 + H, w.GL, c.P->w_ih0 + H, H + w.XD, w.tp_p1x, 3 * H, nullptr, B, 3 * H, d.PO, ACT_NONE, 0.f, c.s));
+  return 0;
+}
+// (2) the sweep's arguments; h0 / h1: the state before step 1 ([T][B][H] buffers of the training form, [B][H] of the inference
+// form), hout: [2,B,H] state after the last frame (inference form) or null
+static TArgs tp_args(const DecCtx& c, const DecFwdIO& io, float* h0, float* h1, float* hout, unsigned* status) {
+  const ZeggsDecParams* P = c.P; const DecWs& w = c.w;
   TArgs a;
   memset(&a, 0, sizeof(a));
-  a.d = d; a.st = *st; a.XD = w.XD; a.GL = w.GL; a.KBX = w.KBX; a.KBC = w.KBC; a.KB0 = KB0; a.KB3 = KB3; a.POL = w.POL;
+  a.d = c.d; a.st = *c.st; a.XD = w.XD; a.GL = w.GL; a.KBX = w.KBX; a.KBC = w.KBC; a.KB0 = TKB0; a.KB3 = 64 + w.KBC; a.POL = w.POL;
   a.PW0 = (const f4*)w.tp_w0; a.PW1 = (const f4*)w.tp_w1; a.PW3 = (const f4*)w.tp_w3;
   a.G0 = w.G0xf; a.G1 = w.G1xf; a.G3 = w.G3xf;
-  a.Gin = w.Gin; a.H0 = w.H0; a.H1 = w.H1; a.GT0 = w.GT0; a.GT1 = w.GT1;
+  a.Gin = w.Gin; a.H0 = h0; a.H1 = h1; a.GT0 = w.GT0; a.GT1 = w.GT1;
+  if (hout) { a.Hout0 = hout; a.Hout1 = hout + (long)c.d.B * c.d.H; }
   a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1; a.cvec = w.cvec; a.l0_w = P->l0_w;
-  a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x; a.gaze = gaze; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
+  a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x;
+  a.gaze = io.gaze; a.pose = io.pose; a.rpos = io.rpos; a.rrot = io.rrot;
   a.sync = sweep_sync_args(w.tp_cnt, tp_errword(w), status);
-  if (tp_dual_supported(NB)) {
-    tp_dual_launch(a, s);
-    ZLAUNCH_CHECK("train_fwd_dual");
-    return 0;
-  }
-  tp_launch<false>(a, NB, t4, s);
-  ZLAUNCH_CHECK("train_fwd_persistent");
+  return a;
+}
+int dec_tp_run(const DecCtx& c, const DecFwdIO& io, bool zeroed, unsigned* status, bool prologue_done) {
+  const ZeggsDecDims& d = c.d; DecWs& w = c.w; hipStream_t s = c.s;
+  ZTRY(require_cus(TNCU, "persistent training rollout"));
+  // operand buffers: zero the pad blocks, then the inputs that do not depend on the rollout
+  if (!zeroed && !prologue_done) ZTRY(dec_tp_zero(d, w, s));
+  const int t4 = tp_use_t4(w) ? 1 : 0;
+  if (!prologue_done)
+    hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, io.speech, io.style, w.G0xf, w.G3xf, TKB0, 64 + w.KBC, w.NB, t4, 0);
+  ZTRY(tp_step1_operands(c, w.H0, w.H1, t4, prologue_done));
+  ZLAUNCH_CHECK("tp_prologue");
+  const TArgs a = tp_args(c, io, w.H0, w.H1, nullptr, status);
+  const bool dual = tp_dual_supported(w.NB);
+  if (dual) tp_dual_launch(a, s);
+  else tp_launch<false>(a, w.NB, t4, s);
+  ZLAUNCH_CHECK(dual ? "train_fwd_dual" : "train_fwd_persistent");
   return 0;
 }
 
@@ -1089,36 +1101,16 @@ int dec_tb_supported(const ZeggsDecDims& d, const DecWs& w) { return d.B >= 2 &&
 // One chunk of d.T frames on the sweep.  The caller has prepared, as for the training rollout: Gin slot 1 (= [hid_1 | x_1] of the
 // 2-slot ring), frame 0 of pose / rpos / rrot, the packs (dec_tp_pack with dec_tb_t4).  h_in / h_out: [2,B,H].  The operand buffers
 // are write-once inside this launch only: pad blocks and arrival slots are zeroed again for every chunk.
-int dec_tb_run(const ZeggsDecDims& d, const ZeggsDecParams* P, const ZeggsDecStats* st, DecWs& w, const float* gaze,
-               const float* speech, const float* style, float* pose, float* rpos, float* rrot, const float* h_in, float* h_out,
-               hipStream_t s, unsigned* status) {
-  const int B = d.B, H = d.H, NB = w.NB, KB0 = TKB0, KB3 = 64 + w.KBC;
-  const long XB = 256L * NB, sG = (long)B * w.GL, sH = (long)B * H;
+int dec_tb_run(const DecCtx& c, const DecFwdIO& io, const float* h_in, float* h_out, unsigned* status) {
+  const ZeggsDecDims& d = c.d; DecWs& w = c.w; hipStream_t s = c.s;
+  const long sH = (long)d.B * d.H;
   ZTRY(require_cus(TNCU, "persistent batch decode"));
   const int t4 = dec_tb_t4(w);
   ZTRY(dec_tp_zero(d, w, s));
-  hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, speech, style, w.G0xf, w.G3xf, KB0, KB3, NB, t4, 1);
-  const float* gin1 = w.Gin + sG;
-  {
-    TXfrag x;
-    x.xf[0] = w.G0xf + (long)KB0 * XB; x.src[0] = gin1;       x.ld[0] = w.GL; x.kofs[0] = 0;
-    x.xf[1] = w.G0xf + (long)KB0 * XB; x.src[1] = h_in;       x.ld[1] = H;    x.kofs[1] = 16 * TKH0;
-    x.xf[2] = w.G1xf + 128 * XB;       x.src[2] = h_in + sH;  x.ld[2] = H;    x.kofs[2] = 16 * 64;
-    const long g = (3L * B * H + 255) / 256;
-    hipLaunchKernelGGL(tp_xfrag_k, dim3((unsigned)(g > 1024 ? 1024 : g)), dim3(256), 0, s, x, H, B, NB, t4);
-  }
-  ZTRY(gemm_nt(gin1 + H, w.GL, P->w_ih0 + H, H + w.XD, w.tp_p1x, 3 * H, nullptr, B, 3 * H, d.PO, ACT_NONE, 0.f, s));
+  hipLaunchKernelGGL(tp_cond_k, dim3(1024), dim3(256), 0, s, d, io.speech, io.style, w.G0xf, w.G3xf, TKB0, 64 + w.KBC, w.NB, t4, 1);
+  ZTRY(tp_step1_operands(c, h_in, h_in + sH, t4, false));
   ZLAUNCH_CHECK("tb_prologue");
-  TArgs a;
-  memset(&a, 0, sizeof(a));
-  a.d = d; a.st = *st; a.XD = w.XD; a.GL = w.GL; a.KBX = w.KBX; a.KBC = w.KBC; a.KB0 = KB0; a.KB3 = KB3; a.POL = w.POL;
-  a.PW0 = (const f4*)w.tp_w0; a.PW1 = (const f4*)w.tp_w1; a.PW3 = (const f4*)w.tp_w3;
-  a.G0 = w.G0xf; a.G1 = w.G1xf; a.G3 = w.G3xf;
-  a.Gin = w.Gin; a.H0 = (float*)h_in; a.H1 = (float*)h_in + sH; a.Hout0 = h_out; a.Hout1 = h_out + sH;
-  a.b_ih0 = P->b_ih0; a.b_hh0 = P->b_hh0; a.b_ih1 = P->b_ih1; a.b_hh1 = P->b_hh1; a.cvec = w.cvec; a.l0_w = P->l0_w;
-  a.l2_b = P->l2_b; a.w_ih0 = P->w_ih0; a.cv0 = w.tp_cv0; a.p1x = w.tp_p1x; a.gaze = gaze; a.pose = pose; a.rpos = rpos; a.rrot = rrot;
-  a.sync = sweep_sync_args(w.tp_cnt, tp_errword(w), status);
-  tp_launch<true>(a, NB, t4, s);
+  tp_launch<true>(tp_args(c, io, (float*)h_in, (float*)h_in + sH, h_out, status), w.NB, t4, s);
   ZLAUNCH_CHECK("batch_fwd_persistent");
   return 0;
 }
