@@ -9,8 +9,10 @@
  *   - plain pointers + sizes, no torch types; all tensors contiguous row-major fp32 DEVICE
  *     memory unless stated; quaternions (w,x,y,z); int64 indices where stated.
  *   - the caller owns all memory.  The library never allocates or frees device memory and does
- *     not synchronise the device (one documented exception: the FIRST use of each persistent
- *     kernel on a process is validated with a stream synchronisation, never inside a capture);
+ *     not synchronise the device (two documented exceptions, never inside a capture: the FIRST use
+ *     of each persistent kernel on a process is validated with a stream synchronisation, and the
+ *     first use of each direct TN GEMM variant is checked on a small allocation and a stream of the
+ *     check's own -- see zeggs_gemm_direct_warm for running those checks ahead of time);
  *     it only enqueues kernels on `stream` (a hipStream_t passed as void*), so every call is
  *     hipGraph-capturable.
  *   - no per-call state is global: what a call needs beyond its arguments travels in the
@@ -73,10 +75,19 @@ int zeggs_gemm_tn_bias(const float* dy, long lddy, const float* x, long ldx, flo
                        float beta, float* db, void* stream);
 /* The direct (LDS-free, barrier-free) TN kernel behind zeggs_gemm_tn / zeggs_gemm_tn_bias issues its operand loads as inline asm with
  * hand-counted waits; every variant (wave tile 64x64 / 128x64, 4 / 6 / 8 operand pairs in flight, plain / "shield") is therefore
- * CHECKED on its first use per process against a float64 host sum (ragged 293 x 155 x 346 product with row sums; synchronises; never
- * inside a stream capture) and the kernel is disabled for the process -- the LDS-tiled stream-K kernel takes its products -- if the
- * check fails.  This entry point runs that check for one variant on demand: 1 = agrees, 0 = does not (tests, toolchain bumps). */
+ * CHECKED on its first use per process against a float64 host sum (ragged 293 x 155 x 346 product with row sums), on a stream and
+ * an allocation of the check's own (it synchronises that stream and frees; never inside a stream capture, where the variant runs
+ * unchecked).  Three outcomes: it AGREES -- the variant is trusted from then on; a MISMATCH -- the kernel is disabled for the
+ * process and the LDS-tiled stream-K kernel takes its products; the check was UNAVAILABLE (an allocation, copy, launch or
+ * synchronise call failed) -- that one product goes to the LDS-tiled kernel, nothing is disabled and the next product checks again.
+ * zeggs_gemm_direct_selftest runs the check for one variant on demand and records nothing: 1 = agrees, 0 = does not (tests,
+ * toolchain bumps).  zeggs_gemm_direct_state: -1 unchecked, 1 ok, 0 failed; host only.  zeggs_gemm_direct_warm runs the first-use
+ * check NOW, on no caller stream, for every variant the calling thread's route can select (both wave tiles when "gemm_direct" is 1,
+ * shield on / off / both for 1 / 0 / 2, at the route's depth), so that no later product of that route stops for it
+ * (zeggs.engine.TrainEngine at construction): 0, or -1 with zeggs_last_error set when a check was unavailable. */
 int zeggs_gemm_direct_selftest(int big, int depth, int shield);
+int zeggs_gemm_direct_state(int big, int depth, int shield);
+int zeggs_gemm_direct_warm(void);
 /* Routing of the TN products launched BY THE CALLING THREAD from now on: the values of the options "gemm_direct", "gemm_direct_shield",
  * "gemm_direct_depth", "gemm_direct_reserve" for this thread's launches, -1 = the process-wide option (zeggs_set_option).  The way
  * a caller with preferences of its own (zeggs/engine.py: TrainEngine wants the shield variant for its three-queue tail) states them

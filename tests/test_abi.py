@@ -72,6 +72,13 @@ def test_gemm_routing_is_per_thread_not_per_process():
     ops._route(ops._DEFAULT_CTX)
     L.zeggs_gemm_route_get(out)
     assert list(out) == base
+    # ... and a route leaves the thread with its context: a raw zeggs_gemm* call after the block gets the outer context's again
+    with ops.use(ctx):
+        ops._route(ctx)
+        L.zeggs_gemm_route_get(out)
+        assert list(out) == [1, 2, 4, 16]
+    L.zeggs_gemm_route_get(out)
+    assert list(out) == base
 
 
 _SWEEP_STATE_CHILD = """

@@ -468,6 +468,104 @@ def test_direct_gemm_variant_selftest(big, depth, shield):
     assert ops.lib().zeggs_gemm_direct_selftest(big, depth, shield) == 1
 
 
+_DIRECT_FIRST_USE_CHILD = """
+import ctypes as C, json, sys, threading
+import torch
+L = C.CDLL(sys.argv[1])
+L.zeggs_last_error.restype = C.c_char_p
+VARIANTS = [(b, d, sh) for b in (0, 1) for d in (4, 6, 8) for sh in (0, 1)]
+states = lambda: {"%d/%d/%d" % v: L.zeggs_gemm_direct_state(*v) for v in VARIANTS}
+def route():
+    o = (C.c_int * 4)()
+    L.zeggs_gemm_route_get(o)
+    return list(o)
+out = {"fresh": states()}
+Mc, N, K, lddy, ldx = 1282, 130, 70, 131, 73          # GemmArgs 130 x 70 x 1282: 81 k-tiles, ragged tiles and strides
+torch.manual_seed(Mc + N)
+dy, x, W0, b0 = torch.randn(Mc, lddy), torch.randn(Mc, ldx), torch.randn(N, K), torch.randn(N)
+ref_w = W0.double() + dy[:, :N].double().T @ x[:, :K].double()
+ref_b = b0.double() + dy[:, :N].double().sum(0)
+dyd, xd = dy.cuda(), x.cuda()
+def product(dW, db, stream):
+    rc = L.zeggs_gemm_tn_bias(C.c_void_p(dyd.data_ptr()), C.c_long(lddy), C.c_void_p(xd.data_ptr()), C.c_long(ldx),
+                              C.c_void_p(dW.data_ptr()), C.c_long(K), Mc, N, K, C.c_float(1.0), C.c_void_p(db.data_ptr()),
+                              C.c_void_p(stream))
+    assert rc == 0, L.zeggs_last_error()
+def errs(dW, db):
+    return [float((dW.cpu().double() - ref_w).abs().max() / ref_w.abs().max()),
+            float((db.cpu().double() - ref_b).abs().max() / ref_b.abs().max())]
+# the warm-up: the variants of the engine's route, nothing else
+L.zeggs_gemm_route(1, 1, 8, 0)
+out["warm_rc"] = L.zeggs_gemm_direct_warm()
+out["warmed"] = states()
+# a capture: the variant runs unchecked and stays unchecked
+L.zeggs_gemm_route(-1, -1, -1, -1)
+dW, db = W0.cuda(), b0.cuda()
+torch.cuda.synchronize()
+graph = torch.cuda.CUDAGraph()
+with torch.cuda.graph(graph):
+    product(dW, db, torch.cuda.current_stream().cuda_stream)
+out["after_capture"] = L.zeggs_gemm_direct_state(0, 4, 0)
+graph.replay()
+torch.cuda.synchronize()
+out["captured"] = errs(dW, db)
+# two threads meet an unchecked variant at the same moment, each on a stream of its own
+gate, outs, failed = threading.Barrier(2), [(W0.cuda(), b0.cuda()) for _ in range(2)], []
+torch.cuda.synchronize()
+def worker(i):
+    try:
+        L.zeggs_gemm_route(3, 0, 6, 0)
+        s = torch.cuda.Stream()
+        gate.wait()
+        product(outs[i][0], outs[i][1], s.cuda_stream)
+        s.synchronize()
+    except BaseException as e:
+        failed.append(repr(e))
+        gate.abort()
+threads = [threading.Thread(target=worker, args=(i,)) for i in range(2)]
+for t in threads: t.start()
+for t in threads: t.join()
+out["thread_failures"] = failed
+out["threads"] = [errs(*o) for o in outs]
+out["after_threads"] = states()
+dW, db = W0.cuda(), b0.cuda()
+product(dW, db, torch.cuda.current_stream().cuda_stream)
+torch.cuda.synchronize()
+out["default_after"] = errs(dW, db)
+out["route_after"] = route()
+out["final"] = states()
+print(json.dumps(out))
+"""
+
+
+def test_direct_gemm_first_use_warm_capture_and_two_threads():
+    """The first use of the direct TN kernel's variants in a process of its own (the states are per process): nothing is checked
+    before a launch; zeggs_gemm_direct_warm checks exactly the variants of the calling thread's route (the engine's: both wave
+    tiles, shield, depth 8); a product captured into a graph runs its variant unchecked and leaves it unchecked; two threads that
+    meet an unchecked variant together, each on its own stream, both get right results, the variant is ok afterwards and the direct
+    kernel is still on.  zeggs_gemm_tn_bias at the smallest shape that reaches the stream-K family (81 k-tiles), ragged tiles and
+    strides, accumulating, against float64."""
+    import json
+    import subprocess
+    import sys
+    r = subprocess.run([sys.executable, "-c", _DIRECT_FIRST_USE_CHILD, str(ops._LIB_PATH)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr
+    out = json.loads(r.stdout.strip().splitlines()[-1])
+    print(out)
+    unchecked = {"%d/%d/%d" % (b, d, sh): -1 for b in (0, 1) for d in (4, 6, 8) for sh in (0, 1)}
+    assert out["fresh"] == unchecked
+    assert out["warm_rc"] == 0
+    assert out["warmed"] == {**unchecked, "0/8/1": 1, "1/8/1": 1}
+    assert out["after_capture"] == -1
+    assert max(out["captured"]) < 4e-6, out["captured"]
+    assert out["thread_failures"] == []
+    assert max(max(e) for e in out["threads"]) < 4e-6, out["threads"]
+    assert out["after_threads"] == {**unchecked, "0/8/1": 1, "1/8/1": 1, "0/6/0": 1}
+    assert max(out["default_after"]) < 4e-6, out["default_after"]
+    assert out["route_after"][0] != 0                   # no check failed: the direct kernel is not disabled
+    assert out["final"] == {**unchecked, "0/8/1": 1, "1/8/1": 1, "0/6/0": 1, "0/4/0": 1}
+
+
 @pytest.mark.parametrize("nplanes", [6, 9])
 def test_bf16_split_tn_product_is_at_least_as_exact_as_the_fp32_matrix_cores(nplanes):
     """EXPERIMENT (option "gemm_split_bf16", default off; csrc/gemm_split.hip): the fp32 TN products of the training tail on the bf16

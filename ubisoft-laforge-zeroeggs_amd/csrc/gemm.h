@@ -21,7 +21,8 @@ struct GemmArgs {
 };
 
 GemmArgs gemm_args(const float* A, const float* B, float* C, int M, int N, int K);
-int launch_gemm(GemmArgs g, int nbatch, hipStream_t s);
+// asum_taken (may be null): whether the launch that ran took GemmArgs.asum (only the direct TN kernel does: gemm_tn_bias)
+int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken = nullptr);
 int gemm_nt(const float* x, long ldx, const float* W, long ldw, float* y, long ldy, const float* bias, int M,
             int N, int K, int act, float beta, hipStream_t s);
 // up to three independent y_i = act_i(x_i W_i^T + bias_i) of the same row count in ONE launch when they are batch-sized (gemm.hip: skinny_multi_k)

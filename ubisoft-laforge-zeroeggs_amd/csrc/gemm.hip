@@ -17,11 +17,13 @@
 #include <vector>
 
 #include "gemm.h"
+#include "gemm_route.h"
 #include "kernels.h"
 
 extern int g_gemm_split_bf16;                          // gemm_split.hip: the fp32-exact bf16 split (experiment, option "gemm_split_bf16", default off)
 bool gemm_split_ok(const GemmArgs& g);
 int launch_tn_split(GemmArgs g, hipStream_t s);
+bool stream_capturing(hipStream_t s);                   // sweep_sync.hip: a failed query reads as capturing
 
 int g_gemm_streamk_wgs = 0;     // zeggs_set_option("gemm_streamk_wgs", n): stream-K workgroups per CU (0: as many as are resident)
 int g_gemm_wg_target = 6144;   // split-K aims at this many workgroups (24 per CU = 6 rounds of 4 resident ones; sweep 1536..12288 in
@@ -732,7 +734,7 @@ __global__ __launch_bounds__(256, 1) void gemm_tn_direct_shield_kernel(GemmArgs 
 // is what `ap[mo[i]]` reads for lane (kh, l31): row 2 pair + kh, column m.
 int g_gemm_direct = 1;         // zeggs_set_option("gemm_direct", v): 0 off (the LDS-tiled stream-K kernel), 1 on (wave tile by output size),
                                // 2 / 3: always the 128 x 64 / the 64 x 64 wave tile (A/B), 5: only the small / batch-reduce products (what
-                               // zeggs.engine.TrainEngine sets when it runs its three-stream schedule: see direct_ok)
+                               // zeggs.engine.TrainEngine sets when it runs its three-stream schedule: gemm_route.h)
 int g_gemm_direct_depth = 4;   // zeggs_set_option("gemm_direct_depth", 4 / 6 / 8): k-pairs of operands in flight per wave
 int g_gemm_direct_shield = 0;  // zeggs_set_option("gemm_direct_shield", 0 / 1 / 2): the variant that owns its SIMDs' register files (2: big products only)
 int g_gemm_asum = 1;           // zeggs_set_option("gemm_asum", 0/1): bias column sums inside the weight-gradient product (A/B)
@@ -740,54 +742,31 @@ int g_gemm_direct_reserve = 0; // zeggs_set_option("gemm_direct_reserve", n): CU
 int g_gemm_direct_wgs = 0;     // zeggs_set_option("gemm_direct_wgs", n): workgroups per CU (0: 1 for the 128 x 64 wave tile, 2 for 64 x 64)
 // Routing of the TN products is per CALLING THREAD (zeggs_gemm_route: what an engine wants for ITS launches travels with its calls,
 // a second engine or a plain caller in the same process keeps the process-wide options above); -1 = the process-wide option.
+// gemm_route.h turns the resolved route and a product's shape into the ONE plan that the first-use check and the launch both get.
 static thread_local int tl_route[4] = {-1, -1, -1, -1};
-static bool g_direct_failed = false;       // a variant's first-use check failed: off for the process, whatever a route says
-static inline int rt_direct() { return g_direct_failed ? 0 : tl_route[0] >= 0 ? tl_route[0] : g_gemm_direct; }
-static inline int rt_shield() { return tl_route[1] >= 0 ? tl_route[1] : g_gemm_direct_shield; }
-static inline int rt_depth() { return tl_route[2] >= 0 ? tl_route[2] : g_gemm_direct_depth; }
-static inline int rt_reserve() { return tl_route[3] >= 0 ? tl_route[3] : g_gemm_direct_reserve; }
-bool direct_ok(const GemmArgs& g) {
-  // 5: only the products of the encoders' backward chains (batch-reduce convolution weight gradients, small outputs): they run
-  // BESIDE the decoder's resident LDS-tiled stream-K workgroups (101 VGPRs x 4 per SIMD, 135 of 160 KB LDS), where a kernel that
-  // needs no LDS and <= 108 VGPRs is the one that still gets a wave per SIMD
-  if (rt_direct() == 5 && !(g.kbatch > 1 || (long)g.M * g.N < 400000)) return false;
-  return rt_direct() && g.sam == 1 && g.sbn == 1 && g.scn == 1 && g.K % 2 == 0 && g.K >= 64 && g.M >= 64 && g.N >= 64 &&
-         ((long)g.M + g.sak) * 4 < (1L << 31) && ((long)g.N + g.sbk) * 4 < (1L << 31);
+static DirectFirstUse g_direct_first_use;
+static TnRoute tn_route() {
+  return resolve(tl_route, TnRoute{g_gemm_direct, g_gemm_direct_shield, g_gemm_direct_depth, g_gemm_direct_reserve},
+                 g_direct_first_use.disabled.load(std::memory_order_acquire));
+}
+static TnShape tn_shape(const GemmArgs& g) { return TnShape{g.M, g.N, g.K, g.kbatch, g.sak, g.sbk, g.sam, g.sbn, g.scn}; }
+static int device_cus() {
+  int dev = 0, ncu = 256;
+  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
+  return ncu;
 }
 // Measured (tools/gemm_direct_probe.py, TFLOP/s incl. the zero fill of C; LDS-tiled stream-K kernel -> direct): dW_hh 3072 x 1024 x 8160
 // 95.5 -> 134.9, dW_ih0 3072 x 2286 108.4 -> 134.9, dW_l2 1131 x 1024 97.6 -> 117.7, dW_l0 1024 x 1262 94.5 -> 113.0, style conv0
-// dW 3402 x 512 x 12288 107.3 -> 128.1, 4096^3 124.6 -> 140.8.  Big outputs (>= 384 tiles of 128 x 128) take the 128 x 64 wave
-// tile with one workgroup per CU (fewer operand bytes per product), the others 64 x 64 wave tiles, two workgroups per CU (finer
-// grain at the ends of the stream-K ranges).
-static thread_local bool tl_asum_consumed = false;      // set by launch_tn_direct when it was given GemmArgs.asum (gemm_tn_bias)
-int launch_tn_direct(GemmArgs g, hipStream_t s) {
-  if (g.asum) tl_asum_consumed = true;
-  const bool big = rt_direct() == 2 || (rt_direct() == 1 && (long)cdiv(g.M, 128) * cdiv(g.N, 128) >= 384);      // (3, 5: 64 x 64)
-  const int mt = big ? 4 : 2, nt = 2;
-  const int tx = cdiv(g.N, 64 * nt), ty = cdiv(g.M, 64 * mt);
-  const int cpb = cdiv(g.K / 2, 8);
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
-  // shield = 2: only the big single-segment products (the decoder's weight gradients on the second queue); the encoders' chain
-  // products stay the kind that fits in beside other queues' workgroups
-  const bool shield = rt_shield() == 1 || (rt_shield() == 2 && g.kbatch == 1 && (long)g.M * g.N >= 400000);
-  long nwg = (long)ncu * (shield ? 1 : g_gemm_direct_wgs > 0 ? g_gemm_direct_wgs : (big ? 1 : 2));
-  // option "gemm_direct_reserve": CUs a shielded product leaves free.  For data-parallel runs: the collective's workgroups live for
-  // the whole exchange, and a stream-K product whose equal-share workgroups do not ALL become resident takes twice as long (the
-  // stragglers start when the first ones end); with the CUs of the collective left out of the grid nobody waits for anybody.
-  // (On one GPU, where nothing else is resident: 8 / 16 / 32 reserved CUs measured 17.13 / 17.17 / 17.02 ms against 17.03.)
-  if (shield && rt_reserve() > 0 && rt_reserve() < ncu / 2) nwg = ncu - rt_reserve();
-  const long total = (long)tx * ty * cpb * g.kbatch;
-  if (nwg > total / 4) nwg = total / 4 > 0 ? total / 4 : 1;     // at least 4 chunks (64 k) per workgroup
-  const int dep = rt_depth();
+// dW 3402 x 512 x 12288 107.3 -> 128.1, 4096^3 124.6 -> 140.8.
+// Launches exactly the variant of the plan (GemmArgs.asum, if given, is taken in the same launch).
+int launch_tn_direct(const GemmArgs& g, const DirectPlan& p, hipStream_t s) {
 #define ZG_DIRECT(MT_, D_)                                                                                                    \
   do {                                                                                                                         \
-    if (shield) hipLaunchKernelGGL((gemm_tn_direct_shield_kernel<MT_, 2, D_>), dim3((unsigned)nwg), dim3(256), 0, s, g, tx, ty, cpb); \
-    else hipLaunchKernelGGL((gemm_tn_direct_kernel<MT_, 2, D_>), dim3((unsigned)nwg), dim3(256), 0, s, g, tx, ty, cpb);      \
+    if (p.shield) hipLaunchKernelGGL((gemm_tn_direct_shield_kernel<MT_, 2, D_>), dim3((unsigned)p.nwg), dim3(256), 0, s, g, p.tx, p.ty, p.cpb); \
+    else hipLaunchKernelGGL((gemm_tn_direct_kernel<MT_, 2, D_>), dim3((unsigned)p.nwg), dim3(256), 0, s, g, p.tx, p.ty, p.cpb); \
   } while (0)
-  // (deeper than 8 was measured under the shield -- 10 / 12 / 16 pairs: nothing; the wait counter's 6 bits end at (D - 1) x 6 <= 63)
-  if (mt == 4) { if (dep >= 8) ZG_DIRECT(4, 8); else if (dep >= 6) ZG_DIRECT(4, 6); else ZG_DIRECT(4, 4); }
-  else { if (dep >= 8) ZG_DIRECT(2, 8); else if (dep >= 6) ZG_DIRECT(2, 6); else ZG_DIRECT(2, 4); }
+  if (p.big) { if (p.depth == 8) ZG_DIRECT(4, 8); else if (p.depth == 6) ZG_DIRECT(4, 6); else ZG_DIRECT(4, 4); }
+  else { if (p.depth == 8) ZG_DIRECT(2, 8); else if (p.depth == 6) ZG_DIRECT(2, 6); else ZG_DIRECT(2, 4); }
 #undef ZG_DIRECT
   ZLAUNCH_CHECK("gemm_tn_direct");
   return 0;
@@ -797,12 +776,10 @@ int launch_tn_direct(GemmArgs g, hipStream_t s) {
 #define ZEGGS_GEMM_SK256 2      // 2: by output size (default)
 #endif
 template <int BM, int BN, int WM, int WN>
-int launch_streamk_cfg(GemmArgs g, hipStream_t s) {
+int launch_streamk_cfg(GemmArgs g, int ncu, hipStream_t s) {
   const int tx = cdiv(g.N, BN), ty = cdiv(g.M, BM);
   const int kt = cdiv(g.K, BK) * g.kbatch;
   g.splitk = kt;
-  int dev = 0, ncu = 256;
-  if (hipGetDevice(&dev) == hipSuccess) (void)hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
   constexpr int resident = WM * WN > 4 ? 2 : ZEGGS_GEMM_MINB;
   long nwg = (long)ncu * (g_gemm_streamk_wgs > 0 ? g_gemm_streamk_wgs : resident);
   const long total = (long)tx * ty * kt;
@@ -821,90 +798,80 @@ int launch_streamk_cfg(GemmArgs g, hipStream_t s) {
   ZLAUNCH_CHECK("gemm_streamk");
   return 0;
 }
-// First use of a direct-kernel variant on this process: a small ragged product with row sums against a float64 host sum.  The
-// variant's operand loads are inline asm the compiler cannot see into ("=v" destinations that are only valid after a hand-placed
-// wait): its correctness rests on the register allocation of the compiler that built the library -- so it is CHECKED
-// where it runs instead of trusted, like the persistent kernels' first use; a mismatch disables the direct kernel for the process
-// (the LDS-tiled stream-K kernel takes over) and says so on stderr.  Never inside a stream capture (the check synchronises).
-static int g_direct_checked[2][3][2];      // [128 x 64 wave tile][depth 4 / 6 / 8][shield]: 0 not yet, 1 ok
-static bool direct_selftest(bool big, int dep, bool shield) {
+// The first-use check of one variant (gemm_route.h: DirectFirstUse; zeggs_gemm_direct_selftest on demand): a small ragged product
+// with row sums against a float64 host sum.  The variant's operand loads are inline asm the compiler cannot see into ("=v"
+// destinations that are only valid after a hand-placed wait): its correctness rests on the register allocation of the compiler
+// that built the library -- so it is CHECKED where it runs instead of trusted, like the persistent kernels' first use.
+// The check touches nothing shared: it launches its variant with the grid of its own shape, not the calling thread's route, on a non-blocking stream
+// of its own (copies, zero fill, launch, ONE synchronise of that stream; nothing on the null stream, nothing behind the caller's
+// queued work) and on ONE allocation carved into A | B | C | row sums.  hipFree at the end synchronises the device: once per
+// variant and process.  A HIP call that fails is UNAVAILABLE (zeggs_last_error names it), not a mismatch.
+static DirectCheck direct_selftest(const DirectPlan& variant) {
+  const bool big = variant.big, shield = variant.shield;
   const int M = big ? 64 * 4 * 2 + 37 : 64 * 2 * 2 + 21, N = 128 + 27, K = 2 * 173;      // ragged tiles, odd pair count
   const long ldA = M + 3, ldB = N + 5;
-  std::vector<float> hA((size_t)K * ldA), hB((size_t)K * ldB), hC((size_t)M * N), hS(M);
+  std::vector<float> hA((size_t)K * ldA), hB((size_t)K * ldB), hC((size_t)M * N + M);      // hC: C | row sums
   unsigned lcg = 12345u;
   auto rnd = [&]() { lcg = lcg * 1664525u + 1013904223u; return (float)((int)(lcg >> 9) - (1 << 22)) * (1.f / (1 << 22)); };
   for (auto& v : hA) v = rnd();
   for (auto& v : hB) v = rnd();
-  float *dA = nullptr, *dB = nullptr, *dC = nullptr, *dS = nullptr;
-  bool ok = hipMalloc(&dA, hA.size() * 4) == hipSuccess && hipMalloc(&dB, hB.size() * 4) == hipSuccess &&
-            hipMalloc(&dC, hC.size() * 4) == hipSuccess && hipMalloc(&dS, hS.size() * 4) == hipSuccess;
-  ok = ok && hipMemcpy(dA, hA.data(), hA.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemcpy(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice) == hipSuccess &&
-       hipMemset(dC, 0, hC.size() * 4) == hipSuccess && hipMemset(dS, 0, hS.size() * 4) == hipSuccess;
-  if (ok) {
+  hipStream_t st = nullptr;
+  float* dA = nullptr;
+  auto run = [&]() {
+    ZCHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking) == hipSuccess, "direct TN GEMM self-test: no stream");
+    ZCHECK(hipMalloc(&dA, (hA.size() + hB.size() + hC.size()) * 4) == hipSuccess, "direct TN GEMM self-test: no memory");
+    float *dB = dA + hA.size(), *dC = dB + hB.size();
+    ZCHECK(hipMemcpyAsync(dA, hA.data(), hA.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemcpyAsync(dB, hB.data(), hB.size() * 4, hipMemcpyHostToDevice, st) == hipSuccess &&
+           hipMemsetAsync(dC, 0, hC.size() * 4, st) == hipSuccess, "direct TN GEMM self-test: copy failed");
     GemmArgs g = gemm_args(dA, dB, dC, M, N, K);      // C(m, n) = sum_k A[k][m] B[k][n]
-    g.sam = 1; g.sak = ldA; g.sbk = ldB; g.sbn = 1; g.scm = N; g.scn = 1; g.asum = dS;
-    int sv[4];
-    for (int i = 0; i < 4; ++i) sv[i] = tl_route[i];
-    tl_route[0] = big ? 2 : 3; tl_route[1] = shield ? 1 : 0; tl_route[2] = dep; tl_route[3] = 0;
-    const bool sv_failed = g_direct_failed;
-    g_direct_failed = false;
-    ok = launch_tn_direct(g, (hipStream_t)0) == 0;
-    tl_asum_consumed = false;
-    g_direct_failed = sv_failed;
-    for (int i = 0; i < 4; ++i) tl_route[i] = sv[i];
-    ok = ok && hipStreamSynchronize((hipStream_t)0) == hipSuccess &&
-         hipMemcpy(hC.data(), dC, hC.size() * 4, hipMemcpyDeviceToHost) == hipSuccess &&
-         hipMemcpy(hS.data(), dS, hS.size() * 4, hipMemcpyDeviceToHost) == hipSuccess;
+    g.sam = 1; g.sak = ldA; g.sbk = ldB; g.sbn = 1; g.scm = N; g.scn = 1; g.asum = dC + (size_t)M * N;
+    ZTRY(launch_tn_direct(g, direct_grid(variant, tn_shape(g), device_cus(), g_gemm_direct_wgs, 0), st));
+    ZCHECK(hipMemcpyAsync(hC.data(), dC, hC.size() * 4, hipMemcpyDeviceToHost, st) == hipSuccess &&
+           hipStreamSynchronize(st) == hipSuccess, "direct TN GEMM self-test: copy back failed");
+    return 0;
+  };
+  const bool ran = run() == 0;
+  if (dA) (void)hipFree(dA);
+  if (st) (void)hipStreamDestroy(st);
+  if (!ran) return DirectCheck::UNAVAILABLE;
+  const float* hS = hC.data() + (size_t)M * N;
+  double worst = 0.0;
+  for (int m = 0; m < M; ++m) {
+    double sa = 0.0;
+    for (int k = 0; k < K; ++k) sa += hA[(size_t)k * ldA + m];
+    worst = fmax(worst, fabs(sa - hS[m]));
   }
-  if (ok) {
-    double worst = 0.0;
-    for (int m = 0; m < M; ++m) {
-      double sa = 0.0;
-      for (int k = 0; k < K; ++k) sa += hA[(size_t)k * ldA + m];
-      worst = fmax(worst, fabs(sa - hS[m]));
+  for (int m = 0; m < M; m += 3)          // (every third row: the columns cover every lane of every fragment)
+    for (int n = 0; n < N; ++n) {
+      double acc = 0.0;
+      for (int k = 0; k < K; ++k) acc += (double)hA[(size_t)k * ldA + m] * hB[(size_t)k * ldB + n];
+      worst = fmax(worst, fabs(acc - hC[(size_t)m * N + n]));
     }
-    for (int m = 0; m < M; m += 3)          // (every third row: the columns cover every lane of every fragment)
-      for (int n = 0; n < N; ++n) {
-        double acc = 0.0;
-        for (int k = 0; k < K; ++k) acc += (double)hA[(size_t)k * ldA + m] * hB[(size_t)k * ldB + n];
-        worst = fmax(worst, fabs(acc - hC[(size_t)m * N + n]));
-      }
-    ok = worst < 2e-3;      // sums of 346 products of magnitude <= 1: fp32 rounding is ~1e-5; a stale operand is O(1)
-    if (!ok) fprintf(stderr, "zeggs: direct TN GEMM self-test (wave tile %s, depth %d%s) is off by %.3g\n", big ? "128x64" : "64x64",
-                     dep, shield ? ", shield" : "", worst);
-  }
-  (void)hipFree(dA); (void)hipFree(dB); (void)hipFree(dC); (void)hipFree(dS);
-  return ok;
+  if (worst < 2e-3) return DirectCheck::AGREES;      // sums of 346 products of magnitude <= 1: fp32 rounding is ~1e-5; a stale operand is O(1)
+  fprintf(stderr, "zeggs: direct TN GEMM self-test (wave tile %s, depth %d%s) is off by %.3g\n", big ? "128x64" : "64x64",
+          variant.depth, shield ? ", shield" : "", worst);
+  return DirectCheck::MISMATCH;
 }
-// true: the variant launch_tn_direct would pick for g is checked (or cannot be checked right now: stream capture)
-static bool direct_checked(const GemmArgs& g, hipStream_t s) {
-  const bool big = rt_direct() == 2 || (rt_direct() == 1 && (long)cdiv(g.M, 128) * cdiv(g.N, 128) >= 384);
-  const bool shield = rt_shield() == 1 || (rt_shield() == 2 && g.kbatch == 1 && (long)g.M * g.N >= 400000);
-  const int di = rt_depth() >= 8 ? 2 : rt_depth() >= 6 ? 1 : 0;
-  int& st = g_direct_checked[big][di][shield];
-  if (st == 1) return true;
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(s, &cap) != hipSuccess || cap != hipStreamCaptureStatusNone) return true;
-  if (direct_selftest(big, di == 2 ? 8 : di == 1 ? 6 : 4, shield)) { st = 1; return true; }
-  fprintf(stderr, "zeggs: the direct TN GEMM kernel is DISABLED for this process (self-test failed: built with another compiler?); "
-                  "the LDS-tiled stream-K kernel takes its products\n");
-  g_direct_failed = true;
-  return false;
-}
-int launch_streamk(GemmArgs g, hipStream_t s) {
+// asum_taken (may be null): the launch that ran took GemmArgs.asum (only the direct kernel does)
+int launch_streamk(GemmArgs g, hipStream_t s, bool* asum_taken) {
   if (gemm_split_ok(g)) return launch_tn_split(g, s);
-  if (direct_ok(g) && direct_checked(g, s)) return launch_tn_direct(g, s);
+  const int ncu = device_cus();      // (one query per product, as ever: the plan and the LDS-tiled grid share it)
+  const DirectPlan plan = direct_plan(tn_route(), tn_shape(g), ncu, g_gemm_direct_wgs);
+  if (plan.use && g_direct_first_use.go(plan, [s] { return stream_capturing(s); }, direct_selftest)) {
+    if (asum_taken) *asum_taken = g.asum != nullptr;
+    return launch_tn_direct(g, plan, s);
+  }
   if (dma_ok(g)) return launch_tn_dma(g, s);
   // 256 x 128 tiles (8 waves, 2 workgroups per CU: 3/4 of the operand bytes per product) pay on the big outputs only: +5 .. +8 %
   // on dW_ih0 (432 tiles of 128 x 128), -4 .. -6 % at 72 .. 200 tiles where the coarser grain costs balance
   // (profiles/r03_gemm_ablation.txt); -DZEGGS_GEMM_SK256=0 / 1 forces never / from 512 rows on
 #if ZEGGS_GEMM_SK256 == 1
-  if (g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, s);
+  if (g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s);
 #elif ZEGGS_GEMM_SK256 != 0
-  if ((long)cdiv(g.M, 128) * cdiv(g.N, 128) >= 384 && g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, s);
+  if (tn_big_output(g.M, g.N) && g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s);
 #endif
-  return launch_streamk_cfg<128, 128, 2, 2>(g, s);
+  return launch_streamk_cfg<128, 128, 2, 2>(g, ncu, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1055,11 +1022,13 @@ void zeggs_gemm_set_direct_depth(int d) { g_gemm_direct_depth = d; }
 void zeggs_gemm_set_direct_shield(int on) { g_gemm_direct_shield = on; }
 void zeggs_gemm_set_direct_reserve(int n) { g_gemm_direct_reserve = n; }
 extern "C" int zeggs_gemm_route(int direct, int shield, int depth, int reserve) {
-  tl_route[0] = direct; tl_route[1] = shield; tl_route[2] = depth; tl_route[3] = reserve;
+  const int r[4] = {direct, shield, depth, reserve};
+  memcpy(tl_route, r, sizeof(r));
   return 0;
 }
 extern "C" int zeggs_gemm_route_get(int* out4) {      // what this thread's next TN product would be routed by
-  out4[0] = rt_direct(); out4[1] = rt_shield(); out4[2] = rt_depth(); out4[3] = rt_reserve();
+  const TnRoute r = tn_route();
+  out4[0] = r.direct; out4[1] = r.shield; out4[2] = r.depth; out4[3] = r.reserve;
   return 0;
 }
 void zeggs_gemm_set_asum(int on) { g_gemm_asum = on; }
@@ -1072,7 +1041,8 @@ int g_gemm_mid_split = 1;      // zeggs_set_option("gemm_mid_split", 0/1): split
 // stream-K and 93 + 39 us as plain split-K tiles (tools/fold_probe.py; round 6: the threshold was 1024, every other stream-K product of the
 // training step has K >= 1536)
 constexpr long SK_MIN_KTILES = 80;
-int launch_gemm(GemmArgs g, int nbatch, hipStream_t s) {
+int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
+  if (asum_taken) *asum_taken = false;
   if (g.M <= 0 || g.N <= 0 || nbatch <= 0) return 0;
   if (g.nb1 <= 0) g.nb1 = 1;
   if (g.kbatch <= 0) g.kbatch = 1;
@@ -1151,7 +1121,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s) {
                          g.scn == 1 && g.scm == g.N && ktiles >= 64;
   if (g_gemm_streamk && can_split && big && g.nb1 == 1 && tiles < 1024 * 3 && ktiles >= SK_MIN_KTILES) {
     if (g.beta == 0.f) ZTRY(k_fill(g.C, (long)g.M * g.N, 0.f, s));     // beta == 1: the atomics accumulate onto C
-    return launch_streamk(g, s);
+    return launch_streamk(g, s, asum_taken);
   }
   if (tiles < g_gemm_wg_target * 5 / 6 && can_split) {
     long sk = (g_gemm_wg_target + tiles - 1) / tiles;
@@ -1251,14 +1221,32 @@ int gemm_tn_bias(const float* dy, long lddy, const float* x, long ldx, float* dW
   g.sam = 1; g.sak = lddy; g.sbk = ldx; g.sbn = 1; g.scm = lddw; g.scn = 1; g.beta = beta;
   // (beta == 0 would need db zeroed first: the separate launch does that; the bf16-split experiment has no row sums either)
   g.asum = (beta == 1.f && g_gemm_asum && !g_gemm_split_bf16) ? db : nullptr;
-  tl_asum_consumed = false;
-  ZTRY(launch_gemm(g, 1, s));
-  if (!tl_asum_consumed) ZTRY(k_colsum(db, dy, M_contract, N, lddy, beta, s));
+  bool asum_taken = false;
+  ZTRY(launch_gemm(g, 1, s, &asum_taken));
+  if (!asum_taken) ZTRY(k_colsum(db, dy, M_contract, N, lddy, beta, s));
   return 0;
 }
 
-extern "C" int zeggs_gemm_direct_selftest(int big, int depth, int shield) {
-  return direct_selftest(big != 0, depth >= 8 ? 8 : depth >= 6 ? 6 : 4, shield != 0) ? 1 : 0;
+extern "C" int zeggs_gemm_direct_selftest(int big, int depth, int shield) {      // on demand: records nothing
+  return direct_selftest(direct_variant(big != 0, depth, shield != 0)) == DirectCheck::AGREES ? 1 : 0;
+}
+extern "C" int zeggs_gemm_direct_state(int big, int depth, int shield) {
+  return g_direct_first_use.at(big != 0, depth, shield != 0).load(std::memory_order_acquire);
+}
+// the first-use check now, on no caller stream, of every variant the calling thread's route can select
+extern "C" int zeggs_gemm_direct_warm(void) {
+  const TnRoute r = tn_route();
+  bool unavailable = false;
+  for (int big = 0; big < 2; ++big)
+    for (int shield = 0; shield < 2; ++shield) {
+      if (!route_selects(r, big, shield)) continue;
+      g_direct_first_use.go(direct_variant(big, r.depth, shield), [] { return false; }, [&](const DirectPlan& v) {
+        const DirectCheck c = direct_selftest(v);
+        unavailable |= c == DirectCheck::UNAVAILABLE;
+        return c;
+      });
+    }
+  return unavailable ? -1 : 0;
 }
 extern "C" int zeggs_gemm_tn_bias(const float* dy, long lddy, const float* x, long ldx, float* dW, long lddw, int M_contract, int N,
                                   int K, float beta, float* db, void* stream) {

@@ -266,6 +266,13 @@ class TrainEngine:
             # The routing belongs to THIS engine's calls (zeggs_gemm_route through ops.EngineContext): another engine or a plain
             # caller in the process keeps the library's defaults; a caller who set the options himself keeps his.
             self.ctx.gemm_route = (1, 1, 8, int(os.environ.get("ZEGGS_GEMM_RESERVE", 32)) if world_size > 1 else 0)
+        if torch.device(dataset.device).type == "cuda":
+            # the first-use check of the variants that route selects, here instead of in the middle of the first backward (a check
+            # that could not run is tried again by the first product that wants the variant)
+            with torch.cuda.device(dataset.device), ops.use(self.ctx):
+                unavailable = ops.gemm_direct_warm()
+                if unavailable:
+                    warnings.warn(f"direct TN GEMM first-use check postponed: {unavailable}")
         # the speech encoder (a short chain of small launches, forward and -- autograd replays a node on the stream of its
         # forward -- backward) beside the style encoder
         self.aux_stream = torch.cuda.Stream(device=dataset.device) if on_gpu else None

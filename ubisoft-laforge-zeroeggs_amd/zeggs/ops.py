@@ -68,7 +68,7 @@ GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "b
 # what the binding needs beyond the header's older entry points: checked when the library is loaded, so that a stale
 # libzeggs_hip.so fails with a message instead of an AttributeError in the middle of a job list
 REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
-                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c")
+                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm")
 
 
 def lib():
@@ -164,7 +164,8 @@ class EngineContext:
         self.prepared_hits = 0
         self.wgrad_keepalive = []          # workspaces the deferred GEMMs still read, until the caller joined wgrad_stream
         self.seed_rng = None               # own noise-seed generator (None: the process-wide stream of ops.manual_seed)
-        self.gemm_route = None             # (direct, shield, depth, reserve) of THIS context's weight-gradient products (zeggs_gemm_route)
+        self.gemm_route = None             # (direct, shield, depth, reserve) of THIS context's weight-gradient products (zeggs_gemm_route);
+                                           # takes precedence over set_option("gemm_direct*") for them (-1 / None: the option)
         self.defer_style_wgrads = False    # the attention style encoder's backward enqueues its chain only and leaves its six weight-
         self.deferred_wgrads = []          # gradient products here as (event, fn()): the caller runs them on another stream and joins
 
@@ -191,6 +192,14 @@ def _route(ectx):
         _tls.route = r
 
 
+def gemm_direct_warm():
+    """The first-use check of every direct weight-gradient kernel variant the current context's route can select, now and on no
+    caller stream (zeggs_gemm_direct_warm), so that no later product stops for it.  -> None, or why a check could not run (the
+    first product that wants that variant tries again)."""
+    _route(current())
+    return None if lib().zeggs_gemm_direct_warm() == 0 else lib().zeggs_last_error().decode()
+
+
 def current():
     return getattr(_tls, "ctx", None) or _DEFAULT_CTX
 
@@ -208,6 +217,7 @@ class use:
 
     def __exit__(self, *exc):
         _tls.ctx = self.prev
+        _route(current())                  # the route goes with its context: a raw zeggs_gemm* caller gets the outer one's again
 
 
 _SIDE_STREAMS = {}
