@@ -638,6 +638,17 @@ int zeggs_parse_table_text(const char* text, size_t len, double* table /* host *
  * blocks, the caller writes the blocks in order); *written = bytes produced.  cap >= rows * (cols * 24 + 1) suffices. */
 int zeggs_format_table_text(const double* table /* host */, long rows, int cols, char* out, size_t cap, size_t* written);
 
+/* The same text made ON THE DEVICE (csrc/text.hip; zeggs_version() >= 105): table [rows, cols] float64 (device) -> text (device): "%f" +
+ * ' ' per number, '\n' per row, the bytes zeggs_format_table_text gives.  row_end [rows] int64 (device): byte offset just past row r's
+ * '\n' (row_end[rows-1] = total).  Never writes at or past text + cap; cap >= rows * (cols * 24 + 1) always suffices; a row that would
+ * pass cap is left out whole and status bit 1 is ORed in (row_end still holds every offset).  status (device unsigned[1], caller-
+ * zeroed, may not be NULL): bit 0 ORed in when any value was out of the domain of the digit routine -- NaN, +-inf, |x| >= 1e15 -- (its
+ * slot then holds "0.000000": placeholder, memory-safe, NOT the answer; the caller formats such a table on the host).  ws: caller-
+ * owned, zeggs_table_text_workspace_bytes(rows, cols) bytes.  rows = 0 returns 0 and touches nothing. */
+size_t zeggs_table_text_workspace_bytes(long rows, int cols);
+int zeggs_table_text_device(const double* table, long rows, int cols, char* text, size_t cap, long long* row_end,
+                            unsigned* status, void* ws, size_t ws_bytes, void* stream);
+
 /* Dataset preparation (csrc/prepare.hip; zeggs_version() >= 103): the stages of ZEGGS/data_pipeline.py:234-736 around preprocess_audio /
  * preprocess_animation.  All pointers are device pointers unless marked; workspaces are caller-owned.
  *

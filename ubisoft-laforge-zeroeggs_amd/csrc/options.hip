@@ -9,6 +9,7 @@ extern int g_decoder_fast, g_bwd_chunks, g_tp_prologue, g_wgrad_order;          
 extern int g_stage_variant, g_timing, g_chain, g_sweep_graphs, g_launch_window;               // decoder_fast.hip
 extern int g_tp_tiles4, g_tp_dual;                                                            // train_persistent.hip, train_dual.hip
 extern int g_gemm_wg_target, g_gemm_streamk_wgs, g_gemm_mid_split, g_gemm_skinny, g_gemm_streamk, g_gemm_split_bf16;   // gemm*.hip
+extern int g_text_emit, g_text_passes;                                                          // text.hip
 extern int g_mel_mfma, g_mel_fft, g_mel_exact_log, g_loss_lds, g_ln_bwd4;                     // mel.hip, loss.hip, kernels.hip
 void zeggs_gemm_set_dma(int on), zeggs_gemm_set_direct(int mode, int wgs), zeggs_gemm_set_direct_depth(int d);           // gemm.hip
 void zeggs_gemm_set_direct_shield(int on), zeggs_gemm_set_direct_reserve(int n), zeggs_gemm_set_asum(int on);
@@ -64,6 +65,9 @@ const Option k_options[] = {
   {"persistent_spin", &g_persistent_spin, MIN0},
   {"ln_bwd4", &g_ln_bwd4, AS_GIVEN},
   {"mel_exact_log", &g_mel_exact_log, AS_GIVEN},
+  // device BVH text: text_emit 1 = the LDS-assembly emit variant (0: per-byte stores); text_passes: bit mask measure / scan / emit (tools/bvh_text_bench.py only)
+  {"text_emit", &g_text_emit, AS_GIVEN},
+  {"text_passes", &g_text_passes, AS_GIVEN},
 };
 }  // namespace
 

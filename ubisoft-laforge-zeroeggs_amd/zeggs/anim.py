@@ -1,5 +1,5 @@
-"""Animation plumbing around the decoder: BVH text I/O on the host, feature extraction and BVH-channel
-conversion on the device (csrc/anim.hip, float64).
+"""Animation plumbing around the decoder: BVH file I/O on the host, feature extraction, BVH-channel conversion (csrc/anim.hip,
+float64) and the formatting of the motion text (csrc/text.hip) on the device.
 
 Semantics follow the reference so that `generate_gesture()` consumes and produces the same files:
   ZEGGS/anim/bvh.py (BVH reader/writer), ZEGGS/data_pipeline.py:90-228 (preprocess_animation),
@@ -134,12 +134,44 @@ def bvh_header(offsets, parents, names=None, order="zyx", nframes=0, frametime=1
     return "\n".join(out) + "\n", seq
 
 
-def bvh_save(filename, data):
-    """Writes root with 6 channels and every other joint with 3 (reference bvh.save, translations=False)."""
-    rots, poss = np.asarray(data["rotations"]), np.asarray(data["positions"])
+TEXT = "device"                   # default of the writers' `text=`: "device" (csrc/text.hip) or "host" (snprintf, hostio.hip)
+TEXT_FALLBACKS = 0                # tables the device formatter handed back to the host one (a value outside its domain)
+TEXT_UPLOAD_MIN_NUMBERS = 3648    # a HOST table goes through the device (upload + format + download) from this many numbers on
+                                  # (16 rows of 228): measured 0.52 ms against the host's 0.76 ms there, 0.51 against 0.43 ms at 4
+                                  # rows, and the device's cost stays under 0.8 ms up to 256 rows (profiles/bvh_text_device.json)
+
+
+def _use_device_text(text, on_device, numbers):
+    text = TEXT if text is None else text
+    if text not in ("device", "host"):
+        raise ValueError(f"text must be 'device' or 'host', not {text!r}")
+    return text == "device" and numbers > 0 and (on_device or (numbers >= TEXT_UPLOAD_MIN_NUMBERS and torch.cuda.is_available()))
+
+
+def bvh_save(filename, data, text=None):
+    """Writes root with 6 channels and every other joint with 3 (reference bvh.save, translations=False).  `rotations` /
+    `positions` may be host arrays or device tensors; text = "device" | "host" (None: anim.TEXT) chooses who formats the motion
+    block: the device for device tensors and for host tables of TEXT_UPLOAD_MIN_NUMBERS numbers or more, else the host."""
+    rots, poss = data["rotations"], data["positions"]
     head, seq = bvh_header(data["offsets"], data["parents"], data.get("names"), data.get("order", "zyx"), len(rots),
                            data.get("frametime", 1.0 / 60.0))
-    # motion block: one row per frame = root position + the rotations in hierarchy order
+    on_device = torch.is_tensor(rots) and rots.is_cuda
+    n = len(rots)
+    if _use_device_text(text, on_device, n * (3 + 3 * len(seq))):
+        # motion block: one row per frame = root position + the rotations in hierarchy order, built and formatted on the device
+        dev = rots.device if on_device else torch.device("cuda")
+        up = lambda a: (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dev, torch.float64)  # noqa: E731
+        table = torch.cat([up(poss[:, 0]).reshape(n, 3),
+                           up(rots)[:, torch.as_tensor(seq, device=dev)].reshape(n, 3 * len(seq))], dim=1).contiguous()
+        with open(filename, "wb") as fh:
+            fh.write(head.encode())
+            fh.write(format_rows_device(table)[0])
+        return
+    if torch.is_tensor(rots):
+        rots = rots.cpu().numpy()
+    if torch.is_tensor(poss):
+        poss = poss.cpu().numpy()
+    rots, poss = np.asarray(rots), np.asarray(poss)
     table = np.concatenate([np.asarray(poss[:, 0], np.float64).reshape(len(rots), 3)] +
                            [np.asarray(rots[:, j], np.float64).reshape(len(rots), 3) for j in seq], axis=1)
     with open(filename, "w") as fh:
@@ -153,11 +185,12 @@ def bvh_save(filename, data):
         raise OSError("zeggs_write_table_text: " + ops.lib().zeggs_last_error().decode())
 
 
-def format_rows(table):
+def format_rows(table, any_magnitude=False):
     """host float64 [rows, cols] (C-contiguous; e.g. a view of a pinned staging buffer) -> bytes of the BVH motion rows
-    (zeggs_format_table_text: releases the GIL, so several host threads format row blocks side by side)"""
+    (zeggs_format_table_text: releases the GIL, so several host threads format row blocks side by side).  The buffer is sized
+    for |values| < 1e15 (24 bytes per number); any_magnitude: for whatever a double can hold ("%f" of 1e308 has 309 digits)."""
     rows, cols = table.shape
-    cap = rows * (cols * 24 + 1) + 400
+    cap = rows * (cols * (330 if any_magnitude else 24) + 1) + 400
     buf = C.create_string_buffer(cap)
     n = C.c_size_t(0)
     ptr = table.ctypes.data_as(C.c_void_p) if isinstance(table, np.ndarray) else C.c_void_p(table.data_ptr())
@@ -165,6 +198,67 @@ def format_rows(table):
     if rc != 0:
         raise RuntimeError("zeggs_format_table_text: " + ops.lib().zeggs_last_error().decode())
     return buf.raw[:n.value]
+
+
+def table_text_device(table, cap=None):
+    """device float64 [rows, cols] (contiguous) -> (text uint8 [cap] device, meta int64 [rows + 1] device), enqueued on the current
+    stream (zeggs_table_text_device): text[:meta[rows - 1]] are the bytes format_rows gives, meta[:rows] the offset just past each
+    row's line end, and the low 32 bits of meta[rows] the status word (bit 0: a value outside the digit routine's domain -- the text
+    then holds a placeholder there and the caller formats the table on the host; bit 1: `cap` was too small)."""
+    if not (table.is_cuda and table.dtype == torch.float64 and table.dim() == 2 and table.is_contiguous()):
+        raise ValueError("table_text_device: a contiguous float64 [rows, cols] device tensor is expected")
+    rows, cols = table.shape
+    if rows == 0 or cols == 0:
+        raise ValueError("table_text_device: empty table")
+    L = ops.lib()
+    L.zeggs_table_text_workspace_bytes.restype = C.c_size_t
+    cap = rows * (cols * 24 + 1) if cap is None else int(cap)
+    text = torch.empty(cap, dtype=torch.uint8, device=table.device)
+    meta = torch.empty(rows + 1, dtype=torch.int64, device=table.device)
+    meta[rows:].zero_()
+    nws = int(L.zeggs_table_text_workspace_bytes(C.c_long(rows), int(cols)))
+    ws = torch.empty(nws, dtype=torch.uint8, device=table.device)      # (stream-ordered: may go back to the allocator on return)
+    rc = L.zeggs_table_text_device(C.c_void_p(table.data_ptr()), C.c_long(rows), int(cols), C.c_void_p(text.data_ptr()),
+                                   C.c_size_t(cap), C.c_void_p(meta.data_ptr()), C.c_void_p(meta[rows:].data_ptr()),
+                                   C.c_void_p(ws.data_ptr()), C.c_size_t(nws), _stream())
+    if rc != 0:
+        raise RuntimeError("zeggs_table_text_device: " + L.zeggs_last_error().decode())
+    return text, meta
+
+
+def _host_pieces(table, bounds):
+    """the out-of-domain rule, in one place: the table is downloaded and formatted by the host routine (snprintf: `nan`, `inf` and
+    hundreds of digits included), and the event is counted"""
+    global TEXT_FALLBACKS
+    TEXT_FALLBACKS += 1
+    host = np.ascontiguousarray(table.cpu().numpy())
+    return [format_rows(host[a:b], any_magnitude=True) for a, b in zip(bounds[:-1], bounds[1:])]
+
+
+def format_rows_device(table, cuts=None):
+    """device float64 [rows, cols] -> the bytes of format_rows, formatted where the numbers are: the row ends come down first (8
+    bytes per row), then exactly row_end[-1] bytes of text into pinned memory.  -> list of memoryview / bytes: the text cut in front
+    of the rows `cuts` (ascending row indices; pieces of different clips share one table in the batch path), one piece without
+    cuts.  A table with a value outside the device routine's domain (status word) is formatted by the host routine instead and
+    counted in TEXT_FALLBACKS."""
+    rows = table.shape[0]
+    bounds = [0] + [int(c) for c in (cuts or [])] + [rows]
+    if any(a > b for a, b in zip(bounds[:-1], bounds[1:])):
+        raise ValueError("format_rows_device: cuts must be ascending row indices within the table")
+    if rows == 0:
+        return [b""] * (len(bounds) - 1)
+    table = table.contiguous()
+    text, meta = table_text_device(table)
+    meta_h = meta.cpu().numpy()                         # (waits for the kernels)
+    if int(meta_h[rows]) & 0xFFFFFFFF:
+        return _host_pieces(table, bounds)
+    total = int(meta_h[rows - 1])
+    host = torch.empty(total, dtype=torch.uint8, pin_memory=True)
+    host.copy_(text[:total], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    view = memoryview(host.numpy())
+    ends = [0] + [int(x) for x in meta_h[:rows]]
+    return [view[ends[a]:ends[b]] for a, b in zip(bounds[:-1], bounds[1:])]
 
 
 # ----------------------------------------------------------------------------- device kernels (csrc/anim.hip)
@@ -265,15 +359,20 @@ def bvh_channels(root_pos, root_rot, lpos, ltxy, start_position=None, start_rota
 
 
 def write_bvh(filename, root_pos, root_rot, lpos, ltxy, parents, names, order, dt, start_position=None,
-              start_rotation=None):
+              start_rotation=None, text=None):
     """reference utils.write_bvh, fed with the decoder's two-axis rotations (the quaternion / euler conversion of
-    generate.py:389 happens on the device)."""
+    generate.py:389 happens on the device; text: see bvh_save)."""
     positions, euler = bvh_channels(root_pos, root_rot, lpos, ltxy, start_position, start_rotation, order)
-    write_bvh_channels(filename, positions, euler, parents, names, order, dt)
+    write_bvh_channels(filename, positions, euler, parents, names, order, dt, text=text)
 
 
-def write_bvh_channels(filename, positions, euler, parents, names, order, dt):
-    """the file half of write_bvh: device channel tables (bvh_channels) -> BVH text"""
+def write_bvh_channels(filename, positions, euler, parents, names, order, dt, text=None):
+    """the file half of write_bvh: device channel tables (bvh_channels) -> BVH text.  The channels stay on the device when the
+    device formats them (text = "device", the default anim.TEXT); only frame 0's positions -- the OFFSETs -- come to the host."""
+    if _use_device_text(text, positions.is_cuda, positions.shape[0] * positions.shape[1] * 3):
+        bvh_save(filename, dict(order=order, offsets=positions[0].cpu().numpy(), names=names, frametime=dt, parents=parents,
+                                positions=positions, rotations=euler), text="device")
+        return
     positions = positions.cpu().numpy()
     bvh_save(filename, dict(order=order, offsets=positions[0], names=names, frametime=dt, parents=parents,
-                            positions=positions, rotations=euler.cpu().numpy()))
+                            positions=positions, rotations=euler.cpu().numpy()), text="host")

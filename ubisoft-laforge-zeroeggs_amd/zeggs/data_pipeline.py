@@ -371,7 +371,8 @@ def data_pipeline(conf, device="cuda", log=None, timings=None):
             if conf["save_trimmed_animation"]:
                 folder.mkdir(exist_ok=True, parents=True)
                 center_take(pos, rot, take["order"], round_f32=(ratio == 1.0))
-                zanim.bvh_save(folder / (name + ".bvh"), dict(take, positions=pos.cpu().numpy(), rotations=rot.cpu().numpy()))
+                # (device float64 channels: the motion text is formatted where they are, anim.TEXT = "host" downloads them instead)
+                zanim.bvh_save(folder / (name + ".bvh"), dict(take, positions=pos, rotations=rot))
                 lap("write_bvh")
             # ---- features, straight into the dataset's buffers
             nframes = rot.shape[0]

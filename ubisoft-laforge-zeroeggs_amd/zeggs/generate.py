@@ -74,16 +74,17 @@ def _example_features(p):
 
 STREAM_MIN_FRAMES = 20000     # clips longer than this are decoded chunk by chunk with the BVH text written meanwhile
 STREAM_CHUNK = 8192
-STREAM_BLOCK = 512            # rows per formatting task (host threads)
+STREAM_BLOCK = 512            # rows per formatting task (host threads; anim.TEXT = "host" only)
 
 
 def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, style, stats, dt, path, parents, names,
                              chunk=None, block=None, threads=None):
     """Long clips (configs[4]: 108 000 frames): the B = 1 rollout runs as a sequence of persistent launches of `chunk` frames,
     each resumed from the state of the one before (zeggs_decoder_fwd_state_ex); behind every chunk its frames are converted to
-    the rows of the BVH motion block ON THE DEVICE (zeggs_pose_to_bvh_table), downloaded on a copy stream into pinned memory
-    and formatted by host threads (zeggs_format_table_text) WHILE the next chunks are being decoded; this thread writes the
-    text blocks in order.  Same file as the one-launch path (decoder -> bvh_channels -> write_bvh_channels) up to the fp32
+    the rows of the BVH motion block ON THE DEVICE (zeggs_pose_to_bvh_table) and formatted there (zeggs_table_text_device: what
+    comes down on the copy streams into pinned memory is the file content; anim.TEXT = "host": the float64 rows come down and
+    host threads format them, zeggs_format_table_text) WHILE the next chunks are being decoded -- _TextStaging; this thread writes
+    the text in order.  Same file as the one-launch path (decoder -> bvh_channels -> write_bvh_channels) up to the fp32
     re-association at the chunk boundaries (joint rotations a few hundredths of a degree apart after 700 free-running frames):
     tests/test_gpu_parity.py::test_generate_gesture_streaming_writer_equals_one_launch.  The decoder's frames are not kept
     (488 MB for 30 minutes).  Give-ups of the persistent kernel are collected in one status word that is looked at ONCE, after
@@ -110,29 +111,30 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
     d.start_pos[:] = [0.0, 0.0, 0.0]
     d.start_rot[:] = [1.0, 0.0, 0.0, 0.0]
     ref_pos, ref_rot = rpos0.to(torch.float32).contiguous(), rrot0.to(torch.float32).contiguous()
-    copy_stream = torch.cuda.Stream(device=dev)
     status = ops.new_status(dev)
     main = torch.cuda.current_stream()
 
     # the last chunk is what nothing hides: its rows are converted, downloaded, formatted (36 us of host time per row: 18 ms for
     # a 512-row task) and written AFTER the decode has ended -- so it is short and its formatting tasks are small
-    workers = threads or min(16, (__import__("os").cpu_count() or 4))
+    # (with the device text a pool thread only waits for a chunk's row ends and issues its sized copy: two are plenty)
+    workers = threads or (2 if anim.TEXT == "device" else min(16, (__import__("os").cpu_count() or 4)))
     tail_rows = max(1, min(chunk // 16, 512))
     RING = 4                                             # pinned staging buffers in flight (page-locking 15 MB costs ~5 ms: not per chunk)
-    ring = _pinned_ring(RING, min(chunk, T) + 1, cols)
+    stage = _TextStaging(dev, RING, min(chunk, T) + 1, cols)
 
     marks = []
 
     def run(pool, fh):
         """decode chunk by chunk; chunk c's text is written while chunks c + 1 .. c + RING - 1 are queued on the device"""
-        pending = []                                     # per chunk in flight: its formatting futures, in row order
+        stage.pool = pool
+        pending = []                                     # per chunk in flight: the getters of its text, in row order
         state = (pose0, rpos0, rrot0, None)
-        k, c = 0, 0                                      # last frame produced so far, chunk index
+        k = 0                                            # last frame produced so far
 
         def drain(keep):
             while len(pending) > keep:
-                for f in pending.pop(0):
-                    fh.write(f.result())
+                for get in pending.pop(0):
+                    fh.write(get())
         while True:
             n = min(chunk, T - 1 - k)                    # new frames of this chunk
             if n == T - 1 - k and n > tail_rows:         # the LAST chunk is short: what follows the end of the decode is only its
@@ -161,25 +163,11 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
             del a_rpos, a_rrot, a_lpos, a_ltxy
             if rc != 0:
                 raise RuntimeError("zeggs_pose_to_bvh_table: " + L.zeggs_last_error().decode())
-            done = torch.cuda.Event()
-            done.record(main)
-            drain(RING - 1)                              # the staging buffer of chunk c - RING has been formatted and written
-            host = ring[c % RING][:rows]
-            with torch.cuda.stream(copy_stream):
-                copy_stream.wait_event(done)
-                host.copy_(table, non_blocking=True)
-                table.record_stream(copy_stream)
-                ev = torch.cuda.Event()
-                ev.record(copy_stream)
-
-            def fmt(host=host, ev=ev, r0=0, r1=0):
-                ev.synchronize()
-                return anim.format_rows(host[r0:r1].numpy())
+            drain(RING - 1)                              # the staging buffer of chunk c - RING has been written
             last = n == 0 or k + n >= T - 1
             blk = block if not last else max(16, -(-rows // (2 * workers)))
-            pending.append([pool.submit(fmt, r0=r0, r1=min(r0 + blk, rows)) for r0 in range(0, rows, blk)])
+            pending.append(stage.submit(table, [(0, rows)], blk)[0])
             k += n
-            c += 1
             if n == 0 or k >= T - 1:
                 break
         marks.append(_t0.perf_counter())                 # everything is enqueued
@@ -213,35 +201,117 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
                 finally:
                     ops.set_option("persistent", was)
     finally:
-        _pinned_release(ring)
+        stage.release()
 
 
-_PINNED = {}                      # (count, cols) -> list of free rings: a ring is CHECKED OUT for the duration of one call
+_PINNED = {}                      # (count, cols, dtype) -> list of free rings: a ring is CHECKED OUT for the duration of one call
 _PINNED_LOCK = __import__("threading").Lock()
 
 
-def _pinned_ring(count, rows, cols):
-    """`count` page-locked float64 staging buffers [rows, cols].  Page-locking is the expensive part (4 x 15 MB for the default
-    chunk), so rings are pooled for the life of the process -- but a ring belongs to ONE call at a time (two
-    generate_gesture() calls on two threads shared the buffers and corrupted each other's rows): take one with this function,
-    give it back with _pinned_release()."""
-    key = (count, cols)
+def _pinned_ring(count, rows, cols, dtype=torch.float64):
+    """`count` page-locked staging buffers [rows, cols] (float64 table rows for the host formatter, uint8 text bytes and int64 row
+    ends for the device one).  Page-locking is the expensive part (4 x 15 MB for the default chunk), so rings are pooled for the
+    life of the process -- but a ring belongs to ONE call at a time (two generate_gesture() calls on two threads shared
+    the buffers and corrupted each other's rows): take one with this function, give it back with _pinned_release()."""
+    key = (count, cols, dtype)
     with _PINNED_LOCK:
         free = _PINNED.setdefault(key, [])
         for i, ring in enumerate(free):
-            if ring[0].shape[0] >= rows:
+            if min(b.shape[0] for b in ring) >= rows:
                 return free.pop(i)
-    return [torch.empty(rows, cols, dtype=torch.float64).pin_memory() for _ in range(count)]
+    return [torch.empty(rows, cols, dtype=dtype).pin_memory() for _ in range(count)]
 
 
 def _pinned_release(ring):
-    """Back to the pool -- which keeps ONE free ring per (count, cols), the largest: a smaller one can serve nobody the larger
+    """Back to the pool -- which keeps ONE free ring per (count, cols, dtype), the largest: a smaller one can serve nobody the larger
     cannot, and page-locked memory that only accumulates with varying clip / chunk sizes is memory the system cannot page."""
     with _PINNED_LOCK:
-        free = _PINNED.setdefault((len(ring), ring[0].shape[1]), [])
+        free = _PINNED.setdefault((len(ring), ring[0].shape[1], ring[0].dtype), [])
         free.append(ring)
-        free.sort(key=lambda r: -r[0].shape[0])
+        free.sort(key=lambda r: -min(b.shape[0] for b in r))
         del free[1:]
+
+
+class _TextStaging:
+    """What one writer call (streaming or batch) needs to turn device tables into text underneath the decode: the copy streams, the
+    pinned rings (checked out for this call) and the two ways to the bytes.
+      anim.TEXT = "device": the table is formatted on `main` behind the kernel that made it (anim.table_text_device); the row ends
+        and the status word come down on the copy stream (8 bytes per row); ONE pool task per table waits for them, issues the copy
+        of exactly row_end[-1] bytes into the pinned byte ring (grown when a table's text is longer than the slot) and hands out
+        memoryviews cut at the spans.  The task holds the table until the status word has been read: a value outside the digit
+        routine's domain sends the table through the host formatter (anim._host_pieces).
+      anim.TEXT = "host": the table comes down as float64 and pool tasks format blocks of rows (anim.format_rows), as before.
+    submit() -> per span a list of callables, each returning the next bytes of that span once they are there."""
+    TEXT_ROW = 12            # bytes per number the byte ring starts with ("-123.456789 "); the bound is 24: slots grow on demand
+
+    def __init__(self, dev, count, rows, cols):
+        self.pool, self.count, self.used = None, count, 0      # (pool: the caller's thread pool, set before submit)
+        self.device_text = anim.TEXT == "device"
+        self.main = torch.cuda.current_stream()
+        self.copy_stream = torch.cuda.Stream(device=dev)
+        if self.device_text:
+            self.text_stream = torch.cuda.Stream(device=dev)      # (the sized copies: never behind the next chunk's row ends)
+            self.rings = [_pinned_ring(count, rows, cols * self.TEXT_ROW + 1, torch.uint8), _pinned_ring(count, rows + 1, 1, torch.int64)]
+        else:
+            self.rings = [_pinned_ring(count, rows, cols)]
+
+    def release(self):
+        for ring in self.rings:
+            _pinned_release(ring)
+
+    def submit(self, table, spans, block):
+        """table [rows, cols] float64 made on `main`; spans [(first row, rows), ...] in row order, covering it.  The caller has
+        drained the slot used `count` submissions ago."""
+        rows = table.shape[0]
+        slot = self.used % self.count
+        self.used += 1
+        if not self.device_text:
+            done = torch.cuda.Event()
+            done.record(self.main)
+            host = self.rings[0][slot][:rows]
+            with torch.cuda.stream(self.copy_stream):
+                self.copy_stream.wait_event(done)
+                host.copy_(table, non_blocking=True)
+                table.record_stream(self.copy_stream)
+                ev = torch.cuda.Event()
+                ev.record(self.copy_stream)
+
+            def fmt(a, b):
+                ev.synchronize()
+                return anim.format_rows(host[a:b].numpy())
+            return [[self.pool.submit(fmt, a, min(a + block, s0 + n)).result for a in range(s0, s0 + n, block)] for s0, n in spans]
+        text, meta = anim.table_text_device(table)
+        done = torch.cuda.Event()
+        done.record(self.main)
+        meta_h = self.rings[1][slot][:rows + 1, 0]
+        with torch.cuda.stream(self.copy_stream):
+            self.copy_stream.wait_event(done)
+            meta_h.copy_(meta, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record(self.copy_stream)
+        bounds = [s0 for s0, _ in spans] + [rows]
+
+        def fetch(keep=(table, text, meta)):      # (the device buffers live until their bytes are on the host: the copies run on
+            ev.synchronize()                      #  other streams than the one the allocator hands their blocks out on)
+            m = meta_h.numpy()
+            if int(m[rows]) & 0xFFFFFFFF:
+                return anim._host_pieces(table, bounds)
+            total = int(m[rows - 1])
+            ring = self.rings[0]
+            if ring[slot].numel() < total:
+                width = ring[slot].shape[1]
+                ring[slot] = torch.empty(-(-(total + total // 4) // width), width, dtype=torch.uint8).pin_memory()
+            flat = ring[slot].view(-1)[:total]
+            with torch.cuda.stream(self.text_stream):
+                flat.copy_(text[:total], non_blocking=True)
+                got = torch.cuda.Event()
+                got.record(self.text_stream)
+            got.synchronize()
+            view = memoryview(flat.numpy())
+            end = lambda r: int(m[r - 1]) if r else 0  # noqa: E731
+            return [view[end(a):end(b)] for a, b in zip(bounds[:-1], bounds[1:])]
+        fut = self.pool.submit(fetch)
+        return [[lambda i=i: fut.result()[i]] for i in range(len(spans))]
 
 
 class _Loaded:
@@ -576,9 +646,10 @@ def decode_plan(bd, firsts, speech, style, plan, status=None, fill=0.0, infos=No
 
 def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, block=None):
     """The clips of `fes` on `batch` rows of the weight-stationary sweep (ops.decoder_batch_chunk), chunk by chunk through the slot
-    plan; every (row, chunk) piece is converted to BVH motion rows on the device (zeggs_pose_to_bvh_table), downloaded into pinned
-    memory on a copy stream and formatted by host threads underneath the following chunks -- the mechanism of
-    _decode_to_bvh_streaming; this thread writes each clip's text in order.  `paths[j]` None: no file for clip j."""
+    plan; every (row, chunk) piece is converted to BVH motion rows on the device (zeggs_pose_to_bvh_table), a chunk's pieces share
+    one table, which is formatted on the device and comes down as text cut at the pieces (anim.TEXT = "host": as float64 rows that
+    host threads format) underneath the following chunks -- _TextStaging, the mechanism of _decode_to_bvh_streaming; this thread
+    writes each clip's text in order.  `paths[j]` None: no file for clip j."""
     import ctypes as C
     from concurrent.futures import ThreadPoolExecutor
     from . import ops
@@ -604,16 +675,14 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
     d = anim.BvhDims(0, J, 1)
     d.start_pos[:] = [0.0, 0.0, 0.0]
     d.start_rot[:] = [1.0, 0.0, 0.0, 0.0]
-    copy_stream = torch.cuda.Stream(device=dev)
     main = torch.cuda.current_stream()
     status = ops.new_status(dev)
-    workers = threads or min(16, (__import__("os").cpu_count() or 4))
+    workers = threads or (2 if anim.TEXT == "device" else min(16, (__import__("os").cpu_count() or 4)))
     block = block or STREAM_BLOCK
-    ring = _pinned_ring(BATCH_RING, batch * chunk, cols)
+    stage = _TextStaging(dev, BATCH_RING, batch * chunk, cols)
     kept = [[] for _ in fes] if return_poses else None
     files = {}
-    pending = []                     # per chunk in flight: [(clip, future), ...] in (row, block) order
-    used = 0                         # staging buffers handed out so far
+    pending = []                     # per chunk in flight: [(clip, getter of the next bytes, clip ends here), ...] in row order
 
     dead = set()                     # clips whose file could not be opened or written: reported, the other clips go on
 
@@ -622,8 +691,8 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
 
     def drain(keep):
         while len(pending) > keep:
-            for j, f, last in pending.pop(0):
-                txt = f.result()
+            for j, get, last in pending.pop(0):
+                txt = get()
                 if live(j):
                     try:
                         files[j].write(txt)
@@ -635,6 +704,7 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
 
     try:
         with ThreadPoolExecutor(max_workers=workers) as pool:
+            stage.pool = pool
             for pieces, pose, rpos, rrot in decode_plan(bd, firsts, speech, style, plan, status=status):
                 for r, j, k, n in pieces:
                     if k == 0 and paths[j] is not None:
@@ -673,28 +743,15 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
                     del a_rpos, a_rrot, a_lpos, a_ltxy
                 if not spans:
                     continue
-                done = torch.cuda.Event()
-                done.record(main)
-                drain(BATCH_RING - 1)            # the staging buffer used BATCH_RING chunks ago has been formatted and written
-                host = ring[used % BATCH_RING][:r0]
-                used += 1
-                with torch.cuda.stream(copy_stream):
-                    copy_stream.wait_event(done)
-                    host.copy_(table[:r0], non_blocking=True)
-                    table.record_stream(copy_stream)
-                    ev = torch.cuda.Event()
-                    ev.record(copy_stream)
-
-                def fmt(host=host, ev=ev, a=0, b=0):
-                    ev.synchronize()
-                    return anim.format_rows(host[a:b].numpy())
-                pending.append([(j, pool.submit(fmt, a=a, b=min(a + block, s0 + rows)), end and a + block >= s0 + rows)
-                                for j, s0, rows, end in spans for a in range(s0, s0 + rows, block)])
+                drain(BATCH_RING - 1)            # the staging buffer used BATCH_RING chunks ago has been written
+                getters = stage.submit(table[:r0], [(s0, rows) for _, s0, rows, _ in spans], block)
+                pending.append([(j, get, end and i == len(gs) - 1) for (j, _, _, end), gs in zip(spans, getters)
+                                for i, get in enumerate(gs)])
             drain(0)
     finally:
         for fh in files.values():
             fh.close()
-        _pinned_release(ring)
+        stage.release()
     if kept is None:
         return None
     return [tuple(torch.cat([p[i] for p in ps]) for i in range(4)) for ps in kept]
