@@ -456,6 +456,15 @@ int zeggs_status_flag(const unsigned* status, float* dst /* device float */, voi
  * `stream`, touching `scratch[0..n)` lightly (may be NULL) -- the stand-in for a collective's resident workgroups that
  * tools/cotenant_probe.py puts beside the iteration's tail and tests/test_gpu_giveup.py across a sweep boundary */
 int zeggs_test_cotenant(int workgroups, int threads, float ms, float* scratch, long n, void* stream);
+/* test hooks (no reference counterpart): the fused attention kernels of the style encoder (csrc/attention.hip) on the caller's
+ * buffers, nothing added.  qkv [B L, 3E] (q | k | v, head h at columns 32 h), O / dO [B L, E], lse / dsum [B NH, L] (lse: the row
+ * log-sum-exp of the scaled scores in BASE 2), dqkv [B L, 3E], dbias [3E] or NULL: += the column sums of dqkv.  p > 0: the mask
+ * of the contract below, element ((b NH + h) L + q) L + k, with `seed` as given (the encoder passes its seed + 3).  The backward
+ * obeys the "attn_bwd_one_launch" option.  Refused, with nothing launched: B or L < 1, E / NH != 32, p outside [0, 1), a pointer
+ * that is not 16-byte aligned -- whatever the "fused_attention" option says. */
+int zeggs_test_attention_fwd(const float* qkv, float* O, float* lse, int B, int L, int E, int NH, float p, uint64_t seed, void* stream);
+int zeggs_test_attention_bwd(const float* qkv, const float* O, const float* lse, const float* dO, float* dqkv, float* dsum,
+                             float* dbias /* may be null */, int B, int L, int E, int NH, float p, uint64_t seed, void* stream);
 
 /* ---------------------------------------------------------------- batch gather
  * replaces SGDataset.__getitem__/get_example + default collate, ZEGGS/dataset.py:110-204, reading

@@ -1,4 +1,6 @@
 """Shared test helpers: seeded nets (reference construction order) and golden loading."""
+import math
+
 import numpy as np
 import torch
 
@@ -1153,3 +1155,255 @@ def radam_teacher_forced(before, g, after, step, lr, eps, betas=(0.9, 0.999), we
     oradam.radam_step(p, g, m, v, step, lr, eps, betas[0], betas[1], weight_decay, degenerated_to_sgd)
     sp = sp + (p - before[0].double()).abs()
     return {k: radam_roundings_torch(a, r, s) for k, a, r, s in zip("pmv", after, (p, m, v), (sp, sm, v))}
+
+
+# ----------------------------------------------------------------------------- fused attention kernels (tests/test_gpu_attention.py)
+# csrc/attention.hip through zeggs_test_attention_fwd / _bwd against plain float64 softmax attention.  tests/test_attention_oracle_cpu.py
+# measures on the CPU what float32 itself costs at every case below (the floors) and proves that the comparison is sharp
+# (negative controls).
+ATTN_HD = 32
+ATTN_P = 0.1
+LOG2E = 1.4426950408889634
+ATTN_FAMILIES = ("mild", "g3", "g6", "lastkey", "onehot", "offset", "equal")
+ATTN_CLASS = dict(mild="mild", equal="mild", g3="peaked", lastkey="peaked", onehot="peaked", offset="peaked", g6="extreme")
+
+
+def attn_class(family, L):
+    """the class whose bounds a case is held to: the family's, except `lastkey` at L = 2 -- "cancel": the last key holds all but
+    p ~ 2e-4 of every row, so dS = P p (dP_1 - dP_0) and with it ALL of dQ and dK is a 2e-4 share of the terms it is the difference
+    of (float32 leaves 6e-8 / 2e-4 of it uncertain).  Kept apart so that its floor does not widen the peaked bounds tenfold."""
+    return "cancel" if (family, L) == ("lastkey", 2) else ATTN_CLASS[family]
+
+
+ATTN_TENSORS = ("O", "lse2", "dQ", "dK", "dV", "dsum", "dbias")
+ATTN_SMALL = 1e-3        # a gradient section whose float64 maximum is below this share of the dV section's is compared on dV's scale
+# (family, B, NH, L, p)
+ATTN_SHAPE_CASES = ([("mild", 2, 4, L, 0.0) for L in (1, 2, 31, 32, 33, 64, 127, 128, 129, 160, 257)] +
+                    [("mild", 1, 1, 33, 0.0), ("mild", 3, 2, 129, 0.0), ("mild", 1, 8, 65, 0.0)])
+ATTN_REGIME_CASES = ([(f, 2, 4, L, 0.0) for f in ATTN_FAMILIES for L in (33, 129, 257)] +
+                     [(f, 2, 4, L, 0.0) for f in ("lastkey", "onehot", "equal") for L in (1, 2, 160)])
+ATTN_DROPOUT_CASES = [(f, 2, 4, L, ATTN_P) for f in ("mild", "g3", "lastkey") for L in (33, 129, 257)]
+ATTN_WRAP = dict(B=270, NH=1, L=4000, p=ATTN_P, heads=(0, 267, 268, 269), seed=90210)      # element 2^32: head 268, row 1741, key 3296
+# THE BOUNDS.  Per family class and tensor: 4 x the largest error of the FLOAT32 evaluation of attention_oracle against its float64
+# evaluation over the class's cases above (the p = 0.1 cases with the masks of hash_keep_scale; the wrap case's four heads count as
+# mild), in the measure of attention_errors.  The margin of 4 is for what the kernels do differently from torch's float32: the
+# 32-key tile order and matrix-core accumulation, v_exp_f32 / v_log_f32 at 1 ulp, log2 e folded into the query scale.  Floors as
+# test_attention_oracle_cpu.py::test_float32_floors_are_within_a_quarter_of_the_bounds measures them (it asserts floor <= bound / 4):
+ATTN_FLOORS = {
+    "mild": dict(O=1.15e-6, lse2=1.35e-7, grad=2.6e-6, dsum=8.4e-7, dbias=6.7e-7),        # measured 1.12e-6 1.29e-7 2.52e-6 8.15e-7 6.51e-7
+    "peaked": dict(O=6.5e-6, lse2=3.2e-7, grad=8.3e-6, dsum=8.2e-6, dbias=4.2e-6),        # measured 6.31e-6 3.13e-7 8.03e-6 7.95e-6 4.04e-6
+    "extreme": dict(O=8.3e-6, lse2=2.15e-7, grad=7.7e-6, dsum=1.0e-5, dbias=4.8e-6),      # measured 8.05e-6 2.07e-7 7.49e-6 9.68e-6 4.68e-6
+    "cancel": dict(O=7.2e-8, lse2=1.75e-7, grad=6.4e-5, dsum=7.0e-8, dbias=5.7e-5),       # measured 6.99e-8 1.68e-7 6.18e-5 6.72e-8 5.54e-5
+}
+# (worst cases: mild O 2x4x257 with dropout, gradients `equal` at 257; peaked O and dsum `offset` at 129 / 257, gradients `offset` at 33;
+# extreme: g6 at 129 / 257; cancel = `lastkey` at L = 2 alone, attn_class.  lse2 is relative to max(1, max |lse2|): 10 (mild) ... 260
+# (g6) in base 2.)
+# The float32 restatement runs its backward in the kernels' form (attention_oracle(d_from_o=True): D = rowsum(dO . O) from the output).
+# With autograd's form -- D = sum_k P_k dP_k, whose roundings cancel against the minuend's -- the `lastkey` L = 2 floors are 2.1e-5 /
+# 9.3e-6 instead of 6.2e-5 / 5.5e-5 and the MI355X kernels measured 7.2e-5 (dQ) / 8.2e-5 (dbias) there: the one excess the first device
+# run found, explained by that rounding, which was then added to the restatement (and `equal`'s dQ floor rose from 1.1e-6 to 2.5e-6).
+# No floor or bound was taken from the kernels' output.
+ATTN_BOUND = {c: {k: 4.0 * v for k, v in f.items()} for c, f in ATTN_FLOORS.items()}
+ATTN_BUGS = ("O_row", "dQ_row", "dK_row", "dV_row", "key_L", "mask_transposed", "bwd_mask_redrawn", "dsum_undropped",
+             "lse_natural", "dK_without_ln2")       # + the hash's high word ignored: hash_keep_scale(bug="hi_ignored")
+
+
+def attn_bound_key(tensor):
+    return "grad" if tensor in ("dQ", "dK", "dV") else tensor
+
+
+def attn_case_id(case):
+    f, B, NH, L, p = case
+    return f"{f}-{B}x{NH}x{L}" + ("-drop" if p > 0 else "")
+
+
+def attn_case_seed(case):
+    f, B, NH, L, p = case
+    return 7000 + 1000 * ATTN_FAMILIES.index(f) + 37 * B + 5 * NH + L
+
+
+def attn_mask_seed(case):
+    return 0x1234567800000000 + attn_case_seed(case)        # (both words of the seed are in use)
+
+
+def attention_case(family, B, NH, L, seed):
+    """seeded inputs of one comparison -> (qkv [B, L, 3E], dO [B, L, E]) float32, E = 32 NH.  `u` is a unit vector per head.
+    mild: randn (logit std 1); g3 / g6: q and k times 3 / 6 (logit std 9 / 36: peaked rows, largest probability 1.0);
+    lastkey: q += 4 u, key L-1 += 12 u (the row maximum is the last key -- in the partial tile when L % 32 != 0);
+    onehot: q += 6 u, key 0 += 40 u (the first probability of nearly every row is exactly 1.0 in float32, the others underflow);
+    offset: q and k += 20 u (a common logit offset of 70 nats that the max subtraction must cancel);
+    equal: all keys identical (the softmax is exactly uniform)."""
+    assert family in ATTN_FAMILIES, family
+    gen = torch.Generator().manual_seed(seed)
+    q, k, v = (torch.randn(B, L, NH, ATTN_HD, generator=gen) for _ in range(3))
+    dO = torch.randn(B, L, NH * ATTN_HD, generator=gen)
+    u = torch.randn(NH, ATTN_HD, generator=gen)
+    u = u / u.norm(dim=-1, keepdim=True)
+    if family in ("g3", "g6"):
+        g = 3.0 if family == "g3" else 6.0
+        q, k = q * g, k * g
+    elif family == "lastkey":
+        q = q + 4.0 * u
+        k[:, L - 1] += 12.0 * u
+    elif family == "onehot":
+        q = q + 6.0 * u
+        k[:, 0] += 40.0 * u
+    elif family == "offset":
+        q, k = q + 20.0 * u, k + 20.0 * u
+    elif family == "equal":
+        k = k[:, :1].expand(B, L, NH, ATTN_HD)
+    E = NH * ATTN_HD
+    return torch.cat([t.reshape(B, L, E) for t in (q, k, v)], dim=-1).contiguous(), dO
+
+
+def attention_oracle(qkv, dO, NH, keep=None, dtype=torch.float64, bug=None, d_from_o=False):
+    """Plain softmax attention + autograd in `dtype`: scores q k^T / sqrt(32), softmax, times the keep-scale `keep` [B, NH, L, L]
+    (None: no dropout), times v.  -> (O [B, L, E], lse2 [B NH, L] = logsumexp(s) log2 e, dqkv [B, L, 3E] of sum(O dO),
+    dsum [B NH, L] = rowsum(dO . O) per head, dbias [3E] = the column sums of dqkv).
+    d_from_o: the backward in the form the kernels use, dS = P (dPd keep - D) with D = rowsum(dO . O) taken from the output (the
+    same function; in float64 equal to autograd's to rounding, in float32 it carries the rounding of that separate dot product).
+    bug: one of ATTN_BUGS, the negative controls -- a model of one wrong line of the kernels; the *_row and key_L bugs touch the
+    last query row (key) of the last head of the last batch entry only."""
+    assert bug is None or bug in ATTN_BUGS, bug
+    B, L, E3 = qkv.shape
+    E = E3 // 3
+    hd = E // NH
+    x = qkv.detach().to(dtype).clone().requires_grad_(True)
+    g = dO.detach().to(dtype)
+    heads = lambda t: t.reshape(B, L, NH, hd).transpose(1, 2)  # noqa: E731  [B, NH, L, hd]
+    q, k, v = heads(x[..., :E]), heads(x[..., E:2 * E]), heads(x[..., 2 * E:])
+    m = None if keep is None else keep.to(dtype)
+    if bug == "mask_transposed" and m is not None:
+        m = m.transpose(-1, -2)
+    if bug == "key_L":           # the clamped copy of key L-1 takes part as key L (last head of the last batch entry)
+        sel = torch.zeros(B, NH, 1, 1, dtype=dtype)
+        sel[-1, -1] = 1.0
+        k = torch.cat([k, k[:, :, -1:]], dim=2)
+        v = torch.cat([v, v[:, :, -1:]], dim=2)
+        if m is not None:
+            m = torch.cat([m, m[..., -1:]], dim=-1)
+    s = torch.matmul(q, k.transpose(-1, -2)) / math.sqrt(hd)
+    if bug == "key_L":
+        s = torch.cat([s[..., :-1], s[..., -1:] + torch.log(sel)], dim=-1)       # every other head: -inf, the key does not exist
+    P = torch.softmax(s, dim=-1)
+    Pd = P if m is None else P * m
+    if bug == "bwd_mask_redrawn" and m is not None:      # the backward sees another mask of the same rate
+        other = m.roll(1, dims=-1)
+        Pd = P * other + (P * m - P * other).detach()
+    Oh = torch.matmul(Pd, v)                                                       # [B, NH, L, hd]
+    gh = heads(g)
+    if d_from_o or (bug == "dsum_undropped" and m is not None):
+        # the kernels' backward (the flash-attention form): dS = P (dPd keep - D) with D = rowsum(dO . O) formed from the STORED
+        # output, a dot product of its own -- in autograd's softmax backward D is sum_k P_k dP_k, the same dP as in the minuend, so
+        # the roundings of dP cancel in dP - D wherever one key holds nearly all of the row (dS = P p (dP_1 - dP_0) at L = 2).
+        # The bug forms D from the undropped probabilities.
+        Os = torch.matmul(P, v) if bug == "dsum_undropped" else Oh
+        D = (gh * Os).sum(-1, keepdim=True).detach()
+        dPd = torch.matmul(gh, v.detach().transpose(-1, -2))
+        dS = P.detach() * ((dPd if m is None else dPd * m) - D)
+        s_lin = (s * dS).sum()                        # its gradient w.r.t. q and k is dS pushed through the scores
+        v_lin = (torch.matmul(Pd.detach(), v) * gh).sum()
+        (dx,) = torch.autograd.grad(s_lin + v_lin, x)
+        dsum = D.squeeze(-1)
+    else:
+        (dx,) = torch.autograd.grad((Oh * gh).sum(), x)
+        dsum = (gh * Oh.detach()).sum(-1)
+    O = Oh.detach().transpose(1, 2).reshape(B, L, E).clone()
+    lse2 = torch.logsumexp(s.detach(), dim=-1) * (1.0 if bug == "lse_natural" else LOG2E)
+    dx = dx.clone()
+    if bug == "O_row":
+        O[-1, -1, E - hd:] *= 1.0 + 1e-3
+    if bug in ("dQ_row", "dK_row", "dV_row"):
+        sec = ("dQ_row", "dK_row", "dV_row").index(bug)
+        dx[-1, -1, sec * E + E - hd:(sec + 1) * E] *= 1.0 + 1e-3
+    if bug == "dK_without_ln2":
+        dx[..., E:2 * E] *= LOG2E
+    return O, lse2.reshape(B * NH, L), dx, dsum.reshape(B * NH, L), dx.sum(dim=(0, 1))
+
+
+def attention_errors(got, ref):
+    """(O, lse2, dqkv, dsum, dbias) of an implementation against the float64 oracle's -> {tensor: error} over ATTN_TENSORS.
+    O, dsum: relerr (max |d| over the tensor's max).  lse2: max |d| / max(1, max |lse2|).  dQ / dK / dV: relerr of the section of
+    dqkv, on the dV section's scale when the section's own float64 maximum is below ATTN_SMALL of it (dQ and dK of `onehot`, dQ of
+    `equal`, dQ and dK at L = 1: their true value is ~ 0).  dbias: the worst of its three sections, each measured the same way (the
+    dK section is a sum of rows of dS, each of which sums to zero).  An entry of `got` may be None: left out."""
+    ref = [t.detach().double().cpu() for t in ref]
+    E = ref[0].shape[-1]
+    out = {}
+
+    def sections(g, r):
+        vmax = float(r[..., 2 * E:].abs().max())
+        errs = []
+        for i in range(3):
+            gs, rs = g[..., i * E:(i + 1) * E], r[..., i * E:(i + 1) * E]
+            scale = float(rs.abs().max())
+            if scale < ATTN_SMALL * vmax:
+                scale = vmax
+            errs.append(float((gs - rs).abs().max()) / max(scale, 1e-300))
+        return errs
+    g = [None if t is None else t.detach().double().cpu().reshape(r.shape) for t, r in zip(got, ref)]
+    if g[0] is not None:
+        out["O"] = relerr(g[0], ref[0])
+    if g[1] is not None:
+        out["lse2"] = float((g[1] - ref[1]).abs().max()) / max(1.0, float(ref[1].abs().max()))
+    if g[2] is not None:
+        out["dQ"], out["dK"], out["dV"] = sections(g[2], ref[2])
+    if g[3] is not None:
+        out["dsum"] = relerr(g[3], ref[3])
+    if g[4] is not None:
+        out["dbias"] = max(sections(g[4], ref[4]))
+    return out
+
+
+def assert_attention(errs, cls, tag=""):
+    """every error of attention_errors within ATTN_BOUND of the class `cls` (attn_class)"""
+    bound = ATTN_BOUND[cls]
+    bad = {k: (e, bound[attn_bound_key(k)]) for k, e in errs.items() if not e <= bound[attn_bound_key(k)]}
+    assert not bad, (tag, cls, bad)
+
+
+# ---- the mask hash of csrc/common.h restated in NumPy (hash_key, mix32k, the (lo, hi) form of dropout_scale_fast):
+# tests/test_gpu_attention.py pins it bit for bit to zeggs_dropout, and draws from it the masks beyond element 2^32
+def _mix32(x, k2=None):
+    x = x.astype(np.uint32)
+    x ^= x >> np.uint32(17); x *= np.uint32(0xed5ad4bb)      # noqa: E702
+    x ^= x >> np.uint32(11)
+    if k2 is not None:
+        x += np.uint32(k2)
+    x *= np.uint32(0xac4c1b51)
+    x ^= x >> np.uint32(15); x *= np.uint32(0x31848bab)      # noqa: E702
+    x ^= x >> np.uint32(14)
+    return x
+
+
+def hash_key(seed):
+    seed = int(seed) & (2 ** 64 - 1)
+    with np.errstate(over="ignore"):
+        a = _mix32(np.array([((seed & 0xffffffff) * 0x9E3779B1 & 0xffffffff) ^ (seed >> 32)], dtype=np.uint32))
+        b = _mix32(a ^ np.uint32(0x85ebca6b))
+    return int(a[0]), int(b[0])
+
+
+def hash_keep_scale(seed, start, n, p, bug=None):
+    """keep-scale (float64: 0 or 1 / (1 - p), the value _device_keep_scale returns) of the elements start .. start + n - 1 of a
+    mask; bug = "hi_ignored": the high word of the 64-bit element index dropped (a negative control)."""
+    idx = np.arange(int(start), int(start) + int(n), dtype=np.uint64)
+    lo, hi = (idx & np.uint64(0xffffffff)).astype(np.uint32), (idx >> np.uint64(32)).astype(np.uint32)
+    if bug == "hi_ignored":
+        hi = np.zeros_like(hi)
+    else:
+        assert bug is None, bug
+    a, b = hash_key(seed)
+    with np.errstate(over="ignore"):
+        h = _mix32((lo ^ ((hi << np.uint32(16)) | (hi >> np.uint32(16)))) + np.uint32(a), b)
+    pf = np.float32(p)
+    u = (h >> np.uint32(8)).astype(np.float32) * np.float32(1.0 / 16777216.0)
+    return np.where(u < pf, 0.0, 1.0 / (1.0 - p))
+
+
+def attention_keep(seed, B, NH, L, p, heads=None, bug=None):
+    """the attention site's keep-scale [B, NH, L, L] (element ((b NH + h) L + q) L + k) from hash_keep_scale; heads: only these
+    flat head numbers b NH + h -> [len(heads), 1, L, L]"""
+    if heads is None:
+        return torch.as_tensor(hash_keep_scale(seed, 0, B * NH * L * L, p, bug)).reshape(B, NH, L, L)
+    return torch.as_tensor(np.stack([hash_keep_scale(seed, bh * L * L, L * L, p, bug) for bh in heads])).reshape(len(heads), 1, L, L)

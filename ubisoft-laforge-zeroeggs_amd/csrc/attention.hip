@@ -391,3 +391,31 @@ int k_attn_bwd(const float* qkv, const float* O, const float* lse, const float* 
   ZLAUNCH_CHECK("attn_bwd_kv");
   return 0;
 }
+
+// ------------------------------------------------------------------ test seam (tests/test_gpu_attention.py)
+// The two launches above on caller-owned buffers, nothing added: what the encoder's call sites check by construction (shape,
+// workspace alignment) is checked here, on the shape alone -- the "fused_attention" option is the encoder's routing, not the kernels'.
+namespace {
+int attn_test_shape(const char* who, int B, int L, int E, int NH, float p) {
+  ZCHECK(B >= 1 && L >= 1, "%s: B %d and L %d must be >= 1", who, B, L);
+  ZCHECK(NH >= 1 && E >= 1 && E % NH == 0 && E / NH == HD, "%s: head width E / NH must be %d (E %d, NH %d)", who, HD, E, NH);
+  ZCHECK(p >= 0.f && p < 1.f, "%s: 0 <= p < 1 (p %g)", who, p);
+  return 0;
+}
+}  // namespace
+
+extern "C" int zeggs_test_attention_fwd(const float* qkv, float* O, float* lse, int B, int L, int E, int NH, float p, uint64_t seed,
+                                        void* stream) {
+  ZTRY(attn_test_shape("test_attention_fwd", B, L, E, NH, p));
+  ZCHECK(qkv && O && lse && ((uintptr_t)qkv | (uintptr_t)O | (uintptr_t)lse) % 16 == 0,
+         "test_attention_fwd: qkv, O and lse must be 16-byte aligned (the kernels read float4)");
+  return k_attn_fwd(qkv, O, lse, B, L, E, NH, p, seed, (hipStream_t)stream);
+}
+extern "C" int zeggs_test_attention_bwd(const float* qkv, const float* O, const float* lse, const float* dO, float* dqkv, float* dsum,
+                                        float* dbias, int B, int L, int E, int NH, float p, uint64_t seed, void* stream) {
+  ZTRY(attn_test_shape("test_attention_bwd", B, L, E, NH, p));
+  ZCHECK(qkv && O && lse && dO && dqkv && dsum &&
+             ((uintptr_t)qkv | (uintptr_t)O | (uintptr_t)lse | (uintptr_t)dO | (uintptr_t)dqkv | (uintptr_t)dsum | (uintptr_t)dbias) % 16 == 0,
+         "test_attention_bwd: qkv, O, lse, dO, dqkv, dsum and dbias must be 16-byte aligned (the kernels read float4)");
+  return k_attn_bwd(qkv, O, lse, dO, dqkv, dsum, dbias, B, L, E, NH, p, seed, (hipStream_t)stream);
+}
