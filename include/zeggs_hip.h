@@ -124,6 +124,35 @@ int zeggs_speech_encoder_bwd_ex(const ZeggsSpeechDims*, const ZeggsSpeechParams*
                                 const float* out, const float* dout, const ZeggsSpeechGrads*, void* ws,
                                 size_t ws_bytes, void* stream, int grads_zeroed);
 
+/* Incremental form for live serving (csrc/live.hip; zeggs_version() >= 106; eval mode, no dropout): R independent rows advance in
+ * ONE launch.  Layer 0 is pointwise, so a frame's layer-0 activation is computed once, when its feature row arrives, and kept in
+ * the row's ring: ring [R, D, H], frame f in slot f % D, D >= KW + (frames a call produces) - 1.
+ *   feats [R, feat_ld, F]   UN-normalised audio features; row r's n_new new frames (n_ring .. n_ring + n_new - 1) start at row
+ *                           feat_off of its block; (x - mean) / std with mean / std [F] is applied inside
+ *   rows[r] (HOST memory, read during the call): n_ring = frames of the row that are in its ring so far (absolute count),
+ *                           [k0, k0 + n_out) the frames to produce, last = index of the signal's last frame once it has ended
+ *                           (then n_ring + n_new == last + 1), else < 0
+ *   out [R, out_ld, O]      row r, index i = speech encoding of frame k0 + i; the rest of a row's block is zero-filled
+ * Edges as the offline encoder's replicate padding: taps before frame 0 read frame 0, taps past `last` read `last`; while the
+ * signal continues frame k needs frame k + (KW-1)/2 in the ring.  The call REFUSES (-1, nothing launched) a row whose taps
+ * would read a frame that is not in the ring yet or not any more.  A row with n_new = n_out = 0 is skipped: its ring is not
+ * touched.  `ws` holds the weights in the kernel's layout: zeggs_speech_encoder_live_prepare, once per weight set, on
+ * zeggs_speech_encoder_live_workspace_bytes(d) bytes (the weight-only work, as zeggs_decoder_batch_prepare). */
+#define ZEGGS_LIVE_MAX_ROWS 64
+typedef struct {
+  int R, F, H, O, KW, D;
+  int feat_ld, out_ld; /* rows per row block of feats / out */
+} ZeggsLiveDims;
+typedef struct {
+  long n_ring, k0, last;
+  int n_new, n_out, feat_off, reserved;
+} ZeggsLiveRow;
+size_t zeggs_speech_encoder_live_workspace_bytes(const ZeggsLiveDims*);
+int zeggs_speech_encoder_live_prepare(const ZeggsLiveDims*, const ZeggsSpeechParams*, void* ws, size_t ws_bytes, void* stream);
+int zeggs_speech_encoder_live(const ZeggsLiveDims*, const ZeggsSpeechParams*, const float* mean, const float* std,
+                              const ZeggsLiveRow* rows, const float* feats, float* ring, float* out, const void* ws,
+                              size_t ws_bytes, void* stream);
+
 /* ---------------------------------------------------------------- StyleEncoderAttn trunk
  * replaces StyleEncoderAttn.forward, ZEGGS/modules.py:391-420 (convs :359-384, FFTBlock :484-612).
  * x [B,L,C] normalised exemplar features, pos [>=L,E] sinusoidal table -> out [B,E] (E = 2*S with VAE). */
@@ -502,6 +531,16 @@ long zeggs_mel_frames_ready(const ZeggsMelDims*, long n_samples);
 size_t zeggs_mel_range_workspace_bytes(const ZeggsMelDims*, long k0, long k1);
 int zeggs_mel_features_range(const ZeggsMelDims*, const float* wav, long n_samples, int final, const double* filterbank,
                              long k0, long k1, float* out, void* ws, size_t ws_bytes, void* stream);
+/* sliding-window form (zeggs_version() >= 106): the same rows [k0, k1) when only the recent part of the signal is kept.
+ * wav_window[i] is sample base + i, n_samples the ABSOLUTE number of samples received so far (the window holds
+ * base .. n_samples - 1).  zeggs_mel_window_first_sample(d, k0), host only: the smallest absolute sample index that any
+ * frame >= k0 loads while the signal continues (left-end reflection, centred / uncentred frames and the x[n-1] of the
+ * pre-emphasis included) -- everything below it can be dropped once frames < k0 are done.  The call refuses a `base` above
+ * what its frames load (final != 0: the right-end reflection counts too).  Same kernels and arithmetic as
+ * zeggs_mel_features_range, to which base = 0 is identical; workspace: zeggs_mel_range_workspace_bytes(d, k0, k1). */
+long zeggs_mel_window_first_sample(const ZeggsMelDims*, long k0);
+int zeggs_mel_features_window(const ZeggsMelDims*, const float* wav_window, long base, long n_samples, int final,
+                              const double* filterbank, long k0, long k1, float* out, void* ws, size_t ws_bytes, void* stream);
 
 /* Loudness normalisation pre-pass of preprocess_audio, ZEGGS/data_pipeline.py:34-39 (pyloudnorm 0.1.0: Meter(rate)
  * .integrated_loudness + normalize.loudness to `target` LUFS; algorithm restated in oracle/loudness.py), mono, on the device:

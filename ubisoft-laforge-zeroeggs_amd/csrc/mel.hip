@@ -93,15 +93,17 @@ __device__ __forceinline__ double mel_exp_sq(double y, int exact) {      // exp(
 
 // sample `src` of the signal the STFT sees: the wav, zero beyond its end, high-pass filtered first when audio_conf.pre_emphasis is on
 // (spectrograms.py:35 -> signal_manipulation.preemphasis = lfilter([1, -c], [1], x): y[n] = x[n] - c x[n-1], y[0] = x[0], in float64)
-__device__ __forceinline__ double mel_sample(const float* wav, long src, long n, long n_avail, double pe) {
-  if (!(src >= 0 && src < n && src < n_avail)) return 0.0;
-  double x = (double)wav[src];
-  if (pe != 0.0 && src > 0) x -= pe * (double)wav[src - 1];
+// `wav[i]` is sample base + i of the signal (base = 0: the whole signal; > 0: a sliding window, zeggs_mel_features_window, whose
+// host side has checked that no frame of the call reads below `base`)
+__device__ __forceinline__ double mel_sample(const float* wav, long src, long n, long n_avail, double pe, long base) {
+  if (!(src >= base && src < n && src < n_avail)) return 0.0;
+  double x = (double)wav[src - base];
+  if (pe != 0.0 && src > base) x -= pe * (double)wav[src - 1 - base];
   return x;
 }
 
 __global__ __launch_bounds__(256) void mel_stft_k(ZeggsMelDims d, const float* wav, long n, long n_avail, const double* fb,
-                                                   double* logmel, double* energy, long m0, int exact) {
+                                                   double* logmel, double* energy, long m0, int exact, long base) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int NF = d.n_fft, NBIN = NF / 2 + 1;
   double* xw = sm;              // [NF] windowed samples
@@ -114,7 +116,7 @@ __global__ __launch_bounds__(256) void mel_stft_k(ZeggsMelDims d, const float* w
   for (int j = threadIdx.x; j < NF; j += blockDim.x) {
     const long p = fr * d.hop + j - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);          // index into the (zero-extended) signal before reflect padding
     long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-    const double x = mel_sample(wav, src, n, n_avail, d.pre_emph);
+    const double x = mel_sample(wav, src, n, n_avail, d.pre_emph, base);
     const double win = 0.5 - 0.5 * cos(2.0 * M_PI * (double)j / (double)(NF - 1));   // scipy hann(sym=True)
     xw[j] = x * win;
     const double ang = 2.0 * M_PI * (double)j / (double)NF;
@@ -188,7 +190,8 @@ __host__ __device__ inline size_t mel_fast_lds(int NF, int hop, int n_mels) {
 // (fp64, k in steps of 4) instead of one fma chain per bin.
 __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, const float* wav, long n, long n_avail,
                                                                 const double* fb, const double* table, const double* wintab,
-                                                                double* logmel, double* energy, long m0, long nfr, int exact) {
+                                                                double* logmel, double* energy, long m0, long nfr, int exact,
+                                                                long base) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int NF = d.n_fft, NBIN = NF / 2 + 1, hop = d.hop, NM = d.n_mels;
   const int ns = (MF - 1) * hop + NF;
@@ -209,7 +212,7 @@ __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, c
   for (int i = tid; i < ns; i += blockDim.x) {
     const long p = fr0 * hop + i - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);
     const long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-    xs[i] = (src >= 0 && src < n && src < n_avail) ? wav[src] : 0.f;
+    xs[i] = (src >= base && src < n && src < n_avail) ? wav[src - base] : 0.f;
   }
   for (int j = tid; j < NF; j += blockDim.x) win[j] = wintab[j];
   if (tid < NM) {                                   // band of mel filter tid
@@ -364,7 +367,8 @@ __host__ __device__ inline size_t mel_fft_lds(int NF, int n_mels) {
 
 __global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan plan, const float* wav, long n, long n_avail,
                                                       const double* fb, const c2* __restrict__ TW, const int* bands,
-                                                      const double* fbp, double* logmel, double* energy, long m0, long nfr, int exact) {
+                                                      const double* fbp, double* logmel, double* energy, long m0, long nfr, int exact,
+                                                      long base) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int NF = d.n_fft, M = NF / 2, NBIN = M + 1, hop = d.hop, NM = d.n_mels;
   c2* bufA = (c2*)smem;                               // [FFB][M]
@@ -386,7 +390,7 @@ __global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan p
       const int j = 2 * m + h;
       const long p = (fr0 + f) * hop + j - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);
       const long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-      const double x = mel_sample(wav, src, n, n_avail, d.pre_emph);
+      const double x = mel_sample(wav, src, n, n_avail, d.pre_emph, base);
       v[h] = x * WIN[j].x;
     }
     bufA[i] = c2{v[0], v[1]};
@@ -600,8 +604,9 @@ static FftPlan fft_plan(int M) {
 }
 
 // STFT frames m0 .. m0 + nfr - 1 -> logmel / energy slots 0 .. nfr - 1
+// (`base`: index of wav[0] in the signal, see mel_sample)
 static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, long n, long n_avail, const double* fb, long m0,
-                       long nfr, hipStream_t s) {
+                       long nfr, hipStream_t s, long base = 0) {
   const int NBIN = d.n_fft / 2 + 1;
   const FftPlan plan = fft_plan(d.n_fft / 2);
   const size_t fft_lds = mel_fft_lds(d.n_fft, d.n_mels);
@@ -618,7 +623,7 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
     hipLaunchKernelGGL(mel_fft_table_k, dim3(16), dim3(256), 0, s, (c2*)w.ftw, d.n_fft / 2, fb, d.n_mels, w.bands, w.fbp);
     ZLAUNCH_CHECK("mel_fft_table");
     hipLaunchKernelGGL(mel_stft_fft_k, dim3((unsigned)((nfr + FFB - 1) / FFB)), dim3(FTHR), fft_lds, s, d, plan, wav, n, n_avail, fb,
-                       (const c2*)w.ftw, w.bands, w.fbp, w.logmel, w.energy, m0, nfr, g_mel_exact_log);
+                       (const c2*)w.ftw, w.bands, w.fbp, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_fft");
     return 0;
   }
@@ -632,12 +637,12 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
     hipLaunchKernelGGL(mel_table_k, dim3(1024), dim3(256), 0, s, w.table, w.win, d.n_fft, NBIN);
     ZLAUNCH_CHECK("mel_table");
     hipLaunchKernelGGL(mel_stft_mfma_k, dim3((unsigned)((nfr + MF - 1) / MF)), dim3(MWAVES * 64), fast_lds, s, d, wav, n, n_avail,
-                       fb, w.table, w.win, w.logmel, w.energy, m0, nfr, g_mel_exact_log);
+                       fb, w.table, w.win, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_mfma");
     return 0;
   }
   const size_t lds = sizeof(double) * (3 * (size_t)d.n_fft + d.n_fft / 2 + 1 + d.n_mels);
-  hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.logmel, w.energy, m0, g_mel_exact_log);
+  hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.logmel, w.energy, m0, g_mel_exact_log, base);
   ZLAUNCH_CHECK("mel_stft");
   return 0;
 }
@@ -702,15 +707,8 @@ extern "C" size_t zeggs_mel_range_workspace_bytes(const ZeggsMelDims* d, long k0
   carve_mel(*d, mspan, a);
   return a.off + 256;
 }
-extern "C" int zeggs_mel_features_range(const ZeggsMelDims* dp, const float* wav, long n_samples, int final,
-                                        const double* filterbank, long k0, long k1, float* out, void* ws, size_t ws_bytes,
-                                        void* stream) {
-  const ZeggsMelDims& d = *dp;
-  hipStream_t s = (hipStream_t)stream;
-  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "mel: bad dims");
-  ZCHECK(n_samples > 0 && k0 >= 0 && k1 > k0, "mel range: empty input");
-  ZCHECK(!(d.flags & MEL_CUBIC), "mel range: resample_method \"cubic\" is a spline over the WHOLE signal -- use zeggs_mel_features");
-  if (!final) ZCHECK(k1 <= zeggs_mel_frames_ready(dp, n_samples), "mel range: frames %ld..%ld need samples not received yet", k0, k1);
+// STFT frames [m0, m1) that the animation frames [k0, k1) interpolate, M = STFT frames of the (finished) signal
+static void mel_range_stft(const ZeggsMelDims& d, long n_samples, int final, long k0, long k1, long* M_, long* m0_, long* m1_) {
   const long M = final ? stft_frames(n_samples, d.n_fft, d.hop, d.flags) : (1L << 40);
   const double r = ((double)d.fs / (double)d.hop) / (double)d.fps;
   long m0 = (long)ceil(r * (double)k0) - 1, m1 = (long)ceil(r * (double)(k1 - 1)) + 1;   // [m0, m1)
@@ -718,13 +716,90 @@ extern "C" int zeggs_mel_features_range(const ZeggsMelDims* dp, const float* wav
   if (m1 < 2) m1 = 2;
   if (m1 > M) m1 = M;
   if (m0 > m1 - 2) m0 = m1 - 2 > 0 ? m1 - 2 : 0;
+  *M_ = M; *m0_ = m0; *m1_ = m1;
+}
+// smallest sample index that the STFT frames [m0, m1) load (the index rule of the three kernels' load sites, on the host): n = signal
+// length of the reflect rule, n_avail = samples present; the sample before it when pre-emphasis is on.  LONG_MAX: they load nothing.
+static long mel_first_load(const ZeggsMelDims& d, long m0, long m1, long n, long n_avail) {
+  const long NF = d.n_fft, neff = n > NF ? n : NF, lim = n < n_avail ? n : n_avail;
+  long best = __LONG_MAX__;
+  for (long m = m0; m < m1; ++m) {
+    const long a = m * d.hop - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2), b = a + NF - 1;      // p = a .. b
+    long lo = __LONG_MAX__;
+    const long ma = a > 0 ? a : 0, mb = b < neff - 1 ? b : neff - 1;            // 0 <= p < neff: src = p
+    if (ma <= mb && ma < lim) lo = ma;
+    if (a < 0) {                                                                // p < 0: src = -p
+      const long c = -(b < -1 ? b : -1);
+      if (c < lim && c < lo) lo = c;
+    }
+    if (b >= neff) {                                                            // p >= neff: src = 2 (neff - 1) - p
+      const long hi = 2 * (neff - 1) - (a > neff ? a : neff);
+      long c = 2 * (neff - 1) - b;
+      if (c < 0) c = 0;
+      if (c <= hi && c < lim && c < lo) lo = c;
+    }
+    if (lo != __LONG_MAX__ && d.pre_emph != 0.0 && lo > 0) --lo;
+    if (lo < best) best = lo;
+    if (b < neff && a >= 0) break;      // no reflection in this frame: every later frame without one starts further right ...
+  }
+  if (m1 > m0) {                        // ... and the frames that reflect at the right end are the last ones
+    for (long m = m1 - 1; m >= m0; --m) {
+      const long a = m * d.hop - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2), b = a + NF - 1;
+      if (b < neff) break;
+      const long hi = 2 * (neff - 1) - (a > neff ? a : neff);
+      long c = 2 * (neff - 1) - b;
+      if (c < 0) c = 0;
+      if (c <= hi && c < lim) {
+        if (d.pre_emph != 0.0 && c > 0) --c;
+        if (c < best) best = c;
+      }
+    }
+  }
+  return best;
+}
+extern "C" long zeggs_mel_window_first_sample(const ZeggsMelDims* d, long k0) {
+  long M, m0, m1;
+  mel_range_stft(*d, 0, 0, k0, k0 + 1, &M, &m0, &m1);
+  const long f = mel_first_load(*d, m0, m1, 1L << 50, 1L << 50);      // (the signal continues: no right end)
+  return f == __LONG_MAX__ ? 0 : f;
+}
+static int mel_range_impl(const ZeggsMelDims* dp, const float* wav, long base, long n_samples, int final, const double* filterbank,
+                          long k0, long k1, float* out, void* ws, size_t ws_bytes, void* stream) {
+  const ZeggsMelDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "mel: bad dims");
+  ZCHECK(n_samples > 0 && k0 >= 0 && k1 > k0, "mel range: empty input");
+  ZCHECK(!(d.flags & MEL_CUBIC), "mel range: resample_method \"cubic\" is a spline over the WHOLE signal -- use zeggs_mel_features");
+  if (!final) ZCHECK(k1 <= zeggs_mel_frames_ready(dp, n_samples), "mel range: frames %ld..%ld need samples not received yet", k0, k1);
+  long M, m0, m1;
+  mel_range_stft(d, n_samples, final, k0, k1, &M, &m0, &m1);
+  const long n = final ? n_samples : (1L << 50);
+  if (base > 0) {
+    const long first = mel_first_load(d, m0, m1, n, n_samples);
+    ZCHECK(base <= first, "mel window: frames %ld..%ld read sample %ld, the window starts at %ld", k0, k1, first, base);
+  }
   Arena a(ws, ws_bytes);
   MelWs w = carve_mel(d, m1 - m0, a);
   ZCHECK(a.ok(), "mel range: workspace too small (%zu < %zu)", ws_bytes, a.off);
-  ZTRY(launch_stft(d, w, wav, final ? n_samples : (1L << 50), n_samples, filterbank, m0, m1 - m0, s));
-  const long n = (k1 - k0) * (d.n_mels + 1), g = (n + 255) / 256;
+  ZTRY(launch_stft(d, w, wav, n, n_samples, filterbank, m0, m1 - m0, s, base));
+  const long nn = (k1 - k0) * (d.n_mels + 1), g = (nn + 255) / 256;
   hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.logmel, w.energy, nullptr, M, m0, k0,
                      (int)(k1 - k0), out);
   ZLAUNCH_CHECK("mel_resample");
   return 0;
+}
+extern "C" int zeggs_mel_features_range(const ZeggsMelDims* dp, const float* wav, long n_samples, int final,
+                                        const double* filterbank, long k0, long k1, float* out, void* ws, size_t ws_bytes,
+                                        void* stream) {
+  return mel_range_impl(dp, wav, 0, n_samples, final, filterbank, k0, k1, out, ws, ws_bytes, stream);
+}
+// The same rows from a sliding window of the signal: wav_window[i] is sample base + i, n_samples the ABSOLUTE count received so
+// far (the window holds samples base .. n_samples - 1).  Refused when a frame of the range would load a sample below `base`
+// (zeggs_mel_window_first_sample(d, k0) while the signal continues; with final != 0 the right-end reflection is looked at too).
+// Workspace: zeggs_mel_range_workspace_bytes(d, k0, k1).
+extern "C" int zeggs_mel_features_window(const ZeggsMelDims* dp, const float* wav_window, long base, long n_samples, int final,
+                                         const double* filterbank, long k0, long k1, float* out, void* ws, size_t ws_bytes,
+                                         void* stream) {
+  ZCHECK(base >= 0 && base < n_samples, "mel window: the window [%ld, %ld) is empty", base, n_samples);
+  return mel_range_impl(dp, wav_window, base, n_samples, final, filterbank, k0, k1, out, ws, ws_bytes, stream);
 }

@@ -1,0 +1,365 @@
+"""Live serving: many audio streams per GPU, constant cost per tick, bounded state.
+
+The serving form of zeggs.stream.GestureStream (same computation: mel + energy -> speech encoder -> autoregressive decoder, any
+chunking of the audio gives the frames of the offline path), for `rows` independent streams on one device:
+
+  * push(sid, chunk) uploads ONLY the new samples into the row's device window (fixed capacity; the samples no later frame loads,
+    zeggs_mel_window_first_sample, are dropped) and computes the mel rows that became ready (zeggs_mel_features_window);
+  * step() advances every row that has `tick` decodable frames by exactly `tick` frames: ONE zeggs_speech_encoder_live launch
+    (layer-0 activations live in a per-row ring, so nothing is re-encoded) and ONE decoder call for all rows --
+    zeggs_decoder_fwd_batch at B = rows, T = tick + 1 (index 0 = the last frame already produced), the weight-stationary sweep where
+    it takes the dimensions; a single-row server uses zeggs_decoder_fwd_state_ex as GestureStream does.  Rows that are idle or
+    short of `tick` frames ride along on finite filler and their state is not committed;
+  * set_style(sid, style, fade) changes the style while speech goes on (the decoder takes a style row per frame);
+  * close(sid) flushes the row's remaining frames with the true right-edge rules (B = 1 entry point) and frees the row.
+
+Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
+look-ahead + one STFT window.  Not here: batching the mel launches across rows, a network front door.
+"""
+import numpy as np
+import torch
+
+from . import audio, ops
+
+LOOKAHEAD = 15        # (31 - 1) / 2 frames of the speech encoder's second convolution
+
+
+def ring_depth(kw, tick):
+    """frames per layer-0 ring: a step reads frames k0 - 1 - (kw-1)/2 .. k0 + tick - 1 + (kw-1)/2"""
+    return int(kw) + int(tick)
+
+
+def style_weight(f, k, fade):
+    """weight of the NEW style at frame f after set_style(..., fade) returned k: 0 before k, then `fade` intermediate frames on a
+    straight line, 1 from frame k + fade on (fade = 0: a step at k)"""
+    return float(min(max((f - k + 1) / (fade + 1.0), 0.0), 1.0))
+
+
+def plan_step(rows, tick, depth, lookahead=LOOKAHEAD):
+    """The pure part of step(): which rows advance and what the encoder launch is told about them.  rows[r]: None (free row) or a
+    dict with "n_feat" (feature rows computed: frames [0, n_feat)), "n_ring" (frames whose layer-0 activation is in the ring) and
+    "kd" (first frame not yet decoded, >= 1).  A row is eligible when frames kd .. kd + tick - 1 all have their look-ahead:
+    kd + tick + lookahead <= n_feat.  -> per row None or dict(k0, k1: frames decoded [k0, k1); enc_k0, n_out: the encoder's output
+    range starts one frame earlier (index 0 of the decoder chunk); n_new: feature rows that enter the ring, frames n_ring ..;
+    slots: their ring slots)."""
+    plan = []
+    for row in rows:
+        if row is None or row["kd"] + tick + lookahead > row["n_feat"]:
+            plan.append(None)
+            continue
+        kd, n_ring = row["kd"], row["n_ring"]
+        n_new = kd + tick + lookahead - n_ring
+        assert 0 <= n_new <= depth
+        plan.append(dict(k0=kd, k1=kd + tick, enc_k0=kd - 1, n_out=tick + 1, n_new=n_new,
+                         slots=[(n_ring + i) % depth for i in range(n_new)]))
+    return plan
+
+
+class _Row:
+    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade")
+
+    def __init__(self, sid):
+        self.sid, self.n, self.base = sid, 0, 0          # samples received (absolute) / absolute index of window[0]
+        self.n_feat, self.fbase, self.n_ring = 0, 0, 0   # feature rows computed / frame of feats[r, 0] / frames in the ring
+        self.kd, self.sent0 = 1, False                   # first frame not yet decoded / frame 0 (the first pose) handed out
+        self.k_style, self.fade = 0, 0                   # last set_style: from frame k_style on, over `fade` frames
+
+
+class LiveServer:
+    """speech_net / decoder: zeggs.modules instances on the device (eval mode); `stats`: dict with audio_input_mean/std,
+    anim_input_mean/std, anim_output_mean/std; `audio_conf`: data_pipeline_conf["audio_conf"]; `rows` streams at most at a time
+    (<= 64), `tick` >= 3 frames per step (the batch sweep needs chunks of >= 4 frames)."""
+
+    def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
+                 device="cuda", window_capacity=16384):
+        g = audio_conf
+        if g.get("normalize_loudness"):
+            raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
+        if tuple(feature_type) != ("mel_spec", "energy"):
+            raise NotImplementedError("live serving supports the shipped feature set [mel_spec, energy]")
+        if g.get("resample_method", "linear") == "cubic":
+            raise ValueError("resample_method 'cubic' is a spline over the whole signal: not available while the signal is still arriving")
+        if not 1 <= rows <= ops.LIVE_MAX_ROWS or tick < 3:
+            raise ValueError(f"LiveServer: rows 1..{ops.LIVE_MAX_ROWS}, tick >= 3")
+        self.dev = torch.device(device)
+        self.rows, self.tick, self.T = int(rows), int(tick), int(tick) + 1
+        self.speech_net, self.decoder = speech_net.eval(), decoder.eval()
+        self.st = {k: v.to(self.dev, torch.float32).contiguous() for k, v in stats.items()}
+        self.dt, self.fps, self.fs = float(dt), float(fps), int(g["sampling_rate"])
+        self.fb, min_clip = audio.mel_tables(g["filter_length"], self.fs, g["n_mel_channels"], g["mel_fmin"], g["mel_fmax"],
+                                             g["min_clipping"], g["normalize_mel_bins"], g.get("real_amplitude", True), self.dev)
+        self.mel = audio.MelDims(g["filter_length"], g["hop_length"], g["n_mel_channels"], self.fs, self.fps, float(min_clip),
+                                 float(g.get("pre_emph_coeff", 0.97)) if g.get("pre_emphasis") else 0.0,
+                                 audio.mel_flags(g.get("centered", True), g.get("normalize_range", True), g.get("resample_method", "linear")))
+        R, F = self.rows, self.mel.n_mels + 1
+        KW = speech_net.layer1.weight.shape[2]
+        if (KW - 1) // 2 != LOOKAHEAD:
+            raise NotImplementedError("live serving assumes the reference's 31-tap speech encoder")
+        self.D = ring_depth(KW, self.tick)
+        self.tail = self.tick + LOOKAHEAD            # frames close() can flush in its last call (what the ring still holds)
+        self.FC = max(4 * (self.tick + LOOKAHEAD + 1), 64)          # feature rows kept per row until their activation is in the ring
+        SP = speech_net.layer2.weight.shape[0]
+        ST = decoder.cell_state_encoder.layer0.weight.shape[1] - int(self.st["anim_input_mean"].numel())
+        self.H = decoder.recurrent_decoder.layer1.hidden_size
+        PO = int(self.st["anim_output_mean"].numel())
+        with torch.no_grad():
+            self.enc = ops.LiveSpeech(speech_net, self.st["audio_input_mean"], self.st["audio_input_std"], R, self.D, self.FC,
+                                      self.tail + 1)
+            self.bd = ops.BatchDecode(decoder, R, self.T, SP, ST, self.st["anim_input_mean"], self.st["anim_input_std"],
+                                      self.st["anim_output_mean"], self.st["anim_output_std"], self.dt)
+        z = lambda *s: torch.zeros(*s, device=self.dev, dtype=torch.float32)  # noqa: E731
+        self.window = [z(int(window_capacity)) for _ in range(R)]   # per row: samples base .. n - 1 of its signal
+        self.feats = z(R, self.FC, F)                # per row: feature rows of frames fbase .. n_feat - 1 (not yet in the ring)
+        self.ring = z(R, self.D, self.enc.d.H)       # per row: layer-0 activations, frame f in slot f % D
+        self.h = z(2, R, self.H)                     # GRU state after each row's last decoded frame
+        self.pose, self.rpos, self.rrot = z(R, PO), z(R, 3), z(R, 4)       # each row's last decoded frame
+        self.rrot[:, 0] = 1.0
+        self.gaze = z(R, self.T, 3)
+        self.sty_old, self.sty_new = z(R, ST), z(R, ST)             # style(f) = lerp(old, new, style_weight(f, k_style, fade))
+        self.mel_ws = ops.mel_range_workspace(self.mel, self.FC + 2, self.dev)
+        self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
+        self.redone_steps = 0
+        self._rows = [None] * R
+        self._sids, self._next_sid = {}, 0
+        self._ops = 0
+        self.stats = dict(uploaded_samples=0, window_capacity=[int(window_capacity)] * R, ring_bytes=self.ring.numel() * 4,
+                          launches_per_step=0, steps=0)
+
+    # ------------------------------------------------------------------ rows
+    def _row(self, sid):
+        if sid not in self._sids:
+            raise KeyError(f"LiveServer: no open stream {sid}")
+        r = self._sids[sid]
+        return r, self._rows[r]
+
+    def open(self, first_pose, style):
+        """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
+        -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init)."""
+        free = [r for r in range(self.rows) if self._rows[r] is None]
+        if not free:
+            raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        r, sid = free[0], self._next_sid
+        self._next_sid += 1
+        f32 = lambda a: a[0:1].to(self.dev, torch.float32).contiguous()  # noqa: E731
+        root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = first_pose[:9]
+        pose0 = torch.cat([f32(x).reshape(1, -1) for x in (root_vel, root_vrt, lpos, ltxy, lvel, lvrt)], dim=1)
+        gaze0, style0 = f32(first_pose[14]), style.to(self.dev, torch.float32).reshape(1, -1).contiguous()
+        with torch.no_grad():
+            self.h[:, r:r + 1] = ops.decoder_state_init(self.bd, pose0, f32(root_pos), f32(root_rot), gaze0, style0)
+        self.pose[r], self.rpos[r], self.rrot[r] = pose0[0], f32(root_pos)[0], f32(root_rot)[0]
+        self.gaze[r] = gaze0
+        self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
+        self._rows[r], self._sids[sid] = _Row(sid), r
+        return sid
+
+    # ------------------------------------------------------------------ audio
+    def _features(self, r, row, k1, final):
+        """feature rows [n_feat, k1) of row r from its window -> feats[r]"""
+        k0 = row.n_feat
+        if k1 <= k0:
+            return
+        pend = k0 - row.n_ring                           # rows still waiting for the ring: frames n_ring .. k0 - 1
+        if k0 - row.fbase + (k1 - k0) > self.FC:         # compact (and grow if this one push needs more than the block holds)
+            keep = self.feats[r, row.n_ring - row.fbase:k0 - row.fbase].clone()
+            if pend + (k1 - k0) > self.FC:
+                self.FC = pend + (k1 - k0)
+                grown = torch.zeros(self.rows, self.FC, self.feats.shape[2], device=self.dev)
+                grown[:, :self.feats.shape[1]] = self.feats
+                self.feats = grown
+                self.mel_ws = ops.mel_range_workspace(self.mel, self.FC + 2, self.dev)
+            self.feats[r, :pend] = keep
+            row.fbase = row.n_ring
+        out = self.feats[r, k0 - row.fbase:k1 - row.fbase]
+        ops.mel_features_window(self.mel, self.window[r], row.base, row.n, final, self.fb, k0, k1, out, self.mel_ws)
+        row.n_feat = k1
+
+    def push(self, sid, wav_chunk):
+        """append samples (float32 in [-1, 1)) to stream `sid`: only they are uploaded; the mel rows that became computable are
+        computed.  Frames leave through step()."""
+        r, row = self._row(sid)
+        chunk = torch.as_tensor(np.ascontiguousarray(wav_chunk, dtype=np.float32))
+        m = int(chunk.numel())
+        if m == 0:
+            return
+        w = self.window[r]
+        if row.n - row.base + m > w.numel():
+            # drop what no frame >= n_feat loads any more; grow only if this single push does not fit beside what must stay
+            nb = max(row.base, min(ops.mel_window_first_sample(self.mel, row.n_feat), row.n))
+            keep = w[nb - row.base:row.n - row.base].clone()
+            if keep.numel() + m > w.numel():
+                w = torch.zeros(keep.numel() + m, device=self.dev)
+                self.window[r] = w
+                self.stats["window_capacity"][r] = int(w.numel())
+            w[:keep.numel()] = keep
+            row.base = nb
+        w[row.n - row.base:row.n - row.base + m].copy_(chunk)
+        row.n += m
+        self.stats["uploaded_samples"] += m
+        ready = min(ops.mel_frames_ready(self.mel, row.n), audio.n_anim_frames(row.n, self.fs, self.fps) - 1)
+        self._features(r, row, ready, final=False)       # (never ahead of the final frame count: it can only grow)
+
+    # ------------------------------------------------------------------ style
+    def set_style(self, sid, style, fade=0):
+        """a new style for stream `sid` from frame k on, k = the first frame not yet decoded (returned); `fade` > 0: a linear
+        cross-fade, frame f carries lerp(old, new, style_weight(f, k, fade))"""
+        r, row = self._row(sid)
+        if fade < 0:
+            raise ValueError("set_style: fade >= 0")
+        w = style_weight(row.kd - 1, row.k_style, row.fade)      # where an unfinished fade stands: the new fade starts there
+        self.sty_old[r] = torch.lerp(self.sty_old[r], self.sty_new[r], w)
+        self.sty_new[r] = style.to(self.dev, torch.float32).reshape(-1)
+        row.k_style, row.fade = row.kd, int(fade)
+        return row.kd
+
+    def _style(self, frames):
+        """style rows [R, n, ST] of the frames frames[r] + 0 .. n - 1 (frames[r] None: the row's current style)"""
+        n = max(len(f) for f in frames if f is not None)
+        wgt = np.ones((self.rows, n, 1), np.float32)
+        for r, f in enumerate(frames):
+            if f is not None:
+                row = self._rows[r]
+                wgt[r, :len(f), 0] = [style_weight(x, row.k_style, row.fade) for x in f]
+        self._ops += 2
+        return torch.lerp(self.sty_old[:, None], self.sty_new[:, None], torch.as_tensor(wgt, device=self.dev)).contiguous()
+
+    # ------------------------------------------------------------------ decode
+    def _encode(self, jobs, out_ld):
+        """one zeggs_speech_encoder_live launch; jobs[r] = None or (enc_k0, n_out, n_new, last) -> speech [R, out_ld, O]"""
+        lr = []
+        for r in range(self.rows):
+            row = self._rows[r]
+            if jobs[r] is None:
+                lr.append(ops.LiveRow(0, 0, -1, 0, 0, 0, 0))
+                continue
+            k0, n_out, n_new, last = jobs[r]
+            lr.append(ops.LiveRow(row.n_ring, k0, last, n_new, n_out, row.n_ring - row.fbase, 0))
+        speech = torch.empty(self.rows, out_ld, self.enc.d.O, device=self.dev)
+        ops.speech_encoder_live(self.enc, lr, self.feats, self.ring, speech)
+        self._ops += 1
+        for r in range(self.rows):
+            if jobs[r] is not None:
+                self._rows[r].n_ring += jobs[r][2]
+        return speech
+
+    def _decode_one(self, r, speech, style, n):
+        """frames kd .. kd + n - 1 of row r alone on the B = 1 entry point (speech / style [1, n + 1, .], index 0 = frame kd - 1);
+        the give-up word is looked at before the state is committed, a chunk that gave up is redone on the stage launches"""
+        st = self.st
+        args = (self.decoder, self.pose[r:r + 1], self.rpos[r:r + 1], self.rrot[r:r + 1],
+                self.gaze[r:r + 1, :1].expand(1, n + 1, 3).contiguous(), speech, style, st["anim_input_mean"], st["anim_input_std"],
+                st["anim_output_mean"], st["anim_output_std"], self.dt)
+        h_in = self.h[:, r:r + 1].contiguous()
+        pose, rpos, rrot, h = ops.decoder_chunk(*args, h_in=h_in, status=self.status)
+        self._ops += 3
+        if ops._persistent_live(0):
+            bits = int(self.status[0].item())
+            if bits:
+                ops._warn_gave_up(bits, "the step")
+                ops.set_option("persistent", 0)
+                ops.fill_(self.status.view(torch.float32))
+                self.redone_steps += 1
+                pose, rpos, rrot, h = ops.decoder_chunk(*args, h_in=h_in, status=self.status)
+        self.h[:, r:r + 1] = h
+        self.pose[r], self.rpos[r], self.rrot[r] = pose[0, -1], rpos[0, -1], rrot[0, -1]
+        self._ops += 4
+        return pose[0], rpos[0], rrot[0]
+
+    def _head(self, r):
+        """frame 0 of row r (its first pose) if it has not been handed out yet, else None; taken BEFORE the row's state moves on"""
+        if self._rows[r].sent0:
+            return None
+        self._rows[r].sent0 = True
+        return self.pose[r:r + 1].clone(), self.rpos[r:r + 1].clone(), self.rrot[r:r + 1].clone()
+
+    @staticmethod
+    def _emit(head, pose, rpos, rrot):
+        """frames 1.. of a decoded chunk (index 0 is the frame it started from), with frame 0 in front once per stream"""
+        o = (pose[1:], rpos[1:], rrot[1:])
+        if head is not None:
+            o = tuple(torch.cat([a, b]) for a, b in zip(head, o))
+        return dict(zip(("pose", "rpos", "rrot"), o))
+
+    def step(self):
+        """-> {sid: {"pose": [tick, PO], "rpos": [tick, 3], "rrot": [tick, 4]}} for every row that had `tick` decodable frames
+        (the first step of a stream also carries frame 0, the first pose, in front)."""
+        rows = [None if x is None else dict(n_feat=x.n_feat, n_ring=x.n_ring, kd=x.kd) for x in self._rows]
+        plan = plan_step(rows, self.tick, self.D)
+        live = [r for r in range(self.rows) if plan[r] is not None]
+        if not live:
+            return {}
+        self._ops = 0
+        tick, T = self.tick, self.T
+        with torch.no_grad():
+            speech = self._encode([None if p is None else (p["enc_k0"], p["n_out"], p["n_new"], -1) for p in plan], T)
+            style = self._style([None if p is None else range(p["enc_k0"], p["k1"]) for p in plan])
+            out = {}
+            heads = {r: self._head(r) for r in live}
+            if self.rows == 1:
+                row = self._rows[0]
+                pose, rpos, rrot = self._decode_one(0, speech, style, tick)
+                out[row.sid] = self._emit(heads[0], pose, rpos, rrot)
+                row.kd += tick
+            else:
+                info = {}
+                pose, rpos, rrot, h = ops.decoder_batch_chunk(self.bd, self.pose, self.rpos, self.rrot, self.gaze, speech, style,
+                                                              self.h, status=self.status, info=info)
+                if info["gave_up"]:                  # (the chunk was redone with mode 1 before anything is committed below)
+                    self.redone_steps += 1
+                mask = torch.zeros(self.rows, dtype=torch.bool)
+                mask[live] = True
+                mask = mask.to(self.dev)
+                # masked commit: rows that did not take part keep their state (theirs was computed from filler)
+                self.h = torch.where(mask[None, :, None], h, self.h)
+                self.pose = torch.where(mask[:, None], pose[:, -1], self.pose)
+                self.rpos = torch.where(mask[:, None], rpos[:, -1], self.rpos)
+                self.rrot = torch.where(mask[:, None], rrot[:, -1], self.rrot)
+                self._ops += 6
+                for r in live:
+                    row = self._rows[r]
+                    out[row.sid] = self._emit(heads[r], pose[r], rpos[r], rrot[r])
+                    row.kd += tick
+        self.stats["launches_per_step"] = self._ops
+        self.stats["steps"] += 1
+        return out
+
+    def drain(self):
+        """step() until no row is eligible -> {sid: frames} concatenated over the steps"""
+        acc = {}
+        while True:
+            out = self.step()
+            if not out:
+                break
+            for sid, o in out.items():
+                acc.setdefault(sid, []).append(o)
+        return {sid: {k: torch.cat([o[k] for o in v]) for k in v[0]} for sid, v in acc.items()}
+
+    def close(self, sid):
+        """end of stream `sid`'s signal: its remaining frames with the right-edge rules of the offline path (reflect padding of the
+        STFT, replicate padding of the speech encoder), decoded for that row alone; the row is free again"""
+        r, row = self._row(sid)
+        n_total = audio.n_anim_frames(row.n, self.fs, self.fps)
+        outs = []
+        with torch.no_grad():
+            if row.n > 0:
+                self._features(r, row, n_total, final=True)
+            if n_total >= 1 and not row.sent0:
+                outs.append(self._head(r))
+            while row.kd < n_total:
+                rem = n_total - row.kd
+                n = rem if rem <= self.tail else self.tick       # the last call flushes what the ring still reaches
+                final = n == rem
+                top = n_total if final else row.kd + n + LOOKAHEAD
+                jobs = [None] * self.rows
+                jobs[r] = (row.kd - 1, n + 1, top - row.n_ring, n_total - 1 if final else -1)
+                speech = self._encode(jobs, self.tail + 1)[r:r + 1, :n + 1].contiguous()
+                frames = [None] * self.rows
+                frames[r] = range(row.kd - 1, row.kd + n)
+                style = self._style(frames)[r:r + 1].contiguous()
+                pose, rpos, rrot = self._decode_one(r, speech, style, n)
+                outs.append((pose[1:], rpos[1:], rrot[1:]))
+                row.kd += n
+        self._rows[r] = None
+        del self._sids[sid]
+        if not outs:
+            return {}
+        return {k: torch.cat([o[i] for o in outs]) for i, k in enumerate(("pose", "rpos", "rrot"))}

@@ -68,7 +68,9 @@ GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "b
 # what the binding needs beyond the header's older entry points: checked when the library is loaded, so that a stale
 # libzeggs_hip.so fails with a message instead of an AttributeError in the middle of a job list
 REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
-                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm")
+                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm",
+                    "zeggs_mel_window_first_sample", "zeggs_mel_features_window", "zeggs_speech_encoder_live",
+                    "zeggs_speech_encoder_live_prepare", "zeggs_speech_encoder_live_workspace_bytes")
 
 
 def lib():
@@ -87,8 +89,11 @@ def lib():
         raise HipLibraryMissing(f"{_LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
     for n in ("zeggs_speech_encoder_workspace_bytes", "zeggs_style_encoder_workspace_bytes",
               "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_style_encoder_input_offset",
-              "zeggs_decoder_batch_workspace_bytes"):
+              "zeggs_decoder_batch_workspace_bytes", "zeggs_mel_range_workspace_bytes",
+              "zeggs_speech_encoder_live_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
+    for n in ("zeggs_mel_frames_ready", "zeggs_mel_window_first_sample"):
+        getattr(L, n).restype = C.c_long
     _LIB = L
     # tuning switches for experiments, e.g. ZEGGS_OPTIONS="bwd_chunks=4,stage_variant=0" (see zeggs_set_option)
     for kv in filter(None, os.environ.get("ZEGGS_OPTIONS", "").split(",")):
@@ -978,6 +983,85 @@ def decoder_batch_chunk(bd, pose0, rpos0, rrot0, gaze, speech, style, h_in, stat
     if info is not None:
         info["path"], info["gave_up"] = batch_last_path(), bits
     return pose, rpos, rrot, h_out
+
+
+# ----------------------------------------------------------------------------- live serving (zeggs/live.py)
+class LiveDims(C.Structure):       # mirrors ZeggsLiveDims
+    _fields_ = [("R", C.c_int), ("F", C.c_int), ("H", C.c_int), ("O", C.c_int), ("KW", C.c_int), ("D", C.c_int),
+                ("feat_ld", C.c_int), ("out_ld", C.c_int)]
+
+
+class LiveRow(C.Structure):        # mirrors ZeggsLiveRow
+    _fields_ = [("n_ring", C.c_long), ("k0", C.c_long), ("last", C.c_long), ("n_new", C.c_int), ("n_out", C.c_int),
+                ("feat_off", C.c_int), ("reserved", C.c_int)]
+
+
+LIVE_MAX_ROWS = 64                 # ZEGGS_LIVE_MAX_ROWS
+
+
+def mel_frames_ready(d, n_samples):
+    """zeggs_mel_frames_ready (host only): animation frames computable from the first n_samples samples while the signal continues"""
+    return int(lib().zeggs_mel_frames_ready(C.byref(d), C.c_long(int(n_samples))))
+
+
+def mel_window_first_sample(d, k0):
+    """zeggs_mel_window_first_sample (host only): the smallest absolute sample index any frame >= k0 loads (d: audio.MelDims)"""
+    return int(lib().zeggs_mel_window_first_sample(C.byref(d), C.c_long(int(k0))))
+
+
+def mel_range_workspace(d, n_frames, device):
+    """a workspace that serves every zeggs_mel_features_range / _window call of at most n_frames frames"""
+    return _ws(lib().zeggs_mel_range_workspace_bytes(C.byref(d), C.c_long(0), C.c_long(int(n_frames))), device)
+
+
+def mel_features_window(d, wav_window, base, n_samples, final, filterbank, k0, k1, out, ws):
+    """zeggs_mel_features_window: rows [k0, k1) of the feature table into `out` [k1 - k0, n_mels + 1] from a sliding window of the
+    signal (wav_window[i] = sample base + i; n_samples = absolute count received so far)."""
+    if out.shape[0] != k1 - k0 or out.shape[1] != d.n_mels + 1 or wav_window.numel() < n_samples - base:
+        raise ValueError("mel_features_window: out / window do not match the range")
+    _check(lib().zeggs_mel_features_window(C.byref(d), _p(wav_window), C.c_long(int(base)), C.c_long(int(n_samples)), int(bool(final)),
+                                           C.c_void_p(filterbank.data_ptr()), C.c_long(int(k0)), C.c_long(int(k1)), _p(out), _p(ws),
+                                           C.c_size_t(ws.numel()), _stream()), "mel_features_window")
+    return out
+
+
+class LiveSpeech:
+    """The speech encoder's weights in the layout of the incremental kernel (zeggs_speech_encoder_live_prepare, once) for `rows`
+    rows with rings of `depth` frames; `feat_ld` / `out_ld`: rows per row block of the feature and output tensors of every call."""
+
+    def __init__(self, speech_net, a_mean, a_std, rows, depth, feat_ld, out_ld):
+        self.params = [_f32c(t) for t in (speech_net.layer0.weight, speech_net.layer0.bias, speech_net.layer1.weight,
+                                          speech_net.layer1.bias, speech_net.layer2.weight, speech_net.layer2.bias)]
+        H, F = self.params[0].shape[0], self.params[0].shape[1]
+        O, KW = self.params[2].shape[0], self.params[2].shape[2]
+        self.mean, self.std = _f32c(a_mean).reshape(-1), _f32c(a_std).reshape(-1)
+        if self.mean.numel() not in (1, F) or self.std.numel() not in (1, F):
+            raise ValueError("LiveSpeech: audio mean / std do not match the encoder's input size")
+        self.mean, self.std = self.mean.expand(F).contiguous(), self.std.expand(F).contiguous()      # (scalars broadcast, as in torch)
+        self.d = LiveDims(int(rows), F, H, O, KW, int(depth), int(feat_ld), int(out_ld))
+        self.P = _ptrs(SpeechPtrs, SPEECH_FIELDS, self.params)
+        L = lib()
+        self.ws = _ws(L.zeggs_speech_encoder_live_workspace_bytes(C.byref(self.d)), self.params[0].device)
+        _check(L.zeggs_speech_encoder_live_prepare(C.byref(self.d), C.byref(self.P), _p(self.ws), C.c_size_t(self.ws.numel()),
+                                                   _stream()), "speech_encoder_live_prepare")
+
+    def dims(self, feat_ld=None, out_ld=None):
+        d = self.d
+        return LiveDims(d.R, d.F, d.H, d.O, d.KW, d.D, int(feat_ld or d.feat_ld), int(out_ld or d.out_ld))
+
+
+def speech_encoder_live(ls, rows, feats, ring, out):
+    """zeggs_speech_encoder_live: ONE launch for all rows.  rows: a sequence of R LiveRow; feats [R, feat_ld, F] un-normalised
+    features (row r's new frames from row LiveRow.feat_off on), ring [R, D, H] the rows' layer-0 rings (updated in place),
+    out [R, out_ld, O] (row r, index i: frame k0 + i; zero beyond n_out)."""
+    d = ls.dims(feats.shape[1], out.shape[1])
+    if len(rows) != d.R or tuple(feats.shape) != (d.R, d.feat_ld, d.F) or tuple(ring.shape) != (d.R, d.D, d.H) or \
+            tuple(out.shape) != (d.R, d.out_ld, d.O):
+        raise ValueError("speech_encoder_live: tensor shapes do not match the LiveSpeech")
+    arr = (LiveRow * d.R)(*rows)
+    _check(lib().zeggs_speech_encoder_live(C.byref(d), C.byref(ls.P), _p(ls.mean), _p(ls.std), arr, _p(feats), _p(ring), _p(out),
+                                           _p(ls.ws), C.c_size_t(ls.ws.numel()), _stream()), "speech_encoder_live")
+    return out
 
 
 # ----------------------------------------------------------------------------- free functions of the Networks layer
