@@ -442,6 +442,29 @@ int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims*, const int* parents, const float*
                           float* dpose, float* drpos, float* drrot, float* dmu, float* dlogvar, float gscale,
                           void* ws, size_t ws_bytes, void* stream, int truth_prepared);
 
+/* Held-out evaluation: the forward alone, PER WINDOW, in float64 (no gradient table, no backward kernel).  rows[b] of window b:
+ *   [0..16]  the 17 weighted L1 terms above for that window alone (means over its T frames, T - 1 for the four finite-difference
+ *            terms, which are 0 at T == 1 and never cross a window's edge): their mean over b is terms[0..16] of zeggs_loss_fwd_bwd
+ *   [17]     its unweighted KL, -0.5 mean_s(1 + logvar - mu^2 - exp(logvar)) (mu == NULL: 0); the caller applies the weight
+ *   [18]     mean over frames and joints of |predicted - true character-space joint position| (MPJPE, the data's unit)
+ *   [19]     |o_rpos - w_rpos| at the window's last frame (root drift)
+ *   [20,21]  mean over frames and joints of |character-space joint velocity| of the prediction / of the truth
+ * Fixed-order sums, no atomics: a window's row is bitwise the same wherever it stands in the batch.  Same argument checks as the
+ * training loss, ahead of any launch; zeggs_loss_eval_workspace_bytes <= zeggs_loss_workspace_bytes for the same dims. */
+#define ZEGGS_EVAL_COLS 22
+size_t zeggs_loss_eval_workspace_bytes(const ZeggsLossDims*);
+int zeggs_loss_eval(const ZeggsLossDims*, const int* parents, const float* o_pose, const float* o_rpos, const float* o_rrot,
+                    const float* w_pose, const float* w_rpos, const float* w_rrot, const float* gaze, const float* mu,
+                    const float* logvar, double* rows /* [B][ZEGGS_EVAL_COLS] */, void* ws, size_t ws_bytes, void* stream);
+/* acc[group[b]] += rows[b] in ascending b (group[b] < 0 or >= groups: row ignored), one thread per (group, column), no atomics;
+ * acc is [groups][ZEGGS_EVAL_COLS + 1], its last column counts the rows.  The caller zeroes acc once. */
+int zeggs_eval_accumulate(const double* rows, const int* group /* [B] */, int B, int groups, double* acc, void* stream);
+/* The matrix products the CALLING THREAD launches from here on (on != 0) never split their contraction over workgroups: split-K /
+ * stream-K combine partial sums with fp32 atomics, so the last bits of a forward pass change from call to call.  With the fixed
+ * order every element is summed by one workgroup, bitwise the same on every call; slower on latency-bound shapes.  Returns the
+ * previous setting.  Off by default; zeggs.evaluate switches it on for the length of an evaluation. */
+int zeggs_gemm_fixed_order(int on);
+
 /* ---------------------------------------------------------------- RAdam
  * replaces RAdam.step, ZEGGS/optimizers.py:31-99, fused over one flat fp32 buffer.
  * rectified != 0: p -= step_scale * m / (sqrt(v) + eps), else p -= step_scale * m (host scalars of

@@ -1035,6 +1035,16 @@ void zeggs_gemm_set_asum(int on) { g_gemm_asum = on; }
 int g_gemm_skinny = 1;          // zeggs_set_option("gemm_skinny", 0/1): batch-sized NT products in one launch
 int g_gemm_streamk = 1;        // zeggs_set_option("gemm_streamk", 0/1): stream-K instead of the many-workgroup split-K
 int g_gemm_mid_split = 1;      // zeggs_set_option("gemm_mid_split", 0/1): split K of the latency-bound narrow-output products
+// zeggs_gemm_fixed_order(1): the products the CALLING THREAD launches from here on never split their contraction over workgroups
+// (split-K / stream-K combine partial sums with fp32 atomics, whose order -- and so the last bits of C -- changes from call to call):
+// every element of C is then summed by one workgroup in one order, bitwise the same on every call.  Slower on the latency-bound
+// shapes the splits exist for; meant for forward-only work whose numbers are compared across calls (zeggs.evaluate).  Off by default.
+static thread_local int t_gemm_fixed_order = 0;
+extern "C" int zeggs_gemm_fixed_order(int on) {
+  const int prev = t_gemm_fixed_order;
+  t_gemm_fixed_order = on != 0;
+  return prev;
+}
 
 // stream-K pays from K = 1280 on.  Below, its equal-share workgroups spend their time on the fix-up atomics of tiles they share: the two
 // fold products of the decoder packs (3072 x 1024 and 1024 x 1024 at K = 1131, once per optimizer step) take 108 + 56 us alone as
@@ -1047,6 +1057,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
   if (g.nb1 <= 0) g.nb1 = 1;
   if (g.kbatch <= 0) g.kbatch = 1;
   g.splitk = 1;
+  const bool may_split = !t_gemm_fixed_order;
   if (g_gemm_skinny && skinny_ok(g, nbatch)) return launch_skinny(skinny_args(g), g.sbk == 1 && g.sbn != 1, s);
   if (g.M <= 32) {
     // batch-sized products (M = B rows against a whole weight matrix: CellStateEncoder, the per-step GEMMs of the
@@ -1055,7 +1066,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
     const long tiles = (long)cdiv(g.N, 128) * nbatch;
     const long ktiles = (long)cdiv(g.K, 16) * g.kbatch;
     const bool plain_beta = g.beta == 0.f || (g.beta == 1.f && g.bias == nullptr && g.act == ACT_NONE);
-    if (nbatch == 1 && g.scn == 1 && plain_beta && ktiles >= 16 && tiles < 128) {
+    if (may_split && nbatch == 1 && g.scn == 1 && plain_beta && ktiles >= 16 && tiles < 128) {
       long sk = (256 + tiles - 1) / tiles;
       if (sk > ktiles / 4) sk = ktiles / 4;
       if (sk > 64) sk = 64;
@@ -1092,7 +1103,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
     const long tiles64 = (long)cdiv(g.M, 64) * cdiv(g.N, 64) * nbatch;
     const bool streamk_case = g_gemm_streamk && nbatch == 1 && g.bias == nullptr && g.act == ACT_NONE && g.scm == g.N && big &&
                               ktiles >= SK_MIN_KTILES && tiles < 1024 * 3;
-    if (g_gemm_mid_split && flat_c && plain_beta && !streamk_case && tiles64 >= 32 && tiles64 < 768 && ktiles >= 16) {
+    if (may_split && g_gemm_mid_split && flat_c && plain_beta && !streamk_case && tiles64 >= 32 && tiles64 < 768 && ktiles >= 16) {
       long sk = (1024 + tiles64 - 1) / tiles64;
       if (sk > ktiles / 6) sk = ktiles / 6;
       if (sk > 8) sk = 8;
@@ -1119,11 +1130,11 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
   // few output tiles but a long contraction (weight gradients): split K over workgroups, combine with fp32 atomics
   const bool can_split = nbatch == 1 && (g.beta == 0.f || g.beta == 1.f) && g.bias == nullptr && g.act == ACT_NONE &&
                          g.scn == 1 && g.scm == g.N && ktiles >= 64;
-  if (g_gemm_streamk && can_split && big && g.nb1 == 1 && tiles < 1024 * 3 && ktiles >= SK_MIN_KTILES) {
+  if (may_split && g_gemm_streamk && can_split && big && g.nb1 == 1 && tiles < 1024 * 3 && ktiles >= SK_MIN_KTILES) {
     if (g.beta == 0.f) ZTRY(k_fill(g.C, (long)g.M * g.N, 0.f, s));     // beta == 1: the atomics accumulate onto C
     return launch_streamk(g, s, asum_taken);
   }
-  if (tiles < g_gemm_wg_target * 5 / 6 && can_split) {
+  if (may_split && tiles < g_gemm_wg_target * 5 / 6 && can_split) {
     long sk = (g_gemm_wg_target + tiles - 1) / tiles;
     if (sk > ktiles / 16) sk = ktiles / 16;
     if (sk > 32) sk = 32;

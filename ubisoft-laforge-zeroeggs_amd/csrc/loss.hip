@@ -788,6 +788,158 @@ __global__ __launch_bounds__(1024) void loss_kl_final_k(const float* mu, const f
   }
 }
 
+// ---------------------------------------------------------------- held-out evaluation: the forward alone, per window
+// The feature pass above fills FO / FW; nothing else of the training call runs (no G, no backward).  rows[b][0..16] are the 17
+// weighted L1 terms of window b alone (term_of's weights, means over that window's T or T - 1 frames), [17] its unweighted KL,
+// [18] MPJPE over the cpos rows, [19] |o_rpos - w_rpos| at its last frame, [20] / [21] mean |cvel| of the prediction / the truth.
+// Stage 1: one workgroup per (slab of feature rows, window).  A wave takes a feature row at a time, its lanes stride over the
+// window's frames (consecutive addresses), every lane sums in float64; a wave's consecutive rows nearly always belong to the same
+// term, so the lane sums are folded (wave_sum_d) only when the term changes.  The Euclidean columns need x, y and z of a joint
+// together: the same workgroup walks its share of the JOINTS for them (the cpos / cvel rows a second time, out of L2).  Each wave
+// owns a row of `wacc`; the workgroup's 22 sums go to PS[window][slab][22].  Stage 2: one thread per (window, column) adds the
+// slabs in ascending order.  No atomics anywhere: the order depends on J and T only, so a window's row does not depend on where
+// in the batch it stands, nor on the batch size.
+constexpr int EVAL_COLS = ZEGGS_EVAL_COLS, EVAL_WAVES = 4, EVAL_MAX_SLABS = 32;
+// at least 64 feature rows per slab: PS (176 bytes per slab and window) then never exceeds the training call's G table (4 bytes per
+// feature row and frame), which is what keeps zeggs_loss_eval_workspace_bytes <= zeggs_loss_workspace_bytes at every shape
+__host__ __device__ inline int eval_slabs(int J) {
+  const int s = (21 + 33 * J) / 64;
+  return s < 1 ? 1 : (s > EVAL_MAX_SLABS ? EVAL_MAX_SLABS : s);
+}
+struct EvalWs {
+  float *FO, *FW, *LM, *PT0, *PT1;
+  double* PS;               // [B][eval_slabs(J)][EVAL_COLS]
+};
+EvalWs carve_eval(const ZeggsLossDims& d, Arena& a) {
+  EvalWs w;
+  const long NF = (long)d.B * d.T;
+  const Off o = offsets(d.J);
+  w.FO = a.f(NF * o.n); w.FW = a.f(NF * o.n); w.LM = a.f(NF * 9 * d.J);
+  const long PO = 6 + 15 * d.J;
+  w.PT0 = a.f(NF * PO); w.PT1 = a.f(NF * PO);
+  w.PS = (double*)a.raw((size_t)d.B * eval_slabs(d.J) * EVAL_COLS * sizeof(double));
+  return w;
+}
+__device__ __forceinline__ double wave_sum_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+__global__ __launch_bounds__(64 * EVAL_WAVES) void loss_eval_rows_k(ZeggsLossDims d, const float* FO, const float* FW, double* PS) {
+  __shared__ double wacc[EVAL_WAVES][EVAL_COLS];
+  const int slab = blockIdx.x, nslab = gridDim.x, b = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int J = d.J, T = d.T;
+  const long NF = (long)d.B * T, f0 = (long)b * T;
+  const Off o = offsets(J);
+  for (int i = threadIdx.x; i < EVAL_WAVES * EVAL_COLS; i += blockDim.x) (&wacc[0][0])[i] = 0.0;
+  __syncthreads();
+  const double inv_dt = 1.0 / (double)d.dt;
+  // ---- columns 0..16: this slab's feature rows
+  {
+    const int e0 = (int)((long)o.n * slab / nslab), e1 = (int)((long)o.n * (slab + 1) / nslab);
+    int cur = -1, cur2 = -1, cur_size = 1;
+    double s1 = 0.0, s2 = 0.0;
+    auto fold = [&]() {      // the lane sums of the term(s) just left -> this wave's row of wacc (wave-uniform branches)
+      if (cur >= 0) {
+        const double v = wave_sum_d(s1);
+        if (lane == 0) wacc[wave][cur] += v / ((double)T * cur_size);
+      }
+      if (cur2 >= 0 && T > 1) {
+        const double v = wave_sum_d(s2);
+        if (lane == 0) wacc[wave][cur2] += v / ((double)(T - 1) * cur_size);
+      }
+      s1 = 0.0; s2 = 0.0;
+    };
+    for (int e = e0 + wave; e < e1; e += EVAL_WAVES) {
+      int id, id2, size; float w, w2;
+      term_of(e, J, id, w, id2, w2, size);
+      if (id != cur) { fold(); cur = id; cur2 = id2; cur_size = size; }
+      const float* fo = FO + (long)e * NF + f0;
+      const float* fw = FW + (long)e * NF + f0;
+      const bool diff = id2 >= 0 && T > 1;
+      const double wd = (double)w, w2d = (double)w2;
+      for (int t = lane; t < T; t += 64) {
+        const double o0 = (double)fo[t], w0 = (double)fw[t];
+        s1 += fabs(wd * (o0 - w0));
+        if (diff && t + 1 < T)      // never across the window's last frame
+          s2 += fabs(w2d * ((((double)fo[t + 1] - o0) - ((double)fw[t + 1] - w0)) * inv_dt));      // (one product: exactly 0 when both sides agree)
+      }
+    }
+    fold();
+  }
+  // ---- columns 18, 20, 21: this slab's joints, x y z together
+  {
+    const int j0 = (int)((long)J * slab / nslab), j1 = (int)((long)J * (slab + 1) / nslab);
+    double sp = 0.0, so = 0.0, sw = 0.0;
+    auto norm3 = [](double x, double y, double z) { return sqrt(x * x + y * y + z * z); };
+    for (int j = j0 + wave; j < j1; j += EVAL_WAVES) {
+      const float* po = FO + (long)(o.cpos + 3 * j) * NF + f0;
+      const float* pw = FW + (long)(o.cpos + 3 * j) * NF + f0;
+      const float* vo = FO + (long)(o.cvel + 3 * j) * NF + f0;
+      const float* vw = FW + (long)(o.cvel + 3 * j) * NF + f0;
+      for (int t = lane; t < T; t += 64) {
+        sp += norm3((double)po[t] - (double)pw[t], (double)po[NF + t] - (double)pw[NF + t], (double)po[2 * NF + t] - (double)pw[2 * NF + t]);
+        so += norm3((double)vo[t], (double)vo[NF + t], (double)vo[2 * NF + t]);
+        sw += norm3((double)vw[t], (double)vw[NF + t], (double)vw[2 * NF + t]);
+      }
+    }
+    if (j1 > j0) {            // (workgroup-uniform)
+      const double n = (double)T * J;
+      sp = wave_sum_d(sp); so = wave_sum_d(so); sw = wave_sum_d(sw);
+      if (lane == 0) { wacc[wave][18] += sp / n; wacc[wave][20] += so / n; wacc[wave][21] += sw / n; }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < EVAL_COLS) {
+    double v = 0.0;
+    for (int k = 0; k < EVAL_WAVES; ++k) v += wacc[k][threadIdx.x];
+    PS[((long)b * nslab + slab) * EVAL_COLS + threadIdx.x] = v;
+  }
+}
+
+// stage 2: one thread per (window, column)
+__global__ __launch_bounds__(256) void loss_eval_final_k(ZeggsLossDims d, const float* FO, const float* FW, const float* mu,
+                                                         const float* logvar, const double* PS, int nslab, double* rows) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (long)d.B * EVAL_COLS) return;
+  const int b = (int)(i / EVAL_COLS), c = (int)(i % EVAL_COLS);
+  const long NF = (long)d.B * d.T;
+  double v = 0.0;
+  if (c == 17) {            // unweighted KL of the window (modules.py:778-779 without the mean over the batch)
+    if (mu && d.S > 0) {
+      for (int s = 0; s < d.S; ++s) {
+        const double m = (double)mu[(long)b * d.S + s], lv = (double)logvar[(long)b * d.S + s];
+        v += 1.0 + lv - m * m - exp(lv);
+      }
+      v = -0.5 * v / (double)d.S;
+    }
+  } else if (c == 19) {     // root drift: distance of the two root positions at the window's last frame
+    const long f = (long)b * d.T + d.T - 1;
+    const Off o = offsets(d.J);
+    for (int k = 0; k < 3; ++k) {
+      const double x = (double)FO[(long)(o.rpos + k) * NF + f] - (double)FW[(long)(o.rpos + k) * NF + f];
+      v += x * x;
+    }
+    v = sqrt(v);
+  } else {
+    for (int s = 0; s < nslab; ++s) v += PS[((long)b * nslab + s) * EVAL_COLS + c];
+  }
+  rows[i] = v;
+}
+
+// acc[group[b]] += rows[b] in ascending b, one thread per (group, column); the last column counts the rows
+__global__ __launch_bounds__(256) void eval_accumulate_k(const double* rows, const int* group, int B, int groups, double* acc) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= groups * (EVAL_COLS + 1)) return;
+  const int g = i / (EVAL_COLS + 1), c = i % (EVAL_COLS + 1);
+  double v = acc[i];
+  for (int b = 0; b < B; ++b)
+    if (group[b] == g) v += c < EVAL_COLS ? rows[(long)b * EVAL_COLS + c] : 1.0;
+  acc[i] = v;
+}
+
 }  // namespace
 
 int g_loss_lds = 1;      // zeggs_set_option("loss_lds", 0): the table walk in global memory (what a part without 160 KB of LDS gets; tests)
@@ -889,5 +1041,53 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
     hipLaunchKernelGGL(loss_rootvel_bwd_k, dim3(cdiv(NF, 256)), dim3(256), 0, s, d, ioO, w.G, w.DQ, dpose, drrot);
     ZLAUNCH_CHECK("loss_rootvel_bwd");
   }
+  return 0;
+}
+
+// ---------------------------------------------------------------- held-out evaluation (forward only, per window)
+extern "C" size_t zeggs_loss_eval_workspace_bytes(const ZeggsLossDims* d) {
+  Arena a(nullptr, 0);
+  carve_eval(*d, a);
+  return a.off + 256;
+}
+
+// The feature pass of the training call (both sides), then the per-window sums: rows [B][ZEGGS_EVAL_COLS], float64.
+extern "C" int zeggs_loss_eval(const ZeggsLossDims* dp, const int* parents, const float* o_pose, const float* o_rpos,
+                               const float* o_rrot, const float* w_pose, const float* w_rpos, const float* w_rrot,
+                               const float* gaze, const float* mu, const float* logvar, double* rows, void* ws, size_t ws_bytes,
+                               void* stream) {
+  const ZeggsLossDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  Arena a(ws, ws_bytes);
+  EvalWs w = carve_eval(d, a);
+  LOSS_CHECK_ARGS(d, a, ws_bytes);
+  ZCHECK(rows != nullptr, "loss_eval: no output table");
+  ZCHECK(mu == nullptr || (logvar != nullptr && d.S >= 1), "loss_eval: mu without logvar / S");
+  const int lds_ok = g_loss_lds ? loss_lds_ready() : 0;
+  const long NF = (long)d.B * d.T;
+  const int PO = 6 + 15 * d.J, nslab = eval_slabs(d.J);
+  FrameIO ioO{o_pose, o_rpos, o_rrot}, ioW{w_pose, w_rpos, w_rrot};
+  const dim3 tg((unsigned)cdiv(NF, 64), (unsigned)cdiv(PO, 64));
+  hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT0, o_pose, NF, PO);
+  hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT1, w_pose, NF, PO);
+  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(2 * NF, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
+                     w.FW, w.LM, 0L, 2 * NF, lds_ok);
+  ZLAUNCH_CHECK("loss_frame_fwd");
+  hipLaunchKernelGGL(loss_eval_rows_k, dim3(nslab, d.B), dim3(64 * EVAL_WAVES), 0, s, d, (const float*)w.FO, (const float*)w.FW, w.PS);
+  ZLAUNCH_CHECK("loss_eval_rows");
+  hipLaunchKernelGGL(loss_eval_final_k, dim3(cdiv((long)d.B * EVAL_COLS, 256)), dim3(256), 0, s, d, (const float*)w.FO, (const float*)w.FW, mu, logvar,
+                     (const double*)w.PS, nslab, rows);
+  ZLAUNCH_CHECK("loss_eval_final");
+  return 0;
+}
+
+// acc [groups][ZEGGS_EVAL_COLS + 1] += the rows of each group, in ascending b (a group index < 0 or >= groups: the row is ignored);
+// the last column counts the rows.  The caller zeroes acc once, ahead of the first batch.
+extern "C" int zeggs_eval_accumulate(const double* rows, const int* group, int B, int groups, double* acc, void* stream) {
+  ZCHECK(B >= 1 && groups >= 1, "eval_accumulate: bad dims");
+  ZCHECK(rows != nullptr && group != nullptr && acc != nullptr, "eval_accumulate: null pointer");
+  hipLaunchKernelGGL(eval_accumulate_k, dim3(cdiv((long)groups * (EVAL_COLS + 1), 256)), dim3(256), 0, (hipStream_t)stream, rows, group, B,
+                     groups, acc);
+  ZLAUNCH_CHECK("eval_accumulate");
   return 0;
 }

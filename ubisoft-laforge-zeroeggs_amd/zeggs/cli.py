@@ -5,6 +5,7 @@
     python -m zeggs.cli generate -o options.json -s style.bvh -a speech.wav ... (ZEGGS/generate.py:414-525)
     python -m zeggs.cli generate -o options.json -c pairs.csv                   (batch mode, same CSV columns)
     python -m zeggs.cli generate -o options.json -c pairs.csv -b 32             (the job list decoded 32 clips at a time)
+    python -m zeggs.cli evaluate -o options.json [--split valid|train]          (score the held-out split; no reference counterpart)
 
 `options.json` is the reference's file (configs/configs_v*.json before training, <output_dir>/options.json after): keys
 `train_opt`, `net_opt`, `paths` {base_path, path_processed_data, output_dir, models_dir}.  Differences from the reference's
@@ -99,8 +100,54 @@ def cmd_generate(a):
     return 0
 
 
+def cmd_evaluate(a):
+    """Score the validation (or training) split with the saved networks: the table by style label on stdout, the whole result as
+    JSON (--json FILE, default <output_dir>/evaluation_<split>.json)."""
+    import numpy as np
+    import torch
+    from . import compat, engine
+    from .evaluate import evaluate, format_table
+    options = json.loads(Path(a.options).read_text())
+    p, _, data = _paths(options)
+    topt, nopt = options["train_opt"], options["net_opt"]
+    kind = topt.get("style_encoding_type", "example")
+    device = torch.device("cuda", 0)
+    if not torch.cuda.is_available():
+        raise SystemExit("evaluate: the ZeroEGGS MI355X engine has no CPU path (no GPU visible)")
+    torch.cuda.set_device(device)
+    models = Path(p["models_dir"])
+    if (models / "decoder.pt").exists():
+        se = compat.load_module(models / "speech_encoder.pt", device).to(device)
+        de = compat.load_module(models / "decoder.pt", device).to(device)
+        st = compat.load_module(models / "style_encoder.pt", device).to(device) if kind == "example" else None
+    else:
+        se, de, st, _ = compat.load_state(models, device)
+        st = st if kind == "example" else None
+    with open(data / "data_definition.json") as f:
+        details = json.load(f)
+    ds = engine.DeviceDataset(np.load(data / "processed_data.npz"), topt["window"], device)
+    iteration = None
+    ck = models / "checkpoints.pt"
+    if ck.exists():         # the KL weight the run had reached: the loss is then the one the training log shows
+        iteration = int(torch.load(ck, map_location="cpu", weights_only=False)["iteration"])
+    res = evaluate(se, de, st, ds, details["parents"], details["dt"], split=a.split, batch=a.batch or topt["batchsize"],
+                   example_len=nopt["style_encoder"]["example_length"], iteration=iteration, max_windows=a.max_windows)
+    print(f"{a.split}: {res['windows']} windows, {res['frames_scored']} of {res['frames_total']} frames scored"
+          + (f", KL weight of iteration {iteration}" if iteration is not None else ""))
+    for line in format_table(res, details["label_names"]):
+        print(line)
+    names = details["label_names"]
+    out = dict(res, split=a.split, iteration=iteration, table=res["table"].tolist(),
+               per_label={names[g] if g < len(names) else str(g): r for g, r in res["per_label"].items()})
+    path = Path(a.json) if a.json else Path(p["output_dir"]) / f"evaluation_{a.split}.json"
+    path.parent.mkdir(parents=True, exist_ok=True)
+    path.write_text(json.dumps(out, indent=2))
+    print(f"written {path}")
+    return 0
+
+
 def main(argv=None):
-    ap = argparse.ArgumentParser(prog="zeggs", description="ZeroEGGS on the MI355X engine: prepare / train / generate")
+    ap = argparse.ArgumentParser(prog="zeggs", description="ZeroEGGS on the MI355X engine: prepare / train / generate / evaluate")
     sub = ap.add_subparsers(dest="cmd", required=True)
     d = sub.add_parser("prepare", help="raw takes -> processed_data.npz, stats.npz, data_definition.json (reference: python data_pipeline.py)")
     d.add_argument("-c", "--conf", required=True, help="pipeline conf (configs/data_pipeline_conf_v*.json layout)")
@@ -126,6 +173,13 @@ def main(argv=None):
     g.add_argument("-b", "--batch", type=int, default=0, metavar="N",
                    help="decode the jobs N clips at a time on the weight-stationary batch sweep (default: one clip per decode)")
     g.set_defaults(fn=cmd_generate)
+    e = sub.add_parser("evaluate", help="score the held-out split with the saved networks (per-window loss, MPJPE, root drift by style label)")
+    e.add_argument("-o", "--options", required=True, help="options.json written by training")
+    e.add_argument("--split", default="valid", choices=("valid", "train"))
+    e.add_argument("--batch", type=int, default=0, metavar="N", help="windows per decoder rollout (default: the training batch size)")
+    e.add_argument("--max-windows", type=int, default=None, metavar="N", help="score only the first N windows of the split")
+    e.add_argument("--json", default=None, metavar="FILE", help="where the result goes (default <output_dir>/evaluation_<split>.json)")
+    e.set_defaults(fn=cmd_evaluate)
     a = ap.parse_args(argv)
     return a.fn(a)
 

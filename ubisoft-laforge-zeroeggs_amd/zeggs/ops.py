@@ -70,7 +70,8 @@ GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "b
 REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
                     "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm",
                     "zeggs_mel_window_first_sample", "zeggs_mel_features_window", "zeggs_speech_encoder_live",
-                    "zeggs_speech_encoder_live_prepare", "zeggs_speech_encoder_live_workspace_bytes")
+                    "zeggs_speech_encoder_live_prepare", "zeggs_speech_encoder_live_workspace_bytes", "zeggs_loss_eval",
+                    "zeggs_loss_eval_workspace_bytes", "zeggs_eval_accumulate", "zeggs_gemm_fixed_order")
 
 
 def lib():
@@ -88,7 +89,8 @@ def lib():
     if missing:
         raise HipLibraryMissing(f"{_LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
     for n in ("zeggs_speech_encoder_workspace_bytes", "zeggs_style_encoder_workspace_bytes",
-              "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_style_encoder_input_offset",
+              "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_loss_eval_workspace_bytes",
+              "zeggs_style_encoder_input_offset",
               "zeggs_decoder_batch_workspace_bytes", "zeggs_mel_range_workspace_bytes",
               "zeggs_speech_encoder_live_workspace_bytes"):
         getattr(L, n).restype = C.c_size_t
@@ -1263,6 +1265,67 @@ def training_loss(o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, parents,
     the gradients computed in the fused forward+backward kernel are handed on without a scaling pass."""
     return _LossFn.apply(o_pose, o_rpos, o_rrot, mu, logvar, w_pose, w_rpos, w_rrot, gaze, parents,
                          float(kl_weight), float(dt), float(gscale), bool(unit_grad), truth_ws)
+
+
+EVAL_COLS = 22                                     # ZEGGS_EVAL_COLS
+
+
+def _pd(t, dtype):
+    """device pointer of a contiguous tensor of `dtype` (float64 tables / int32 group indices of the evaluation calls)"""
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise RuntimeError(f"zeggs.ops: expected a contiguous {dtype} tensor on a GPU")
+    return C.c_void_p(t.data_ptr())
+
+
+def loss_eval(o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, parents, dt, mu=None, logvar=None, rows=None, ws=None):
+    """The loss section's forward alone, per window (zeggs_loss_eval) -> rows float64 [B, EVAL_COLS]: columns 0..16 the weighted
+    L1 terms of each window, 17 its unweighted KL (0 without mu), 18 MPJPE, 19 root drift at the last frame, 20 / 21 mean joint
+    speed of the prediction / the truth.  No gradient is built and nothing is differentiable.  `rows` / `ws`: the table of an
+    earlier call / a workspace of loss_eval_workspace() to use again when they fit."""
+    o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze = (_f32c(t) for t in (o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze))
+    B, T, PO = o_pose.shape
+    S = mu.shape[1] if mu is not None else 0
+    d = LossDims(B, T, (PO - 6) // 15, S, float(dt))
+    L = lib()
+    dev = o_pose.device
+    need = int(L.zeggs_loss_eval_workspace_bytes(C.byref(d)))
+    if ws is None or ws.numel() < need or ws.device != dev:
+        ws = _ws(need, dev)
+    if rows is None or tuple(rows.shape) != (B, EVAL_COLS) or rows.device != dev:
+        rows = torch.empty(B, EVAL_COLS, device=dev, dtype=torch.float64)
+    _check(L.zeggs_loss_eval(C.byref(d), _p(parents), _p(o_pose), _p(o_rpos), _p(o_rrot), _p(w_pose), _p(w_rpos), _p(w_rrot),
+                             _p(gaze), _p(_f32c(mu)) if mu is not None else None,
+                             _p(_f32c(logvar)) if mu is not None else None, _pd(rows, torch.float64), _p(ws),
+                             C.c_size_t(ws.numel()), _stream()), "loss_eval")
+    return rows
+
+
+class fixed_order_gemms:
+    """`with ops.fixed_order_gemms():` -- the matrix products this thread launches inside the block never split their contraction
+    over workgroups (zeggs_gemm_fixed_order): no fp32 atomics, so a forward pass is bitwise the same on every call."""
+
+    def __enter__(self):
+        self.prev = lib().zeggs_gemm_fixed_order(1)
+
+    def __exit__(self, *exc):
+        lib().zeggs_gemm_fixed_order(int(self.prev))
+        return False
+
+
+def loss_eval_workspace(B, T, J, S, dt, device):
+    """a workspace for loss_eval calls of these dimensions (zeggs_loss_eval_workspace_bytes)"""
+    d = LossDims(int(B), int(T), int(J), int(S), float(dt))
+    return _ws(lib().zeggs_loss_eval_workspace_bytes(C.byref(d)), device)
+
+
+def eval_accumulate(rows, group, acc):
+    """acc [groups, EVAL_COLS + 1] float64 += the rows of each group in ascending row order (zeggs_eval_accumulate); group: int32
+    [B], a negative entry leaves its row out; the last column of acc counts the rows.  The caller zeroes acc once."""
+    B, groups = rows.shape[0], acc.shape[0]
+    assert rows.shape == (B, EVAL_COLS) and acc.shape == (groups, EVAL_COLS + 1) and group.shape == (B,)
+    _check(lib().zeggs_eval_accumulate(_pd(rows, torch.float64), _pd(group, torch.int32), int(B), int(groups),
+                                       _pd(acc, torch.float64), _stream()), "eval_accumulate")
+    return acc
 
 
 # ----------------------------------------------------------------------------- optimizer / data

@@ -8,7 +8,10 @@ reference).  Differences (documented in DESIGN.md): the dataset lives in HBM and
 kernel; data parallelism over torch.distributed (RCCL) when WORLD_SIZE > 1.  Like the reference it renders three
 training and three validation clips (ground truth + prediction) to logs_dir/samples/*.bvh at every checkpoint
 (train.py:516-760) and logs the loss terms under logs_dir/tb when `use_tensorboard` is set (TensorBoard event files
-when the tensorboard package is importable, a scalars.jsonl with the same tags otherwise).
+when the tensorboard package is importable, a scalars.jsonl with the same tags otherwise).  Beyond the reference: the
+validation split is SCORED at every checkpoint (zeggs.evaluate; also every train_options["eval_every"] iterations when that
+key is present and > 0, batches of train_options["eval_batch"], default `batchsize`): one row per evaluation in
+logs_dir/eval.csv, and valid/* scalars beside the training ones.
 """
 import copy
 import datetime
@@ -47,7 +50,7 @@ LOSS_TAGS = ("loss_root_pos", "loss_root_rot", "loss_root_vel", "loss_root_vrt",
 
 class ScalarLog:
     """`use_tensorboard` sink (train.py:100-103,437-463): a SummaryWriter when tensorboard is installed, else the
-    same tags as JSON lines in <dir>/scalars.jsonl."""
+    same tags as JSON lines in <dir>/scalars.jsonl (held-out evaluations: <dir>/valid_scalars.jsonl)."""
 
     def __init__(self, directory):
         directory = Path(directory)
@@ -69,8 +72,36 @@ class ScalarLog:
                                         "losses/losses": dict(zip(LOSS_TAGS, terms))}) + "\n")
             self.file.flush()
 
+    def add_eval(self, iteration, result):
+        """a held-out evaluation (zeggs.evaluate.evaluate): valid/total_loss, valid/losses, valid/mpjpe"""
+        if self.writer is not None:
+            self.writer.add_scalar("valid/total_loss", result["loss"], iteration)
+            self.writer.add_scalars("valid/losses", result["terms"], iteration)
+            self.writer.add_scalar("valid/mpjpe", result["mpjpe"], iteration)
+        else:       # a file of its own: scalars.jsonl keeps one line per training iteration
+            with open(Path(self.file.name).with_name("valid_scalars.jsonl"), "a") as fh:
+                fh.write(json.dumps({"iteration": iteration, "valid/total_loss": result["loss"],
+                                     "valid/losses": result["terms"], "valid/mpjpe": result["mpjpe"]}) + "\n")
+
     def close(self):
         (self.writer or self.file).close()
+
+
+EVAL_CSV_COLUMNS = ("iteration", "windows", "frames_scored", "frames_total", "loss", "kl", "mpjpe", "root_drift", "speed_pred",
+                    "speed_true") + LOSS_TAGS
+
+
+def append_eval_csv(path, iteration, result):
+    """one row per evaluation in logs_dir/eval.csv (header when the file is new)"""
+    import csv
+    path = Path(path)
+    new = not path.exists()
+    with open(path, "a", newline="") as fh:
+        w = csv.writer(fh)
+        if new:
+            w.writerow(EVAL_CSV_COLUMNS)
+        flat = dict(result, iteration=iteration, **result["terms"])
+        w.writerow([flat[k] for k in EVAL_CSV_COLUMNS])
 
 
 def render_samples(samples_dir, iteration, ds, se, de, st, details, example_len, count=3, seconds=30):
@@ -191,6 +222,7 @@ def train(models_dir, logs_dir, path_processed_data, path_data_definition, train
     labels_onehot = None
     if style_type == "label":       # one-hot row per training range (dataset.py:150-151), gathered per window by a HIP kernel
         labels_onehot = torch.as_tensor(np.eye(nlabels, dtype=np.float32)[ds.ranges_train_labels]).to(device)
+    eval_every, eval_batch = int(train_options.get("eval_every", 0) or 0), int(train_options.get("eval_batch", batchsize))
     perm_rng = np.random.default_rng(train_options["seed"])           # identical on every rank
     for _ in range(epoch):                                             # resume: replay the permutations already consumed
         perm_rng.permutation(len(ds))
@@ -222,6 +254,9 @@ def train(models_dir, logs_dir, path_processed_data, path_data_definition, train
                 # the weights are about to be read for keeps: drain the give-up protocol first (steps a persistent sweep lost
                 # within the last few iterations are re-run on the stage kernels NOW; every rank, same iteration)
                 eng.flush()
+            scoring = len(ds.ranges_valid) > 0 and (checkpoint or (eval_every > 0 and iteration % eval_every == 0))
+            if scoring and not checkpoint:
+                eng.flush()                  # (the same drain ahead of an evaluation between two checkpoints)
             if eng.replayed:                 # steps the engine re-ran: their losses replace the NaN ones logged at the time
                 for it_r, loss_r, terms_r in eng.replayed:
                     if scalars is not None:
@@ -236,6 +271,14 @@ def train(models_dir, logs_dir, path_processed_data, path_data_definition, train
             if rank == 0 and iteration % 50 == 0:
                 sys.stdout.write(f"\r| epoch {epoch} | it {iteration} | batch {bi}/{nb} | loss {float(loss.detach()):.4f} "
                                  f"| {datetime.datetime.now() - start} |")
+            if scoring:                      # every rank: its share of the validation windows, one all-reduce of the table
+                from .evaluate import evaluate
+                held_out = evaluate(se, de, st, ds, parents, dt, split="valid", batch=eval_batch,
+                                    example_len=st_opt["example_length"], iteration=iteration, world=world, rank=rank)
+                if rank == 0 and held_out["windows"] > 0:      # (ranges shorter than a window: nothing was scored)
+                    append_eval_csv(logs_dir / "eval.csv", iteration, held_out)
+                    if scalars is not None:
+                        scalars.add_eval(iteration, held_out)
             if rank == 0 and checkpoint:
                 snap = [compact_copy(m) if m is not None else None for m in (se, de, st)]
                 osd = eng.opt.state_dict()                 # moments are views of the flat buffers: store them compact
