@@ -464,6 +464,32 @@ int zeggs_eval_accumulate(const double* rows, const int* group /* [B] */, int B,
  * order every element is summed by one workgroup, bitwise the same on every call; slower on latency-bound shapes.  Returns the
  * previous setting.  Off by default; zeggs.evaluate switches it on for the length of an evaluation. */
 int zeggs_gemm_fixed_order(int on);
+/* test hook (no reference counterpart): the route log of the CALLING THREAD's matrix products.  The GEMM launcher writes it at the
+ * point where it commits to a route; it never reads it, so the hook cannot change which route a call takes.  Cost: a few stores of
+ * plain thread-local integers per product -- no lock, no device work.
+ *   last4   (may be NULL) of the thread's last product: [0] route id, [1] splitk (1: unsplit, 0: stream-K, whose workgroups take equal
+ *           shares of the k-tiles instead), [2] [3] the workgroup tile BM x BN (skinny: 16 ceil(M / 16) rows, 16 columns)
+ *   counts  (may be NULL) ncounts entries: launches per route id since the last reset (ids >= the return value read 0)
+ *   reset   != 0: the log is cleared after it has been read
+ * Returns the number of route ids.  Ids: */
+enum {
+  ZEGGS_GEMM_ROUTE_NONE = 0,       /* nothing launched since the reset */
+  ZEGGS_GEMM_ROUTE_SKINNY,         /* the one-launch kernel of the batch-sized products */
+  ZEGGS_GEMM_ROUTE_M32_SPLIT,      /* M <= 32: zero fill, 32 x 128 tiles with atomics, bias / activation pass */
+  ZEGGS_GEMM_ROUTE_M32,            /* M <= 32: plain 32 x 128 tiles */
+  ZEGGS_GEMM_ROUTE_MID_SPLIT,      /* mid-size narrow outputs: 64 x 64 tiles, splitk 2 .. 8 */
+  ZEGGS_GEMM_ROUTE_SK_DIRECT,      /* stream-K: the direct TN kernel */
+  ZEGGS_GEMM_ROUTE_SK_BF16_SPLIT,  /* stream-K: the bf16-split experiment */
+  ZEGGS_GEMM_ROUTE_SK_DMA,         /* stream-K: the LDS-DMA TN kernel */
+  ZEGGS_GEMM_ROUTE_SK_LDS_128,     /* stream-K: LDS-tiled, 128 x 128 */
+  ZEGGS_GEMM_ROUTE_SK_LDS_256,     /* stream-K: LDS-tiled, 256 x 128 */
+  ZEGGS_GEMM_ROUTE_SPLITK,         /* plain split-K on 128 x 128 or 64 x 64 tiles */
+  ZEGGS_GEMM_ROUTE_HALF,           /* unsplit 128 x 64 tiles */
+  ZEGGS_GEMM_ROUTE_TILE_128,       /* unsplit 128 x 128 */
+  ZEGGS_GEMM_ROUTE_TILE_64,        /* unsplit 64 x 64 */
+  ZEGGS_GEMM_ROUTE_COUNT
+};
+int zeggs_test_gemm_route_log(int reset, int* last4, long* counts, int ncounts);
 
 /* ---------------------------------------------------------------- RAdam
  * replaces RAdam.step, ZEGGS/optimizers.py:31-99, fused over one flat fp32 buffer.
@@ -501,6 +527,13 @@ int zeggs_radam_step_wd(float* p, const float* g, float* m, float* v, long n, fl
  * float, 1.f - 0.999f = 0.00099998713 is 1.3e-5 relative off in exp_avg_sq at every step).  The four entry points above keep
  * their signatures and forward 1.f - beta; a caller that compares moments or checkpoints with the reference uses this one. */
 int zeggs_radam_step_c(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2, float comp1, float comp2,
+                       float eps, float step_scale, int rectified, float decay, unsigned* status, const float* gflag,
+                       int count_skip, void* stream);
+/* the same with beta1, beta2 and their complements as DOUBLES: the first moment m = beta1 m + (1 - beta1) g is formed in double and
+ * rounded once (where the two terms cancel, the float32 roundings of the products and of 0.9f are a multiple of what is left of m,
+ * and the step carries it into p); the second moment uses (float)beta2, (float)comp2 as before.  zeggs_radam_step_c and the entry
+ * points above are this one with their float arguments widened.  zeggs.ops.radam_step calls this one. */
+int zeggs_radam_step_d(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2, double comp1, double comp2,
                        float eps, float step_scale, int rectified, float decay, unsigned* status, const float* gflag,
                        int count_skip, void* stream);
 int zeggs_status_flag(const unsigned* status, float* dst /* device float */, void* stream);

@@ -1407,3 +1407,262 @@ def attention_keep(seed, B, NH, L, p, heads=None, bug=None):
     if heads is None:
         return torch.as_tensor(hash_keep_scale(seed, 0, B * NH * L * L, p, bug)).reshape(B, NH, L, L)
     return torch.as_tensor(np.stack([hash_keep_scale(seed, bh * L * L, L * L, p, bug) for bh in heads])).reshape(len(heads), 1, L, L)
+
+
+# ----------------------------------------------------------------------------- the GEMM launcher, route by route (tests/test_gpu_gemm_routes.py)
+# launch_gemm of csrc/gemm.hip through ops.gemm on buffers of the test's own, every route it can choose (the route log of
+# zeggs_test_gemm_route_log says which one a call took), against the float64 product.  tests/test_gemm_oracle_cpu.py measures on
+# the CPU what float32 itself costs at every case (the floors) and proves that the comparison is sharp (GEMM_BUGS).
+GEMM_CANARY_TAIL = 4096         # floats behind every output (and one float in front of it in the "odd" variant)
+GEMM_CANARY = 1234.5
+GEMM_VARIANTS = ("aligned", "odd")      # odd: every base pointer one float past a 16-byte boundary, odd leading dimensions of A and B
+GEMM_BUGS = ("last_ktile", "k_term", "segment_twice", "edge_row", "bias_shift", "act_before_bias", "beta_on_partials",
+             "batch_neighbour_A", "conv_no_overlap", "alpha_omitted")
+GEMM_SPLITTING = ("m32-split", "mid-split", "streamk-direct", "streamk-lds-128x128", "streamk-lds-256x128", "splitk")
+_T64, _M32 = ("tile-64x64", 1, 64, 64), ("m32", 1, 32, 128)
+_SK128, _SK256 = ("streamk-lds-128x128", 0, 128, 128), ("streamk-lds-256x128", 0, 256, 128)
+
+
+def _gemm_case(M, N, K, layout, route, fixed, **kw):
+    """One row of the matrix.  route / fixed: (route name, splitk, BM, BN) the log must show with default routing / inside
+    ops.fixed_order_gemms(); no_mid / no_streamk: the same with the option gemm_mid_split / gemm_streamk at 0 (None: not run).
+    lda: the conv form, A(m, k) = xp[m lda + k] with lda < K (overlapping rows).  sample: floors and mutations over gemm_sample_rows only."""
+    c = dict(M=M, N=N, K=K, layout=layout, route=route, fixed=fixed, alpha=1.0, beta=0.0, bias=False, act=0, ldc=None, nbatch=1,
+             lda=None, no_mid=None, no_streamk=None, sample=False)
+    assert not set(kw) - set(c), kw
+    c.update(kw)
+    c["id"] = (f"{M}x{N}x{K}-{layout}" + (f"-x{c['nbatch']}" if c["nbatch"] > 1 else "") + (f"-conv{c['lda']}" if c["lda"] else "") +
+               (f"-a{c['alpha']:g}" if c["alpha"] != 1.0 else "") + (f"-b{c['beta']:g}" if c["beta"] else "") +
+               ("-bias" if c["bias"] else "") + ("", "-elu", "-relu")[c["act"]] + (f"-ldc{c['ldc']}" if c["ldc"] else ""))
+    # which mutations of GEMM_BUGS apply: the first three rows everywhere; the others where the case has what they break
+    split = route[0] in GEMM_SPLITTING
+    c["bugs"] = tuple(b for b, on in (
+        ("last_ktile", True), ("k_term", True), ("edge_row", True), ("segment_twice", split), ("bias_shift", c["bias"]),
+        ("act_before_bias", c["bias"] and c["act"] != 0), ("beta_on_partials", split and c["beta"] != 0.0),
+        ("batch_neighbour_A", c["nbatch"] > 1), ("conv_no_overlap", c["lda"] is not None), ("alpha_omitted", c["alpha"] != 1.0)) if on)
+    return c
+
+
+# The smallest shapes that reach each route (launch_gemm's rules replayed by hand; the route log on the device is the arbiter).
+# act: 0 none, 1 ELU, 2 ReLU.  Layouts: NN A [M, K] B [K, N]; NT B [N, K]; TN A [K, M].
+GEMM_CASES = (
+    _gemm_case(5, 70, 250, "TN", ("m32-split", 4, 32, 128), _M32),
+    _gemm_case(31, 130, 257, "NT", ("m32-split", 4, 32, 128), _M32, alpha=0.5, bias=True, act=1, ldc=135),     # fill + bias pass on strided rows
+    _gemm_case(32, 129, 1000, "TN", ("m32-split", 15, 32, 128), _M32, beta=1.0),                               # no fill: onto a loaded C
+    _gemm_case(17, 200, 300, "TN", _M32, _M32, alpha=2.0, beta=0.5),
+    _gemm_case(33, 1000, 67, "NT", ("skinny", 1, 48, 16), ("skinny", 1, 48, 16), bias=True, act=1),
+    _gemm_case(450, 200, 250, "NN", ("mid-split", 2, 64, 64), _T64, no_mid=_T64),
+    _gemm_case(449, 193, 251, "NT", ("mid-split", 2, 64, 64), _T64, no_mid=_T64, bias=True, act=2, ldc=197),   # bias pass, ld > N
+    _gemm_case(450, 200, 250, "TN", ("mid-split", 2, 64, 64), _T64, no_mid=_T64, beta=1.0),                    # accumulating
+    _gemm_case(100, 130, 300, "NN", ("mid-split", 3, 64, 64), _T64, no_mid=_T64, nbatch=6, bias=True, act=1),  # batched flat C: bsC = M ldc
+    _gemm_case(512, 256, 270, "NN", ("mid-split", 2, 64, 64), _T64, no_mid=_T64, lda=90),                      # overlapping rows, 3 taps
+    _gemm_case(130, 70, 1266, "NN", _SK128, _T64, no_streamk=("splitk", 5, 128, 128)),
+    _gemm_case(257, 129, 1281, "NT", _SK128, _T64, no_streamk=("splitk", 5, 128, 128), beta=1.0),
+    _gemm_case(300, 128, 1290, "NN", _SK128, _T64, no_streamk=("splitk", 5, 128, 128), lda=430),               # conv_flat's form
+    _gemm_case(130, 70, 1267, "TN", _SK128, _T64, no_streamk=("splitk", 5, 128, 128)),                         # odd K: direct refuses
+    _gemm_case(130, 70, 1266, "TN", ("streamk-direct", 0, 128, 128), _T64, no_streamk=("splitk", 5, 128, 128)),
+    _gemm_case(3072, 2048, 1280, "NN", _SK256, ("half", 1, 128, 64), no_streamk=("splitk", 5, 128, 128), sample=True),
+    _gemm_case(3000, 2049, 1270, "NN", _SK256, ("tile-128x128", 1, 128, 128), no_streamk=("splitk", 5, 128, 128), sample=True),
+    _gemm_case(513, 129, 1262, "NN", ("splitk", 4, 128, 128), _T64, no_streamk=("splitk", 4, 128, 128)),
+    _gemm_case(40, 1000, 1100, "TN", ("splitk", 4, 64, 64), _T64, no_streamk=("splitk", 4, 64, 64)),           # not "big": M <= 64
+    _gemm_case(1000, 40, 1100, "NN", ("splitk", 4, 64, 64), _T64, no_streamk=("splitk", 4, 64, 64)),
+    _gemm_case(2100, 2048, 40, "NT", ("half", 1, 128, 64), ("half", 1, 128, 64), bias=True, act=1),
+    _gemm_case(1030, 1800, 24, "NN", ("tile-128x128", 1, 128, 128), ("tile-128x128", 1, 128, 128), bias=True, act=2),   # ragged edges
+    _gemm_case(200, 70, 33, "NN", _T64, _T64),
+)
+GEMM_ROUTES_COVERED = ("skinny", "m32-split", "m32", "mid-split", "streamk-direct", "streamk-lds-128x128", "streamk-lds-256x128",
+                       "splitk", "half", "tile-128x128", "tile-64x64")
+# THE BOUNDS.  Per case: 4 x the floor, the largest error (gemm_error) of the FLOAT32 evaluation of gemm_oracle -- one running sum
+# over k per element -- against its float64 evaluation, the larger of the two alignment variants' (the two 6-million-element cases:
+# over gemm_sample_rows).  The margin of 4 is for the different but equally long summation orders of the matrix-core k-pairs, the
+# split segments and the atomics.  Floors as tests/test_gemm_oracle_cpu.py::test_float32_floors measures them (it asserts
+# 2 x floor <= bound <= 8 x floor); nothing was taken from the device's output.
+GEMM_FLOORS = {
+    "5x70x250-TN": 1.4e-07,                             # measured 1.34e-07 (aligned) 1.21e-07 (odd)
+    "31x130x257-NT-a0.5-bias-elu-ldc135": 1.8e-07,      # measured 1.74e-07 (aligned) 1.57e-07 (odd)
+    "32x129x1000-TN-b1": 2.1e-07,                       # measured 2.06e-07 (aligned) 2.03e-07 (odd)
+    "17x200x300-TN-a2-b0.5": 2e-07,                     # measured 1.71e-07 (aligned) 1.97e-07 (odd)
+    "33x1000x67-NT-bias-elu": 2.2e-07,                  # measured 2.18e-07 (aligned) 2.08e-07 (odd)
+    "450x200x250-NN": 3.2e-07,                          # measured 3.17e-07 (aligned) 2.6e-07 (odd)
+    "449x193x251-NT-bias-relu-ldc197": 2.6e-07,         # measured 2.5e-07 (aligned) 2.51e-07 (odd)
+    "450x200x250-TN-b1": 2.4e-07,                       # measured 2.14e-07 (aligned) 2.3e-07 (odd)
+    "100x130x300-NN-x6-bias-elu": 3.2e-07,              # measured 2.57e-07 (aligned) 3.16e-07 (odd)
+    "512x256x270-NN-conv90": 3.1e-07,                   # measured 2.98e-07 (aligned) 3.09e-07 (odd)
+    "130x70x1266-NN": 2.6e-07,                          # measured 2.3e-07 (aligned) 2.52e-07 (odd)
+    "257x129x1281-NT-b1": 2.6e-07,                      # measured 2.51e-07 (aligned) 2.21e-07 (odd)
+    "300x128x1290-NN-conv430": 2.9e-07,                 # measured 2.4e-07 (aligned) 2.87e-07 (odd)
+    "130x70x1267-TN": 2.7e-07,                          # measured 1.9e-07 (aligned) 2.6e-07 (odd)
+    "130x70x1266-TN": 2.2e-07,                          # measured 2.13e-07 (aligned) 1.77e-07 (odd)
+    "3072x2048x1280-NN": 3e-07,                         # measured 2.72e-07 (aligned) 2.91e-07 (odd)
+    "3000x2049x1270-NN": 3e-07,                         # measured 2.92e-07 (aligned) 2.51e-07 (odd)
+    "513x129x1262-NN": 2.9e-07,                         # measured 2.81e-07 (aligned) 2.52e-07 (odd)
+    "40x1000x1100-TN": 2.4e-07,                         # measured 2.38e-07 (aligned) 2.13e-07 (odd)
+    "1000x40x1100-NN": 2.5e-07,                         # measured 2.21e-07 (aligned) 2.44e-07 (odd)
+    "2100x2048x40-NT-bias-elu": 4.1e-07,                # measured 4.02e-07 (aligned) 3.4e-07 (odd)
+    "1030x1800x24-NN-bias-relu": 2.9e-07,               # measured 2.84e-07 (aligned) 2.84e-07 (odd)
+    "200x70x33-NN": 2.1e-07,                            # measured 1.95e-07 (aligned) 2.02e-07 (odd)
+}
+GEMM_BOUND = {k: 4.0 * v for k, v in GEMM_FLOORS.items()}
+_GEMM_DATA, _GEMM_TRUTH = {}, {}
+
+
+def gemm_case_id(case):
+    return case["id"]
+
+
+def gemm_sample_rows(case):
+    """the rows the floor of a `sample` case is taken on: every 128-row tile edge with its neighbours, every 64th row, the last"""
+    M = case["M"]
+    rows = {M - 1} | set(range(0, M, 64)) | {r + d for r in range(0, M, 128) for d in (-1, 0, 1)}
+    return torch.as_tensor(sorted(r for r in rows if 0 <= r < M))
+
+
+def _gemm_odd(n, odd):
+    return n if not odd else n + 1 if n % 2 == 0 else n + 2
+
+
+def gemm_case_data(case, variant="aligned"):
+    """The buffers of one comparison, seeded, on the host (cached; leave them unchanged) -> dict: A, B flat float32 buffers with
+    `off` floats in front of the operand, sa = (sam, sak), sb = (sbk, sbn), bs = (bsA, bsB, bsC) in elements, bias [N] or None,
+    C the flat output buffer as the device gets it -- `off` canary floats, nbatch M rows of ldc (the N result columns NaN when
+    beta = 0, else the loaded C0; the padding columns canary), GEMM_CANARY_TAIL canary floats -- ldc, and C0 [nbatch, M, N] or None."""
+    key = (case["id"], variant)
+    if key in _GEMM_DATA:
+        return _GEMM_DATA[key]
+    assert variant in GEMM_VARIANTS, variant
+    odd = variant == "odd"
+    off = 1 if odd else 0
+    M, N, K, nb, lay = case["M"], case["N"], case["K"], case["nbatch"], case["layout"]
+    gen = torch.Generator().manual_seed(9000 + 2 * [c["id"] for c in GEMM_CASES].index(case["id"]) + off)
+    if case["lda"] is not None:
+        assert lay == "NN"
+        lda = case["lda"] + off
+        sa, span_a = (lda, 1), (M - 1) * lda + K
+    elif lay == "TN":
+        lda = _gemm_odd(M, odd)
+        sa, span_a = (1, lda), K * lda
+    else:
+        lda = _gemm_odd(K, odd)
+        sa, span_a = (lda, 1), M * lda
+    if lay == "NT":
+        ldb = _gemm_odd(K, odd)
+        sb, span_b = (1, ldb), N * ldb
+    else:
+        ldb = _gemm_odd(N, odd)
+        sb, span_b = (ldb, 1), K * ldb
+    ldc = case["ldc"] or N
+    A = torch.randn(off + nb * span_a, generator=gen)
+    B = torch.randn(off + nb * span_b, generator=gen)
+    bias = torch.randn(N, generator=gen) if case["bias"] else None
+    C0 = torch.randn(nb, M, N, generator=gen) if case["beta"] != 0.0 else None
+    C = torch.full((off + nb * M * ldc + GEMM_CANARY_TAIL,), GEMM_CANARY)
+    body = C[off:off + nb * M * ldc].view(nb, M, ldc)
+    body[:, :, :N] = C0 if C0 is not None else float("nan")
+    d = dict(A=A, B=B, C=C, C0=C0, bias=bias, off=off, sa=sa, sb=sb, ldc=ldc,
+             bs=(span_a, span_b, M * ldc) if nb > 1 else (0, 0, 0), span=(span_a, span_b))
+    _GEMM_DATA[key] = d
+    return d
+
+
+def gemm_operands(case, variant="aligned", dtype=torch.float64, bug=None):
+    """A [nbatch, M, K], B [nbatch, K, N] as the kernel addresses them in the buffers of gemm_case_data, contiguous in `dtype`"""
+    d = gemm_case_data(case, variant)
+    M, N, K, nb = case["M"], case["N"], case["K"], case["nbatch"]
+    (sam, sak), (sbk, sbn), (span_a, span_b) = d["sa"], d["sb"], d["span"]
+    A = torch.as_strided(d["A"], (nb, M, K), (span_a, sam, sak), d["off"]).to(dtype).contiguous()
+    B = torch.as_strided(d["B"], (nb, K, N), (span_b, sbk, sbn), d["off"]).to(dtype).contiguous()
+    if bug == "conv_no_overlap":        # every tap reads the row's own first lda values: the rows do not reach into the next ones
+        A = A[:, :, torch.arange(K) % sam].contiguous()
+    if bug == "batch_neighbour_A":      # entry 1 reads entry 0's A
+        A[1] = A[0]
+    return A, B
+
+
+def _gemm_segment(case):
+    """the k-range [k0, k1) of the second split segment, as gemm_kernel cuts the 16-wide k-tiles (stream-K: in thirds)"""
+    nkt = (case["K"] + 15) // 16
+    S = case["route"][1] if case["route"][1] > 1 else 3
+    return 16 * (nkt * 1 // S), min(case["K"], 16 * (nkt * 2 // S))
+
+
+def gemm_oracle(case, dtype=torch.float64, variant="aligned", bug=None, rows=None):
+    """act(alpha A B + bias + beta C0) of one case in `dtype` -> [nbatch, M (or len(rows)), N].  float64: the truth (torch.matmul);
+    float32: one running sum over k per element, every product and every sum rounded (the floor).  rows: only these rows of M.
+    bug: one of GEMM_BUGS, a model of one wrong line of the launcher or a kernel (the negative controls)."""
+    assert bug is None or bug in GEMM_BUGS, bug
+    d = gemm_case_data(case, variant)
+    M, N, K = case["M"], case["N"], case["K"]
+    A, B = gemm_operands(case, variant, dtype, bug)
+    sel = torch.arange(M) if rows is None else rows
+    A = A[:, sel].clone()
+    if bug == "last_ktile":
+        A[:, :, 16 * ((K - 1) // 16):] = 0
+    if bug == "k_term":
+        A[:, :, K // 2] = 0
+    if bug == "segment_twice":
+        k0, k1 = _gemm_segment(case)
+        A[:, :, k0:k1] *= 2
+    if dtype == torch.float64:
+        acc = torch.matmul(A, B)
+    else:
+        acc = torch.zeros(A.shape[0], A.shape[1], N, dtype=dtype)
+        for k in range(K):
+            acc += A[:, :, k:k + 1] * B[:, k:k + 1, :]
+    alpha = 1.0 if bug == "alpha_omitted" else case["alpha"]
+    act = (lambda t: t, torch.nn.functional.elu, torch.relu)[case["act"]]
+    v = acc * alpha if alpha != 1.0 else acc
+    bias = None if d["bias"] is None else d["bias"].to(dtype)
+    if bias is not None and bug == "bias_shift":
+        bias = bias.roll(1)
+    if bias is not None and bug != "act_before_bias":
+        v = v + bias
+    if case["beta"] != 0.0:
+        c0 = d["C0"][:, sel].to(dtype) * case["beta"]
+        v = v + c0 + (c0 if bug == "beta_on_partials" else 0)
+    v = act(v)
+    if bias is not None and bug == "act_before_bias":
+        v = v + bias
+    if bug == "edge_row":       # the first row of the last row tile (the last row where there is one tile) holds its upper neighbour's
+        BM = case["route"][2]
+        r = BM * ((M - 1) // BM) if M > BM else M - 1
+        pos = {int(x): i for i, x in enumerate(sel)}
+        v[:, pos[r]] = v[:, pos[r - 1]]
+    return v
+
+
+def gemm_denominator(case, variant="aligned", rows=None):
+    """|alpha| sum_k |a_mk b_kn| + |beta c0_mn| + |bias_n| in float64: what an element's error is measured against"""
+    d = gemm_case_data(case, variant)
+    A, B = gemm_operands(case, variant)
+    if rows is not None:
+        A = A[:, rows]
+    den = abs(case["alpha"]) * torch.matmul(A.abs(), B.abs())
+    if d["bias"] is not None:
+        den = den + d["bias"].double().abs()
+    if case["beta"] != 0.0:
+        den = den + abs(case["beta"]) * (d["C0"] if rows is None else d["C0"][:, rows]).double().abs()
+    return den
+
+
+def gemm_error(got, ref, den):
+    """max over ALL elements of |got - ref| / den (per element: a wrong element of small magnitude cannot hide behind a large one)
+    -> (error, (batch, row, column) where it fell).  A NaN in `got` is an infinite error."""
+    e = (got.double() - ref).abs() / den
+    e = torch.where(torch.isnan(e), torch.full_like(e, float("inf")), e)
+    i = int(e.argmax())
+    return float(e.flatten()[i]), tuple(int(x) for x in np.unravel_index(i, tuple(e.shape)))
+
+
+def gemm_truth(case, variant="aligned"):
+    """(float64 oracle, denominator) over every element, computed once per case and variant"""
+    key = (case["id"], variant)
+    if key not in _GEMM_TRUTH:
+        _GEMM_TRUTH[key] = (gemm_oracle(case, torch.float64, variant), gemm_denominator(case, variant))
+    return _GEMM_TRUTH[key]
+
+
+def gemm_floor(case, variant="aligned"):
+    """what the float32 running sum loses at this case, in the measure of gemm_error (`sample` cases: over gemm_sample_rows)"""
+    rows = gemm_sample_rows(case) if case["sample"] else None
+    ref, den = gemm_oracle(case, torch.float64, variant, rows=rows), gemm_denominator(case, variant, rows)
+    return gemm_error(gemm_oracle(case, torch.float32, variant, rows=rows), ref, den)[0]

@@ -48,6 +48,16 @@ def test_example_rows_for_is_the_dataset_rule(example_len):
                                   ds.example_rows(np.asarray(pos), example_len))
 
 
+def test_example_longer_than_the_data_in_front_of_it_is_refused():
+    """the rule places an example that does not fit into [start, end) so that it ENDS at `end`: longer than `end` frames, it would
+    start before frame 0 -- rows the device gather would read unchecked.  Refused on the host; the longest example that fits passes."""
+    ranges = np.array([[42, 63], [63, 84]])
+    starts, index = evaluate.plan_windows(ranges, W)
+    assert evaluate.example_rows_for(starts, ranges, index, W, 86, 84).min() == 0
+    with pytest.raises(ValueError, match="example_len 88"):
+        evaluate.example_rows_for(starts, ranges, index, W, 88, 84)
+
+
 @pytest.mark.parametrize("world", [1, 2, 3])
 def test_shards_partition_the_batches(world):
     for nb in (0, 1, 2, 7):

@@ -245,6 +245,38 @@ def test_two_ranks_sum_to_the_single_rank_table():
     np.testing.assert_allclose(parts[0] + parts[1], whole, rtol=1e-12, atol=0)
 
 
+def test_evaluate_counts_no_splitting_route_and_the_same_forward_outside_does():
+    """What the two-rank test above rests on, shown not to be vacuous at its shape (window 8, batch 4, example 16): on the calling
+    thread's route log (ops.gemm_route_log) evaluate() launches products, none of them on a route that splits its contraction --
+    and ONE forward of the same networks on a batch of the same shape outside the block does take splitting routes (measured: the
+    mid-split once and the LDS-tiled stream-K kernel twice, in the style encoder), so without the fixed order the scores would
+    carry the atomics' call-to-call rounding.  The shape did not have to be enlarged."""
+    window, batch, L = 8, 4, 16
+    data = synth.make_processed(2, 3, 21, seed=17)
+    se, de, st = nets = _nets()
+    ds = engine.DeviceDataset(data, window, torch.device(DEV))
+    splitting = set(ops.GEMM_SPLITTING_ROUTES)
+    ops.gemm_route_log(reset=True)
+    evaluate.evaluate(*nets, ds, synth.PARENTS, synth.DT, split="valid", batch=batch, example_len=L, iteration=helpers.LOSS_KL_ITERATION)
+    inside = ops.gemm_route_log(reset=True)["counts"]
+    assert sum(inside.values()) > 0 and not splitting & set(inside), inside
+    twin = dict(data)
+    twin["ranges_train"], twin["ranges_train_labels"] = data["ranges_valid"], data["ranges_valid_labels"]
+    tds = engine.DeviceDataset(twin, window, torch.device(DEV))
+    with torch.no_grad():
+        b = tds.batch(np.arange(batch), L, style_encoder=st.encoder)
+        ops.gemm_route_log(reset=True)
+        speech = se(b["audio"])
+        z, _, _ = st(b["example"], 1.0, eps=torch.zeros(batch, 64, device=DEV))
+        ops.decoder_core(de, b["pose0"], b["rpos0"], b["rrot0"], b["gaze"], speech, ops.broadcast_time(z, window), tds.in_mean,
+                         tds.in_std, tds.out_mean, tds.out_std, synth.DT)
+    torch.cuda.synchronize()
+    outside = ops.gemm_route_log(reset=True)["counts"]
+    print(f"\nMEASURED routes inside evaluate(): {inside}; one forward outside: {outside}")
+    assert splitting & set(outside), outside
+    assert ops.lib().zeggs_gemm_fixed_order(0) == 0           # evaluate() left the thread as it found it
+
+
 def test_evaluate_empty_split():
     ds = engine.DeviceDataset(synth.make_processed(2, 0, 21, seed=17), 8, torch.device(DEV))
     res = evaluate.evaluate(*_nets(), ds, synth.PARENTS, synth.DT, batch=4, example_len=16)

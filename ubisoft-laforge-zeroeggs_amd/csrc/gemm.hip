@@ -775,6 +775,18 @@ int launch_tn_direct(const GemmArgs& g, const DirectPlan& p, hipStream_t s) {
 #ifndef ZEGGS_GEMM_SK256
 #define ZEGGS_GEMM_SK256 2      // 2: by output size (default)
 #endif
+// Route log (test hook zeggs_test_gemm_route_log, include/zeggs_hip.h): which route launch_gemm / launch_streamk COMMITTED to for the
+// calling thread's last product, and how many launches each route has had since the last reset.  Plain thread-local integers written
+// where the route is chosen: a handful of stores per product, no lock, no device work, and nothing reads them to decide anything.
+// The numbers are the header's ZEGGS_GEMM_ROUTE_* list (zeggs.ops.GEMM_ROUTES names them in the same order).
+enum GemmRoute { GR_NONE = 0, GR_SKINNY, GR_M32_SPLIT, GR_M32, GR_MID_SPLIT, GR_SK_DIRECT, GR_SK_BF16_SPLIT, GR_SK_DMA, GR_SK_LDS_128,
+                 GR_SK_LDS_256, GR_SPLITK, GR_HALF, GR_TILE_128, GR_TILE_64, GR_COUNT };
+struct GemmRouteLog { int route, splitk, bm, bn; long count[GR_COUNT]; };
+static thread_local GemmRouteLog tl_gemm_log;
+static inline void log_route(int route, int splitk, int bm, int bn) {
+  tl_gemm_log.route = route; tl_gemm_log.splitk = splitk; tl_gemm_log.bm = bm; tl_gemm_log.bn = bn;
+  ++tl_gemm_log.count[route];
+}
 template <int BM, int BN, int WM, int WN>
 int launch_streamk_cfg(GemmArgs g, int ncu, hipStream_t s) {
   const int tx = cdiv(g.N, BN), ty = cdiv(g.M, BM);
@@ -855,22 +867,24 @@ static DirectCheck direct_selftest(const DirectPlan& variant) {
 }
 // asum_taken (may be null): the launch that ran took GemmArgs.asum (only the direct kernel does)
 int launch_streamk(GemmArgs g, hipStream_t s, bool* asum_taken) {
-  if (gemm_split_ok(g)) return launch_tn_split(g, s);
+  if (gemm_split_ok(g)) { log_route(GR_SK_BF16_SPLIT, 0, 256, 128); return launch_tn_split(g, s); }
   const int ncu = device_cus();      // (one query per product, as ever: the plan and the LDS-tiled grid share it)
   const DirectPlan plan = direct_plan(tn_route(), tn_shape(g), ncu, g_gemm_direct_wgs);
   if (plan.use && g_direct_first_use.go(plan, [s] { return stream_capturing(s); }, direct_selftest)) {
     if (asum_taken) *asum_taken = g.asum != nullptr;
+    log_route(GR_SK_DIRECT, 0, plan.big ? 256 : 128, 128);
     return launch_tn_direct(g, plan, s);
   }
-  if (dma_ok(g)) return launch_tn_dma(g, s);
+  if (dma_ok(g)) { log_route(GR_SK_DMA, 0, 128, 128); return launch_tn_dma(g, s); }
   // 256 x 128 tiles (8 waves, 2 workgroups per CU: 3/4 of the operand bytes per product) pay on the big outputs only: +5 .. +8 %
   // on dW_ih0 (432 tiles of 128 x 128), -4 .. -6 % at 72 .. 200 tiles where the coarser grain costs balance
   // (profiles/r03_gemm_ablation.txt); -DZEGGS_GEMM_SK256=0 / 1 forces never / from 512 rows on
 #if ZEGGS_GEMM_SK256 == 1
-  if (g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s);
+  if (g.M >= 512) { log_route(GR_SK_LDS_256, 0, 256, 128); return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s); }
 #elif ZEGGS_GEMM_SK256 != 0
-  if (tn_big_output(g.M, g.N) && g.M >= 512) return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s);
+  if (tn_big_output(g.M, g.N) && g.M >= 512) { log_route(GR_SK_LDS_256, 0, 256, 128); return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s); }
 #endif
+  log_route(GR_SK_LDS_128, 0, 128, 128);
   return launch_streamk_cfg<128, 128, 2, 2>(g, ncu, s);
 }
 
@@ -1058,7 +1072,10 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
   if (g.kbatch <= 0) g.kbatch = 1;
   g.splitk = 1;
   const bool may_split = !t_gemm_fixed_order;
-  if (g_gemm_skinny && skinny_ok(g, nbatch)) return launch_skinny(skinny_args(g), g.sbk == 1 && g.sbn != 1, s);
+  if (g_gemm_skinny && skinny_ok(g, nbatch)) {
+    log_route(GR_SKINNY, 1, 16 * (cdiv(g.M, 16) < 4 ? cdiv(g.M, 16) : 4), 16);
+    return launch_skinny(skinny_args(g), g.sbk == 1 && g.sbn != 1, s);
+  }
   if (g.M <= 32) {
     // batch-sized products (M = B rows against a whole weight matrix: CellStateEncoder, the per-step GEMMs of the
     // generic decoder path): N / 128 workgroups would leave most of the chip idle -> split K over workgroups
@@ -1079,6 +1096,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
           ZLAUNCH_CHECK("gemm_rows_fill");
         }
         g.bias = nullptr; g.act = ACT_NONE; g.splitk = (int)sk;
+        log_route(GR_M32_SPLIT, g.splitk, 32, 128);
         ZTRY((launch_cfg<32, 128, 1, 4>(g, nbatch, s)));
         if (bias || act != ACT_NONE) {
           hipLaunchKernelGGL(rows_bias_act_k, dim3((unsigned)(blocks > 1024 ? 1024 : blocks)), dim3(256), 0, s, g.C, bias, g.M,
@@ -1088,6 +1106,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
         return 0;
       }
     }
+    log_route(GR_M32, 1, 32, 128);
     return launch_cfg<32, 128, 1, 4>(g, nbatch, s);
   }
   const bool big = g.M > 64 && g.N > 64;
@@ -1117,6 +1136,7 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
           ZLAUNCH_CHECK("gemm_rows_fill");
         }
         g.bias = nullptr; g.act = ACT_NONE; g.splitk = (int)sk;
+        log_route(GR_MID_SPLIT, g.splitk, 64, 64);
         ZTRY((launch_cfg<64, 64, 2, 2>(g, nbatch, s)));
         if (bias || act != ACT_NONE) {
           hipLaunchKernelGGL(rows_bias_act_k, dim3((unsigned)(blocks > 2048 ? 2048 : blocks)), dim3(256), 0, s, g.C, bias, rows,
@@ -1145,10 +1165,25 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
   }
   // 1 .. 2 tiles of 128 x 128 per CU and no split (bias / activation epilogue): half the CUs would carry two tiles, the others one;
   // 128 x 64 tiles give every CU the same share (the style encoder's first conv: 384 -> 768 tiles)
-  if (ZEGGS_GEMM_HALF_TILES && big && g.splitk == 1 && tiles > 256 && tiles < 512 && g.N % 64 == 0)
+  if (ZEGGS_GEMM_HALF_TILES && big && g.splitk == 1 && tiles > 256 && tiles < 512 && g.N % 64 == 0) {
+    log_route(GR_HALF, 1, 128, 64);
     return launch_cfg<128, 64, 2, 2>(g, nbatch, s);
-  if (big && (tiles * g.splitk >= 128 || g.splitk > 1)) return launch_cfg<128, 128, 2, 2>(g, nbatch, s);
+  }
+  if (big && (tiles * g.splitk >= 128 || g.splitk > 1)) {
+    log_route(g.splitk > 1 ? GR_SPLITK : GR_TILE_128, g.splitk, 128, 128);
+    return launch_cfg<128, 128, 2, 2>(g, nbatch, s);
+  }
+  log_route(g.splitk > 1 ? GR_SPLITK : GR_TILE_64, g.splitk, 64, 64);
   return launch_cfg<64, 64, 2, 2>(g, nbatch, s);
+}
+
+// test hook (include/zeggs_hip.h): the calling thread's route log.  last4 (may be null): route, splitk, BM, BN of its last product;
+// counts (may be null): ncounts entries, launches per route id since the last reset.  reset != 0 clears the log AFTER it is read.
+extern "C" int zeggs_test_gemm_route_log(int reset, int* last4, long* counts, int ncounts) {
+  if (last4) { last4[0] = tl_gemm_log.route; last4[1] = tl_gemm_log.splitk; last4[2] = tl_gemm_log.bm; last4[3] = tl_gemm_log.bn; }
+  for (int i = 0; counts && i < ncounts; ++i) counts[i] = i < GR_COUNT ? tl_gemm_log.count[i] : 0;
+  if (reset) tl_gemm_log = GemmRouteLog{};
+  return GR_COUNT;
 }
 
 GemmArgs gemm_args(const float* A, const float* B, float* C, int M, int N, int K) {

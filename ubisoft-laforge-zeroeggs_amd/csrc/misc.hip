@@ -22,9 +22,15 @@ namespace {
 // decay = weight_decay * lr (optimizers.py:88-95: p += -weight_decay * lr * p BEFORE the update, only when the step is applied)
 // c1, c2 = the complements 1 - beta1, 1 - beta2 as the CALLER rounded them: the reference passes float(1 - beta) computed in double
 // (0.001f for beta2 = 0.999), while 1.f - 0.999f = 0.00099998713 -- 1.3e-5 relative in v at every step (zeggs_radam_step_c)
+// The first moment is formed in DOUBLE from the caller's double beta1 and 1 - beta1 and rounded once (zeggs_radam_step_d): b1 m and
+// (1 - b1) g cancel wherever a gradient turns against its average, the float32 roundings of the two products and of 0.9f itself are
+// then a multiple of the m that is left, and p -= scale m / ... carries that multiple whole where p is still near zero (zero-
+// initialised biases in the first steps: 13 .. 31 float32 roundings of |p| + |dp| from run to run over the engine's 25.5 M
+// parameters, hundreds on uncorrelated gradients; one rounding of m itself now).  v has no such cancellation and stays in float32.
+// Two conversions and two fp64 operations per element under 28 bytes of traffic: not measurable.
 // 16-byte vector accesses: 16 B read x4 + 12 B written per parameter = the algorithmic 28 B/param.
 __global__ __launch_bounds__(256) void radam_k(float* p, const float* g, float* m, float* v, long n4, long n,
-                                                float b1, float b2, float c1, float c2, float eps, float scale, int rect, float decay,
+                                                double b1, float b2, double c1, float c2, float eps, float scale, int rect, float decay,
                                                 unsigned* status, const float* gflag, int count_skip) {
   // guarded step (zeggs_radam_step_guarded): a persistent sweep of this iteration gave up on this rank (sticky status word) or
   // on another one (gflag: the all-reduced flag) -> the gradients are invalid, the whole step is a no-op and is counted
@@ -37,7 +43,7 @@ __global__ __launch_bounds__(256) void radam_k(float* p, const float* g, float* 
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       vv[k] = vv[k] * b2 + c2 * gv[k] * gv[k];
-      mv[k] = mv[k] * b1 + c1 * gv[k];
+      mv[k] = (float)((double)mv[k] * b1 + c1 * (double)gv[k]);
       if (decay != 0.f) pv[k] += -decay * pv[k];
       pv[k] += rect ? -scale * (mv[k] / (sqrtf(vv[k]) + eps)) : -scale * mv[k];
     }
@@ -47,7 +53,7 @@ __global__ __launch_bounds__(256) void radam_k(float* p, const float* g, float* 
   if (blockIdx.x == 0 && threadIdx.x < (n - n4 * 4)) {
     long i = n4 * 4 + threadIdx.x;
     float vv = v[i] * b2 + c2 * g[i] * g[i];
-    float mv = m[i] * b1 + c1 * g[i];
+    float mv = (float)((double)m[i] * b1 + c1 * (double)g[i]);
     if (decay != 0.f) p[i] += -decay * p[i];
     p[i] += rect ? -scale * (mv / (sqrtf(vv) + eps)) : -scale * mv;
     m[i] = mv; v[i] = vv;
@@ -198,17 +204,23 @@ inline int g1(long n) { long g = (n + 255) / 256; return (int)(g > 8192 ? 8192 :
 
 }  // namespace
 
-extern "C" int zeggs_radam_step_c(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2,
-                                  float comp1, float comp2, float eps, float step_scale, int rectified, float decay,
+extern "C" int zeggs_radam_step_d(float* p, const float* g, float* m, float* v, long n, double beta1, double beta2,
+                                  double comp1, double comp2, float eps, float step_scale, int rectified, float decay,
                                   unsigned* status, const float* gflag, int count_skip, void* stream) {
   ZCHECK(((uintptr_t)p | (uintptr_t)g | (uintptr_t)m | (uintptr_t)v) % 16 == 0, "radam: buffers must be 16-byte aligned");
   if (n <= 0) return 0;
   long n4 = n / 4;
   hipLaunchKernelGGL(radam_k, dim3(g1(n4 > 0 ? n4 : 1)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, n4, n, beta1,
-                     beta2, comp1, comp2, eps, step_scale, rectified, decay, status, status ? gflag : (const float*)nullptr,
+                     (float)beta2, comp1, (float)comp2, eps, step_scale, rectified, decay, status, status ? gflag : (const float*)nullptr,
                      count_skip);
   ZLAUNCH_CHECK("radam");
   return 0;
+}
+extern "C" int zeggs_radam_step_c(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2,
+                                  float comp1, float comp2, float eps, float step_scale, int rectified, float decay,
+                                  unsigned* status, const float* gflag, int count_skip, void* stream) {
+  return zeggs_radam_step_d(p, g, m, v, n, beta1, beta2, comp1, comp2, eps, step_scale, rectified, decay, status, gflag, count_skip,
+                            stream);
 }
 extern "C" int zeggs_radam_step(float* p, const float* g, float* m, float* v, long n, float beta1, float beta2,
                                 float eps, float step_scale, int rectified, void* stream) {

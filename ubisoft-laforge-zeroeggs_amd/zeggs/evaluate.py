@@ -42,6 +42,11 @@ def example_rows_for(starts, ranges, range_index, window, example_len, n_frames)
     cur = end - start
     k = np.arange(example_len)[None, :]
     rows = np.where(k < cur[:, None], start[:, None] + k, end[:, None] - example_len + k)
+    # an example longer than the frames in front of its window's range end would start before frame 0: the gather kernel reads the
+    # rows it is given unchecked (an out-of-bounds read on the device), so it is refused here, on the host, ahead of any launch
+    if rows.size and (rows.min() < 0 or rows.max() >= n_frames):
+        raise ValueError(f"example_len {example_len} reaches outside the dataset's {n_frames} frames (source rows {int(rows.min())} .. "
+                         f"{int(rows.max())}): shorten the style example")
     return rows.astype(np.int64)
 
 

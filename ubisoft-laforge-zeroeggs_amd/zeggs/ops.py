@@ -71,7 +71,8 @@ REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_
                     "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm",
                     "zeggs_mel_window_first_sample", "zeggs_mel_features_window", "zeggs_speech_encoder_live",
                     "zeggs_speech_encoder_live_prepare", "zeggs_speech_encoder_live_workspace_bytes", "zeggs_loss_eval",
-                    "zeggs_loss_eval_workspace_bytes", "zeggs_eval_accumulate", "zeggs_gemm_fixed_order")
+                    "zeggs_loss_eval_workspace_bytes", "zeggs_eval_accumulate", "zeggs_gemm_fixed_order",
+                    "zeggs_test_gemm_route_log", "zeggs_radam_step_d")
 
 
 def lib():
@@ -1312,6 +1313,25 @@ class fixed_order_gemms:
         return False
 
 
+# route ids of zeggs_test_gemm_route_log (include/zeggs_hip.h: ZEGGS_GEMM_ROUTE_*), in the header's order
+GEMM_ROUTES = ("none", "skinny", "m32-split", "m32", "mid-split", "streamk-direct", "streamk-bf16-split", "streamk-dma",
+               "streamk-lds-128x128", "streamk-lds-256x128", "splitk", "half", "tile-128x128", "tile-64x64")
+GEMM_SPLITTING_ROUTES = ("m32-split", "mid-split", "streamk-direct", "streamk-bf16-split", "streamk-dma", "streamk-lds-128x128",
+                         "streamk-lds-256x128", "splitk")       # the routes that combine partial sums with fp32 atomics
+
+
+def gemm_route_log(reset=False):
+    """Test hook: the route log of the calling thread's matrix products (zeggs_test_gemm_route_log) with names instead of numbers ->
+    {"route", "splitk" (1 unsplit, 0 stream-K), "tile": (BM, BN)} of the last product and "counts": {route: launches since the last
+    reset} (routes never taken are left out).  reset: clear the log after reading it."""
+    last, counts = (C.c_int * 4)(), (C.c_long * len(GEMM_ROUTES))()
+    n = lib().zeggs_test_gemm_route_log(int(bool(reset)), last, counts, len(GEMM_ROUTES))
+    if n != len(GEMM_ROUTES):
+        raise RuntimeError(f"zeggs.ops.GEMM_ROUTES names {len(GEMM_ROUTES)} routes, the library has {n}: rebuild it")
+    return {"route": GEMM_ROUTES[last[0]], "splitk": int(last[1]), "tile": (int(last[2]), int(last[3])),
+            "counts": {GEMM_ROUTES[i]: int(c) for i, c in enumerate(counts) if c}}
+
+
 def loss_eval_workspace(B, T, J, S, dt, device):
     """a workspace for loss_eval calls of these dimensions (zeggs_loss_eval_workspace_bytes)"""
     d = LossDims(int(B), int(T), int(J), int(S), float(dt))
@@ -1334,9 +1354,10 @@ def radam_step(p, g, m, v, beta1, beta2, eps, step_scale, rectified, status=None
     persistent sweep of the iteration gave up here (status[0]) or on another rank (gflag, a device float).  A step applied in
     pieces (slices of the flat buffers) counts its skip in ONE of them: count=False for the others.
     decay = weight_decay * lr (reference optimizers.py:88-95), 0 when the step is not applied."""
-    # the complements in double, as the reference forms them: float(1 - 0.999) = 0.001f, while 1.f - 0.999f = 0.00099998713
-    _check(lib().zeggs_radam_step_c(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_float(beta1), C.c_float(beta2),
-                                    C.c_float(1 - beta1), C.c_float(1 - beta2), C.c_float(eps), C.c_float(step_scale),
+    # the complements in double, as the reference forms them: float(1 - 0.999) = 0.001f, while 1.f - 0.999f = 0.00099998713; the
+    # kernel rounds them for the second moment and forms the first moment in double (zeggs_radam_step_d)
+    _check(lib().zeggs_radam_step_d(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_double(beta1), C.c_double(beta2),
+                                    C.c_double(1 - beta1), C.c_double(1 - beta2), C.c_float(eps), C.c_float(step_scale),
                                     int(rectified), C.c_float(decay),
                                     C.c_void_p(status.data_ptr()) if status is not None else None,
                                     _p(gflag) if gflag is not None and status is not None else None, int(bool(count)), _stream()),
