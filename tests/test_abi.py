@@ -229,3 +229,134 @@ def _frame_accounting(L, d, flags):
                 assert 200 * hi + (800 if flags & 1 else 400) <= n, (n, kk, hi)      # its window ends inside the received samples
         assert k <= audio.n_anim_frames(n) + 1
     assert int(L.zeggs_mel_frames_ready(C.byref(d), C.c_long(480000))) >= audio.n_anim_frames(480000) - 3
+
+
+# ----------------------------------------------------------------------------- the binding (zeggs/capi.py) against the header
+_SCALARS = {"int": "int", "long": "long", "size_t": "size_t", "uint64_t": "uint64", "float": "float", "double": "double"}
+_ELEMENTS = {"float": "f32*", "double": "f64*", "int": "i32*", "unsigned": "i32*", "int64_t": "i64*", "long": "i64*",
+             "long long": "i64*", "uint8_t": "u8*", "unsigned char": "u8*", "char": "u8*", "void": "any*"}
+_C_WORDS = {"int", "long", "unsigned", "char", "float", "double", "void", "size_t", "uint64_t", "int64_t", "uint8_t"}
+_CTYPES = {"int": ctypes.c_int, "long": ctypes.c_long, "size_t": ctypes.c_size_t, "uint64_t": ctypes.c_uint64, "float": ctypes.c_float,
+           "double": ctypes.c_double}
+
+
+def _header_text():
+    return re.sub(r"/\*.*?\*/", " ", (ROOT / "include" / "zeggs_hip.h").read_text(), flags=re.S)
+
+
+def _declarator(text):
+    """'const float* x' -> (base type, pointer depth, name or None, array length or None)"""
+    m = re.search(r"\[(\d+)\]\s*$", text)
+    text = text[:m.start()] if m else text
+    depth = text.count("*")
+    words = text.replace("*", " ").replace("const", " ").split()
+    name = words.pop() if len(words) > 1 and words[-1] not in _C_WORDS and not words[-1].startswith("Zeggs") else None
+    return " ".join(words), depth, name, int(m.group(1)) if m else None
+
+
+def _header_prototypes():
+    """{name: (return base type, return pointer depth, [(base type, pointer depth)])} of every zeggs_* function the header declares"""
+    out = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w \*]*?)\b(zeggs_\w+)\s*\(([^()]*)\)\s*;", _header_text()):
+        rbase, rdepth, _, _ = _declarator(ret + " f")
+        plist = [] if params.strip() in ("", "void") else [_declarator(p)[:2] for p in params.split(",")]
+        assert name not in out
+        out[name] = (rbase, rdepth, plist)
+    return out
+
+
+def _header_structs():
+    """{ZeggsX: [(field name, base type, pointer depth, array length or None)]} of every typedef struct of the header"""
+    out = {}
+    for body, name in re.findall(r"typedef\s+struct\s*\{(.*?)\}\s*(Zeggs\w+)\s*;", _header_text(), flags=re.S):
+        fields = []
+        for decl in filter(None, (d.strip() for d in body.split(";"))):
+            first, *more = [p.strip() for p in decl.split(",")]
+            base, depth, fname, n = _declarator(first)
+            fields.append((fname, base, depth, n))
+            for p in more:                       # `float *a, *b` / `int B, T`: every further declarator has its own stars
+                m = re.fullmatch(r"(\**)\s*(\w+)(?:\[(\d+)\])?", p)
+                fields.append((m.group(2), base, len(m.group(1)), int(m.group(3)) if m.group(3) else None))
+        out[name] = fields
+    return out
+
+
+def test_prototype_table_is_the_header():
+    """capi.PROTOTYPES against include/zeggs_hip.h: the same names; per function the return kind, the parameter count, every
+    parameter's kind and every device pointer's element type.  A host pointer or a stream of the table is a pointer in the header."""
+    from zeggs import capi
+    header = _header_prototypes()
+    assert len(header) == 121 and set(header) == set(capi.PROTOTYPES)
+    assert {b for _, _, ps in header.values() for b, depth in ps if depth == 0} == set(_SCALARS)       # no struct by value
+    for name, (rbase, rdepth, params) in header.items():
+        ret, kinds = capi.signature(name)
+        want = {("int", 0): ("status", "mask", "int"), ("long", 0): ("long",), ("size_t", 0): ("size_t",), ("char", 1): ("str",)}
+        assert ret in want[(rbase, rdepth)], (name, ret)
+        assert len(kinds) == len(params), name
+        for i, (kind, (base, depth)) in enumerate(zip(kinds, params)):
+            where = (name, i, kind, base, depth)
+            assert kind in capi.KINDS, where
+            if depth == 0:
+                assert kind == _SCALARS[base], where
+            elif kind == "str":
+                assert (base, depth) == ("char", 1), where
+            elif kind == "stream":
+                assert (base, depth) == ("void", 1), where
+            elif kind == "host*":
+                assert depth >= 1, where
+            elif base.startswith("Zeggs"):
+                assert kind == base + "*" and depth == 1 and base in capi.STRUCTS, where
+            else:
+                assert depth == 1 and kind == _ELEMENTS[base], where
+
+
+def test_struct_mirrors_are_the_header():
+    """every typedef struct of the header has a mirror in capi.STRUCTS with the same field names, order and C types; the pointer
+    records are all pointers, named by their *_FIELDS tuple in order"""
+    from zeggs import capi
+    structs = _header_structs()
+    assert set(structs) == set(capi.STRUCTS) and len(structs) == 21
+    records = {"ZeggsSpeechParams": capi.SPEECH_FIELDS, "ZeggsSpeechGrads": capi.SPEECH_FIELDS, "ZeggsStyleParams": capi.STYLE_FIELDS,
+               "ZeggsStyleGrads": capi.STYLE_FIELDS, "ZeggsStyleGruParams": capi.STYLE_GRU_FIELDS,
+               "ZeggsStyleGruGrads": capi.STYLE_GRU_FIELDS, "ZeggsDecParams": capi.DEC_FIELDS, "ZeggsDecGrads": capi.DEC_FIELDS,
+               "ZeggsDecStats": capi.STATS_FIELDS, "ZeggsAnimOut": capi.ANIM_OUT_FIELDS}
+    for name, fields in structs.items():
+        mirror = capi.STRUCTS[name]._fields_
+        assert [f for f, _ in mirror] == [f for f, _, _, _ in fields], name
+        if name in records:
+            assert tuple(f for f, _ in mirror) == records[name] and all(depth == 1 for _, _, depth, _ in fields), name
+        for (f, ctype), (_, base, depth, n) in zip(mirror, fields):
+            want = ctypes.c_void_p if depth else _CTYPES[base]
+            assert ctype is (want * n if n else want), (name, f)
+    assert all(depth == 0 or name in records or name == "ZeggsDecCall" for name, fs in structs.items() for _, _, depth, _ in fs)
+
+
+def test_typed_handle_host_only_calls():
+    """The typed handle (capi.api()) without a GPU: bare Python ints above 2^31 arrive as the `long` / `size_t` they are, a 3.7 GB
+    size comes back whole, a refused call raises with the function's name and the library's text, a CPU tensor is refused before
+    the library is entered; the raw handle (ops.lib()) is the same dlopen handle with no argument types."""
+    from zeggs import audio, capi
+    api, L = capi.api(), ops.lib()
+    d = audio.MelDims(800, 200, 80, 16000, 60.0, 1e-5, 0.0, 0)
+    for n in (2 ** 31 + 12345, 3 * 2 ** 32 + 7):
+        assert api.zeggs_mel_frames_ready(d, n) == L.zeggs_mel_frames_ready(ctypes.byref(d), ctypes.c_long(n)) > 2 ** 31 // 400
+        k = n // 300
+        assert api.zeggs_mel_window_first_sample(d, k) == L.zeggs_mel_window_first_sample(ctypes.byref(d), ctypes.c_long(k)) > 2 ** 31 // 2
+        assert api.zeggs_table_text_workspace_bytes(n, 7) == L.zeggs_table_text_workspace_bytes(ctypes.c_long(n), 7) > 2 ** 31
+    dd = ops.DecDims(1, 1801, synth.POSE_IN, synth.POSE_OUT, 64, 64, 1024, synth.DT)
+    assert api.zeggs_decoder_workspace_bytes(dd, 1) == _WORKSPACE_BYTES[(1, 1801, 64, 1024, 0)][1] == 3748302080
+    with pytest.raises(RuntimeError, match=r"^zeggs_set_option: .*no_such_option"):
+        api.zeggs_set_option(b"no_such_option", 1)
+    assert L.zeggs_set_option(b"no_such_option", 1) != 0
+    with pytest.raises(RuntimeError, match="zeggs_fill: .*not on a GPU"):
+        api.zeggs_fill(torch.zeros(4), 4, 0.0, None)
+    f32 = capi.KINDS["f32*"]
+    with pytest.raises(RuntimeError, match="not on a GPU"):          # the GPU refusal comes before the dtype check
+        f32.from_param(torch.zeros(4, dtype=torch.float64))
+    assert f32.from_param(None) is None
+    f32.from_param(ctypes.c_void_p(64)), f32.from_param(64)         # an address passes as it is
+    with pytest.raises(TypeError):
+        f32.from_param(1.5)
+    assert L.zeggs_fill.argtypes is None and api.zeggs_fill.argtypes is not None
+    assert L._handle == api._handle
+    assert L.zeggs_decoder_workspace_bytes.restype is ctypes.c_size_t and L.zeggs_last_error.restype is ctypes.c_char_p

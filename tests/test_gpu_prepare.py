@@ -135,10 +135,12 @@ def test_spline_long_audio_table_and_short_table_error():
     check_spline(100000, 1, long_reference)
     with pytest.raises(ValueError):
         dp.spline_resample(g(table(3, 1, 0)), 5)
-    L = dp._lib()                                    # the C entry refuses it too
+    from zeggs import ops
+    L = ops.lib()                                    # the C entry refuses it too
     y, out, ws = g(table(3, 2, 0)), torch.empty(5, 2, dtype=torch.float64, device=DEV), torch.empty(4096, dtype=torch.uint8, device=DEV)
     import ctypes
-    assert L.zeggs_spline_resample(dp._ptr(y), ctypes.c_long(3), 2, ctypes.c_long(5), dp._ptr(out), dp._ptr(ws), ctypes.c_size_t(4096), None) != 0
+    ptr = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
+    assert L.zeggs_spline_resample(ptr(y), ctypes.c_long(3), 2, ctypes.c_long(5), ptr(out), ptr(ws), ctypes.c_size_t(4096), None) != 0
     assert b"4 rows" in L.zeggs_last_error()
 
 

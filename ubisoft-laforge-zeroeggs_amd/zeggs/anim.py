@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import ops
+from .capi import ANIM_OUT_FIELDS, AnimDims, AnimOut, BvhDims, api  # noqa: F401
 
 _CHAN = {"Xrotation": "x", "Yrotation": "y", "Zrotation": "z"}
 _CHAN_INV = {v: k for k, v in _CHAN.items()}
@@ -77,9 +78,11 @@ def bvh_load(filename):
     if nframes > 0 and ncols > 0 and off < len(raw):
         out = np.empty((nframes, ncols), dtype=np.float64)
         base = C.cast(C.c_char_p(raw), C.c_void_p).value
-        if ops.lib().zeggs_parse_table_text(C.c_void_p(base + off), C.c_size_t(len(raw) - off), out.ctypes.data_as(C.c_void_p),
-                                            C.c_long(nframes), int(ncols)) == 0:
+        try:
+            api().zeggs_parse_table_text(base + off, len(raw) - off, out.ctypes.data, nframes, int(ncols))
             data = out
+        except RuntimeError:
+            pass
     body = None
     if data is None:
         rows = [ln for ln in raw[off:].decode().splitlines() if ln.strip()][:nframes]
@@ -179,10 +182,10 @@ def bvh_save(filename, data, text=None):
     # the motion block is formatted by the library's host helper (same correctly-rounded "%f" as numpy.savetxt gives, ten
     # times faster: a 30-minute clip is 24.6 M numbers)
     table = np.ascontiguousarray(table, dtype=np.float64)
-    rc = ops.lib().zeggs_write_table_text(str(filename).encode(), 1, table.ctypes.data_as(C.c_void_p), C.c_long(table.shape[0]),
-                                          int(table.shape[1]))
-    if rc != 0:      # as np.savetxt / open() would: an OSError, which generate_gesture() reports and survives (generate.py:407)
-        raise OSError("zeggs_write_table_text: " + ops.lib().zeggs_last_error().decode())
+    try:
+        api().zeggs_write_table_text(str(filename).encode(), 1, table.ctypes.data, table.shape[0], int(table.shape[1]))
+    except RuntimeError as e:      # as np.savetxt / open() would: an OSError, which generate_gesture() reports and survives (generate.py:407)
+        raise OSError(str(e)) from None
 
 
 def format_rows(table, any_magnitude=False):
@@ -193,10 +196,8 @@ def format_rows(table, any_magnitude=False):
     cap = rows * (cols * (330 if any_magnitude else 24) + 1) + 400
     buf = C.create_string_buffer(cap)
     n = C.c_size_t(0)
-    ptr = table.ctypes.data_as(C.c_void_p) if isinstance(table, np.ndarray) else C.c_void_p(table.data_ptr())
-    rc = ops.lib().zeggs_format_table_text(ptr, C.c_long(rows), int(cols), buf, C.c_size_t(cap), C.byref(n))
-    if rc != 0:
-        raise RuntimeError("zeggs_format_table_text: " + ops.lib().zeggs_last_error().decode())
+    ptr = table.ctypes.data if isinstance(table, np.ndarray) else table.data_ptr()          # (host memory either way)
+    api().zeggs_format_table_text(ptr, rows, int(cols), buf, cap, C.byref(n))
     return buf.raw[:n.value]
 
 
@@ -210,19 +211,13 @@ def table_text_device(table, cap=None):
     rows, cols = table.shape
     if rows == 0 or cols == 0:
         raise ValueError("table_text_device: empty table")
-    L = ops.lib()
-    L.zeggs_table_text_workspace_bytes.restype = C.c_size_t
+    L = api()
     cap = rows * (cols * 24 + 1) if cap is None else int(cap)
     text = torch.empty(cap, dtype=torch.uint8, device=table.device)
     meta = torch.empty(rows + 1, dtype=torch.int64, device=table.device)
     meta[rows:].zero_()
-    nws = int(L.zeggs_table_text_workspace_bytes(C.c_long(rows), int(cols)))
-    ws = torch.empty(nws, dtype=torch.uint8, device=table.device)      # (stream-ordered: may go back to the allocator on return)
-    rc = L.zeggs_table_text_device(C.c_void_p(table.data_ptr()), C.c_long(rows), int(cols), C.c_void_p(text.data_ptr()),
-                                   C.c_size_t(cap), C.c_void_p(meta.data_ptr()), C.c_void_p(meta[rows:].data_ptr()),
-                                   C.c_void_p(ws.data_ptr()), C.c_size_t(nws), _stream())
-    if rc != 0:
-        raise RuntimeError("zeggs_table_text_device: " + L.zeggs_last_error().decode())
+    ws = ops._ws(L.zeggs_table_text_workspace_bytes(rows, int(cols)), table.device)      # (stream-ordered: may go back to the allocator on return)
+    L.zeggs_table_text_device(table, rows, int(cols), text, cap, meta, meta[rows:].view(torch.int32), ws, ws.numel(), ops._stream())
     return text, meta
 
 
@@ -262,11 +257,6 @@ def format_rows_device(table, cuts=None):
 
 
 # ----------------------------------------------------------------------------- device kernels (csrc/anim.hip)
-class AnimDims(C.Structure):       # mirrors ZeggsAnimDims
-    _fields_ = [("N", C.c_int), ("J", C.c_int), ("hips", C.c_int), ("spine2", C.c_int), ("head", C.c_int),
-                ("dt", C.c_double), ("order", C.c_int)]
-
-
 def order_code(order):
     """'zyx' -> the packed channel order of ZeggsAnimDims / ZeggsBvhDims (axis of channel i in bits 2i..2i+1)"""
     if sorted(order) != ["x", "y", "z"]:
@@ -280,16 +270,7 @@ ANIM_OUT = (("root_pos", 3, torch.float64), ("root_rot", 4, torch.float64), ("ro
             ("cpos", -3, torch.float64), ("crot", -4, torch.float64), ("cvel", -3, torch.float64),
             ("cvrt", -3, torch.float64), ("ctxy", -6, torch.float32), ("gaze_pos", 3, torch.float64),
             ("gaze_dir", 3, torch.float64))
-AnimOut = type("AnimOut", (C.Structure,), {"_fields_": [(n, C.c_void_p) for n, _, _ in ANIM_OUT]})   # ZeggsAnimOut
-
-
-class BvhDims(C.Structure):        # mirrors ZeggsBvhDims
-    _fields_ = [("T", C.c_int), ("J", C.c_int), ("rebase", C.c_int), ("start_pos", C.c_double * 3),
-                ("start_rot", C.c_double * 4), ("order", C.c_int)]
-
-
-def _stream():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
+assert tuple(n for n, _, _ in ANIM_OUT) == ANIM_OUT_FIELDS      # (the record itself: capi.AnimOut)
 
 
 def preprocess_animation(anim, device=None):
@@ -311,19 +292,14 @@ def preprocess_animation_device(rot, pos, parents, names, frametime, order):
     N, J = rot.shape[0], rot.shape[1]
     d = AnimDims(N, J, names.index("Hips"), names.index("Spine2"), names.index("Head"), float(frametime),
                  order_code(order))      # any channel order (quat.from_euler takes any)
-    L = ops.lib()
-    L.zeggs_anim_features_workspace_bytes.restype = C.c_size_t
-    ws = torch.empty(int(L.zeggs_anim_features_workspace_bytes(C.byref(d))), dtype=torch.uint8, device=device)
+    L = api()
+    ws = ops._ws(L.zeggs_anim_features_workspace_bytes(d), device)
     out, ptr = {}, AnimOut()
     for n, w, dt in ANIM_OUT:
         shape = (N, w) if w > 0 else ((N, J, 2, 3) if w == -6 else (N, J, -w))
         out[n] = torch.empty(shape, dtype=dt, device=device)
         setattr(ptr, n, out[n].data_ptr())
-    rc = L.zeggs_anim_features(C.byref(d), C.c_void_p(parents.data_ptr()), C.c_void_p(rot.data_ptr()),
-                               C.c_void_p(pos.data_ptr()), C.byref(ptr), C.c_void_p(ws.data_ptr()),
-                               C.c_size_t(ws.numel()), _stream())
-    if rc != 0:
-        raise RuntimeError("zeggs_anim_features: " + L.zeggs_last_error().decode())
+    L.zeggs_anim_features(d, parents, rot, pos, ptr, ws, ws.numel(), ops._stream())
     order = ("root_pos", "root_rot", "root_vel", "root_vrt", "lpos", "lrot", "ltxy", "lvel", "lvrt", "cpos", "crot",
              "ctxy", "cvel", "cvrt", "gaze_pos", "gaze_dir")
     return tuple(out[k] for k in order)
@@ -349,12 +325,7 @@ def bvh_channels(root_pos, root_rot, lpos, ltxy, start_position=None, start_rota
     root_pos, root_rot, lpos, ltxy = f(root_pos), f(root_rot), f(lpos), f(ltxy)
     positions = torch.empty(T, J, 3, dtype=torch.float64, device=lpos.device)
     euler = torch.empty(T, J, 3, dtype=torch.float64, device=lpos.device)
-    L = ops.lib()
-    rc = L.zeggs_pose_to_bvh(C.byref(d), C.c_void_p(root_pos.data_ptr()), C.c_void_p(root_rot.data_ptr()),
-                             C.c_void_p(lpos.data_ptr()), C.c_void_p(ltxy.data_ptr()),
-                             C.c_void_p(positions.data_ptr()), C.c_void_p(euler.data_ptr()), _stream())
-    if rc != 0:
-        raise RuntimeError("zeggs_pose_to_bvh: " + L.zeggs_last_error().decode())
+    api().zeggs_pose_to_bvh(d, root_pos, root_rot, lpos, ltxy, positions, euler, ops._stream())
     return positions, euler
 
 

@@ -11,11 +11,7 @@ import numpy as np
 import torch
 
 from . import ops
-
-
-class MelDims(C.Structure):
-    _fields_ = [("n_fft", C.c_int), ("hop", C.c_int), ("n_mels", C.c_int), ("fs", C.c_int), ("fps", C.c_float),
-                ("min_clip", C.c_float), ("pre_emph", C.c_double), ("flags", C.c_int)]
+from .capi import MelDims, api  # noqa: F401
 
 
 RESAMPLE_FLAGS = {"linear": 0, "nearest": 4, "cubic": 8}
@@ -85,23 +81,16 @@ def mel_features(wav, n_frames, n_fft=800, hop=200, n_mels=80, fs=16000, fps=60.
     w = torch.as_tensor(np.asarray(wav, dtype=np.float32) if not torch.is_tensor(wav) else wav,
                         dtype=torch.float32).to(dev).contiguous()
     d = MelDims(n_fft, hop, n_mels, fs, float(fps), float(min_clip), float(pre_emph), mel_flags(centered, normalize_range, resample_method))
-    L = ops.lib()
-    L.zeggs_mel_workspace_bytes.restype = C.c_size_t
-    ws = torch.empty(int(L.zeggs_mel_workspace_bytes(C.byref(d), C.c_long(w.numel()))), dtype=torch.uint8, device=dev)
+    L = api()
+    ws = ops._ws(L.zeggs_mel_workspace_bytes(d, w.numel()), dev)
     out = torch.empty(n_frames, n_mels + 1, device=dev, dtype=torch.float32)
-    rc = L.zeggs_mel_features(C.byref(d), C.c_void_p(w.data_ptr()), C.c_long(w.numel()), C.c_void_p(fb.data_ptr()),
-                              int(n_frames), C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()),
-                              C.c_size_t(ws.numel()), C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError("zeggs_mel_features: " + L.zeggs_last_error().decode())
+    L.zeggs_mel_features(d, w, w.numel(), fb, int(n_frames), out, ws, ws.numel(), ops._stream())
     return out
 
 
 def stft_frame_count(n_samples, n_fft=800, hop=200):
     d = MelDims(n_fft, hop, 80, 16000, 60.0, 1e-5, 0.0, 0)
-    L = ops.lib()
-    L.zeggs_mel_stft_frames.restype = C.c_long
-    return int(L.zeggs_mel_stft_frames(C.byref(d), C.c_long(n_samples)))
+    return api().zeggs_mel_stft_frames(d, n_samples)
 
 
 # ----------------------------------------------------------------------------- BS.1770 loudness (host, O(n))
@@ -220,18 +209,13 @@ def normalize_loudness_device(wav, rate, target=-20.0, device="cuda", chunk=4096
         coef += [b[0], b[1], b[2], a[1], a[2]]
         trans += list(np.linalg.matrix_power(np.array([[-a[1], 1.0], [-a[2], 0.0]]), int(chunk)).ravel())
     coef, trans = (C.c_double * 10)(*coef), (C.c_double * 8)(*trans)
-    L = ops.lib()
-    L.zeggs_loudness_workspace_bytes.restype = C.c_size_t
-    ws = torch.empty(int(L.zeggs_loudness_workspace_bytes(C.c_long(n), int(nblocks), C.c_long(chunk))), dtype=torch.uint8, device=dev)
+    L = api()
+    ws = ops._ws(L.zeggs_loudness_workspace_bytes(n, int(nblocks), chunk), dev)
     lo_d, hi_d = torch.as_tensor(lo).to(dev), torch.as_tensor(hi).to(dev)
     res = torch.empty(2, dtype=torch.float64, device=dev)
     gain = torch.empty(1, dtype=torch.float32, device=dev)
-    ptr = lambda t: C.c_void_p(t.data_ptr())  # noqa: E731
-    rc = L.zeggs_loudness_gain(ptr(w), C.c_long(n), int(rate), C.c_double(target), coef, trans, C.c_long(chunk), ptr(lo_d),
-                               ptr(hi_d), int(nblocks), int(bool(f32)), ptr(res), ptr(gain), ptr(ws), C.c_size_t(ws.numel()),
-                               C.c_void_p(torch.cuda.current_stream().cuda_stream))
-    if rc != 0:
-        raise RuntimeError("zeggs_loudness_gain: " + L.zeggs_last_error().decode())
+    L.zeggs_loudness_gain(w, n, int(rate), target, coef, trans, chunk, lo_d, hi_d, int(nblocks), int(bool(f32)), res, gain, ws,
+                          ws.numel(), ops._stream())
     lufs = float(res[0])
     if not np.isfinite(lufs):
         raise ValueError(f"integrated loudness is not finite ({lufs}): the signal is silent under the -70 LUFS gate")

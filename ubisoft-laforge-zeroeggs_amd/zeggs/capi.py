@@ -1,0 +1,342 @@
+"""The one ctypes binding of libzeggs_hip.so (C ABI: include/zeggs_hip.h): the mirrors of the header's structs, one prototype row
+per function, and the two handles of the library.
+
+  api()   the TYPED handle the package calls: `argtypes` and `restype` of every row are set when the library is loaded, a status
+          return other than 0 raises RuntimeError("<function>: <zeggs_last_error()>"), and a device-pointer parameter takes a
+          tensor (checked: on a GPU, contiguous, the element type of the header) or None -- call sites pass tensors and plain
+          Python numbers.
+  raw()   a second CDLL of the same file with the rows' `restype` only: no `argtypes`, no error check.  What ops.lib() returns;
+          tests, tools and the benchmark call it with hand-wrapped arguments and look at the return codes themselves.  Both
+          handles share the dlopen handle, and so every global of the library.
+
+A new entry point is a declaration in the header plus one row in PROTOTYPES (tests/test_abi.py compares the two).  torch is
+imported when a tensor is first converted, not when this module is.
+"""
+import ctypes as C
+import os
+import threading
+from pathlib import Path
+
+LIB_PATH = Path(os.environ.get("ZEGGS_LIB") or Path(__file__).resolve().parent / "libzeggs_hip.so")   # ZEGGS_LIB: A/B builds
+OPTIONS = {}             # switches set through ops.set_option / ZEGGS_OPTIONS (the library's defaults otherwise)
+
+
+class HipLibraryMissing(RuntimeError):
+    pass
+
+
+# ----------------------------------------------------------------------------- structs (mirror zeggs_hip.h)
+def _struct(name, fields):
+    return type(name, (C.Structure,), {"_fields_": [(f, t) for t, names in fields for f in names.split()]})
+
+
+def _ptr_struct(name, fields):
+    return type(name, (C.Structure,), {"_fields_": [(f, C.c_void_p) for f in fields]})
+
+
+SpeechDims = _struct("SpeechDims", [(C.c_int, "B T F H O KW"), (C.c_float, "dropout_p"), (C.c_uint64, "seed")])
+LiveDims = _struct("LiveDims", [(C.c_int, "R F H O KW D feat_ld out_ld")])
+LiveRow = _struct("LiveRow", [(C.c_long, "n_ring k0 last"), (C.c_int, "n_new n_out feat_off reserved")])
+StyleDims = _struct("StyleDims", [(C.c_int, "B L C H E NH dropout"), (C.c_uint64, "seed")])
+StyleGruDims = _struct("StyleGruDims", [(C.c_int, "B L C H O")])
+DecDims = _struct("DecDims", [(C.c_int, "B T PI PO SP ST H"), (C.c_float, "dt"), (C.c_int, "film")])
+# the per-call controls of zeggs_decoder_fwd_ex / _bwd_ex
+DecCall = _struct("DecCall", [(C.c_int, "prepared defer_wgrads"), (C.c_void_p, "wgrad_stream status"), (C.c_int, "grads_zeroed")])
+LossDims = _struct("LossDims", [(C.c_int, "B T J S"), (C.c_float, "dt")])
+MelDims = _struct("MelDims", [(C.c_int, "n_fft hop n_mels fs"), (C.c_float, "fps min_clip"), (C.c_double, "pre_emph"), (C.c_int, "flags")])
+AnimDims = _struct("AnimDims", [(C.c_int, "N J hips spine2 head"), (C.c_double, "dt"), (C.c_int, "order")])
+BvhDims = _struct("BvhDims", [(C.c_int, "T J rebase"), (C.c_double * 3, "start_pos"), (C.c_double * 4, "start_rot"), (C.c_int, "order")])
+
+SPEECH_FIELDS = ("w0", "b0", "w1", "b1", "w2", "b2")
+STYLE_FIELDS = ("c0_w", "c0_b", "ln0_g", "ln0_b", "c4_w", "c4_b", "ln1_g", "ln1_b", "in_w", "in_b", "out_w", "out_b",
+                "lna_g", "lna_b", "ff0_w", "ff0_b", "ff2_w", "ff2_b", "lnf_g", "lnf_b")
+STYLE_GRU_FIELDS = ("c0_w", "c0_b", "c2_w", "c2_b", "w_ih", "w_hh", "b_ih", "b_hh", "w_ih_r", "w_hh_r", "b_ih_r",
+                    "b_hh_r", "p_w", "p_b")
+DEC_FIELDS = ("l0_w", "l0_b", "w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "l2_w", "l2_b",
+              "c0_w", "c0_b", "c1_w", "c1_b", "c2_w", "c2_b",
+              "l3_w", "l3_b", "g_w", "g_b", "be_w", "be_b")          # last six: rnn_cond "film" only (else NULL)
+STATS_FIELDS = ("in_mean", "in_std", "out_mean", "out_std")
+ANIM_OUT_FIELDS = ("root_pos", "root_rot", "root_vel", "root_vrt", "lpos", "lrot", "lvel", "lvrt", "ltxy", "cpos", "crot", "cvel",
+                   "cvrt", "ctxy", "gaze_pos", "gaze_dir")
+SpeechPtrs = _ptr_struct("SpeechPtrs", SPEECH_FIELDS)
+StylePtrs = _ptr_struct("StylePtrs", STYLE_FIELDS)
+StyleGruPtrs = _ptr_struct("StyleGruPtrs", STYLE_GRU_FIELDS)
+DecPtrs = _ptr_struct("DecPtrs", DEC_FIELDS)
+DecStats = _ptr_struct("DecStats", STATS_FIELDS)
+AnimOut = _ptr_struct("AnimOut", ANIM_OUT_FIELDS)
+
+# header struct -> its mirror (a parameter record and its gradient record share one)
+STRUCTS = {
+    "ZeggsSpeechDims": SpeechDims, "ZeggsSpeechParams": SpeechPtrs, "ZeggsSpeechGrads": SpeechPtrs, "ZeggsLiveDims": LiveDims,
+    "ZeggsLiveRow": LiveRow, "ZeggsStyleDims": StyleDims, "ZeggsStyleParams": StylePtrs, "ZeggsStyleGrads": StylePtrs,
+    "ZeggsStyleGruDims": StyleGruDims, "ZeggsStyleGruParams": StyleGruPtrs, "ZeggsStyleGruGrads": StyleGruPtrs,
+    "ZeggsDecDims": DecDims, "ZeggsDecParams": DecPtrs, "ZeggsDecGrads": DecPtrs, "ZeggsDecStats": DecStats, "ZeggsDecCall": DecCall,
+    "ZeggsLossDims": LossDims, "ZeggsMelDims": MelDims, "ZeggsAnimDims": AnimDims, "ZeggsAnimOut": AnimOut, "ZeggsBvhDims": BvhDims,
+}
+
+# ----------------------------------------------------------------------------- prototypes
+# One row per function of the header: "<return>: <parameter> <parameter> ...".
+#   return     status (an int, 0 = success: anything else raises with zeggs_last_error) | mask (an int >= 0, a negative one raises
+#              alike) | int | long | size_t | str (as they are)
+#   parameter  int long size_t uint64 float double | str (C string) | ZeggsX* (pointer to that struct; an instance is passed by
+#              reference, an array as it is) | f32* f64* i32* i64* u8* any* (DEVICE pointer with the header's element type: float,
+#              double, int / unsigned, int64_t / long / long long, uint8_t / unsigned char / char (uint8 or bool tensors), void) |
+#              host* (a pointer the library reads or writes on the HOST: ctypes arrays, byref() of an out-parameter, an address) |
+#              stream (a hipStream_t as void*)
+PROTOTYPES = {
+    "zeggs_version": "int:",
+    "zeggs_last_error": "str:",
+    "zeggs_set_option": "status: str int",
+    "zeggs_timing_ms": "status: int host*",
+    "zeggs_gemm": "status: f32* f32* f32* f32* int int int long long long long long long int long long long float float int stream",
+    "zeggs_gemm_tn_bias": "status: f32* long f32* long f32* long int int int float f32* stream",
+    "zeggs_gemm_direct_selftest": "int: int int int",
+    "zeggs_gemm_direct_state": "int: int int int",
+    "zeggs_gemm_direct_warm": "status:",
+    "zeggs_gemm_route": "status: int int int int",
+    "zeggs_gemm_route_get": "status: host*",
+    "zeggs_gemm_kbatch": "status: f32* f32* f32* int int int long long long long long long int long long float stream",
+    "zeggs_speech_encoder_workspace_bytes": "size_t: ZeggsSpeechDims*",
+    "zeggs_speech_encoder_fwd": "status: ZeggsSpeechDims* ZeggsSpeechParams* f32* f32* any* size_t stream",
+    "zeggs_speech_encoder_bwd": "status: ZeggsSpeechDims* ZeggsSpeechParams* f32* f32* f32* ZeggsSpeechGrads* any* size_t stream",
+    "zeggs_speech_encoder_bwd_ex": "status: ZeggsSpeechDims* ZeggsSpeechParams* f32* f32* f32* ZeggsSpeechGrads* any* size_t stream int",
+    "zeggs_speech_encoder_live_workspace_bytes": "size_t: ZeggsLiveDims*",
+    "zeggs_speech_encoder_live_prepare": "status: ZeggsLiveDims* ZeggsSpeechParams* any* size_t stream",
+    # rows: a HOST array of ZeggsLiveRow
+    "zeggs_speech_encoder_live": "status: ZeggsLiveDims* ZeggsSpeechParams* f32* f32* ZeggsLiveRow* f32* f32* f32* any* size_t stream",
+    "zeggs_style_encoder_workspace_bytes": "size_t: ZeggsStyleDims*",
+    "zeggs_style_encoder_fwd": "status: ZeggsStyleDims* ZeggsStyleParams* f32* f32* f32* any* size_t stream",
+    "zeggs_style_encoder_fwd_part": "status: ZeggsStyleDims* ZeggsStyleParams* f32* f32* f32* any* size_t stream int",
+    "zeggs_style_encoder_input_offset": "size_t: ZeggsStyleDims*",
+    "zeggs_style_encoder_bwd": "status: ZeggsStyleDims* ZeggsStyleParams* f32* ZeggsStyleGrads* any* size_t stream",
+    "zeggs_style_encoder_bwd_ex": "status: ZeggsStyleDims* ZeggsStyleParams* f32* ZeggsStyleGrads* any* size_t stream int",
+    "zeggs_style_encoder_bwd_part": "status: ZeggsStyleDims* ZeggsStyleParams* f32* ZeggsStyleGrads* any* size_t stream int int",
+    "zeggs_style_encoder_gru_workspace_bytes": "size_t: ZeggsStyleGruDims*",
+    "zeggs_style_encoder_gru_fwd": "status: ZeggsStyleGruDims* ZeggsStyleGruParams* f32* f32* any* size_t stream",
+    "zeggs_style_encoder_gru_bwd": "status: ZeggsStyleGruDims* ZeggsStyleGruParams* f32* ZeggsStyleGruGrads* any* size_t stream",
+    "zeggs_vae_reparam_fwd": "status: f32* f32* f32* f32* f32* int int float stream",
+    "zeggs_vae_reparam_bwd": "status: f32* f32* f32* f32* f32* f32* int int float stream",
+    "zeggs_decoder_workspace_bytes": "size_t: ZeggsDecDims* int",
+    "zeggs_decoder_fwd": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* f32* f32* int any* "
+                         "size_t stream",
+    "zeggs_decoder_fwd_state": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* "
+                               "f32* any* size_t stream",
+    "zeggs_persistent_state": "int: int",
+    "zeggs_tp_stamps": "status: ZeggsDecDims* any* size_t host*",
+    "zeggs_tp_waits": "status: ZeggsDecDims* any* size_t host*",
+    "zeggs_tp_dual_stamps": "status: ZeggsDecDims* any* size_t host*",
+    "zeggs_bp_stamps": "status: ZeggsDecDims* any* size_t host*",
+    "zeggs_bp_waits": "status: ZeggsDecDims* any* size_t host*",
+    "zeggs_decoder_chain_errors": "status: ZeggsDecDims* int any* size_t host*",
+    "zeggs_decoder_chain_stamps": "status: ZeggsDecDims* int any* size_t host*",
+    "zeggs_decoder_bwd": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* ZeggsDecGrads* f32* "
+                         "f32* any* size_t stream",
+    "zeggs_decoder_fwd_ex": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* f32* f32* int any* "
+                            "size_t stream ZeggsDecCall*",
+    "zeggs_decoder_bwd_ex": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* ZeggsDecGrads* f32* "
+                            "f32* any* size_t stream ZeggsDecCall*",
+    "zeggs_decoder_fwd_state_ex": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* f32* f32* "
+                                  "f32* f32* any* size_t stream ZeggsDecCall*",
+    "zeggs_decoder_batch_workspace_bytes": "size_t: ZeggsDecDims*",
+    "zeggs_decoder_batch_prepare": "mask: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* any* size_t stream",
+    "zeggs_decoder_state_init": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* any* size_t stream",
+    "zeggs_decoder_fwd_batch": "status: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* "
+                               "f32* any* size_t stream ZeggsDecCall* int",
+    "zeggs_decoder_batch_last_path": "int:",
+    "zeggs_decoder_wgrads": "status: ZeggsDecDims* ZeggsDecGrads* any* size_t int stream",
+    "zeggs_decoder_prepare": "mask: ZeggsDecDims* ZeggsDecParams* ZeggsDecStats* any* size_t stream",
+    "zeggs_side_stream": "status: host*",
+    "zeggs_loss_workspace_bytes": "size_t: ZeggsLossDims*",
+    "zeggs_loss_fwd_bwd": "status: ZeggsLossDims* i32* f32* f32* f32* f32* f32* f32* f32* f32* f32* float f32* f32* f32* f32* f32* f32* "
+                          "float any* size_t stream",
+    "zeggs_loss_prepare_truth": "status: ZeggsLossDims* i32* f32* f32* f32* f32* any* size_t stream",
+    "zeggs_loss_fwd_bwd_ex": "status: ZeggsLossDims* i32* f32* f32* f32* f32* f32* f32* f32* f32* f32* float f32* f32* f32* f32* f32* "
+                             "f32* float any* size_t stream int",
+    "zeggs_loss_eval_workspace_bytes": "size_t: ZeggsLossDims*",
+    "zeggs_loss_eval": "status: ZeggsLossDims* i32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f64* any* size_t stream",
+    "zeggs_eval_accumulate": "status: f64* i32* int int f64* stream",
+    "zeggs_gemm_fixed_order": "int: int",                                                                       # the previous setting
+    "zeggs_test_gemm_route_log": "int: int host* host* int",                                                    # the number of route ids
+    "zeggs_radam_step": "status: f32* f32* f32* f32* long float float float float int stream",
+    "zeggs_radam_step_guarded": "status: f32* f32* f32* f32* long float float float float int i32* f32* stream",
+    "zeggs_radam_step_guarded_part": "status: f32* f32* f32* f32* long float float float float int i32* f32* int stream",
+    "zeggs_radam_step_wd": "status: f32* f32* f32* f32* long float float float float int float i32* f32* int stream",
+    "zeggs_radam_step_c": "status: f32* f32* f32* f32* long float float float float float float int float i32* f32* int stream",
+    "zeggs_radam_step_d": "status: f32* f32* f32* f32* long double double double double float float int float i32* f32* int stream",
+    "zeggs_status_flag": "status: i32* f32* stream",
+    "zeggs_test_cotenant": "status: int int float f32* long stream",
+    "zeggs_test_attention_fwd": "status: f32* f32* f32* int int int int float uint64 stream",
+    "zeggs_test_attention_bwd": "status: f32* f32* f32* f32* f32* f32* f32* int int int int float uint64 stream",
+    "zeggs_gather_windows": "status: f32* int i64* int int f32* stream",
+    "zeggs_gather_rows": "status: f32* int i64* long f32* int stream",
+    "zeggs_mel_stft_frames": "long: ZeggsMelDims* long",
+    "zeggs_mel_workspace_bytes": "size_t: ZeggsMelDims* long",
+    "zeggs_mel_features": "status: ZeggsMelDims* f32* long f64* int f32* any* size_t stream",
+    "zeggs_mel_frames_ready": "long: ZeggsMelDims* long",
+    "zeggs_mel_range_workspace_bytes": "size_t: ZeggsMelDims* long long",
+    "zeggs_mel_features_range": "status: ZeggsMelDims* f32* long int f64* long long f32* any* size_t stream",
+    "zeggs_mel_window_first_sample": "long: ZeggsMelDims* long",
+    "zeggs_mel_features_window": "status: ZeggsMelDims* f32* long long int f64* long long f32* any* size_t stream",
+    "zeggs_loudness_workspace_bytes": "size_t: long int long",
+    # coef[10] / trans[8]: prepared and read on the host
+    "zeggs_loudness_gain": "status: f32* long int double host* host* long i64* i64* int int f64* f32* any* size_t stream",
+    "zeggs_gather_example": "status: f32* int i64* int int f32* f32* f32* int int stream",
+    "zeggs_normalize_rows": "status: f32* long int long f32* f32* float stream",
+    "zeggs_fill": "status: f32* long float stream",
+    "zeggs_scale_copy": "status: f32* f32* long f32* float stream",
+    "zeggs_randn": "status: f32* long uint64 stream",
+    "zeggs_dropout": "status: f32* long float uint64 stream",
+    "zeggs_broadcast_time": "status: f32* f32* int int int stream",
+    "zeggs_sum_time": "status: f32* f32* int int int stream",
+    "zeggs_normalize_vec_fwd": "status: f32* f32* long int float stream",
+    "zeggs_normalize_vec_bwd": "status: f32* f32* f32* long int float stream",
+    "zeggs_vectorize_input_fwd": "status: int int f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* stream",
+    "zeggs_vectorize_input_bwd": "status: int int f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* stream",
+    "zeggs_devectorize_output_fwd": "status: int int float f32* f32* f32* f32* f32* f32* f32* f32* stream",
+    "zeggs_devectorize_output_bwd": "status: int int float f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* f32* stream",
+    "zeggs_kl_div_fwd": "status: f32* f32* int int f32* stream",
+    "zeggs_kl_div_bwd": "status: f32* f32* int int f32* f32* f32* stream",
+    "zeggs_mask_from_lengths": "status: i64* int int u8* stream",
+    "zeggs_anim_features_workspace_bytes": "size_t: ZeggsAnimDims*",
+    "zeggs_anim_features": "status: ZeggsAnimDims* i32* f64* f64* ZeggsAnimOut* any* size_t stream",
+    "zeggs_pose_to_bvh": "status: ZeggsBvhDims* f32* f32* f32* f32* f64* f64* stream",
+    "zeggs_pose_to_bvh_table": "status: ZeggsBvhDims* f32* f32* f32* f32* f32* f32* i32* f64* stream",
+    "zeggs_write_table_text": "status: str int host* long int",
+    "zeggs_parse_table_text": "status: host* size_t host* long int",        # text: an address inside a larger host buffer, not a whole C string
+    "zeggs_format_table_text": "status: host* long int host* size_t host*",
+    "zeggs_table_text_workspace_bytes": "size_t: long int",
+    "zeggs_table_text_device": "status: f64* long int u8* size_t i64* i32* any* size_t stream",
+    "zeggs_spline_chunk": "status: host* host* host*",
+    "zeggs_spline_resample_workspace_bytes": "size_t: long int",
+    "zeggs_spline_resample": "status: f64* long int long f64* any* size_t stream",
+    "zeggs_rot_stretch_workspace_bytes": "size_t: long int long",
+    "zeggs_rot_stretch": "status: f64* long int long int f64* any* size_t stream",
+    "zeggs_audio_prepare": "status: f32* long i64* int long long f32* f64* stream",
+    "zeggs_center_take": "status: f64* f64* long int int int any* size_t stream",
+    "zeggs_masked_stats_workspace_bytes": "size_t: long int",
+    "zeggs_masked_stats": "status: f32* u8* long int f64* f64* f64* any* size_t stream",
+    "zeggs_sweep_graph_stats": "status: host* host*",
+}
+
+
+# ----------------------------------------------------------------------------- parameter types
+class DevicePointer(C.c_void_p):
+    """A device-pointer parameter: takes a tensor (on a GPU, contiguous, one of `dtypes`), None, a c_void_p or an address."""
+    dtypes = None        # names of the torch dtypes it takes (None: any)
+    _ok = None           # the dtypes themselves, once torch is there
+
+    @classmethod
+    def from_param(cls, t):
+        if t is None:
+            return None
+        try:
+            on_gpu = t.is_cuda
+        except AttributeError:
+            if isinstance(t, (int, C.c_void_p)):
+                return C.c_void_p.from_param(t)
+            raise TypeError(f"zeggs: a tensor, None or an address where the library reads a device pointer, not {type(t).__name__}") from None
+        if not on_gpu:
+            raise RuntimeError("zeggs: tensor is not on a GPU (the HIP engine has no CPU path)")
+        if cls.dtypes is not None:
+            if cls._ok is None:
+                import torch
+                cls._ok = tuple(getattr(torch, n) for n in cls.dtypes)
+            if t.dtype not in cls._ok:
+                raise TypeError(f"zeggs: {t.dtype} tensor where the library reads {' / '.join(cls.dtypes)}")
+        if not t.is_contiguous():
+            raise RuntimeError("zeggs: tensor must be contiguous")
+        return C.c_void_p(t.data_ptr())
+
+
+def _device_pointer(name, dtypes):
+    return type(name, (DevicePointer,), {"dtypes": dtypes})
+
+
+KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_uint64, "float": C.c_float, "double": C.c_double,
+         "str": C.c_char_p, "host*": C.c_void_p, "stream": C.c_void_p,
+         "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
+         "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
+         "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in STRUCTS.items()})
+RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
+
+
+def signature(name):
+    """-> (return kind, [parameter kinds]) of a row"""
+    ret, _, params = PROTOTYPES[name].partition(":")
+    return ret, params.split()
+
+
+# ----------------------------------------------------------------------------- the two handles
+class _Typed(C.CDLL):
+    """CDLL whose functions hand on what a parameter type's from_param raised (ctypes wraps it in an ArgumentError) as the
+    RuntimeError / TypeError it was, with the function's name in front."""
+
+    def __init__(self, path):
+        super().__init__(path)
+        base = self._FuncPtr
+
+        class _Fn(base):
+            _flags_, _restype_ = base._flags_, base._restype_
+
+            def __call__(self, *args, _call=base.__call__):
+                try:
+                    return _call(self, *args)
+                except C.ArgumentError as e:
+                    raise (TypeError if ": TypeError: " in str(e) else RuntimeError)(f"{self.__name__}: {e}") from None
+        self._FuncPtr = _Fn
+
+
+_HANDLES = None
+_LOCK = threading.Lock()
+
+
+def _load():
+    global _HANDLES
+    with _LOCK:
+        if _HANDLES is not None:
+            return _HANDLES
+        if not LIB_PATH.exists():
+            raise HipLibraryMissing(
+                f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
+                "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
+        typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
+        missing = [n for n in PROTOTYPES if not hasattr(plain, n)]
+        if missing:
+            raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
+        last_error = typed.zeggs_last_error
+
+        def status(rc, fn, args):
+            if rc != 0:
+                raise RuntimeError(f"{fn.__name__}: {last_error().decode()}")
+            return rc
+
+        def mask(rc, fn, args):
+            return rc if rc >= 0 else status(rc, fn, args)
+        for name in PROTOTYPES:
+            ret, params = signature(name)
+            fn = getattr(typed, name)
+            fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]
+            if ret in ("status", "mask"):
+                fn.errcheck = status if ret == "status" else mask
+            getattr(plain, name).restype = RETURNS[ret]
+        # tuning switches for experiments, e.g. ZEGGS_OPTIONS="bwd_chunks=4,stage_variant=0" (see zeggs_set_option)
+        for kv in filter(None, os.environ.get("ZEGGS_OPTIONS", "").split(",")):
+            k, v = kv.split("=")
+            try:
+                typed.zeggs_set_option(k.strip().encode(), int(v))
+            except RuntimeError as e:
+                raise RuntimeError(f"ZEGGS_OPTIONS: {str(e).partition(': ')[2]}") from None
+            OPTIONS[k.strip()] = int(v)
+        _HANDLES = (typed, plain)
+        return _HANDLES
+
+
+def api():
+    """The typed handle (loads the library built by __graft_entry__.build() / csrc/build.sh on first use)."""
+    return (_HANDLES or _load())[0]
+
+
+def raw():
+    """The handle without argument types or error checks (ops.lib())."""
+    return (_HANDLES or _load())[1]

@@ -30,6 +30,8 @@ from pathlib import Path
 
 import numpy as np
 
+from .capi import api
+
 NOT_IMPLEMENTED_KEYS = ("visualize_spectrogram", "visualize_gaze", "save_normalized_animations")
 ANIM_FPS = 60
 
@@ -131,37 +133,10 @@ def check_conf(conf):
 
 
 # ----------------------------------------------------------------------------- device kernels (csrc/prepare.hip)
-def _lib():
-    from . import ops
-    L = ops.lib()
-    for n in ("zeggs_spline_resample_workspace_bytes", "zeggs_rot_stretch_workspace_bytes", "zeggs_masked_stats_workspace_bytes"):
-        getattr(L, n).restype = C.c_size_t
-    return L
-
-
-def _stream():
-    import torch
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _ptr(t):
-    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-
-
-def _ws(nbytes, device):
-    import torch
-    return torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
-
-
-def _check(rc, what):
-    if rc != 0:
-        raise RuntimeError(f"{what}: {_lib().zeggs_last_error().decode()}")
-
-
 def spline_chunk():
     """(rows per elimination chunk, halo rows, widest table on the thread-per-chunk kernel) of zeggs_spline_resample"""
     c, h, w = C.c_int(0), C.c_int(0), C.c_int(0)
-    _lib().zeggs_spline_chunk(C.byref(c), C.byref(h), C.byref(w))
+    api().zeggs_spline_chunk(C.byref(c), C.byref(h), C.byref(w))
     return c.value, h.value, w.value
 
 
@@ -169,6 +144,7 @@ def spline_resample(y, m):
     """y: device float64 [N, W] (or [N]) -> [m, W] ([m]): the not-a-knot cubic spline over the integer grid at linspace(0, N-1, m)
     (scipy griddata(method="cubic") on 1-D points).  N < 4 raises ValueError, as scipy does."""
     import torch
+    from . import ops
     if not (y.is_cuda and y.dtype == torch.float64):
         raise RuntimeError("spline_resample: a float64 tensor on the GPU is needed (the HIP engine has no CPU path)")
     flat = y.dim() == 1
@@ -176,28 +152,26 @@ def spline_resample(y, m):
     n, w = t.shape
     if n < 4:
         raise ValueError(f"a cubic spline needs at least 4 rows, got {n}")
-    L = _lib()
+    L = api()
     out = torch.empty(int(m), w, dtype=torch.float64, device=y.device)
-    ws = _ws(L.zeggs_spline_resample_workspace_bytes(C.c_long(n), int(w)), y.device)
-    _check(L.zeggs_spline_resample(_ptr(t), C.c_long(n), int(w), C.c_long(int(m)), _ptr(out), _ptr(ws), C.c_size_t(ws.numel()), _stream()),
-           "zeggs_spline_resample")
+    ws = ops._ws(max(L.zeggs_spline_resample_workspace_bytes(n, int(w)), 256), y.device)
+    L.zeggs_spline_resample(t, n, int(w), int(m), out, ws, ws.numel(), ops._stream())
     return out.reshape(-1) if flat else out.reshape((int(m),) + tuple(y.shape[1:]))
 
 
 def rot_stretch(euler, m, order):
     """euler: device float64 [N, J, 3] degrees in channel order `order` -> [m, J, 3] (from_euler, unroll, spline, normalise, to_euler)"""
     import torch
-    from . import anim
+    from . import anim, ops
     code = anim._to_euler_order(order)          # raises NotImplementedError for orders quat.to_euler does not have, as bvh_channels
     e = euler.contiguous()
     n, j = e.shape[0], e.shape[1]
     if n < 4:
         raise ValueError(f"a cubic spline needs 4 frames, got {n}")
-    L = _lib()
+    L = api()
     out = torch.empty(int(m), j, 3, dtype=torch.float64, device=e.device)
-    ws = _ws(L.zeggs_rot_stretch_workspace_bytes(C.c_long(n), int(j), C.c_long(int(m))), e.device)
-    _check(L.zeggs_rot_stretch(_ptr(e), C.c_long(n), int(j), C.c_long(int(m)), int(code), _ptr(out), _ptr(ws), C.c_size_t(ws.numel()),
-                               _stream()), "zeggs_rot_stretch")
+    ws = ops._ws(max(L.zeggs_rot_stretch_workspace_bytes(n, int(j), int(m)), 256), e.device)
+    L.zeggs_rot_stretch(e, n, int(j), int(m), int(code), out, ws, ws.numel(), ops._stream())
     return out
 
 
@@ -205,40 +179,39 @@ def audio_prepare(wav, intervals, start, end, want_f64=False):
     """wav: device float32 [n]; intervals: int64 [K, 2] (host) -> (float32 [len], float64 [len] or None): the signal times the union of
     the intervals, cut to [start, end) (clipped at the signal's end like a numpy slice)"""
     import torch
+    from . import ops
     n = wav.numel()
     length = max(min(int(end), n) - int(start), 0)
     iv = torch.as_tensor(np.ascontiguousarray(intervals, dtype=np.int64).reshape(-1, 2)).to(wav.device)
     o32 = torch.empty(length, dtype=torch.float32, device=wav.device)
     o64 = torch.empty(length, dtype=torch.float64, device=wav.device) if want_f64 else None
-    _check(_lib().zeggs_audio_prepare(_ptr(wav), C.c_long(n), _ptr(iv), int(iv.shape[0]), C.c_long(int(start)), C.c_long(max(int(end), int(start))),
-                                      _ptr(o32), _ptr(o64), _stream()), "zeggs_audio_prepare")
+    api().zeggs_audio_prepare(wav, n, iv, int(iv.shape[0]), int(start), max(int(end), int(start)), o32, o64, ops._stream())
     return o32, o64
 
 
 def center_take(pos, rot, order, round_f32):
     """the centring of data_pipeline.py:449-459 IN PLACE on device float64 [N, J, 3] positions / euler degrees"""
-    from . import anim
+    from . import anim, ops
     code = anim._to_euler_order(order)
     assert pos.is_contiguous() and rot.is_contiguous()
-    ws = _ws(64, pos.device)
-    _check(_lib().zeggs_center_take(_ptr(pos), _ptr(rot), C.c_long(pos.shape[0]), int(pos.shape[1]), int(code), int(bool(round_f32)),
-                                    _ptr(ws), C.c_size_t(ws.numel()), _stream()), "zeggs_center_take")
+    ws = ops._ws(256, pos.device)
+    api().zeggs_center_take(pos, rot, pos.shape[0], int(pos.shape[1]), int(code), int(bool(round_f32)), ws, ws.numel(), ops._stream())
 
 
 def masked_stats(x, mask):
     """x: device float32 [R, ...]; mask: device bool / uint8 [R] -> (mean [D], std [D], pooled std [1]) float64 device tensors over the
     masked rows (population std; pooled = the std of all masked elements).  Bitwise reproducible."""
     import torch
+    from . import ops
     if not (x.is_cuda and x.dtype == torch.float32):
         raise RuntimeError("masked_stats: a float32 tensor on the GPU is needed (the HIP engine has no CPU path)")
     t = x.reshape(x.shape[0], -1).contiguous()
     r, d = t.shape
     mk = mask.to(torch.uint8).contiguous()
-    L = _lib()
+    L = api()
     out = torch.empty(2 * d + 1, dtype=torch.float64, device=x.device)
-    ws = _ws(L.zeggs_masked_stats_workspace_bytes(C.c_long(r), int(d)), x.device)
-    _check(L.zeggs_masked_stats(_ptr(t), _ptr(mk), C.c_long(r), int(d), _ptr(out[:d]), _ptr(out[d:2 * d]), _ptr(out[2 * d:]), _ptr(ws),
-                                C.c_size_t(ws.numel()), _stream()), "zeggs_masked_stats")
+    ws = ops._ws(max(L.zeggs_masked_stats_workspace_bytes(r, int(d)), 256), x.device)
+    L.zeggs_masked_stats(t, mk, r, int(d), out[:d], out[d:2 * d], out[2 * d:], ws, ws.numel(), ops._stream())
     return out[:d], out[d:2 * d], out[2 * d:]
 
 

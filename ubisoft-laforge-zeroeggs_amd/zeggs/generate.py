@@ -89,7 +89,6 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
     tests/test_gpu_parity.py::test_generate_gesture_streaming_writer_equals_one_launch.  The decoder's frames are not kept
     (488 MB for 30 minutes).  Give-ups of the persistent kernel are collected in one status word that is looked at ONCE, after
     the last chunk: then everything is redone on the stage launches."""
-    import ctypes as C
     import time as _t0
     from concurrent.futures import ThreadPoolExecutor
     from . import ops
@@ -99,7 +98,7 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
     T = speech.shape[1]
     J = len(parents)
     in_mean, in_std, out_mean, out_std = stats
-    L = ops.lib()
+    L = ops.api()
     cols = 3 + 3 * J
     # frame 0 is the given first pose: its joint positions are the OFFSETs of the file (utils.write_bvh: offsets = positions[0])
     sl = lambda a, b: pose0[:, a:b]  # noqa: E731
@@ -155,14 +154,8 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
             P = pose[0, lo:]
             a_rpos, a_rrot = rpos[0, lo:].contiguous(), rrot[0, lo:].contiguous()
             a_lpos, a_ltxy = P[:, 6:6 + 3 * J].contiguous(), P[:, 6 + 3 * J:6 + 9 * J].contiguous()
-            rc = L.zeggs_pose_to_bvh_table(C.byref(d), C.c_void_p(a_rpos.data_ptr()), C.c_void_p(a_rrot.data_ptr()),
-                                           C.c_void_p(a_lpos.data_ptr()), C.c_void_p(a_ltxy.data_ptr()),
-                                           C.c_void_p(ref_pos.data_ptr()), C.c_void_p(ref_rot.data_ptr()),
-                                           C.c_void_p(seq_dev.data_ptr()), C.c_void_p(table.data_ptr()),
-                                           C.c_void_p(main.cuda_stream))
+            L.zeggs_pose_to_bvh_table(d, a_rpos, a_rrot, a_lpos, a_ltxy, ref_pos, ref_rot, seq_dev, table, main.cuda_stream)
             del a_rpos, a_rrot, a_lpos, a_ltxy
-            if rc != 0:
-                raise RuntimeError("zeggs_pose_to_bvh_table: " + L.zeggs_last_error().decode())
             drain(RING - 1)                              # the staging buffer of chunk c - RING has been written
             last = n == 0 or k + n >= T - 1
             blk = block if not last else max(16, -(-rows // (2 * workers)))
@@ -650,13 +643,12 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
     one table, which is formatted on the device and comes down as text cut at the pieces (anim.TEXT = "host": as float64 rows that
     host threads format) underneath the following chunks -- _TextStaging, the mechanism of _decode_to_bvh_streaming; this thread
     writes each clip's text in order.  `paths[j]` None: no file for clip j."""
-    import ctypes as C
     from concurrent.futures import ThreadPoolExecutor
     from . import ops
     dev = ld.device
     J, dt = len(ld.parents), ld.dt
     cols = 3 + 3 * J
-    L = ops.lib()
+    L = ops.api()
     firsts = [_first_frame(fe["feat"]) for fe in fes]
     speech = [fe["speech"][0] for fe in fes]
     style = [fe["final"].contiguous()[0] for fe in fes]
@@ -731,13 +723,7 @@ def _decode_batch(ld, fes, paths, bd, batch, chunk, return_poses, threads=None, 
                         d.T = rows
                         out = table[r0:r0 + rows]
                         ref_pos, ref_rot = firsts[j][1], firsts[j][2]
-                        rc = L.zeggs_pose_to_bvh_table(C.byref(d), C.c_void_p(a_rpos.data_ptr()), C.c_void_p(a_rrot.data_ptr()),
-                                                       C.c_void_p(a_lpos.data_ptr()), C.c_void_p(a_ltxy.data_ptr()),
-                                                       C.c_void_p(ref_pos.data_ptr()), C.c_void_p(ref_rot.data_ptr()),
-                                                       C.c_void_p(seq_dev.data_ptr()), C.c_void_p(out.data_ptr()),
-                                                       C.c_void_p(main.cuda_stream))
-                        if rc != 0:
-                            raise RuntimeError("zeggs_pose_to_bvh_table: " + L.zeggs_last_error().decode())
+                        L.zeggs_pose_to_bvh_table(d, a_rpos, a_rrot, a_lpos, a_ltxy, ref_pos, ref_rot, seq_dev, out, main.cuda_stream)
                         spans.append((j, r0, rows, k + n == lengths[j] - 1))
                         r0 += rows
                     del a_rpos, a_rrot, a_lpos, a_ltxy

@@ -1,4 +1,4 @@
-"""ctypes binding of libzeggs_hip.so (C ABI: include/zeggs_hip.h) + autograd glue.
+"""Wrappers of libzeggs_hip.so (C ABI: include/zeggs_hip.h; the ctypes binding itself is zeggs/capi.py) + autograd glue.
 
 PyTorch is used here only as plumbing: device memory (tensors), the current HIP
 stream and autograd bookkeeping.  Every arithmetic op of the hot path is a call
@@ -6,107 +6,29 @@ into the hand-written gfx950 library.  There is deliberately NO fallback: if the
 shared library is missing or a tensor is not on a GPU, these functions raise.
 """
 import ctypes as C
-import os
-from pathlib import Path
 
 import numpy as np
 import torch
 
-_LIB = None
-_LIB_PATH = Path(os.environ.get("ZEGGS_LIB") or Path(__file__).resolve().parent / "libzeggs_hip.so")   # ZEGGS_LIB: A/B builds
-c_f = C.c_void_p  # device pointers are passed as raw addresses
+from . import capi
+from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
+                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, SpeechDims, SpeechPtrs, StyleDims, StyleGruDims,
+                   StyleGruPtrs, StylePtrs, api)
 
-
-class HipLibraryMissing(RuntimeError):
-    pass
-
-
-# ----------------------------------------------------------------------------- structs (mirror zeggs_hip.h)
-class SpeechDims(C.Structure):
-    _fields_ = [("B", C.c_int), ("T", C.c_int), ("F", C.c_int), ("H", C.c_int), ("O", C.c_int), ("KW", C.c_int),
-                ("dropout_p", C.c_float), ("seed", C.c_uint64)]
-
-
-class StyleDims(C.Structure):
-    _fields_ = [("B", C.c_int), ("L", C.c_int), ("C", C.c_int), ("H", C.c_int), ("E", C.c_int), ("NH", C.c_int),
-                ("dropout", C.c_int), ("seed", C.c_uint64)]
-
-
-class DecDims(C.Structure):
-    _fields_ = [("B", C.c_int), ("T", C.c_int), ("PI", C.c_int), ("PO", C.c_int), ("SP", C.c_int), ("ST", C.c_int),
-                ("H", C.c_int), ("dt", C.c_float), ("film", C.c_int)]
-
-
-class LossDims(C.Structure):
-    _fields_ = [("B", C.c_int), ("T", C.c_int), ("J", C.c_int), ("S", C.c_int), ("dt", C.c_float)]
-
-
-def _ptr_struct(name, fields):
-    return type(name, (C.Structure,), {"_fields_": [(f, C.c_void_p) for f in fields]})
-
-
-SPEECH_FIELDS = ("w0", "b0", "w1", "b1", "w2", "b2")
-STYLE_FIELDS = ("c0_w", "c0_b", "ln0_g", "ln0_b", "c4_w", "c4_b", "ln1_g", "ln1_b", "in_w", "in_b", "out_w", "out_b",
-                "lna_g", "lna_b", "ff0_w", "ff0_b", "ff2_w", "ff2_b", "lnf_g", "lnf_b")
-DEC_FIELDS = ("l0_w", "l0_b", "w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "l2_w", "l2_b",
-              "c0_w", "c0_b", "c1_w", "c1_b", "c2_w", "c2_b",
-              "l3_w", "l3_b", "g_w", "g_b", "be_w", "be_b")          # last six: rnn_cond "film" only (else NULL)
-SpeechPtrs = _ptr_struct("SpeechPtrs", SPEECH_FIELDS)
-StylePtrs = _ptr_struct("StylePtrs", STYLE_FIELDS)
-DecPtrs = _ptr_struct("DecPtrs", DEC_FIELDS)
-DecStats = _ptr_struct("DecStats", ("in_mean", "in_std", "out_mean", "out_std"))
-
-
-class DecCall(C.Structure):       # mirrors ZeggsDecCall: the per-call controls of zeggs_decoder_fwd_ex / _bwd_ex
-    _fields_ = [("prepared", C.c_int), ("defer_wgrads", C.c_int), ("wgrad_stream", C.c_void_p), ("status", C.c_void_p),
-                ("grads_zeroed", C.c_int)]
-
+_LIB_PATH = capi.LIB_PATH
 
 COUNTERS = {}                                      # which optional paths ran (tests): "style_in_place"
 STATUS_WORDS = 4                                   # ZEGGS_STATUS_WORDS
 GAVE_UP = {1: "B=1 decode kernel", 2: "training rollout", 4: "BPTT sweep", 8: "batch decode sweep"}     # ZEGGS_GAVE_UP_* bits of status[0]
-# what the binding needs beyond the header's older entry points: checked when the library is loaded, so that a stale
-# libzeggs_hip.so fails with a message instead of an AttributeError in the middle of a job list
-REQUIRED_SYMBOLS = ("zeggs_decoder_batch_workspace_bytes", "zeggs_decoder_batch_prepare", "zeggs_decoder_state_init",
-                    "zeggs_decoder_fwd_batch", "zeggs_decoder_batch_last_path", "zeggs_radam_step_c", "zeggs_gemm_direct_warm",
-                    "zeggs_mel_window_first_sample", "zeggs_mel_features_window", "zeggs_speech_encoder_live",
-                    "zeggs_speech_encoder_live_prepare", "zeggs_speech_encoder_live_workspace_bytes", "zeggs_loss_eval",
-                    "zeggs_loss_eval_workspace_bytes", "zeggs_eval_accumulate", "zeggs_gemm_fixed_order",
-                    "zeggs_test_gemm_route_log", "zeggs_radam_step_d")
 
 
 def lib():
-    """Load the HIP library (built by __graft_entry__.build() / csrc/build.sh)."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    if not _LIB_PATH.exists():
-        raise HipLibraryMissing(
-            f"{_LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
-            "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
-    L = C.CDLL(str(_LIB_PATH))
-    L.zeggs_last_error.restype = C.c_char_p
-    missing = [n for n in REQUIRED_SYMBOLS if not hasattr(L, n)]
-    if missing:
-        raise HipLibraryMissing(f"{_LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
-    for n in ("zeggs_speech_encoder_workspace_bytes", "zeggs_style_encoder_workspace_bytes",
-              "zeggs_decoder_workspace_bytes", "zeggs_loss_workspace_bytes", "zeggs_loss_eval_workspace_bytes",
-              "zeggs_style_encoder_input_offset",
-              "zeggs_decoder_batch_workspace_bytes", "zeggs_mel_range_workspace_bytes",
-              "zeggs_speech_encoder_live_workspace_bytes"):
-        getattr(L, n).restype = C.c_size_t
-    for n in ("zeggs_mel_frames_ready", "zeggs_mel_window_first_sample"):
-        getattr(L, n).restype = C.c_long
-    _LIB = L
-    # tuning switches for experiments, e.g. ZEGGS_OPTIONS="bwd_chunks=4,stage_variant=0" (see zeggs_set_option)
-    for kv in filter(None, os.environ.get("ZEGGS_OPTIONS", "").split(",")):
-        k, v = kv.split("=")
-        if L.zeggs_set_option(k.strip().encode(), int(v)) != 0:
-            raise RuntimeError(f"ZEGGS_OPTIONS: {L.zeggs_last_error().decode()}")
-        _OPTIONS[k.strip()] = int(v)
-    return L
+    """The library (built by __graft_entry__.build() / csrc/build.sh) as tests, tools and the benchmark call it: return types
+    set, arguments wrapped by the caller, return codes left to the caller.  The package itself calls capi.api()."""
+    return capi.raw()
 
 
+# _check / _p: for callers of lib() (the typed handle makes both checks itself)
 def _check(rc, what):
     if rc != 0:
         raise RuntimeError(f"{what}: {lib().zeggs_last_error().decode()}")
@@ -130,6 +52,12 @@ def _stream():
 
 def _f32c(t):
     return t.detach().to(torch.float32).contiguous()
+
+
+def _f32r(t):
+    """_f32c for a tensor that a call only READS through its address (inference entry points: nothing is saved): what is float32
+    and contiguous already goes as it is (0.5 us instead of 3 us per tensor on the per-chunk path of a stream)"""
+    return t if t.dtype is torch.float32 and t.is_contiguous() else _f32c(t)
 
 
 def _ws(nbytes, device):
@@ -196,7 +124,7 @@ def _route(ectx):
     ctypes call when the thread's route changes, nothing otherwise."""
     r = ectx.gemm_route or (-1, -1, -1, -1)
     if getattr(_tls, "route", (-1, -1, -1, -1)) != r:
-        lib().zeggs_gemm_route(*[int(x) for x in r])
+        api().zeggs_gemm_route(*[int(x) for x in r])
         _tls.route = r
 
 
@@ -205,7 +133,11 @@ def gemm_direct_warm():
     caller stream (zeggs_gemm_direct_warm), so that no later product stops for it.  -> None, or why a check could not run (the
     first product that wants that variant tries again)."""
     _route(current())
-    return None if lib().zeggs_gemm_direct_warm() == 0 else lib().zeggs_last_error().decode()
+    try:
+        api().zeggs_gemm_direct_warm()
+    except RuntimeError as e:
+        return str(e)
+    return None
 
 
 def current():
@@ -238,11 +170,9 @@ def side_stream(device=None):
     if idx not in _SIDE_STREAMS:
         with torch.cuda.device(idx):
             h = C.c_void_p(0)
-            _check(lib().zeggs_side_stream(C.byref(h)), "side_stream")
+            api().zeggs_side_stream(C.byref(h))
             _SIDE_STREAMS[idx] = torch.cuda.ExternalStream(h.value, device=torch.device("cuda", idx))
     return _SIDE_STREAMS[idx]
-
-
 
 
 def new_status(device):
@@ -292,7 +222,7 @@ def _grad_targets(orig_params, params, ectx):
 
 
 def fill_(t, value=0.0):
-    _check(lib().zeggs_fill(_p(t), C.c_long(t.numel()), C.c_float(value), _stream()), "fill")
+    api().zeggs_fill(t, t.numel(), value, _stream())
     return t
 
 
@@ -300,16 +230,14 @@ def scale_copy(src, dev_scale=None, alpha=1.0, out=None):
     """out = alpha * dev_scale[0] * src (dev_scale: 1-element device tensor or None)"""
     src = src if src.is_contiguous() else src.contiguous()
     out = torch.empty_like(src) if out is None else out
-    _check(lib().zeggs_scale_copy(_p(out), _p(src), C.c_long(src.numel()), _p(dev_scale) if dev_scale is not None else None,
-                                  C.c_float(alpha), _stream()), "scale_copy")
+    api().zeggs_scale_copy(out, src, src.numel(), dev_scale, alpha, _stream())
     return out
 
 
 def randn(shape, device, seed=None):
     """Standard normal samples from the library's counter-hash stream (seeded by ops.manual_seed)."""
     out = torch.empty(*shape, device=device, dtype=torch.float32)
-    _check(lib().zeggs_randn(_p(out), C.c_long(out.numel()), C.c_uint64(next_seed() if seed is None else int(seed)),
-                             _stream()), "randn")
+    api().zeggs_randn(out, out.numel(), next_seed() if seed is None else int(seed), _stream())
     return out
 
 
@@ -319,7 +247,7 @@ class _BroadcastTimeFn(torch.autograd.Function):
         z = _f32c(z)
         B, S = z.shape
         out = torch.empty(B, T, S, device=z.device, dtype=torch.float32)
-        _check(lib().zeggs_broadcast_time(_p(out), _p(z), B, T, S, _stream()), "broadcast_time")
+        api().zeggs_broadcast_time(out, z, B, T, S, _stream())
         ctx.dims = (B, T, S)
         return out
 
@@ -327,7 +255,7 @@ class _BroadcastTimeFn(torch.autograd.Function):
     def backward(ctx, dout):
         B, T, S = ctx.dims
         dz = torch.empty(B, S, device=dout.device, dtype=torch.float32)
-        _check(lib().zeggs_sum_time(_p(dz), _p(_f32c(dout)), B, T, S, _stream()), "sum_time")
+        api().zeggs_sum_time(dz, _f32c(dout), B, T, S, _stream())
         return dz, None
 
 
@@ -345,11 +273,8 @@ def _ptrs(cls, fields, tensors):
 
 # ----------------------------------------------------------------------------- raw GEMM (tests)
 def gemm(A, B, Cmat, M, N, K, sa, sb, sc, bias=None, nbatch=1, bs=(0, 0, 0), alpha=1.0, beta=0.0, act=0):
-    rc = lib().zeggs_gemm(_p(A), _p(B), _p(Cmat), _p(bias), M, N, K, C.c_long(sa[0]), C.c_long(sa[1]),
-                          C.c_long(sb[0]), C.c_long(sb[1]), C.c_long(sc[0]), C.c_long(sc[1]), nbatch,
-                          C.c_long(bs[0]), C.c_long(bs[1]), C.c_long(bs[2]), C.c_float(alpha), C.c_float(beta), act,
-                          _stream())
-    _check(rc, "zeggs_gemm")
+    api().zeggs_gemm(A, B, Cmat, bias, M, N, K, sa[0], sa[1], sb[0], sb[1], sc[0], sc[1], nbatch, bs[0], bs[1], bs[2], alpha, beta,
+                     act, _stream())
     return Cmat
 
 
@@ -364,12 +289,11 @@ class _SpeechFn(torch.autograd.Function):
         params = [_f32c(t) for t in (w0, b0, w1, b1, w2, b2)]
         B, T, F = x.shape
         d = SpeechDims(B, T, F, w0.shape[0], w2.shape[0], w1.shape[2], float(p), int(seed))
-        L = lib()
-        ws = _ws(L.zeggs_speech_encoder_workspace_bytes(C.byref(d)), x.device)
+        L = api()
+        ws = _ws(L.zeggs_speech_encoder_workspace_bytes(d), x.device)
         out = torch.empty(B, T, d.O, device=x.device, dtype=torch.float32)
         P = _ptrs(SpeechPtrs, SPEECH_FIELDS, params)
-        _check(L.zeggs_speech_encoder_fwd(C.byref(d), C.byref(P), _p(x), _p(out), _p(ws), C.c_size_t(ws.numel()),
-                                          _stream()), "speech_encoder_fwd")
+        L.zeggs_speech_encoder_fwd(d, P, x, out, ws, ws.numel(), _stream())
         ctx.d, ctx.ws = d, ws
         ctx.save_for_backward(x, out, *params)
         return out
@@ -377,14 +301,13 @@ class _SpeechFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         x, out, *params = ctx.saved_tensors
-        L = lib()
+        L = api()
         _route(ctx.ectx)
         grads, rets = _grad_targets(ctx.orig, params, ctx.ectx)
         P = _ptrs(SpeechPtrs, SPEECH_FIELDS, params)
         G = _ptrs(SpeechPtrs, SPEECH_FIELDS, grads)
         zeroed = int(ctx.ectx.direct_grads and all(r is None for r in rets))     # the engine zeroes its flat gradient buffer per step
-        _check(L.zeggs_speech_encoder_bwd_ex(C.byref(ctx.d), C.byref(P), _p(x), _p(out), _p(_f32c(dout)), C.byref(G),
-                                             _p(ctx.ws), C.c_size_t(ctx.ws.numel()), _stream(), zeroed), "speech_encoder_bwd")
+        L.zeggs_speech_encoder_bwd_ex(ctx.d, P, x, out, _f32c(dout), G, ctx.ws, ctx.ws.numel(), _stream(), zeroed)
         return (None, *rets, None, None)
 
 
@@ -435,31 +358,28 @@ class _StyleFn(torch.autograd.Function):
         B, Lx, Cx = x.shape
         H, E = params[0].shape[0], params[4].shape[0]
         d = StyleDims(B, Lx, Cx, H, E, nheads, int(dropout), int(seed))
-        L = lib()
-        need = int(L.zeggs_style_encoder_workspace_bytes(C.byref(d)))
+        L = api()
+        need = int(L.zeggs_style_encoder_workspace_bytes(d))
         # an example that style_input_buffer() + gather_example() put where the workspace keeps the first convolution's padded input:
         # the encoder runs IN that workspace and skips its own padding copy (zeggs_style_encoder_fwd_part, part | 4); anything that
         # does not match exactly (another shape, a copy of the tensor, a workspace of another size) takes the ordinary path
         ws, inplace = getattr(x, "_zeggs_style_ws", None), 0
         if ws is not None and x.dtype == torch.float32 and ws.numel() == need and x.stride() == ((Lx + 2) * Cx, Cx, 1) and \
-                x.data_ptr() == ws.data_ptr() + int(L.zeggs_style_encoder_input_offset(C.byref(d))) + 4 * Cx:
-            inplace, xptr = 4, C.c_void_p(x.data_ptr())
+                x.data_ptr() == ws.data_ptr() + int(L.zeggs_style_encoder_input_offset(d)) + 4 * Cx:
+            inplace, xptr = 4, C.c_void_p(x.data_ptr())      # (a strided view of the padded buffer: by address)
             COUNTERS["style_in_place"] = COUNTERS.get("style_in_place", 0) + 1
         else:
             x = _f32c(x)
-            ws, xptr = _ws(need, x.device), _p(x)
+            ws, xptr = _ws(need, x.device), x
         out = torch.empty(B, E, device=x.device, dtype=torch.float32)
         P = _ptrs(StylePtrs, STYLE_FIELDS, params)
         hook = getattr(ctx.ectx, "after_style_head", None)
         if hook is not None:       # (an engine that releases its other queues once the chip-filling first product is enqueued)
-            _check(L.zeggs_style_encoder_fwd_part(C.byref(d), C.byref(P), xptr, _p(pos), _p(out), _p(ws),
-                                                  C.c_size_t(ws.numel()), _stream(), 1 | inplace), "style_encoder_fwd (head)")
+            L.zeggs_style_encoder_fwd_part(d, P, xptr, pos, out, ws, ws.numel(), _stream(), 1 | inplace)
             hook()
-            _check(L.zeggs_style_encoder_fwd_part(C.byref(d), C.byref(P), xptr, _p(pos), _p(out), _p(ws),
-                                                  C.c_size_t(ws.numel()), _stream(), 2 | inplace), "style_encoder_fwd (rest)")
+            L.zeggs_style_encoder_fwd_part(d, P, xptr, pos, out, ws, ws.numel(), _stream(), 2 | inplace)
         else:
-            _check(L.zeggs_style_encoder_fwd_part(C.byref(d), C.byref(P), xptr, _p(pos), _p(out), _p(ws),
-                                                  C.c_size_t(ws.numel()), _stream(), 3 | inplace), "style_encoder_fwd")
+            L.zeggs_style_encoder_fwd_part(d, P, xptr, pos, out, ws, ws.numel(), _stream(), 3 | inplace)
         ctx.d, ctx.ws = d, ws
         ctx.save_for_backward(*params)
         return out
@@ -467,7 +387,7 @@ class _StyleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         params = list(ctx.saved_tensors)
-        L = lib()
+        L = api()
         _route(ctx.ectx)
         grads, rets = _grad_targets(ctx.orig, params, ctx.ectx)
         P = _ptrs(StylePtrs, STYLE_FIELDS, params)
@@ -478,30 +398,18 @@ class _StyleFn(torch.autograd.Function):
         if ectx.defer_style_wgrads and zeroed:
             # the chain now, on this stream; the six weight-gradient products later, where the caller puts them (they read the operands
             # the chain parked in the workspace: zeggs_style_encoder_bwd_part)
-            _check(L.zeggs_style_encoder_bwd_part(C.byref(ctx.d), C.byref(P), _p(dout), C.byref(G), _p(ctx.ws),
-                                                  C.c_size_t(ctx.ws.numel()), _stream(), zeroed, 1), "style_encoder_bwd (chain)")
+            L.zeggs_style_encoder_bwd_part(ctx.d, P, dout, G, ctx.ws, ctx.ws.numel(), _stream(), zeroed, 1)
             ev = torch.cuda.Event()
             ev.record()
             d, ws, keep = ctx.d, ctx.ws, (params, grads, dout)
 
             def products():
                 _route(ectx)
-                _check(L.zeggs_style_encoder_bwd_part(C.byref(d), C.byref(P), _p(keep[2]), C.byref(G), _p(ws),
-                                                      C.c_size_t(ws.numel()), _stream(), zeroed, 2), "style_encoder_bwd (products)")
+                L.zeggs_style_encoder_bwd_part(d, P, keep[2], G, ws, ws.numel(), _stream(), zeroed, 2)
             ectx.deferred_wgrads.append((ev, products))
             return (None, None, None, None, None, *rets)
-        _check(L.zeggs_style_encoder_bwd_ex(C.byref(ctx.d), C.byref(P), _p(dout), C.byref(G), _p(ctx.ws),
-                                            C.c_size_t(ctx.ws.numel()), _stream(), zeroed), "style_encoder_bwd")
+        L.zeggs_style_encoder_bwd_ex(ctx.d, P, dout, G, ctx.ws, ctx.ws.numel(), _stream(), zeroed)
         return (None, None, None, None, None, *rets)
-
-
-STYLE_GRU_FIELDS = ("c0_w", "c0_b", "c2_w", "c2_b", "w_ih", "w_hh", "b_ih", "b_hh", "w_ih_r", "w_hh_r", "b_ih_r",
-                    "b_hh_r", "p_w", "p_b")
-StyleGruPtrs = _ptr_struct("StyleGruPtrs", STYLE_GRU_FIELDS)
-
-
-class StyleGruDims(C.Structure):       # mirrors ZeggsStyleGruDims
-    _fields_ = [("B", C.c_int), ("L", C.c_int), ("C", C.c_int), ("H", C.c_int), ("O", C.c_int)]
 
 
 class _StyleGruFn(torch.autograd.Function):
@@ -514,13 +422,11 @@ class _StyleGruFn(torch.autograd.Function):
         params = [_f32c(t) for t in params]
         B, Lx, Cx = x.shape
         d = StyleGruDims(B, Lx, Cx, params[0].shape[0], params[12].shape[0])
-        L = lib()
-        L.zeggs_style_encoder_gru_workspace_bytes.restype = C.c_size_t
-        ws = _ws(L.zeggs_style_encoder_gru_workspace_bytes(C.byref(d)), x.device)
+        L = api()
+        ws = _ws(L.zeggs_style_encoder_gru_workspace_bytes(d), x.device)
         out = torch.empty(B, d.O, device=x.device, dtype=torch.float32)
         P = _ptrs(StyleGruPtrs, STYLE_GRU_FIELDS, params)
-        _check(L.zeggs_style_encoder_gru_fwd(C.byref(d), C.byref(P), _p(x), _p(out), _p(ws), C.c_size_t(ws.numel()),
-                                             _stream()), "style_encoder_gru_fwd")
+        L.zeggs_style_encoder_gru_fwd(d, P, x, out, ws, ws.numel(), _stream())
         ctx.d, ctx.ws = d, ws
         ctx.save_for_backward(*params)
         return out
@@ -532,8 +438,7 @@ class _StyleGruFn(torch.autograd.Function):
         grads, rets = _grad_targets(ctx.orig, params, ctx.ectx)
         P = _ptrs(StyleGruPtrs, STYLE_GRU_FIELDS, params)
         G = _ptrs(StyleGruPtrs, STYLE_GRU_FIELDS, grads)
-        _check(lib().zeggs_style_encoder_gru_bwd(C.byref(ctx.d), C.byref(P), _p(_f32c(dout)), C.byref(G), _p(ctx.ws),
-                                                 C.c_size_t(ctx.ws.numel()), _stream()), "style_encoder_gru_bwd")
+        api().zeggs_style_encoder_gru_bwd(ctx.d, P, _f32c(dout), G, ctx.ws, ctx.ws.numel(), _stream())
         return (None, *rets)
 
 
@@ -553,11 +458,11 @@ def style_input_buffer(enc, B, L, Cx, training, device, ws=None):
     earlier call to use again when it still fits."""
     params = style_param_list(enc)
     d = StyleDims(int(B), int(L), int(Cx), params[0].shape[0], params[4].shape[0], 4, 1 if training else 0, 0)
-    Lb = lib()
-    need = int(Lb.zeggs_style_encoder_workspace_bytes(C.byref(d)))
+    Lb = api()
+    need = Lb.zeggs_style_encoder_workspace_bytes(d)
     if ws is None or ws.numel() != need or ws.device != torch.device(device):
         ws = _ws(need, device)
-    off = int(Lb.zeggs_style_encoder_input_offset(C.byref(d)))
+    off = Lb.zeggs_style_encoder_input_offset(d)
     xp = ws[off:off + 4 * B * (L + 2) * Cx].view(torch.float32).view(B, L + 2, Cx)
     return ws, xp
 
@@ -576,8 +481,8 @@ def gather_example(frames, rows, mean, std, out, pad=1):
     B, Lr = rows.shape
     Wo = out.shape[2]
     assert out.shape == (B, Lr + 2 * pad, Wo) and out.is_contiguous() and mean.numel() == Wo and std.numel() == Wo
-    _check(lib().zeggs_gather_example(_p(frames), frames.shape[1], _p(rows.contiguous()), int(B), int(Lr), _p(_f32c(mean)),
-                                      _p(_f32c(std)), _p(out), int(Wo), int(pad), _stream()), "gather_example")
+    api().zeggs_gather_example(frames, frames.shape[1], rows.contiguous(), int(B), int(Lr), _f32c(mean), _f32c(std), out, int(Wo),
+                               int(pad), _stream())
     return out
 
 
@@ -592,8 +497,7 @@ class _VaeFn(torch.autograd.Function):
         enc, eps = _f32c(enc), _f32c(eps)
         B = enc.shape[0]
         z, mu, lv = (torch.empty(B, S, device=enc.device, dtype=torch.float32) for _ in range(3))
-        _check(lib().zeggs_vae_reparam_fwd(_p(enc), _p(eps), _p(z), _p(mu), _p(lv), B, S, C.c_float(temperature),
-                                           _stream()), "vae_reparam_fwd")
+        api().zeggs_vae_reparam_fwd(enc, eps, z, mu, lv, B, S, temperature, _stream())
         ctx.save_for_backward(enc, eps)
         ctx.t, ctx.S = temperature, S
         ctx.set_materialize_grads(False)
@@ -603,9 +507,8 @@ class _VaeFn(torch.autograd.Function):
     def backward(ctx, dz, dmu, dlv):
         enc, eps = ctx.saved_tensors
         denc = torch.empty_like(enc)
-        c = lambda g: _p(_f32c(g)) if g is not None else None  # noqa: E731
-        _check(lib().zeggs_vae_reparam_bwd(_p(enc), _p(eps), c(dz), c(dmu), c(dlv), _p(denc), enc.shape[0], ctx.S,
-                                           C.c_float(ctx.t), _stream()), "vae_reparam_bwd")
+        c = lambda g: _f32c(g) if g is not None else None  # noqa: E731
+        api().zeggs_vae_reparam_bwd(enc, eps, c(dz), c(dmu), c(dlv), denc, enc.shape[0], ctx.S, ctx.t, _stream())
         return denc, None, None, None
 
 
@@ -663,18 +566,16 @@ def decoder_prepare(dec, B, T, SP, ST, in_mean, in_std, out_mean, out_std, dt, s
     stats = [_f32c(t) for t in (in_mean, in_std, out_mean, out_std)]
     PO, H = int(stats[2].numel()), dec.recurrent_decoder.layer1.hidden_size
     d = DecDims(int(B), int(T), PO + 3, PO, int(SP), int(ST), H, float(dt), 1 if len(params) == len(DEC_FIELDS) else 0)
-    L = lib()
-    ws = _ws(L.zeggs_decoder_workspace_bytes(C.byref(d), 1), params[0].device)
+    L = api()
+    ws = _ws(L.zeggs_decoder_workspace_bytes(d, 1), params[0].device)
     P = _ptrs(DecPtrs, DEC_FIELDS, params)
-    S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), stats)
+    S = _ptrs(DecStats, STATS_FIELDS, stats)
     stream.wait_stream(torch.cuda.current_stream())       # the optimizer step that produced these weights
     # (no record_stream: the workspace belongs to the current stream's pool and its next user there -- the forward that picks
     #  it up, or whoever gets the block after it -- comes after a wait for `stream`; a recorded stream would park the block
     #  in the allocator's pending list, and every device synchronisation would then cost a few iterations of re-allocation)
     with torch.cuda.stream(stream):
-        mask = L.zeggs_decoder_prepare(C.byref(d), C.byref(P), C.byref(S), _p(ws), C.c_size_t(ws.numel()),
-                                       C.c_void_p(stream.cuda_stream))
-        _check(min(mask, 0), "decoder_prepare")
+        mask = L.zeggs_decoder_prepare(d, P, S, ws, ws.numel(), stream.cuda_stream)
         ev = torch.cuda.Event()
         ev.record(stream)
         if after is not None:       # (more work of the caller for `stream`, behind the packs and outside what the forward waits for)
@@ -706,7 +607,7 @@ class _DecoderFn(torch.autograd.Function):
         # needs_input_grad ignores torch.no_grad(): the caller's grad mode selects the BPTT workspace / ring path
         training = bool(grad_mode) and any(ctx.needs_input_grad)
         d = DecDims(B, T, PO + 3, PO, SP, ST, H, float(dt), 1 if len(params) == len(DEC_FIELDS) else 0)
-        L = lib()
+        L = api()
         dev = pose0.device
         prep = ectx.prepared
         mask = 0
@@ -717,12 +618,12 @@ class _DecoderFn(torch.autograd.Function):
             torch.cuda.current_stream().wait_event(ev)
         else:
             _drop_prepared(ectx)                            # (waits for the side stream before the block is released)
-            ws = _ws(L.zeggs_decoder_workspace_bytes(C.byref(d), int(training)), pose0.device)
+            ws = _ws(L.zeggs_decoder_workspace_bytes(d, int(training)), pose0.device)
         pose = torch.empty(B, T, PO, device=dev, dtype=torch.float32)
         rpos = torch.empty(B, T, 3, device=dev, dtype=torch.float32)
         rrot = torch.empty(B, T, 4, device=dev, dtype=torch.float32)
         P = _ptrs(DecPtrs, DEC_FIELDS, params)
-        S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), stats)
+        S = _ptrs(DecStats, STATS_FIELDS, stats)
         capturing = torch.cuda.is_current_stream_capturing()
         # Give-up detection (ZeggsDecCall.status).  An engine passes ITS status words and looks at them itself (device-guarded
         # optimizer step, lagged read-back: engine.TrainEngine).  Every other caller gets a per-thread word that is inspected
@@ -742,9 +643,8 @@ class _DecoderFn(torch.autograd.Function):
         call = DecCall(int(mask) & 1, 0, None, status.data_ptr() if status is not None else None, 0)
 
         def run():
-            _check(L.zeggs_decoder_fwd_ex(C.byref(d), C.byref(P), C.byref(S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze),
-                                          _p(speech), _p(style), _p(pose), _p(rpos), _p(rrot), int(training), _p(ws),
-                                          C.c_size_t(ws.numel()), _stream(), C.byref(call)), "decoder_fwd")
+            L.zeggs_decoder_fwd_ex(d, P, S, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, int(training), ws, ws.numel(),
+                                   _stream(), call)
         run()
         if own is not None:
             bits = int(own[0].item())                      # one 4-byte read-back per rollout
@@ -773,7 +673,7 @@ class _DecoderFn(torch.autograd.Function):
         d = ctx.d
         ectx = ctx.ectx
         _route(ectx)
-        L = lib()
+        L = api()
         dev = pose.device
         z = lambda g, ref: fill_(torch.empty_like(ref)) if g is None else _f32c(g)  # noqa: E731
         dpose, drpos, drrot = z(dpose, pose), z(drpos, rpos), z(drrot, rrot)
@@ -782,7 +682,7 @@ class _DecoderFn(torch.autograd.Function):
         dstyle = torch.empty(d.B, d.T, d.ST, device=dev, dtype=torch.float32)
         P = _ptrs(DecPtrs, DEC_FIELDS, params)
         G = _ptrs(DecPtrs, DEC_FIELDS, grads)
-        S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), stats)
+        S = _ptrs(DecStats, STATS_FIELDS, stats)
         direct = ectx.direct_grads and all(r is None for r in rets)
         side = ectx.wgrad_stream if direct and not torch.cuda.is_current_stream_capturing() else None
         # with a gradient exchange waiting (engine hook) the deferred GEMMs come in two halves of the parameter order, so that
@@ -794,9 +694,8 @@ class _DecoderFn(torch.autograd.Function):
                        ctx.status.data_ptr() if ctx.status is not None else None, int(direct))
 
         def run():
-            _check(L.zeggs_decoder_bwd_ex(C.byref(d), C.byref(P), C.byref(S), _p(gaze), _p(pose), _p(rpos), _p(rrot),
-                                          _p(dpose), _p(drpos), _p(drrot), C.byref(G), _p(dspeech), _p(dstyle), _p(ctx.ws),
-                                          C.c_size_t(ctx.ws.numel()), _stream(), C.byref(call)), "decoder_bwd")
+            L.zeggs_decoder_bwd_ex(d, P, S, gaze, pose, rpos, rrot, dpose, drpos, drrot, G, dspeech, dstyle, ctx.ws, ctx.ws.numel(),
+                                   _stream(), call)
         run()
         if ctx.own_status and not torch.cuda.is_current_stream_capturing():
             # plain autograd use (no engine looking at the word later): the gradients go to the caller's optimizer next
@@ -816,8 +715,7 @@ class _DecoderFn(torch.autograd.Function):
                 side.wait_stream(torch.cuda.current_stream())       # the CellStateEncoder gradients come from this stream
                 with torch.cuda.stream(side):
                     after(0)         # layer2, GRU layer 1, CellStateEncoder: final behind the GEMMs already on `side`
-                    _check(L.zeggs_decoder_wgrads(C.byref(d), C.byref(G), _p(ctx.ws), C.c_size_t(ctx.ws.numel()), 4 | 8,
-                                                  C.c_void_p(side.cuda_stream)), "decoder_wgrads")
+                    L.zeggs_decoder_wgrads(d, G, ctx.ws, ctx.ws.numel(), 4 | 8, side.cuda_stream)
                     after(1)         # layer0, GRU layer 0
             elif ectx.decoder_grads_final is not None:
                 side.wait_stream(torch.cuda.current_stream())       # the CellStateEncoder gradients come from this stream
@@ -839,8 +737,7 @@ def last_decoder_chain_errors():
         return 0
     d, training, ws = _LAST_DECODER_WS
     out = C.c_int(0)
-    _check(lib().zeggs_decoder_chain_errors(C.byref(d), training, _p(ws), C.c_size_t(ws.numel()), C.byref(out)),
-           "decoder_chain_errors")
+    api().zeggs_decoder_chain_errors(d, training, ws, ws.numel(), C.byref(out))
     return int(out.value)
 
 
@@ -872,26 +769,24 @@ def decoder_chunk(dec, pose0, rpos0, rrot0, gaze, speech, style, in_mean, in_std
     produced (pose0 / rpos0 / rrot0; index 0 of gaze / speech / style belongs to it), h_in [2,B,H] the GRU state after it (None:
     first chunk, CellStateEncoder).  -> pose [B,N,PO], rpos, rrot, h_out [2,B,H].  Nothing is read back: `status` (device
     words, ops.new_status) collects a give-up bit of the persistent kernel for the CALLER to look at when it chooses to."""
-    pose0, rpos0, rrot0, gaze, speech, style = (_f32c(t) for t in (pose0, rpos0, rrot0, gaze, speech, style))
-    stats = [_f32c(t) for t in (in_mean, in_std, out_mean, out_std)]
-    params = [_f32c(t) for t in decoder_param_list(dec)]
+    pose0, rpos0, rrot0, gaze, speech, style = (_f32r(t) for t in (pose0, rpos0, rrot0, gaze, speech, style))
+    stats = [_f32r(t) for t in (in_mean, in_std, out_mean, out_std)]
+    params = [_f32r(t) for t in decoder_param_list(dec)]
     B, N, SP = speech.shape
     PO, H = pose0.shape[1], dec.recurrent_decoder.layer1.hidden_size
     d = DecDims(B, N, PO + 3, PO, SP, style.shape[2], H, float(dt), 1 if len(params) == len(DEC_FIELDS) else 0)
-    L = lib()
+    L = api()
     dev = pose0.device
-    ws = _ws(L.zeggs_decoder_workspace_bytes(C.byref(d), 0), dev)
+    ws = _ws(L.zeggs_decoder_workspace_bytes(d, 0), dev)
     pose = torch.empty(B, N, PO, device=dev, dtype=torch.float32)
     rpos = torch.empty(B, N, 3, device=dev, dtype=torch.float32)
     rrot = torch.empty(B, N, 4, device=dev, dtype=torch.float32)
     h_out = torch.empty(2, B, H, device=dev, dtype=torch.float32)
     P = _ptrs(DecPtrs, DEC_FIELDS, params)
-    S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), stats)
+    S = _ptrs(DecStats, STATS_FIELDS, stats)
     call = DecCall(0, 0, None, status.data_ptr() if status is not None else None, 0)
-    _check(L.zeggs_decoder_fwd_state_ex(C.byref(d), C.byref(P), C.byref(S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze),
-                                        _p(speech), _p(style), _p(pose), _p(rpos), _p(rrot),
-                                        _p(_f32c(h_in)) if h_in is not None else None, _p(h_out), _p(ws),
-                                        C.c_size_t(ws.numel()), _stream(), C.byref(call)), "decoder_fwd_state_ex")
+    L.zeggs_decoder_fwd_state_ex(d, P, S, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot,
+                                 _f32r(h_in) if h_in is not None else None, h_out, ws, ws.numel(), _stream(), call)
     return pose, rpos, rrot, h_out
 
 
@@ -902,7 +797,7 @@ BATCH_PATHS = {0: None, 1: "persistent", 2: "stage"}
 def batch_last_path():
     """Which path this thread's last decoder_batch_chunk took: "persistent" (the weight-stationary sweep), "stage" (the stage
     launches: unsupported dimensions, a sweep that is switched off or gave up) or None."""
-    return BATCH_PATHS[int(lib().zeggs_decoder_batch_last_path())]
+    return BATCH_PATHS[api().zeggs_decoder_batch_last_path()]
 
 
 class BatchDecode:
@@ -916,15 +811,13 @@ class BatchDecode:
         self.B, self.chunk, self.SP, self.ST = int(B), int(chunk), int(SP), int(ST)
         self.PO, self.H, self.dt = int(self.stats[2].numel()), dec.recurrent_decoder.layer1.hidden_size, float(dt)
         self.film = 1 if len(self.params) == len(DEC_FIELDS) else 0
-        L = lib()
+        L = api()
         _route(current())
         d = self.dims(self.chunk)
-        self.ws = _ws(L.zeggs_decoder_batch_workspace_bytes(C.byref(d)), self.params[0].device)
+        self.ws = _ws(L.zeggs_decoder_batch_workspace_bytes(d), self.params[0].device)
         self.P = _ptrs(DecPtrs, DEC_FIELDS, self.params)
-        self.S = _ptrs(DecStats, ("in_mean", "in_std", "out_mean", "out_std"), self.stats)
-        self.mask = int(L.zeggs_decoder_batch_prepare(C.byref(d), C.byref(self.P), C.byref(self.S), _p(self.ws),
-                                                      C.c_size_t(self.ws.numel()), _stream()))
-        _check(min(self.mask, 0), "decoder_batch_prepare")
+        self.S = _ptrs(DecStats, STATS_FIELDS, self.stats)
+        self.mask = L.zeggs_decoder_batch_prepare(d, self.P, self.S, self.ws, self.ws.numel(), _stream())
         self.sweep = self.mask != 0
 
     def dims(self, T, B=None):
@@ -939,9 +832,7 @@ def decoder_state_init(bd, pose0, rpos0, rrot0, gaze0, style0):
     assert 1 <= n <= bd.B
     h = torch.empty(2, n, bd.H, device=pose0.device, dtype=torch.float32)
     d = bd.dims(1, n)
-    _check(lib().zeggs_decoder_state_init(C.byref(d), C.byref(bd.P), C.byref(bd.S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze0),
-                                          _p(style0), _p(h), _p(bd.ws), C.c_size_t(bd.ws.numel()), _stream()),
-           "decoder_state_init")
+    api().zeggs_decoder_state_init(d, bd.P, bd.S, pose0, rpos0, rrot0, gaze0, style0, h, bd.ws, bd.ws.numel(), _stream())
     return h
 
 
@@ -958,7 +849,7 @@ def decoder_batch_chunk(bd, pose0, rpos0, rrot0, gaze, speech, style, h_in, stat
     if B != bd.B or N > bd.chunk or N < 2 or SP != bd.SP or style.shape[2] != bd.ST:
         raise ValueError(f"decoder_batch_chunk: [{B},{N}] rows x frames on a BatchDecode of [{bd.B},<={bd.chunk}]")
     _route(current())
-    L = lib()
+    L = api()
     dev = pose0.device
     d = bd.dims(N)
     pose = torch.empty(B, N, bd.PO, device=dev, dtype=torch.float32)
@@ -969,9 +860,8 @@ def decoder_batch_chunk(bd, pose0, rpos0, rrot0, gaze, speech, style, h_in, stat
     call = DecCall(bd.mask, 0, None, status.data_ptr() if status is not None else None, 0)
 
     def run(mode, gaze=gaze, speech=speech, style=style):
-        _check(L.zeggs_decoder_fwd_batch(C.byref(d), C.byref(bd.P), C.byref(bd.S), _p(pose0), _p(rpos0), _p(rrot0), _p(gaze),
-                                         _p(speech), _p(style), _p(pose), _p(rpos), _p(rrot), _p(h_in), _p(h_out), _p(bd.ws),
-                                         C.c_size_t(bd.ws.numel()), _stream(), C.byref(call), int(mode)), "decoder_fwd_batch")
+        L.zeggs_decoder_fwd_batch(d, bd.P, bd.S, pose0, rpos0, rrot0, gaze, speech, style, pose, rpos, rrot, h_in, h_out, bd.ws,
+                                  bd.ws.numel(), _stream(), call, int(mode))
     run(1 if stage else 0)
     bits = 0
     if watch and batch_last_path() == "persistent":
@@ -989,42 +879,44 @@ def decoder_batch_chunk(bd, pose0, rpos0, rrot0, gaze, speech, style, h_in, stat
 
 
 # ----------------------------------------------------------------------------- live serving (zeggs/live.py)
-class LiveDims(C.Structure):       # mirrors ZeggsLiveDims
-    _fields_ = [("R", C.c_int), ("F", C.c_int), ("H", C.c_int), ("O", C.c_int), ("KW", C.c_int), ("D", C.c_int),
-                ("feat_ld", C.c_int), ("out_ld", C.c_int)]
-
-
-class LiveRow(C.Structure):        # mirrors ZeggsLiveRow
-    _fields_ = [("n_ring", C.c_long), ("k0", C.c_long), ("last", C.c_long), ("n_new", C.c_int), ("n_out", C.c_int),
-                ("feat_off", C.c_int), ("reserved", C.c_int)]
-
-
 LIVE_MAX_ROWS = 64                 # ZEGGS_LIVE_MAX_ROWS
 
 
 def mel_frames_ready(d, n_samples):
     """zeggs_mel_frames_ready (host only): animation frames computable from the first n_samples samples while the signal continues"""
-    return int(lib().zeggs_mel_frames_ready(C.byref(d), C.c_long(int(n_samples))))
+    return api().zeggs_mel_frames_ready(d, int(n_samples))
 
 
 def mel_window_first_sample(d, k0):
     """zeggs_mel_window_first_sample (host only): the smallest absolute sample index any frame >= k0 loads (d: audio.MelDims)"""
-    return int(lib().zeggs_mel_window_first_sample(C.byref(d), C.c_long(int(k0))))
+    return api().zeggs_mel_window_first_sample(d, int(k0))
 
 
-def mel_range_workspace(d, n_frames, device):
-    """a workspace that serves every zeggs_mel_features_range / _window call of at most n_frames frames"""
-    return _ws(lib().zeggs_mel_range_workspace_bytes(C.byref(d), C.c_long(0), C.c_long(int(n_frames))), device)
+def mel_range_workspace(d, n_frames, device, k0=0):
+    """a workspace that serves every zeggs_mel_features_range / _window call of at most n_frames frames (k0: sized for the rows
+    [k0, k0 + n_frames) exactly)"""
+    return _ws(api().zeggs_mel_range_workspace_bytes(d, int(k0), int(k0) + int(n_frames)), device)
+
+
+def _mel_out_fits(d, k0, k1, out):
+    return out.shape[0] == k1 - k0 and out.shape[1] == d.n_mels + 1
 
 
 def mel_features_window(d, wav_window, base, n_samples, final, filterbank, k0, k1, out, ws):
     """zeggs_mel_features_window: rows [k0, k1) of the feature table into `out` [k1 - k0, n_mels + 1] from a sliding window of the
     signal (wav_window[i] = sample base + i; n_samples = absolute count received so far)."""
-    if out.shape[0] != k1 - k0 or out.shape[1] != d.n_mels + 1 or wav_window.numel() < n_samples - base:
+    if not _mel_out_fits(d, k0, k1, out) or wav_window.numel() < n_samples - base:
         raise ValueError("mel_features_window: out / window do not match the range")
-    _check(lib().zeggs_mel_features_window(C.byref(d), _p(wav_window), C.c_long(int(base)), C.c_long(int(n_samples)), int(bool(final)),
-                                           C.c_void_p(filterbank.data_ptr()), C.c_long(int(k0)), C.c_long(int(k1)), _p(out), _p(ws),
-                                           C.c_size_t(ws.numel()), _stream()), "mel_features_window")
+    api().zeggs_mel_features_window(d, wav_window, int(base), int(n_samples), int(bool(final)), filterbank, int(k0), int(k1), out, ws,
+                                    ws.numel(), _stream())
+    return out
+
+
+def mel_features_range(d, wav, final, filterbank, k0, k1, out, ws):
+    """zeggs_mel_features_range: the same rows from the whole signal received so far (`wav`: every sample from the first one on)"""
+    if not _mel_out_fits(d, k0, k1, out):
+        raise ValueError("mel_features_range: out does not match the range")
+    api().zeggs_mel_features_range(d, wav, wav.numel(), int(bool(final)), filterbank, int(k0), int(k1), out, ws, ws.numel(), _stream())
     return out
 
 
@@ -1043,10 +935,9 @@ class LiveSpeech:
         self.mean, self.std = self.mean.expand(F).contiguous(), self.std.expand(F).contiguous()      # (scalars broadcast, as in torch)
         self.d = LiveDims(int(rows), F, H, O, KW, int(depth), int(feat_ld), int(out_ld))
         self.P = _ptrs(SpeechPtrs, SPEECH_FIELDS, self.params)
-        L = lib()
-        self.ws = _ws(L.zeggs_speech_encoder_live_workspace_bytes(C.byref(self.d)), self.params[0].device)
-        _check(L.zeggs_speech_encoder_live_prepare(C.byref(self.d), C.byref(self.P), _p(self.ws), C.c_size_t(self.ws.numel()),
-                                                   _stream()), "speech_encoder_live_prepare")
+        L = api()
+        self.ws = _ws(L.zeggs_speech_encoder_live_workspace_bytes(self.d), self.params[0].device)
+        L.zeggs_speech_encoder_live_prepare(self.d, self.P, self.ws, self.ws.numel(), _stream())
 
     def dims(self, feat_ld=None, out_ld=None):
         d = self.d
@@ -1062,8 +953,7 @@ def speech_encoder_live(ls, rows, feats, ring, out):
             tuple(out.shape) != (d.R, d.out_ld, d.O):
         raise ValueError("speech_encoder_live: tensor shapes do not match the LiveSpeech")
     arr = (LiveRow * d.R)(*rows)
-    _check(lib().zeggs_speech_encoder_live(C.byref(d), C.byref(ls.P), _p(ls.mean), _p(ls.std), arr, _p(feats), _p(ring), _p(out),
-                                           _p(ls.ws), C.c_size_t(ls.ws.numel()), _stream()), "speech_encoder_live")
+    api().zeggs_speech_encoder_live(d, ls.P, ls.mean, ls.std, arr, feats, ring, out, ls.ws, ls.ws.numel(), _stream())
     return out
 
 
@@ -1076,8 +966,7 @@ class _NormalizeFn(torch.autograd.Function):
         x = _f32c(x)
         W = x.shape[-1]
         y = torch.empty_like(x)
-        _check(lib().zeggs_normalize_vec_fwd(_p(x), _p(y), C.c_long(x.numel() // max(W, 1)), W, C.c_float(eps), _stream()),
-               "normalize_vec_fwd")
+        api().zeggs_normalize_vec_fwd(x, y, x.numel() // max(W, 1), W, eps, _stream())
         ctx.save_for_backward(x)
         ctx.eps = eps
         return y
@@ -1087,8 +976,7 @@ class _NormalizeFn(torch.autograd.Function):
         x, = ctx.saved_tensors
         W = x.shape[-1]
         dx = torch.empty_like(x)
-        _check(lib().zeggs_normalize_vec_bwd(_p(x), _p(_f32c(dy)), _p(dx), C.c_long(x.numel() // max(W, 1)), W,
-                                             C.c_float(ctx.eps), _stream()), "normalize_vec_bwd")
+        api().zeggs_normalize_vec_bwd(x, _f32c(dy), dx, x.numel() // max(W, 1), W, ctx.eps, _stream())
         return dx, None
 
 
@@ -1104,8 +992,7 @@ class _VectorizeFn(torch.autograd.Function):
         in_mean, in_std = _f32c(in_mean), _f32c(in_std)
         B, J = a[4].shape[0], a[4].shape[1]
         out = torch.empty(B, 9 + 15 * J, device=a[0].device, dtype=torch.float32)
-        _check(lib().zeggs_vectorize_input_fwd(B, J, *[_p(t) for t in a], _p(in_mean), _p(in_std), _p(out), _stream()),
-               "vectorize_input_fwd")
+        api().zeggs_vectorize_input_fwd(B, J, *a, in_mean, in_std, out, _stream())
         ctx.save_for_backward(a[0], a[1], a[8], in_std)
         ctx.shapes = [t.shape for t in a]
         ctx.dims = (B, J)
@@ -1116,8 +1003,7 @@ class _VectorizeFn(torch.autograd.Function):
         root_pos, root_rot, gaze_pos, in_std = ctx.saved_tensors
         B, J = ctx.dims
         g = [torch.empty(sh, device=root_pos.device, dtype=torch.float32) for sh in ctx.shapes]
-        _check(lib().zeggs_vectorize_input_bwd(B, J, _p(root_pos), _p(root_rot), _p(gaze_pos), _p(in_std), _p(_f32c(dout)),
-                                               *[_p(t) for t in g], _stream()), "vectorize_input_bwd")
+        api().zeggs_vectorize_input_bwd(B, J, root_pos, root_rot, gaze_pos, in_std, _f32c(dout), *g, _stream())
         return (*g, None, None)
 
 
@@ -1136,9 +1022,7 @@ class _DevectorizeFn(torch.autograd.Function):
         pose = torch.empty(B, 6 + 15 * J, device=dev, dtype=torch.float32)
         nrp = torch.empty(B, 3, device=dev, dtype=torch.float32)
         nrr = torch.empty(B, 4, device=dev, dtype=torch.float32)
-        _check(lib().zeggs_devectorize_output_fwd(B, J, C.c_float(dt), _p(predicted), _p(root_pos), _p(root_rot),
-                                                  _p(out_mean), _p(out_std), _p(pose), _p(nrp), _p(nrr), _stream()),
-               "devectorize_output_fwd")
+        api().zeggs_devectorize_output_fwd(B, J, dt, predicted, root_pos, root_rot, out_mean, out_std, pose, nrp, nrr, _stream())
         ctx.save_for_backward(predicted, root_pos, root_rot, out_mean, out_std)
         ctx.dims = (B, J, dt)
         ctx.set_materialize_grads(False)
@@ -1148,11 +1032,10 @@ class _DevectorizeFn(torch.autograd.Function):
     def backward(ctx, dpose, dnrp, dnrr):
         predicted, root_pos, root_rot, out_mean, out_std = ctx.saved_tensors
         B, J, dt = ctx.dims
-        c = lambda g: _p(_f32c(g)) if g is not None else None  # noqa: E731
+        c = lambda g: _f32c(g) if g is not None else None  # noqa: E731
         dpred, drp, drr = torch.empty_like(predicted), torch.empty_like(root_pos), torch.empty_like(root_rot)
-        _check(lib().zeggs_devectorize_output_bwd(B, J, C.c_float(dt), _p(predicted), _p(root_pos), _p(root_rot),
-                                                  _p(out_mean), _p(out_std), c(dpose), c(dnrp), c(dnrr), _p(dpred), _p(drp),
-                                                  _p(drr), _stream()), "devectorize_output_bwd")
+        api().zeggs_devectorize_output_bwd(B, J, dt, predicted, root_pos, root_rot, out_mean, out_std, c(dpose), c(dnrp), c(dnrr),
+                                           dpred, drp, drr, _stream())
         return dpred, drp, drr, None, None, None, None
 
 
@@ -1166,8 +1049,7 @@ class _KLFn(torch.autograd.Function):
     def forward(ctx, mu, logvar):
         mu, logvar = _f32c(mu), _f32c(logvar)
         out = torch.empty((), device=mu.device, dtype=torch.float32)
-        _check(lib().zeggs_kl_div_fwd(_p(mu), _p(logvar), mu.shape[0], mu.numel() // mu.shape[0], _p(out), _stream()),
-               "kl_div_fwd")
+        api().zeggs_kl_div_fwd(mu, logvar, mu.shape[0], mu.numel() // mu.shape[0], out, _stream())
         ctx.save_for_backward(mu, logvar)
         return out
 
@@ -1175,8 +1057,7 @@ class _KLFn(torch.autograd.Function):
     def backward(ctx, dout):
         mu, logvar = ctx.saved_tensors
         dmu, dlv = torch.empty_like(mu), torch.empty_like(logvar)
-        _check(lib().zeggs_kl_div_bwd(_p(mu), _p(logvar), mu.shape[0], mu.numel() // mu.shape[0], _p(_f32c(dout).reshape(1)),
-                                      _p(dmu), _p(dlv), _stream()), "kl_div_bwd")
+        api().zeggs_kl_div_bwd(mu, logvar, mu.shape[0], mu.numel() // mu.shape[0], _f32c(dout).reshape(1), dmu, dlv, _stream())
         return dmu, dlv
 
 
@@ -1192,7 +1073,7 @@ def mask_from_lengths(lengths):
     B = lengths.shape[0]
     max_len = int(lengths.max().item())
     mask = torch.empty(B, max_len, device=lengths.device, dtype=torch.uint8)
-    _check(lib().zeggs_mask_from_lengths(_p(lengths), B, max_len, _p(mask), _stream()), "mask_from_lengths")
+    api().zeggs_mask_from_lengths(lengths, B, max_len, mask, _stream())
     return mask.view(torch.bool)
 
 
@@ -1208,21 +1089,19 @@ class _LossFn(torch.autograd.Function):
         has_kl = mu is not None and kl_weight > 0
         S = mu.shape[1] if mu is not None else 0
         d = LossDims(B, T, J, S, float(dt))
-        L = lib()
+        L = api()
         dev = o_pose.device
-        need = L.zeggs_loss_workspace_bytes(C.byref(d))
+        need = L.zeggs_loss_workspace_bytes(d)
         prepared = truth_ws is not None and truth_ws.numel() >= need       # (loss_prepare_truth filled its truth half)
         ws = truth_ws if prepared else _ws(need, dev)
         terms = torch.empty(19, device=dev, dtype=torch.float32)
         dpose, drpos, drrot = torch.empty_like(o_pose), torch.empty_like(o_rpos), torch.empty_like(o_rrot)
         dmu = torch.empty(B, S, device=dev) if mu is not None else None
         dlv = torch.empty(B, S, device=dev) if mu is not None else None
-        _check(L.zeggs_loss_fwd_bwd_ex(C.byref(d), _p(parents), _p(o_pose), _p(o_rpos), _p(o_rrot), _p(w_pose),
-                                       _p(w_rpos), _p(w_rrot), _p(gaze), _p(_f32c(mu)) if mu is not None else None,
-                                       _p(_f32c(logvar)) if mu is not None else None,
-                                       C.c_float(kl_weight if has_kl else 0.0), _p(terms), _p(dpose), _p(drpos),
-                                       _p(drrot), _p(dmu), _p(dlv), C.c_float(gscale), _p(ws), C.c_size_t(ws.numel()),
-                                       _stream(), int(prepared)), "loss_fwd_bwd")
+        L.zeggs_loss_fwd_bwd_ex(d, parents, o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze,
+                                _f32c(mu) if mu is not None else None, _f32c(logvar) if mu is not None else None,
+                                kl_weight if has_kl else 0.0, terms, dpose, drpos, drrot, dmu, dlv, gscale, ws, ws.numel(), _stream(),
+                                int(prepared))
         ctx.save_for_backward(dpose, drpos, drrot, dmu, dlv)
         ctx.unit_grad = bool(unit_grad)
         ctx.mark_non_differentiable(terms)
@@ -1250,12 +1129,11 @@ def loss_prepare_truth(w_pose, w_rpos, w_rrot, gaze, parents, dt, ws=None):
     w_pose, w_rpos, w_rrot, gaze = (_f32c(t) for t in (w_pose, w_rpos, w_rrot, gaze))
     B, T, PO = w_pose.shape
     d = LossDims(B, T, (PO - 6) // 15, 0, float(dt))
-    L = lib()
-    need = int(L.zeggs_loss_workspace_bytes(C.byref(d)))
+    L = api()
+    need = int(L.zeggs_loss_workspace_bytes(d))
     if ws is None or ws.numel() != need or ws.device != w_pose.device:
         ws = _ws(need, w_pose.device)
-    _check(L.zeggs_loss_prepare_truth(C.byref(d), _p(parents), _p(w_pose), _p(w_rpos), _p(w_rrot), _p(gaze), _p(ws),
-                                      C.c_size_t(ws.numel()), _stream()), "loss_prepare_truth")
+    L.zeggs_loss_prepare_truth(d, parents, w_pose, w_rpos, w_rrot, gaze, ws, ws.numel(), _stream())
     return ws
 
 
@@ -1271,13 +1149,6 @@ def training_loss(o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, parents,
 EVAL_COLS = 22                                     # ZEGGS_EVAL_COLS
 
 
-def _pd(t, dtype):
-    """device pointer of a contiguous tensor of `dtype` (float64 tables / int32 group indices of the evaluation calls)"""
-    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
-        raise RuntimeError(f"zeggs.ops: expected a contiguous {dtype} tensor on a GPU")
-    return C.c_void_p(t.data_ptr())
-
-
 def loss_eval(o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, parents, dt, mu=None, logvar=None, rows=None, ws=None):
     """The loss section's forward alone, per window (zeggs_loss_eval) -> rows float64 [B, EVAL_COLS]: columns 0..16 the weighted
     L1 terms of each window, 17 its unweighted KL (0 without mu), 18 MPJPE, 19 root drift at the last frame, 20 / 21 mean joint
@@ -1287,17 +1158,15 @@ def loss_eval(o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, parents, dt,
     B, T, PO = o_pose.shape
     S = mu.shape[1] if mu is not None else 0
     d = LossDims(B, T, (PO - 6) // 15, S, float(dt))
-    L = lib()
+    L = api()
     dev = o_pose.device
-    need = int(L.zeggs_loss_eval_workspace_bytes(C.byref(d)))
+    need = int(L.zeggs_loss_eval_workspace_bytes(d))
     if ws is None or ws.numel() < need or ws.device != dev:
         ws = _ws(need, dev)
     if rows is None or tuple(rows.shape) != (B, EVAL_COLS) or rows.device != dev:
         rows = torch.empty(B, EVAL_COLS, device=dev, dtype=torch.float64)
-    _check(L.zeggs_loss_eval(C.byref(d), _p(parents), _p(o_pose), _p(o_rpos), _p(o_rrot), _p(w_pose), _p(w_rpos), _p(w_rrot),
-                             _p(gaze), _p(_f32c(mu)) if mu is not None else None,
-                             _p(_f32c(logvar)) if mu is not None else None, _pd(rows, torch.float64), _p(ws),
-                             C.c_size_t(ws.numel()), _stream()), "loss_eval")
+    L.zeggs_loss_eval(d, parents, o_pose, o_rpos, o_rrot, w_pose, w_rpos, w_rrot, gaze, _f32c(mu) if mu is not None else None,
+                      _f32c(logvar) if mu is not None else None, rows, ws, ws.numel(), _stream())
     return rows
 
 
@@ -1306,10 +1175,10 @@ class fixed_order_gemms:
     over workgroups (zeggs_gemm_fixed_order): no fp32 atomics, so a forward pass is bitwise the same on every call."""
 
     def __enter__(self):
-        self.prev = lib().zeggs_gemm_fixed_order(1)
+        self.prev = api().zeggs_gemm_fixed_order(1)
 
     def __exit__(self, *exc):
-        lib().zeggs_gemm_fixed_order(int(self.prev))
+        api().zeggs_gemm_fixed_order(int(self.prev))
         return False
 
 
@@ -1325,7 +1194,7 @@ def gemm_route_log(reset=False):
     {"route", "splitk" (1 unsplit, 0 stream-K), "tile": (BM, BN)} of the last product and "counts": {route: launches since the last
     reset} (routes never taken are left out).  reset: clear the log after reading it."""
     last, counts = (C.c_int * 4)(), (C.c_long * len(GEMM_ROUTES))()
-    n = lib().zeggs_test_gemm_route_log(int(bool(reset)), last, counts, len(GEMM_ROUTES))
+    n = api().zeggs_test_gemm_route_log(int(bool(reset)), last, counts, len(GEMM_ROUTES))
     if n != len(GEMM_ROUTES):
         raise RuntimeError(f"zeggs.ops.GEMM_ROUTES names {len(GEMM_ROUTES)} routes, the library has {n}: rebuild it")
     return {"route": GEMM_ROUTES[last[0]], "splitk": int(last[1]), "tile": (int(last[2]), int(last[3])),
@@ -1335,7 +1204,7 @@ def gemm_route_log(reset=False):
 def loss_eval_workspace(B, T, J, S, dt, device):
     """a workspace for loss_eval calls of these dimensions (zeggs_loss_eval_workspace_bytes)"""
     d = LossDims(int(B), int(T), int(J), int(S), float(dt))
-    return _ws(lib().zeggs_loss_eval_workspace_bytes(C.byref(d)), device)
+    return _ws(api().zeggs_loss_eval_workspace_bytes(d), device)
 
 
 def eval_accumulate(rows, group, acc):
@@ -1343,8 +1212,7 @@ def eval_accumulate(rows, group, acc):
     [B], a negative entry leaves its row out; the last column of acc counts the rows.  The caller zeroes acc once."""
     B, groups = rows.shape[0], acc.shape[0]
     assert rows.shape == (B, EVAL_COLS) and acc.shape == (groups, EVAL_COLS + 1) and group.shape == (B,)
-    _check(lib().zeggs_eval_accumulate(_pd(rows, torch.float64), _pd(group, torch.int32), int(B), int(groups),
-                                       _pd(acc, torch.float64), _stream()), "eval_accumulate")
+    api().zeggs_eval_accumulate(rows, group, int(B), int(groups), acc, _stream())
     return acc
 
 
@@ -1356,17 +1224,13 @@ def radam_step(p, g, m, v, beta1, beta2, eps, step_scale, rectified, status=None
     decay = weight_decay * lr (reference optimizers.py:88-95), 0 when the step is not applied."""
     # the complements in double, as the reference forms them: float(1 - 0.999) = 0.001f, while 1.f - 0.999f = 0.00099998713; the
     # kernel rounds them for the second moment and forms the first moment in double (zeggs_radam_step_d)
-    _check(lib().zeggs_radam_step_d(_p(p), _p(g), _p(m), _p(v), C.c_long(p.numel()), C.c_double(beta1), C.c_double(beta2),
-                                    C.c_double(1 - beta1), C.c_double(1 - beta2), C.c_float(eps), C.c_float(step_scale),
-                                    int(rectified), C.c_float(decay),
-                                    C.c_void_p(status.data_ptr()) if status is not None else None,
-                                    _p(gflag) if gflag is not None and status is not None else None, int(bool(count)), _stream()),
-           "radam_step")
+    api().zeggs_radam_step_d(p, g, m, v, p.numel(), beta1, beta2, 1 - beta1, 1 - beta2, eps, step_scale, int(rectified), decay, status,
+                             gflag if status is not None else None, int(bool(count)), _stream())
 
 
 def status_flag(status, dst):
     """dst[0] (device float) = 1.0 if status[0] has a give-up bit, else 0.0 -- the word that rides on the gradient all-reduce"""
-    _check(lib().zeggs_status_flag(C.c_void_p(status.data_ptr()), _p(dst), _stream()), "status_flag")
+    api().zeggs_status_flag(status, dst, _stream())
 
 
 def gather_windows(frames, starts, T, out=None):
@@ -1374,7 +1238,7 @@ def gather_windows(frames, starts, T, out=None):
     B, W = starts.shape[0], frames.shape[1]
     if out is None or out.shape != (B, T, W) or not out.is_contiguous():
         out = torch.empty(B, T, W, device=frames.device, dtype=torch.float32)
-    _check(lib().zeggs_gather_windows(_p(frames), W, _p(starts), B, T, _p(out), _stream()), "gather_windows")
+    api().zeggs_gather_windows(frames, W, starts, B, T, out, _stream())
     return out
 
 
@@ -1385,8 +1249,7 @@ def gather_rows(frames, rows, out=None, out_ld=None):
     if out is None:
         out = torch.empty(*rows.shape, W, device=frames.device, dtype=torch.float32)
         out_ld = W
-    _check(lib().zeggs_gather_rows(_p(frames), W, _p(rows.contiguous()), C.c_long(n), _p(out), int(out_ld), _stream()),
-           "gather_rows")
+    api().zeggs_gather_rows(frames, W, rows.contiguous(), n, out, int(out_ld), _stream())
     return out
 
 
@@ -1396,12 +1259,11 @@ def normalize_rows_(x, mean, std):
     rows = x.numel() // W
     vec = std if torch.is_tensor(std) and std.dim() > 0 else None
     sc = 1.0 if vec is not None else float(std)
-    _check(lib().zeggs_normalize_rows(_p(x), C.c_long(rows), W, C.c_long(W), _p(mean), _p(vec) if vec is not None else None,
-                                      C.c_float(sc), _stream()), "normalize_rows")
+    api().zeggs_normalize_rows(x, rows, W, W, mean, vec, sc, _stream())
     return x
 
 
-_OPTIONS = {}            # switches set through set_option / ZEGGS_OPTIONS (the library's defaults otherwise)
+_OPTIONS = capi.OPTIONS  # switches set through set_option / ZEGGS_OPTIONS (the library's defaults otherwise)
 _PERSISTENT_OPTION = ("persistent", "train_persistent", "bwd_persistent")
 
 
@@ -1409,13 +1271,13 @@ def _persistent_live(which):
     """True if persistent kernel `which` (0 B=1 decode, 1 training rollout, 2 BPTT sweep) is switched on and validated on this
     process -- only then can a call have ended in an undetected give-up (an unvalidated kernel is checked, with a stream
     synchronisation, by the library itself)."""
-    return _OPTIONS.get(_PERSISTENT_OPTION[which], 1) != 0 and lib().zeggs_persistent_state(which) == 1
+    return _OPTIONS.get(_PERSISTENT_OPTION[which], 1) != 0 and api().zeggs_persistent_state(which) == 1
 
 
 def set_option(name, value):
     """Runtime switches of the library (e.g. "decoder_fast": 1 packed stage kernels / 0 generic GEMM path)."""
     global _CHAIN_DIAGNOSTICS, _LAST_DECODER_WS
-    _check(lib().zeggs_set_option(name.encode(), int(value)), "set_option")
+    api().zeggs_set_option(name.encode(), int(value))
     _OPTIONS[name] = int(value)
     if name == "chain":
         _CHAIN_DIAGNOSTICS = bool(value)

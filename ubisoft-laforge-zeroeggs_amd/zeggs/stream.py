@@ -15,8 +15,6 @@ Latency = 15 frames of look-ahead (250 ms at 60 fps) + one STFT window; `finish(
 right-edge rules.  BS.1770 loudness normalisation needs the whole signal and is therefore a pre-pass the caller
 applies (or skips) before streaming, as in the offline path.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
@@ -64,9 +62,6 @@ class GestureStream:
         # one, so a rollout that did not complete must be noticed before it is carried forward (checked after every chunk)
         self.status = ops.new_status(self.dev)
         self.redone_chunks = 0
-        self._L = ops.lib()
-        self._L.zeggs_mel_frames_ready.restype = C.c_long
-        self._L.zeggs_mel_range_workspace_bytes.restype = C.c_size_t
 
     # ------------------------------------------------------------------ audio features
     def _extend_features(self, k1, final):
@@ -74,16 +69,8 @@ class GestureStream:
         if k1 <= k0:
             return
         w = torch.as_tensor(self.wav, device=self.dev)
-        L, d = self._L, self.mel
-        ws = torch.empty(int(L.zeggs_mel_range_workspace_bytes(C.byref(d), C.c_long(k0), C.c_long(k1))), dtype=torch.uint8,
-                         device=self.dev)
-        out = torch.empty(k1 - k0, d.n_mels + 1, device=self.dev, dtype=torch.float32)
-        rc = L.zeggs_mel_features_range(C.byref(d), C.c_void_p(w.data_ptr()), C.c_long(w.numel()), int(final),
-                                        C.c_void_p(self.fb.data_ptr()), C.c_long(k0), C.c_long(k1),
-                                        C.c_void_p(out.data_ptr()), C.c_void_p(ws.data_ptr()), C.c_size_t(ws.numel()),
-                                        C.c_void_p(torch.cuda.current_stream().cuda_stream))
-        if rc != 0:
-            raise RuntimeError("zeggs_mel_features_range: " + L.zeggs_last_error().decode())
+        out = torch.empty(k1 - k0, self.mel.n_mels + 1, device=self.dev, dtype=torch.float32)
+        ops.mel_features_range(self.mel, w, final, self.fb, k0, k1, out, ops.mel_range_workspace(self.mel, k1 - k0, self.dev, k0))
         self.feats = torch.cat([self.feats, out], dim=0)
 
     # ------------------------------------------------------------------ decode frames [n_emitted, upto)
@@ -106,32 +93,15 @@ class GestureStream:
         with torch.no_grad():
             sp = self.speech_net(x)[:, (k0 - 1 - lo):(k1 - lo)].contiguous()          # [1, N+1, SP]
         N1 = sp.shape[1]
-        d = ops.DecDims(1, N1, self.pose.shape[1] + 3, self.pose.shape[1], sp.shape[2], self.style.shape[1],
-                        self.decoder.recurrent_decoder.layer1.hidden_size, self.dt,
-                        1 if hasattr(self.decoder.recurrent_decoder, "gammas_predictor") else 0)
-        L = self._L
-        params = [t.detach().to(torch.float32).contiguous() for t in ops.decoder_param_list(self.decoder)]
-        P = ops._ptrs(ops.DecPtrs, ops.DEC_FIELDS, params)
-        S = ops._ptrs(ops.DecStats, ("in_mean", "in_std", "out_mean", "out_std"),
-                      [self.stats[k].contiguous() for k in ("anim_input_mean", "anim_input_std", "anim_output_mean",
-                                                            "anim_output_std")])
-        ws = torch.empty(int(L.zeggs_decoder_workspace_bytes(C.byref(d), 0)), dtype=torch.uint8, device=self.dev)
         gaze = self.gaze.repeat(N1, 1)[None].contiguous()
         style = self.style.repeat(N1, 1)[None].contiguous()
-        pose = torch.empty(1, N1, d.PO, device=self.dev)
-        rpos, rrot = torch.empty(1, N1, 3, device=self.dev), torch.empty(1, N1, 4, device=self.dev)
-        h_out = torch.empty(2, 1, d.H, device=self.dev)
-        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None  # noqa: E731
-        call = ops.DecCall(0, 0, None, self.status.data_ptr(), 0)
+        st = self.stats
 
         def run():
-            rc = L.zeggs_decoder_fwd_state_ex(C.byref(d), C.byref(P), C.byref(S), p(self.pose), p(self.rpos), p(self.rrot),
-                                              p(gaze), p(sp), p(style), p(pose), p(rpos), p(rrot), p(self.h), p(h_out), p(ws),
-                                              C.c_size_t(ws.numel()), C.c_void_p(torch.cuda.current_stream().cuda_stream),
-                                              C.byref(call))
-            if rc != 0:
-                raise RuntimeError("zeggs_decoder_fwd_state_ex: " + L.zeggs_last_error().decode())
-        run()
+            return ops.decoder_chunk(self.decoder, self.pose, self.rpos, self.rrot, gaze, sp, style, st["anim_input_mean"],
+                                     st["anim_input_std"], st["anim_output_mean"], st["anim_output_std"], self.dt, h_in=self.h,
+                                     status=self.status)
+        pose, rpos, rrot, h_out = run()
         if ops._persistent_live(0):       # a validated persistent kernel may have run: look at the word before the chunk's
             bits = int(self.status[0].item())     # state becomes the next chunk's input (the frames go to the host anyway)
             if bits:
@@ -139,7 +109,7 @@ class GestureStream:
                 ops.set_option("persistent", 0)
                 ops.fill_(self.status.view(torch.float32))
                 self.redone_chunks += 1
-                run()                     # same inputs (self.pose / self.h are untouched so far), stage launches
+                pose, rpos, rrot, h_out = run()      # same inputs (self.pose / self.h are untouched so far), stage launches
         self.h = h_out
         self.pose, self.rpos, self.rrot = pose[:, -1].contiguous(), rpos[:, -1].contiguous(), rrot[:, -1].contiguous()
         out.setdefault("pose", []).append(pose[0, 1:])
@@ -158,7 +128,7 @@ class GestureStream:
         frames that became computable (possibly an empty dict)"""
         assert not self.finished
         self.wav = np.concatenate([self.wav, np.asarray(wav_chunk, np.float32)])
-        ready = int(self._L.zeggs_mel_frames_ready(C.byref(self.mel), C.c_long(len(self.wav))))
+        ready = ops.mel_frames_ready(self.mel, len(self.wav))
         # never run ahead of the final frame count (it can only grow with more samples)
         ready = min(ready, audio.n_anim_frames(len(self.wav)) - 1)
         self._extend_features(ready, final=False)
