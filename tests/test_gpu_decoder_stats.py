@@ -5,8 +5,8 @@ Why: synth.make_stats() and both recorded statistics files have out_mean == in_m
 fold of the statistics into the weights (decoder_fast.hip merge_prep_k / cvec, tp_common.h cv0 / p1x, train_dual.hip,
 decode_persistent.hip, the unfolded form and its BPTT in decoder.hip) was zero in every test; and with them the half turn per frame
 h = dt / 2 |root_vrt| stays in [2.8e-3, 6.4e-3], one of the three branches (h < 1e-5: quat_normalize([1, x]); h < 1: polynomials;
-h >= 1: libm) of quat_exp_mul / quat_exp / qexp_bwd / quat_exp_ctx / qexp_bwd_ctx (dec_math.h) and qexp_bwd_coef
-(train_bwd_persistent.hip).  helpers.decoder_stats(kind) gives the statistics, tests/test_decoder_stats_oracle_cpu.py proves on the
+h >= 1: libm) of quat_exp_mul (root_step) and quat_exp_ctx with qexp_bwd_ctx / qexp_bwd_coef (root_bwd / root_prepare), all in
+dec_math.h, the one statement every decoder kernel calls.  helpers.decoder_stats(kind) gives the statistics, tests/test_decoder_stats_oracle_cpu.py proves on the
 CPU that every case lies in its branch and that each bound below trips on the bug it is meant for.
 
 Which case launches which kernels (helpers.DEC_TRAIN_CASES / DEC_INFER_CASES; every case asserts it):

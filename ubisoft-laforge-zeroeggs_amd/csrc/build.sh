@@ -9,7 +9,12 @@ mkdir -p $BD
 pids=()
 SRC="gemm gemm_split kernels attention encoders options decoder decoder_fast sweep_sync decode_persistent train_persistent train_dual train_bwd_persistent loudness loss misc mel anim prepare style_gru hostio text funcs live"
 for f in $SRC; do
-  if [ ! -f $BD/$f.o ] || [ $f.hip -nt $BD/$f.o ] || [ common.h -nt $BD/$f.o ] || [ anim_math.h -nt $BD/$f.o ] || [ decoder_ws.h -nt $BD/$f.o ] || [ dec_math.h -nt $BD/$f.o ] || [ ../../include/zeggs_hip.h -nt $BD/$f.o ] || [ kernels.h -nt $BD/$f.o ] || [ gemm.h -nt $BD/$f.o ] || [ tp_common.h -nt $BD/$f.o ] || [ sweep_sync.h -nt $BD/$f.o ] || [ dec_prologue.h -nt $BD/$f.o ] || [ gemm_route.h -nt $BD/$f.o ] || [ text_math.h -nt $BD/$f.o ]; then
+  stale=0
+  [ -f $BD/$f.o ] || stale=1
+  for dep in $f.hip *.h ../../include/zeggs_hip.h; do      # every header: one missing from a list means stale objects
+    if [ $dep -nt $BD/$f.o ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-result $ZEGGS_DEFS -c $f.hip -o $BD/$f.o &
     pids+=($!)
   fi

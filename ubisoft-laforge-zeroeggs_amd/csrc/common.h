@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
+#include "quat_math.h"
 
 // ---------------------------------------------------------------- error state
 // last-error string (thread-local); every extern "C" entry returns 0 or -1.
@@ -85,35 +86,6 @@ __device__ __forceinline__ float d_act(float x, int act) {
   if (act == ACT_ELU) return d_elu(x);
   if (act == ACT_RELU) return x > 0.f ? x : 0.f;
   return x;
-}
-
-struct V3 {
-  float x, y, z;
-};
-__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
-__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return V3{a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return V3{a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ V3 operator*(float s, V3 a) { return V3{s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) {
-  return V3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x};
-}
-__device__ __forceinline__ float dot(V3 a, V3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-struct Q4 {
-  float w, x, y, z;
-};
-// reference anim/tquat.py:18-20: t = 2 (q_v x v); v + w t + q_v x t
-__device__ __forceinline__ V3 quat_mul_vec(Q4 q, V3 v) {
-  V3 qv = v3(q.x, q.y, q.z);
-  V3 t = 2.0f * cross(qv, v);
-  return v + q.w * t + cross(qv, t);
-}
-__device__ __forceinline__ Q4 quat_inv(Q4 q) { return Q4{q.w, -q.x, -q.y, -q.z}; }
-// reference anim/tquat.py:6-15
-__device__ __forceinline__ Q4 quat_mul(Q4 x, Q4 y) {
-  return Q4{y.w * x.w - y.x * x.x - y.y * x.y - y.z * x.z,
-            y.w * x.x + y.x * x.w - y.y * x.z + y.z * x.y,
-            y.w * x.y + y.x * x.z + y.y * x.w - y.z * x.x,
-            y.w * x.z - y.x * x.y + y.y * x.x + y.z * x.w};
 }
 
 // counter-based RNG for dropout masks / the VAE noise: same (seed, index) -> same bits in fwd and bwd.

@@ -27,7 +27,7 @@ __device__ __forceinline__ void dec_init_body(int b, const ZeggsDecDims& d, cons
     float* r = rrot + ((long)b * d.T) * 4; r[0] = q.w; r[1] = q.x; r[2] = q.y; r[3] = q.z;
     for (int f = 0; f < 2 && f < d.T; ++f) {
       const float* gz = gaze + ((long)b * d.T + f) * 3;
-      V3 gd = quat_mul_vec(quat_inv(q), v3(gz[0], gz[1], gz[2]) - rp);
+      V3 gd = gaze_dir(q, rp, v3(gz[0], gz[1], gz[2]));
       float gv[3] = {gd.x, gd.y, gd.z};
       for (int k = 0; k < 3; ++k) {
         float e = (gv[k] - st.in_mean[d.PO + k]) / st.in_std[d.PO + k];

@@ -274,18 +274,12 @@ __global__ __launch_bounds__(PTHR, 2) void decode_persistent_k(PArgs a) {
       for (int q = 0; q < 7; ++q) rt[q] = rootst[q];
       if (next) { const float* gz = a.gaze + (long)(t + 1) * 3; rt[7] = gz[0]; rt[8] = gz[1]; rt[9] = gz[2]; }
       V3 npos; Q4 nq;
-      {   // root_step of decoder_fast.hip, restated here (file-local there)
-        const Q4 q = Q4{rt[0], rt[1], rt[2], rt[3]};
-        const V3 pos = v3(rt[4], rt[5], rt[6]);
-        npos = quat_mul_vec(q, d.dt * v3(p[0], p[1], p[2])) + pos;
-        const V3 uu = quat_mul_vec(q, d.dt * v3(p[3], p[4], p[5]));
-        nq = quat_exp_mul(0.5f * uu, q);
-        if (next) {
-          const V3 gd = quat_mul_vec(quat_inv(nq), v3(rt[7], rt[8], rt[9]) - npos);
-          genc[0] = (gd.x - cg[0]) * cg[3];
-          genc[1] = (gd.y - cg[1]) * cg[4];
-          genc[2] = (gd.z - cg[2]) * cg[5];
-        }
+      root_step(d.dt, Q4{rt[0], rt[1], rt[2], rt[3]}, v3(rt[4], rt[5], rt[6]), p, npos, nq);
+      if (next) {
+        const V3 gd = gaze_dir(nq, npos, v3(rt[7], rt[8], rt[9]));
+        genc[0] = (gd.x - cg[0]) * cg[3];
+        genc[1] = (gd.y - cg[1]) * cg[4];
+        genc[2] = (gd.z - cg[2]) * cg[5];
       }
       rootst[0] = nq.w; rootst[1] = nq.x; rootst[2] = nq.y; rootst[3] = nq.z;
       rootst[4] = npos.x; rootst[5] = npos.y; rootst[6] = npos.z;

@@ -56,13 +56,9 @@ __global__ void gru_gate_fwd_k(const float* gi, const float* gh, const float* hp
     long b = i / H;
     const float* gib = gi + b * 3 * H;
     const float* ghb = gh + b * 3 * H;
-    float r = d_sigmoid(gib[u] + ghb[u]);
-    float z = d_sigmoid(gib[H + u] + ghb[H + u]);
-    float nh = ghb[2 * H + u];
-    float nn = d_tanh(gib[2 * H + u] + r * nh);
-    float hp = hprev[i];
-    hout[i] = (1.f - z) * nn + z * hp;
-    if (GT) GT[i] = f4{r, z, nn, nh};
+    f4 gt;
+    hout[i] = gru_cell_fwd(gib[u] + ghb[u], gib[H + u] + ghb[H + u], gib[2 * H + u], ghb[2 * H + u], hprev[i], gt);
+    if (GT) GT[i] = gt;
   }
 }
 
@@ -74,18 +70,12 @@ __global__ void gru_gate_bwd_k(const float* dh, const f4* GT, const float* hprev
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     int u = (int)(i % H);
     long b = i / H;
-    const f4 gt = GT[i];
-    float g = dh[i], r = gt.x, z = gt.y, nn = gt.z, nh = gt.w, hp = hprev[i];
-    float dn = g * (1.f - z);
-    float dz = g * (hp - nn);
-    float dan = dn * (1.f - nn * nn);
-    float dar = dan * nh * r * (1.f - r);
-    float daz = dz * z * (1.f - z);
+    const GruGrad gg = gru_cell_bwd(dh[i], GT[i], hprev[i]);
     float* dib = di + b * 3 * H;
     float* dhb = dhh + b * 3 * H;
-    dib[u] = dar; dib[H + u] = daz; dib[2 * H + u] = dan;
-    dhb[u] = dar; dhb[H + u] = daz; dhb[2 * H + u] = dan * r;
-    dhc[i] = g * z;
+    dib[u] = gg.dar; dib[H + u] = gg.daz; dib[2 * H + u] = gg.dan;
+    dhb[u] = gg.dar; dhb[H + u] = gg.daz; dhb[2 * H + u] = gg.dhn();
+    dhc[i] = gg.dhc();
   }
 }
 
@@ -107,45 +97,17 @@ __global__ void dec_devec_k(ZeggsDecDims d, ZeggsDecStats st, const float* y, in
     const float* rp = rpos + ((long)b * d.T + t - 1) * 3;
     Q4 q = Q4{rq[0], rq[1], rq[2], rq[3]};
     V3 pos = v3(rp[0], rp[1], rp[2]);
-#if defined(ZEGGS_ROOT_FP64) && ZEGGS_ROOT_FP64
-    // DIAGNOSTIC build (tools/drift_ab.py): the root integration of the generic path evaluated in float64 from the same fp32
-    // inputs, rounded once at the end -- separates "rounding inside the root integration" from everything else
     V3 npos; Q4 nq;
-    {
-      auto qmv = [](const double* q4, const double* v, double* o) {
-        const double tx = 2.0 * (q4[2] * v[2] - q4[3] * v[1]), ty = 2.0 * (q4[3] * v[0] - q4[1] * v[2]),
-                     tz = 2.0 * (q4[1] * v[1] - q4[2] * v[0]);
-        o[0] = v[0] + q4[0] * tx + (q4[2] * tz - q4[3] * ty);
-        o[1] = v[1] + q4[0] * ty + (q4[3] * tx - q4[1] * tz);
-        o[2] = v[2] + q4[0] * tz + (q4[1] * ty - q4[2] * tx);
-      };
-      const double qd[4] = {q.w, q.x, q.y, q.z}, dtd = (double)d.dt;
-      const double v[3] = {dtd * p[0], dtd * p[1], dtd * p[2]}, w3[3] = {dtd * p[3], dtd * p[4], dtd * p[5]};
-      double o[3], u3[3];
-      qmv(qd, v, o);
-      npos = v3((float)(o[0] + pos.x), (float)(o[1] + pos.y), (float)(o[2] + pos.z));
-      qmv(qd, w3, u3);
-      const double hx = 0.5 * u3[0], hy = 0.5 * u3[1], hz = 0.5 * u3[2], h = sqrt(hx * hx + hy * hy + hz * hz);
-      double e[4];
-      if (h < 1e-5) { const double n = sqrt(1.0 + h * h) + 1e-5; e[0] = 1.0 / n; e[1] = hx / n; e[2] = hy / n; e[3] = hz / n; }
-      else { const double sc = sin(h) / h; e[0] = cos(h); e[1] = hx * sc; e[2] = hy * sc; e[3] = hz * sc; }
-      // quat_mul(e, q)
-      nq = Q4{(float)(qd[0] * e[0] - qd[1] * e[1] - qd[2] * e[2] - qd[3] * e[3]),
-              (float)(qd[0] * e[1] + qd[1] * e[0] - qd[2] * e[3] + qd[3] * e[2]),
-              (float)(qd[0] * e[2] + qd[1] * e[3] + qd[2] * e[0] - qd[3] * e[1]),
-              (float)(qd[0] * e[3] - qd[1] * e[2] + qd[2] * e[1] + qd[3] * e[0])};
-    }
-    V3 u = v3(0.f, 0.f, 0.f); (void)u;
+#if defined(ZEGGS_ROOT_FP64) && ZEGGS_ROOT_FP64
+    root_step_fp64(d.dt, q, pos, p, npos, nq);      // diagnostic build (tools/drift_ab.py), this path only
 #else
-    V3 npos = quat_mul_vec(q, d.dt * v3(p[0], p[1], p[2])) + pos;
-    V3 u = quat_mul_vec(q, d.dt * v3(p[3], p[4], p[5]));
-    Q4 nq = quat_exp_mul(0.5f * u, q);
+    root_step(d.dt, q, pos, p, npos, nq);
 #endif
     float* op = rpos + ((long)b * d.T + t) * 3; op[0] = npos.x; op[1] = npos.y; op[2] = npos.z;
     float* oq = rrot + ((long)b * d.T + t) * 4; oq[0] = nq.w; oq[1] = nq.x; oq[2] = nq.y; oq[3] = nq.z;
     if (gin_next) {
       const float* gz = gaze + ((long)b * d.T + t + 1) * 3;
-      V3 gd = quat_mul_vec(quat_inv(nq), v3(gz[0], gz[1], gz[2]) - npos);
+      V3 gd = gaze_dir(nq, npos, v3(gz[0], gz[1], gz[2]));
       float gv[3] = {gd.x, gd.y, gd.z};
       for (int k = 0; k < 3; ++k)
         gin_next[(long)b * GL + d.H + d.PO + k] = (gv[k] - st.in_mean[d.PO + k]) / st.in_std[d.PO + k];
@@ -178,37 +140,18 @@ __global__ void dec_devec_bwd_k(ZeggsDecDims d, ZeggsDecStats st, const float* d
     Q4 g_rr = Q4{cr[3] + e[0], cr[4] + e[1], cr[5] + e[2], cr[6] + e[3]};
     const float* rq = rrot + ((long)b * d.T + t) * 4;
     const float* rp = rpos + ((long)b * d.T + t) * 3;
-    Q4 q_t = Q4{rq[0], rq[1], rq[2], rq[3]};
-    V3 p_t = v3(rp[0], rp[1], rp[2]);
+    V3 gz = v3(0.f, 0.f, 0.f), dgd = gz;
     if (dxb) {   // gaze direction of x_{t+1}
-      const float* gz = gaze + ((long)b * d.T + t + 1) * 3;
-      V3 dgd = v3(dxb[d.PO] / st.in_std[d.PO], dxb[d.PO + 1] / st.in_std[d.PO + 1],
-                  dxb[d.PO + 2] / st.in_std[d.PO + 2]);
-      Q4 dqi; V3 dv;
-      qmv_bwd(quat_inv(q_t), v3(gz[0], gz[1], gz[2]) - p_t, dgd, dqi, dv);
-      g_rr.w += dqi.w; g_rr.x -= dqi.x; g_rr.y -= dqi.y; g_rr.z -= dqi.z;
-      g_rp = g_rp - dv;
+      const float* gp = gaze + ((long)b * d.T + t + 1) * 3;
+      gz = v3(gp[0], gp[1], gp[2]);
+      dgd = v3(dxb[d.PO] / st.in_std[d.PO], dxb[d.PO + 1] / st.in_std[d.PO + 1], dxb[d.PO + 2] / st.in_std[d.PO + 2]);
     }
     const float* pq = rrot + ((long)b * d.T + t - 1) * 4;
-    Q4 q_p = Q4{pq[0], pq[1], pq[2], pq[3]};
     const float* pt = pose + ((long)b * d.T + t) * d.PO;
-    V3 vel = v3(pt[0], pt[1], pt[2]), vrt = v3(pt[3], pt[4], pt[5]);
-    // rpos_t = qmv(q_p, vel dt) + rpos_{t-1}
-    Q4 dq1; V3 dv1;
-    qmv_bwd(q_p, d.dt * vel, g_rp, dq1, dv1);
-    // rrot_t = qmul(E, q_p), E = qexp(u/2), u = qmv(q_p, vrt dt)
-    V3 u = quat_mul_vec(q_p, d.dt * vrt);
-    Q4 E = quat_exp(0.5f * u);
-    Q4 dE, dqy;
-    qmul_bwd(E, q_p, g_rr, dE, dqy);
-    V3 du = 0.5f * qexp_bwd(0.5f * u, dE);
-    Q4 dq2; V3 dv2;
-    qmv_bwd(q_p, d.dt * vrt, du, dq2, dv2);
-    g6[0] += d.dt * dv1.x; g6[1] += d.dt * dv1.y; g6[2] += d.dt * dv1.z;
-    g6[3] += d.dt * dv2.x; g6[4] += d.dt * dv2.y; g6[5] += d.dt * dv2.z;
+    root_bwd(d.dt, Q4{rq[0], rq[1], rq[2], rq[3]}, v3(rp[0], rp[1], rp[2]), gz, dgd, dxb != nullptr,
+             Q4{pq[0], pq[1], pq[2], pq[3]}, v3(pt[0], pt[1], pt[2]), v3(pt[3], pt[4], pt[5]), g_rp, g_rr, g6);
     cr[0] = g_rp.x; cr[1] = g_rp.y; cr[2] = g_rp.z;
-    cr[3] = dq1.w + dqy.w + dq2.w; cr[4] = dq1.x + dqy.x + dq2.x;
-    cr[5] = dq1.y + dqy.y + dq2.y; cr[6] = dq1.z + dqy.z + dq2.z;
+    cr[3] = g_rr.w; cr[4] = g_rr.x; cr[5] = g_rr.y; cr[6] = g_rr.z;
     for (int c = 0; c < 6; ++c) dyb[c] = g6[c] * st.out_std[c];
   }
 }

@@ -234,7 +234,7 @@ __device__ __forceinline__ void run_blocks(const f4* __restrict__ wp, const f4* 
 #undef ZCOMP
 }
 
-// backward of the root integration of frame `f` (see dec_devec_bwd_k in decoder.hip for the derivation).
+// backward of the root integration of frame `f`: gathers the operands of ::root_bwd (dec_math.h).
 // g6: in = dpose[f][0:6] + dx/sigma_i (when a next step exists); out = total grad wrt pose[f][0:6] (de-normalised).
 __device__ void root_bwd(const ZeggsDecDims& d, const ZeggsDecStats& st, int b, int f, bool has_next, const float* dgd_in,
                          const float* gaze, const float* pose, const float* rpos, const float* rrot, const float* drpos,
@@ -246,52 +246,30 @@ __device__ void root_bwd(const ZeggsDecDims& d, const ZeggsDecStats& st, int b, 
   Q4 g_rr = Q4{cr[3] + e[0], cr[4] + e[1], cr[5] + e[2], cr[6] + e[3]};
   const float* rq = rrot + ((long)b * d.T + f) * 4;
   const float* rp = rpos + ((long)b * d.T + f) * 3;
-  Q4 q_t = Q4{rq[0], rq[1], rq[2], rq[3]};
-  V3 p_t = v3(rp[0], rp[1], rp[2]);
+  V3 gz = v3(0.f, 0.f, 0.f), dgd = gz;
   if (has_next) {
-    const float* gz = gaze + ((long)b * d.T + f + 1) * 3;
-    V3 dgd = v3(dgd_in[0] / st.in_std[d.PO], dgd_in[1] / st.in_std[d.PO + 1], dgd_in[2] / st.in_std[d.PO + 2]);
-    Q4 dqi; V3 dv;
-    qmv_bwd(quat_inv(q_t), v3(gz[0], gz[1], gz[2]) - p_t, dgd, dqi, dv);
-    g_rr.w += dqi.w; g_rr.x -= dqi.x; g_rr.y -= dqi.y; g_rr.z -= dqi.z;
-    g_rp = g_rp - dv;
+    const float* gp = gaze + ((long)b * d.T + f + 1) * 3;
+    gz = v3(gp[0], gp[1], gp[2]);
+    dgd = v3(dgd_in[0] / st.in_std[d.PO], dgd_in[1] / st.in_std[d.PO + 1], dgd_in[2] / st.in_std[d.PO + 2]);
   }
   const float* pq = rrot + ((long)b * d.T + f - 1) * 4;
-  Q4 q_p = Q4{pq[0], pq[1], pq[2], pq[3]};
   const float* pt = pose + ((long)b * d.T + f) * d.PO;
-  V3 vel = v3(pt[0], pt[1], pt[2]), vrt = v3(pt[3], pt[4], pt[5]);
-  Q4 dq1; V3 dv1;
-  qmv_bwd(q_p, d.dt * vel, g_rp, dq1, dv1);
-  V3 u = quat_mul_vec(q_p, d.dt * vrt);
-  QExpCtx ec;
-  Q4 E = quat_exp_ctx(0.5f * u, ec);
-  Q4 dE, dqy;
-  qmul_bwd(E, q_p, g_rr, dE, dqy);
-  V3 du = 0.5f * qexp_bwd_ctx(0.5f * u, dE, ec);
-  Q4 dq2; V3 dv2;
-  qmv_bwd(q_p, d.dt * vrt, du, dq2, dv2);
-  g6[0] += d.dt * dv1.x; g6[1] += d.dt * dv1.y; g6[2] += d.dt * dv1.z;
-  g6[3] += d.dt * dv2.x; g6[4] += d.dt * dv2.y; g6[5] += d.dt * dv2.z;
+  ::root_bwd(d.dt, Q4{rq[0], rq[1], rq[2], rq[3]}, v3(rp[0], rp[1], rp[2]), gz, dgd, has_next, Q4{pq[0], pq[1], pq[2], pq[3]},
+           v3(pt[0], pt[1], pt[2]), v3(pt[3], pt[4], pt[5]), g_rp, g_rr, g6);
   if (carry_out) {
     float* co = carry_out + b * 8;
     co[0] = g_rp.x; co[1] = g_rp.y; co[2] = g_rp.z;
-    co[3] = dq1.w + dqy.w + dq2.w; co[4] = dq1.x + dqy.x + dq2.x;
-    co[5] = dq1.y + dqy.y + dq2.y; co[6] = dq1.z + dqy.z + dq2.z;
+    co[3] = g_rr.w; co[4] = g_rr.x; co[5] = g_rr.y; co[6] = g_rr.z;
   }
 }
 
-// root integration of frame t from the de-normalised root velocities p6 (reference: devectorize_output,
-// ZEGGS/modules.py:139-176) and, when a next step exists, the normalised gaze direction of x_{t+1}.
-// rt = [rrot_{t-1}(4) | rpos_{t-1}(3) | gaze_{t+1}(3)]
+// ::root_step + gaze_dir (dec_math.h) on the stage kernels' operand record, and, when a next step exists, the normalised
+// gaze direction of x_{t+1}.      rt = [rrot_{t-1}(4) | rpos_{t-1}(3) | gaze_{t+1}(3)]
 __device__ __forceinline__ void root_step(const ZeggsDecDims& d, const ZeggsDecStats& st, const float (&rt)[10],
                                           const float (&p)[6], bool next, V3& npos, Q4& nq, float (&genc)[3]) {
-  const Q4 q = Q4{rt[0], rt[1], rt[2], rt[3]};
-  const V3 pos = v3(rt[4], rt[5], rt[6]);
-  npos = quat_mul_vec(q, d.dt * v3(p[0], p[1], p[2])) + pos;
-  const V3 uu = quat_mul_vec(q, d.dt * v3(p[3], p[4], p[5]));
-  nq = quat_exp_mul(0.5f * uu, q);
+  ::root_step(d.dt, Q4{rt[0], rt[1], rt[2], rt[3]}, v3(rt[4], rt[5], rt[6]), p, npos, nq);
   if (next) {
-    const V3 gd = quat_mul_vec(quat_inv(nq), v3(rt[7], rt[8], rt[9]) - npos);
+    const V3 gd = gaze_dir(nq, npos, v3(rt[7], rt[8], rt[9]));
     genc[0] = (gd.x - st.in_mean[d.PO]) / st.in_std[d.PO];
     genc[1] = (gd.y - st.in_mean[d.PO + 1]) / st.in_std[d.PO + 1];
     genc[2] = (gd.z - st.in_mean[d.PO + 2]) / st.in_std[d.PO + 2];
@@ -751,18 +729,13 @@ __global__ __launch_bounds__(WAVES * 64, CH ? 4 : WAVES / 4) void stage_k(StageA
         const int b = eb, U = tile * 16 + ev;
         const long i = (long)b * H + U;
         const float g = FV(0, ev, b) + pre[0];
-        const float r = pre[1], z = pre[2], nn = pre[3], nh = pre[4], hp = pre[5];
-        const float dn = g * (1.f - z);
-        const float dz = g * (hp - nn);
-        const float dan = dn * (1.f - nn * nn);
-        const float dar = dan * nh * r * (1.f - r);
-        const float daz = dz * z * (1.f - z);
+        const GruGrad gg = gru_cell_bwd(g, f4{pre[1], pre[2], pre[3], pre[4]}, pre[5]);
         float* di = G.o1 + (long)b * 3 * H;
-        di[U] = dar; di[H + U] = daz; di[2 * H + U] = dan;
-        G.o2[i] = dan * r;                 // hidden-side gradient: only its n rows differ from di (r, z rows are shared)
-        G.o3[xf_index(b, U, LNB)] = dar; G.o3[xf_index(b, H + U, LNB)] = daz; G.o3[xf_index(b, 2 * H + U, LNB)] = dan;
-        G.o4[xf_index(b, U, LNB)] = dan * r;
-        G.o0[i] = g * z;
+        di[U] = gg.dar; di[H + U] = gg.daz; di[2 * H + U] = gg.dan;
+        G.o2[i] = gg.dhn();                  // hidden-side gradient: only its n rows differ from di (r, z rows are shared)
+        G.o3[xf_index(b, U, LNB)] = gg.dar; G.o3[xf_index(b, H + U, LNB)] = gg.daz; G.o3[xf_index(b, 2 * H + U, LNB)] = gg.dan;
+        G.o4[xf_index(b, U, LNB)] = gg.dhn();
+        G.o0[i] = gg.dhc();
       }
     } break;
     case EPI_GRU_BWD_M: if constexpr (FAM == 1) {   // layer-1 gate gradients of step t-1 in the launch that produces dy_{t-1}:
@@ -785,18 +758,13 @@ __global__ __launch_bounds__(WAVES * 64, CH ? 4 : WAVES / 4) void stage_k(StageA
         float g = FV(0, ev, b) + pre[0];
 #pragma unroll
         for (int c = 0; c < 6; ++c) g = fmaf(rt[c], dsh[ebl * 6 + c], g);
-        const float r = pre[1], z = pre[2], nn = pre[3], nh = pre[4], hp = pre[5];
-        const float dn = g * (1.f - z);
-        const float dz = g * (hp - nn);
-        const float dan = dn * (1.f - nn * nn);
-        const float dar = dan * nh * r * (1.f - r);
-        const float daz = dz * z * (1.f - z);
+        const GruGrad gg = gru_cell_bwd(g, f4{pre[1], pre[2], pre[3], pre[4]}, pre[5]);
         float* di = G.o1 + (long)b * 3 * H;
-        di[U] = dar; di[H + U] = daz; di[2 * H + U] = dan;
-        G.o2[i] = dan * r;                 // hidden-side gradient: only its n rows differ from di (r, z rows are shared)
-        G.o3[xf_index(b, U, LNB)] = dar; G.o3[xf_index(b, H + U, LNB)] = daz; G.o3[xf_index(b, 2 * H + U, LNB)] = dan;
-        G.o4[xf_index(b, U, LNB)] = dan * r;
-        G.o0[i] = g * z;
+        di[U] = gg.dar; di[H + U] = gg.daz; di[2 * H + U] = gg.dan;
+        G.o2[i] = gg.dhn();                  // hidden-side gradient: only its n rows differ from di (r, z rows are shared)
+        G.o3[xf_index(b, U, LNB)] = gg.dar; G.o3[xf_index(b, H + U, LNB)] = gg.daz; G.o3[xf_index(b, 2 * H + U, LNB)] = gg.dan;
+        G.o4[xf_index(b, U, LNB)] = gg.dhn();
+        G.o0[i] = gg.dhc();
       }
     } break;
     case EPI_ADD: if constexpr (FAM == 1) {

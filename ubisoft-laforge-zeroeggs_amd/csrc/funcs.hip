@@ -73,9 +73,8 @@ __global__ void vectorize_fwd_k(VecIn a, int B, int J, const float* mean, const 
   if (threadIdx.x == 0) {
     const float* rq = a.root_rot + b * 4;
     Q4 q = Q4{rq[0], rq[1], rq[2], rq[3]};
-    V3 v = v3(a.gaze_pos[b * 3] - a.root_pos[b * 3], a.gaze_pos[b * 3 + 1] - a.root_pos[b * 3 + 1],
-              a.gaze_pos[b * 3 + 2] - a.root_pos[b * 3 + 2]);
-    V3 gd = quat_mul_vec(quat_inv(q), v);
+    V3 gd = gaze_dir(q, v3(a.root_pos[b * 3], a.root_pos[b * 3 + 1], a.root_pos[b * 3 + 2]),
+                     v3(a.gaze_pos[b * 3], a.gaze_pos[b * 3 + 1], a.gaze_pos[b * 3 + 2]));
     const float g[3] = {gd.x, gd.y, gd.z};
     for (int k = 0; k < 3; ++k) out[(long)b * PI + PO + k] = (g[k] - mean[PO + k]) / stdv[PO + k];
   }
@@ -95,10 +94,9 @@ __global__ void vectorize_bwd_k(VecIn a, VecGrad g, int B, int J, const float* s
               a.gaze_pos[b * 3 + 2] - a.root_pos[b * 3 + 2]);
     V3 dgd = v3(dout[(long)b * PI + PO] / stdv[PO], dout[(long)b * PI + PO + 1] / stdv[PO + 1],
                 dout[(long)b * PI + PO + 2] / stdv[PO + 2]);
-    Q4 dqi; V3 dv;
-    qmv_bwd(quat_inv(q), v, dgd, dqi, dv);
-    float* dq = g.root_rot + b * 4;          // d/dq of quat_inv(q): the vector part changes sign
-    dq[0] = dqi.w; dq[1] = -dqi.x; dq[2] = -dqi.y; dq[3] = -dqi.z;
+    Q4 dq; V3 dv;
+    gaze_dir_bwd(q, v, dgd, dq, dv);
+    float* dr = g.root_rot + b * 4; dr[0] = dq.w; dr[1] = dq.x; dr[2] = dq.y; dr[3] = dq.z;
     float* dg = g.gaze_pos + b * 3; dg[0] = dv.x; dg[1] = dv.y; dg[2] = dv.z;
     float* dp = g.root_pos + b * 3; dp[0] = -dv.x; dp[1] = -dv.y; dp[2] = -dv.z;
   }
@@ -116,9 +114,8 @@ __global__ void devectorize_fwd_k(int B, int PO, float dt, const float* pred, co
     for (int c = 0; c < 6; ++c) p[c] = pred[(long)b * PO + c] * stdv[c] + mean[c];
     Q4 q = Q4{root_rot[b * 4], root_rot[b * 4 + 1], root_rot[b * 4 + 2], root_rot[b * 4 + 3]};
     V3 pos = v3(root_pos[b * 3], root_pos[b * 3 + 1], root_pos[b * 3 + 2]);
-    V3 np = quat_mul_vec(q, dt * v3(p[0], p[1], p[2])) + pos;
-    V3 u = quat_mul_vec(q, dt * v3(p[3], p[4], p[5]));
-    Q4 nq = quat_exp_mul(0.5f * u, q);
+    V3 np; Q4 nq;
+    root_step(dt, q, pos, p, np, nq);
     nrpos[b * 3] = np.x; nrpos[b * 3 + 1] = np.y; nrpos[b * 3 + 2] = np.z;
     nrrot[b * 4] = nq.w; nrrot[b * 4 + 1] = nq.x; nrrot[b * 4 + 2] = nq.y; nrrot[b * 4 + 3] = nq.z;
   }
@@ -139,22 +136,11 @@ __global__ void devectorize_bwd_k(int B, int PO, float dt, const float* pred, co
     Q4 q = Q4{root_rot[b * 4], root_rot[b * 4 + 1], root_rot[b * 4 + 2], root_rot[b * 4 + 3]};
     V3 g_rp = dnrpos ? v3(dnrpos[b * 3], dnrpos[b * 3 + 1], dnrpos[b * 3 + 2]) : v3(0.f, 0.f, 0.f);
     Q4 g_rr = dnrrot ? Q4{dnrrot[b * 4], dnrrot[b * 4 + 1], dnrrot[b * 4 + 2], dnrrot[b * 4 + 3]} : Q4{0.f, 0.f, 0.f, 0.f};
-    V3 vel = v3(p[0], p[1], p[2]), vrt = v3(p[3], p[4], p[5]);
-    Q4 dq1; V3 dv1;
-    qmv_bwd(q, dt * vel, g_rp, dq1, dv1);
-    V3 u = quat_mul_vec(q, dt * vrt);
-    Q4 E = quat_exp(0.5f * u);
-    Q4 dE, dqy;
-    qmul_bwd(E, q, g_rr, dE, dqy);
-    V3 du = 0.5f * qexp_bwd(0.5f * u, dE);
-    Q4 dq2; V3 dv2;
-    qmv_bwd(q, dt * vrt, du, dq2, dv2);
-    g6[0] += dt * dv1.x; g6[1] += dt * dv1.y; g6[2] += dt * dv1.z;
-    g6[3] += dt * dv2.x; g6[4] += dt * dv2.y; g6[5] += dt * dv2.z;
+    Q4 dq;
+    root_step_bwd(dt, q, v3(p[0], p[1], p[2]), v3(p[3], p[4], p[5]), g_rp, g_rr, g6, dq);
     for (int c = 0; c < 6; ++c) dpred[(long)b * PO + c] = g6[c] * stdv[c];
     drpos[b * 3] = g_rp.x; drpos[b * 3 + 1] = g_rp.y; drpos[b * 3 + 2] = g_rp.z;
-    drrot[b * 4] = dq1.w + dqy.w + dq2.w; drrot[b * 4 + 1] = dq1.x + dqy.x + dq2.x;
-    drrot[b * 4 + 2] = dq1.y + dqy.y + dq2.y; drrot[b * 4 + 3] = dq1.z + dqy.z + dq2.z;
+    drrot[b * 4] = dq.w; drrot[b * 4 + 1] = dq.x; drrot[b * 4 + 2] = dq.y; drrot[b * 4 + 3] = dq.z;
   }
 }
 

@@ -107,15 +107,6 @@ __device__ __forceinline__ Q4 quat_to_xform_bwd(Q4 q, const M3& g) {
   d.z = 2.f * (-2.f * q.z * m[0] - q.w * m[1] + q.x * m[2] + q.w * m[3] - 2.f * q.z * m[4] + q.y * m[5] + q.x * m[6] + q.y * m[7]);
   return d;
 }
-__device__ __forceinline__ void qmv_bwd(Q4 q, V3 v, V3 g, Q4& dq, V3& dv) {
-  V3 qv = v3(q.x, q.y, q.z);
-  V3 t = 2.0f * cross(qv, v);
-  float dw = dot(g, t);
-  V3 dt = q.w * g + cross(g, qv);
-  V3 dqv = cross(t, g) + 2.0f * cross(v, dt);
-  dv = g + 2.0f * cross(dt, qv);
-  dq = Q4{dw, dqv.x, dqv.y, dqv.z};
-}
 __device__ __forceinline__ float vnorm(V3 a) { return sqrtf(a.x * a.x + a.y * a.y + a.z * a.z); }
 // grad of a/(|a|+e) wrt a, upstream g
 __device__ __forceinline__ V3 normalize_bwd(V3 a, V3 g, float e) {

@@ -11,6 +11,7 @@
 #include "common.h"
 #include "gemm.h"
 #include "kernels.h"
+#include "dec_math.h"
 
 namespace {
 
@@ -23,12 +24,9 @@ __global__ void sg_gate_fwd_k(const float* gi, const float* gh, const float* hpr
     long b = i / H;
     const float* gib = gi + b * 3 * H;
     const float* ghb = gh + b * 3 * H;
-    float r = d_sigmoid(gib[u] + ghb[u]);
-    float z = d_sigmoid(gib[H + u] + ghb[H + u]);
-    float nh = ghb[2 * H + u];
-    float nn = d_tanh(gib[2 * H + u] + r * nh);
-    hout[i] = (1.f - z) * nn + z * hprev[i];
-    R[i] = r; Z[i] = z; N[i] = nn; NH[i] = nh;
+    f4 gt;
+    hout[i] = gru_cell_fwd(gib[u] + ghb[u], gib[H + u] + ghb[H + u], gib[2 * H + u], ghb[2 * H + u], hprev[i], gt);
+    R[i] = gt.x; Z[i] = gt.y; N[i] = gt.z; NH[i] = gt.w;
   }
 }
 // dh (ld = lddh) -> di, dhh [B,3H]; dhc = dh * z (direct path to h_prev)
@@ -38,17 +36,12 @@ __global__ void sg_gate_bwd_k(const float* dh, long lddh, const float* R, const 
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     int u = (int)(i % H);
     long b = i / H;
-    float g = dh[b * lddh + u], r = R[i], z = Z[i], nn = N[i], nh = NH[i], hp = hprev[i];
-    float dn = g * (1.f - z);
-    float dz = g * (hp - nn);
-    float dan = dn * (1.f - nn * nn);
-    float dar = dan * nh * r * (1.f - r);
-    float daz = dz * z * (1.f - z);
+    const GruGrad gg = gru_cell_bwd(dh[b * lddh + u], f4{R[i], Z[i], N[i], NH[i]}, hprev[i]);
     float* dib = di + b * 3 * H;
     float* dhb = dhh + b * 3 * H;
-    dib[u] = dar; dib[H + u] = daz; dib[2 * H + u] = dan;
-    dhb[u] = dar; dhb[H + u] = daz; dhb[2 * H + u] = dan * r;
-    if (dhc) dhc[i] = g * z;
+    dib[u] = gg.dar; dib[H + u] = gg.daz; dib[2 * H + u] = gg.dan;
+    dhb[u] = gg.dar; dhb[H + u] = gg.daz; dhb[2 * H + u] = gg.dhn();
+    if (dhc) dhc[i] = gg.dhc();
   }
 }
 __global__ void sg_concat_k(float* cat, const float* a, const float* b, int B, int H) {

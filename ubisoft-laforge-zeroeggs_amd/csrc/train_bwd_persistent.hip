@@ -155,127 +155,6 @@ __device__ __forceinline__ float root_item(const float* drpos, const float* drro
   if (item < 27) return pose[bf * PO + item - 21];
   return dpose[bf * PO + item - 27];
 }
-struct RootIn {
-  float a[3], e[4], rq[4], rp[3], gz[3], pq[4], pt[6], dp[6];
-  template <class F>
-  __device__ __forceinline__ void gather(F get) {      // get(item) -> value
-#pragma unroll
-    for (int i = 0; i < 3; ++i) { a[i] = get(i); rp[i] = get(11 + i); gz[i] = get(14 + i); }
-#pragma unroll
-    for (int i = 0; i < 4; ++i) { e[i] = get(3 + i); rq[i] = get(7 + i); pq[i] = get(17 + i); }
-#pragma unroll
-    for (int i = 0; i < 6; ++i) { pt[i] = get(21 + i); dp[i] = get(27 + i); }
-  }
-};
-// backward of the root integration of frame f with the adjoint carry in registers (decoder_fast.hip root_bwd, decoder.hip
-// dec_devec_bwd_k): cr = gradient wrt (root_pos_f, root_rot_f) arriving from the later frames.
-// g6: in = dpose[f][0:6] + dx/sigma_i ; out = total gradient wrt pose[f][0:6] (de-normalised output space)
-__device__ __forceinline__ void root_bwd_reg(const ZeggsDecDims& d, const float* gaze_in_std /* [3] */, const RootIn& ri,
-                                             const float (&dgd_in)[3], float (&cr)[7], float (&g6)[6], bool has_next = true) {
-  V3 g_rp = v3(cr[0] + ri.a[0], cr[1] + ri.a[1], cr[2] + ri.a[2]);
-  Q4 g_rr = Q4{cr[3] + ri.e[0], cr[4] + ri.e[1], cr[5] + ri.e[2], cr[6] + ri.e[3]};
-  const Q4 q_t = Q4{ri.rq[0], ri.rq[1], ri.rq[2], ri.rq[3]};
-  const V3 p_t = v3(ri.rp[0], ri.rp[1], ri.rp[2]);
-  if (has_next) {
-    const V3 dgd = v3(dgd_in[0] / gaze_in_std[0], dgd_in[1] / gaze_in_std[1], dgd_in[2] / gaze_in_std[2]);
-    Q4 dqi; V3 dv;
-    qmv_bwd(quat_inv(q_t), v3(ri.gz[0], ri.gz[1], ri.gz[2]) - p_t, dgd, dqi, dv);
-    g_rr.w += dqi.w; g_rr.x -= dqi.x; g_rr.y -= dqi.y; g_rr.z -= dqi.z;
-    g_rp = g_rp - dv;
-  }
-  const Q4 q_p = Q4{ri.pq[0], ri.pq[1], ri.pq[2], ri.pq[3]};
-  const V3 vel = v3(ri.pt[0], ri.pt[1], ri.pt[2]), vrt = v3(ri.pt[3], ri.pt[4], ri.pt[5]);
-  Q4 dq1; V3 dv1;
-  qmv_bwd(q_p, d.dt * vel, g_rp, dq1, dv1);
-  const V3 u = quat_mul_vec(q_p, d.dt * vrt);
-  QExpCtx ec;
-  const Q4 E = quat_exp_ctx(0.5f * u, ec);
-  Q4 dE, dqy;
-  qmul_bwd(E, q_p, g_rr, dE, dqy);
-  const V3 du = 0.5f * qexp_bwd_ctx(0.5f * u, dE, ec);
-  Q4 dq2; V3 dv2;
-  qmv_bwd(q_p, d.dt * vrt, du, dq2, dv2);
-  g6[0] += d.dt * dv1.x; g6[1] += d.dt * dv1.y; g6[2] += d.dt * dv1.z;
-  g6[3] += d.dt * dv2.x; g6[4] += d.dt * dv2.y; g6[5] += d.dt * dv2.z;
-  cr[0] = g_rp.x; cr[1] = g_rp.y; cr[2] = g_rp.z;
-  cr[3] = dq1.w + dqy.w + dq2.w; cr[4] = dq1.x + dqy.x + dq2.x;
-  cr[5] = dq1.y + dqy.y + dq2.y; cr[6] = dq1.z + dqy.z + dq2.z;
-}
-
-// The same backward split in two for the persistent kernel: everything that depends on forward data only (the rotations,
-// quat_exp and its sine / cosine) is evaluated one phase ahead by the root thread and parked in its LDS column (33 values,
-// in place of the raw inputs); what is left behind the hand-off is linear in the incoming gradients.
-struct RootPre { Q4 qti; V3 w; Q4 qp; V3 dvel, dvrt, hu; Q4 E; float ea, eb_, ec; float dp[6]; };
-// backward of quat_exp at a prepared point x: du = ea * g_v + (eb_ * g_w + ec * <g_v, x>) * x   (dec_math.h qexp_bwd_ctx with the
-// divisions by the norm done when the frame was prepared)
-__device__ __forceinline__ void qexp_bwd_coef(V3 x, const QExpCtx& c, float& ea, float& eb_, float& ec) {
-  if (c.h < 1e-5f) {
-    const float n = sqrtf(1.f + c.h * c.h), ne = n + 1e-5f, k = 1.f / (n * ne * ne);
-    ea = 1.f / ne; eb_ = -k; ec = -k;
-  } else {
-    const float s = c.sh / c.h, ds = (c.h * c.ch - c.sh) / (c.h * c.h);
-    ea = s; eb_ = -s; ec = ds / c.h;
-  }
-}
-__device__ __forceinline__ void root_prepare(const ZeggsDecDims& d, const RootIn& ri, RootPre& o) {
-  o.qti = quat_inv(Q4{ri.rq[0], ri.rq[1], ri.rq[2], ri.rq[3]});
-  o.w = v3(ri.gz[0], ri.gz[1], ri.gz[2]) - v3(ri.rp[0], ri.rp[1], ri.rp[2]);
-  o.qp = Q4{ri.pq[0], ri.pq[1], ri.pq[2], ri.pq[3]};
-  o.dvel = d.dt * v3(ri.pt[0], ri.pt[1], ri.pt[2]);
-  o.dvrt = d.dt * v3(ri.pt[3], ri.pt[4], ri.pt[5]);
-  o.hu = 0.5f * quat_mul_vec(o.qp, o.dvrt);
-  QExpCtx ctx;
-  o.E = quat_exp_ctx(o.hu, ctx);
-  qexp_bwd_coef(o.hu, ctx, o.ea, o.eb_, o.ec);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) o.dp[i] = ri.dp[i];
-}
-template <class F>
-__device__ __forceinline__ void root_pre_store(const RootPre& o, F put) {      // put(slot, value)
-  put(0, o.qti.w); put(1, o.qti.x); put(2, o.qti.y); put(3, o.qti.z); put(4, o.w.x); put(5, o.w.y); put(6, o.w.z);
-  put(7, o.qp.w); put(8, o.qp.x); put(9, o.qp.y); put(10, o.qp.z); put(11, o.dvel.x); put(12, o.dvel.y); put(13, o.dvel.z);
-  put(14, o.dvrt.x); put(15, o.dvrt.y); put(16, o.dvrt.z); put(17, o.hu.x); put(18, o.hu.y); put(19, o.hu.z);
-  put(20, o.E.w); put(21, o.E.x); put(22, o.E.y); put(23, o.E.z); put(24, o.ea); put(25, o.eb_); put(26, o.ec);
-#pragma unroll
-  for (int i = 0; i < 6; ++i) put(27 + i, o.dp[i]);
-}
-// cr: adjoint of (root_pos_f, root_rot_f) INCLUDING this frame's direct loss gradients (drpos / drrot were added when the
-// frame was prepared).  The prepared values are fetched (get(slot), see root_pre_store) right where they are used: the
-// workgroup's registers are full of weights, and 33 values loaded up front get spilled to scratch around this code.
-template <class F>
-__device__ __forceinline__ void root_apply(const ZeggsDecDims& d, const float* gaze_rstd /* 1 / in_std[PO..PO+2] */, F get,
-                                           const float (&dgd_in)[3], float (&cr)[7], float (&g6)[6]) {
-  V3 g_rp = v3(cr[0], cr[1], cr[2]);
-  Q4 g_rr = Q4{cr[3], cr[4], cr[5], cr[6]};
-  {
-    const V3 dgd = v3(dgd_in[0] * gaze_rstd[0], dgd_in[1] * gaze_rstd[1], dgd_in[2] * gaze_rstd[2]);
-    Q4 dqi; V3 dv;
-    qmv_bwd(Q4{get(0), get(1), get(2), get(3)}, v3(get(4), get(5), get(6)), dgd, dqi, dv);
-    g_rr.w += dqi.w; g_rr.x -= dqi.x; g_rr.y -= dqi.y; g_rr.z -= dqi.z;
-    g_rp = g_rp - dv;
-  }
-  __builtin_amdgcn_sched_barrier(0);
-  const Q4 qp = Q4{get(7), get(8), get(9), get(10)};
-  Q4 dq1; V3 dv1;
-  qmv_bwd(qp, v3(get(11), get(12), get(13)), g_rp, dq1, dv1);
-  g6[0] += d.dt * dv1.x; g6[1] += d.dt * dv1.y; g6[2] += d.dt * dv1.z;
-  __builtin_amdgcn_sched_barrier(0);
-  Q4 dE, dqy;
-  qmul_bwd(Q4{get(20), get(21), get(22), get(23)}, qp, g_rr, dE, dqy);
-  __builtin_amdgcn_sched_barrier(0);
-  V3 du;
-  {
-    const V3 hu = v3(get(17), get(18), get(19)), gv = v3(dE.x, dE.y, dE.z);
-    du = 0.5f * (get(24) * gv + (get(25) * dE.w + get(26) * dot(gv, hu)) * hu);
-  }
-  Q4 dq2; V3 dv2;
-  qmv_bwd(qp, v3(get(14), get(15), get(16)), du, dq2, dv2);
-  g6[3] += d.dt * dv2.x; g6[4] += d.dt * dv2.y; g6[5] += d.dt * dv2.z;
-  cr[0] = g_rp.x; cr[1] = g_rp.y; cr[2] = g_rp.z;
-  cr[3] = dq1.w + dqy.w + dq2.w; cr[4] = dq1.x + dqy.x + dq2.x;
-  cr[5] = dq1.y + dqy.y + dq2.y; cr[6] = dq1.z + dqy.z + dq2.z;
-}
-
 // dx rows: workgroup c owns rows 8c .. 8c+7 (two aligned groups of four: one 16-byte store each); its dXa (P3) stays in
 // LDS for P4.  The 9 root / gaze columns (0..5, PO..PO+2) are the exception: whoever owns them in P3 sends their dXa to
 // workgroup 0 through SP, and workgroup 0 owns them in P4 (slots 0..7 = rows 0..7, slots 8..10 = PO..PO+2).
@@ -422,15 +301,10 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
   // GRU backward of one (unit, batch row): g = total gradient wrt h_t; leaves the gate gradients in the exchange buffer
   // (kind 0 r, 1 z, 2 n, 3 hidden-side n), returns g * z
   auto gru_bwd = [&](float g, const f4& gt, float hp) -> float {
-    const float r = gt[0], z = gt[1], nn = gt[2], nh = gt[3];
-    const float dn = g * (1.f - z);
-    const float dz = g * (hp - nn);
-    const float dan = dn * (1.f - nn * nn);
-    const float dar = dan * nh * r * (1.f - r);
-    const float daz = dz * z * (1.f - z);
-    ((float*)&ex[0][eb])[er] = dar; ((float*)&ex[1][eb])[er] = daz; ((float*)&ex[2][eb])[er] = dan;
-    ((float*)&ex[3][eb])[er] = dan * r;          // hidden side: only its n rows differ from the input side
-    return g * z;
+    const GruGrad gg = gru_cell_bwd(g, gt, hp);
+    ((float*)&ex[0][eb])[er] = gg.dar; ((float*)&ex[1][eb])[er] = gg.daz; ((float*)&ex[2][eb])[er] = gg.dan;
+    ((float*)&ex[3][eb])[er] = gg.dhn();         // hidden side: only its n rows differ from the input side
+    return gg.dhc();
   };
   // ... and 128 threads (gate kind, batch row) store them: canonical DI [B][3H] / DH [B][H] and the operand of the next phase
   auto gru_store = [&](float* DI, float* DHc, float* OP, long t) {
@@ -553,7 +427,7 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
         RootIn ri;
         ri.gather([&](int item) { return rin[item][eb]; });
         RootPre pre;
-        root_prepare(d, ri, pre);
+        root_prepare(d.dt, ri, pre);
 #pragma unroll
         for (int q = 0; q < 3; ++q) crs[q][eb] += ri.a[q];
 #pragma unroll
@@ -649,7 +523,7 @@ __global__ __launch_bounds__(BTHR, 2) void train_bwd_persistent_k(BArgs a) {
 #pragma unroll
             for (int q = 0; q < 3; ++q) dgd[q] = sp9[6 + q][eb];
             BPT(18);
-            root_apply(d, rst + 6, pre, dgd, cr, g6);
+            root_apply(d.dt, rst + 6, pre, dgd, cr, g6);
             BPT(19);
 #pragma unroll
             for (int q = 0; q < 7; ++q) crs[q][eb] = cr[q];
@@ -777,12 +651,17 @@ __global__ void bp_dy_last_k(ZeggsDecDims d, ZeggsDecStats st, const float* dpos
   const float* dpb = dpose + ((long)b * d.T + t) * d.PO;
   for (int cc = 6 + threadIdx.x; cc < d.PO; cc += blockDim.x) dy[(long)b * POL + cc] = dpb[cc] * st.out_std[cc];
   if (threadIdx.x == 0) {
-    float g6[6], cr[7] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, dgd[3] = {0.f, 0.f, 0.f};
+    float g6[6];
     RootIn ri;
     ri.gather([&](int item) { return root_item(drpos, drrot, rrot, rpos, gaze, pose, dpose, d.T, d.PO, b, t, false, item); });
     for (int q = 0; q < 6; ++q) g6[q] = dpb[q];
-    root_bwd_reg(d, st.in_std + d.PO, ri, dgd, cr, g6, false);
+    V3 g_rp = v3(0.f + ri.a[0], 0.f + ri.a[1], 0.f + ri.a[2]);      // (zero carry: no later frame)
+    Q4 g_rr = Q4{0.f + ri.e[0], 0.f + ri.e[1], 0.f + ri.e[2], 0.f + ri.e[3]};
+    root_bwd(d.dt, Q4{ri.rq[0], ri.rq[1], ri.rq[2], ri.rq[3]}, v3(ri.rp[0], ri.rp[1], ri.rp[2]), v3(0.f, 0.f, 0.f), v3(0.f, 0.f, 0.f),
+             false, Q4{ri.pq[0], ri.pq[1], ri.pq[2], ri.pq[3]}, v3(ri.pt[0], ri.pt[1], ri.pt[2]), v3(ri.pt[3], ri.pt[4], ri.pt[5]),
+             g_rp, g_rr, g6);
     for (int q = 0; q < 6; ++q) dy[(long)b * POL + q] = g6[q] * st.out_std[q];
+    const float cr[7] = {g_rp.x, g_rp.y, g_rp.z, g_rr.w, g_rr.x, g_rr.y, g_rr.z};
     for (int q = 0; q < 7; ++q) carry[b * 8 + q] = cr[q];
   }
 }

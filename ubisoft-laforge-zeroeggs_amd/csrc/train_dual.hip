@@ -451,14 +451,11 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_dual_k(TArgs a) {
         float pv[6];
 #pragma unroll
         for (int qq = 0; qq < 6; ++qq) pv[qq] = (FV(9 + qq, b) + cB[9 + qq][0]) * cB[9 + qq][1] + cB[9 + qq][2];
-        const Q4 qr = rq_;
-        const V3 pos = rp_;
-        const V3 npos = quat_mul_vec(qr, d.dt * v3(pv[0], pv[1], pv[2])) + pos;
-        const V3 uu = quat_mul_vec(qr, d.dt * v3(pv[3], pv[4], pv[5]));
-        const Q4 nq = quat_exp_mul(0.5f * uu, qr);
+        V3 npos; Q4 nq;
+        root_step(d.dt, rq_, rp_, pv, npos, nq);
         rq_ = nq; rp_ = npos;
         if (next) {
-          const V3 gd = quat_mul_vec(quat_inv(nq), v3(gz_[0], gz_[1], gz_[2]) - npos);
+          const V3 gd = gaze_dir(nq, npos, v3(gz_[0], gz_[1], gz_[2]));
           genc[0] = (gd.x - cG[0]) * cG[3];
           genc[1] = (gd.y - cG[1]) * cG[4];
           genc[2] = (gd.z - cG[2]) * cG[5];

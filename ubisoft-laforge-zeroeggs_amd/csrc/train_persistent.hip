@@ -733,13 +733,12 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
         for (int q = 0; q < 6; ++q) p[q] = (FV(9 + q, b) + cB[9 + q][0]) * cB[9 + q][1] + cB[9 + q][2];
         const Q4 q = rq_;
         const V3 pos = rp_;
-        const V3 npos = quat_mul_vec(q, d.dt * v3(p[0], p[1], p[2])) + pos;
-        const V3 uu = quat_mul_vec(q, d.dt * v3(p[3], p[4], p[5]));
-        const Q4 nq = quat_exp_mul(0.5f * uu, q);
+        V3 npos; Q4 nq;
+        root_step(d.dt, q, pos, p, npos, nq);
         rq_ = nq; rp_ = npos;
         float genc[3] = {0.f, 0.f, 0.f};
         if (next) {
-          const V3 gd = quat_mul_vec(quat_inv(nq), v3(gz_[0], gz_[1], gz_[2]) - npos);
+          const V3 gd = gaze_dir(nq, npos, v3(gz_[0], gz_[1], gz_[2]));
           genc[0] = (gd.x - cG[0]) * cG[3];
           genc[1] = (gd.y - cG[1]) * cG[4];
           genc[2] = (gd.z - cG[2]) * cG[5];
