@@ -7,9 +7,16 @@
   time beside it (mel stays per row: rows pushes per tick).
   baseline, same session: zeggs.stream.GestureStream.push of the same 4-frame chunk at the same two ages (one stream, B = 1).
 
+  --leg push_many: the audio side of a tick, per rows in {1, 8, 32, 64}: two servers in ONE process are fed the same rows' signals
+  up to 10 s, then tick by tick the same chunks -- one through push() per stream, the other through ONE push_many() -- each
+  synchronised before and after the tick's pushes, taking turns, >= 200 ticks: median, p95, min, max of both, the step beside
+  them, what push_many enqueued, and whether the two servers' pending features are bitwise equal at the end
+  -> profiles/live_push_many.json.
+
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
     python tools/live_bench.py [--out profiles/live_stream.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
+    python tools/live_bench.py --leg push_many [--out profiles/live_push_many.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -96,6 +103,68 @@ def case_server(rows, age, steps):
                 uploaded_samples=srv.stats["uploaded_samples"])
 
 
+def case_push_many(rows, steps, age=10):
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    srv = {k: live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK) for k in ("push", "push_many")}
+    sids = {k: [s.open(first, st) for st in styles] for k, s in srv.items()}
+
+    def feed(k, lo, hi):
+        if k == "push":
+            for r, sid in enumerate(sids[k]):
+                srv[k].push(sid, _samples(base, r, lo, hi))
+        else:
+            srv[k].push_many({sid: _samples(base, r, lo, hi) for r, sid in enumerate(sids[k])})
+
+    pos = 0
+    while pos < age * FS:                                  # bring every row of both servers to the age
+        for k in srv:
+            feed(k, pos, pos + FS)
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    t = {k: dict(push=[], step=[]) for k in srv}
+    ops_seen, i = set(), 0
+    while len(t["push_many"]["step"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        for k in (("push", "push_many") if i % 2 else ("push_many", "push")):      # taking turns at going first
+            chunks = [_samples(base, r, pos, nxt) for r in range(rows)]            # (the slicing is not what is timed)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == "push":
+                for sid, c in zip(sids[k], chunks):
+                    srv[k].push(sid, c)
+            else:
+                srv[k].push_many(dict(zip(sids[k], chunks)))
+            torch.cuda.synchronize()
+            t[k]["push"].append(time.perf_counter() - t0)
+            if k == "push_many":
+                ops_seen.add(srv[k].stats["ops_last_push_many"])
+            while True:
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k]["step"].append(dt)
+        pos = nxt
+    a, b = srv["push"], srv["push_many"]
+    same = all((x.n, x.base, x.n_feat, x.fbase, x.n_ring, x.kd) == (y.n, y.base, y.n_feat, y.fbase, y.n_ring, y.kd)
+               for x, y in zip(a._rows, b._rows))
+    same = same and all(torch.equal(a.feats[r, w.n_ring - w.fbase:w.n_feat - w.fbase].view(torch.int32),
+                                    b.feats[r, w.n_ring - w.fbase:w.n_feat - w.fbase].view(torch.int32)) for r, w in enumerate(a._rows))
+    return dict(kind="push_many", rows=rows, age_s=age, tick=TICK, pushes_per_tick=_summary(t["push"]["push"]),
+                push_many_per_tick=_summary(t["push_many"]["push"]), step_beside_push=_summary(t["push"]["step"]),
+                step_beside_push_many=_summary(t["push_many"]["step"]), ops_per_push_many=sorted(ops_seen),
+                pending_features_bitwise_equal=bool(same))
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -127,15 +196,21 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--case", default=None, help="internal: one case in a child process, e.g. server:8:10 or baseline:600")
+    ap.add_argument("--leg", default="step", choices=("step", "push_many"))
+    ap.add_argument("--case", default=None, help="internal: one case in a child process, e.g. server:8:10, baseline:600 or push_many:64")
     a = ap.parse_args()
     if a.case:
         kind, *rest = a.case.split(":")
-        res = case_server(int(rest[0]), int(rest[1]), a.steps) if kind == "server" else case_baseline(int(rest[0]), a.steps)
+        res = (case_server(int(rest[0]), int(rest[1]), a.steps) if kind == "server" else
+               case_push_many(int(rest[0]), a.steps) if kind == "push_many" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
     cases = [f"baseline:{g}" for g in ages] + [f"server:{r}:{g}" for r in rows for g in ages]
+    if a.leg == "push_many":
+        cases = [f"push_many:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_push_many.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -147,6 +222,14 @@ def main():
         results.append(json.loads(line[7:]))
         print(c, line[7:], flush=True)
     import torch
+    if a.leg == "push_many":
+        pays = [r["rows"] for r in results if r["push_many_per_tick"]["median_ms"] < r["pushes_per_tick"]["median_ms"]]
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0),
+                   tick_frames=TICK, ticks_per_case=a.steps, row_counts_at_which_push_many_is_faster=pays, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
     budget = 1e3 * TICK / FPS
     srv = [r for r in results if r["kind"] == "server"]
     live_rows = {g: max([r["rows"] for r in srv if r["age_s"] == g and r["step"]["p95_ms"] < budget], default=0) for g in ages}

@@ -11,7 +11,7 @@ SRC="gemm gemm_split kernels attention encoders options decoder decoder_fast swe
 for f in $SRC; do
   stale=0
   [ -f $BD/$f.o ] || stale=1
-  for dep in $f.hip *.h ../../include/zeggs_hip.h; do      # every header: one missing from a list means stale objects
+  for dep in $f.hip *.h ../../include/zeggs_hip.h ../../include/zeggs_hip_live.h; do     # every header: one missing from a list means stale objects
     if [ $dep -nt $BD/$f.o ]; then stale=1; fi
   done
   if [ $stale = 1 ]; then

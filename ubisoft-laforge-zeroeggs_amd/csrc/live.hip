@@ -9,7 +9,7 @@
 // its output channel and the 64 lanes of a wave read 1 KB contiguously (zeggs_speech_encoder_live_prepare, once per weight set);
 // the KW - 1 + 8 activation rows a pass needs are staged in LDS and read as wave-uniform 16-byte broadcasts; per-row arguments
 // travel by value in the kernel arguments (scalar loads, no device-side table to upload); no scratch memory.
-#include "../../include/zeggs_hip.h"
+#include "../../include/zeggs_hip_live.h"
 #include "common.h"
 
 namespace {
@@ -199,5 +199,78 @@ extern "C" int zeggs_speech_encoder_live(const ZeggsLiveDims* dp, const ZeggsSpe
   hipLaunchKernelGGL(live_speech_k, dim3((unsigned)d.R), dim3(LTHR), live_lds(d), (hipStream_t)stream, d, lr, mean, stdv, feats, ring, out,
                      p, P->b0, P->b1, P->b2);
   ZLAUNCH_CHECK("live_speech");
+  return 0;
+}
+
+// ---------------------------------------------------------------- many small copies in one launch (include/zeggs_hip_live.h)
+// What a tick's audio side moves between device buffers -- window compactions, the new samples behind them, pending feature rows --
+// as ONE launch: blockIdx.y = segment, the workgroups of a segment stride over it.  Windows are appended at arbitrary sample
+// offsets, so a segment's ends are only float-aligned: where source and destination share their offset within 16 bytes the body
+// moves in 16-byte lanes between a scalar head and tail, otherwise float by float (coalesced either way).
+namespace {
+constexpr int SEG_THR = 256, SEG_MAX_X = 32;
+__global__ __launch_bounds__(SEG_THR) void copy_segments_k(const ZeggsSeg* __restrict__ segs) {
+  const ZeggsSeg sg = segs[blockIdx.y];
+  const float* src = sg.src;
+  float* dst = sg.dst;
+  const long cnt = sg.count;
+  if (cnt <= 0) return;
+  const uintptr_t sa = (uintptr_t)src, da = (uintptr_t)dst;
+  long head = cnt, nv = 0;
+  if (((sa ^ da) & 15) == 0) {
+    head = (long)(((16 - (da & 15)) & 15) >> 2);
+    if (head > cnt) head = cnt;
+    nv = (cnt - head) >> 2;
+  }
+  const long tail0 = head + 4 * nv, tid = (long)blockIdx.x * SEG_THR + threadIdx.x, stride = (long)gridDim.x * SEG_THR;
+  const f4* sv = (const f4*)(src + head);
+  f4* dv = (f4*)(dst + head);
+  for (long i = tid; i < nv; i += stride) dv[i] = sv[i];
+  for (long i = tid; i < head; i += stride) dst[i] = src[i];
+  for (long i = tail0 + tid; i < cnt; i += stride) dst[i] = src[i];
+}
+}  // namespace
+
+extern "C" int zeggs_copy_segments(const ZeggsSeg* segs, const ZeggsSeg* segs_dev, int n, void* stream) {
+  ZCHECK(n >= 0 && n <= ZEGGS_MAX_SEGMENTS, "copy segments: %d segments (0..%d)", n, ZEGGS_MAX_SEGMENTS);
+  if (n == 0) return 0;
+  ZCHECK(segs != nullptr, "copy segments: NULL records");
+  // destinations in address order: neighbours must not overlap, and no source may reach into any of them
+  struct Span { uintptr_t lo, hi; int i; };
+  Span dsts[ZEGGS_MAX_SEGMENTS];
+  int nd = 0;
+  long most = 0;
+  for (int i = 0; i < n; ++i) {
+    const ZeggsSeg& g = segs[i];
+    ZCHECK(g.count >= 0, "copy segments: segment %d: negative count %ld", i, g.count);
+    if (g.count == 0) continue;
+    ZCHECK(g.src != nullptr && g.dst != nullptr && (uintptr_t)g.src % 4 == 0 && (uintptr_t)g.dst % 4 == 0,
+           "copy segments: segment %d: NULL or misaligned pointer", i);
+    dsts[nd++] = Span{(uintptr_t)g.dst, (uintptr_t)(g.dst + g.count), i};
+    if (g.count > most) most = g.count;
+  }
+  if (nd == 0) return 0;
+  for (int i = 1; i < nd; ++i) {      // insertion sort: the callers' lists are short and nearly ordered
+    const Span x = dsts[i];
+    int j = i - 1;
+    for (; j >= 0 && dsts[j].lo > x.lo; --j) dsts[j + 1] = dsts[j];
+    dsts[j + 1] = x;
+  }
+  for (int i = 1; i < nd; ++i)
+    ZCHECK(dsts[i - 1].hi <= dsts[i].lo, "copy segments: the destinations of segments %d and %d overlap", dsts[i - 1].i, dsts[i].i);
+  for (int i = 0; i < n; ++i) {
+    const ZeggsSeg& g = segs[i];
+    if (g.count == 0) continue;
+    const uintptr_t lo = (uintptr_t)g.src, hi = (uintptr_t)(g.src + g.count);
+    int a = 0, b = nd;                  // first destination that ends above lo
+    while (a < b) { const int m = (a + b) / 2; if (dsts[m].hi > lo) b = m; else a = m + 1; }
+    ZCHECK(a == nd || dsts[a].lo >= hi, "copy segments: the source of segment %d overlaps the destination of segment %d", i,
+           a < nd ? dsts[a].i : -1);
+  }
+  ZCHECK(segs_dev != nullptr, "copy segments: the records must also be in device memory (segs_dev)");
+  const long gx = (most + 4 * SEG_THR - 1) / (4 * SEG_THR);
+  hipLaunchKernelGGL(copy_segments_k, dim3((unsigned)(gx > SEG_MAX_X ? SEG_MAX_X : gx), (unsigned)n), dim3(SEG_THR), 0, (hipStream_t)stream,
+                     segs_dev);
+  ZLAUNCH_CHECK("copy_segments");
   return 0;
 }

@@ -15,7 +15,7 @@
 // as a dense matrix resident in L2) and the log/normalise chain run on the same workgroup.
 #include <math.h>
 
-#include "../../include/zeggs_hip.h"
+#include "../../include/zeggs_hip_live.h"
 #include "common.h"
 
 namespace {
@@ -365,11 +365,12 @@ __host__ __device__ inline size_t mel_fft_lds(int NF, int n_mels) {
   return sizeof(double) * 2 * ((size_t)2 * FFB * (NF / 2)) + sizeof(double) * MFB_CAP + sizeof(int) * 3 * (size_t)n_mels + 64;
 }
 
-__global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan plan, const float* wav, long n, long n_avail,
-                                                      const double* fb, const c2* __restrict__ TW, const int* bands,
-                                                      const double* fbp, double* logmel, double* energy, long m0, long nfr, int exact,
-                                                      long base) {
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+// One workgroup's share: STFT frames fr0 .. fr0 + FFB - 1 of ONE signal -> logmel / energy slots slot0 .. (those below nfr are
+// stored).  The body of mel_stft_fft_k and of mel_stft_fft_batch_k: one statement of the per-frame arithmetic for both.
+__device__ __forceinline__ void mel_stft_fft_frames(const ZeggsMelDims& d, const FftPlan& plan, const float* wav, long n, long n_avail,
+                                                    const double* fb, const c2* __restrict__ TW, const int* bands,
+                                                    const double* fbp, double* logmel, double* energy, const long fr0,
+                                                    const long slot0, long nfr, int exact, long base, unsigned char* smem) {
   const int NF = d.n_fft, M = NF / 2, NBIN = M + 1, hop = d.hop, NM = d.n_mels;
   c2* bufA = (c2*)smem;                               // [FFB][M]
   c2* bufB = bufA + (size_t)FFB * M;                  // [FFB][M]
@@ -378,7 +379,6 @@ __global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan p
   int* bhi = blo + NM;
   int* bof = bhi + NM;
   const int tid = threadIdx.x;
-  const long fr0 = m0 + (long)blockIdx.x * FFB, slot0 = (long)blockIdx.x * FFB;
   const long neff = n > NF ? n : NF;
   const c2* WIN = TW + 2 * M + 1;
   // windowed samples, packed: z[m] = xw[2 m] + i xw[2 m + 1]
@@ -477,6 +477,39 @@ __global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan p
   }
 }
 
+__global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan plan, const float* wav, long n, long n_avail,
+                                                      const double* fb, const c2* __restrict__ TW, const int* bands,
+                                                      const double* fbp, double* logmel, double* energy, long m0, long nfr, int exact,
+                                                      long base) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, TW, bands, fbp, logmel, energy, m0 + (long)blockIdx.x * FFB, (long)blockIdx.x * FFB,
+                      nfr, exact, base, smem);
+}
+
+// The batched form (zeggs_mel_features_batch): workgroup b works on row r with blk0[r] <= b < blk0[r + 1], block b - blk0[r] of that
+// row's nfr[r] STFT frames m0[r] ..; a row's logmel / energy slots are [r S, r S + nfr[r]).  What the host derived per row travels by
+// value (1.5 KB); the records themselves (pointers, counts) are read from device memory, wave-uniformly.
+struct MelBatchPlan {
+  int blk0[ZEGGS_LIVE_MAX_ROWS + 1];
+  int nfr[ZEGGS_LIVE_MAX_ROWS];
+  long m0[ZEGGS_LIVE_MAX_ROWS];
+  long M[ZEGGS_LIVE_MAX_ROWS];       // STFT frames of the finished signal (final) or 2^40
+};
+__global__ __launch_bounds__(FTHR) void mel_stft_fft_batch_k(ZeggsMelDims d, FftPlan plan, const ZeggsMelRow* __restrict__ rows,
+                                                            MelBatchPlan bp, int R, long S, const double* fb,
+                                                            const c2* __restrict__ TW, const int* bands, const double* fbp,
+                                                            double* logmel, double* energy, int exact) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  int r = 0;
+  while (r + 1 < R && (int)blockIdx.x >= bp.blk0[r + 1]) ++r;
+  const long blk = (long)((int)blockIdx.x - bp.blk0[r]);
+  const float* wav = rows[r].wav;
+  const long n_avail = rows[r].n_samples, base = rows[r].base;
+  const long n = rows[r].final ? n_avail : (1L << 50);
+  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, TW, bands, fbp, logmel + (size_t)r * S * d.n_mels, energy + (size_t)r * S,
+                      bp.m0[r] + blk * FFB, blk * FFB, (long)bp.nfr[r], exact, base, smem);
+}
+
 // resample_method = "cubic": interp1d(kind = "cubic") = the interpolating cubic spline with not-a-knot ends (make_interp_spline(k = 3)) over
 // the integer frame grid 0 .. M-1, one per column (80 mel channels, griddata's 1-D path, + the energy).  In terms of the second derivatives
 // S_i:  S_{i-1} + 4 S_i + S_{i+1} = 6 (y_{i-1} - 2 y_i + y_{i+1}) =: r_i  (i = 1 .. M-2), and the not-a-knot conditions S_0 - 2 S_1 + S_2 = 0,
@@ -550,36 +583,48 @@ __global__ __launch_bounds__(128) void mel_spline_solve_k(ZeggsMelDims d, long M
 // (interp1d(fill_value = "extrapolate"): the end pieces continue); "nearest": both take the nearest frame, halves round DOWN, ends clamp
 // (interp1d's bounds x_i + 1/2 searched from the left; griddata sets fill_value = "extrapolate" for this method).
 // animation frames k0 .. k0 + n_frames - 1; logmel / energy hold the STFT frames m0 .. (indices relative to m0)
+// one element: column c (mel channel, or the energy at c == n_mels) of animation frame k; logmel / energy indexed by ABSOLUTE STFT frame
+__device__ __forceinline__ float mel_resample_elem(const ZeggsMelDims& d, const double* logmel, const double* energy, const double* spl,
+                                                   long M, int c, long k) {
+  const int W = d.n_mels + 1;
+  const double t = (((double)d.fs / (double)d.hop) / (double)d.fps) * (double)k;
+  if (d.flags & MEL_NEAREST) {
+    long q = (long)ceil(t - 0.5);
+    q = q < 0 ? 0 : q > M - 1 ? M - 1 : q;
+    return (float)(c < d.n_mels ? logmel[q * d.n_mels + c] : energy[q]);
+  }
+  long hi = (long)ceil(t);            // searchsorted(side=left) over the integer grid
+  if (hi < 1) hi = 1;
+  if (hi > M - 1) hi = M - 1;
+  const long lo = hi - 1;
+  if (M < 2) return nanf("");
+  if (c < d.n_mels && (t < 0.0 || t > (double)(M - 1))) return nanf("");
+  const double ylo = c < d.n_mels ? logmel[lo * d.n_mels + c] : energy[lo], yhi = c < d.n_mels ? logmel[hi * d.n_mels + c] : energy[hi];
+  if (d.flags & MEL_CUBIC) {
+    const double u = t - (double)lo, v = 1.0 - u;
+    return (float)(ylo * v + yhi * u + ((v * v * v - v) * spl[lo * W + c] + (u * u * u - u) * spl[hi * W + c]) / 6.0);
+  }
+  return (float)((yhi - ylo) * (t - (double)lo) + ylo);
+}
 __global__ void mel_resample_k(ZeggsMelDims d, const double* logmel, const double* energy, const double* spl, long M, long m0, long k0,
                                int n_frames, float* out) {
   const int W = d.n_mels + 1;
   const long n = (long)n_frames * W;
   logmel -= m0 * d.n_mels;
   energy -= m0;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % W);
-    const long k = k0 + i / W;
-    const double t = (((double)d.fs / (double)d.hop) / (double)d.fps) * (double)k;
-    if (d.flags & MEL_NEAREST) {
-      long q = (long)ceil(t - 0.5);
-      q = q < 0 ? 0 : q > M - 1 ? M - 1 : q;
-      out[i] = (float)(c < d.n_mels ? logmel[q * d.n_mels + c] : energy[q]);
-      continue;
-    }
-    long hi = (long)ceil(t);            // searchsorted(side=left) over the integer grid
-    if (hi < 1) hi = 1;
-    if (hi > M - 1) hi = M - 1;
-    const long lo = hi - 1;
-    if (M < 2) { out[i] = nanf(""); continue; }
-    if (c < d.n_mels && (t < 0.0 || t > (double)(M - 1))) { out[i] = nanf(""); continue; }
-    const double ylo = c < d.n_mels ? logmel[lo * d.n_mels + c] : energy[lo], yhi = c < d.n_mels ? logmel[hi * d.n_mels + c] : energy[hi];
-    if (d.flags & MEL_CUBIC) {
-      const double u = t - (double)lo, v = 1.0 - u;
-      out[i] = (float)(ylo * v + yhi * u + ((v * v * v - v) * spl[lo * W + c] + (u * u * u - u) * spl[hi * W + c]) / 6.0);
-    } else {
-      out[i] = (float)((yhi - ylo) * (t - (double)lo) + ylo);
-    }
-  }
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    out[i] = mel_resample_elem(d, logmel, energy, spl, M, (int)(i % W), k0 + i / W);
+}
+// the batched sibling: blockIdx.y = row; M, m0 (plan) and k0, the frame count and the output (record) are the row's own
+__global__ void mel_resample_batch_k(ZeggsMelDims d, const ZeggsMelRow* __restrict__ rows, MelBatchPlan bp, long S, const double* logmel,
+                                     const double* energy) {
+  const int W = d.n_mels + 1, r = blockIdx.y;
+  const long k0 = rows[r].k0, n = (rows[r].k1 - k0) * W;
+  float* out = rows[r].out;
+  logmel += ((long)r * S - bp.m0[r]) * d.n_mels;
+  energy += (long)r * S - bp.m0[r];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
+    out[i] = mel_resample_elem(d, logmel, energy, nullptr, bp.M[r], (int)(i % W), k0 + i / W);
 }
 
 }  // namespace
@@ -603,15 +648,23 @@ static FftPlan fft_plan(int M) {
   return p;
 }
 
+thread_local int t_mel_launches = 0;      // kernels enqueued by this thread's range / window / batch calls (zeggs_mel_batch_last_ops)
+
+// whether the FFT form takes these dimensions (and the option allows it); *plan: its radices
+static bool mel_fft_form(const ZeggsMelDims& d, FftPlan* plan) {
+  *plan = fft_plan(d.n_fft / 2);
+  return g_mel_fft && plan->nst > 0 && d.n_fft % 2 == 0 && mel_fft_lds(d.n_fft, d.n_mels) <= 160 * 1024 &&
+         (size_t)FFB * d.n_mels <= (size_t)2 * FFB * (d.n_fft / 2);
+}
+
 // STFT frames m0 .. m0 + nfr - 1 -> logmel / energy slots 0 .. nfr - 1
 // (`base`: index of wav[0] in the signal, see mel_sample)
 static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, long n, long n_avail, const double* fb, long m0,
                        long nfr, hipStream_t s, long base = 0) {
   const int NBIN = d.n_fft / 2 + 1;
-  const FftPlan plan = fft_plan(d.n_fft / 2);
+  FftPlan plan;
   const size_t fft_lds = mel_fft_lds(d.n_fft, d.n_mels);
-  if (g_mel_fft && plan.nst > 0 && d.n_fft % 2 == 0 && fft_lds <= 160 * 1024 && (size_t)FFB * d.n_mels <= (size_t)2 * FFB * (d.n_fft / 2) &&
-      nfr >= 1) {
+  if (mel_fft_form(d, &plan) && nfr >= 1) {
     static bool fft_attr_set = false;
     if (!fft_attr_set) {
       if (hipFuncSetAttribute((const void*)mel_stft_fft_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
@@ -625,6 +678,7 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
     hipLaunchKernelGGL(mel_stft_fft_k, dim3((unsigned)((nfr + FFB - 1) / FFB)), dim3(FTHR), fft_lds, s, d, plan, wav, n, n_avail, fb,
                        (const c2*)w.ftw, w.bands, w.fbp, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_fft");
+    t_mel_launches += 2;
     return 0;
   }
   const size_t fast_lds = mel_fast_lds(d.n_fft, d.hop, d.n_mels);
@@ -639,11 +693,13 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
     hipLaunchKernelGGL(mel_stft_mfma_k, dim3((unsigned)((nfr + MF - 1) / MF)), dim3(MWAVES * 64), fast_lds, s, d, wav, n, n_avail,
                        fb, w.table, w.win, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_mfma");
+    t_mel_launches += 2;
     return 0;
   }
   const size_t lds = sizeof(double) * (3 * (size_t)d.n_fft + d.n_fft / 2 + 1 + d.n_mels);
   hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.logmel, w.energy, m0, g_mel_exact_log, base);
   ZLAUNCH_CHECK("mel_stft");
+  t_mel_launches += 1;
   return 0;
 }
 
@@ -763,21 +819,29 @@ extern "C" long zeggs_mel_window_first_sample(const ZeggsMelDims* d, long k0) {
   const long f = mel_first_load(*d, m0, m1, 1L << 50, 1L << 50);      // (the signal continues: no right end)
   return f == __LONG_MAX__ ? 0 : f;
 }
+// the argument checks of a range / window call, ahead of any launch (`who`: "" or the batched call's "mel batch: row r: ");
+// -> the STFT frames [m0, m1) the range interpolates and M
+static int mel_range_check(const ZeggsMelDims& d, long base, long n_samples, int final, long k0, long k1, const char* who, long* M,
+                           long* m0, long* m1) {
+  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "%smel: bad dims", who);
+  ZCHECK(n_samples > 0 && k0 >= 0 && k1 > k0, "%smel range: empty input", who);
+  ZCHECK(!(d.flags & MEL_CUBIC), "%smel range: resample_method \"cubic\" is a spline over the WHOLE signal -- use zeggs_mel_features", who);
+  if (!final)
+    ZCHECK(k1 <= zeggs_mel_frames_ready(&d, n_samples), "%smel range: frames %ld..%ld need samples not received yet", who, k0, k1);
+  mel_range_stft(d, n_samples, final, k0, k1, M, m0, m1);
+  if (base > 0) {
+    const long first = mel_first_load(d, *m0, *m1, final ? n_samples : (1L << 50), n_samples);
+    ZCHECK(base <= first, "%smel window: frames %ld..%ld read sample %ld, the window starts at %ld", who, k0, k1, first, base);
+  }
+  return 0;
+}
 static int mel_range_impl(const ZeggsMelDims* dp, const float* wav, long base, long n_samples, int final, const double* filterbank,
                           long k0, long k1, float* out, void* ws, size_t ws_bytes, void* stream) {
   const ZeggsMelDims& d = *dp;
   hipStream_t s = (hipStream_t)stream;
-  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "mel: bad dims");
-  ZCHECK(n_samples > 0 && k0 >= 0 && k1 > k0, "mel range: empty input");
-  ZCHECK(!(d.flags & MEL_CUBIC), "mel range: resample_method \"cubic\" is a spline over the WHOLE signal -- use zeggs_mel_features");
-  if (!final) ZCHECK(k1 <= zeggs_mel_frames_ready(dp, n_samples), "mel range: frames %ld..%ld need samples not received yet", k0, k1);
   long M, m0, m1;
-  mel_range_stft(d, n_samples, final, k0, k1, &M, &m0, &m1);
+  ZTRY(mel_range_check(d, base, n_samples, final, k0, k1, "", &M, &m0, &m1));
   const long n = final ? n_samples : (1L << 50);
-  if (base > 0) {
-    const long first = mel_first_load(d, m0, m1, n, n_samples);
-    ZCHECK(base <= first, "mel window: frames %ld..%ld read sample %ld, the window starts at %ld", k0, k1, first, base);
-  }
   Arena a(ws, ws_bytes);
   MelWs w = carve_mel(d, m1 - m0, a);
   ZCHECK(a.ok(), "mel range: workspace too small (%zu < %zu)", ws_bytes, a.off);
@@ -786,6 +850,7 @@ static int mel_range_impl(const ZeggsMelDims* dp, const float* wav, long base, l
   hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.logmel, w.energy, nullptr, M, m0, k0,
                      (int)(k1 - k0), out);
   ZLAUNCH_CHECK("mel_resample");
+  t_mel_launches += 1;
   return 0;
 }
 extern "C" int zeggs_mel_features_range(const ZeggsMelDims* dp, const float* wav, long n_samples, int final,
@@ -802,4 +867,137 @@ extern "C" int zeggs_mel_features_window(const ZeggsMelDims* dp, const float* wa
                                          void* stream) {
   ZCHECK(base >= 0 && base < n_samples, "mel window: the window [%ld, %ld) is empty", base, n_samples);
   return mel_range_impl(dp, wav_window, base, n_samples, final, filterbank, k0, k1, out, ws, ws_bytes, stream);
+}
+
+// ---------------------------------------------------------------- batched form (include/zeggs_hip_live.h)
+namespace {
+struct MelTables { c2* ftw; double* fbp; int* bands; };
+MelTables carve_mel_tables(const ZeggsMelDims& d, Arena& a) {
+  MelTables t;
+  t.ftw = (c2*)a.raw(sizeof(double) * 2 * ((size_t)2 * d.n_fft + 1));
+  t.fbp = (double*)a.raw(sizeof(double) * MFB_CAP);
+  t.bands = (int*)a.raw(sizeof(int) * 3 * (size_t)d.n_mels);
+  return t;
+}
+// STFT slots per row of a call whose rows ask for at most F animation frames each (m1 - m0 <= r (F - 1) + 3, mel_range_stft)
+long mel_batch_slots(const ZeggsMelDims& d, long F) {
+  return (long)ceil((((double)d.fs / (double)d.hop) / (double)d.fps) * (double)(F > 1 ? F : 1)) + 4;
+}
+struct MelBatchWs { ZeggsMelRow* rows; double* logmel; double* energy; void* row_ws; size_t row_ws_bytes; };
+// records | logmel, energy of all rows; the fall-back's per-row workspace shares the second region (the rows run one after another)
+MelBatchWs carve_mel_batch(const ZeggsMelDims& d, int R, long S, Arena& a) {
+  MelBatchWs w;
+  w.rows = (ZeggsMelRow*)a.raw(sizeof(ZeggsMelRow) * ZEGGS_LIVE_MAX_ROWS);
+  const size_t mark = align_up(a.off, 256);
+  w.logmel = (double*)a.raw(sizeof(double) * (size_t)R * S * d.n_mels);
+  w.energy = (double*)a.raw(sizeof(double) * (size_t)R * S);
+  const size_t end = a.off;
+  Arena b(nullptr, 0);
+  carve_mel(d, S, b);
+  w.row_ws = a.dry ? nullptr : (void*)(a.base + mark);
+  w.row_ws_bytes = b.off;
+  if (mark + b.off > end) a.off = mark + b.off;
+  return w;
+}
+}  // namespace
+
+extern "C" size_t zeggs_mel_batch_tables_bytes(const ZeggsMelDims* d) {
+  Arena a(nullptr, 0);
+  carve_mel_tables(*d, a);
+  return a.off + 256;
+}
+
+extern "C" int zeggs_mel_batch_prepare(const ZeggsMelDims* dp, const double* filterbank, void* tables, size_t bytes, void* stream) {
+  const ZeggsMelDims& d = *dp;
+  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "mel: bad dims");
+  Arena a(tables, bytes);
+  MelTables t = carve_mel_tables(d, a);
+  ZCHECK(tables != nullptr && filterbank != nullptr && a.ok(), "mel batch: table buffer too small (%zu < %zu)", bytes, a.off);
+  hipLaunchKernelGGL(mel_fft_table_k, dim3(16), dim3(256), 0, (hipStream_t)stream, t.ftw, d.n_fft / 2, filterbank, d.n_mels, t.bands, t.fbp);
+  ZLAUNCH_CHECK("mel_fft_table");
+  return 0;
+}
+
+extern "C" size_t zeggs_mel_batch_workspace_bytes(const ZeggsMelDims* d, int rows, long max_frames_per_row) {
+  Arena a(nullptr, 0);
+  carve_mel_batch(*d, rows, mel_batch_slots(*d, max_frames_per_row), a);
+  return a.off + 256;
+}
+
+extern "C" int zeggs_mel_batch_last_ops() { return t_mel_launches; }
+
+extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRow* rows, const ZeggsMelRow* rows_dev, int R,
+                                        const double* filterbank, const void* tables, void* ws, size_t ws_bytes, void* stream) {
+  const ZeggsMelDims& d = *dp;
+  hipStream_t s = (hipStream_t)stream;
+  t_mel_launches = 0;
+  ZCHECK(R >= 1 && R <= ZEGGS_LIVE_MAX_ROWS, "mel batch: %d rows (1..%d)", R, ZEGGS_LIVE_MAX_ROWS);
+  ZCHECK(rows != nullptr && filterbank != nullptr && tables != nullptr && ws != nullptr, "mel batch: NULL argument");
+  ZCHECK(d.n_fft >= 2 && d.n_fft % 2 == 0 && d.hop > 0 && d.n_mels > 0, "mel: bad dims");
+  // ---- every row's checks, all ahead of any launch
+  MelBatchPlan bp{};
+  long maxF = 0, max_elems = 0;
+  int live = 0;
+  for (int r = 0; r < R; ++r) {
+    const ZeggsMelRow& w = rows[r];
+    char who[40];
+    snprintf(who, sizeof who, "mel batch: row %d: ", r);
+    bp.blk0[r + 1] = bp.blk0[r];
+    ZCHECK(w.k0 >= 0 && w.k1 >= w.k0, "%sframes %ld..%ld", who, w.k0, w.k1);
+    if (w.k1 == w.k0) continue;      // the row takes no part
+    ZCHECK(w.wav != nullptr && w.out != nullptr, "%sNULL window or output", who);
+    ZCHECK(w.base >= 0 && w.base < w.n_samples, "%smel window: the window [%ld, %ld) is empty", who, w.base, w.n_samples);
+    long m1;
+    ZTRY(mel_range_check(d, w.base, w.n_samples, w.final, w.k0, w.k1, who, &bp.M[r], &bp.m0[r], &m1));
+    bp.nfr[r] = (int)(m1 - bp.m0[r]);
+    bp.blk0[r + 1] = bp.blk0[r] + (bp.nfr[r] + FFB - 1) / FFB;
+    if (w.k1 - w.k0 > maxF) maxF = w.k1 - w.k0;
+    ++live;
+  }
+  const long S = mel_batch_slots(d, maxF);
+  Arena a(ws, ws_bytes);
+  MelBatchWs w = carve_mel_batch(d, R, S, a);
+  ZCHECK(a.off + 256 <= ws_bytes, "mel batch: workspace too small (%zu < %zu)", ws_bytes, a.off + 256);
+  for (int r = 0; r < R; ++r) ZCHECK(bp.nfr[r] <= S, "mel batch: row %d: %d STFT frames in %ld slots", r, bp.nfr[r], S);
+  if (live == 0) return 0;
+  FftPlan plan;
+  if (!mel_fft_form(d, &plan)) {      // the per-row path, row after row (each call checks its row again)
+    for (int r = 0; r < R; ++r) {
+      const ZeggsMelRow& q = rows[r];
+      if (q.k1 == q.k0) continue;
+      ZTRY(mel_range_impl(dp, q.wav, q.base, q.n_samples, q.final, filterbank, q.k0, q.k1, q.out, w.row_ws, w.row_ws_bytes, stream));
+    }
+    return 0;
+  }
+  static bool attr_set = false;      // (per kernel: mel_stft_fft_k's own opt-in does not cover this one)
+  if (!attr_set) {
+    if (hipFuncSetAttribute((const void*)mel_stft_fft_batch_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
+      zeggs_set_error("mel batch: cannot raise the LDS limit of the FFT kernel");
+      return -1;
+    }
+    attr_set = true;
+  }
+  if (rows_dev == nullptr) {
+    if (hipMemcpyAsync(w.rows, rows, sizeof(ZeggsMelRow) * R, hipMemcpyHostToDevice, s) != hipSuccess) {
+      zeggs_set_error("mel batch: cannot upload the row records");
+      return -1;
+    }
+    rows_dev = w.rows;
+    ++t_mel_launches;
+  }
+  Arena ta((void*)tables, (size_t)1 << 40);
+  const MelTables t = carve_mel_tables(d, ta);
+  hipLaunchKernelGGL(mel_stft_fft_batch_k, dim3((unsigned)bp.blk0[R]), dim3(FTHR), mel_fft_lds(d.n_fft, d.n_mels), s, d, plan, rows_dev, bp,
+                     R, S, filterbank, (const c2*)t.ftw, (const int*)t.bands, (const double*)t.fbp, w.logmel, w.energy, g_mel_exact_log);
+  ZLAUNCH_CHECK("mel_stft_fft_batch");
+  for (int r = 0; r < R; ++r) {
+    const long e = (rows[r].k1 - rows[r].k0) * (d.n_mels + 1);
+    if (e > max_elems) max_elems = e;
+  }
+  const long g = (max_elems + 255) / 256;
+  hipLaunchKernelGGL(mel_resample_batch_k, dim3((unsigned)(g > 64 ? 64 : g), (unsigned)R), dim3(256), 0, s, d, rows_dev, bp, S,
+                     (const double*)w.logmel, (const double*)w.energy);
+  ZLAUNCH_CHECK("mel_resample_batch");
+  t_mel_launches += 2;
+  return 0;
 }

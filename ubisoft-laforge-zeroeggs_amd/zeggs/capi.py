@@ -9,7 +9,8 @@ per function, and the two handles of the library.
           tests, tools and the benchmark call it with hand-wrapped arguments and look at the return codes themselves.  Both
           handles share the dlopen handle, and so every global of the library.
 
-A new entry point is a declaration in the header plus one row in PROTOTYPES (tests/test_abi.py compares the two).  torch is
+A new entry point is a declaration in the header plus one row in PROTOTYPES (tests/test_abi.py compares the two); the second
+header include/zeggs_hip_live.h has its own tables, EXT_STRUCTS / EXT_PROTOTYPES (tests/test_live_push_cpu.py), same loader.  torch is
 imported when a tensor is first converted, not when this module is.
 """
 import ctypes as C
@@ -218,6 +219,21 @@ PROTOTYPES = {
     "zeggs_sweep_graph_stats": "status: host* host*",
 }
 
+# ----------------------------------------------------------------------------- the second header (include/zeggs_hip_live.h)
+# Per-row records with device pointers inside (the main header's set is closed: tests/test_abi.py); bound by the same loader.
+MelRow = _struct("MelRow", [(C.c_void_p, "wav out"), (C.c_long, "base n_samples k0 k1"), (C.c_int, "final")])
+Seg = _struct("Seg", [(C.c_void_p, "src dst"), (C.c_long, "count")])
+EXT_STRUCTS = {"ZeggsMelRow": MelRow, "ZeggsSeg": Seg}
+EXT_PROTOTYPES = {
+    "zeggs_mel_batch_tables_bytes": "size_t: ZeggsMelDims*",
+    "zeggs_mel_batch_prepare": "status: ZeggsMelDims* f64* any* size_t stream",
+    "zeggs_mel_batch_workspace_bytes": "size_t: ZeggsMelDims* int long",
+    # rows_host: a HOST array of ZeggsMelRow; rows_dev: the same records on the device (an address cast to the pointer type) or None
+    "zeggs_mel_features_batch": "status: ZeggsMelDims* ZeggsMelRow* ZeggsMelRow* int f64* any* any* size_t stream",
+    "zeggs_mel_batch_last_ops": "int:",
+    "zeggs_copy_segments": "status: ZeggsSeg* ZeggsSeg* int stream",
+}
+
 
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
@@ -257,13 +273,13 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in STRUCTS.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
-    ret, _, params = PROTOTYPES[name].partition(":")
+    ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -301,7 +317,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in PROTOTYPES if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -313,7 +329,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in PROTOTYPES:
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

@@ -5,6 +5,8 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
 
   * push(sid, chunk) uploads ONLY the new samples into the row's device window (fixed capacity; the samples no later frame loads,
     zeggs_mel_window_first_sample, are dropped) and computes the mel rows that became ready (zeggs_mel_features_window);
+  * push_many({sid: chunk}) is push() for all streams of a tick at once: the same bookkeeping and feature bits, but one upload, one
+    or two zeggs_copy_segments launches and the two launches of zeggs_mel_features_batch whatever the number of rows;
   * step() advances every row that has `tick` decodable frames by exactly `tick` frames: ONE zeggs_speech_encoder_live launch
     (layer-0 activations live in a per-row ring, so nothing is re-encoded) and ONE decoder call for all rows --
     zeggs_decoder_fwd_batch at B = rows, T = tick + 1 (index 0 = the last frame already produced), the weight-stationary sweep where
@@ -14,8 +16,10 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
   * close(sid) flushes the row's remaining frames with the true right-edge rules (B = 1 entry point) and frees the row.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
-look-ahead + one STFT window.  Not here: batching the mel launches across rows, a network front door.
+look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
 """
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -53,6 +57,91 @@ def plan_step(rows, tick, depth, lookahead=LOOKAHEAD):
         plan.append(dict(k0=kd, k1=kd + tick, enc_k0=kd - 1, n_out=tick + 1, n_new=n_new,
                          slots=[(n_ring + i) % depth for i in range(n_new)]))
     return plan
+
+
+def plan_push(rows, caps, lens, FC, width, first_sample, frames_ready):
+    """The pure part of push_many(): push()'s bookkeeping for several rows, in order, as ONE list of copies.  rows[i]: dict with
+    n, base (samples received / absolute index of the window's first sample), n_feat, fbase, n_ring (feature rows computed / frame of
+    the pending block's first row / frames in the ring); caps[i]: capacity of the row's window; lens[i]: samples of its chunk (0: the
+    row takes no part, as push() returns at once); FC: rows of a pending-feature block, `width` floats each; first_sample(k):
+    zeggs_mel_window_first_sample; frames_ready(n): feature rows computable from n samples while the signal goes on.
+    -> dict(rows=[dict(n, base, n_feat, fbase: the new counters; cap: capacity the row's window needs; swap: the window was
+    compacted INTO the row's alternate buffer, which is the current one from now on; k0, k1: feature rows to compute, into row
+    k0 - fbase of the block)], segs, segs_back: the copies of the first and the second launch, FC: the (grown) block size,
+    n_stage: samples in the staging area).  A copy is (src, src_off, dst, dst_off, count) in floats; src / dst are ("win", i) the
+    row's current window BEFORE the call, ("alt", i) its alternate, ("stage", None) all chunks one after another, ("feats", i)
+    the row's pending block, ("scratch", i) the row's block of the scratch area.  No copy is in place: a compaction goes to the
+    other buffer, kept feature rows go to scratch and come back in the second launch (the block itself cannot move: the encoder
+    reads it at a fixed stride)."""
+    out, segs, back, soff = [], [], [], 0
+    for i, (st, cap, m) in enumerate(zip(rows, caps, lens)):
+        n, base, n_feat, fbase, n_ring = (int(st[k]) for k in ("n", "base", "n_feat", "fbase", "n_ring"))
+        cap, m, swap, k0, k1 = int(cap), int(m), False, n_feat, n_feat
+        if m > 0:
+            if n - base + m > cap:
+                # drop what no frame >= n_feat loads any more; grow only if this single chunk does not fit beside what must stay
+                nb = max(base, min(first_sample(n_feat), n))
+                keep = n - nb
+                cap = max(cap, keep + m)
+                if keep:
+                    segs.append((("win", i), nb - base, ("alt", i), 0, keep))
+                swap, base = True, nb
+            segs.append((("stage", None), soff, ("alt" if swap else "win", i), n - base, m))
+            soff += m
+            n += m
+            k1 = max(int(frames_ready(n)), k0)
+            if k1 > k0:
+                pend = k0 - n_ring                           # rows still waiting for the ring: frames n_ring .. k0 - 1
+                if k0 - fbase + (k1 - k0) > FC:              # compact (and grow if this one chunk needs more than the block holds)
+                    FC = max(FC, pend + (k1 - k0))
+                    if pend:
+                        segs.append((("feats", i), (n_ring - fbase) * width, ("scratch", i), 0, pend * width))
+                        back.append((("scratch", i), 0, ("feats", i), 0, pend * width))
+                    fbase = n_ring
+                n_feat = k1
+        out.append(dict(n=n, base=base, n_feat=n_feat, fbase=fbase, cap=cap, swap=swap, k0=k0, k1=k1))
+    return dict(rows=out, segs=segs, segs_back=back, FC=FC, n_stage=soff)
+
+
+class _Staging:
+    """What one push_many() uploads, as ONE block: [copy records | copy records of the second launch | mel records | samples].
+    Two pinned host blocks take turns, each guarded by an event recorded behind its copy, so a block is never rewritten while a
+    copy from it may be in flight; one device block (calls on a stream are ordered)."""
+
+    def __init__(self, rows, n_samples, dev):
+        a64 = lambda x: (x + 63) // 64 * 64  # noqa: E731
+        self.rows, self.n_samples = rows, int(n_samples)
+        self.o_back = a64(3 * rows * C.sizeof(ops.Seg))
+        self.o_mel = self.o_back + a64(rows * C.sizeof(ops.Seg))
+        self.o_smp = self.o_mel + a64(rows * C.sizeof(ops.MelRow))
+        self.nbytes = self.o_smp + 4 * self.n_samples
+        self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
+        self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.view = []
+        for h in self.host:
+            b = h.numpy()
+            self.view.append(dict(segs=(ops.Seg * (3 * rows)).from_buffer(b, 0), back=(ops.Seg * rows).from_buffer(b, self.o_back),
+                                  mel=(ops.MelRow * rows).from_buffer(b, self.o_mel), smp=b[self.o_smp:].view(np.float32)))
+        self.events, self.turn = [None, None], 0
+
+    def take(self):
+        """the next host block, once the copy that last read it is done"""
+        self.turn ^= 1
+        if self.events[self.turn] is not None:
+            self.events[self.turn].synchronize()
+        return self.view[self.turn]
+
+    def upload(self, n_samples):
+        nb = self.o_smp + 4 * int(n_samples)
+        self.dev[:nb].copy_(self.host[self.turn][:nb], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[self.turn] = ev
+
+    def idle(self):
+        for ev in self.events:
+            if ev is not None:
+                ev.synchronize()
 
 
 class _Row:
@@ -117,13 +206,19 @@ class LiveServer:
         self.gaze = z(R, self.T, 3)
         self.sty_old, self.sty_new = z(R, ST), z(R, ST)             # style(f) = lerp(old, new, style_weight(f, k_style, fade))
         self.mel_ws = ops.mel_range_workspace(self.mel, self.FC + 2, self.dev)
+        # push_many(): the window's alternate buffer (a compaction copies into it and the two swap), scratch for kept feature
+        # rows, the batched front-end's tables and workspace, the staging blocks of the one upload per call
+        self._alt = [z(int(window_capacity)) for _ in range(R)]
+        self._scratch = torch.empty_like(self.feats)
+        self._mb = ops.MelBatch(self.mel, self.fb, R, self.FC, self.dev)
+        self._stage = _Staging(R, R * 2048, self.dev)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
         self._sids, self._next_sid = {}, 0
         self._ops = 0
         self.stats = dict(uploaded_samples=0, window_capacity=[int(window_capacity)] * R, ring_bytes=self.ring.numel() * 4,
-                          launches_per_step=0, steps=0)
+                          launches_per_step=0, steps=0, ops_last_push_many=0)
 
     # ------------------------------------------------------------------ rows
     def _row(self, sid):
@@ -153,6 +248,16 @@ class LiveServer:
         return sid
 
     # ------------------------------------------------------------------ audio
+    def _grow_feats(self, FC):
+        """more rows per pending-feature block (one push brought more frames than a block holds): every row's block is re-laid"""
+        self.FC = FC
+        grown = torch.zeros(self.rows, FC, self.feats.shape[2], device=self.dev)
+        grown[:, :self.feats.shape[1]] = self.feats
+        self.feats = grown
+        self._scratch = torch.empty_like(grown)
+        self.mel_ws = ops.mel_range_workspace(self.mel, FC + 2, self.dev)
+        self._mb.resize(FC)
+
     def _features(self, r, row, k1, final):
         """feature rows [n_feat, k1) of row r from its window -> feats[r]"""
         k0 = row.n_feat
@@ -162,11 +267,7 @@ class LiveServer:
         if k0 - row.fbase + (k1 - k0) > self.FC:         # compact (and grow if this one push needs more than the block holds)
             keep = self.feats[r, row.n_ring - row.fbase:k0 - row.fbase].clone()
             if pend + (k1 - k0) > self.FC:
-                self.FC = pend + (k1 - k0)
-                grown = torch.zeros(self.rows, self.FC, self.feats.shape[2], device=self.dev)
-                grown[:, :self.feats.shape[1]] = self.feats
-                self.feats = grown
-                self.mel_ws = ops.mel_range_workspace(self.mel, self.FC + 2, self.dev)
+                self._grow_feats(pend + (k1 - k0))
             self.feats[r, :pend] = keep
             row.fbase = row.n_ring
         out = self.feats[r, k0 - row.fbase:k1 - row.fbase]
@@ -197,6 +298,76 @@ class LiveServer:
         self.stats["uploaded_samples"] += m
         ready = min(ops.mel_frames_ready(self.mel, row.n), audio.n_anim_frames(row.n, self.fs, self.fps) - 1)
         self._features(r, row, ready, final=False)       # (never ahead of the final frame count: it can only grow)
+
+    def push_many(self, chunks):
+        """push() for many streams at once: chunks = {sid: samples}.  Same bookkeeping per row (plan_push), same feature bits,
+        but what the call enqueues does not depend on the number of rows: ONE upload (copy records, mel records and all new
+        samples in a pinned block), ONE zeggs_copy_segments (window compactions into the alternate buffers, the new samples
+        behind them, kept feature rows to scratch), a second one only when some row compacts its feature block, and the TWO
+        launches of zeggs_mel_features_batch -- stats["ops_last_push_many"] <= 5.  Growth (a chunk that does not fit its window,
+        more new frames than a feature block holds) reallocates first, as in push().  An unknown sid raises KeyError before
+        anything changes."""
+        items = [(self._row(sid), np.ascontiguousarray(c, dtype=np.float32).reshape(-1)) for sid, c in chunks.items()]
+        items = [(r, row, c) for (r, row), c in items if c.size]
+        self.stats["ops_last_push_many"] = n_ops = 0
+        if not items:
+            return
+        F = self.feats.shape[2]
+        plan = plan_push([dict(n=w.n, base=w.base, n_feat=w.n_feat, fbase=w.fbase, n_ring=w.n_ring) for _, w, _ in items],
+                         [self.window[r].numel() for r, _, _ in items], [c.size for _, _, c in items], self.FC, F,
+                         lambda k: ops.mel_window_first_sample(self.mel, k),
+                         lambda n: min(ops.mel_frames_ready(self.mel, n), audio.n_anim_frames(n, self.fs, self.fps) - 1))
+        # ---- growth, the one exception to "nothing is allocated"
+        if plan["FC"] > self.FC:
+            self._grow_feats(plan["FC"])
+            n_ops += 3
+        for (r, _, _), p in zip(items, plan["rows"]):
+            if p["swap"] and self._alt[r].numel() < p["cap"]:
+                self._alt[r] = torch.zeros(p["cap"], device=self.dev)
+                n_ops += 1
+        if plan["n_stage"] > self._stage.n_samples:
+            self._stage.idle()
+            self._stage = _Staging(self.rows, 2 * plan["n_stage"], self.dev)
+        # ---- the staging block: records with device addresses, then the samples
+        stg = self._stage
+        blk = stg.take()
+        pos = 0
+        for _, _, c in items:
+            blk["smp"][pos:pos + c.size] = c
+            pos += c.size
+        block_bytes = 4 * self.FC * F
+        where = {"win": lambda i: self.window[items[i][0]].data_ptr(), "alt": lambda i: self._alt[items[i][0]].data_ptr(),
+                 "stage": lambda i: stg.dev.data_ptr() + stg.o_smp, "feats": lambda i: self.feats.data_ptr() + items[i][0] * block_bytes,
+                 "scratch": lambda i: self._scratch.data_ptr() + items[i][0] * block_bytes}
+        for name in ("segs", "back"):
+            for j, ((sk, si), so, (dk, di), do, cnt) in enumerate(plan["segs" if name == "segs" else "segs_back"]):
+                g = blk[name][j]
+                g.src, g.dst, g.count = where[sk](si) + 4 * so, where[dk](di) + 4 * do, cnt
+        n_mel = 0
+        for (r, _, _), p in zip(items, plan["rows"]):
+            if p["k1"] > p["k0"]:
+                q = blk["mel"][n_mel]
+                q.wav = (self._alt[r] if p["swap"] else self.window[r]).data_ptr()
+                q.out = self.feats.data_ptr() + r * block_bytes + 4 * (p["k0"] - p["fbase"]) * F
+                q.base, q.n_samples, q.k0, q.k1, q.final = p["base"], p["n"], p["k0"], p["k1"], 0
+                n_mel += 1
+        # ---- at most five operations
+        with torch.no_grad():
+            stg.upload(plan["n_stage"])
+            ops.copy_segments(blk["segs"], len(plan["segs"]), stg.dev.data_ptr())
+            n_ops += 2
+            if plan["segs_back"]:
+                ops.copy_segments(blk["back"], len(plan["segs_back"]), stg.dev.data_ptr() + stg.o_back)
+                n_ops += 1
+            if n_mel:
+                n_ops += ops.mel_features_batch(self._mb, blk["mel"], n_mel, stg.dev.data_ptr() + stg.o_mel)
+        for (r, row, c), p in zip(items, plan["rows"]):
+            if p["swap"]:
+                self.window[r], self._alt[r] = self._alt[r], self.window[r]
+                self.stats["window_capacity"][r] = int(self.window[r].numel())
+            row.n, row.base, row.n_feat, row.fbase = p["n"], p["base"], p["n_feat"], p["fbase"]
+            self.stats["uploaded_samples"] += int(c.size)
+        self.stats["ops_last_push_many"] = n_ops
 
     # ------------------------------------------------------------------ style
     def set_style(self, sid, style, fade=0):

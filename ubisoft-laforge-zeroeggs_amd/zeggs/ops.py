@@ -12,8 +12,8 @@ import torch
 
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
-                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, SpeechDims, SpeechPtrs, StyleDims, StyleGruDims,
-                   StyleGruPtrs, StylePtrs, api)
+                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, MelRow, Seg, SpeechDims, SpeechPtrs, StyleDims,
+                   StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
 
@@ -918,6 +918,43 @@ def mel_features_range(d, wav, final, filterbank, k0, k1, out, ws):
         raise ValueError("mel_features_range: out does not match the range")
     api().zeggs_mel_features_range(d, wav, wav.numel(), int(bool(final)), filterbank, int(k0), int(k1), out, ws, ws.numel(), _stream())
     return out
+
+
+class MelBatch:
+    """The batched front-end's tables (zeggs_mel_batch_prepare: twiddles, window, packed filterbank -- once per dims and
+    filterbank) and a workspace for calls of at most `rows` rows of at most `max_frames` feature rows each."""
+
+    def __init__(self, d, filterbank, rows, max_frames, device):
+        L = api()
+        self.d, self.fb, self.rows = d, filterbank, int(rows)
+        self.tables = _ws(L.zeggs_mel_batch_tables_bytes(d), device)
+        L.zeggs_mel_batch_prepare(d, filterbank, self.tables, self.tables.numel(), _stream())
+        self.resize(max_frames)
+
+    def resize(self, max_frames):
+        self.max_frames = int(max_frames)
+        self.ws = _ws(api().zeggs_mel_batch_workspace_bytes(self.d, self.rows, self.max_frames), self.tables.device)
+
+
+def _records(cls, address):
+    """a device address as the pointer-to-record parameter of the second header's entry points (None: no device copy)"""
+    return C.cast(C.c_void_p(int(address)), C.POINTER(cls)) if address else None
+
+
+def mel_features_batch(mb, rows, n, rows_dev=None):
+    """zeggs_mel_features_batch: rows[:n] a HOST array of MelRow (device addresses inside), `rows_dev` the device address of a copy
+    of the same records (None: the library uploads them) -> what the call enqueued (2 launches on the FFT form whatever n is)"""
+    if not 1 <= n <= mb.rows or max(r.k1 - r.k0 for r in rows[:n]) > mb.max_frames:
+        raise ValueError("mel_features_batch: more rows or frames than the MelBatch was sized for")
+    L = api()
+    L.zeggs_mel_features_batch(mb.d, rows, _records(MelRow, rows_dev), int(n), mb.fb, mb.tables, mb.ws, mb.ws.numel(), _stream())
+    return L.zeggs_mel_batch_last_ops()
+
+
+def copy_segments(segs, n, segs_dev):
+    """zeggs_copy_segments: segs[:n] a HOST array of Seg (device addresses, counts in floats), segs_dev the device address of a
+    copy of the same records: ONE launch for all of them"""
+    api().zeggs_copy_segments(segs, _records(Seg, segs_dev), int(n), _stream())
 
 
 class LiveSpeech:
