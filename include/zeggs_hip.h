@@ -597,6 +597,12 @@ int zeggs_mel_features_range(const ZeggsMelDims*, const float* wav, long n_sampl
 long zeggs_mel_window_first_sample(const ZeggsMelDims*, long k0);
 int zeggs_mel_features_window(const ZeggsMelDims*, const float* wav_window, long base, long n_samples, int final,
                               const double* filterbank, long k0, long k1, float* out, void* ws, size_t ws_bytes, void* stream);
+/* (zeggs_version() >= 108) Which form of the STFT the calling thread's last mel call enqueued (zeggs_mel_features_batch too): 0 none
+ * yet, 1 FFT, 2 matrix-core DFT, 3 direct DFT, 4 batched FFT.  The form follows from the dims and the options "mel_fft" / "mel_mfma":
+ * FFT where n_fft / 2 factors into 4s, 5s and 2s, n_mels <= n_fft and its LDS fits; else the matrix-core DFT where n_fft % 4 == 0,
+ * n_fft <= 894, no pre-emphasis and its LDS fits; else the direct DFT, which needs 8 (3 n_fft + n_fft / 2 + 1 + n_mels) bytes of LDS
+ * per STFT frame and is refused ahead of the launch above 160 KB (n_fft > 5828 at 80 mel channels).  A refused call leaves it as it was. */
+int zeggs_mel_last_form(void);
 
 /* Loudness normalisation pre-pass of preprocess_audio, ZEGGS/data_pipeline.py:34-39 (pyloudnorm 0.1.0: Meter(rate)
  * .integrated_loudness + normalize.loudness to `target` LUFS; algorithm restated in oracle/loudness.py), mono, on the device:

@@ -291,6 +291,66 @@ def gold_mel(ref):
     print("mel_resample.npz", {k: int(np.isnan(v).sum()) for k, v in out4.items() if "feat" in k})
 
 
+# STFT shapes other than the shipped 800 / 200 / 80 at 60 fps: tag -> (n_fft, hop, n_mels, fps, samples), 16 kHz.  What each is
+# for, and which kernel form it reaches, is tabled in tests/test_mel_shapes_oracle_cpu.py (which checks this table against its own).
+MEL_SHAPE_CASES = {
+    "r2": (1024, 256, 80, 60, 6000), "r2b": (400, 160, 80, 50, 5000), "big": (2048, 512, 80, 30, 9000), "f3": (600, 150, 80, 60, 5000),
+    "f3d": (900, 225, 80, 60, 5000), "wide": (892, 223, 80, 60, 5000), "widem": (892, 150, 80, 60, 5000), "r5": (250, 100, 40, 60, 3000),
+    "empty": (160, 80, 80, 100, 3000), "r4": (128, 64, 64, 60, 3000), "odd": (254, 64, 32, 60, 3000), "lds": (2400, 600, 80, 60, 9000),
+    "short": (512, 128, 40, 60, 300), "hop": (1024, 300, 80, 60, 6000), "gap": (400, 500, 80, 30, 9000), "tiny": (10, 5, 4, 60, 400),
+    "many": (64, 16, 80, 60, 2000), "slow": (640, 320, 80, 60, 5000),
+}
+# option cases on those signals: (tag, name, audio_conf overrides)
+MEL_SHAPE_OPTIONS = (("r2", "pre", {"pre_emphasis": True}), ("f3", "uncraw", {"centered": False, "normalize_range": False}),
+                     ("r2b", "cubic", {"resample_method": "cubic"}), ("r2", "nearest", {"resample_method": "nearest"}))
+
+
+def gold_mel_shapes(ref):
+    """tests/golden/mel_shapes.npz: the reference's preprocess_audio with audio_conf.filter_length / hop_length / n_mel_channels and the
+    frame rate overridden per case.  Per case the feature table (float32, NaNs as they come) and the STFT frame count; the signals are
+    NOT stored -- a test regenerates them with zeggs.synth.synth_wav(n, seed = n_fft + hop) and checks them against `sig` (float64 sum,
+    first three, last three samples) first."""
+    import logging
+    conf = json.load(open(ref_shims.root() / "data" / "processed_v1" / "data_pipeline_conf.json"))
+    base = dict(conf["audio_conf"], normalize_loudness=False, sampling_rate=16000, mel_fmin=20, mel_fmax=7600, pre_emphasis=False,
+                centered=True, normalize_range=True, real_amplitude=True, normalize_mel_bins=True, resample_method="linear")
+    dp = ref.data_pipeline
+    out = {"tags": np.array(list(MEL_SHAPE_CASES)), "options": np.array([f"{t}:{o}" for t, o, _ in MEL_SHAPE_OPTIONS])}
+
+    def run(tag, name, over):
+        n_fft, hop, n_mels, fps, n = MEL_SHAPE_CASES[tag]
+        wav = synth.synth_wav(n, seed=n_fft + hop).astype(np.float32) / 32768.0
+        nfr = int(round(float(fps) * (n / 16000)))
+        ac = dict(base, filter_length=n_fft, hop_length=hop, n_mel_channels=n_mels, **over)
+        cfg = ref.DictConfig(ac)
+        feat = dp.preprocess_audio(wav, fps, nfr, cfg, feature_type=conf["audio_feature_type"])
+        mel, _ = dp.extract_mel_spectrogram_for_tts(
+            wav_signal=wav, fs=16000, n_fft=n_fft, step_size=hop, n_mels=n_mels, mel_fmin=ac["mel_fmin"], mel_fmax=ac["mel_fmax"],
+            min_amplitude=ac["min_clipping"], pre_emphasis=ac["pre_emphasis"], pre_emph_coeff=ac["pre_emph_coeff"], dynamic_range=None,
+            real_amplitude=True, centered=ac["centered"], normalize_mel_bins=True, normalize_range=ac["normalize_range"], logger=logging.getLogger(__name__))
+        assert feat.dtype == np.float32 and feat.shape == (nfr, n_mels + 1) and mel.shape[0] == n_mels
+        sfx = f"_{name}" if name else ""
+        out[f"{tag}_feat{sfx}"], out[f"{tag}_M{sfx}"] = feat, np.int64(mel.shape[1])
+        if not name:
+            w64 = wav.astype(np.float64)
+            out[f"{tag}_dims"] = np.array([n_fft, hop, n_mels, fps, n], np.int64)
+            out[f"{tag}_seed"], out[f"{tag}_nframes"] = np.int64(n_fft + hop), np.int64(nfr)
+            out[f"{tag}_sig"] = np.concatenate([[w64.sum()], w64[:3], w64[-3:]])
+
+    logging.disable(logging.WARNING)      # "Empty filters detected in mel frequency basis" (spectrograms.py:438-441): what some cases are for
+    try:
+        for tag in MEL_SHAPE_CASES:
+            run(tag, "", {})
+        for tag, name, over in MEL_SHAPE_OPTIONS:
+            run(tag, name, over)
+    finally:
+        logging.disable(logging.NOTSET)
+    out["pre_emph_coeff"] = np.float64(base["pre_emph_coeff"])
+    np.savez_compressed(GOLD / "mel_shapes.npz", **out)
+    print("mel_shapes.npz", (GOLD / "mel_shapes.npz").stat().st_size, "bytes;",
+          {t: (int(out[f"{t}_M"]), int(np.isnan(out[f"{t}_feat"]).any(axis=1).sum())) for t in MEL_SHAPE_CASES})
+
+
 def gold_anim_orders(ref):
     """BVH channel orders other than the rigs' "zyx": preprocess_animation of the reference on clips whose rotation channels are
     declared (and meant) in other orders -- quat.from_euler takes any (anim/quat.py:154-163) -- and the euler channels utils.write_bvh /
@@ -1059,6 +1119,8 @@ def main():
         gold_nets(ref)
     if "mel" in which:
         gold_mel(ref)
+    if "mel_shapes" in which:      # (by name only: not part of the default list)
+        gold_mel_shapes(ref)
     if "dataset" in which:
         gold_dataset(ref)
     if "radam" in which:

@@ -286,7 +286,7 @@ def test_prototype_table_is_the_header():
     parameter's kind and every device pointer's element type.  A host pointer or a stream of the table is a pointer in the header."""
     from zeggs import capi
     header = _header_prototypes()
-    assert len(header) == 121 and set(header) == set(capi.PROTOTYPES)
+    assert len(header) == 122 and set(header) == set(capi.PROTOTYPES)
     assert {b for _, _, ps in header.values() for b, depth in ps if depth == 0} == set(_SCALARS)       # no struct by value
     for name, (rbase, rdepth, params) in header.items():
         ret, kinds = capi.signature(name)

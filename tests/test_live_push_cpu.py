@@ -225,7 +225,7 @@ def test_extension_prototypes_are_the_second_header():
     exports them all, the header includes the main one and names the version, and PROTOTYPES is still the main header's set"""
     header = _header_prototypes()
     assert set(header) == set(capi.EXT_PROTOTYPES) and len(header) == 6
-    assert not set(capi.EXT_PROTOTYPES) & set(capi.PROTOTYPES) and len(capi.PROTOTYPES) == 121 and len(capi.STRUCTS) == 21
+    assert not set(capi.EXT_PROTOTYPES) & set(capi.PROTOTYPES) and len(capi.PROTOTYPES) == 122 and len(capi.STRUCTS) == 21
     assert {b for _, _, ps in header.values() for b, depth in ps if depth == 0} <= set(_SCALARS)       # no struct by value
     structs = {**capi.STRUCTS, **capi.EXT_STRUCTS}
     for name, (rbase, rdepth, params) in header.items():

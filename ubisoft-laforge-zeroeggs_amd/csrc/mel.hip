@@ -649,6 +649,8 @@ static FftPlan fft_plan(int M) {
 }
 
 thread_local int t_mel_launches = 0;      // kernels enqueued by this thread's range / window / batch calls (zeggs_mel_batch_last_ops)
+thread_local int t_mel_form = 0;          // the STFT form this thread enqueued last (zeggs_mel_last_form): set where t_mel_launches is bumped
+constexpr size_t MEL_LDS_MAX = 160 * 1024;      // dynamic LDS a workgroup may be given (with the per-kernel opt-in above 64 KB)
 
 // whether the FFT form takes these dimensions (and the option allows it); *plan: its radices
 static bool mel_fft_form(const ZeggsMelDims& d, FftPlan* plan) {
@@ -679,6 +681,7 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
                        (const c2*)w.ftw, w.bands, w.fbp, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_fft");
     t_mel_launches += 2;
+    t_mel_form = 1;
     return 0;
   }
   const size_t fast_lds = mel_fast_lds(d.n_fft, d.hop, d.n_mels);
@@ -694,12 +697,26 @@ static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, 
                        fb, w.table, w.win, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_mfma");
     t_mel_launches += 2;
+    t_mel_form = 2;
     return 0;
   }
+  // the direct form takes what the other two decline; its frame, cos / sin table, amplitudes and mel values live in LDS, which ends it
+  // (n_fft <= 5828 at 80 mel channels) -- refused here, ahead of the launch
   const size_t lds = sizeof(double) * (3 * (size_t)d.n_fft + d.n_fft / 2 + 1 + d.n_mels);
+  ZCHECK(lds <= MEL_LDS_MAX, "mel: n_fft = %d with %d mel channels needs %zu bytes of LDS per STFT frame, a workgroup has %zu", d.n_fft,
+         d.n_mels, lds, MEL_LDS_MAX);
+  static bool direct_attr_set = false;
+  if (!direct_attr_set) {       // (n_fft >= 2318 at 80 mel channels is past the 64 KB a kernel gets without the opt-in)
+    if (hipFuncSetAttribute((const void*)mel_stft_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MEL_LDS_MAX) != hipSuccess) {
+      zeggs_set_error("mel: cannot raise the LDS limit of the direct kernel");
+      return -1;
+    }
+    direct_attr_set = true;
+  }
   hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.logmel, w.energy, m0, g_mel_exact_log, base);
   ZLAUNCH_CHECK("mel_stft");
   t_mel_launches += 1;
+  t_mel_form = 3;
   return 0;
 }
 
@@ -925,6 +942,7 @@ extern "C" size_t zeggs_mel_batch_workspace_bytes(const ZeggsMelDims* d, int row
 }
 
 extern "C" int zeggs_mel_batch_last_ops() { return t_mel_launches; }
+extern "C" int zeggs_mel_last_form(void) { return t_mel_form; }
 
 extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRow* rows, const ZeggsMelRow* rows_dev, int R,
                                         const double* filterbank, const void* tables, void* ws, size_t ws_bytes, void* stream) {
@@ -999,5 +1017,6 @@ extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRo
                      (const double*)w.logmel, (const double*)w.energy);
   ZLAUNCH_CHECK("mel_resample_batch");
   t_mel_launches += 2;
+  t_mel_form = 4;
   return 0;
 }

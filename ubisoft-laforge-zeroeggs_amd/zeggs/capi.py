@@ -178,6 +178,7 @@ PROTOTYPES = {
     "zeggs_mel_features_range": "status: ZeggsMelDims* f32* long int f64* long long f32* any* size_t stream",
     "zeggs_mel_window_first_sample": "long: ZeggsMelDims* long",
     "zeggs_mel_features_window": "status: ZeggsMelDims* f32* long long int f64* long long f32* any* size_t stream",
+    "zeggs_mel_last_form": "int:",
     "zeggs_loudness_workspace_bytes": "size_t: long int long",
     # coef[10] / trans[8]: prepared and read on the host
     "zeggs_loudness_gain": "status: f32* long int double host* host* long i64* i64* int int f64* f32* any* size_t stream",

@@ -887,6 +887,15 @@ def mel_frames_ready(d, n_samples):
     return api().zeggs_mel_frames_ready(d, int(n_samples))
 
 
+MEL_FORMS = {0: None, 1: "fft", 2: "mfma", 3: "direct", 4: "fft_batch"}
+
+
+def mel_last_form():
+    """zeggs_mel_last_form: the STFT form this thread's last mel call enqueued -- 0 none yet, 1 FFT, 2 matrix-core DFT, 3 direct DFT,
+    4 batched FFT (MEL_FORMS names them)"""
+    return api().zeggs_mel_last_form()
+
+
 def mel_window_first_sample(d, k0):
     """zeggs_mel_window_first_sample (host only): the smallest absolute sample index any frame >= k0 loads (d: audio.MelDims)"""
     return api().zeggs_mel_window_first_sample(d, int(k0))
