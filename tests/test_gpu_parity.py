@@ -867,7 +867,7 @@ def test_mel_resample_methods_vs_reference(golden_dir):
         audio.preprocess_audio(gd["a_wav"], 60, 60, dict(base, resample_method="quadratic", centered=True), ["mel_spec", "energy"])
     with pytest.raises(RuntimeError, match="at least 4 STFT frames"):      # (scipy's interp1d raises for fewer points than the order needs, too)
         audio.mel_features(gd["a_wav"][:1300], 4, centered=False, resample_method="cubic")
-    # a long table (the elimination runs in batches of eight rows: every remainder of the row count), against the oracle's recurrence
+    # long tables (the elimination runs in chunks of 64 rows, csrc/spline.hip: nine row counts across a chunk), against the oracle's recurrence
     from oracle import mel as omel
     for n in (16000 * 7 + 200 * r + 13 for r in range(9)):
         wav = synth.synth_wav(n, seed=n).astype(np.float32) / 32768.0
@@ -911,6 +911,25 @@ def test_mel_resample_methods_vs_reference(golden_dir):
     np.testing.assert_allclose(st, audio.mel_features(wav, nfr, resample_method="nearest").cpu().numpy(), atol=1e-6, rtol=1e-6)
     rc, msg = ranges("cubic")
     assert rc != 0 and "WHOLE signal" in msg
+
+
+@pytest.mark.parametrize("frames", ["4", "5", "6", "C+1", "C+2", "C+3", "2C+H+5"])
+def test_mel_cubic_at_short_signals_vs_reference(frames):
+    """resample_method = "cubic" where the spline solver (csrc/spline.hip, on the [STFT frames, 81] feature table) changes path: 4 STFT
+    frames (the ends alone), 5 and 6 (the first interior rows), and one, two, three rows into the second chunk of C rows, and a table
+    of more than two chunks plus their look-ahead of H rows -- against the oracle's preprocess_audio at the shipped dims."""
+    from oracle import mel as omel
+    from zeggs import audio, data_pipeline as dp
+    c, h, _ = dp.spline_chunk()
+    m = {"4": 4, "5": 5, "6": 6, "C+1": c + 1, "C+2": c + 2, "C+3": c + 3, "2C+H+5": 2 * c + h + 5}[frames]
+    n = 200 * (m - 1) + 13      # (centred, n_fft 800, hop 200: a signal shorter than n_fft is extended to it and has 4 frames)
+    assert audio.stft_frame_count(n) == m and n <= 35000
+    wav = synth.synth_wav(n, seed=n).astype(np.float32) / 32768.0
+    nfr = audio.n_anim_frames(n)
+    feat = audio.mel_features(wav, nfr, resample_method="cubic").cpu().numpy()
+    ref = omel.preprocess_audio(wav, nfr, resample_method="cubic")
+    np.testing.assert_array_equal(np.isnan(feat), np.isnan(ref))
+    np.testing.assert_allclose(feat, ref, atol=3e-6, rtol=3e-6, equal_nan=True)
 
 
 @pytest.mark.parametrize("pre,real,centered,norm", [(0.0, True, True, True), (0.97, True, True, True), (0.0, False, False, True),

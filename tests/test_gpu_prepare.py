@@ -110,7 +110,7 @@ def chunking():
     return C_, H_, NW_
 
 
-@pytest.mark.parametrize("w", [1, 3, 300])
+@pytest.mark.parametrize("w", [1, 3, 81, 300])      # 81: the audio feature table (two column tiles, the second partly filled)
 @pytest.mark.parametrize("size", ["4", "5", "6", "C-1", "C", "C+1", "2C+H+3"])
 def test_spline_vs_dense_solve(size, w):
     c, h, _ = chunking()

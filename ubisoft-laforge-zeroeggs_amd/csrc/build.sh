@@ -7,7 +7,7 @@ OUT=${ZEGGS_OUT:-../zeggs/libzeggs_hip.so}
 BD=${ZEGGS_BUILD_DIR:-build}
 mkdir -p $BD
 pids=()
-SRC="gemm gemm_split kernels attention encoders options decoder decoder_fast sweep_sync decode_persistent train_persistent train_dual train_bwd_persistent loudness loss misc mel anim prepare style_gru hostio text funcs live"
+SRC="gemm gemm_split kernels attention encoders options decoder decoder_fast sweep_sync decode_persistent train_persistent train_dual train_bwd_persistent loudness loss misc mel anim spline prepare style_gru hostio text funcs live"
 for f in $SRC; do
   stale=0
   [ -f $BD/$f.o ] || stale=1

@@ -5,70 +5,58 @@
 // [0,1]); ZEGGS/data_pipeline.py:62-80 (10**(x/20) -> ln, linear resampling to the animation rate,
 // energy = ||exp(mel)||_2 resampled with extrapolation).
 //
-// Three forms of the STFT, same results (float32 features bit-identical, tools/mel_ab.py): the FFT form mel_stft_fft_k (round 4,
-// default: a half-length complex mixed-radix FFT + split, what the reference's np.fft.rfft computes), the DFT as a float64
-// matrix-core product mel_stft_mfma_k (round 3, option mel_fft = 0) and the direct DFT below (other n_fft).
-// The reference's spectrogram is float64, so this kernel computes in float64 as well (MI355X runs f64
-// FMAs at full vector rate): one workgroup per STFT frame, the windowed frame and an n_fft-entry
-// cos/sin table are staged in LDS, each thread evaluates a direct DFT for its bins (index k*n mod n_fft
-// walks the table, no trigonometry in the loop), then the 80 x 401 filterbank (742 non-zeros, given
-// as a dense matrix resident in L2) and the log/normalise chain run on the same workgroup.
+// The reference's spectrogram is float64, so everything here computes in float64 as well (MI355X runs f64 FMAs at full vector
+// rate).  Three forms of the STFT, same results (float32 features bit-identical, tools/mel_ab.py), chosen from the dims by
+// launch_stft: the FFT form mel_stft_fft_k (default: a half-length complex mixed-radix FFT + split, what the reference's
+// np.fft.rfft computes), the DFT as a float64 matrix-core product mel_stft_mfma_k (option mel_fft = 0) and the direct DFT
+// mel_stft_k (other n_fft).  They differ in how a frame's amplitudes come about; the sample index rule and the window
+// (mel_math.h), the per-frame tail (mel_frame_tail), the filterbank's band table (mel_pack_bands) and the float64 feature table
+// [STFT frames, n_mels + 1] that the resampling reads (the splines of resample_method = "cubic": spline.h) are stated once.
+#include <atomic>
 #include <math.h>
 
 #include "../../include/zeggs_hip_live.h"
 #include "common.h"
+#include "mel_math.h"
+#include "spline.h"
 
 namespace {
 
-// ---- matrix-core DFT (mel_stft_mfma_k): 32 STFT frames per workgroup, the DFT as a [frames, n_fft] x [n_fft, 2 bins] fp64
-// product on v_mfma_f64_16x16x4_f64 against a cos / -sin table built once per call
+// the matrix-core form (mel_stft_mfma_k): 32 STFT frames per workgroup
 constexpr int MF = 32, MWAVES = 8, MTPW = 7, MCOLP = MWAVES * MTPW * 16;      // frames, waves, column tiles per wave, 896 columns
 constexpr int MFB_CAP = 2048;                                                  // filterbank non-zeros staged in LDS
+typedef double c2 __attribute__((ext_vector_type(2)));     // (re, im)
 
+// what a call builds once from the dims and the filterbank for the FFT and matrix-core forms (the batched form: zeggs_mel_batch_prepare)
+struct MelTables {
+  c2* ftw;          // FFT form: [n_fft / 2 + n_fft / 2 + 1 + n_fft] complex (twiddles of the half-length transform, of the split, window)
+  double* fbp;      // the filterbank's non-zeros, band after band [MFB_CAP]
+  int* bands;       // [3 n_mels] first bin | one past the last bin | offset in fbp
+};
+MelTables carve_mel_tables(const ZeggsMelDims& d, Arena& a) {
+  MelTables t;
+  t.ftw = (c2*)a.raw(sizeof(double) * 2 * ((size_t)2 * d.n_fft + 1));
+  t.fbp = (double*)a.raw(sizeof(double) * MFB_CAP);
+  t.bands = (int*)a.raw(sizeof(int) * 3 * (size_t)d.n_mels);
+  return t;
+}
 struct MelWs {
-  double* logmel;   // [M, n_mels]
-  double* energy;   // [M]
+  double* feat;     // [M, n_mels + 1] log-mel | energy of every STFT frame
   double* table;    // [n_fft, MCOLP]: column 2k = cos(2 pi j k / n_fft), 2k+1 = -sin(.), zero beyond bin n_fft/2
   double* win;      // [n_fft] symmetric Hann
-  double* ftw;      // FFT form: [n_fft / 2 + n_fft / 2 + 1 + n_fft] complex (twiddles of the half-length transform, of the split, window)
-  double* fbp;      // FFT form: the filterbank's non-zeros, band after band [MFB_CAP]
-  int* bands;       // FFT form: [3 n_mels] first bin | one past the last bin | offset in fbp
+  MelTables t;
   double* spl;      // resample_method = "cubic": second derivatives of the interpolating splines [M, n_mels + 1]
-  double* cp;       //   ... and the right-hand sides of their tridiagonal systems [M, n_mels + 1]
 };
 MelWs carve_mel(const ZeggsMelDims& d, long M, Arena& a) {
   MelWs w;
-  w.logmel = (double*)a.raw(sizeof(double) * M * d.n_mels);
-  w.energy = (double*)a.raw(sizeof(double) * M);
+  w.feat = (double*)a.raw(sizeof(double) * M * (d.n_mels + 1));
   w.table = (double*)a.raw(sizeof(double) * (size_t)d.n_fft * MCOLP);
   w.win = (double*)a.raw(sizeof(double) * (size_t)d.n_fft);
-  w.ftw = (double*)a.raw(sizeof(double) * 2 * ((size_t)2 * d.n_fft + 1));
-  w.fbp = (double*)a.raw(sizeof(double) * MFB_CAP);
-  w.bands = (int*)a.raw(sizeof(int) * 3 * (size_t)d.n_mels);
-  w.spl = w.cp = nullptr;
-  if (d.flags & 8) {      // MEL_CUBIC
-    w.spl = (double*)a.raw(sizeof(double) * M * (d.n_mels + 1));
-    w.cp = (double*)a.raw(sizeof(double) * M * (d.n_mels + 1));
-  }
+  w.t = carve_mel_tables(d, a);
+  w.spl = (d.flags & MEL_CUBIC) ? (double*)a.raw(sizeof(double) * M * (d.n_mels + 1)) : nullptr;
   return w;
 }
 
-// spectrograms.py:233-246 (integer rule)
-// ZeggsMelDims.flags: bit 0 = audio_conf.centered is FALSE (no reflect padding: frame m starts at sample m hop, spectrograms.py:237-239),
-// bit 1 = audio_conf.normalize_range is FALSE (the stored value is 20 log10 s, not mapped to [0, 1], spectrograms.py:123-129)
-// bits 2-3 = audio_conf.resample_method (data_pipeline.py:65-79: scipy.interpolate.griddata for the mel table, interp1d for the energy):
-// 0 "linear" (the shipped configurations), 4 "nearest", 8 "cubic"
-#define MEL_UNCENTERED 1
-#define MEL_RAW_RANGE 2
-#define MEL_NEAREST 4
-#define MEL_CUBIC 8
-inline long stft_frames(long n, int n_fft, int hop, int flags = 0) {
-  long np = (n > n_fft ? n : n_fft) + ((flags & MEL_UNCENTERED) ? 0 : 2 * (long)(n_fft / 2));
-  return (np % hop == 0) ? (np - n_fft) / hop : 1 + (np - n_fft) / hop;
-}
-
-// STFT frames m0 .. m0 + gridDim.x - 1.  n = signal length for the reflect rule, n_avail = samples present in `wav`
-// (streaming: n is unknown yet and passed as a huge value; the caller only asks for frames that end before n_avail)
 // The clipped mel amplitude s -> what the reference stores: v = (20 log10 s + range) / range (spectrograms.py:121-129), then
 // data_pipeline.py:62-63 takes y = ln(10^(v / 20)), and the frame's energy is || exp(y) ||_2 (data_pipeline.py:28-30,75).  Four
 // float64 transcendentals per mel value (log10, pow, log, exp) bounded the front-end in round 4 (not memory).  Round 5:
@@ -91,34 +79,105 @@ __device__ __forceinline__ double mel_exp_sq(double y, int exact) {      // exp(
   return z * z;
 }
 
-// sample `src` of the signal the STFT sees: the wav, zero beyond its end, high-pass filtered first when audio_conf.pre_emphasis is on
-// (spectrograms.py:35 -> signal_manipulation.preemphasis = lfilter([1, -c], [1], x): y[n] = x[n] - c x[n-1], y[0] = x[0], in float64)
-// `wav[i]` is sample base + i of the signal (base = 0: the whole signal; > 0: a sliding window, zeggs_mel_features_window, whose
-// host side has checked that no frame of the call reads below `base`)
+// Sample `src` (mel_math.h: mel_src) of the signal the STFT sees: the wav, zero where it is not loaded, high-pass filtered first when
+// audio_conf.pre_emphasis is on (spectrograms.py:35 -> signal_manipulation.preemphasis = lfilter([1, -c], [1], x): y[n] = x[n] - c x[n-1],
+// y[0] = x[0], in float64).  n = signal length for the reflect rule, n_avail = samples present in `wav` (streaming: n is unknown yet and
+// passed as a huge value; the caller only asks for frames that end before n_avail); `wav[i]` is sample base + i of the signal (base = 0:
+// the whole signal; > 0: a sliding window, zeggs_mel_features_window, whose host side has checked that no frame of the call reads below `base`)
 __device__ __forceinline__ double mel_sample(const float* wav, long src, long n, long n_avail, double pe, long base) {
-  if (!(src >= base && src < n && src < n_avail)) return 0.0;
+  if (!mel_loaded(src, n, n_avail, base)) return 0.0;
   double x = (double)wav[src - base];
   if (pe != 0.0 && src > base) x -= pe * (double)wav[src - 1 - base];
   return x;
 }
 
-__global__ __launch_bounds__(256) void mel_stft_k(ZeggsMelDims d, const float* wav, long n, long n_avail, const double* fb,
-                                                   double* logmel, double* energy, long m0, int exact, long base) {
+// The filterbank's bands, found and packed ONCE per call by one workgroup: bands[m] = first non-zero bin of filter m, bands[NM + m] = one
+// past its last, bands[2 NM + m] = offset of the band in fbp (-1: does not fit MFB_CAP, read from the dense matrix) -- every STFT workgroup
+// copies these few KB into LDS instead of scanning the dense [n_mels, n_bins] matrix itself (that scan was 2/3 of the FFT form's first
+// version's time).  All threads walk the dense matrix together (min / max through global atomics on the band table itself: a serial scan
+// per filter was 0.13 ms of a 1.7 ms front-end).
+__device__ void mel_pack_bands(const double* fb, int NM, int NBIN, int* bands, double* fbp) {
+  for (int m = threadIdx.x; m < NM; m += blockDim.x) { bands[m] = NBIN; bands[NM + m] = 0; }
+  __syncthreads();
+  for (int i = threadIdx.x; i < NM * NBIN; i += blockDim.x) {
+    const int m = i / NBIN, k = i - m * NBIN;
+    if (fb[i] != 0.0) { atomicMin(bands + m, k); atomicMax(bands + NM + m, k + 1); }
+  }
+  __syncthreads();
+  for (int m = threadIdx.x; m < NM; m += blockDim.x)
+    if (bands[NM + m] == 0) bands[m] = 0;            // an all-zero filter: empty band [0, 0)
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int o = 0;
+    for (int m = 0; m < NM; ++m) {
+      const int w = bands[NM + m] - bands[m];
+      if (o + w <= MFB_CAP) { bands[2 * NM + m] = o; o += w; } else bands[2 * NM + m] = -1;
+    }
+  }
+  __syncthreads();
+  for (int m = threadIdx.x; m < NM; m += blockDim.x)
+    if (bands[2 * NM + m] >= 0)
+      for (int k = bands[m]; k < bands[NM + m]; ++k) fbp[bands[2 * NM + m] + k - bands[m]] = fb[(long)m * NBIN + k];
+}
+// ... and a workgroup's copy of them: fbs [MFB_CAP], blo [3 NM] in LDS (first bin | one past the last | offset, contiguous)
+__device__ __forceinline__ void mel_stage_bands(const int* bands, const double* fbp, int NM, double* fbs, int* blo) {
+  for (int i = threadIdx.x; i < 3 * NM; i += blockDim.x) blo[i] = bands[i];
+  for (int i = threadIdx.x; i < MFB_CAP; i += blockDim.x) fbs[i] = fbp[i];
+}
+
+// The per-frame tail of all three forms: amplitudes amp [F][n_bins] of F STFT frames in LDS (written, and a barrier passed) -> rows
+// slot0 .. slot0 + F - 1 of the feature table (those below nfr are stored): mel band sum, |.|, clip, log chain, and in column n_mels the
+// energy || exp(log-mel) ||_2 (data_pipeline.py:28-30,75).  Filter m adds its band in bin order, from the staged non-zeros fbs where it
+// has an offset, from the dense matrix fb otherwise; blo == nullptr (the direct form builds no band table): the whole dense row, which
+// gives the same bits -- fma(0, a, s) == s for finite a, and s starts at +0.  esq [F][n_mels]: LDS scratch apart from amp.  Every thread
+// takes the exponential of its own value; the frame's thread only adds, in mel order.
+__device__ __forceinline__ void mel_frame_tail(const ZeggsMelDims& d, int F, const double* amp, double* esq, const int* blo, const double* fbs,
+                                               const double* fb, double* feat, long slot0, long nfr, int exact) {
+  const int NF = d.n_fft, NBIN = NF / 2 + 1, NM = d.n_mels, W = NM + 1, tid = threadIdx.x;
+  const int* bhi = blo != nullptr ? blo + NM : nullptr;
+  const int* bof = blo != nullptr ? blo + 2 * NM : nullptr;
+  const double amin = (double)d.min_clip / (double)NF;  // spectrograms.py:88-90
+  const double rng = -20.0 * log10(amin);
+  for (int it = tid; it < F * NM; it += blockDim.x) {
+    const int f = it / NM, m = it % NM;
+    const double* av = amp + (size_t)f * NBIN;
+    double s = 0.0;
+    if (blo != nullptr && bof[m] >= 0) {
+      const double* fv = fbs + bof[m] - blo[m];
+      for (int k = blo[m]; k < bhi[m]; ++k) s = fma(fv[k], av[k], s);
+    } else {
+      const double* fv = fb + (long)m * NBIN;
+      const int lo = blo != nullptr ? blo[m] : 0, hi = blo != nullptr ? bhi[m] : NBIN;
+      for (int k = lo; k < hi; ++k) s = fma(fv[k], av[k], s);
+    }
+    s = fabs(s);
+    if (s < amin) s = amin;
+    const double y = mel_logamp(s, rng, exact, d.flags);
+    esq[it] = mel_exp_sq(y, exact);
+    if (slot0 + f < nfr) feat[(slot0 + f) * W + m] = y;
+  }
+  __syncthreads();
+  if (tid < F && slot0 + tid < nfr) {
+    double e = 0.0;
+    for (int m = 0; m < NM; ++m) e += esq[tid * NM + m];
+    feat[(slot0 + tid) * W + NM] = sqrt(e);
+  }
+}
+
+// ---- direct DFT (mel_stft_k): one workgroup per STFT frame m0 + blockIdx.x, the windowed frame and an n_fft-entry cos/sin table are
+// staged in LDS, each thread evaluates a direct DFT for its bins (index k*n mod n_fft walks the table, no trigonometry in the loop)
+__global__ __launch_bounds__(256) void mel_stft_k(ZeggsMelDims d, const float* wav, long n, long n_avail, const double* fb, double* feat,
+                                                   long m0, int exact, long base) {
   extern __shared__ __attribute__((aligned(16))) double sm[];
   const int NF = d.n_fft, NBIN = NF / 2 + 1;
   double* xw = sm;              // [NF] windowed samples
   double* ct = xw + NF;         // [NF] cos(2 pi j / NF)
   double* st = ct + NF;         // [NF] sin
   double* amp = st + NF;        // [NBIN]
-  double* melv = amp + NBIN;    // [n_mels]
+  double* esq = amp + NBIN;     // [n_mels]
   const long fr = m0 + blockIdx.x, slot = blockIdx.x;
-  const long neff = n > NF ? n : NF;   // zero-extended to n_fft when shorter (spectrograms.py:233-234)
   for (int j = threadIdx.x; j < NF; j += blockDim.x) {
-    const long p = fr * d.hop + j - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);          // index into the (zero-extended) signal before reflect padding
-    long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-    const double x = mel_sample(wav, src, n, n_avail, d.pre_emph, base);
-    const double win = 0.5 - 0.5 * cos(2.0 * M_PI * (double)j / (double)(NF - 1));   // scipy hann(sym=True)
-    xw[j] = x * win;
+    xw[j] = mel_sample(wav, mel_src(d, fr, j, n), n, n_avail, d.pre_emph, base) * mel_hann(j, NF);
     const double ang = 2.0 * M_PI * (double)j / (double)NF;
     ct[j] = cos(ang);
     st[j] = sin(ang);
@@ -137,31 +196,16 @@ __global__ __launch_bounds__(256) void mel_stft_k(ZeggsMelDims d, const float* w
     amp[k] = sqrt(re * re + im * im) / (double)NF;     // real_amplitude (spectrograms.py:266-267)
   }
   __syncthreads();
-  const double amin = (double)d.min_clip / (double)NF;  // spectrograms.py:88-90
-  const double rng = -20.0 * log10(amin);
-  for (int m = threadIdx.x; m < d.n_mels; m += blockDim.x) {
-    const double* f = fb + (long)m * NBIN;
-    double s = 0.0;
-    for (int k = 0; k < NBIN; ++k) s = fma(f[k], amp[k], s);
-    s = fabs(s);
-    if (s < amin) s = amin;
-    const double y = mel_logamp(s, rng, exact, d.flags);
-    melv[m] = y;
-    logmel[slot * d.n_mels + m] = y;
-  }
-  __syncthreads();
-  if (threadIdx.x == 0) {                               // energy = || exp(mel) ||_2 (data_pipeline.py:28-30,75)
-    double e = 0.0;
-    for (int m = 0; m < d.n_mels; ++m) e += mel_exp_sq(melv[m], exact);
-    energy[slot] = sqrt(e);
-  }
+  mel_frame_tail(d, 1, amp, esq, nullptr, nullptr, fb, feat, slot, slot + 1, exact);
 }
 
+// ---- matrix-core DFT (mel_stft_mfma_k): 32 STFT frames per workgroup, the DFT as a [frames, n_fft] x [n_fft, 2 bins] fp64
+// product on v_mfma_f64_16x16x4_f64 against a cos / -sin table built once per call
 typedef double d4 __attribute__((ext_vector_type(4)));
 
 // DFT basis + window, once per call (the angle is reduced exactly: (j k) mod n_fft -- the same table entries the direct
-// kernel above walks)
-__global__ void mel_table_k(double* T, double* win, int NF, int NBIN) {
+// kernel above walks); block 0 also packs the filterbank's bands
+__global__ void mel_table_k(double* T, double* win, int NF, int NBIN, const double* fb, int NM, int* bands, double* fbp) {
   const long n = (long)NF * MCOLP;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
     const int j = (int)(i / MCOLP), c = (int)(i % MCOLP), k = c >> 1;
@@ -171,12 +215,13 @@ __global__ void mel_table_k(double* T, double* win, int NF, int NBIN) {
       v = (c & 1) ? -sin(ang) : cos(ang);
     }
     T[i] = v;
-    if (i < NF) win[i] = 0.5 - 0.5 * cos(2.0 * M_PI * (double)i / (double)(NF - 1));   // scipy hann(sym=True)
+    if (i < NF) win[i] = mel_hann((int)i, NF);
   }
+  if (blockIdx.x == 0) mel_pack_bands(fb, NM, NBIN, bands, fbp);
 }
 
 // LDS of mel_stft_mfma_k (bytes): raw samples of the 32 overlapping frames | window | amplitudes [32][NBIN] | staged filterbank
-// non-zeros | band tables.  The log-mel values of the workgroup's frames reuse the sample area after the products.
+// non-zeros | band tables.  The tail's scratch reuses the sample area after the products.
 __host__ __device__ inline size_t mel_fast_lds(int NF, int hop, int n_mels) {
   const size_t ns = (size_t)(MF - 1) * hop + NF;
   size_t xs = ns * sizeof(float), mv = (size_t)MF * n_mels * sizeof(double);
@@ -185,13 +230,13 @@ __host__ __device__ inline size_t mel_fast_lds(int NF, int hop, int n_mels) {
   return xs + sizeof(double) * ((size_t)NF + (size_t)MF * (NF / 2 + 1) + MFB_CAP) + sizeof(int) * 3 * (size_t)n_mels + 64;
 }
 
-// STFT frames m0 + 32 blockIdx.x ... (nfr frames in all): same results as mel_stft_k -- identical table entries, window, clip /
-// log chain and summation order of the mel and energy sums; only the 800-term DFT sums are accumulated by the matrix cores
-// (fp64, k in steps of 4) instead of one fma chain per bin.
+// STFT frames m0 + 32 blockIdx.x ... (nfr frames in all): same results as mel_stft_k -- identical table entries, window and tail;
+// only the n_fft-term DFT sums are accumulated by the matrix cores (fp64, k in steps of 4) instead of one fma chain per bin.
+// It stages raw float32 samples (launch_stft sends pre-emphasis elsewhere).
 __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, const float* wav, long n, long n_avail,
                                                                 const double* fb, const double* table, const double* wintab,
-                                                                double* logmel, double* energy, long m0, long nfr, int exact,
-                                                                long base) {
+                                                                const int* bands, const double* fbp, double* feat, long m0, long nfr,
+                                                                int exact, long base) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   const int NF = d.n_fft, NBIN = NF / 2 + 1, hop = d.hop, NM = d.n_mels;
   const int ns = (MF - 1) * hop + NF;
@@ -199,37 +244,20 @@ __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, c
   if (mv_bytes > xs_bytes) xs_bytes = mv_bytes;
   xs_bytes = (xs_bytes + 15) / 16 * 16;
   float* xs = (float*)smem;                         // [ns] samples (reflect rule applied)
-  double* melv = (double*)smem;                     // [MF][NM] after the products
+  double* esq = (double*)smem;                      // [MF][NM] after the products
   double* win = (double*)(smem + xs_bytes);         // [NF]
   double* amp = win + NF;                           // [MF][NBIN]
-  double* fbs = amp + (size_t)MF * NBIN;            // [MFB_CAP] non-zero bands of the filterbank, mel after mel
-  int* blo = (int*)(fbs + MFB_CAP);                 // [NM] first bin of the band
-  int* bhi = blo + NM;                              // [NM] one past its last bin
-  int* bof = bhi + NM;                              // [NM] offset of the band in fbs (-1: not staged, read from fb)
+  double* fbs = amp + (size_t)MF * NBIN;            // [MFB_CAP]
+  int* blo = (int*)(fbs + MFB_CAP);                 // [3 NM]
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const long fr0 = m0 + (long)blockIdx.x * MF, slot0 = (long)blockIdx.x * MF;
-  const long neff = n > NF ? n : NF;
-  for (int i = tid; i < ns; i += blockDim.x) {
-    const long p = fr0 * hop + i - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);
-    const long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-    xs[i] = (src >= base && src < n && src < n_avail) ? wav[src - base] : 0.f;
+  for (int i = tid; i < ns; i += blockDim.x) {      // (tap i of frame fr0 = tap i - f hop of frame fr0 + f)
+    const long src = mel_src(d, fr0, i, n);
+    xs[i] = mel_loaded(src, n, n_avail, base) ? wav[src - base] : 0.f;
   }
   for (int j = tid; j < NF; j += blockDim.x) win[j] = wintab[j];
-  if (tid < NM) {                                   // band of mel filter tid
-    const double* f = fb + (long)tid * NBIN;
-    int lo = 0, hi = 0;
-    for (int k = 0; k < NBIN; ++k)
-      if (f[k] != 0.0) { if (hi == 0) lo = k; hi = k + 1; }
-    blo[tid] = lo; bhi[tid] = hi;
-  }
+  mel_stage_bands(bands, fbp, NM, fbs, blo);
   __syncthreads();
-  if (tid == 0) {
-    int o = 0;
-    for (int m = 0; m < NM; ++m) {
-      const int w = bhi[m] - blo[m];
-      if (o + w <= MFB_CAP) { bof[m] = o; o += w; } else bof[m] = -1;
-    }
-  }
   // ---- DFT: P[frame][col] = sum_j xw[frame][j] T[j][col]; this wave: column tiles wave * MTPW .. + MTPW - 1, both row tiles
   d4 acc[2][MTPW];
 #pragma unroll
@@ -272,36 +300,7 @@ __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, c
         if (!(col & 1) && bin < NBIN) amp[(size_t)fr * NBIN + bin] = sqrt(v * v + o * o) / (double)NF;   // real_amplitude
       }
   __syncthreads();
-  for (int m = tid; m < NM; m += blockDim.x) {       // filterbank bands -> LDS (the 742 non-zeros of the shipped filterbank)
-    if (bof[m] >= 0)
-      for (int k = blo[m]; k < bhi[m]; ++k) fbs[bof[m] + k - blo[m]] = fb[(long)m * NBIN + k];
-  }
-  __syncthreads();
-  const double amin = (double)d.min_clip / (double)NF;
-  const double rng = -20.0 * log10(amin);
-  for (int it = tid; it < MF * NM; it += blockDim.x) {
-    const int f = it / NM, m = it % NM;
-    const double* av = amp + (size_t)f * NBIN;
-    double s = 0.0;
-    if (bof[m] >= 0) {
-      const double* fv = fbs + bof[m] - blo[m];
-      for (int k = blo[m]; k < bhi[m]; ++k) s = fma(fv[k], av[k], s);
-    } else {
-      const double* fv = fb + (long)m * NBIN;
-      for (int k = blo[m]; k < bhi[m]; ++k) s = fma(fv[k], av[k], s);
-    }
-    s = fabs(s);
-    if (s < amin) s = amin;
-    const double y = mel_logamp(s, rng, exact, d.flags);
-    melv[it] = y;                                   // (the sample area: the products are done)
-    if (slot0 + f < nfr) logmel[(slot0 + f) * NM + m] = y;
-  }
-  __syncthreads();
-  if (tid < MF && slot0 + tid < nfr) {
-    double e = 0.0;
-    for (int m = 0; m < NM; ++m) e += mel_exp_sq(melv[tid * NM + m], exact);
-    energy[slot0 + tid] = sqrt(e);
-  }
+  mel_frame_tail(d, MF, amp, esq, blo, fbs, fb, feat, slot0, nfr, exact);      // (esq is the sample area: the products are done)
 }
 
 
@@ -311,7 +310,7 @@ __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, c
 // n_fft = 800), then the usual split X[k] = (Z[k] + conj Z[M-k]) / 2 - i / 2 e^{-2 pi i k / N} (Z[k] - conj Z[M-k]).
 // 19 kFLOP per STFT frame instead of 1.28 MFLOP; the launch is bound by the log / exp chain of the 80 mel values and by LDS
 // traffic, not by the transform.  Twiddles come from two tables built once per call in float64 (exact angle reduction), so
-// the spectrum agrees with the matrix form to a few ulp; mel / clip / log chain and summation orders are the same code.
+// the spectrum agrees with the matrix form to a few ulp.
 constexpr int FFB = 4;            // STFT frames per workgroup
 #ifndef ZEGGS_MEL_FFT_THREADS
 #define ZEGGS_MEL_FFT_THREADS 320 // 5 waves: the radix-5 stages (4 x 80 butterflies) and the mel / log chain (4 x 80 values) are ONE pass each
@@ -319,67 +318,37 @@ constexpr int FFB = 4;            // STFT frames per workgroup
 constexpr int FTHR = ZEGGS_MEL_FFT_THREADS;
 constexpr int FMAXST = 8;         // stages
 struct FftPlan { int nst; int radix[FMAXST]; };
-typedef double c2 __attribute__((ext_vector_type(2)));     // (re, im)
 __device__ __forceinline__ c2 cmul(c2 a, c2 b) { return c2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }
 __device__ __forceinline__ c2 cmul_mi(c2 a) { return c2{a.y, -a.x}; }      // a * (-i)
 
 // TW[n] = exp(-2 pi i n / M), n < M;  TW[M + k] = exp(-2 pi i k / (2 M)), k <= M;  TW[2 M + 1 + j] = (hann window j, 0), j < 2 M.
-// Block 0 also packs the filterbank ONCE per call: bands[m] = first bin, bands[NM + m] = one past the last bin, bands[2 NM + m] =
-// offset of the band's non-zeros in fbp (-1: does not fit, read from the dense matrix) -- every STFT workgroup copies these few
-// KB into LDS instead of scanning the dense [n_mels, n_bins] matrix itself (that scan was 2/3 of the first version's time).
+// Block 0 also packs the filterbank's bands.
 __global__ void mel_fft_table_k(c2* TW, int M, const double* fb, int NM, int* bands, double* fbp) {
-  const int NF = 2 * M, n = 2 * M + 1 + NF, NBIN = M + 1;
+  const int NF = 2 * M, n = 2 * M + 1 + NF;
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
     if (i < M) { const double a = 2.0 * M_PI * (double)i / (double)M; TW[i] = c2{cos(a), -sin(a)}; }
     else if (i <= 2 * M) { const double a = 2.0 * M_PI * (double)(i - M) / (double)NF; TW[i] = c2{cos(a), -sin(a)}; }
-    else { const int j = i - 2 * M - 1; TW[i] = c2{0.5 - 0.5 * cos(2.0 * M_PI * (double)j / (double)(NF - 1)), 0.0}; }
+    else TW[i] = c2{mel_hann(i - 2 * M - 1, NF), 0.0};
   }
-  if (blockIdx.x == 0) {
-    // first / last non-zero bin of every mel filter: all threads walk the dense matrix together (min / max through global atomics
-    // on the band table itself: a serial scan per filter was 0.13 ms of a 1.7 ms front-end)
-    for (int m = threadIdx.x; m < NM; m += blockDim.x) { bands[m] = NBIN; bands[NM + m] = 0; }
-    __syncthreads();
-    for (int i = threadIdx.x; i < NM * NBIN; i += blockDim.x) {
-      const int m = i / NBIN, k = i - m * NBIN;
-      if (fb[i] != 0.0) { atomicMin(bands + m, k); atomicMax(bands + NM + m, k + 1); }
-    }
-    __syncthreads();
-    for (int m = threadIdx.x; m < NM; m += blockDim.x)
-      if (bands[NM + m] == 0) bands[m] = 0;            // an all-zero filter: empty band [0, 0)
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int o = 0;
-      for (int m = 0; m < NM; ++m) {
-        const int w = bands[NM + m] - bands[m];
-        if (o + w <= MFB_CAP) { bands[2 * NM + m] = o; o += w; } else bands[2 * NM + m] = -1;
-      }
-    }
-    __syncthreads();
-    for (int m = threadIdx.x; m < NM; m += blockDim.x)
-      if (bands[2 * NM + m] >= 0)
-        for (int k = bands[m]; k < bands[NM + m]; ++k) fbp[bands[2 * NM + m] + k - bands[m]] = fb[(long)m * NBIN + k];
-  }
+  if (blockIdx.x == 0) mel_pack_bands(fb, NM, M + 1, bands, fbp);
 }
 
 __host__ __device__ inline size_t mel_fft_lds(int NF, int n_mels) {
   return sizeof(double) * 2 * ((size_t)2 * FFB * (NF / 2)) + sizeof(double) * MFB_CAP + sizeof(int) * 3 * (size_t)n_mels + 64;
 }
 
-// One workgroup's share: STFT frames fr0 .. fr0 + FFB - 1 of ONE signal -> logmel / energy slots slot0 .. (those below nfr are
+// One workgroup's share: STFT frames fr0 .. fr0 + FFB - 1 of ONE signal -> feature rows slot0 .. (those below nfr are
 // stored).  The body of mel_stft_fft_k and of mel_stft_fft_batch_k: one statement of the per-frame arithmetic for both.
 __device__ __forceinline__ void mel_stft_fft_frames(const ZeggsMelDims& d, const FftPlan& plan, const float* wav, long n, long n_avail,
-                                                    const double* fb, const c2* __restrict__ TW, const int* bands,
-                                                    const double* fbp, double* logmel, double* energy, const long fr0,
+                                                    const double* fb, const MelTables& tab, double* feat, const long fr0,
                                                     const long slot0, long nfr, int exact, long base, unsigned char* smem) {
-  const int NF = d.n_fft, M = NF / 2, NBIN = M + 1, hop = d.hop, NM = d.n_mels;
+  const int NF = d.n_fft, M = NF / 2, NBIN = M + 1, NM = d.n_mels;
+  const c2* __restrict__ TW = tab.ftw;
   c2* bufA = (c2*)smem;                               // [FFB][M]
   c2* bufB = bufA + (size_t)FFB * M;                  // [FFB][M]
   double* fbs = (double*)(bufB + (size_t)FFB * M);    // [MFB_CAP]
-  int* blo = (int*)(fbs + MFB_CAP);
-  int* bhi = blo + NM;
-  int* bof = bhi + NM;
+  int* blo = (int*)(fbs + MFB_CAP);                   // [3 NM]
   const int tid = threadIdx.x;
-  const long neff = n > NF ? n : NF;
   const c2* WIN = TW + 2 * M + 1;
   // windowed samples, packed: z[m] = xw[2 m] + i xw[2 m + 1]
   for (int i = tid; i < FFB * M; i += blockDim.x) {
@@ -388,15 +357,11 @@ __device__ __forceinline__ void mel_stft_fft_frames(const ZeggsMelDims& d, const
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int j = 2 * m + h;
-      const long p = (fr0 + f) * hop + j - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2);
-      const long src = p < 0 ? -p : (p >= neff ? 2 * (neff - 1) - p : p);
-      const double x = mel_sample(wav, src, n, n_avail, d.pre_emph, base);
-      v[h] = x * WIN[j].x;
+      v[h] = mel_sample(wav, mel_src(d, fr0 + f, j, n), n, n_avail, d.pre_emph, base) * WIN[j].x;
     }
     bufA[i] = c2{v[0], v[1]};
   }
-  for (int i = tid; i < 3 * NM; i += blockDim.x) blo[i] = bands[i];          // blo | bhi | bof are contiguous
-  for (int i = tid; i < MFB_CAP; i += blockDim.x) fbs[i] = fbp[i];
+  mel_stage_bands(tab.bands, tab.fbp, NM, fbs, blo);
   __syncthreads();
   // ---- Stockham stages: x -> y, natural order in, natural order out
   c2* x = bufA;
@@ -449,45 +414,19 @@ __device__ __forceinline__ void mel_stft_fft_frames(const ZeggsMelDims& d, const
     amp[(size_t)f * NBIN + k] = sqrt(X.x * X.x + X.y * X.y) / (double)NF;
   }
   __syncthreads();
-  double* melv = (double*)x;                          // [FFB][NM] squares of exp(log-mel): the spectrum buffer is free now
-  const double amin = (double)d.min_clip / (double)NF;
-  const double rng = -20.0 * log10(amin);
-  for (int it = tid; it < FFB * NM; it += blockDim.x) {
-    const int f = it / NM, m = it % NM;
-    const double* av = amp + (size_t)f * NBIN;
-    double sacc = 0.0;
-    if (bof[m] >= 0) {
-      const double* fv = fbs + bof[m] - blo[m];
-      for (int k = blo[m]; k < bhi[m]; ++k) sacc = fma(fv[k], av[k], sacc);
-    } else {
-      const double* fv = fb + (long)m * NBIN;
-      for (int k = blo[m]; k < bhi[m]; ++k) sacc = fma(fv[k], av[k], sacc);
-    }
-    sacc = fabs(sacc);
-    if (sacc < amin) sacc = amin;
-    const double yv = mel_logamp(sacc, rng, exact, d.flags);
-    melv[it] = mel_exp_sq(yv, exact);                                 // (every thread its own exp; the frame's thread only adds, in mel order)
-    if (slot0 + f < nfr) logmel[(slot0 + f) * NM + m] = yv;
-  }
-  __syncthreads();
-  if (tid < FFB && slot0 + tid < nfr) {
-    double e = 0.0;
-    for (int m = 0; m < NM; ++m) e += melv[tid * NM + m];
-    energy[slot0 + tid] = sqrt(e);
-  }
+  mel_frame_tail(d, FFB, amp, (double*)x, blo, fbs, fb, feat, slot0, nfr, exact);      // (the spectrum buffer is free now)
 }
 
 __global__ __launch_bounds__(FTHR) void mel_stft_fft_k(ZeggsMelDims d, FftPlan plan, const float* wav, long n, long n_avail,
-                                                      const double* fb, const c2* __restrict__ TW, const int* bands,
-                                                      const double* fbp, double* logmel, double* energy, long m0, long nfr, int exact,
+                                                      const double* fb, MelTables tab, double* feat, long m0, long nfr, int exact,
                                                       long base) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, TW, bands, fbp, logmel, energy, m0 + (long)blockIdx.x * FFB, (long)blockIdx.x * FFB,
-                      nfr, exact, base, smem);
+  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, tab, feat, m0 + (long)blockIdx.x * FFB, (long)blockIdx.x * FFB, nfr, exact,
+                      base, smem);
 }
 
 // The batched form (zeggs_mel_features_batch): workgroup b works on row r with blk0[r] <= b < blk0[r + 1], block b - blk0[r] of that
-// row's nfr[r] STFT frames m0[r] ..; a row's logmel / energy slots are [r S, r S + nfr[r]).  What the host derived per row travels by
+// row's nfr[r] STFT frames m0[r] ..; a row's feature rows are [r S, r S + nfr[r]) of one table.  What the host derived per row travels by
 // value (1.5 KB); the records themselves (pointers, counts) are read from device memory, wave-uniformly.
 struct MelBatchPlan {
   int blk0[ZEGGS_LIVE_MAX_ROWS + 1];
@@ -496,9 +435,8 @@ struct MelBatchPlan {
   long M[ZEGGS_LIVE_MAX_ROWS];       // STFT frames of the finished signal (final) or 2^40
 };
 __global__ __launch_bounds__(FTHR) void mel_stft_fft_batch_k(ZeggsMelDims d, FftPlan plan, const ZeggsMelRow* __restrict__ rows,
-                                                            MelBatchPlan bp, int R, long S, const double* fb,
-                                                            const c2* __restrict__ TW, const int* bands, const double* fbp,
-                                                            double* logmel, double* energy, int exact) {
+                                                            MelBatchPlan bp, int R, long S, const double* fb, MelTables tab,
+                                                            double* feat, int exact) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   int r = 0;
   while (r + 1 < R && (int)blockIdx.x >= bp.blk0[r + 1]) ++r;
@@ -506,92 +444,21 @@ __global__ __launch_bounds__(FTHR) void mel_stft_fft_batch_k(ZeggsMelDims d, Fft
   const float* wav = rows[r].wav;
   const long n_avail = rows[r].n_samples, base = rows[r].base;
   const long n = rows[r].final ? n_avail : (1L << 50);
-  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, TW, bands, fbp, logmel + (size_t)r * S * d.n_mels, energy + (size_t)r * S,
-                      bp.m0[r] + blk * FFB, blk * FFB, (long)bp.nfr[r], exact, base, smem);
+  mel_stft_fft_frames(d, plan, wav, n, n_avail, fb, tab, feat + (size_t)r * S * (d.n_mels + 1), bp.m0[r] + blk * FFB, blk * FFB,
+                      (long)bp.nfr[r], exact, base, smem);
 }
 
-// resample_method = "cubic": interp1d(kind = "cubic") = the interpolating cubic spline with not-a-knot ends (make_interp_spline(k = 3)) over
-// the integer frame grid 0 .. M-1, one per column (80 mel channels, griddata's 1-D path, + the energy).  In terms of the second derivatives
-// S_i:  S_{i-1} + 4 S_i + S_{i+1} = 6 (y_{i-1} - 2 y_i + y_{i+1}) =: r_i  (i = 1 .. M-2), and the not-a-knot conditions S_0 - 2 S_1 + S_2 = 0,
-// S_{M-3} - 2 S_{M-2} + S_{M-1} = 0 turn the first and last equation into S_1 = r_1 / 6, S_{M-2} = r_{M-2} / 6.  What is left (i = 2 .. M-3) is a
-// diagonally dominant tridiagonal system: one thread per column eliminates forward and substitutes back (the columns of a row are contiguous:
-// coalesced).  float64 throughout, as scipy.
-__global__ void mel_spline_rhs_k(ZeggsMelDims d, const double* logmel, const double* energy, long M, double* S) {
-  const int W = d.n_mels + 1;
-  const long n = M * W;
-  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x) {
-    const int c = (int)(i % W);
-    const long m = i / W;
-    auto y = [&](long q) { return c < d.n_mels ? logmel[q * d.n_mels + c] : energy[q]; };
-    S[i] = (m >= 1 && m <= M - 2) ? 6.0 * ((y(m - 1) - y(m)) - (y(m) - y(m + 1))) : 0.0;
-  }
-}
-// The system is strictly diagonally dominant: what a row feels of a row k places away decays like (2 - sqrt 3)^k = 0.268^k (1e-23 at
-// k = 40).  So the elimination is cut into chunks of SPL_CH rows that start SPL_HL rows early (from an arbitrary state: forgotten long
-// before the chunk's own rows) and run SPL_HL rows past their end before substituting back -- exact to the last bit of float64, one
-// workgroup per chunk, one thread per column: 144 000 rows (30 minutes of audio) in ~0.1 ms instead of 45 ms as one sequential sweep.
-constexpr int SPL_CH = 128, SPL_HL = 40;
-__global__ __launch_bounds__(128) void mel_spline_solve_k(ZeggsMelDims d, long M, const double* R, double* S) {
-  __shared__ double cpl[SPL_CH + 2 * SPL_HL];          // elimination coefficients of the rows this chunk walks (column-independent)
-  __shared__ double halo[SPL_HL][128];                 // d' of the rows past the chunk's end
-  const int W = d.n_mels + 1, c = threadIdx.x;
-  const bool on = c < W;
-  const long lo = 2, hi = M - 3;                       // interior unknowns
-  const double s1 = on ? R[1 * W + c] / 6.0 : 0.0, sl = on ? R[(M - 2) * W + c] / 6.0 : 0.0;
-  if (hi >= lo) {
-    const long a = lo + (long)blockIdx.x * SPL_CH, b = (a + SPL_CH - 1 < hi) ? a + SPL_CH - 1 : hi;
-    if (a <= hi) {
-      const long st = (a - SPL_HL > lo) ? a - SPL_HL : lo, en = (b + SPL_HL < hi) ? b + SPL_HL : hi;
-      double cprev = 0.0, dprev = 0.0;
-      for (long i = st; i <= en; ++i) {
-        double rhs = on ? R[i * W + c] : 0.0;
-        if (i == lo) rhs -= s1;
-        if (i == hi) rhs -= sl;
-        const double den = (i == st) ? 4.0 : 4.0 - cprev;      // (i == st > lo: an arbitrary start, forgotten SPL_HL rows later)
-        cprev = 1.0 / den;
-        dprev = (rhs - ((i == st) ? 0.0 : dprev)) / den;
-        if (c == 0) cpl[i - st] = cprev;
-        if (on) {
-          if (i >= a && i <= b) S[i * W + c] = dprev;
-          else if (i > b) halo[i - b - 1][c] = dprev;
-        }
-      }
-      __syncthreads();
-      double x = 0.0;
-      for (long i = en; i >= a; --i) {
-        const double dp = (i > b) ? halo[i - b - 1][c] : (on ? S[i * W + c] : 0.0);
-        x = (i == en) ? dp : dp - cpl[i - st] * x;            // (en < hi: as if the row behind were zero -- forgotten before row b)
-        if (on && i <= b) S[i * W + c] = x;
-      }
-    }
-  }
-  // the two rows next to the ends and the ends themselves (not-a-knot), by the chunks that hold their neighbours
-  if (on && blockIdx.x == 0) {
-    const double s2 = M > 4 ? S[2 * W + c] : sl;
-    S[1 * W + c] = s1;
-    S[c] = 2.0 * s1 - s2;
-  }
-  const long nchunk = hi >= lo ? (hi - lo) / SPL_CH + 1 : 1;
-  if (on && blockIdx.x == nchunk - 1) {
-    const double sm3 = M > 4 ? S[(M - 3) * W + c] : s1;
-    S[(M - 2) * W + c] = sl;
-    S[(M - 1) * W + c] = 2.0 * sl - sm3;
-  }
-}
-
-// resampling at t_k = ((fs/hop)/fps) k.  "linear" / "cubic": mel -> NaN outside the hull (griddata's fill value), the energy extrapolates
+// resampling at t_k = mel_rate k.  "linear" / "cubic": mel -> NaN outside the hull (griddata's fill value), the energy extrapolates
 // (interp1d(fill_value = "extrapolate"): the end pieces continue); "nearest": both take the nearest frame, halves round DOWN, ends clamp
 // (interp1d's bounds x_i + 1/2 searched from the left; griddata sets fill_value = "extrapolate" for this method).
-// animation frames k0 .. k0 + n_frames - 1; logmel / energy hold the STFT frames m0 .. (indices relative to m0)
-// one element: column c (mel channel, or the energy at c == n_mels) of animation frame k; logmel / energy indexed by ABSOLUTE STFT frame
-__device__ __forceinline__ float mel_resample_elem(const ZeggsMelDims& d, const double* logmel, const double* energy, const double* spl,
-                                                   long M, int c, long k) {
+// one element: column c (mel channel, or the energy at c == n_mels) of animation frame k; feat / spl indexed by ABSOLUTE STFT frame
+__device__ __forceinline__ float mel_resample_elem(const ZeggsMelDims& d, const double* feat, const double* spl, long M, int c, long k) {
   const int W = d.n_mels + 1;
-  const double t = (((double)d.fs / (double)d.hop) / (double)d.fps) * (double)k;
+  const double t = mel_rate(d) * (double)k;
   if (d.flags & MEL_NEAREST) {
     long q = (long)ceil(t - 0.5);
     q = q < 0 ? 0 : q > M - 1 ? M - 1 : q;
-    return (float)(c < d.n_mels ? logmel[q * d.n_mels + c] : energy[q]);
+    return (float)feat[q * W + c];
   }
   long hi = (long)ceil(t);            // searchsorted(side=left) over the integer grid
   if (hi < 1) hi = 1;
@@ -599,32 +466,26 @@ __device__ __forceinline__ float mel_resample_elem(const ZeggsMelDims& d, const 
   const long lo = hi - 1;
   if (M < 2) return nanf("");
   if (c < d.n_mels && (t < 0.0 || t > (double)(M - 1))) return nanf("");
-  const double ylo = c < d.n_mels ? logmel[lo * d.n_mels + c] : energy[lo], yhi = c < d.n_mels ? logmel[hi * d.n_mels + c] : energy[hi];
-  if (d.flags & MEL_CUBIC) {
-    const double u = t - (double)lo, v = 1.0 - u;
-    return (float)(ylo * v + yhi * u + ((v * v * v - v) * spl[lo * W + c] + (u * u * u - u) * spl[hi * W + c]) / 6.0);
-  }
+  const double ylo = feat[lo * W + c], yhi = feat[hi * W + c];
+  if (d.flags & MEL_CUBIC) return (float)spline_piece(ylo, yhi, spl[lo * W + c], spl[hi * W + c], t - (double)lo);
   return (float)((yhi - ylo) * (t - (double)lo) + ylo);
 }
-__global__ void mel_resample_k(ZeggsMelDims d, const double* logmel, const double* energy, const double* spl, long M, long m0, long k0,
-                               int n_frames, float* out) {
+// animation frames k0 .. k0 + n_frames - 1; feat holds the STFT frames m0 .. (rows relative to m0)
+__global__ void mel_resample_k(ZeggsMelDims d, const double* feat, const double* spl, long M, long m0, long k0, int n_frames, float* out) {
   const int W = d.n_mels + 1;
   const long n = (long)n_frames * W;
-  logmel -= m0 * d.n_mels;
-  energy -= m0;
+  feat -= m0 * W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    out[i] = mel_resample_elem(d, logmel, energy, spl, M, (int)(i % W), k0 + i / W);
+    out[i] = mel_resample_elem(d, feat, spl, M, (int)(i % W), k0 + i / W);
 }
 // the batched sibling: blockIdx.y = row; M, m0 (plan) and k0, the frame count and the output (record) are the row's own
-__global__ void mel_resample_batch_k(ZeggsMelDims d, const ZeggsMelRow* __restrict__ rows, MelBatchPlan bp, long S, const double* logmel,
-                                     const double* energy) {
+__global__ void mel_resample_batch_k(ZeggsMelDims d, const ZeggsMelRow* __restrict__ rows, MelBatchPlan bp, long S, const double* feat) {
   const int W = d.n_mels + 1, r = blockIdx.y;
   const long k0 = rows[r].k0, n = (rows[r].k1 - k0) * W;
   float* out = rows[r].out;
-  logmel += ((long)r * S - bp.m0[r]) * d.n_mels;
-  energy += (long)r * S - bp.m0[r];
+  feat += ((long)r * S - bp.m0[r]) * W;
   for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)gridDim.x * blockDim.x)
-    out[i] = mel_resample_elem(d, logmel, energy, nullptr, bp.M[r], (int)(i % W), k0 + i / W);
+    out[i] = mel_resample_elem(d, feat, nullptr, bp.M[r], (int)(i % W), k0 + i / W);
 }
 
 }  // namespace
@@ -652,68 +513,62 @@ thread_local int t_mel_launches = 0;      // kernels enqueued by this thread's r
 thread_local int t_mel_form = 0;          // the STFT form this thread enqueued last (zeggs_mel_last_form): set where t_mel_launches is bumped
 constexpr size_t MEL_LDS_MAX = 160 * 1024;      // dynamic LDS a workgroup may be given (with the per-kernel opt-in above 64 KB)
 
+// The opt-in, once per kernel and process; `done` is that kernel's flag.  Two threads that arrive together both set the attribute (it
+// is idempotent); neither launches before its own call has returned.
+static int mel_lds_opt_in(const void* kernel, std::atomic<bool>& done, const char* who, const char* name) {
+  if (done.load(std::memory_order_acquire)) return 0;
+  ZCHECK(hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MEL_LDS_MAX) == hipSuccess,
+         "%s: cannot raise the LDS limit of the %s kernel", who, name);
+  done.store(true, std::memory_order_release);
+  return 0;
+}
+
 // whether the FFT form takes these dimensions (and the option allows it); *plan: its radices
 static bool mel_fft_form(const ZeggsMelDims& d, FftPlan* plan) {
   *plan = fft_plan(d.n_fft / 2);
-  return g_mel_fft && plan->nst > 0 && d.n_fft % 2 == 0 && mel_fft_lds(d.n_fft, d.n_mels) <= 160 * 1024 &&
+  return g_mel_fft && plan->nst > 0 && d.n_fft % 2 == 0 && mel_fft_lds(d.n_fft, d.n_mels) <= MEL_LDS_MAX &&
          (size_t)FFB * d.n_mels <= (size_t)2 * FFB * (d.n_fft / 2);
 }
 
-// STFT frames m0 .. m0 + nfr - 1 -> logmel / energy slots 0 .. nfr - 1
+// STFT frames m0 .. m0 + nfr - 1 -> rows 0 .. nfr - 1 of w.feat
 // (`base`: index of wav[0] in the signal, see mel_sample)
 static int launch_stft(const ZeggsMelDims& d, const MelWs& w, const float* wav, long n, long n_avail, const double* fb, long m0,
                        long nfr, hipStream_t s, long base = 0) {
   const int NBIN = d.n_fft / 2 + 1;
   FftPlan plan;
-  const size_t fft_lds = mel_fft_lds(d.n_fft, d.n_mels);
   if (mel_fft_form(d, &plan) && nfr >= 1) {
-    static bool fft_attr_set = false;
-    if (!fft_attr_set) {
-      if (hipFuncSetAttribute((const void*)mel_stft_fft_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-        zeggs_set_error("mel: cannot raise the LDS limit of the FFT kernel");
-        return -1;
-      }
-      fft_attr_set = true;
-    }
-    hipLaunchKernelGGL(mel_fft_table_k, dim3(16), dim3(256), 0, s, (c2*)w.ftw, d.n_fft / 2, fb, d.n_mels, w.bands, w.fbp);
+    static std::atomic<bool> opted{false};
+    ZTRY(mel_lds_opt_in((const void*)mel_stft_fft_k, opted, "mel", "FFT"));
+    hipLaunchKernelGGL(mel_fft_table_k, dim3(16), dim3(256), 0, s, w.t.ftw, d.n_fft / 2, fb, d.n_mels, w.t.bands, w.t.fbp);
     ZLAUNCH_CHECK("mel_fft_table");
-    hipLaunchKernelGGL(mel_stft_fft_k, dim3((unsigned)((nfr + FFB - 1) / FFB)), dim3(FTHR), fft_lds, s, d, plan, wav, n, n_avail, fb,
-                       (const c2*)w.ftw, w.bands, w.fbp, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
+    hipLaunchKernelGGL(mel_stft_fft_k, dim3((unsigned)((nfr + FFB - 1) / FFB)), dim3(FTHR), mel_fft_lds(d.n_fft, d.n_mels), s, d, plan, wav, n,
+                       n_avail, fb, w.t, w.feat, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_fft");
     t_mel_launches += 2;
     t_mel_form = 1;
     return 0;
   }
   const size_t fast_lds = mel_fast_lds(d.n_fft, d.hop, d.n_mels);
-  if (g_mel_mfma && d.pre_emph == 0.0 && d.n_fft % 4 == 0 && 2 * NBIN <= MCOLP && fast_lds <= 160 * 1024 && nfr >= 1) {   // (stages float32 samples)
-    static bool attr_set = false;
-    if (!attr_set) {       // more than 64 KB of dynamic LDS needs the opt-in
-      (void)hipFuncSetAttribute((const void*)mel_stft_mfma_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      attr_set = true;
-    }
-    hipLaunchKernelGGL(mel_table_k, dim3(1024), dim3(256), 0, s, w.table, w.win, d.n_fft, NBIN);
+  if (g_mel_mfma && d.pre_emph == 0.0 && d.n_fft % 4 == 0 && 2 * NBIN <= MCOLP && fast_lds <= MEL_LDS_MAX && nfr >= 1) {   // (stages float32 samples)
+    static std::atomic<bool> opted{false};
+    ZTRY(mel_lds_opt_in((const void*)mel_stft_mfma_k, opted, "mel", "matrix-core"));
+    hipLaunchKernelGGL(mel_table_k, dim3(1024), dim3(256), 0, s, w.table, w.win, d.n_fft, NBIN, fb, d.n_mels, w.t.bands, w.t.fbp);
     ZLAUNCH_CHECK("mel_table");
     hipLaunchKernelGGL(mel_stft_mfma_k, dim3((unsigned)((nfr + MF - 1) / MF)), dim3(MWAVES * 64), fast_lds, s, d, wav, n, n_avail,
-                       fb, w.table, w.win, w.logmel, w.energy, m0, nfr, g_mel_exact_log, base);
+                       fb, w.table, w.win, w.t.bands, w.t.fbp, w.feat, m0, nfr, g_mel_exact_log, base);
     ZLAUNCH_CHECK("mel_stft_mfma");
     t_mel_launches += 2;
     t_mel_form = 2;
     return 0;
   }
   // the direct form takes what the other two decline; its frame, cos / sin table, amplitudes and mel values live in LDS, which ends it
-  // (n_fft <= 5828 at 80 mel channels) -- refused here, ahead of the launch
+  // (n_fft <= 5828 at 80 mel channels; from 2318 on it is past the 64 KB a kernel gets without the opt-in) -- refused here, ahead of the launch
   const size_t lds = sizeof(double) * (3 * (size_t)d.n_fft + d.n_fft / 2 + 1 + d.n_mels);
   ZCHECK(lds <= MEL_LDS_MAX, "mel: n_fft = %d with %d mel channels needs %zu bytes of LDS per STFT frame, a workgroup has %zu", d.n_fft,
          d.n_mels, lds, MEL_LDS_MAX);
-  static bool direct_attr_set = false;
-  if (!direct_attr_set) {       // (n_fft >= 2318 at 80 mel channels is past the 64 KB a kernel gets without the opt-in)
-    if (hipFuncSetAttribute((const void*)mel_stft_k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)MEL_LDS_MAX) != hipSuccess) {
-      zeggs_set_error("mel: cannot raise the LDS limit of the direct kernel");
-      return -1;
-    }
-    direct_attr_set = true;
-  }
-  hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.logmel, w.energy, m0, g_mel_exact_log, base);
+  static std::atomic<bool> opted{false};
+  ZTRY(mel_lds_opt_in((const void*)mel_stft_k, opted, "mel", "direct"));
+  hipLaunchKernelGGL(mel_stft_k, dim3((unsigned)nfr), dim3(256), lds, s, d, wav, n, n_avail, fb, w.feat, m0, g_mel_exact_log, base);
   ZLAUNCH_CHECK("mel_stft");
   t_mel_launches += 1;
   t_mel_form = 3;
@@ -743,17 +598,12 @@ extern "C" int zeggs_mel_features(const ZeggsMelDims* dp, const float* wav, long
   ZTRY(launch_stft(d, w, wav, n_samples, n_samples, filterbank, 0L, M, s));
   if (n_frames > 0) {
     long n = (long)n_frames * (d.n_mels + 1), g = (n + 255) / 256;
-    if (d.flags & MEL_CUBIC) {
+    if (d.flags & MEL_CUBIC) {      // one spline per column of the feature table over the WHOLE signal
       ZCHECK(M >= 4, "mel: resample_method \"cubic\" needs at least 4 STFT frames (got %ld)", M);      // (scipy raises the same way)
-      ZCHECK(d.n_mels + 1 <= 128, "mel: resample_method \"cubic\" supports up to 127 mel channels");
-      const long nn = M * (d.n_mels + 1), gg = (nn + 255) / 256;
-      hipLaunchKernelGGL(mel_spline_rhs_k, dim3((unsigned)(gg > 4096 ? 4096 : gg)), dim3(256), 0, s, d, w.logmel, w.energy, M, w.cp);
-      const long nchunk = M - 3 >= 2 ? (M - 5) / SPL_CH + 1 : 1;
-      hipLaunchKernelGGL(mel_spline_solve_k, dim3((unsigned)nchunk), dim3(128), 0, s, d, M, w.cp, w.spl);
+      spline_second_derivatives(w.feat, M, d.n_mels + 1, w.spl, s);
       ZLAUNCH_CHECK("mel_spline");
     }
-    hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.logmel, w.energy, w.spl, M,
-                       0L, 0L, n_frames, out);
+    hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.feat, w.spl, M, 0L, 0L, n_frames, out);
     ZLAUNCH_CHECK("mel_resample");
   }
   return 0;
@@ -763,77 +613,17 @@ extern "C" int zeggs_mel_features(const ZeggsMelDims* dp, const float* wav, long
 //   final == 0: the signal continues; every STFT frame the range needs must end inside the n_samples present
 //               (zeggs_mel_frames_ready tells how far that is) -- no right-edge reflection, no end clamps;
 //   final != 0: n_samples is the whole signal: identical to rows k0..k1-1 of zeggs_mel_features.
-extern "C" long zeggs_mel_frames_ready(const ZeggsMelDims* d, long n_samples) {
-  // STFT frame m is complete when 200 m + 400 <= n; animation frame k interpolates STFT frames ceil(t)-1, ceil(t)
-  // (uncentered: frame m covers samples m hop .. m hop + n_fft - 1)
-  const long mmax = (d->flags & MEL_UNCENTERED) ? (n_samples - d->n_fft) / d->hop : (n_samples - d->n_fft / 2) / d->hop;      // last complete STFT frame (may be < 1)
-  if (mmax < 1) return 0;
-  const double r = ((double)d->fs / (double)d->hop) / (double)d->fps;
-  long k = (long)floor((double)mmax / r);                           // largest k with t_k <= mmax
-  while (k >= 0 && ceil(r * (double)k) > (double)mmax) --k;
-  return k + 1;                                                     // frames 0 .. k are computable
-}
+extern "C" long zeggs_mel_frames_ready(const ZeggsMelDims* d, long n_samples) { return mel_frames_ready(*d, n_samples); }
 extern "C" size_t zeggs_mel_range_workspace_bytes(const ZeggsMelDims* d, long k0, long k1) {
-  const double r = ((double)d->fs / (double)d->hop) / (double)d->fps;
-  const long mspan = (long)ceil(r * (double)(k1 - 1)) - (long)floor(r * (double)k0) + 4;
   Arena a(nullptr, 0);
-  carve_mel(*d, mspan, a);
+  carve_mel(*d, mel_range_slots(*d, k0, k1), a);
   return a.off + 256;
 }
-// STFT frames [m0, m1) that the animation frames [k0, k1) interpolate, M = STFT frames of the (finished) signal
-static void mel_range_stft(const ZeggsMelDims& d, long n_samples, int final, long k0, long k1, long* M_, long* m0_, long* m1_) {
-  const long M = final ? stft_frames(n_samples, d.n_fft, d.hop, d.flags) : (1L << 40);
-  const double r = ((double)d.fs / (double)d.hop) / (double)d.fps;
-  long m0 = (long)ceil(r * (double)k0) - 1, m1 = (long)ceil(r * (double)(k1 - 1)) + 1;   // [m0, m1)
-  if (m0 < 0) m0 = 0;
-  if (m1 < 2) m1 = 2;
-  if (m1 > M) m1 = M;
-  if (m0 > m1 - 2) m0 = m1 - 2 > 0 ? m1 - 2 : 0;
-  *M_ = M; *m0_ = m0; *m1_ = m1;
-}
-// smallest sample index that the STFT frames [m0, m1) load (the index rule of the three kernels' load sites, on the host): n = signal
-// length of the reflect rule, n_avail = samples present; the sample before it when pre-emphasis is on.  LONG_MAX: they load nothing.
-static long mel_first_load(const ZeggsMelDims& d, long m0, long m1, long n, long n_avail) {
-  const long NF = d.n_fft, neff = n > NF ? n : NF, lim = n < n_avail ? n : n_avail;
-  long best = __LONG_MAX__;
-  for (long m = m0; m < m1; ++m) {
-    const long a = m * d.hop - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2), b = a + NF - 1;      // p = a .. b
-    long lo = __LONG_MAX__;
-    const long ma = a > 0 ? a : 0, mb = b < neff - 1 ? b : neff - 1;            // 0 <= p < neff: src = p
-    if (ma <= mb && ma < lim) lo = ma;
-    if (a < 0) {                                                                // p < 0: src = -p
-      const long c = -(b < -1 ? b : -1);
-      if (c < lim && c < lo) lo = c;
-    }
-    if (b >= neff) {                                                            // p >= neff: src = 2 (neff - 1) - p
-      const long hi = 2 * (neff - 1) - (a > neff ? a : neff);
-      long c = 2 * (neff - 1) - b;
-      if (c < 0) c = 0;
-      if (c <= hi && c < lim && c < lo) lo = c;
-    }
-    if (lo != __LONG_MAX__ && d.pre_emph != 0.0 && lo > 0) --lo;
-    if (lo < best) best = lo;
-    if (b < neff && a >= 0) break;      // no reflection in this frame: every later frame without one starts further right ...
-  }
-  if (m1 > m0) {                        // ... and the frames that reflect at the right end are the last ones
-    for (long m = m1 - 1; m >= m0; --m) {
-      const long a = m * d.hop - ((d.flags & MEL_UNCENTERED) ? 0 : NF / 2), b = a + NF - 1;
-      if (b < neff) break;
-      const long hi = 2 * (neff - 1) - (a > neff ? a : neff);
-      long c = 2 * (neff - 1) - b;
-      if (c < 0) c = 0;
-      if (c <= hi && c < lim) {
-        if (d.pre_emph != 0.0 && c > 0) --c;
-        if (c < best) best = c;
-      }
-    }
-  }
-  return best;
-}
+constexpr long MEL_M_OPEN = 1L << 40, MEL_N_OPEN = 1L << 50;      // STFT frames / samples of a signal that continues
 extern "C" long zeggs_mel_window_first_sample(const ZeggsMelDims* d, long k0) {
-  long M, m0, m1;
-  mel_range_stft(*d, 0, 0, k0, k0 + 1, &M, &m0, &m1);
-  const long f = mel_first_load(*d, m0, m1, 1L << 50, 1L << 50);      // (the signal continues: no right end)
+  long m0, m1;
+  mel_range_stft(*d, MEL_M_OPEN, k0, k0 + 1, &m0, &m1);
+  const long f = mel_first_load(*d, m0, m1, MEL_N_OPEN, MEL_N_OPEN);      // (the signal continues: no right end)
   return f == __LONG_MAX__ ? 0 : f;
 }
 // the argument checks of a range / window call, ahead of any launch (`who`: "" or the batched call's "mel batch: row r: ");
@@ -844,10 +634,11 @@ static int mel_range_check(const ZeggsMelDims& d, long base, long n_samples, int
   ZCHECK(n_samples > 0 && k0 >= 0 && k1 > k0, "%smel range: empty input", who);
   ZCHECK(!(d.flags & MEL_CUBIC), "%smel range: resample_method \"cubic\" is a spline over the WHOLE signal -- use zeggs_mel_features", who);
   if (!final)
-    ZCHECK(k1 <= zeggs_mel_frames_ready(&d, n_samples), "%smel range: frames %ld..%ld need samples not received yet", who, k0, k1);
-  mel_range_stft(d, n_samples, final, k0, k1, M, m0, m1);
+    ZCHECK(k1 <= mel_frames_ready(d, n_samples), "%smel range: frames %ld..%ld need samples not received yet", who, k0, k1);
+  *M = final ? stft_frames(n_samples, d.n_fft, d.hop, d.flags) : MEL_M_OPEN;
+  mel_range_stft(d, *M, k0, k1, m0, m1);
   if (base > 0) {
-    const long first = mel_first_load(d, *m0, *m1, final ? n_samples : (1L << 50), n_samples);
+    const long first = mel_first_load(d, *m0, *m1, final ? n_samples : MEL_N_OPEN, n_samples);
     ZCHECK(base <= first, "%smel window: frames %ld..%ld read sample %ld, the window starts at %ld", who, k0, k1, first, base);
   }
   return 0;
@@ -858,14 +649,13 @@ static int mel_range_impl(const ZeggsMelDims* dp, const float* wav, long base, l
   hipStream_t s = (hipStream_t)stream;
   long M, m0, m1;
   ZTRY(mel_range_check(d, base, n_samples, final, k0, k1, "", &M, &m0, &m1));
-  const long n = final ? n_samples : (1L << 50);
+  const long n = final ? n_samples : MEL_N_OPEN;
   Arena a(ws, ws_bytes);
   MelWs w = carve_mel(d, m1 - m0, a);
   ZCHECK(a.ok(), "mel range: workspace too small (%zu < %zu)", ws_bytes, a.off);
   ZTRY(launch_stft(d, w, wav, n, n_samples, filterbank, m0, m1 - m0, s, base));
   const long nn = (k1 - k0) * (d.n_mels + 1), g = (nn + 255) / 256;
-  hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.logmel, w.energy, nullptr, M, m0, k0,
-                     (int)(k1 - k0), out);
+  hipLaunchKernelGGL(mel_resample_k, dim3((unsigned)(g > 4096 ? 4096 : g)), dim3(256), 0, s, d, w.feat, nullptr, M, m0, k0, (int)(k1 - k0), out);
   ZLAUNCH_CHECK("mel_resample");
   t_mel_launches += 1;
   return 0;
@@ -888,26 +678,13 @@ extern "C" int zeggs_mel_features_window(const ZeggsMelDims* dp, const float* wa
 
 // ---------------------------------------------------------------- batched form (include/zeggs_hip_live.h)
 namespace {
-struct MelTables { c2* ftw; double* fbp; int* bands; };
-MelTables carve_mel_tables(const ZeggsMelDims& d, Arena& a) {
-  MelTables t;
-  t.ftw = (c2*)a.raw(sizeof(double) * 2 * ((size_t)2 * d.n_fft + 1));
-  t.fbp = (double*)a.raw(sizeof(double) * MFB_CAP);
-  t.bands = (int*)a.raw(sizeof(int) * 3 * (size_t)d.n_mels);
-  return t;
-}
-// STFT slots per row of a call whose rows ask for at most F animation frames each (m1 - m0 <= r (F - 1) + 3, mel_range_stft)
-long mel_batch_slots(const ZeggsMelDims& d, long F) {
-  return (long)ceil((((double)d.fs / (double)d.hop) / (double)d.fps) * (double)(F > 1 ? F : 1)) + 4;
-}
-struct MelBatchWs { ZeggsMelRow* rows; double* logmel; double* energy; void* row_ws; size_t row_ws_bytes; };
-// records | logmel, energy of all rows; the fall-back's per-row workspace shares the second region (the rows run one after another)
+struct MelBatchWs { ZeggsMelRow* rows; double* feat; void* row_ws; size_t row_ws_bytes; };
+// records | feature table of all rows, S slots each; the fall-back's per-row workspace shares the second region (the rows run one after another)
 MelBatchWs carve_mel_batch(const ZeggsMelDims& d, int R, long S, Arena& a) {
   MelBatchWs w;
   w.rows = (ZeggsMelRow*)a.raw(sizeof(ZeggsMelRow) * ZEGGS_LIVE_MAX_ROWS);
   const size_t mark = align_up(a.off, 256);
-  w.logmel = (double*)a.raw(sizeof(double) * (size_t)R * S * d.n_mels);
-  w.energy = (double*)a.raw(sizeof(double) * (size_t)R * S);
+  w.feat = (double*)a.raw(sizeof(double) * (size_t)R * S * (d.n_mels + 1));
   const size_t end = a.off;
   Arena b(nullptr, 0);
   carve_mel(d, S, b);
@@ -987,14 +764,8 @@ extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRo
     }
     return 0;
   }
-  static bool attr_set = false;      // (per kernel: mel_stft_fft_k's own opt-in does not cover this one)
-  if (!attr_set) {
-    if (hipFuncSetAttribute((const void*)mel_stft_fft_batch_k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-      zeggs_set_error("mel batch: cannot raise the LDS limit of the FFT kernel");
-      return -1;
-    }
-    attr_set = true;
-  }
+  static std::atomic<bool> opted{false};      // (per kernel: mel_stft_fft_k's own opt-in does not cover this one)
+  ZTRY(mel_lds_opt_in((const void*)mel_stft_fft_batch_k, opted, "mel batch", "FFT"));
   if (rows_dev == nullptr) {
     if (hipMemcpyAsync(w.rows, rows, sizeof(ZeggsMelRow) * R, hipMemcpyHostToDevice, s) != hipSuccess) {
       zeggs_set_error("mel batch: cannot upload the row records");
@@ -1006,7 +777,7 @@ extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRo
   Arena ta((void*)tables, (size_t)1 << 40);
   const MelTables t = carve_mel_tables(d, ta);
   hipLaunchKernelGGL(mel_stft_fft_batch_k, dim3((unsigned)bp.blk0[R]), dim3(FTHR), mel_fft_lds(d.n_fft, d.n_mels), s, d, plan, rows_dev, bp,
-                     R, S, filterbank, (const c2*)t.ftw, (const int*)t.bands, (const double*)t.fbp, w.logmel, w.energy, g_mel_exact_log);
+                     R, S, filterbank, t, w.feat, g_mel_exact_log);
   ZLAUNCH_CHECK("mel_stft_fft_batch");
   for (int r = 0; r < R; ++r) {
     const long e = (rows[r].k1 - rows[r].k0) * (d.n_mels + 1);
@@ -1014,7 +785,7 @@ extern "C" int zeggs_mel_features_batch(const ZeggsMelDims* dp, const ZeggsMelRo
   }
   const long g = (max_elems + 255) / 256;
   hipLaunchKernelGGL(mel_resample_batch_k, dim3((unsigned)(g > 64 ? 64 : g), (unsigned)R), dim3(256), 0, s, d, rows_dev, bp, S,
-                     (const double*)w.logmel, (const double*)w.energy);
+                     (const double*)w.feat);
   ZLAUNCH_CHECK("mel_resample_batch");
   t_mel_launches += 2;
   t_mel_form = 4;
