@@ -778,10 +778,12 @@ _DEC_NETS, _DEC_CASES = {}, {}
 
 def decoder_net(tag):
     """(cached; callers move a deepcopy to the device) the seeded decoders of the statistics tests: "main" (build_nets), "film" (rnn_cond="film", the construction of
-    test_gpu_parity._variant_nets), "h512" (nhidden = 512)"""
+    test_gpu_parity._variant_nets), "h512" (nhidden = 512); the tags of DEC_DIM_NETS: decoders at other dimensions (below)"""
     if tag not in _DEC_NETS:
         if tag == "main":
             _DEC_NETS[tag] = build_nets()[1]
+        elif tag in DEC_DIM_NETS:
+            _DEC_NETS[tag] = _decoder_dim_net(tag)
         else:
             assert tag in ("film", "h512"), tag
             torch.manual_seed(4321 if tag == "film" else 77)
@@ -804,11 +806,10 @@ def decoder_case(B, T):
     return _DEC_CASES[(B, T)]
 
 
-def decoder_weighting(name, B, T):
+def decoder_weighting(name, B, T, J=synth.NJ):
     """weights of the differentiated sum over the 8 outputs.  "all": seeded normal weights on everything; "root": on root_pos and
     root_rot of the LAST frame only -- every gradient then arrives through the root adjoint carried over T - 1 steps and through the
     gaze direction."""
-    J = synth.NJ
     shapes = [(B, T, 3), (B, T, 4), (B, T, 3), (B, T, 3), (B, T, J, 3), (B, T, J, 2, 3), (B, T, J, 3), (B, T, J, 3)]
     gen = torch.Generator().manual_seed(11)
     wts = [torch.randn(*sh, generator=gen) for sh in shapes]
@@ -1010,6 +1011,249 @@ DEC_INFER_KINDS = ("tied", "untied", "still", "brisk", "spin", "zero")
 def decoder_shapes():
     """every (decoder, B, T) the GPU file runs"""
     return sorted({c[1:] for c in DEC_TRAIN_CASES} | {("main", B, T) for _, B, T in DEC_INFER_CASES})
+
+
+# ----------------------------------------------------------------------------- the decoder at other dimensions
+# (tests/test_gpu_decoder_dims.py on the device, tests/test_decoder_dims_oracle_cpu.py on the CPU.)  Everything above builds ONE
+# family: synth.NJ = 75 joints (PI = 1134, PO = 1131), SP = ST = 64, H in {512, 768, 1024}.  PI, PO, SP, ST and H are free
+# dimensions of the C ABI; the rigs and widths below reach the tile edges of each of them and both sides of every limit of the
+# four *_supported predicates.
+# rig: (J joints, SP speech columns, ST style columns); PO = 6 + 15 J, PI = PO + 3, XD = PI + SP + ST
+DEC_DIM_RIGS = {"j24": (24, 64, 64),           # KBX = 32: the per-frame operand of the rollout (201 blocks) is wider than 64 + KBX + 64
+                "j6": (6, 32, 16),             # PO = 96 (a multiple of 16), XD = 147 (16 * 9 + 3), KBC = 3
+                "j1": (1, 8, 4),               # PO = 21 (the fast path needs 16), KBC = 1
+                "j76": (76, 64, 64),           # nTPO = 72: the widest rig all three persistent kernels accept
+                "j77": (77, 64, 64),           # nTPO = 73: the BPTT sweep and the decode kernel (2 H + XD = 3340) decline
+                "j86": (86, 64, 64),           # PO = 1296 > 1280: every persistent kernel declines
+                "wide-cond": (24, 100, 64)}    # SP + ST = 164 > 128, KBC = 11: the rollout and the decode kernel decline
+# decoder tag: (rig, H, rnn_cond)
+DEC_DIM_NETS = {"j24": ("j24", 1024, "normal"), "j6": ("j6", 1024, "normal"), "j1": ("j1", 1024, "normal"),
+                "j76": ("j76", 1024, "normal"), "j77": ("j77", 1024, "normal"), "j86": ("j86", 1024, "normal"),
+                "wide-cond": ("wide-cond", 1024, "normal"),
+                "h16": ("j6", 16, "normal"),   # nT5 = 4, last GRU unit tile: 1 unit
+                "h48": ("j6", 48, "normal"),   # nT5 = 10, last tile: 3 units
+                "h80": ("j6", 80, "normal"),   # nT5 = 16, last tile: a full 5
+                "film-j24-h48": ("j24", 48, "film"),
+                "h24-generic": ("j6", 24, "normal")}      # H % 16 != 0: the fast path declines
+
+
+def decoder_dims(net):
+    """-> dict(J, SP, ST, PO, PI, XD, H, film) of a tag of DEC_DIM_NETS (XD: the step input, without the style under FiLM)"""
+    rig, Hn, cond = DEC_DIM_NETS[net]
+    J, SP, ST = DEC_DIM_RIGS[rig]
+    PO = 6 + 15 * J
+    film = cond == "film"
+    return dict(rig=rig, J=J, SP=SP, ST=ST, PO=PO, PI=PO + 3, XD=PO + 3 + SP + (0 if film else ST), H=Hn, film=film)
+
+
+def decoder_rig(J, SP, ST, kind="untied", dtype=torch.float32, device="cpu"):
+    """-> (PI, PO, dict(in_mean, in_std, out_mean, out_std)) of a J-joint rig, seeded by (J, SP, ST): the construction of
+    synth.make_stats / decoder_stats at another width.  tied: out_mean == in_mean[:PO]; untied: out_mean ~ N(0, 1) from its own
+    generator and out_std[3:6] = (0.8, 1.1, 0.6).  out_std keeps PO // 28 exact zeros behind the six root columns (constant
+    channels; 40 of 1131 at J = 75)."""
+    assert kind in ("tied", "untied"), kind
+    PO = 6 + 15 * J
+    PI = PO + 3
+    rng = np.random.default_rng(1000 * J + 10 * SP + ST)
+    im = rng.normal(0.0, 1.0, PI).astype(np.float32)
+    isd = rng.uniform(0.5, 2.0, PI).astype(np.float32)
+    om = im[:PO].copy()
+    osd = rng.uniform(0.3, 1.5, PO).astype(np.float32)
+    osd[6 + rng.choice(PO - 6, PO // 28, replace=False)] = 0.0
+    if kind == "untied":
+        om = np.random.default_rng(2024 + J).standard_normal(PO).astype(np.float32)
+        osd[3:6] = (0.8, 1.1, 0.6)
+    t = lambda a: torch.as_tensor(a).to(dtype).to(device)  # noqa: E731
+    return PI, PO, dict(in_mean=t(im), in_std=t(isd), out_mean=t(om), out_std=t(osd))
+
+
+def decoder_dim_stats(net, kind, dtype=torch.float32, device="cpu"):
+    d = decoder_dims(net)
+    return decoder_rig(d["J"], d["SP"], d["ST"], kind, dtype, device)[2]
+
+
+def _decoder_dim_net(tag):
+    d = decoder_dims(tag)
+    torch.manual_seed(5000 + sorted(DEC_DIM_NETS).index(tag))
+    kw = dict(rnn_cond="film") if d["film"] else {}
+    return modules.Decoder(d["PI"], d["PO"], d["SP"], d["ST"], d["H"], 2, **kw)
+
+
+_DEC_DIM_CASES = {}
+
+
+def _random_rotations(rng, n):
+    """n rotation matrices [n, 3, 3] from uniformly random unit quaternions"""
+    q = rng.standard_normal((n, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    w, x, y, z = q.T
+    return np.stack([np.stack([1 - 2 * (y * y + z * z), 2 * (x * y - w * z), 2 * (x * z + w * y)], 1),
+                     np.stack([2 * (x * y + w * z), 1 - 2 * (x * x + z * z), 2 * (y * z - w * x)], 1),
+                     np.stack([2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)], 1)], 1)
+
+
+def decoder_dim_case(rig, B, T):
+    """float32 inputs of a [B, T] rollout on a rig of DEC_DIM_RIGS, the dict of decoder_case: unit root quaternions (general, not
+    yaw only), ltxy = the first two axes of a random rotation per joint (orthonormal rows), velocities as finite differences of a
+    smooth track (the scales of synth.make_clip), a gaze target 180 units away, speech / style ~ 0.5 N(0, 1); cached, read-only"""
+    key = (rig, B, T)
+    if key in _DEC_DIM_CASES:
+        return _DEC_DIM_CASES[key]
+    J, SP, ST = DEC_DIM_RIGS[rig]
+    rng = np.random.default_rng(31 * J + 7 * B + T)
+    f = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32))  # noqa: E731
+    q = rng.standard_normal((B, 4))
+    q /= np.linalg.norm(q, axis=1, keepdims=True)
+    track = np.stack([synth._smooth(rng, 2, 3 + 3 * J, 0.05) for _ in range(B)])        # [B, 2, 3 + 3 J]: root and joint positions
+    vel = (track[:, 1] - track[:, 0]) / synth.DT
+    hel = np.stack([synth._smooth(rng, 2, 3 + 3 * J, 0.02) for _ in range(B)])          # helical angles: their difference is vrt
+    vrt = (hel[:, 1] - hel[:, 0]) / synth.DT
+    R = _random_rotations(rng, B * J).reshape(B, J, 3, 3)
+    ltxy = np.stack([R[..., :, 0], R[..., :, 1]], axis=2)                                # [B, J, 2, 3]
+    lpos = rng.normal(0, 8.0, (1, J, 3)) + track[:, 0, 3:].reshape(B, J, 3)
+    fp = [f(rng.standard_normal((B, 3)) * 20.0), f(q), f(vel[:, :3] * 30), f(vrt[:, :3]), f(lpos), f(ltxy),
+          f(vel[:, 3:].reshape(B, J, 3)), f(vrt[:, 3:].reshape(B, J, 3))]
+    gaze = f(np.tile(np.array([[[10.0, 150.0, 100.0]]]), (B, T, 1)) + rng.normal(0, 1.0, (B, 1, 3)))
+    gen = torch.Generator().manual_seed(4 + J)
+    speech, style = torch.randn(B, T, SP, generator=gen) * 0.5, torch.randn(B, T, ST, generator=gen) * 0.5
+    _DEC_DIM_CASES[key] = dict(fp=fp, gaze=gaze, speech=speech, style=style, B=B, T=T, J=J)
+    return _DEC_DIM_CASES[key]
+
+
+def decoder_dim_oracle(net, B, T, kind, weighting=None, dtype=torch.float64, de=None):
+    """decoder_oracle of a DEC_DIM_NETS decoder (or `de`, a modified copy of it) on its rig's case and statistics"""
+    d = decoder_dims(net)
+    wts = None if weighting is None else decoder_weighting(weighting, B, T, d["J"])
+    return decoder_oracle(de or decoder_net(net), decoder_dim_case(d["rig"], B, T), decoder_dim_stats(net, kind), wts, dtype)
+
+
+_DEC_DIM_ORACLE = {}
+
+
+def decoder_dim_oracle_cached(net, B, T, kind, weighting=None, dtype=torch.float64):
+    """the float64 (or float32) oracle of a case, computed once per process and left unchanged"""
+    key = (net, B, T, kind, weighting, dtype)
+    if key not in _DEC_DIM_ORACLE:
+        _DEC_DIM_ORACLE[key] = decoder_dim_oracle(net, B, T, kind, weighting, dtype)
+    return _DEC_DIM_ORACLE[key]
+
+
+def decoder_dim_limits(net):
+    """Which kernels take a decoder's dimensions, from the limits as the kernel files state them (never by asking the library;
+    tests/test_decoder_dims_oracle_cpu.py holds the same table written by hand).  Batch and frame counts are the case's business:
+    every case here has B <= 64 and T >= 4.
+      fast    decoder_fast.hip  dec_fast_supported:        H % 16 == 0, PI == PO + 3, PO >= 16
+      tp      train_persistent.hip  dec_tp_supported:      normal, H == 1024, 16 <= PO <= 1280 (5 x 256 columns), SP + ST <= 128,
+                                                           1 <= KBC <= 8; on the fast path only
+      bp      train_bwd_persistent.hip  dec_bp_supported:  normal, H == 1024, PO >= 16, (PO + 15) / 16 <= 72, XD <= 2048; fast path only
+      dp      decode_persistent.hip  dec_persistent_supported:  normal, H == 1024, 2 H + XD <= 3328 (26 x 128), SP + ST <= 128,
+                                                           6 <= PO <= 1280"""
+    d = decoder_dims(net)
+    PO, XD, Hn, C = d["PO"], d["XD"], d["H"], d["SP"] + d["ST"]
+    KBC = (C + 15) // 16
+    big = Hn == 1024 and not d["film"]
+    fast = Hn % 16 == 0 and d["PI"] == PO + 3 and PO >= 16
+    return dict(fast=fast,
+                tp=fast and big and 16 <= PO <= 1280 and C <= 128 and 1 <= KBC <= 8,
+                bp=fast and big and PO >= 16 and (PO + 15) // 16 <= 72 and XD <= 2048,
+                dp=big and 2 * Hn + XD <= 3328 and C <= 128 and 6 <= PO <= 1280)
+
+
+# path -> library switches (the defaults otherwise) and which persistent kernels it asks for; "default" / "b1-default": no switch,
+# whatever the limits give
+DEC_DIM_TRAIN_OPTIONS = {"generic": dict(decoder_fast=0), "stage": dict(train_persistent=0, bwd_persistent=0),
+                         "tp16-tiles4=0": dict(tp_tiles4=0, bwd_persistent=0), "tp16-tiles4=1": dict(bwd_persistent=0),
+                         "tp4": dict(bwd_persistent=0), "dual": dict(tp_dual=1, bwd_persistent=0), "bptt": {}, "default": {}}
+DEC_DIM_INFER_OPTIONS = {"ring": {}, "b1-persistent": {}, "b1-default": {}, "b1-stage-gemv": dict(persistent=0),
+                         "b1-stage-mfma": dict(persistent=0, stage_variant=1024), "batch-chunk4": {}}
+_DEC_DIM_WANTS = {"generic": (), "stage": (), "tp16-tiles4=0": ("tp",), "tp16-tiles4=1": ("tp",), "tp4": ("tp",), "dual": ("tp",),
+                  "bptt": ("tp", "bp"), "default": ("tp", "bp"), "ring": (), "b1-persistent": ("dp",), "b1-default": ("dp",),
+                  "b1-stage-gemv": (), "b1-stage-mfma": (), "batch-chunk4": ("tp",)}
+_DEC_DIM_STATE = dict(dp=0, tp=1, bp=2)        # the index of zeggs_persistent_state
+
+
+def decoder_dim_ran(path, net):
+    """the persistent kernels (zeggs_persistent_state indices) that must have run for a path on a decoder: those the path asks for
+    and the limits grant"""
+    lim = decoder_dim_limits(net)
+    return tuple(sorted(_DEC_DIM_STATE[k] for k in _DEC_DIM_WANTS[path] if lim[k]))
+
+
+def _dim_train(net, *cases):
+    return [(p, net, B, T, k) for p, B, T, k in cases]
+
+
+_U, _TI = "untied", "tied"
+_PER_WIDTH_TRAIN = (("generic", 2, 6, _U), ("stage", 5, 6, _U), ("stage", 33, 4, _U))
+_PER_WIDTH_INFER = (("ring", 3, 7, _U), ("b1-stage-gemv", 1, 6, _U), ("b1-stage-mfma", 1, 6, _U))
+# (path, decoder, B, T, statistics kind); weighting `all` throughout.  Shapes: the smallest that reach each path (DEC_TRAIN_CASES).
+DEC_DIM_TRAIN_CASES = tuple(
+    _dim_train("j24", ("stage", 5, 6, _U), ("tp16-tiles4=0", 5, 6, _U), ("tp16-tiles4=1", 5, 6, _U), ("tp4", 17, 5, _U),
+               ("dual", 17, 5, _U), ("bptt", 5, 6, _U), ("bptt", 17, 5, _U), ("bptt", 40, 4, _U), ("bptt", 5, 6, _TI)) +
+    _dim_train("j6", ("stage", 5, 6, _U), ("tp16-tiles4=0", 5, 6, _U), ("tp16-tiles4=1", 5, 6, _U), ("tp4", 17, 5, _U),
+               ("dual", 17, 5, _U), ("bptt", 40, 4, _U), ("bptt", 5, 6, _TI)) +
+    _dim_train("j1", ("stage", 5, 6, _U), ("tp16-tiles4=1", 5, 6, _U), ("bptt", 5, 6, _U), ("bptt", 5, 6, _TI)) +
+    _dim_train("j76", ("bptt", 5, 6, _U), ("bptt", 5, 6, _TI)) +
+    _dim_train("j77", ("default", 5, 6, _U), ("default", 5, 6, _TI)) +         # the rollout runs, the BPTT sweep declines
+    _dim_train("j86", ("default", 5, 4, _U), ("default", 5, 4, _TI)) +         # both decline
+    _dim_train("wide-cond", ("stage", 5, 6, _U), ("stage", 5, 6, _TI),
+               ("default", 5, 6, _U)) +          # the rollout declines; the BPTT sweep has no limit on SP + ST and runs
+    _dim_train("h16", *_PER_WIDTH_TRAIN) + _dim_train("h48", *_PER_WIDTH_TRAIN) + _dim_train("h80", *_PER_WIDTH_TRAIN) +
+    _dim_train("film-j24-h48", ("default", 5, 6, _U)) +
+    _dim_train("h24-generic", ("default", 2, 6, _U)))
+_B1 = (("b1-persistent", 1, 6, _U), ("b1-stage-gemv", 1, 6, _U), ("b1-stage-mfma", 1, 6, _U), ("ring", 3, 7, _U),
+       ("batch-chunk4", 3, 9, _U))
+DEC_DIM_INFER_CASES = tuple(
+    _dim_train("j24", *_B1) + _dim_train("j6", *_B1) + _dim_train("j1", ("b1-persistent", 1, 6, _U)) +
+    _dim_train("j76", ("b1-persistent", 1, 6, _U)) + _dim_train("j77", ("b1-default", 1, 6, _U)) +
+    _dim_train("j86", ("b1-default", 1, 6, _U)) + _dim_train("wide-cond", ("ring", 3, 7, _U), ("b1-default", 1, 6, _U)) +
+    _dim_train("h16", *_PER_WIDTH_INFER) + _dim_train("h48", *_PER_WIDTH_INFER) + _dim_train("h80", *_PER_WIDTH_INFER) +
+    _dim_train("film-j24-h48", ("ring", 3, 7, _U)))
+# Bounds: DEC_OUT_BOUND / DEC_GRAD_BOUND through assert_decoder_outputs / assert_decoder_grads, as tests/test_gpu_decoder_stats.py.
+# A case whose FLOAT32 ORACLE is not within a quarter of them would get 4 x that oracle's own distance here, with the measured value
+# beside it; none does (tests/test_decoder_dims_oracle_cpu.py::test_float32_oracle_within_a_quarter_of_every_bound).
+
+
+def decoder_dim_shapes(training=None):
+    """every (decoder, B, T, kind) the GPU file runs: training cases, inference cases, or both"""
+    tr = {c[1:] for c in DEC_DIM_TRAIN_CASES}
+    inf = {c[1:] for c in DEC_DIM_INFER_CASES}
+    return sorted(tr if training is True else inf if training is False else tr | inf)
+
+
+def decoder_dim_edges(net):
+    """the last (partial) tile of each tiled dimension of a decoder -> dict(PO=(lo, hi) rows of the output layer, XD=(lo, hi)
+    columns of the step input, H=(lo, hi) GRU units): 16-wide tiles of PO and XD, 5-unit tiles of H (nT5 = (H + 4) / 5)"""
+    d = decoder_dims(net)
+    last16 = lambda n: (16 * ((n + 15) // 16 - 1), n)  # noqa: E731
+    return dict(PO=last16(d["PO"]), XD=last16(d["XD"]), H=(5 * ((d["H"] + 4) // 5 - 1), d["H"]))
+
+
+def decoder_edge_zeroed(net, edge):
+    """a copy of the decoder with the weights of one edge of decoder_dim_edges zeroed: PO -- those rows of the output layer (weight
+    and bias); XD -- those columns of layer0 and of GRU layer 0's input weights (behind its H hid columns); H -- those units: their
+    rows (gates r, z, n) of both GRU layers' weights and biases"""
+    import copy
+    de = copy.deepcopy(decoder_net(net))
+    d = decoder_dims(net)
+    lo, hi = decoder_dim_edges(net)[edge]
+    r, Hn = de.recurrent_decoder, d["H"]
+    sd_ = dict(r.named_parameters())
+    with torch.no_grad():
+        if edge == "PO":
+            last = "layer3" if d["film"] else "layer2"
+            sd_[last + ".weight"][lo:hi] = 0.0
+            sd_[last + ".bias"][lo:hi] = 0.0
+        elif edge == "XD":
+            sd_["layer0.weight"][:, lo:hi] = 0.0
+            sd_["layer1.weight_ih_l0"][:, Hn + lo:Hn + hi] = 0.0
+        else:
+            assert edge == "H", edge
+            for k, v in sd_.items():
+                if k.startswith("layer1."):
+                    for gate in range(3):
+                        v[gate * Hn + lo:gate * Hn + hi] = 0.0
+    return de
 
 
 # ---- RAdam (tests/test_radam_oracle_cpu.py measures and proves on the CPU, tests/test_gpu_radam.py runs the device).

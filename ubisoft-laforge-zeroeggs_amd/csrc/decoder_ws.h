@@ -51,6 +51,15 @@ struct DecWs {
 };
 
 inline int round4(int x) { return (x + 3) / 4 * 4; }
+// GRU layer 0 operand of one step of the persistent rollout, in k-blocks (layout and reasons: tp_common.h): [hid_t (64) | gaze (1) |
+// speech / style (TKC) | h0_{t-1} (64) | h1_{t-1} (64)].  The pose columns are folded onto h1_{t-1}, so the frame does NOT depend on
+// XD: every launch that touches G0xf walks TKB0 blocks per frame, and both carves below size it by tp_g0_blocks.
+namespace zeggs_tp {
+constexpr int TKC = 8, TFR0 = 65, TKH0 = TFR0 + TKC, TKH1 = TKH0 + 64, TKB0 = TKH1 + 64;      // 65, 73, 137, 201
+// blocks per frame of G0xf: what the sweep walks.  Rigs with KBX > 73 (XD > 1168) keep the 64 + KBX + 64 blocks of the layout that
+// had the pose columns as an operand: their workspace sizes are pinned (tests/test_abi.py) and callers have sized buffers by them.
+inline long tp_g0_blocks(int KBX) { return 64 + KBX + 64 > TKB0 ? 64 + KBX + 64 : TKB0; }
+}
 constexpr int FILM_GB = 32;     // frames per block of inference-time FiLM modulation vectors
 
 inline DecWs carve_dec(const ZeggsDecDims& d, int training, Arena& a) {
@@ -138,7 +147,7 @@ inline DecWs carve_dec(const ZeggsDecDims& d, int training, Arena& a) {
     w.xf_bytes_bwd = a.off - align_up(o0, 256);
     w.dXa = a.f(B * (long)w.XD);
     if (d.H == 1024 && d.B <= 64 && !d.film) {
-      const long KB0 = 64 + w.KBX + 64, KB3 = 64 + w.KBC;
+      const long KB0 = zeggs_tp::tp_g0_blocks(w.KBX), KB3 = 64 + w.KBC;
       w.tp_w0 = a.f(256L * 8 * 26 * BLK); w.tp_w1 = a.f(256L * 8 * 16 * BLK); w.tp_w3 = a.f(256L * 8 * 9 * BLK);   // [wg][wave][block]
       w.G0xf = a.f(T * KB0 * XB); w.G1xf = a.f(T * 128 * XB); w.G3xf = a.f(T * KB3 * XB);
       w.tp_n0s = a.f(3 * H * (long)w.POL); w.tp_n0 = a.f(3 * H * H); w.tp_cv0 = a.f(3 * H); w.tp_p1x = a.f(B * 3 * H);
@@ -161,7 +170,7 @@ inline DecWs carve_dec_batch(const ZeggsDecDims& d, Arena& a) {
   DecWs w = carve_dec(d, 0, a);
   if (d.H == 1024 && d.B <= 64 && !d.film) {
     const long BLK = 256, T = d.T, H = d.H, XB = 256L * w.NB;
-    const long KB0 = 64 + w.KBX + 64 > 201 ? 64 + w.KBX + 64 : 201, KB3 = 64 + w.KBC;      // (the sweep walks zeggs_tp::TKB0 = 201 blocks)
+    const long KB0 = zeggs_tp::tp_g0_blocks(w.KBX), KB3 = 64 + w.KBC;
     w.tp_w0 = a.f(256L * 8 * 26 * BLK); w.tp_w1 = a.f(256L * 8 * 16 * BLK); w.tp_w3 = a.f(256L * 8 * 9 * BLK);   // [wg][wave][block]
     w.tp_n0s = a.f(3 * H * (long)w.POL); w.tp_n0 = a.f(3 * H * H); w.tp_cv0 = a.f(3 * H); w.tp_p1x = a.f((long)d.B * 3 * H);
     w.tp_cnt = (unsigned*)a.f(8192);

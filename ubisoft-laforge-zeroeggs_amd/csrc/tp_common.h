@@ -22,7 +22,7 @@ constexpr int TJ0 = TNO0 + TNF0, TJ1 = TNO1 + TNF1, TJ3 = TNO3 + TNF3;
 // first pose instead: its product comes from a small prologue GEMM and the h1 slot of that step stays zero.)
 // Only k-blocks [0, TFR0) are fresh; the old ones are ordered [cond | h0 | h1]: h0_{t-1} is two hand-offs old when the previous
 // output stage waits, h1_{t-1} one.
-constexpr int TKC = 8, TFR0 = 65, TKH0 = TFR0 + TKC, TKH1 = TKH0 + 64, TKB0 = TKH1 + 64;      // 65, 73, 137, 201
+// TKC, TFR0, TKH0, TKH1, TKB0 (= 8, 65, 73, 137, 201 k-blocks): decoder_ws.h, where carve_dec sizes the operand buffer by them
 // ... of which only the 64 blocks of hid_t are walked: the gaze block would give ONE wave a ninth fresh block (every workgroup
 // waits for it: +1/8 on the matrix-core time of the phase's critical part) for three columns -- the gate threads add them instead
 // (9 FMAs each; every workgroup has the normalised gaze direction in LDS anyway, from its own root integration).  The block keeps
