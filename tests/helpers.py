@@ -1910,3 +1910,229 @@ def gemm_floor(case, variant="aligned"):
     rows = gemm_sample_rows(case) if case["sample"] else None
     ref, den = gemm_oracle(case, torch.float64, variant, rows=rows), gemm_denominator(case, variant, rows)
     return gemm_error(gemm_oracle(case, torch.float32, variant, rows=rows), ref, den)[0]
+
+
+# ----------------------------------------------------------------------------- live serving at other dimensions
+# (tests/test_gpu_live_dims.py on the device, tests/test_live_encoder_oracle_cpu.py on the host)
+# The incremental speech encoder (csrc/live.hip) takes any F, any odd KW and any H, O that are multiples of 4 dividing 512; FRP =
+# 512 / O output frames and FA = 512 / H feature rows go through one pass of its workgroup.  `bs`: the largest burst in steady
+# state; the ring holds D = KW - 1 + bs frames, the least that admits it; `long`: the longest row, > 2 D frames.
+LIVE_KERNEL_CASES = (
+    dict(id="r64-81-64-64-31", F=81, H=64, O=64, KW=31, R=64, bs=23, long=150),     # every row active, 64 lengths
+    dict(id="81-128-32-31", F=81, H=128, O=32, KW=31, R=3, bs=17, long=150),        # H != O, FRP = 16, FA = 4
+    dict(id="81-32-128-31", F=81, H=32, O=128, KW=31, R=3, bs=23, long=150),        # FRP = 4, FA = 16
+    dict(id="20-512-64-3", F=20, H=512, O=64, KW=3, R=3, bs=9, long=60),            # FA = 1
+    dict(id="20-16-512-5", F=20, H=16, O=512, KW=5, R=3, bs=7, long=40),            # FRP = 1
+    dict(id="3-4-4-1", F=3, H=4, O=4, KW=1, R=3, bs=129, long=600),                 # KW = 1, FRP = FA = 128
+    dict(id="81-256-16-29", F=81, H=256, O=16, KW=29, R=3, bs=33, long=140),        # 64 144 bytes of LDS
+)
+LIVE_LDS_REFUSED = (81, 256, 16, 31)                                                # 66 192 bytes
+
+
+def live_case_depth(case):
+    return case["KW"] - 1 + case["bs"]
+
+
+def live_case_lens(case):
+    """row lengths.  R = 64: 1, 2, half, half + 1, KW - 1, KW and 58 other lengths up to case["long"], all different; R = 3: one of
+    those six (by the case's position in the table), a middle row, the long row"""
+    KW, half = case["KW"], (case["KW"] - 1) // 2
+    short = sorted({n for n in (1, 2, half, half + 1, KW - 1, KW) if n >= 1})
+    if case["R"] == 3:
+        i = [c["id"] for c in LIVE_KERNEL_CASES].index(case["id"])
+        FRP = 512 // case["O"]        # the middle row: long enough for the bursts 1, FRP - 1, FRP, FRP + 1 and bs, whole
+        return [short[i % len(short)], max(live_case_depth(case) * 3 // 2 + 1, 3 * FRP + case["bs"] + 6), case["long"]]
+    rng = np.random.default_rng(64)
+    rest = [int(n) for n in rng.permutation(np.arange(3, case["long"])) if int(n) not in short][:case["R"] - len(short) - 1]
+    lens = short + rest + [case["long"]]
+    order = rng.permutation(len(lens))
+    return [lens[i] for i in order]
+
+
+def live_schedule(case):
+    """The seeded burst schedule of a case -> dict(lens, D, feat_ld, out_ld, calls); calls[c][r] = (n_ring, k0, last, n_new,
+    n_out, feat_off), the record of row r in launch c ((0, 0, -1, 0, 0, 0): the row takes no part -- not started yet or finished).
+
+    Every row walks the same pattern of (burst, output policy) from its own starting point, begins at its own call, and what the
+    pattern asks is cut to what the ring admits: a burst never overwrites a frame that a pending output still reads.  Bursts: 1,
+    FRP - 1, FRP, FRP + 1, bs and D (whole, at a row's start: the largest the ring admits; cut to bs later); policies: all that is
+    ready (-1), none (0: ring fill only, and the call after it brings no frames: output from the ring alone), at most n (> 0).
+    Rows of at most KW frames arrive and end in ONE call.  feat_off = (call + row) % 4, and feat_ld / out_ld are the largest
+    feat_off + n_new / n_out of the schedule: both limits are reached."""
+    KW, R, D = case["KW"], case["R"], live_case_depth(case)
+    half, FRP, bs = (KW - 1) // 2, 512 // case["O"], case["bs"]
+    lens = live_case_lens(case)
+    pattern = [(1, -1), (FRP - 1, -1), (FRP, -1), (FRP + 1, -1), (bs, -1), (2, 0), (0, -1), (D, -1), (3, 0), (0, 2), (bs, -1),
+               (0, -1), (1, -1), (FRP + 1, 0), (0, -1), (2 * FRP + 1, -1)]
+    rng = np.random.default_rng(1000 + len(case["id"]) + case["F"] + case["H"] + case["O"] + KW)
+    start = [int(rng.integers(0, 6)) for _ in range(R)]
+    phase = [7 if n > 2 * D and r % 2 == 0 else int(rng.integers(0, len(pattern))) for r, n in enumerate(lens)]   # 7: D at the start
+    if R == 3:
+        phase[1] = 0
+    n_ring, done, step = [0] * R, [0] * R, [0] * R
+    calls, c = [], 0
+    idle = (0, 0, -1, 0, 0, 0)
+    while any(done[r] < lens[r] for r in range(R)):
+        recs = []
+        for r, n in enumerate(lens):
+            if c < start[r] or done[r] == n:
+                recs.append(idle)
+                continue
+            b, pol = pattern[(phase[r] + step[r]) % len(pattern)]
+            step[r] += 1
+            if n <= KW:
+                b, pol = n, -1                                           # delivered and ended in one call: every tap replicates
+            room = D - n_ring[r] + max(0, done[r] - half)                # frames that fit without overwriting a frame still to be read
+            n_new = max(0, min(b, n - n_ring[r], D, room))
+            total = n_ring[r] + n_new
+            ready = (n if total == n else max(done[r], total - half)) - done[r]
+            n_out = ready if pol < 0 else min(pol, ready)
+            if n_new == 0 and n_out == 0:
+                n_out = ready
+            if n_new == 0 and n_out == 0:                                # nothing pending: room >= D - KW + 1 >= 1
+                n_new = 1
+                total = n_ring[r] + 1
+                n_out = (n if total == n else max(done[r], total - half)) - done[r]
+            recs.append((n_ring[r], done[r], n - 1 if total == n else -1, n_new, n_out, (c + r) % 4))
+            n_ring[r], done[r] = total, done[r] + n_out
+        calls.append(recs)
+        c += 1
+        assert c < 4000
+    return dict(lens=lens, D=D, calls=calls, feat_ld=max(rec[5] + rec[3] for recs in calls for rec in recs),
+                out_ld=max(rec[4] for recs in calls for rec in recs))
+
+
+def live_case_nets(case):
+    """seeded Conv1d(F, H, 1), Conv1d(H, O, KW), Linear(O, O) on a plain namespace: what ops.LiveSpeech reads"""
+    import types
+    torch.manual_seed(SEED + case["F"] + case["H"] + case["O"] + case["KW"])
+    nn = torch.nn
+    return types.SimpleNamespace(layer0=nn.Conv1d(case["F"], case["H"], 1), layer1=nn.Conv1d(case["H"], case["O"], case["KW"]),
+                                 layer2=nn.Linear(case["O"], case["O"]))
+
+
+def live_case_weights(net):
+    return {f"layer{i}.{k}": getattr(getattr(net, f"layer{i}"), k).detach() for i in range(3) for k in ("weight", "bias")}
+
+
+_LIVE_DATA = {}
+
+
+def live_case_data(case):
+    """-> dict(net, mean, std [F] float32, feats: per row [n, F] float32 un-normalised, sched, ref: per row the float64 whole-row
+    oracle [n, O]), computed once per case.  mean ~ N(0, 1) / 4, std in [0.5, 2]: (x - mean) / std in float32 loses about one unit
+    of roundoff of |x| / std <= 4.5, nothing to cancellation."""
+    if case["id"] not in _LIVE_DATA:
+        from oracle import nets as onets
+        net, sched = live_case_nets(case), live_schedule(case)
+        rng = np.random.default_rng(SEED + 1)
+        mean = torch.as_tensor((rng.standard_normal(case["F"]) / 4).astype(np.float32))
+        std = torch.as_tensor(rng.uniform(0.5, 2.0, case["F"]).astype(np.float32))
+        feats = [torch.as_tensor(rng.standard_normal((n, case["F"])).astype(np.float32)) * std + mean for n in sched["lens"]]
+        w = {k: v.double() for k, v in live_case_weights(net).items()}
+        with torch.no_grad():
+            ref = [onets.speech_encoder(w, ((f.double() - mean.double()) / std.double())[None])[0] for f in feats]
+        _LIVE_DATA[case["id"]] = dict(net=net, mean=mean, std=std, feats=feats, sched=sched, ref=ref)
+    return _LIVE_DATA[case["id"]]
+
+
+def live_feat_block(data, c):
+    """the sliding feature block of launch c, [R, feat_ld, F]: row r's new frames n_ring .. n_ring + n_new - 1 from row feat_off
+    on, 1e3 everywhere else (a frame read from the wrong place is far outside the bound)"""
+    s = data["sched"]
+    blk = torch.full((len(s["lens"]), s["feat_ld"], data["mean"].numel()), 1e3)
+    for r, (n_ring, _, _, n_new, _, off) in enumerate(s["calls"][c]):
+        blk[r, off:off + n_new] = data["feats"][r][n_ring:n_ring + n_new]
+    return blk
+
+
+# ---- the yardstick of tests/test_gpu_live.py, shared with tests/test_gpu_live_dims.py: the offline rollout and its bound
+LIVE_DEV = "cuda:0"
+LIVE_KEYS = ("pose", "rpos", "rrot")
+LIVE_CONF = dict(pre_emphasis=False, pre_emph_coeff=0.97, centered=True, real_amplitude=True, normalize_mel_bins=True,
+                 normalize_range=True, min_clipping=1e-5, sampling_rate=16000, mel_fmin=20, mel_fmax=7600,
+                 n_mel_channels=80, filter_length=800, hop_length=200, resample_method="linear", normalize_loudness=False)
+_LIVE_CACHE = {}
+
+
+def _live_cached(key, make):
+    if key not in _LIVE_CACHE:
+        _LIVE_CACHE[key] = make()
+    return _LIVE_CACHE[key]
+
+
+def live_nets():
+    def make():
+        se, de, _ = build_nets()
+        return se.to(LIVE_DEV).eval(), de.to(LIVE_DEV).eval()
+    return _live_cached("nets", make)
+
+
+def live_stats():
+    return _live_cached("stats", lambda: {k: torch.as_tensor(np.asarray(v), dtype=torch.float32, device=LIVE_DEV)
+                                          for k, v in synth.make_stats().items()})
+
+
+def live_first(seed):
+    from zeggs import anim
+    return _live_cached(("first", seed), lambda: anim.preprocess_animation(synth.make_bvh_clip(8, seed=seed), LIVE_DEV))
+
+
+def live_wav(nsamp, seed):
+    return _live_cached(("wav", nsamp, seed), lambda: synth.synth_wav(nsamp, seed=seed).astype(np.float32) / 32768.0)
+
+
+def live_style(seed):
+    return torch.randn(1, 64, device=LIVE_DEV, generator=torch.Generator(LIVE_DEV).manual_seed(seed)) * 0.5
+
+
+def live_offline(wav, first, style_rows):
+    """the offline path: style_rows [1, 64] (constant) or [n_frames, 64] -> (pose, rpos, rrot) [n_frames, .]"""
+    from zeggs import audio, ops
+    se, de = live_nets()
+    st = live_stats()
+    n_frames = audio.n_anim_frames(len(wav))
+    feats = torch.as_tensor(audio.preprocess_audio(wav, 60, n_frames, LIVE_CONF, ["mel_spec", "energy"]), device=LIVE_DEV)
+    with torch.no_grad():
+        sp = se(((feats[None] - st["audio_input_mean"]) / st["audio_input_std"]).contiguous())
+        f32 = lambda a: a[0:1].to(torch.float32).contiguous()  # noqa: E731
+        rp, rr, rv, rw, lp, _, lt, lv, lw = first[:9]
+        pose0 = torch.cat([f32(x).reshape(1, -1) for x in (rv, rw, lp, lt, lv, lw)], dim=1)
+        gaze = f32(first[14]).repeat(n_frames, 1)[None].contiguous()
+        style = style_rows if style_rows.shape[0] == n_frames else style_rows.repeat(n_frames, 1)
+        ref = ops.decoder_core(de, pose0, f32(rp), f32(rr), gaze, sp, style[None].contiguous(), st["anim_input_mean"],
+                               st["anim_input_std"], st["anim_output_mean"], st["anim_output_std"], synth.DT)
+    return tuple(r[0] for r in ref)
+
+
+def live_offline_cached(nsamp, wseed, fseed, sseed):
+    return _live_cached(("offline", nsamp, wseed, fseed, sseed),
+                        lambda: live_offline(live_wav(nsamp, wseed), live_first(fseed), live_style(sseed)))
+
+
+def live_server(rows, tick, **kw):
+    from zeggs import live
+    se, de = live_nets()
+    return live.LiveServer(se, de, live_stats(), LIVE_CONF, synth.DT, rows=rows, tick=tick, **kw)
+
+
+def live_cat(parts):
+    parts = [p for p in parts if p]
+    return {k: torch.cat([p[k] for p in parts], dim=0) for k in LIVE_KEYS}
+
+
+def live_err(got, ref):
+    e = {}
+    for k, r in zip(LIVE_KEYS, ref):
+        assert got[k].shape == r.shape, (k, got[k].shape, r.shape)
+        assert torch.isfinite(got[k]).all(), k
+        e[k] = float((got[k] - r).abs().max())
+    return e
+
+
+def live_bound(srv):
+    """1e-4 where the rows rode the sweep, 5e-5 otherwise -- and which of the two ran is asserted, not assumed"""
+    from zeggs import ops
+    path = ops.batch_last_path()
+    assert path == ("persistent" if srv.bd.sweep else "stage"), (path, srv.bd.sweep)
+    return 1e-4 if path == "persistent" else 5e-5

@@ -6,7 +6,6 @@ generate_gesture() fixture -- never the new code against itself.
 Bounds: 5e-5 for re-associated fp32 on this chain (test_streaming_matches_offline_generation); 1e-4 where the rows rode the
 weight-stationary sweep (test_gpu_batch_decode.test_single_chunk_vs_oracle)."""
 import ctypes as C
-import functools
 import warnings
 
 import numpy as np
@@ -14,15 +13,13 @@ import pytest
 import torch
 
 import helpers
-from zeggs import anim, audio, live, ops, synth
+from zeggs import anim, audio, ops, synth
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
+DEV = helpers.LIVE_DEV
 SPIN = 1 << 21
-KEYS = ("pose", "rpos", "rrot")
-CONF = dict(pre_emphasis=False, pre_emph_coeff=0.97, centered=True, real_amplitude=True, normalize_mel_bins=True,
-            normalize_range=True, min_clipping=1e-5, sampling_rate=16000, mel_fmin=20, mel_fmax=7600,
-            n_mel_channels=80, filter_length=800, hop_length=200, resample_method="linear", normalize_loudness=False)
+KEYS = helpers.LIVE_KEYS
+CONF = helpers.LIVE_CONF
 
 
 @pytest.fixture
@@ -33,62 +30,9 @@ def restore_options():
         ops.set_option(k, v)
 
 
-@functools.lru_cache(maxsize=None)
-def _nets():
-    se, de, _ = helpers.build_nets()
-    return se.to(DEV).eval(), de.to(DEV).eval()
-
-
-@functools.lru_cache(maxsize=None)
-def _stats():
-    return {k: torch.as_tensor(np.asarray(v), dtype=torch.float32, device=DEV) for k, v in synth.make_stats().items()}
-
-
-@functools.lru_cache(maxsize=None)
-def _first(seed):
-    return anim.preprocess_animation(synth.make_bvh_clip(8, seed=seed), DEV)
-
-
-@functools.lru_cache(maxsize=None)
-def _wav(nsamp, seed):
-    return synth.synth_wav(nsamp, seed=seed).astype(np.float32) / 32768.0
-
-
-def _style(seed):
-    return torch.randn(1, 64, device=DEV, generator=torch.Generator(DEV).manual_seed(seed)) * 0.5
-
-
-def _offline(wav, first, style_rows):
-    """the offline path: style_rows [1, 64] (constant) or [n_frames, 64] -> (pose, rpos, rrot) [n_frames, .]"""
-    se, de = _nets()
-    st = _stats()
-    n_frames = audio.n_anim_frames(len(wav))
-    feats = torch.as_tensor(audio.preprocess_audio(wav, 60, n_frames, CONF, ["mel_spec", "energy"]), device=DEV)
-    with torch.no_grad():
-        sp = se(((feats[None] - st["audio_input_mean"]) / st["audio_input_std"]).contiguous())
-        f32 = lambda a: a[0:1].to(torch.float32).contiguous()  # noqa: E731
-        rp, rr, rv, rw, lp, _, lt, lv, lw = first[:9]
-        pose0 = torch.cat([f32(x).reshape(1, -1) for x in (rv, rw, lp, lt, lv, lw)], dim=1)
-        gaze = f32(first[14]).repeat(n_frames, 1)[None].contiguous()
-        style = style_rows if style_rows.shape[0] == n_frames else style_rows.repeat(n_frames, 1)
-        ref = ops.decoder_core(de, pose0, f32(rp), f32(rr), gaze, sp, style[None].contiguous(), st["anim_input_mean"],
-                               st["anim_input_std"], st["anim_output_mean"], st["anim_output_std"], synth.DT)
-    return tuple(r[0] for r in ref)
-
-
-@functools.lru_cache(maxsize=None)
-def _offline_cached(nsamp, wseed, fseed, sseed):
-    return _offline(_wav(nsamp, wseed), _first(fseed), _style(sseed))
-
-
-def _server(rows, tick, **kw):
-    se, de = _nets()
-    return live.LiveServer(se, de, _stats(), CONF, synth.DT, rows=rows, tick=tick, **kw)
-
-
-def _cat(parts):
-    parts = [p for p in parts if p]
-    return {k: torch.cat([p[k] for p in parts], dim=0) for k in KEYS}
+# the offline rollout, its bound and the seeded inputs live in tests/helpers.py (shared with tests/test_gpu_live_dims.py)
+_nets, _stats, _first, _wav, _style = helpers.live_nets, helpers.live_stats, helpers.live_first, helpers.live_wav, helpers.live_style
+_offline, _offline_cached, _server, _cat = helpers.live_offline, helpers.live_offline_cached, helpers.live_server, helpers.live_cat
 
 
 def _feed(srv, sid, wav, chunks):
@@ -103,20 +47,7 @@ def _feed(srv, sid, wav, chunks):
     return _cat(parts)
 
 
-def _err(got, ref):
-    e = {}
-    for k, r in zip(KEYS, ref):
-        assert got[k].shape == r.shape, (k, got[k].shape, r.shape)
-        assert torch.isfinite(got[k]).all(), k
-        e[k] = float((got[k] - r).abs().max())
-    return e
-
-
-def _bound(srv):
-    """1e-4 where the rows rode the sweep, 5e-5 otherwise -- and which of the two ran is asserted, not assumed"""
-    path = ops.batch_last_path()
-    assert path == ("persistent" if srv.bd.sweep else "stage"), (path, srv.bd.sweep)
-    return 1e-4 if path == "persistent" else 5e-5
+_err, _bound = helpers.live_err, helpers.live_bound
 
 
 # ----------------------------------------------------------------------------- 1. mel window == mel range
