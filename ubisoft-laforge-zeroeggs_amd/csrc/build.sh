@@ -2,7 +2,8 @@
 # Build the MI355X engine library: every .hip translation unit -> zeggs/libzeggs_hip.so (gfx950 only).
 set -e
 cd "$(dirname "$0")"
-# experiments: ZEGGS_DEFS="-DZEGGS_U=4" ZEGGS_OUT=../zeggs/libzeggs_alt.so bash build.sh ; load with ZEGGS_LIB=<path>
+# measurement builds: ZEGGS_DEFS="-DZEGGS_TPSTAT" ZEGGS_OUT=../zeggs/libzeggs_alt.so ZEGGS_BUILD_DIR=build_v_alt bash build.sh ; load with
+# ZEGGS_LIB=<path>  (the switches the sources test: tools/README.md, "Compile-time switches")
 OUT=${ZEGGS_OUT:-../zeggs/libzeggs_hip.so}
 BD=${ZEGGS_BUILD_DIR:-build}
 mkdir -p $BD

@@ -172,43 +172,26 @@ __device__ __forceinline__ long xf_index(int b, int k, int NB) {
   return ((((long)(k >> 4) * NB + (b >> 4)) * 64 + ((((k >> 2) & 3) << 4) | (b & 15))) << 2) | (k & 3);
 }
 
-// limiter experiments (tools/stage_bench.py with an alternative build): -DZEGGS_NOX re-reads ONE activation block
-// (no activation traffic), -DZEGGS_NOMFMA replaces the matrix op by one VALU add (results are garbage, timing only)
-#ifdef ZEGGS_NOX
-#define ZXSEL(kb) ((kb) & 0)
-#else
-#define ZXSEL(kb) (kb)
-#endif
-#ifdef ZEGGS_NOMFMA
-#define ZMAC(A, w, x) A[0] += (w) + (x)
-#else
-#define ZMAC(A, w, x) A = __builtin_amdgcn_mfma_f32_16x16x4f32(w, x, A, 0, 0, 0)
-#endif
-
-// UG = k-blocks per register buffer (0: the build's default ZEGGS_U)
-template <int NB, int UG = 0>   // NB here = batch blocks handled by this workgroup; LNB = batch blocks in the fragment layout
+// U = k-blocks per register buffer
+template <int NB, int U = 2>   // NB here = batch blocks handled by this workgroup; LNB = batch blocks in the fragment layout
 __device__ __forceinline__ void run_blocks(const f4* __restrict__ wp, const f4* __restrict__ xp, int lo, int hi,
                                            f4 (&acc)[NB], int LNB) {
   // Software pipeline with two register buffers: the loads of group g+1 are in flight while group g feeds the
   // matrix cores.  The steady-state loop is branch-free (the look-ahead index is clamped, a redundant reload of
   // the last group is cheaper than a branch that would force s_waitcnt vmcnt(0)).
-#ifndef ZEGGS_U
-#define ZEGGS_U 2
-#endif
-  constexpr int U = UG ? UG : ZEGGS_U;
   const int n = hi - lo, ng = n / U;
   f4 w0[U], x0[U][NB], w1[U], x1[U][NB];
 #define ZLOAD(W, X, G)                                                                         \
   _Pragma("unroll") for (int u = 0; u < U; ++u) {                                              \
     const long kb_ = lo + (long)(G) * U + u;                                                   \
     W[u] = wp[kb_ * 64];                                                                       \
-    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) X[u][nb] = xp[(ZXSEL(kb_) * LNB + nb) * 64];      \
+    _Pragma("unroll") for (int nb = 0; nb < NB; ++nb) X[u][nb] = xp[(kb_ * LNB + nb) * 64];      \
   }
 #define ZCOMP(W, X)                                                                            \
   _Pragma("unroll") for (int u = 0; u < U; ++u)                                                \
     _Pragma("unroll") for (int c = 0; c < 4; ++c)                                              \
       _Pragma("unroll") for (int nb = 0; nb < NB; ++nb)                                        \
-        ZMAC(acc[nb], W[u][c], X[u][nb][c]);
+        acc[nb] = __builtin_amdgcn_mfma_f32_16x16x4f32(W[u][c], X[u][nb][c], acc[nb], 0, 0, 0);
   if (ng > 0) {
     ZLOAD(w0, x0, 0)
     int g = 0;
@@ -594,7 +577,7 @@ __global__ __launch_bounds__(WAVES * 64, CH ? 4 : WAVES / 4) void stage_k(StageA
         const f4* xp = (const f4*)G.seg[s].x + nb0 * 64 + lane;
         // the forward stage of 49-64 rows: one k-block per buffer (two would be 80 operand registers beside 32 accumulators
         // and the epilogue operands: 67 spilled at the 128 registers a 16-wave workgroup leaves a wave)
-        constexpr int UG = (NB == 4 && FAM == 0) ? 1 : 0;
+        constexpr int UG = (NB == 4 && FAM == 0) ? 1 : 2;
         if (G.seg[s].acc == 0) run_blocks<NB, UG>(wp, xp, lo, hi, acc[0], LNB);
         else run_blocks<NB, UG>(wp, xp, lo, hi, acc[1], LNB);
       }

@@ -31,10 +31,7 @@ int g_gemm_wg_target = 6144;   // split-K aims at this many workgroups (24 per C
 
 namespace {
 
-#ifndef ZEGGS_GEMM_BK
-#define ZEGGS_GEMM_BK 16
-#endif
-constexpr int BK = ZEGGS_GEMM_BK;      // k-extent of a tile (A/B loaders move BM * BK / threads floats per thread: 16 or 32 at 128 x 128)
+constexpr int BK = 16;      // k-extent of a tile (A/B loaders move BM * BK / threads floats per thread: 16 or 32 at 128 x 128)
 
 template <int E>
 __device__ __forceinline__ void load_contig(float (&r)[E], const float* p, int nvalid) {
@@ -90,27 +87,8 @@ __device__ __forceinline__ void load_full(float (&r)[E], const float* p) {
 
 // four workgroups (waves per SIMD) resident per CU: the compiler then keeps the 64 accumulators + operands in 101 VGPRs
 // instead of 78 + 64 AGPRs (3 per SIMD); 1-5 % on the training shapes
-#ifndef ZEGGS_GEMM_MINB
-#define ZEGGS_GEMM_MINB 4
-#endif
-#ifndef ZEGGS_GEMM_HALF_TILES
-#define ZEGGS_GEMM_HALF_TILES 1
-#endif
-#ifndef ZEGGS_GEMM_SWP
-#define ZEGGS_GEMM_SWP 0
-#endif
-#ifndef ZEGGS_GEMM_MIDSTORE
-#define ZEGGS_GEMM_MIDSTORE 0      // (with ZEGGS_GEMM_SWP) k-pair in front of which the next tile is stored to LDS; 0: after the products
-#endif
-#ifndef ZEGGS_GEMM_ABL
-#define ZEGGS_GEMM_ABL 0           // timing experiments (wrong results): 1 no per-k LDS fetch, 2 no loads / stores, 3 = 2 + no barrier, 4 = 1 + 3
-#endif
-#ifndef ZEGGS_GEMM_BUMP
-#define ZEGGS_GEMM_BUMP 0      // carried source addresses: +3 .. 4 % on the GEMM alone, -0.6 % on the training iteration (three alternating A/B pairs)
-#endif
-#ifndef ZEGGS_GEMM_SWIZZLE
-#define ZEGGS_GEMM_SWIZZLE 1
-#endif
+constexpr int GEMM_MINB = 4;
+
 // One output tile (m_base, n_base) of batch entry (A, B, C) over the k-tiles [t_begin, ntiles) of its contraction (a tile has
 // nkt * kbatch of them).  atomic: the result is a partial sum -> fp32 atomics onto C (split-K / stream-K segments).
 template <int BM, int BN, int WM, int WN, bool AKC, bool BKC>
@@ -138,33 +116,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const float* A, con
 
   // interior blocks take a branch-free path (unguarded vector loads); edge blocks / the K tail use guarded loads
   const bool interior = (m_base + BM <= g.M) && (n_base + BN <= g.N);
-#if ZEGGS_GEMM_BUMP
-  // Tiles are loaded in order (t_begin, t_begin + 1, ...): this thread's source addresses advance by a constant per tile, so they
-  // are carried instead of being rebuilt from the tile index (an integer division and four 64-bit multiply-adds, ~70 scalar
-  // instructions in front of every tile's loads -- all co-resident workgroups reach them together, nobody issues products
-  // meanwhile).  nx_*: state of the NEXT tile to be loaded.
-  int nx_kb = t_begin / nkt, nx_k = (t_begin - nx_kb * nkt) * BK;
-  const float* nx_a = A + (long)nx_kb * g.kbsA + (AKC ? (long)(m_base + a_r) * g.sam + (nx_k + a_c) : (long)(nx_k + a_r) * g.sak + (m_base + a_c));
-  const float* nx_b = B + (long)nx_kb * g.kbsB + (BKC ? (long)(n_base + b_r) * g.sbn + (nx_k + b_c) : (long)(nx_k + b_r) * g.sbk + (n_base + b_c));
-  const long a_step = AKC ? (long)BK : (long)BK * g.sak, b_step = BKC ? (long)BK : (long)BK * g.sbk;
-  const long a_wrap = g.kbsA - (long)nkt * a_step, b_wrap = g.kbsB - (long)nkt * b_step;      // from the last k-tile of a segment to the next segment
-#endif
   auto gload_r = [&](float (&ra)[EA], float (&rb)[EB], int tile) {
-#if ZEGGS_GEMM_BUMP
-    (void)tile;
-    const int k_base = nx_k;
-    const float* pa = nx_a;
-    const float* pb = nx_b;
-    nx_k += BK; nx_a += a_step; nx_b += b_step;
-    if (nx_k >= nkt * BK) { nx_k = 0; nx_a += a_wrap; nx_b += b_wrap; }
-    if (interior && k_base + BK <= g.K) {
-      load_full<EA>(ra, pa);
-      load_full<EB>(rb, pb);
-      return;
-    }
-    const float* Ab = pa - (AKC ? (long)(m_base + a_r) * g.sam + (k_base + a_c) : (long)(k_base + a_r) * g.sak + (m_base + a_c));
-    const float* Bb = pb - (BKC ? (long)(n_base + b_r) * g.sbn + (k_base + b_c) : (long)(k_base + b_r) * g.sbk + (n_base + b_c));
-#else
     const int kb = tile / nkt, k_base = (tile % nkt) * BK;
     const float* Ab = A + (long)kb * g.kbsA;
     const float* Bb = B + (long)kb * g.kbsB;
@@ -175,7 +127,6 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const float* A, con
       else load_full<EB>(rb, Bb + (long)(k_base + b_r) * g.sbk + (n_base + b_c));
       return;
     }
-#endif
     if constexpr (AKC) {
       int m = m_base + a_r, k = k_base + a_c;
       int nv = (m < g.M) ? (g.K - k) : 0;
@@ -214,6 +165,7 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const float* A, con
     }
   };
 
+  // (kept as wrappers: with ra / rb captured by the bodies themselves the compiler emits another address prologue)
   auto gload = [&](int tile) { gload_r(ra, rb, tile); };
   auto sstore = [&](int buf) { sstore_r(ra, rb, buf); };
 
@@ -235,79 +187,22 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const float* A, con
     const int cur = (t - t_begin) & 1;
     const float* As = As2[cur];
     const float* Bs = Bs2[cur];
-#if ZEGGS_GEMM_ABL == 2 || ZEGGS_GEMM_ABL == 3 || ZEGGS_GEMM_ABL == 4 || ZEGGS_GEMM_ABL == 6   // (timing experiment: no global loads / LDS stores after the first tile)
-    if (t + 1 < ntiles && t == t_begin) gload(t + 1);
-#else
     if (t + 1 < ntiles) gload(t + 1);
-#endif
-#if ZEGGS_GEMM_SWP
-    // operand fetch of k-pair kp + 1 in flight under the products of k-pair kp
-    float a[2][MT], b[2][NTL];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) a[0][i] = As[kh * LDA + wm * TM + i * 32 + l31];
-#pragma unroll
-    for (int j = 0; j < NTL; ++j) b[0][j] = Bs[kh * LDB + wn * TN + j * 32 + l31];
-#pragma unroll
-    for (int kp = 0; kp < BK / 2; ++kp) {
-#if ZEGGS_GEMM_MIDSTORE > 0
-      // the next tile goes to the other LDS buffer in the MIDDLE of this tile's products (its global loads were issued at the
-      // top; the buffer's last readers passed the barrier at the end of the previous tile): the end of a tile is then only
-      // the barrier, not drain + store + barrier -- which all co-resident workgroups reach together (they share the matrix
-      // pipe round-robin and run in lockstep), so nobody covers it
-      if (kp == ZEGGS_GEMM_MIDSTORE && t + 1 < ntiles) { sstore(cur ^ 1); __builtin_amdgcn_sched_barrier(0); }
-#endif
-      if (kp + 1 < BK / 2) {
-#pragma unroll
-        for (int i = 0; i < MT; ++i) a[(kp + 1) & 1][i] = As[(2 * kp + 2 + kh) * LDA + wm * TM + i * 32 + l31];
-#pragma unroll
-        for (int j = 0; j < NTL; ++j) b[(kp + 1) & 1][j] = Bs[(2 * kp + 2 + kh) * LDB + wn * TN + j * 32 + l31];
-      }
-      __builtin_amdgcn_sched_barrier(0);      // (left alone, the compiler sinks the fetch back next to its first use)
-#pragma unroll
-      for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NTL; ++j)
-          acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kp & 1][i], b[kp & 1][j], acc[i][j], 0, 0, 0);
-      __builtin_amdgcn_sched_barrier(0);
-    }
-#else
 #pragma unroll
     for (int kp = 0; kp < BK / 2; ++kp) {
       float a[MT], b[NTL];
-#if ZEGGS_GEMM_ABL == 1 || ZEGGS_GEMM_ABL == 4      // (timing experiment, results wrong: operands fetched once per tile)
-      const int kq = 0;
-#else
-      const int kq = kp;
-#endif
 #pragma unroll
-      for (int i = 0; i < MT; ++i) a[i] = As[(2 * kq + kh) * LDA + wm * TM + i * 32 + l31];
+      for (int i = 0; i < MT; ++i) a[i] = As[(2 * kp + kh) * LDA + wm * TM + i * 32 + l31];
 #pragma unroll
-      for (int j = 0; j < NTL; ++j) b[j] = Bs[(2 * kq + kh) * LDB + wn * TN + j * 32 + l31];
+      for (int j = 0; j < NTL; ++j) b[j] = Bs[(2 * kp + kh) * LDB + wn * TN + j * 32 + l31];
 #pragma unroll
       for (int i = 0; i < MT; ++i)
 #pragma unroll
         for (int j = 0; j < NTL; ++j)
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i], b[j], acc[i][j], 0, 0, 0);
     }
-#endif
-#if ZEGGS_GEMM_ABL == 2 || ZEGGS_GEMM_ABL == 3 || ZEGGS_GEMM_ABL == 4
-    if (t + 1 < ntiles && t == t_begin) { sstore(0); sstore(1); }
-#elif ZEGGS_GEMM_ABL == 5      // loads kept (and waited for), no LDS stores after the first tile
-    if (t + 1 < ntiles) {
-      if (t == t_begin) { sstore(0); sstore(1); }
-#pragma unroll
-      for (int i = 0; i < EA; ++i) asm volatile("" ::"v"(ra[i]));
-#pragma unroll
-      for (int i = 0; i < EB; ++i) asm volatile("" ::"v"(rb[i]));
-    }
-#elif !(ZEGGS_GEMM_SWP && ZEGGS_GEMM_MIDSTORE > 0)
     if (t + 1 < ntiles) sstore(cur ^ 1);
-#endif
-#if ZEGGS_GEMM_ABL == 3 || ZEGGS_GEMM_ABL == 4
-    if (t == t_begin) __syncthreads();
-#else
     __syncthreads();
-#endif
   }
 
   // epilogue: D layout of 32x32x2: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)
@@ -332,15 +227,16 @@ __device__ __forceinline__ void gemm_tile(const GemmArgs& g, const float* A, con
 }
 
 template <int BM, int BN, int WM, int WN, bool AKC, bool BKC>
-__global__ __launch_bounds__(WM* WN * 64, ZEGGS_GEMM_MINB) void gemm_kernel(GemmArgs g) {
+__global__ __launch_bounds__(WM* WN * 64, GEMM_MINB) void gemm_kernel(GemmArgs g) {
   constexpr int LDA = BM + 4, LDB = BN + 4;
   __shared__ __attribute__((aligned(16))) float As2[2][BK * LDA];   // double-buffered: one barrier per k-tile
   __shared__ __attribute__((aligned(16))) float Bs2[2][BK * LDB];
   // Tile order.  Workgroups go to the 8 XCDs round-robin in launch order, and every XCD has its own L2: XCD k takes the k-th
   // CONTIGUOUS eighth of the tile list instead of every eighth tile, and within a k-split the list walks groups of GEMM_GM tile
   // rows column by column, so the tiles in flight on an XCD share a few A row panels and B column panels.
+  constexpr bool XCD_ORDER = true;      // the plain launch order re-reads the panels through eight L2s
   int bx = blockIdx.x, by = blockIdx.y, zz = blockIdx.z;
-  if (ZEGGS_GEMM_SWIZZLE) {
+  if (XCD_ORDER) {
     const unsigned gx = gridDim.x, gy = gridDim.y, plane = gx * gy, total = plane * gridDim.z;
     const unsigned L = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
     const unsigned xcd = L & 7, idx = L >> 3, q = total >> 3, r = total & 7;
@@ -371,7 +267,7 @@ __global__ __launch_bounds__(WM* WN * 64, ZEGGS_GEMM_MINB) void gemm_kernel(Gemm
 // work).  A range that crosses a tile boundary finishes the first tile's share and starts the next: at most two epilogues,
 // always atomics onto the zeroed C.  g.splitk carries the number of k-tiles per output tile here.
 template <int BM, int BN, int WM, int WN, bool AKC, bool BKC>
-__global__ __launch_bounds__(WM* WN * 64, (WM * WN > 4 ? 2 : ZEGGS_GEMM_MINB)) void gemm_streamk_kernel(GemmArgs g, int tiles_x, int tiles_y) {
+__global__ __launch_bounds__(WM* WN * 64, (WM * WN > 4 ? 2 : GEMM_MINB)) void gemm_streamk_kernel(GemmArgs g, int tiles_x, int tiles_y) {
   constexpr int LDA = BM + 4, LDB = BN + 4;
   __shared__ __attribute__((aligned(16))) float As2[2][BK * LDA];
   __shared__ __attribute__((aligned(16))) float Bs2[2][BK * LDB];
@@ -424,14 +320,11 @@ int launch_cfg(const GemmArgs& g, int nbatch, hipStream_t s) {
   return 0;
 }
 
-#ifndef ZEGGS_GEMM_DMA_DEFAULT
-#define ZEGGS_GEMM_DMA_DEFAULT 0
-#endif
 // ---------------------------------------------------------------------------------------------------------------------------
 // Stream-K weight-gradient product (TN: A(m,k) = dy[k][m], B(k,n) = x[k][n], both rows contiguous) with the tiles brought in by
 // LDS-DMA (global_load_lds_dwordx4: 16 bytes per lane straight into LDS, no staging registers, no ds_write pass) through a ring
 // of THREE LDS buffers, so that two tiles are in flight while one is multiplied.  Measured on the register-staged kernel above
-// (tools/gemm_probe.py, ablation builds): without its global loads the matrix pipe is busy 0.85 instead of 0.75 of the time,
+// (profiles/r03_gemm_ablation.txt): without its global loads the matrix pipe is busy 0.85 instead of 0.75 of the time,
 // without the LDS store pass another 0.04 -- with one tile of prefetch distance and four co-resident workgroups that share the
 // pipe oldest-first, a wave reaches its store pass ~1 us after it issued the loads, sooner than the fabric answers.
 //   * a wave moves rows 4w .. 4w+3 of the [16 x 128] A and B tiles: two instructions per operand (lanes 0-31 one row, 32-63 the
@@ -535,7 +428,7 @@ __global__ __launch_bounds__(256, 3) void gemm_tn_dma_kernel(GemmArgs g, int til
   }
 }
 
-int g_gemm_dma = ZEGGS_GEMM_DMA_DEFAULT;      // zeggs_set_option("gemm_dma", 0/1)
+int g_gemm_dma = 0;      // zeggs_set_option("gemm_dma", 0/1)
 bool dma_ok(const GemmArgs& g) {
   auto a16 = [](const void* p) { return ((size_t)p & 15) == 0; };
   return g_gemm_dma && g.sam == 1 && g.sbn == 1 && g.scn == 1 && g.K % DK == 0 && g.sak % 4 == 0 && g.sbk % 4 == 0 &&
@@ -772,9 +665,6 @@ int launch_tn_direct(const GemmArgs& g, const DirectPlan& p, hipStream_t s) {
   return 0;
 }
 
-#ifndef ZEGGS_GEMM_SK256
-#define ZEGGS_GEMM_SK256 2      // 2: by output size (default)
-#endif
 // Route log (test hook zeggs_test_gemm_route_log, include/zeggs_hip.h): which route launch_gemm / launch_streamk COMMITTED to for the
 // calling thread's last product, and how many launches each route has had since the last reset.  Plain thread-local integers written
 // where the route is chosen: a handful of stores per product, no lock, no device work, and nothing reads them to decide anything.
@@ -792,7 +682,7 @@ int launch_streamk_cfg(GemmArgs g, int ncu, hipStream_t s) {
   const int tx = cdiv(g.N, BN), ty = cdiv(g.M, BM);
   const int kt = cdiv(g.K, BK) * g.kbatch;
   g.splitk = kt;
-  constexpr int resident = WM * WN > 4 ? 2 : ZEGGS_GEMM_MINB;
+  constexpr int resident = WM * WN > 4 ? 2 : GEMM_MINB;
   long nwg = (long)ncu * (g_gemm_streamk_wgs > 0 ? g_gemm_streamk_wgs : resident);
   const long total = (long)tx * ty * kt;
   // at least 16 k-tiles per workgroup: every workgroup ends in one or two partial-tile epilogues of 64 atomics per lane, and with
@@ -878,12 +768,8 @@ int launch_streamk(GemmArgs g, hipStream_t s, bool* asum_taken) {
   if (dma_ok(g)) { log_route(GR_SK_DMA, 0, 128, 128); return launch_tn_dma(g, s); }
   // 256 x 128 tiles (8 waves, 2 workgroups per CU: 3/4 of the operand bytes per product) pay on the big outputs only: +5 .. +8 %
   // on dW_ih0 (432 tiles of 128 x 128), -4 .. -6 % at 72 .. 200 tiles where the coarser grain costs balance
-  // (profiles/r03_gemm_ablation.txt); -DZEGGS_GEMM_SK256=0 / 1 forces never / from 512 rows on
-#if ZEGGS_GEMM_SK256 == 1
-  if (g.M >= 512) { log_route(GR_SK_LDS_256, 0, 256, 128); return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s); }
-#elif ZEGGS_GEMM_SK256 != 0
+  // (profiles/r03_gemm_ablation.txt)
   if (tn_big_output(g.M, g.N) && g.M >= 512) { log_route(GR_SK_LDS_256, 0, 256, 128); return launch_streamk_cfg<256, 128, 4, 2>(g, ncu, s); }
-#endif
   log_route(GR_SK_LDS_128, 0, 128, 128);
   return launch_streamk_cfg<128, 128, 2, 2>(g, ncu, s);
 }
@@ -1165,7 +1051,8 @@ int launch_gemm(GemmArgs g, int nbatch, hipStream_t s, bool* asum_taken) {
   }
   // 1 .. 2 tiles of 128 x 128 per CU and no split (bias / activation epilogue): half the CUs would carry two tiles, the others one;
   // 128 x 64 tiles give every CU the same share (the style encoder's first conv: 384 -> 768 tiles)
-  if (ZEGGS_GEMM_HALF_TILES && big && g.splitk == 1 && tiles > 256 && tiles < 512 && g.N % 64 == 0) {
+  constexpr bool HALF_TILES = true;
+  if (HALF_TILES && big && g.splitk == 1 && tiles > 256 && tiles < 512 && g.N % 64 == 0) {
     log_route(GR_HALF, 1, 128, 64);
     return launch_cfg<128, 64, 2, 2>(g, nbatch, s);
   }

@@ -13,12 +13,9 @@
 #include "kernels.h"
 #include <type_traits>
 
-// waves of a frame workgroup (64 frames = the lanes; the waves share the joints of a tree level)
-#ifndef ZEGGS_LOSS_WAVES
-#define ZEGGS_LOSS_WAVES 8
-#endif
-
 namespace {
+
+constexpr int LOSS_WAVES = 8;      // waves of a frame workgroup (64 frames = the lanes; the waves share the joints of a tree level)
 
 struct Off {
   int rpos, rmat, rvel, rvrt, lpos, ltxy, lvel, lvrt, cpos, cmat, cvel, cvrt, gaze, n;
@@ -191,7 +188,7 @@ extern __shared__ float loss_msg[];
 // One workgroup = 64 consecutive frames (lanes) x 8 waves sharing the joints of each tree level.
 // items gid0 .. gid_end - 1 of the 2 NF (side, frame) pairs: [0, NF) = prediction, [NF, 2 NF) = ground truth (the truth half
 // depends on the batch only: zeggs_loss_prepare_truth runs it ahead of the step)
-__global__ __launch_bounds__(64 * ZEGGS_LOSS_WAVES) void loss_frame_fwd_k(ZeggsLossDims d, const int* parents, FrameIO io0, FrameIO io1,
+__global__ __launch_bounds__(64 * LOSS_WAVES) void loss_frame_fwd_k(ZeggsLossDims d, const int* parents, FrameIO io0, FrameIO io1,
                                                         const float* PT0, const float* PT1, const float* gaze, float* F0,
                                                         float* F1, float* LM_, long gid0, long gid_end, int lds_ok) {
   __shared__ Levels lv;
@@ -479,7 +476,7 @@ __device__ void build_children(Children& Cn, const int* parents, int J) {      /
 // joint's while it waits for this one's messages (JIn of joint i of the next level in flight across the barrier)
 struct JIn { M3 pm, L, gcm; V3 pw, lp, lv, lw, gcp, gcv, gcw, glp, glv, glw, x, yi, gx, gyi; };
 
-__global__ __launch_bounds__(64 * ZEGGS_LOSS_WAVES) void loss_frame_bwd_k(ZeggsLossDims d, const int* parents, FrameIO io, const float* gaze,
+__global__ __launch_bounds__(64 * LOSS_WAVES) void loss_frame_bwd_k(ZeggsLossDims d, const int* parents, FrameIO io, const float* gaze,
                                                          const float* PT, const float* F, const float* LM, float* G,
                                                          float* DPT, float* drpos, float* DQ, int lds_ok) {
   __shared__ Levels lv;
@@ -975,7 +972,7 @@ extern "C" int zeggs_loss_prepare_truth(const ZeggsLossDims* dp, const int* pare
   const int PO = 6 + 15 * d.J;
   FrameIO ioW{w_pose, w_rpos, w_rrot};
   hipLaunchKernelGGL(transpose_k, dim3((unsigned)cdiv(NF, 64), (unsigned)cdiv(PO, 64)), dim3(256), 0, s, w.PT1, w_pose, NF, PO);
-  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(NF, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioW, ioW, w.PT1, w.PT1, gaze, w.FW, w.FW,
+  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(NF, 64)), dim3(64 * LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioW, ioW, w.PT1, w.PT1, gaze, w.FW, w.FW,
                      w.LM, NF, 2 * NF, lds_ok);
   ZLAUNCH_CHECK("loss_prepare_truth");
   return 0;
@@ -1010,7 +1007,7 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
   if (!truth_prepared) hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT1, w_pose, NF, PO);
   // (truth_prepared: zeggs_loss_prepare_truth has filled PT1 / FW of THIS workspace; only the prediction side is left)
   const long gend = truth_prepared ? NF : 2 * NF;
-  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(gend, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
+  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(gend, 64)), dim3(64 * LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
                      w.FW, w.LM, 0L, gend, lds_ok);
   ZLAUNCH_CHECK("loss_frame_fwd");
   if (d.T % 4 == 0 && ((uintptr_t)w.FO % 16 == 0) && ((uintptr_t)w.FW % 16 == 0) && ((uintptr_t)w.G % 16 == 0))      // (= vec4 below)
@@ -1022,7 +1019,7 @@ extern "C" int zeggs_loss_fwd_bwd_ex(const ZeggsLossDims* dp, const int* parents
                      gscale, (const float*)w.PS, o.n, d.J);
   ZLAUNCH_CHECK("loss_kl_final");
   if (dpose) {
-    hipLaunchKernelGGL(loss_frame_bwd_k, dim3(cdiv(NF, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, gaze, w.PT0, w.FO, w.LM, w.G,
+    hipLaunchKernelGGL(loss_frame_bwd_k, dim3(cdiv(NF, 64)), dim3(64 * LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, gaze, w.PT0, w.FO, w.LM, w.G,
                        w.DPT, drpos, w.DQ, lds_ok);
     ZLAUNCH_CHECK("loss_frame_bwd");
     // back to [frame][PO] (columns 0..5 hold nothing yet: the root-velocity kernel below writes them)
@@ -1061,7 +1058,7 @@ extern "C" int zeggs_loss_eval(const ZeggsLossDims* dp, const int* parents, cons
   const dim3 tg((unsigned)cdiv(NF, 64), (unsigned)cdiv(PO, 64));
   hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT0, o_pose, NF, PO);
   hipLaunchKernelGGL(transpose_k, tg, dim3(256), 0, s, w.PT1, w_pose, NF, PO);
-  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(2 * NF, 64)), dim3(64 * ZEGGS_LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
+  hipLaunchKernelGGL(loss_frame_fwd_k, dim3(cdiv(2 * NF, 64)), dim3(64 * LOSS_WAVES), lds_ok ? LOSS_LDS_BYTES : 0, s, d, parents, ioO, ioW, w.PT0, w.PT1, gaze, w.FO,
                      w.FW, w.LM, 0L, 2 * NF, lds_ok);
   ZLAUNCH_CHECK("loss_frame_fwd");
   hipLaunchKernelGGL(loss_eval_rows_k, dim3(nslab, d.B), dim3(64 * EVAL_WAVES), 0, s, d, (const float*)w.FO, (const float*)w.FW, w.PS);

@@ -312,10 +312,7 @@ __global__ __launch_bounds__(MWAVES * 64) void mel_stft_mfma_k(ZeggsMelDims d, c
 // traffic, not by the transform.  Twiddles come from two tables built once per call in float64 (exact angle reduction), so
 // the spectrum agrees with the matrix form to a few ulp.
 constexpr int FFB = 4;            // STFT frames per workgroup
-#ifndef ZEGGS_MEL_FFT_THREADS
-#define ZEGGS_MEL_FFT_THREADS 320 // 5 waves: the radix-5 stages (4 x 80 butterflies) and the mel / log chain (4 x 80 values) are ONE pass each
-#endif
-constexpr int FTHR = ZEGGS_MEL_FFT_THREADS;
+constexpr int FTHR = 320;          // 5 waves: the radix-5 stages (4 x 80 butterflies) and the mel / log chain (4 x 80 values) are ONE pass each
 constexpr int FMAXST = 8;         // stages
 struct FftPlan { int nst; int radix[FMAXST]; };
 __device__ __forceinline__ c2 cmul(c2 a, c2 b) { return c2{a.x * b.x - a.y * b.y, a.x * b.y + a.y * b.x}; }

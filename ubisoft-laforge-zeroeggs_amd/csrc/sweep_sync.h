@@ -34,11 +34,7 @@ __device__ __forceinline__ void stp(float* p, float v) {       // published: wri
 // knows to be in flight (s_waitcnt vmcnt(0): about a microsecond) before this one: call stp4 BEFORE the plain stores of an
 // epilogue, never after them.
 __device__ __forceinline__ void stp4(float* p, f4 v) {
-#ifdef ZEGGS_TP_NOSTP      // (timing experiment, results wrong: nothing is published)
-  asm volatile("" ::"v"(p), "v"(v) : "memory");
-#else
   asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(v) : "memory");
-#endif
 }
 
 // Arrival slots: workgroup c publishes "I have finished phase instance p" by storing p + 1 into slot[c] (a write-through

@@ -80,12 +80,8 @@ __device__ __forceinline__ void tp_mma(const f4 (&wr)[NJT], const f4* wl, const 
   }
 }
 
-#ifndef ZEGGS_T4_TL0
-#define ZEGGS_T4_TL0 8      // LDS-parked k-blocks of GRU layer 0 in the 4-row form (B <= 32; 4 / 0 parked blocks or 3 / 4 blocks per group spill 6 .. 24 registers)
-#endif
-#ifndef ZEGGS_T4_GU
-#define ZEGGS_T4_GU 2       // k-blocks per operand-prefetch group in the 4-row form (B <= 32; 4 / 0 parked blocks or 3 / 4 blocks per group spill 6 .. 24 registers)
-#endif
+constexpr int T4_TL0 = 8;      // LDS-parked k-blocks of GRU layer 0 in the 4-row form (B <= 32; 4 / 0 parked blocks or 3 / 4 blocks per group spill 6 .. 24 registers)
+constexpr int T4_GU = 2;       // k-blocks per operand-prefetch group in the 4-row form (B <= 32; same measurement)
 // ---- 4-row tiles for the two GRU phases (option "tp_tiles4", batch tiles in pairs: 17..32 and 49..64 rows).  A 16-row tile of
 // v_mfma_f32_16x16x4 holds (r, z, n_input, n_hidden) x 4 units, and every k-block multiplies one all-zero n row group (input-side
 // blocks have no hidden-side n weights and vice versa): a quarter of the GRU phases' matrix-core time.  v_mfma_f32_4x4x1 with
@@ -96,7 +92,7 @@ template <int NT, int NW, int OFF, int NJ, bool WLDS, int PH, int IABS>
 __device__ __forceinline__ void tp_mma4(const float (&wq)[NW], const float* wl, const f4* __restrict__ xb, int kb0, int hi,
                                         f4 (&acc)[4][NT]) {
   if constexpr (NJ <= 0) return;
-  constexpr int GU = NT >= 2 ? 1 : ZEGGS_T4_GU;
+  constexpr int GU = NT >= 2 ? 1 : T4_GU;
   constexpr int NG = (NJ + GU - 1) / GU;
   asm volatile("" : "+s"(kb0));
   f4 xa[GU][2][NT], xq[GU][2][NT];
@@ -164,19 +160,6 @@ __device__ __forceinline__ void tp_mma4(const float (&wq)[NW], const float* wl, 
 #define TPT(i)
 #endif
 
-#ifndef ZEGGS_TP_W0ARRIVE
-#define ZEGGS_TP_W0ARRIVE 0      // (experiment: see arrive_gru)
-#endif
-#ifndef ZEGGS_TP_WAVEWAIT
-#define ZEGGS_TP_WAVEWAIT 0      // (measured: every wave polling for its own producers = 8x the polls: 22.5 -> 24.1 us per step)
-#endif
-#if ZEGGS_TP_WAVEWAIT
-#define TP_FAIL_AT_WAIT
-#define TP_FAIL_AT_REDUCE if (fail) break
-#else
-#define TP_FAIL_AT_WAIT if (fail) break
-#define TP_FAIL_AT_REDUCE
-#endif
 template <bool C, typename A, typename B> struct tp_pick { typedef A type; };
 template <typename A, typename B> struct tp_pick<false, A, B> { typedef B type; };
 // INF: the inference form (zeggs_decoder_fwd_batch) -- the same rollout of one CHUNK resumed from a given state: a.H0 / a.H1 are the
@@ -190,7 +173,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
   __shared__ f4 red[8][NB][64];
   __shared__ f4 fin[NB][64];
   __shared__ f4 w3[8 * TJ3 * 64];             // output-stage weights of this workgroup (72 KB)
-  constexpr int TL0 = (T4 && NB == 2) ? ZEGGS_T4_TL0 : tl0(NB), TS0 = ts0(NB), TS1 = ts1(NB);
+  constexpr int TL0 = (T4 && NB == 2) ? T4_TL0 : tl0(NB), TS0 = ts0(NB), TS1 = ts1(NB);
   constexpr bool SPREAD = TS0 > 0;       // old parts spread over all three hand-off windows
   __shared__ f4 w0l[8 * (TL0 > 0 ? TL0 : 1) * 64];   // the first TL0 (old-part) k-blocks of GRU layer 0: relieves the register file
   __shared__ float gsh[BP * 3];               // normalised gaze direction of x_{t+1} per batch row
@@ -351,12 +334,6 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     return o;
   };
   auto reduce_gate4 = [&](f4 (&acc)[4][NT], f4 (&out)[4]) {
-#ifdef ZEGGS_TP_NORED      // (timing experiment, results wrong: no cross-wave reduction -- every gate thread takes its own wave's partial sums;
-    // what the LDS round trip + barrier + 16 serial reads of the reducing threads cost a GRU phase)
-#pragma unroll
-    for (int g = 0; g < 4; ++g) out[g] = acc[g][0];
-    return;
-#endif
     // one v_permlane32_swap folds the k-halves of TWO values: swap(a, b) = ([a_lo | b_lo], [a_hi | b_hi]), whose sum holds the folded a
     // in lanes < 32 and the folded b in lanes >= 32 -- gates (0, 2) and (1, 3) pair up, every lane has something to store
 #pragma unroll
@@ -372,7 +349,6 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
         red4[wave][lane < 32 ? g : g + 2][nt][lane & 31] = v;
       }
     __syncthreads();
-    if (ZEGGS_TP_W0ARRIVE == 2 && wave == 0) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
     for (int g = 0; g < 4; ++g) out[g] = f4{0.f, 0.f, 0.f, 0.f};
     if (tid < 64 * NT) {
@@ -421,39 +397,17 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
 #ifdef ZEGGS_TPSTAT
       const unsigned long long w0 = wall_clock64();
 #endif
-#if ZEGGS_TP_WAVEWAIT
-      // every wave for the producers of its own k-blocks: no barrier, no broadcast; a give-up is noticed by everybody behind the
-      // phase's reduction barrier (`fail` is checked there: all waves of a workgroup must meet the same barriers)
-      if (!slots_wait(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, (lane & 7) == wave)) fail = 1;
-#else
-#ifndef ZEGGS_TP_NOPOLL      // (timing experiment, results wrong: nobody waits for anybody -- the step as pure per-CU work)
       if (wave == 0 && !(a.sync.stag ? slots_wait2(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, a.sync.stag) : slots_wait(a.sync.cnt, (unsigned)(p + 1), a.sync.spin, true, a.sync.nap))) fail = 1;
-#endif
-#endif
 #ifdef ZEGGS_TPSTAT
       wsum[(p + 1) % 3] += wall_clock64() - w0;
 #endif
     }
-#if !ZEGGS_TP_WAVEWAIT
     __syncthreads();
-#endif
   };
   auto arrive = [&](long p) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     if (tid == 0) __hip_atomic_store((gu32*)(a.sync.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  // GRU phases in the 4-row form with one batch tile: wave 0 is the only publisher.  Experiment (-DZEGGS_TP_W0ARRIVE=1 / 2): it raises
-  // the flag alone, without the workgroup barrier, so that the other seven waves run the next phase's old-operand products beside
-  // its reduction / gate math / publishes (2: wave 0 at raised priority meanwhile).  Round 3 measured form 1 at +0.5 us per step.
-  auto arrive_gru = [&](long p) {
-    if constexpr (ZEGGS_TP_W0ARRIVE != 0 && T4 && NT == 1) {
-      if (wave == 0) {
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        if (tid == 0) __hip_atomic_store((gu32*)(a.sync.cnt + c), (unsigned)(p + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (ZEGGS_TP_W0ARRIVE == 2) __builtin_amdgcn_s_setprio(0);
-      }
-    } else arrive(p);
   };
 
   GAcc acc1, acc2;              // accumulators of GRU layer 0 / 1: started in the windows of earlier phases
@@ -489,21 +443,13 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       const f4* x1 = (const f4*)(a.G1 + (long)t * 128 * XB) + lane;
       // window: the rest of this phase's old part, h1_{t-1} through the fold (cond and h0_{t-1} ran in the window of the previous
       // output stage)
-#ifndef ZEGGS_TP_NOWIN      // (timing experiment: the hand-off latency with empty windows; results are wrong)
       TP_MMA0(TS0, TNO0 - TS0, x0, TFR0 + wave + 8 * TS0, a.KB0, acc1);
-#endif
       zero_g(acc2);
       if constexpr (TS1 > 0) TP_MMA1(0, TS1, x1, 64 + wave, 128, acc2);
       wait_phase(p1 - 1);
-      TP_FAIL_AT_WAIT;
+      if (fail) break;
       TPT(1);
-#ifdef ZEGGS_TP_L2HIT      // (timing experiment, results wrong: the "fresh" blocks are read from the PREVIOUS step's operand -- lines this XCD's L2
-      // already holds -- to measure what the first touch of freshly published data costs a phase: the upper bound of ANY scheme
-      // that would place the hand-off data in the consumer's L2 ahead of the wait; HISTORY round 5)
-      TP_MMA0(TNO0, TNF0, (t > 1 ? x0 - (long)a.KB0 * XB / 4 : x0), wave, TFRW, acc1);
-#else
       TP_MMA0(TNO0, TNF0, x0, wave, TFRW, acc1);  // fresh part
-#endif
     } else {
       zero_g(accg);
       const f4* x0 = (const f4*)(a.G0 + (long)t * a.KB0 * XB) + lane;
@@ -511,7 +457,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
       TP_MMA0_LDS(TL0, x0, TFR0 + wave, a.KB0, accg);
       TP_MMA0(TL0, TNO0 - TL0, x0, TFR0 + wave + 8 * TL0, a.KB0, accg);
       wait_phase(p1 - 1);
-      TP_FAIL_AT_WAIT;
+      if (fail) break;
       TPT(1);
       TP_MMA0(TNO0, TNF0, x0, wave, TFRW, accg);  // fresh part
     }
@@ -519,7 +465,6 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     f4 fv0 = f4{0.f, 0.f, 0.f, 0.f}, gq[4];
     if constexpr (T4) reduce_gate4(*(SPREAD ? &acc1 : &accg), gq);
     else fv0 = reduce_gate(*(SPREAD ? &acc1 : &accg));
-    TP_FAIL_AT_REDUCE;
     TPT(3);
     if constexpr (T4) {
       if (gact4) {      // two units (u0, u0 + 1) of batch row gb per lane; the lower lane assembles and publishes the four
@@ -595,28 +540,22 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     }
     }
     TPT(4);
-    arrive_gru(p1);
+    arrive(p1);
     TPT(5);
     // ================================================================ GRU layer 1 : [h0_t | h1_{t-1}]
     if constexpr (SPREAD) {
       const f4* x1 = (const f4*)(a.G1 + (long)t * 128 * XB) + lane;
-#ifndef ZEGGS_TP_NOWIN
       TP_MMA1(TS1, TNO1 - TS1, x1, 64 + wave + 8 * TS1, 128, acc2);   // window: rest of the old part
-#endif
       wait_phase(p2 - 1);
-      TP_FAIL_AT_WAIT;
+      if (fail) break;
       TPT(6);
-#ifdef ZEGGS_TP_L2HIT
-      TP_MMA1(TNO1, TNF1, (t > 1 ? x1 - 128L * XB / 4 : x1), wave, 64, acc2);
-#else
       TP_MMA1(TNO1, TNF1, x1, wave, 64, acc2);               // h0_t
-#endif
     } else {
       zero_g(accg);
       const f4* x1 = (const f4*)(a.G1 + (long)t * 128 * XB) + lane;
       TP_MMA1(0, TNO1, x1, 64 + wave, 128, accg);             // h1_{t-1}: before the hand-off
       wait_phase(p2 - 1);
-      TP_FAIL_AT_WAIT;
+      if (fail) break;
       TPT(6);
       TP_MMA1(TNO1, TNF1, x1, wave, 64, accg);                // h0_t
     }
@@ -624,7 +563,6 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     f4 fv1 = f4{0.f, 0.f, 0.f, 0.f};
     if constexpr (T4) reduce_gate4(*(SPREAD ? &acc2 : &accg), gq);
     else fv1 = reduce_gate(*(SPREAD ? &acc2 : &accg));
-    TP_FAIL_AT_REDUCE;
     TPT(8);
     if constexpr (T4) {
       if (gact4) {
@@ -687,7 +625,7 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     }
     }
     TPT(9);
-    arrive_gru(p2);
+    arrive(p2);
     TPT(10);
     // ================================================================ output stage : [h1_t | cond_{t+1}]
     float gz_[3] = {0.f, 0.f, 0.f};          // gaze target of frame t+1 (an input): in flight under the products
@@ -697,11 +635,8 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
     {
       const f4* x3 = (const f4*)(a.G3 + (long)t * a.KB3 * XB) + lane;
       const f4* wl3 = w3 + wave * TJ3 * 64 + lane;
-#ifndef ZEGGS_TP_NOWIN
       tp_mma<NB, TJ0 - TL0, 0, TNO3, true>(wr0, wl3, x3, 64 + wave, a.KB3, acc);          // cond_{t+1}: before the hand-off
-#endif
       zero_g(acc1);
-#ifndef ZEGGS_TP_NOWIN
       if constexpr (SPREAD) {
         if (next) {     // window: cond and h0_t blocks of the NEXT step's GRU layer 0 (h0_t was published two hand-offs ago)
           const f4* x0n = (const f4*)(a.G0 + (long)(t + 1) * a.KB0 * XB) + lane;
@@ -709,19 +644,13 @@ __global__ __launch_bounds__(TTHR, 2) void train_fwd_persistent_k(TArgs a) {
           TP_MMA0(TL0, TS0 - TL0, x0n, TFR0 + wave + 8 * TL0, a.KB0, acc1);
         }
       }
-#endif
       wait_phase(p3 - 1);
-      TP_FAIL_AT_WAIT;
+      if (fail) break;
       TPT(11);
-#ifdef ZEGGS_TP_L2HIT
-      tp_mma<NB, TJ0 - TL0, TNO3, TNF3, true>(wr0, wl3, (t > 1 ? x3 - (long)a.KB3 * XB / 4 : x3), wave, 64, acc);
-#else
       tp_mma<NB, TJ0 - TL0, TNO3, TNF3, true>(wr0, wl3, x3, wave, 64, acc);               // h1_t
-#endif
     }
     TPT(12);
     reduce(acc);
-    TP_FAIL_AT_REDUCE;
     TPT(13);
     {
       float* gnext = a.Gin + (long)(t + 1) * sG;                       // canonical [hid | x] row of step t+1
