@@ -13,10 +13,17 @@
   them, what push_many enqueued, and whether the two servers' pending features are bitwise equal at the end
   -> profiles/live_push_many.json.
 
+  --leg loudness (or --loudness): what running loudness normalisation adds to push_many, per rows in {1, 8, 32, 64} and stream age
+  in {10 s, 600 s}: two servers in ONE process, loudness=None and loudness="running", are fed the same rows' signals up to the age
+  through push_many, then tick by tick the same chunks, each call synchronised before and after, taking turns, >= 200 ticks:
+  median, p95, min, max of both, what each enqueued, and whether the cost with loudness on moves with the stream's age by more
+  than the spread -> profiles/live_loudness.json.
+
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
     python tools/live_bench.py [--out profiles/live_stream.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg push_many [--out profiles/live_push_many.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg loudness [--out profiles/live_loudness.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
 """
 import argparse
 import json
@@ -165,6 +172,53 @@ def case_push_many(rows, steps, age=10):
                 pending_features_bitwise_equal=bool(same))
 
 
+def case_loudness(rows, age, steps):
+    """push_many with running loudness off and on: two servers in ONE process, the same rows' signals up to `age` (1 s
+    push_many calls, drained), then tick by tick the same chunks, each call synchronised before and after, taking turns"""
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    srv = {k: live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, loudness=v) for k, v in (("off", None), ("on", "running"))}
+    sids = {k: [s.open(first, st) for st in styles] for k, s in srv.items()}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    t = {k: dict(push=[], step=[]) for k in srv}
+    ops_seen, i = {k: set() for k in srv}, 0
+    while len(t["on"]["step"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]                # (the slicing is not what is timed)
+        for k in (("off", "on") if i % 2 else ("on", "off")):                      # taking turns at going first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            torch.cuda.synchronize()
+            t[k]["push"].append(time.perf_counter() - t0)
+            ops_seen[k].add(srv[k].stats["ops_last_push_many"])
+            while True:
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k]["step"].append(dt)
+        pos = nxt
+    state = srv["on"].loudness(sids["on"][0])
+    return dict(kind="loudness", rows=rows, age_s=age, tick=TICK, samples_per_row_and_tick=round(TICK * FS / FPS, 1),
+                push_many_off=_summary(t["off"]["push"]), push_many_on=_summary(t["on"]["push"]), step_off=_summary(t["off"]["step"]),
+                step_on=_summary(t["on"]["step"]), ops_per_push_many_off=sorted(ops_seen["off"]), ops_per_push_many_on=sorted(ops_seen["on"]),
+                row0_state=dict(lufs=round(state["lufs"], 4), gain=round(state["gain"], 6), blocks=state["blocks"], gated=state["gated"]))
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -196,13 +250,18 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many"))
-    ap.add_argument("--case", default=None, help="internal: one case in a child process, e.g. server:8:10, baseline:600 or push_many:64")
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness"))
+    ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
+    ap.add_argument("--case", default=None,
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64 or loudness:64:600")
     a = ap.parse_args()
+    if a.loudness:
+        a.leg = "loudness"
     if a.case:
         kind, *rest = a.case.split(":")
         res = (case_server(int(rest[0]), int(rest[1]), a.steps) if kind == "server" else
-               case_push_many(int(rest[0]), a.steps) if kind == "push_many" else case_baseline(int(rest[0]), a.steps))
+               case_push_many(int(rest[0]), a.steps) if kind == "push_many" else
+               case_loudness(int(rest[0]), int(rest[1]), a.steps) if kind == "loudness" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -211,6 +270,10 @@ def main():
         cases = [f"push_many:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_push_many.json")
+    if a.leg == "loudness":
+        cases = [f"loudness:{r}:{g}" for r in rows for g in ages]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_loudness.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -226,6 +289,26 @@ def main():
         pays = [r["rows"] for r in results if r["push_many_per_tick"]["median_ms"] < r["pushes_per_tick"]["median_ms"]]
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0),
                    tick_frames=TICK, ticks_per_case=a.steps, row_counts_at_which_push_many_is_faster=pays, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "loudness":
+        cost, age_effect = {}, {}
+        for n in rows:
+            mine = {r["age_s"]: r for r in results if r["rows"] == n}
+            lo = mine[ages[0]]
+            cost[str(n)] = dict(push_many_off_median_ms=lo["push_many_off"]["median_ms"], push_many_on_median_ms=lo["push_many_on"]["median_ms"],
+                                added_ms=round(lo["push_many_on"]["median_ms"] - lo["push_many_off"]["median_ms"], 4))
+            if len(ages) >= 2:
+                hi = mine[ages[-1]]
+                spread = max(x["push_many_on"]["p95_ms"] - x["push_many_on"]["min_ms"] for x in (lo, hi))
+                age_effect[str(n)] = dict(median_ms_young=lo["push_many_on"]["median_ms"], median_ms_old=hi["push_many_on"]["median_ms"],
+                                          spread_ms=round(spread, 4), differs_by_more_than_the_spread=abs(
+                                              hi["push_many_on"]["median_ms"] - lo["push_many_on"]["median_ms"]) > spread)
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, cost_of_running_loudness_per_push_many=cost, age_effect_on_push_many_with_loudness=age_effect,
+                   results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

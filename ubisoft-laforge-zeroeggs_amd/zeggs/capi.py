@@ -10,8 +10,9 @@ per function, and the two handles of the library.
           handles share the dlopen handle, and so every global of the library.
 
 A new entry point is a declaration in the header plus one row in PROTOTYPES (tests/test_abi.py compares the two); the second
-header include/zeggs_hip_live.h has its own tables, EXT_STRUCTS / EXT_PROTOTYPES (tests/test_live_push_cpu.py), same loader.  torch is
-imported when a tensor is first converted, not when this module is.
+header include/zeggs_hip_live.h has its own tables, EXT_STRUCTS / EXT_PROTOTYPES (tests/test_live_push_cpu.py), the third,
+include/zeggs_hip_loudness.h, LOUD_STRUCTS / LOUD_PROTOTYPES (tests/test_live_loudness_cpu.py): same loader.  torch is imported
+when a tensor is first converted, not when this module is.
 """
 import ctypes as C
 import os
@@ -235,6 +236,20 @@ EXT_PROTOTYPES = {
     "zeggs_copy_segments": "status: ZeggsSeg* ZeggsSeg* int stream",
 }
 
+# ----------------------------------------------------------------------------- the third header (include/zeggs_hip_loudness.h)
+# Running loudness normalisation of live serving (tests/test_live_loudness_cpu.py compares these tables with the header).
+LoudDims = _struct("LoudDims", [(C.c_int, "fs rows ring_blocks warmup"), (C.c_double, "target gain_lo gain_hi"), (C.c_double * 10, "coef")])
+LoudRow = _struct("LoudRow", [(C.c_void_p, "src dst"), (C.c_long, "count"), (C.c_int, "row")])
+LOUD_STRUCTS = {"ZeggsLoudDims": LoudDims, "ZeggsLoudRow": LoudRow}
+LOUD_PROTOTYPES = {
+    "zeggs_live_loudness_state_bytes": "size_t: ZeggsLoudDims*",
+    "zeggs_live_loudness_reset": "status: ZeggsLoudDims* any* size_t int float stream",
+    "zeggs_live_loudness_hold": "status: ZeggsLoudDims* any* size_t int int stream",
+    # rows_host: a HOST array of ZeggsLoudRow; rows_dev: the same records on the device (an address cast to the pointer type), None for one
+    "zeggs_live_loudness_push": "status: ZeggsLoudDims* ZeggsLoudRow* ZeggsLoudRow* int any* size_t stream",
+    "zeggs_live_loudness_read": "status: ZeggsLoudDims* any* size_t int host* stream",
+}
+
 
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
@@ -274,13 +289,13 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
-    ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES[name]).partition(":")
+    ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -318,7 +333,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -330,7 +345,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

@@ -13,7 +13,10 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
     it takes the dimensions; a single-row server uses zeggs_decoder_fwd_state_ex as GestureStream does.  Rows that are idle or
     short of `tick` frames ride along on finite filler and their state is not committed;
   * set_style(sid, style, fade) changes the style while speech goes on (the decoder takes a style row per frame);
-  * close(sid) flushes the row's remaining frames with the true right-edge rules (B = 1 entry point) and frees the row.
+  * close(sid) flushes the row's remaining frames with the true right-edge rules (B = 1 entry point) and frees the row;
+  * LiveServer(loudness="running") normalises every row's loudness as its audio arrives (the streaming counterpart of
+    audio_conf.normalize_loudness): a running BS.1770 gated estimate per row on the device, the gain applied as the samples enter
+    the window (zeggs_live_loudness_push: one more launch per push / push_many); loudness(sid) reads it, hold(sid) freezes the gain.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -104,16 +107,18 @@ def plan_push(rows, caps, lens, FC, width, first_sample, frames_ready):
 
 
 class _Staging:
-    """What one push_many() uploads, as ONE block: [copy records | copy records of the second launch | mel records | samples].
+    """What one push_many() uploads, as ONE block: [copy records | copy records of the second launch | mel records | loudness
+    records (`loud_rows` of them: none on a server without running loudness) | samples].
     Two pinned host blocks take turns, each guarded by an event recorded behind its copy, so a block is never rewritten while a
     copy from it may be in flight; one device block (calls on a stream are ordered)."""
 
-    def __init__(self, rows, n_samples, dev):
+    def __init__(self, rows, n_samples, dev, loud_rows=0):
         a64 = lambda x: (x + 63) // 64 * 64  # noqa: E731
-        self.rows, self.n_samples = rows, int(n_samples)
+        self.rows, self.n_samples, self.loud_rows = rows, int(n_samples), int(loud_rows)
         self.o_back = a64(3 * rows * C.sizeof(ops.Seg))
         self.o_mel = self.o_back + a64(rows * C.sizeof(ops.Seg))
-        self.o_smp = self.o_mel + a64(rows * C.sizeof(ops.MelRow))
+        self.o_loud = self.o_mel + a64(rows * C.sizeof(ops.MelRow))
+        self.o_smp = self.o_loud + a64(self.loud_rows * C.sizeof(ops.LoudRow))
         self.nbytes = self.o_smp + 4 * self.n_samples
         self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
@@ -121,7 +126,8 @@ class _Staging:
         for h in self.host:
             b = h.numpy()
             self.view.append(dict(segs=(ops.Seg * (3 * rows)).from_buffer(b, 0), back=(ops.Seg * rows).from_buffer(b, self.o_back),
-                                  mel=(ops.MelRow * rows).from_buffer(b, self.o_mel), smp=b[self.o_smp:].view(np.float32)))
+                                  mel=(ops.MelRow * rows).from_buffer(b, self.o_mel), smp=b[self.o_smp:].view(np.float32),
+                                  loud=(ops.LoudRow * self.loud_rows).from_buffer(b, self.o_loud)))
         self.events, self.turn = [None, None], 0
 
     def take(self):
@@ -144,6 +150,36 @@ class _Staging:
                 ev.synchronize()
 
 
+LOUDNESS_DEFAULTS = dict(target=-20.0, horizon=60.0, warmup=1, gain_db=(-30.0, 30.0))
+
+
+def loudness_options(loudness):
+    """LiveServer's `loudness` argument -> None (off) or dict(target, horizon, warmup, gain_db, ring_blocks): "running" is the
+    defaults, a dict overrides them.  `horizon`: seconds the estimate looks back over, a positive multiple of 0.1 s (one gating
+    block per 0.1 s: ring_blocks = round(horizon * 10)); `warmup` >= 1 gated blocks before the first estimate; `gain_db` (lo, hi)
+    bounds of the gain in dB.  Anything else raises ValueError."""
+    if loudness is None:
+        return None
+    if loudness == "running":
+        loudness = {}
+    if not isinstance(loudness, dict) or set(loudness) - set(LOUDNESS_DEFAULTS):
+        raise ValueError(f"LiveServer: loudness is None, 'running' or a dict with keys {sorted(LOUDNESS_DEFAULTS)}")
+    o = dict(LOUDNESS_DEFAULTS, **loudness)
+    try:
+        target, horizon, warmup = float(o["target"]), float(o["horizon"]), int(o["warmup"])
+        lo, hi = (float(x) for x in o["gain_db"])
+    except (TypeError, ValueError):
+        raise ValueError(f"LiveServer: loudness options {loudness!r}") from None
+    blocks = round(horizon * 10) if np.isfinite(horizon) else 0
+    if not (blocks >= 1 and abs(horizon * 10 - blocks) < 1e-6):
+        raise ValueError(f"LiveServer: loudness horizon {horizon} s is not a positive multiple of 0.1 s")
+    if warmup < 1 or warmup != o["warmup"]:
+        raise ValueError(f"LiveServer: loudness warmup {o['warmup']} (an integer >= 1)")
+    if not lo <= hi or not np.isfinite([lo, hi, target]).all():
+        raise ValueError(f"LiveServer: loudness gain_db {o['gain_db']} (lo <= hi) / target {target}")
+    return dict(target=target, horizon=horizon, warmup=warmup, gain_db=(lo, hi), ring_blocks=int(blocks))
+
+
 class _Row:
     __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade")
 
@@ -157,12 +193,19 @@ class _Row:
 class LiveServer:
     """speech_net / decoder: zeggs.modules instances on the device (eval mode); `stats`: dict with audio_input_mean/std,
     anim_input_mean/std, anim_output_mean/std; `audio_conf`: data_pipeline_conf["audio_conf"]; `rows` streams at most at a time
-    (<= 64), `tick` >= 3 frames per step (the batch sweep needs chunks of >= 4 frames)."""
+    (<= 64), `tick` >= 3 frames per step (the batch sweep needs chunks of >= 4 frames).
+
+    `loudness`: None, "running" or a dict (loudness_options) -- running loudness normalisation for every row, the streaming
+    counterpart of audio_conf.normalize_loudness: each row keeps a BS.1770 gated estimate of what it has received over the last
+    `horizon` seconds, and new samples enter its window times the gain that brings the estimate to `target` LUFS (one more
+    launch per push / push_many: zeggs_live_loudness_push).  With None a conf that asks for loudness normalisation
+    is refused, as before: there is no whole signal to measure."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384):
+                 device="cuda", window_capacity=16384, loudness=None):
         g = audio_conf
-        if g.get("normalize_loudness"):
+        loud = loudness_options(loudness)
+        if loud is None and g.get("normalize_loudness"):
             raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
         if tuple(feature_type) != ("mel_spec", "energy"):
             raise NotImplementedError("live serving supports the shipped feature set [mel_spec, energy]")
@@ -211,7 +254,12 @@ class LiveServer:
         self._alt = [z(int(window_capacity)) for _ in range(R)]
         self._scratch = torch.empty_like(self.feats)
         self._mb = ops.MelBatch(self.mel, self.fb, R, self.FC, self.dev)
-        self._stage = _Staging(R, R * 2048, self.dev)
+        # running loudness: the rows' state, and push()'s staging area for one chunk (push_many's chunks ride in its staging block)
+        self.loudness_conf = loud
+        self._loud = None if loud is None else ops.LiveLoudness(self.fs, R, loud["ring_blocks"], loud["warmup"], loud["target"],
+                                                                loud["gain_db"], audio._kweighting(self.fs), self.dev)
+        self._chunk = z(2048) if loud else None
+        self._stage = _Staging(R, R * 2048, self.dev, R if loud else 0)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -227,12 +275,17 @@ class LiveServer:
         r = self._sids[sid]
         return r, self._rows[r]
 
-    def open(self, first_pose, style):
+    def open(self, first_pose, style, gain=1.0):
         """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
-        -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init)."""
+        -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
+        what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing."""
+        if self._loud is None and float(gain) != 1.0:
+            raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
         free = [r for r in range(self.rows) if self._rows[r] is None]
         if not free:
             raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        if self._loud is not None:
+            ops.live_loudness_reset(self._loud, free[0], gain)
         r, sid = free[0], self._next_sid
         self._next_sid += 1
         f32 = lambda a: a[0:1].to(self.dev, torch.float32).contiguous()  # noqa: E731
@@ -293,7 +346,16 @@ class LiveServer:
                 self.stats["window_capacity"][r] = int(w.numel())
             w[:keep.numel()] = keep
             row.base = nb
-        w[row.n - row.base:row.n - row.base + m].copy_(chunk)
+        if self._loud is None:
+            w[row.n - row.base:row.n - row.base + m].copy_(chunk)
+        else:                                            # the same kernel as push_many(), one record (in the kernel arguments)
+            if self._chunk.numel() < m:
+                self._chunk = torch.empty(2 * m, device=self.dev)
+            self._chunk[:m].copy_(chunk)
+            rec = (ops.LoudRow * 1)()
+            rec[0].src, rec[0].dst = self._chunk.data_ptr(), w.data_ptr() + 4 * (row.n - row.base)
+            rec[0].count, rec[0].row = m, r
+            ops.live_loudness_push(self._loud, rec, 1)
         row.n += m
         self.stats["uploaded_samples"] += m
         ready = min(ops.mel_frames_ready(self.mel, row.n), audio.n_anim_frames(row.n, self.fs, self.fps) - 1)
@@ -306,7 +368,9 @@ class LiveServer:
         behind them, kept feature rows to scratch), a second one only when some row compacts its feature block, and the TWO
         launches of zeggs_mel_features_batch -- stats["ops_last_push_many"] <= 5.  Growth (a chunk that does not fit its window,
         more new frames than a feature block holds) reallocates first, as in push().  An unknown sid raises KeyError before
-        anything changes."""
+        anything changes.  With running loudness the new samples leave the copy list and are the records of ONE
+        zeggs_live_loudness_push (uploaded in the same block): <= 6 operations; windows, features and loudness state are
+        bitwise those of push(), however the signal is cut and whichever rows share a call."""
         items = [(self._row(sid), np.ascontiguousarray(c, dtype=np.float32).reshape(-1)) for sid, c in chunks.items()]
         items = [(r, row, c) for (r, row), c in items if c.size]
         self.stats["ops_last_push_many"] = n_ops = 0
@@ -327,7 +391,7 @@ class LiveServer:
                 n_ops += 1
         if plan["n_stage"] > self._stage.n_samples:
             self._stage.idle()
-            self._stage = _Staging(self.rows, 2 * plan["n_stage"], self.dev)
+            self._stage = _Staging(self.rows, 2 * plan["n_stage"], self.dev, self._stage.loud_rows)
         # ---- the staging block: records with device addresses, then the samples
         stg = self._stage
         blk = stg.take()
@@ -339,8 +403,15 @@ class LiveServer:
         where = {"win": lambda i: self.window[items[i][0]].data_ptr(), "alt": lambda i: self._alt[items[i][0]].data_ptr(),
                  "stage": lambda i: stg.dev.data_ptr() + stg.o_smp, "feats": lambda i: self.feats.data_ptr() + items[i][0] * block_bytes,
                  "scratch": lambda i: self._scratch.data_ptr() + items[i][0] * block_bytes}
-        for name in ("segs", "back"):
-            for j, ((sk, si), so, (dk, di), do, cnt) in enumerate(plan["segs" if name == "segs" else "segs_back"]):
+        segs, loud = plan["segs"], []
+        if self._loud is not None:
+            # the new samples do not go through the copy launch: they enter their windows through the loudness kernel, scaled
+            loud = [s for s in segs if s[0][0] == "stage"]
+            segs = [s for s in segs if s[0][0] != "stage"]
+            for q, ((sk, si), so, (dk, di), do, cnt) in zip(blk["loud"], loud):
+                q.src, q.dst, q.count, q.row = where[sk](si) + 4 * so, where[dk](di) + 4 * do, cnt, items[di][0]
+        for name, copies in (("segs", segs), ("back", plan["segs_back"])):
+            for j, ((sk, si), so, (dk, di), do, cnt) in enumerate(copies):
                 g = blk[name][j]
                 g.src, g.dst, g.count = where[sk](si) + 4 * so, where[dk](di) + 4 * do, cnt
         n_mel = 0
@@ -351,11 +422,16 @@ class LiveServer:
                 q.out = self.feats.data_ptr() + r * block_bytes + 4 * (p["k0"] - p["fbase"]) * F
                 q.base, q.n_samples, q.k0, q.k1, q.final = p["base"], p["n"], p["k0"], p["k1"], 0
                 n_mel += 1
-        # ---- at most five operations
+        # ---- at most five operations (six with running loudness)
         with torch.no_grad():
             stg.upload(plan["n_stage"])
-            ops.copy_segments(blk["segs"], len(plan["segs"]), stg.dev.data_ptr())
-            n_ops += 2
+            n_ops += 1
+            if segs or self._loud is None:
+                ops.copy_segments(blk["segs"], len(segs), stg.dev.data_ptr())
+                n_ops += 1
+            if loud:
+                ops.live_loudness_push(self._loud, blk["loud"], len(loud), stg.dev.data_ptr() + stg.o_loud)
+                n_ops += 1
             if plan["segs_back"]:
                 ops.copy_segments(blk["back"], len(plan["segs_back"]), stg.dev.data_ptr() + stg.o_back)
                 n_ops += 1
@@ -368,6 +444,23 @@ class LiveServer:
             row.n, row.base, row.n_feat, row.fbase = p["n"], p["base"], p["n_feat"], p["fbase"]
             self.stats["uploaded_samples"] += int(c.size)
         self.stats["ops_last_push_many"] = n_ops
+
+    # ------------------------------------------------------------------ running loudness
+    def _loud_row(self, sid):
+        if self._loud is None:
+            raise RuntimeError("LiveServer: running loudness is off (LiveServer(loudness=...))")
+        return self._row(sid)[0]
+
+    def loudness(self, sid):
+        """-> dict(lufs: the row's last estimate (NaN before the first), gain: what new samples are multiplied by, blocks: gating
+        blocks completed, gated: blocks past the relative gate at the last one, held: the last block left the gain as it was --
+        no estimate, or hold()).  One small read-back that waits for the stream: monitoring, not for the tick path."""
+        got = ops.live_loudness_read(self._loud, self._loud_row(sid))
+        return {k: got[k] for k in ("lufs", "gain", "blocks", "gated", "held")}
+
+    def hold(self, sid, on=True):
+        """freeze the row's gain at what it is (it goes on metering), or release it: the next estimate moves it again"""
+        ops.live_loudness_hold(self._loud, self._loud_row(sid), on)
 
     # ------------------------------------------------------------------ style
     def set_style(self, sid, style, fade=0):

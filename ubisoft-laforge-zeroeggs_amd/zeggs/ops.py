@@ -12,8 +12,8 @@ import torch
 
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
-                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, MelRow, Seg, SpeechDims, SpeechPtrs, StyleDims,
-                   StyleGruDims, StyleGruPtrs, StylePtrs, api)
+                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow, Seg, SpeechDims, SpeechPtrs,
+                   StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
 
@@ -964,6 +964,46 @@ def copy_segments(segs, n, segs_dev):
     """zeggs_copy_segments: segs[:n] a HOST array of Seg (device addresses, counts in floats), segs_dev the device address of a
     copy of the same records: ONE launch for all of them"""
     api().zeggs_copy_segments(segs, _records(Seg, segs_dev), int(n), _stream())
+
+
+class LiveLoudness:
+    """The running loudness state of `rows` live rows (include/zeggs_hip_loudness.h): the dims record -- `coef`, the K-weighting
+    biquads for `fs` as [(b, a), (b, a)] (audio._kweighting), the estimate's look-back of `ring_blocks` gating blocks (10 per
+    second), `warmup`, `target` LUFS, the gain's bounds in dB -- and the state buffer, every row reset to gain 1."""
+
+    def __init__(self, fs, rows, ring_blocks, warmup, target, gain_db, coef, device):
+        coef = [c for b, a in coef for c in (b[0], b[1], b[2], a[1], a[2])]
+        self.d = LoudDims(int(fs), int(rows), int(ring_blocks), int(warmup), float(target), float(gain_db[0]), float(gain_db[1]),
+                          (C.c_double * 10)(*coef))
+        nbytes = api().zeggs_live_loudness_state_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LiveLoudness: {api().zeggs_last_error().decode()}")
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        for r in range(int(rows)):
+            live_loudness_reset(self, r, 1.0)
+
+
+def live_loudness_reset(ll, row, gain=1.0):
+    """zeggs_live_loudness_reset: the row starts from nothing at gain `gain`"""
+    api().zeggs_live_loudness_reset(ll.d, ll.state, ll.state.numel(), int(row), float(gain), _stream())
+
+
+def live_loudness_hold(ll, row, on=True):
+    """zeggs_live_loudness_hold: freeze (or release) the row's gain; it goes on metering"""
+    api().zeggs_live_loudness_hold(ll.d, ll.state, ll.state.numel(), int(row), int(bool(on)), _stream())
+
+
+def live_loudness_push(ll, rows, n, rows_dev=None):
+    """zeggs_live_loudness_push: rows[:n] a HOST array of LoudRow (device addresses, counts in samples), `rows_dev` the device address
+    of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
+    api().zeggs_live_loudness_push(ll.d, rows, _records(LoudRow, rows_dev), int(n), ll.state, ll.state.numel(), _stream())
+
+
+def live_loudness_read(ll, row):
+    """zeggs_live_loudness_read (waits for the stream) -> dict(lufs, gain, blocks, gated, held, samples, hold)"""
+    out = (C.c_double * 8)()
+    api().zeggs_live_loudness_read(ll.d, ll.state, ll.state.numel(), int(row), C.addressof(out), _stream())
+    return dict(lufs=out[0], gain=out[1], blocks=int(out[2]), gated=int(out[3]), held=bool(out[4]), samples=int(out[5]), hold=bool(out[6]))
 
 
 class LiveSpeech:
