@@ -19,11 +19,18 @@
   median, p95, min, max of both, what each enqueued, and whether the cost with loudness on moves with the stream's age by more
   than the spread -> profiles/live_loudness.json.
 
+  --leg resample: what a row at a rate and format of its own costs push_many, per rows in {1, 8, 32, 64} and stream age in
+  {10 s, 600 s}: four servers in ONE process -- all rows native float32, or all rows opened at 48 kHz s16, each with loudness off
+  and on -- are fed the same rows' signals (the 48 kHz ones three samples per native sample) up to the age through push_many, then
+  tick by tick, each call synchronised before and after, taking turns, >= 200 ticks: median, p95, min, max of all four, what each
+  enqueued and uploaded, and the converting server's median over the native one's in the same run -> profiles/live_resample.json.
+
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
     python tools/live_bench.py [--out profiles/live_stream.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg push_many [--out profiles/live_push_many.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg loudness [--out profiles/live_loudness.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
+    python tools/live_bench.py --leg resample [--out profiles/live_resample.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
 """
 import argparse
 import json
@@ -219,6 +226,71 @@ def case_loudness(rows, age, steps):
                 row0_state=dict(lufs=round(state["lufs"], 4), gain=round(state["gain"], 6), blocks=state["blocks"], gated=state["gated"]))
 
 
+def case_resample(rows, age, steps, fi=48000):
+    """push_many on native float32 rows and on rows opened at 48 kHz s16, with running loudness off and on: four servers in ONE
+    process, the same rows' signals up to `age` (1 s push_many calls, drained), then tick by tick, each call synchronised before
+    and after, taking turns at going first"""
+    import numpy as np
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    up = fi // FS
+    pcm = [np.round(w * 32767.0).astype(np.int16) for w in base]
+
+    def chunk(kind, r, lo, hi):
+        if kind == "native":
+            return _samples(base, r, lo, hi)
+        w = pcm[r % len(pcm)]                                                      # sample and hold: `up` raw samples per native one
+        return w[(np.arange(up * lo, up * hi) // up + 977 * r) % len(w)]
+
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    kinds = [(k, l) for l in ("off", "on") for k in ("native", "s16")]
+    srv = {kl: live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, loudness="running" if kl[1] == "on" else None) for kl in kinds}
+    sids = {kl: [s.open(first, st, **(dict(rate=fi, pcm="s16") if kl[0] == "s16" else {})) for st in styles] for kl, s in srv.items()}
+    pos = 0
+    while pos < age * FS:
+        for kl in kinds:
+            srv[kl].push_many({sid: chunk(kl[0], r, pos, pos + FS) for r, sid in enumerate(sids[kl])})
+            srv[kl].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    t = {kl: dict(push=[], step=[]) for kl in kinds}
+    ops_seen, i = {kl: set() for kl in kinds}, 0
+    bytes0 = {kl: srv[kl].stats["uploaded_bytes"] for kl in kinds}
+    while len(t[kinds[-1]]["push"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = {k: [chunk(k, r, pos, nxt) for r in range(rows)] for k in ("native", "s16")}      # (the slicing is not what is timed)
+        for kl in kinds[i % 4:] + kinds[:i % 4]:                                   # taking turns at going first
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            srv[kl].push_many(dict(zip(sids[kl], chunks[kl[0]])))
+            torch.cuda.synchronize()
+            t[kl]["push"].append(time.perf_counter() - t0)
+            ops_seen[kl].add(srv[kl].stats["ops_last_push_many"])
+            while True:
+                t0 = time.perf_counter()
+                out = srv[kl].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[kl]["step"].append(dt)
+        pos = nxt
+    res = dict(kind="resample", rows=rows, age_s=age, tick=TICK, input_rate=fi, samples_per_row_and_tick=round(TICK * FS / FPS, 1),
+               raw_samples_per_row_and_tick=round(TICK * fi / FPS, 1))
+    for k, l in kinds:
+        res[f"push_many_{k}_loudness_{l}"] = _summary(t[(k, l)]["push"])
+        res[f"step_{k}_loudness_{l}"] = _summary(t[(k, l)]["step"])
+        res[f"ops_per_push_many_{k}_loudness_{l}"] = sorted(ops_seen[(k, l)])
+        res[f"uploaded_bytes_per_tick_{k}_loudness_{l}"] = round((srv[(k, l)].stats["uploaded_bytes"] - bytes0[(k, l)]) / len(t[(k, l)]["push"]))
+    for l in ("off", "on"):
+        res[f"s16_over_native_loudness_{l}"] = round(res[f"push_many_s16_loudness_{l}"]["median_ms"] / res[f"push_many_native_loudness_{l}"]["median_ms"], 3)
+    return res
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -250,10 +322,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64 or loudness:64:600")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600 or resample:64:600")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -261,7 +333,8 @@ def main():
         kind, *rest = a.case.split(":")
         res = (case_server(int(rest[0]), int(rest[1]), a.steps) if kind == "server" else
                case_push_many(int(rest[0]), a.steps) if kind == "push_many" else
-               case_loudness(int(rest[0]), int(rest[1]), a.steps) if kind == "loudness" else case_baseline(int(rest[0]), a.steps))
+               case_loudness(int(rest[0]), int(rest[1]), a.steps) if kind == "loudness" else
+               case_resample(int(rest[0]), int(rest[1]), a.steps) if kind == "resample" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -274,6 +347,10 @@ def main():
         cases = [f"loudness:{r}:{g}" for r in rows for g in ages]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_loudness.json")
+    if a.leg == "resample":
+        cases = [f"resample:{r}:{g}" for r in rows for g in ages]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_resample.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -309,6 +386,20 @@ def main():
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, cost_of_running_loudness_per_push_many=cost, age_effect_on_push_many_with_loudness=age_effect,
                    results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "resample":
+        cost = {}
+        for r in results:
+            cost[f"{r['rows']} rows, {r['age_s']} s"] = {
+                f"loudness_{l}": dict(native_median_ms=r[f"push_many_native_loudness_{l}"]["median_ms"],
+                                      s16_48k_median_ms=r[f"push_many_s16_loudness_{l}"]["median_ms"],
+                                      added_ms=round(r[f"push_many_s16_loudness_{l}"]["median_ms"] - r[f"push_many_native_loudness_{l}"]["median_ms"], 4),
+                                      s16_over_native=r[f"s16_over_native_loudness_{l}"]) for l in ("off", "on")}
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, push_many_native_against_48k_s16=cost, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

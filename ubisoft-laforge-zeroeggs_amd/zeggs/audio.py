@@ -222,6 +222,110 @@ def normalize_loudness_device(wav, rate, target=-20.0, device="cuda", chunk=4096
     return ops.scale_copy(w, gain), lufs
 
 
+# ----------------------------------------------------------------------------- rate conversion (csrc/resample_math.h)
+RESAMPLE_DEFAULTS = dict(zero_crossings=64, rolloff=0.95, beta=10.0)
+RESAMPLE_MAX_L, RESAMPLE_MAX_DECIMATION, RESAMPLE_MAX_ZERO_CROSSINGS = 640, 24, 64
+
+
+def resample_ratio(fi, fo):
+    """-> (L, M) = (fo, fi) / gcd(fi, fo); ValueError naming both rates where the converter does not go: M / L <= 24, L <= 640"""
+    if fi != int(fi) or fo != int(fo) or int(fi) < 1 or int(fo) < 1:
+        raise ValueError(f"resample: rates {fi} Hz -> {fo} Hz are not positive integers")
+    fi, fo = int(fi), int(fo)
+    g = int(np.gcd(fi, fo))
+    L, M = fo // g, fi // g
+    if L > RESAMPLE_MAX_L or M > RESAMPLE_MAX_DECIMATION * L:
+        raise ValueError(f"resample: {fi} Hz -> {fo} Hz is the ratio {L} / {M}: supported are L <= {RESAMPLE_MAX_L} and "
+                         f"M / L <= {RESAMPLE_MAX_DECIMATION}")
+    return L, M
+
+
+def resample_options(options=None):
+    """dict(zero_crossings, rolloff, beta) over RESAMPLE_DEFAULTS, checked: zero_crossings an integer 1 .. 64, 0 < rolloff <= 1,
+    beta >= 0 and finite.  Anything else raises ValueError."""
+    if options is None:
+        options = {}
+    if not isinstance(options, dict) or set(options) - set(RESAMPLE_DEFAULTS):
+        raise ValueError(f"resample: options are a dict with keys {sorted(RESAMPLE_DEFAULTS)}")
+    o = dict(RESAMPLE_DEFAULTS, **options)
+    try:
+        Z, rolloff, beta = int(o["zero_crossings"]), float(o["rolloff"]), float(o["beta"])
+    except (TypeError, ValueError):
+        raise ValueError(f"resample: options {options!r}") from None
+    if Z != o["zero_crossings"] or not 1 <= Z <= RESAMPLE_MAX_ZERO_CROSSINGS:
+        raise ValueError(f"resample: zero_crossings {o['zero_crossings']} (an integer 1 .. {RESAMPLE_MAX_ZERO_CROSSINGS})")
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"resample: rolloff {rolloff} (0 < rolloff <= 1)")
+    if not (np.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"resample: beta {beta} (>= 0)")
+    return dict(zero_crossings=Z, rolloff=rolloff, beta=beta)
+
+
+def resample_table(fi, fo, zero_crossings=64, rolloff=0.95, beta=10.0):
+    """The converter's coefficients in float64 -> (table [L, taps], (L, M, WL)).  Row `phase` serves the outputs m with
+    (m M) mod L == phase; its tap j sits on input k = floor(m M / L) - H + j, H = ceil(W), taps = 2 H + 1:
+    table[phase, j] = h(phase / L + H - j), h(t) = c sinc(c t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta) for |t| < W, else 0,
+    with s = min(1, L / M), c = rolloff s, W = zero_crossings / s = WL / L."""
+    L, M = resample_ratio(fi, fo)
+    o = resample_options(dict(zero_crossings=zero_crossings, rolloff=rolloff, beta=beta))
+    Z = o["zero_crossings"]
+    WL = Z * max(L, M)
+    H = -(-WL // L)
+    num = np.arange(L, dtype=np.int64)[:, None] + (H - np.arange(2 * H + 1, dtype=np.int64))[None, :] * L    # t L, exact
+    t = num / float(L)
+    W = WL / float(L)
+    c = o["rolloff"] * min(1.0, L / float(M))
+    inside = np.abs(num) < WL
+    r = np.where(inside, t / W, 0.0)
+    h = c * np.sinc(c * t) * np.i0(o["beta"] * np.sqrt(1.0 - r * r)) / np.i0(o["beta"])
+    return np.ascontiguousarray(np.where(inside, h, 0.0)), (L, M, WL)
+
+
+def resample_ready(n, L, M, WL):
+    """outputs ready after n inputs while the signal goes on (output m sits at m M / L and needs p_m + W <= n); WL == 0: n"""
+    n = int(n)
+    if WL == 0:
+        return n
+    return 0 if n * L < WL else (n * L - WL) // M + 1
+
+
+def resample_total(n, L, M):
+    """outputs of a signal of n inputs in all: ceil(n L / M)"""
+    return -(-int(n) * L // M)
+
+
+def resample_history(L, WL):
+    """past inputs a row carries from call to call: ceil(2 W)"""
+    return -(-2 * WL // L)
+
+
+def resample_device(x, fi, fo, zero_crossings=64, rolloff=0.95, beta=10.0, device="cuda"):
+    """A whole MONO signal at `fi` Hz -> float32 tensor on `device` at `fo` Hz, ceil(n fo / fi) samples
+    (zeggs_resample_whole: zeros before and behind the signal).  `x`: float samples, or int16 PCM (x = s / 32768).  Bitwise
+    what a LiveServer row opened at rate=fi receives through any cutting of the signal; for someone who wants to convert a
+    clip explicitly before generate_gesture().  fi == fo converts the format only."""
+    dev = torch.device(device)
+    if torch.is_tensor(x):
+        s16 = x.dtype == torch.int16
+        w = x if s16 else x.to(torch.float32)
+    else:
+        a = np.asarray(x)
+        s16 = a.dtype == np.int16
+        w = torch.as_tensor(np.ascontiguousarray(a if s16 else a.astype(np.float32)))
+    if w.dim() != 1:
+        raise ValueError("resample_device: mono signals only")
+    w = w.to(dev).contiguous()
+    if int(fi) == int(fo):
+        table, (L, M, WL) = np.ones((1, 1)), (1, 1, 0)
+        resample_ratio(fi, fo)
+    else:
+        table, (L, M, WL) = resample_table(fi, fo, zero_crossings, rolloff, beta)
+    n = w.numel()
+    out = torch.empty(resample_total(n, L, M), dtype=torch.float32, device=dev)
+    api().zeggs_resample_whole(torch.as_tensor(table).to(dev), L, M, WL, w, int(s16), n, out, out.numel(), ops._stream())
+    return out
+
+
 def preprocess_audio(audio_data, anim_fs, anim_length, params, feature_type, device="cuda"):
     """Drop-in for reference data_pipeline.preprocess_audio (same arguments, returns float32 ndarray
     [anim_length, 81]); `params` may be a dict or an attribute-style config."""

@@ -16,7 +16,11 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
   * close(sid) flushes the row's remaining frames with the true right-edge rules (B = 1 entry point) and frees the row;
   * LiveServer(loudness="running") normalises every row's loudness as its audio arrives (the streaming counterpart of
     audio_conf.normalize_loudness): a running BS.1770 gated estimate per row on the device, the gain applied as the samples enter
-    the window (zeggs_live_loudness_push: one more launch per push / push_many); loudness(sid) reads it, hold(sid) freezes the gain.
+    the window (zeggs_live_loudness_push: one more launch per push / push_many); loudness(sid) reads it, hold(sid) freezes the gain;
+  * open(..., rate=48000, pcm="s16") takes a stream at a rate and sample format of its own: its raw samples are uploaded and a
+    band-limited converter on the device (zeggs_resample_push: one more launch in a call where some row converts; per-row
+    history carried from call to call) writes the server-rate samples in front of the loudness stage and the window, bitwise
+    independent of the cuts, of push() against push_many() and of the other rows.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -108,25 +112,28 @@ def plan_push(rows, caps, lens, FC, width, first_sample, frames_ready):
 
 class _Staging:
     """What one push_many() uploads, as ONE block: [copy records | copy records of the second launch | mel records | loudness
-    records (`loud_rows` of them: none on a server without running loudness) | samples].
+    records (`loud_rows` of them: none on a server without running loudness) | samples], and in a call with converting rows,
+    behind the samples the call stages (tail()): [converter records | the converting rows' raw input, 2 bytes a sample for s16].
     Two pinned host blocks take turns, each guarded by an event recorded behind its copy, so a block is never rewritten while a
     copy from it may be in flight; one device block (calls on a stream are ordered)."""
 
-    def __init__(self, rows, n_samples, dev, loud_rows=0):
+    def __init__(self, rows, n_samples, dev, loud_rows=0, tail_bytes=0):
         a64 = lambda x: (x + 63) // 64 * 64  # noqa: E731
         self.rows, self.n_samples, self.loud_rows = rows, int(n_samples), int(loud_rows)
         self.o_back = a64(3 * rows * C.sizeof(ops.Seg))
         self.o_mel = self.o_back + a64(rows * C.sizeof(ops.Seg))
         self.o_loud = self.o_mel + a64(rows * C.sizeof(ops.MelRow))
         self.o_smp = self.o_loud + a64(self.loud_rows * C.sizeof(ops.LoudRow))
-        self.nbytes = self.o_smp + 4 * self.n_samples
+        self.tail_bytes = int(tail_bytes)               # room behind the samples for converter records and raw input
+        self.nbytes = self.o_smp + 4 * self.n_samples + self.tail_bytes
         self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
         self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
         self.view = []
         for h in self.host:
             b = h.numpy()
             self.view.append(dict(segs=(ops.Seg * (3 * rows)).from_buffer(b, 0), back=(ops.Seg * rows).from_buffer(b, self.o_back),
-                                  mel=(ops.MelRow * rows).from_buffer(b, self.o_mel), smp=b[self.o_smp:].view(np.float32),
+                                  mel=(ops.MelRow * rows).from_buffer(b, self.o_mel),
+                                  smp=b[self.o_smp:self.o_smp + 4 * self.n_samples].view(np.float32), block=b,
                                   loud=(ops.LoudRow * self.loud_rows).from_buffer(b, self.o_loud)))
         self.events, self.turn = [None, None], 0
 
@@ -137,8 +144,15 @@ class _Staging:
             self.events[self.turn].synchronize()
         return self.view[self.turn]
 
-    def upload(self, n_samples):
-        nb = self.o_smp + 4 * int(n_samples)
+    def tail(self, n_samples, n_records, raw_bytes):
+        """where a call that stages n_samples floats puts its converter records and raw input, and where the block then ends"""
+        a64 = lambda x: (x + 63) // 64 * 64  # noqa: E731
+        o_rs = a64(self.o_smp + 4 * int(n_samples))
+        o_raw = o_rs + a64(int(n_records) * C.sizeof(ops.ResampleRow))
+        return o_rs, o_raw, o_raw + int(raw_bytes)
+
+    def upload(self, n_samples, end=None):
+        nb = self.o_smp + 4 * int(n_samples) if end is None else int(end)
         self.dev[:nb].copy_(self.host[self.turn][:nb], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
@@ -180,14 +194,41 @@ def loudness_options(loudness):
     return dict(target=target, horizon=horizon, warmup=warmup, gain_db=(lo, hi), ring_blocks=int(blocks))
 
 
+def resample_row(rate, pcm, fs):
+    """open()'s `rate` / `pcm` on a server at `fs` Hz -> None (today's row: float32 at the server's rate) or (input rate, format
+    code).  ValueError for an unknown format and for a rate the converter does not take (naming both rates)."""
+    if pcm not in ops.RS_FORMATS:
+        raise ValueError(f"LiveServer.open: pcm {pcm!r} (one of {sorted(ops.RS_FORMATS)})")
+    if rate is None or rate == fs:
+        return None if pcm == "f32" else (int(fs), ops.RS_FORMATS[pcm])
+    if isinstance(rate, bool) or not isinstance(rate, (int, float, np.integer, np.floating)):
+        raise ValueError(f"LiveServer.open: rate {rate!r} Hz (the server runs at {fs} Hz)")
+    audio.resample_ratio(rate, fs)
+    return int(rate), ops.RS_FORMATS[pcm]
+
+
+def _samples(chunk, rs):
+    """a pushed chunk as the flat array that is uploaded: float32, or int16 for a row opened with pcm="s16"; an array whose dtype
+    does not match the row's format is refused"""
+    a = np.asarray(chunk)
+    if rs is not None and rs["fmt"] == ops.RS_S16:
+        if a.dtype != np.int16:
+            raise TypeError(f"LiveServer: a row opened with pcm='s16' takes int16 samples, not {a.dtype}")
+        return np.ascontiguousarray(a).reshape(-1)
+    if hasattr(chunk, "dtype") and a.dtype.kind in "iub":
+        raise TypeError(f"LiveServer: a float32 row takes float samples in [-1, 1), not {a.dtype} (open(..., pcm='s16') for 16-bit PCM)")
+    return np.ascontiguousarray(a, dtype=np.float32).reshape(-1)
+
+
 class _Row:
-    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade")
+    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs")
 
     def __init__(self, sid):
         self.sid, self.n, self.base = sid, 0, 0          # samples received (absolute) / absolute index of window[0]
         self.n_feat, self.fbase, self.n_ring = 0, 0, 0   # feature rows computed / frame of feats[r, 0] / frames in the ring
         self.kd, self.sent0 = 1, False                   # first frame not yet decoded / frame 0 (the first pose) handed out
         self.k_style, self.fade = 0, 0                   # last set_style: from frame k_style on, over `fade` frames
+        self.rs = None                                   # a converting row: dict(fi, fmt, table, L, M, WL, n_in: raw samples received)
 
 
 class LiveServer:
@@ -199,12 +240,17 @@ class LiveServer:
     counterpart of audio_conf.normalize_loudness: each row keeps a BS.1770 gated estimate of what it has received over the last
     `horizon` seconds, and new samples enter its window times the gain that brings the estimate to `target` LUFS (one more
     launch per push / push_many: zeggs_live_loudness_push).  With None a conf that asks for loudness normalisation
-    is refused, as before: there is no whole signal to measure."""
+    is refused, as before: there is no whole signal to measure.
+
+    `resample`: None or dict(zero_crossings=64, rolloff=0.95, beta=10.0) -- the filter of the rows that open() takes at a rate
+    or sample format of their own (audio.resample_options).  A server on which no such row was opened holds no
+    converter state and enqueues what it always did."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None):
         g = audio_conf
         loud = loudness_options(loudness)
+        self.resample_conf = audio.resample_options(resample)
         if loud is None and g.get("normalize_loudness"):
             raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
         if tuple(feature_type) != ("mel_spec", "energy"):
@@ -260,13 +306,14 @@ class LiveServer:
                                                                 loud["gain_db"], audio._kweighting(self.fs), self.dev)
         self._chunk = z(2048) if loud else None
         self._stage = _Staging(R, R * 2048, self.dev, R if loud else 0)
+        self._rs = None                              # ops.LiveResample, from the first open(..., rate= / pcm=) on
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
         self._sids, self._next_sid = {}, 0
         self._ops = 0
         self.stats = dict(uploaded_samples=0, window_capacity=[int(window_capacity)] * R, ring_bytes=self.ring.numel() * 4,
-                          launches_per_step=0, steps=0, ops_last_push_many=0)
+                          launches_per_step=0, steps=0, ops_last_push_many=0, uploaded_bytes=0, resampled_rows=0)
 
     # ------------------------------------------------------------------ rows
     def _row(self, sid):
@@ -275,10 +322,15 @@ class LiveServer:
         r = self._sids[sid]
         return r, self._rows[r]
 
-    def open(self, first_pose, style, gain=1.0):
+    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32"):
         """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
         -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
-        what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing."""
+        what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing.
+        `rate` / `pcm`: what this stream delivers -- `rate` Hz (None: the server's rate) as "f32" (float32 in [-1, 1)) or "s16"
+        (int16 PCM, x = s / 32768).  Anything but float32 at the server's rate is converted on the device as it arrives
+        (zeggs_resample_push: band-limited, in front of the loudness stage and the window); a rate the converter does not
+        take raises ValueError naming both rates."""
+        rs = resample_row(rate, pcm, self.fs)
         if self._loud is None and float(gain) != 1.0:
             raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
         free = [r for r in range(self.rows) if self._rows[r] is None]
@@ -297,7 +349,13 @@ class LiveServer:
         self.pose[r], self.rpos[r], self.rrot[r] = pose0[0], f32(root_pos)[0], f32(root_rot)[0]
         self.gaze[r] = gaze0
         self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
-        self._rows[r], self._sids[sid] = _Row(sid), r
+        row = _Row(sid)
+        if rs is not None:
+            if self._rs is None:
+                self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
+            row.rs = dict(self._rs.table(rs[0]), fi=rs[0], fmt=rs[1], n_in=0)
+            ops.live_resample_reset(self._rs, r)
+        self._rows[r], self._sids[sid] = row, r
         return sid
 
     # ------------------------------------------------------------------ audio
@@ -331,7 +389,9 @@ class LiveServer:
         """append samples (float32 in [-1, 1)) to stream `sid`: only they are uploaded; the mel rows that became computable are
         computed.  Frames leave through step()."""
         r, row = self._row(sid)
-        chunk = torch.as_tensor(np.ascontiguousarray(wav_chunk, dtype=np.float32))
+        if row.rs is not None:                           # a converting row: the same launches as push_many(), one record each
+            return self.push_many({sid: wav_chunk})
+        chunk = torch.as_tensor(_samples(wav_chunk, None))
         m = int(chunk.numel())
         if m == 0:
             return
@@ -358,6 +418,7 @@ class LiveServer:
             ops.live_loudness_push(self._loud, rec, 1)
         row.n += m
         self.stats["uploaded_samples"] += m
+        self.stats["uploaded_bytes"] += 4 * m
         ready = min(ops.mel_frames_ready(self.mel, row.n), audio.n_anim_frames(row.n, self.fs, self.fps) - 1)
         self._features(r, row, ready, final=False)       # (never ahead of the final frame count: it can only grow)
 
@@ -370,15 +431,30 @@ class LiveServer:
         more new frames than a feature block holds) reallocates first, as in push().  An unknown sid raises KeyError before
         anything changes.  With running loudness the new samples leave the copy list and are the records of ONE
         zeggs_live_loudness_push (uploaded in the same block): <= 6 operations; windows, features and loudness state are
-        bitwise those of push(), however the signal is cut and whichever rows share a call."""
-        items = [(self._row(sid), np.ascontiguousarray(c, dtype=np.float32).reshape(-1)) for sid, c in chunks.items()]
-        items = [(r, row, c) for (r, row), c in items if c.size]
+        bitwise those of push(), however the signal is cut and whichever rows share a call.
+        A row opened at a rate or format of its own takes its raw samples (int16 for pcm="s16"): they ride behind the float
+        samples of the same one upload, the host plans with audio.resample_ready how many converted samples the row owes, and
+        ONE zeggs_resample_push for all such rows writes them where the copy launch or the loudness launch finds its sources
+        -- exactly one more operation, <= 6 (<= 7 with running loudness), and only in a call in which some row converts."""
+        rows = [self._row(sid) for sid in chunks]
+        items = [(r, row, _samples(c, row.rs)) for (r, row), c in zip(rows, chunks.values())]
+        self._push_rows([(r, row, c) for r, row, c in items if c.size], False)
+
+    def _push_rows(self, items, final):
+        """push_many() behind its argument checks; `final` (close()): the converting rows' signals end here, their tails enter
+        the windows against zero padding"""
         self.stats["ops_last_push_many"] = n_ops = 0
-        if not items:
+        conv = [i for i, (_, w, _) in enumerate(items) if w.rs is not None]
+        lens = [c.size for _, _, c in items]
+        for i in conv:
+            q, n1 = items[i][1].rs, items[i][1].rs["n_in"] + lens[i]
+            due = audio.resample_total(n1, q["L"], q["M"]) if final else audio.resample_ready(n1, q["L"], q["M"], q["WL"])
+            lens[i] = due - items[i][1].n               # (a converting row's n: converted samples in its window = outputs so far)
+        if not any(c.size or m for (_, _, c), m in zip(items, lens)):
             return
         F = self.feats.shape[2]
         plan = plan_push([dict(n=w.n, base=w.base, n_feat=w.n_feat, fbase=w.fbase, n_ring=w.n_ring) for _, w, _ in items],
-                         [self.window[r].numel() for r, _, _ in items], [c.size for _, _, c in items], self.FC, F,
+                         [self.window[r].numel() for r, _, _ in items], lens, self.FC, F,
                          lambda k: ops.mel_window_first_sample(self.mel, k),
                          lambda n: min(ops.mel_frames_ready(self.mel, n), audio.n_anim_frames(n, self.fs, self.fps) - 1))
         # ---- growth, the one exception to "nothing is allocated"
@@ -389,16 +465,33 @@ class LiveServer:
             if p["swap"] and self._alt[r].numel() < p["cap"]:
                 self._alt[r] = torch.zeros(p["cap"], device=self.dev)
                 n_ops += 1
-        if plan["n_stage"] > self._stage.n_samples:
+        raw_bytes = sum((items[i][2].nbytes + 63) // 64 * 64 for i in conv)
+        if plan["n_stage"] > self._stage.n_samples or (conv and self._stage.tail(plan["n_stage"], len(conv), raw_bytes)[2] > self._stage.nbytes):
             self._stage.idle()
-            self._stage = _Staging(self.rows, 2 * plan["n_stage"], self.dev, self._stage.loud_rows)
-        # ---- the staging block: records with device addresses, then the samples
+            n_smp = 2 * plan["n_stage"] if plan["n_stage"] > self._stage.n_samples else self._stage.n_samples
+            self._stage = _Staging(self.rows, n_smp, self.dev, self._stage.loud_rows,
+                                   max(self._stage.tail_bytes, 2 * (raw_bytes + self.rows * C.sizeof(ops.ResampleRow) + 128)) if conv
+                                   else self._stage.tail_bytes)
+        # ---- the staging block: records with device addresses, then the samples (a converting row's share of the sample area
+        # is written by the converter on the device), then the converter's records and raw input
         stg = self._stage
         blk = stg.take()
-        pos = 0
-        for _, _, c in items:
-            blk["smp"][pos:pos + c.size] = c
-            pos += c.size
+        pos, end = 0, None
+        for (_, w, c), m in zip(items, lens):
+            if w.rs is None:
+                blk["smp"][pos:pos + m] = c
+            pos += m
+        if conv:
+            o_rs, o_raw, end = stg.tail(plan["n_stage"], len(conv), raw_bytes)
+            rs_recs = (ops.ResampleRow * len(conv)).from_buffer(blk["block"], o_rs)
+            offs = np.concatenate([[0], np.cumsum(lens)])
+            for q, i in zip(rs_recs, conv):
+                (r, w, c), t = items[i], items[i][1].rs
+                blk["block"][o_raw:o_raw + c.nbytes] = c.view(np.uint8)
+                q.src, q.dst, q.table = stg.dev.data_ptr() + o_raw, stg.dev.data_ptr() + stg.o_smp + 4 * int(offs[i]), t["table"].data_ptr()
+                q.count, q.n_in, q.n_out, q.outputs, q.WL = c.size, t["n_in"], w.n, lens[i], t["WL"]
+                q.row, q.format, q.final, q.L, q.M = r, t["fmt"], int(final), t["L"], t["M"]
+                o_raw += (c.nbytes + 63) // 64 * 64
         block_bytes = 4 * self.FC * F
         where = {"win": lambda i: self.window[items[i][0]].data_ptr(), "alt": lambda i: self._alt[items[i][0]].data_ptr(),
                  "stage": lambda i: stg.dev.data_ptr() + stg.o_smp, "feats": lambda i: self.feats.data_ptr() + items[i][0] * block_bytes,
@@ -422,11 +515,14 @@ class LiveServer:
                 q.out = self.feats.data_ptr() + r * block_bytes + 4 * (p["k0"] - p["fbase"]) * F
                 q.base, q.n_samples, q.k0, q.k1, q.final = p["base"], p["n"], p["k0"], p["k1"], 0
                 n_mel += 1
-        # ---- at most five operations (six with running loudness)
+        # ---- at most five operations (six with running loudness), one more in a call with converting rows
         with torch.no_grad():
-            stg.upload(plan["n_stage"])
+            stg.upload(plan["n_stage"], end)
             n_ops += 1
-            if segs or self._loud is None:
+            if conv:
+                ops.live_resample_push(self._rs, rs_recs, len(conv), stg.dev.data_ptr() + o_rs)
+                n_ops += 1
+            if segs:
                 ops.copy_segments(blk["segs"], len(segs), stg.dev.data_ptr())
                 n_ops += 1
             if loud:
@@ -442,7 +538,12 @@ class LiveServer:
                 self.window[r], self._alt[r] = self._alt[r], self.window[r]
                 self.stats["window_capacity"][r] = int(self.window[r].numel())
             row.n, row.base, row.n_feat, row.fbase = p["n"], p["base"], p["n_feat"], p["fbase"]
-            self.stats["uploaded_samples"] += int(c.size)
+            if row.rs is None:
+                self.stats["uploaded_samples"] += int(c.size)
+            else:
+                row.rs["n_in"] += int(c.size)
+                self.stats["resampled_rows"] += 1
+        self.stats["uploaded_bytes"] += stg.o_smp + 4 * plan["n_stage"] if end is None else end
         self.stats["ops_last_push_many"] = n_ops
 
     # ------------------------------------------------------------------ running loudness
@@ -601,6 +702,8 @@ class LiveServer:
         """end of stream `sid`'s signal: its remaining frames with the right-edge rules of the offline path (reflect padding of the
         STFT, replicate padding of the speech encoder), decoded for that row alone; the row is free again"""
         r, row = self._row(sid)
+        if row.rs is not None:                           # the converter's tail enters the window ahead of the final features
+            self._push_rows([(r, row, np.zeros(0, np.int16 if row.rs["fmt"] == ops.RS_S16 else np.float32))], True)
         n_total = audio.n_anim_frames(row.n, self.fs, self.fps)
         outs = []
         with torch.no_grad():

@@ -12,7 +12,8 @@ import torch
 
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
-                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow, Seg, SpeechDims, SpeechPtrs,
+                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow, ResampleDims, ResampleRow,
+                   Seg, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
@@ -1004,6 +1005,51 @@ def live_loudness_read(ll, row):
     out = (C.c_double * 8)()
     api().zeggs_live_loudness_read(ll.d, ll.state, ll.state.numel(), int(row), C.addressof(out), _stream())
     return dict(lufs=out[0], gain=out[1], blocks=int(out[2]), gated=int(out[3]), held=bool(out[4]), samples=int(out[5]), hold=bool(out[6]))
+
+
+RS_F32, RS_S16 = 0, 1              # ZEGGS_RS_F32 / ZEGGS_RS_S16
+RS_FORMATS = {"f32": RS_F32, "s16": RS_S16}
+
+
+class LiveResample:
+    """The rate converter of `rows` live rows (include/zeggs_hip_resample.h): the state -- per row a ring of past input samples,
+    sized for the largest supported decimation at the server's `zero_crossings` -- and the coefficient tables on the device, one
+    per input rate, built in float64 (audio.resample_table) and uploaded when a row first asks for the rate (open(), never on
+    the tick path).  `fo`: the server's rate; `options`: audio.resample_options()."""
+
+    def __init__(self, fo, rows, options, device):
+        from . import audio
+        self.fo, self.options, self.dev = int(fo), audio.resample_options(options), torch.device(device)
+        self.d = ResampleDims(int(rows), 2 * self.options["zero_crossings"] * audio.RESAMPLE_MAX_DECIMATION)
+        nbytes = api().zeggs_resample_state_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LiveResample: {api().zeggs_last_error().decode()}")
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=self.dev)
+        self.tables = {}
+
+    def table(self, fi):
+        """-> dict(table: float64 tensor on the device, L, M, WL) for input rate `fi` (fi == fo: the pass-through table, one tap
+        of 1.0); ValueError for a rate the converter does not take"""
+        from . import audio
+        fi = int(fi) if fi == int(fi) else fi
+        if fi not in self.tables:
+            if fi == self.fo:
+                tab, (L, M, WL) = np.ones((1, 1)), (1, 1, 0)
+            else:
+                tab, (L, M, WL) = audio.resample_table(fi, self.fo, **self.options)
+            self.tables[fi] = dict(table=torch.as_tensor(tab).to(self.dev).contiguous(), L=L, M=M, WL=WL)
+        return self.tables[fi]
+
+
+def live_resample_reset(rs, row):
+    """zeggs_resample_reset: the row's history is all zeros"""
+    api().zeggs_resample_reset(rs.d, rs.state, rs.state.numel(), int(row), _stream())
+
+
+def live_resample_push(rs, rows, n, rows_dev=None):
+    """zeggs_resample_push: rows[:n] a HOST array of ResampleRow (device addresses, the caller's counters), `rows_dev` the device
+    address of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
+    api().zeggs_resample_push(rs.d, rows, _records(ResampleRow, rows_dev), int(n), rs.state, rs.state.numel(), _stream())
 
 
 class LiveSpeech:
