@@ -25,12 +25,21 @@
   tick by tick, each call synchronised before and after, taking turns, >= 200 ticks: median, p95, min, max of all four, what each
   enqueued and uploaded, and the converting server's median over the native one's in the same run -> profiles/live_resample.json.
 
+  --leg frames: what the output head costs a step and what it saves a client, per rows in {1, 8, 32, 64} and stream age in
+  {10 s, 600 s}: two servers in ONE process, frames=None and frames with all three outputs (local, world, bvh), are fed the same
+  rows' signals up to the age through push_many, then tick by tick the same chunks; each step() synchronised before and after,
+  taking turns at going first, >= 200 ticks: median, p95, min, max of both, what each enqueues per step (the head adds exactly
+  two operations: asserted), the bytes it downloads per step -- and, timed in the same run on the plain server's output, what a
+  client has to do today for the BVH part of the same result: per stream anim.bvh_channels on the returned tensors and the
+  .cpu() of both -> profiles/live_frames.json.
+
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
     python tools/live_bench.py [--out profiles/live_stream.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg push_many [--out profiles/live_push_many.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg loudness [--out profiles/live_loudness.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg resample [--out profiles/live_resample.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
+    python tools/live_bench.py --leg frames [--out profiles/live_frames.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
 """
 import argparse
 import json
@@ -291,6 +300,62 @@ def case_resample(rows, age, steps, fi=48000):
     return res
 
 
+def case_frames(rows, age, steps):
+    """step() with the output head off and on (local, world, bvh), and the client-side conversion of the plain server's output:
+    two servers in ONE process, the same rows' signals up to `age` (1 s push_many calls, drained), then tick by tick"""
+    import torch
+    from zeggs import anim, live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    head = dict(parents=synth.PARENTS, names=synth.BONE_NAMES, what=("local", "world", "bvh"), order="zyx", text=False)
+    srv = {k: live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, frames=v) for k, v in (("off", None), ("on", head))}
+    sids = {k: [s.open(first, st, **(dict(start_position=[0.0, 0.0, 0.0], start_rotation=[1.0, 0.0, 0.0, 0.0]) if k == "on" else {}))
+                for st in styles] for k, s in srv.items()}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    J = len(synth.PARENTS)
+    t = {k: [] for k in ("off", "on", "client")}
+    ops_seen, i = {k: set() for k in srv}, 0
+    bytes0 = srv["on"].stats["frame_bytes"]
+    while len(t["on"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]
+        for k in (("off", "on") if i % 2 else ("on", "off")):                      # taking turns at going first
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            while True:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows and ("frames" in out[sids[k][0]]) == (k == "on")
+                t[k].append(dt)
+                ops_seen[k].add(srv[k].stats["launches_per_step"])
+                if k == "off":                                                     # what a client does with it today, per stream
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    for o in out.values():
+                        n = o["pose"].shape[0]
+                        p, e = anim.bvh_channels(o["rpos"], o["rrot"], o["pose"][:, 6:6 + 3 * J].reshape(n, J, 3),
+                                                 o["pose"][:, 6 + 3 * J:6 + 9 * J].reshape(n, J, 2, 3), [0.0, 0.0, 0.0], [1.0, 0.0, 0.0, 0.0])
+                        p, e = p.cpu(), e.cpu()
+                    t["client"].append(time.perf_counter() - t0)
+        pos = nxt
+    assert ops_seen["on"] == {x + 2 for x in ops_seen["off"]} and len(ops_seen["on"]) == 1, (ops_seen)
+    return dict(kind="frames", rows=rows, age_s=age, tick=TICK, step_off=_summary(t["off"]), step_on=_summary(t["on"]),
+                client_bvh_channels_and_cpu=_summary(t["client"]), launches_per_step_off=sorted(ops_seen["off"]),
+                launches_per_step_on=sorted(ops_seen["on"]), frame_bytes_per_step=round((srv["on"].stats["frame_bytes"] - bytes0) / len(t["on"])))
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -322,10 +387,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600 or resample:64:600")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600 or frames:64:600")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -334,7 +399,8 @@ def main():
         res = (case_server(int(rest[0]), int(rest[1]), a.steps) if kind == "server" else
                case_push_many(int(rest[0]), a.steps) if kind == "push_many" else
                case_loudness(int(rest[0]), int(rest[1]), a.steps) if kind == "loudness" else
-               case_resample(int(rest[0]), int(rest[1]), a.steps) if kind == "resample" else case_baseline(int(rest[0]), a.steps))
+               case_resample(int(rest[0]), int(rest[1]), a.steps) if kind == "resample" else
+               case_frames(int(rest[0]), int(rest[1]), a.steps) if kind == "frames" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -351,6 +417,10 @@ def main():
         cases = [f"resample:{r}:{g}" for r in rows for g in ages]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_resample.json")
+    if a.leg == "frames":
+        cases = [f"frames:{r}:{g}" for r in rows for g in ages]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_frames.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -400,6 +470,27 @@ def main():
                                       s16_over_native=r[f"s16_over_native_loudness_{l}"]) for l in ("off", "on")}
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, push_many_native_against_48k_s16=cost, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "frames":
+        table, age_effect = {}, {}
+        for r in results:
+            table[f"{r['rows']} rows, {r['age_s']} s"] = dict(
+                step_off_median_ms=r["step_off"]["median_ms"], step_off_p95_ms=r["step_off"]["p95_ms"], step_on_median_ms=r["step_on"]["median_ms"],
+                step_on_p95_ms=r["step_on"]["p95_ms"], client_median_ms=r["client_bvh_channels_and_cpu"]["median_ms"],
+                client_p95_ms=r["client_bvh_channels_and_cpu"]["p95_ms"],
+                head_added_ms=round(r["step_on"]["median_ms"] - r["step_off"]["median_ms"], 4), frame_bytes_per_step=r["frame_bytes_per_step"])
+        if len(ages) >= 2:
+            for n in rows:
+                lo, hi = ([r for r in results if r["rows"] == n and r["age_s"] == g][0]["step_on"] for g in (ages[0], ages[-1]))
+                spread = max(lo["p95_ms"] - lo["min_ms"], hi["p95_ms"] - hi["min_ms"])
+                age_effect[str(n)] = dict(median_ms_young=lo["median_ms"], median_ms_old=hi["median_ms"], spread_ms=round(spread, 4),
+                                          differs_by_more_than_the_spread=abs(hi["median_ms"] - lo["median_ms"]) > spread)
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, step_without_and_with_the_head_and_the_client_side_conversion=table,
+                   age_effect_on_step_time_with_the_head=age_effect, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

@@ -20,7 +20,11 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
   * open(..., rate=48000, pcm="s16") takes a stream at a rate and sample format of its own: its raw samples are uploaded and a
     band-limited converter on the device (zeggs_resample_push: one more launch in a call where some row converts; per-row
     history carried from call to call) writes the server-rate samples in front of the loudness stage and the window, bitwise
-    independent of the cuts, of push() against push_many() and of the other rows.
+    independent of the cuts, of push() against push_many() and of the other rows;
+  * LiveServer(frames=dict(parents=...)) adds an output head: step() and close() also return, under "frames", what a renderer or
+    a BVH recorder takes of the new frames -- the placed root, local and world-space joint transforms, BVH motion rows (and their
+    text) -- converted for all rows by ONE launch (zeggs_live_frames) and brought down by ONE copy into pinned memory per step;
+    open(..., start_position=, start_rotation=) says where a character stands, bvh_header(sid, n) gives the head of its file.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -30,7 +34,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import audio, ops
+from . import anim, audio, ops
 
 LOOKAHEAD = 15        # (31 - 1) / 2 frames of the speech encoder's second convolution
 
@@ -207,6 +211,120 @@ def resample_row(rate, pcm, fs):
     return int(rate), ops.RS_FORMATS[pcm]
 
 
+FRAMES_DEFAULTS = dict(parents=None, names=None, what=("local", "world", "bvh"), order="zyx", text=False)
+
+
+def frames_options(frames):
+    """LiveServer's `frames` argument -> None (off) or dict(parents, names, what: the names in the order local, world, bvh, mask:
+    their bits, order, text, seq: the joint order of the BVH rows).  ValueError for anything but a dict with keys of
+    FRAMES_DEFAULTS, for a dict without `parents` or with a skeleton the kernel refuses, an unknown `what`, a channel order
+    quat.to_euler does not have, `names` of another length, and `text` without "bvh"."""
+    if frames is None:
+        return None
+    if not isinstance(frames, dict) or set(frames) - set(FRAMES_DEFAULTS):
+        raise ValueError(f"LiveServer: frames is None or a dict with keys {sorted(FRAMES_DEFAULTS)}")
+    o = dict(FRAMES_DEFAULTS, **frames)
+    if o["parents"] is None:
+        raise ValueError("LiveServer: frames needs the skeleton: frames=dict(parents=...)")
+    parents = [int(p) for p in o["parents"]]
+    seq = ops.frames_seq(parents)
+    mask = ops.frames_what(o["what"])
+    if o["order"] not in ("zyx", "xzy"):
+        raise ValueError(f"LiveServer: frames order {o['order']!r} ('zyx' or 'xzy': what quat.to_euler converts to)")
+    names = None if o["names"] is None else [str(n) for n in o["names"]]
+    if names is not None and len(names) != len(parents):
+        raise ValueError(f"LiveServer: frames has {len(names)} names for {len(parents)} joints")
+    if o["text"] and not mask & ops.FRAMES_WHAT["bvh"]:
+        raise ValueError("LiveServer: frames text=True formats the BVH rows: what must hold 'bvh'")
+    return dict(parents=parents, names=names, what=tuple(n for n in ("local", "world", "bvh") if mask & ops.FRAMES_WHAT[n]), mask=mask,
+                order=o["order"], text=bool(o["text"]), seq=seq)
+
+
+def frames_placement(start_position, start_rotation):
+    """open()'s placement -> None (neither given: the root is handed out as it is) or (position [3], rotation [4], float64);
+    ValueError when only one of the two is given or a shape is wrong"""
+    if start_position is None and start_rotation is None:
+        return None
+    if start_position is None or start_rotation is None:
+        raise ValueError("LiveServer.open: start_position and start_rotation come together (both or neither)")
+    pos, rot = np.asarray(start_position, np.float64).reshape(-1), np.asarray(start_rotation, np.float64).reshape(-1)
+    if pos.size != 3 or rot.size != 4 or not (np.isfinite(pos).all() and np.isfinite(rot).all()):
+        raise ValueError("LiveServer.open: start_position is [3], start_rotation a quaternion [4] (w first)")
+    return pos, rot
+
+
+def frames_unpack(buf, counts, J, mask, copy=True):
+    """the packed block of one zeggs_live_frames call on the host (uint8) -> per record the dict of arrays.  The block:
+    [BVH rows float64 [N][3 + 3J] | LOCAL float32 [N][7 + 7J] | WORLD float32 [N][7J]], N = sum(counts), an area whose bit is off
+    in `mask` missing; record i owns rows sum(counts[:i]) .. of each."""
+    N, BL, LL, WL = int(sum(counts)), 3 + 3 * J, 7 + 7 * J, 7 * J
+    use = [bool(mask & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
+    o_loc = N * BL * 8 * use[0]
+    o_wld = o_loc + N * LL * 4 * use[1]
+    bvh = buf[:o_loc].view(np.float64).reshape(N, BL) if use[0] else None
+    loc = buf[o_loc:o_wld].view(np.float32).reshape(N, LL) if use[1] else None
+    wld = buf[o_wld:o_wld + N * WL * 4].view(np.float32).reshape(N, WL) if use[2] else None
+    out, a = [], 0
+    own = (lambda x: np.array(x)) if copy else (lambda x: x)
+    for c in counts:
+        o = {}
+        if use[1]:
+            x = loc[a:a + c]
+            o.update(root_pos=own(x[:, 0:3]), root_rot=own(x[:, 3:7]), lrot=own(x[:, 7:7 + 4 * J]).reshape(c, J, 4),
+                     lpos=own(x[:, 7 + 4 * J:]).reshape(c, J, 3))
+        if use[2]:
+            x = wld[a:a + c]
+            o.update(gpos=own(x[:, :3 * J]).reshape(c, J, 3), grot=own(x[:, 3 * J:]).reshape(c, J, 4))
+        if use[0]:
+            o["bvh"] = own(bvh[a:a + c])
+        out.append(o)
+        a += c
+    return out
+
+
+def frames_cat(parts):
+    """the "frames" of consecutive steps of a stream as one: arrays concatenated along the frames, "text" joined"""
+    return {k: b"".join(p[k] for p in parts) if k == "text" else np.concatenate([p[k] for p in parts]) for k in parts[0]}
+
+
+def frames_block_bytes(N, J, mask):
+    """bytes of the packed block of N frames (frames_unpack)"""
+    per = sum(n for k, n in (("bvh", (3 + 3 * J) * 8), ("local", (7 + 7 * J) * 4), ("world", 7 * J * 4)) if mask & ops.FRAMES_WHAT[k])
+    return int(N) * per
+
+
+class _FrameStaging:
+    """What the output head of a step needs beside the rows' state, allocated once: the device block the one launch writes
+    (frames_unpack's layout, sized for every row at max_frames), a small ring of pinned host blocks the one download lands in,
+    each guarded by the event recorded behind its copy, and the records of the launch in pinned host memory -- page-locked
+    memory is device accessible, so the kernel reads its records where the host wrote them and no upload is enqueued.  The
+    records are rewritten only after the step that used them has waited for its download, which is ordered behind the launch."""
+    RING = 3
+
+    def __init__(self, rows, max_frames, J, mask, dev):
+        self.J, self.mask = J, mask
+        self.nbytes = frames_block_bytes(rows * max_frames, J, mask)
+        self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self.events, self.turn = [None] * self.RING, 0
+        self.rec_mem = torch.zeros(rows * C.sizeof(ops.FramesRow), dtype=torch.uint8).pin_memory()
+        self.recs = (ops.FramesRow * rows).from_buffer(self.rec_mem.numpy())
+
+    def download(self, nbytes):
+        """one device-to-host copy of the block's first nbytes into the next pinned block -> that block's bytes, once they are
+        there (a view: frames_unpack copies what it hands out)"""
+        self.turn = (self.turn + 1) % self.RING
+        if self.events[self.turn] is not None:
+            self.events[self.turn].synchronize()
+        host = self.host[self.turn]
+        host[:nbytes].copy_(self.dev[:nbytes], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[self.turn] = ev
+        ev.synchronize()
+        return host.numpy()[:nbytes]
+
+
 def _samples(chunk, rs):
     """a pushed chunk as the flat array that is uploaded: float32, or int16 for a row opened with pcm="s16"; an array whose dtype
     does not match the row's format is refused"""
@@ -221,7 +339,7 @@ def _samples(chunk, rs):
 
 
 class _Row:
-    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs")
+    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs", "offsets")
 
     def __init__(self, sid):
         self.sid, self.n, self.base = sid, 0, 0          # samples received (absolute) / absolute index of window[0]
@@ -229,6 +347,7 @@ class _Row:
         self.kd, self.sent0 = 1, False                   # first frame not yet decoded / frame 0 (the first pose) handed out
         self.k_style, self.fade = 0, 0                   # last set_style: from frame k_style on, over `fade` frames
         self.rs = None                                   # a converting row: dict(fi, fmt, table, L, M, WL, n_in: raw samples received)
+        self.offsets = None                              # frames: the joint positions of frame 0 as placed (the OFFSETs of a BVH file)
 
 
 class LiveServer:
@@ -244,13 +363,22 @@ class LiveServer:
 
     `resample`: None or dict(zero_crossings=64, rolloff=0.95, beta=10.0) -- the filter of the rows that open() takes at a rate
     or sample format of their own (audio.resample_options).  A server on which no such row was opened holds no
-    converter state and enqueues what it always did."""
+    converter state and enqueues what it always did.
+
+    `frames`: None or dict(parents=..., names=None, what=("local", "world", "bvh"), order="zyx", text=False) -- the output head
+    (frames_options): step() and close() also return, under "frames", what a renderer or a BVH recorder takes of the
+    new frames, as host arrays: "root_pos" [n, 3], "root_rot" [n, 4], "lrot" [n, J, 4], "lpos" [n, J, 3] (local), "gpos"
+    [n, J, 3], "grot" [n, J, 4] (world, the root folded into joint 0), "bvh" [n, 3 + 3J] float64 (the motion rows of a BVH file
+    in the joint order of bvh_header()) and with text=True "text", those rows as the bytes of the file.  One more launch
+    (zeggs_live_frames) and one download per step whatever the number of rows; quaternions keep their sign from frame to
+    frame and from step to step.  With None the server holds no such state and enqueues what it always did."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None, resample=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None):
         g = audio_conf
         loud = loudness_options(loudness)
         self.resample_conf = audio.resample_options(resample)
+        self.frames_conf = frames_options(frames)
         if loud is None and g.get("normalize_loudness"):
             raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
         if tuple(feature_type) != ("mel_spec", "energy"):
@@ -307,6 +435,14 @@ class LiveServer:
         self._chunk = z(2048) if loud else None
         self._stage = _Staging(R, R * 2048, self.dev, R if loud else 0)
         self._rs = None                              # ops.LiveResample, from the first open(..., rate= / pcm=) on
+        self._fr = self._fr_stage = None             # the output head: the rows' state (ops.LiveFrames) and its staging blocks
+        if self.frames_conf is not None:
+            fc = self.frames_conf
+            if 6 + 15 * len(fc["parents"]) != PO:
+                raise ValueError(f"LiveServer: frames has {len(fc['parents'])} joints, the decoder's pose rows hold {(PO - 6) // 15}")
+            # a record: a step's tick frames (+ frame 0 once), or what close() flushes in one decoder call
+            self._fr = ops.LiveFrames(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
+            self._fr_stage = _FrameStaging(R, self._fr.d.max_frames, self._fr.J, fc["mask"], self.dev)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -314,6 +450,8 @@ class LiveServer:
         self._ops = 0
         self.stats = dict(uploaded_samples=0, window_capacity=[int(window_capacity)] * R, ring_bytes=self.ring.numel() * 4,
                           launches_per_step=0, steps=0, ops_last_push_many=0, uploaded_bytes=0, resampled_rows=0)
+        if self._fr is not None:
+            self.stats["frame_bytes"] = 0            # bytes the output head has downloaded so far
 
     # ------------------------------------------------------------------ rows
     def _row(self, sid):
@@ -322,15 +460,21 @@ class LiveServer:
         r = self._sids[sid]
         return r, self._rows[r]
 
-    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32"):
+    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None):
         """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
         -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
         what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing.
         `rate` / `pcm`: what this stream delivers -- `rate` Hz (None: the server's rate) as "f32" (float32 in [-1, 1)) or "s16"
         (int16 PCM, x = s / 32768).  Anything but float32 at the server's rate is converted on the device as it arrives
         (zeggs_resample_push: band-limited, in front of the loudness stage and the window); a rate the converter does not
-        take raises ValueError naming both rates."""
+        take raises ValueError naming both rates.
+        `start_position` [3] / `start_rotation` [4] (a server with `frames`; both or neither): where the character stands -- the
+        root of the stream's frames is re-based on its frame 0, start_rot ref_rot^-1 (x - ref_pos) + start_pos, as write_bvh
+        does for a clip; with neither the root is handed out as the decoder integrates it."""
         rs = resample_row(rate, pcm, self.fs)
+        place = frames_placement(start_position, start_rotation)
+        if place is not None and self._fr is None:
+            raise ValueError("LiveServer.open: a placement needs the output head (LiveServer(frames=...))")
         if self._loud is None and float(gain) != 1.0:
             raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
         free = [r for r in range(self.rows) if self._rows[r] is None]
@@ -355,8 +499,94 @@ class LiveServer:
                 self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
             row.rs = dict(self._rs.table(rs[0]), fi=rs[0], fmt=rs[1], n_in=0)
             ops.live_resample_reset(self._rs, r)
+        if self._fr is not None:
+            J = self._fr.J
+            p0, r0 = f32(root_pos).reshape(1, 3), f32(root_rot).reshape(1, 4)
+            if place is None:
+                ops.live_frames_reset(self._fr, r)
+            else:
+                ops.live_frames_reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
+            pos0, _ = anim.bvh_channels(p0, r0, pose0[:, 6:6 + 3 * J].reshape(1, J, 3), pose0[:, 6 + 3 * J:6 + 9 * J].reshape(1, J, 2, 3),
+                                        *(place or (None, None)), order=self.frames_conf["order"])
+            row.offsets = pos0[0].cpu().numpy()
         self._rows[r], self._sids[sid] = row, r
         return sid
+
+    # ------------------------------------------------------------------ frames out
+    def bvh_header(self, sid, nframes=0):
+        """the head of a BVH file for stream `sid` (anim.bvh_header: HIERARCHY and the MOTION head for `nframes` frames at the
+        server's dt) with the joint positions of the stream's frame 0, as placed, as OFFSETs -- what write_bvh and
+        generate_gesture write.  Followed by the stream's "text" (or anim.format_rows of its "bvh" rows) it is a BVH file."""
+        if self._fr is None:
+            raise RuntimeError("LiveServer: the output head is off (LiveServer(frames=...))")
+        fc = self.frames_conf
+        head, seq = anim.bvh_header(self._row(sid)[1].offsets, fc["parents"], fc["names"], fc["order"], int(nframes), self.dt)
+        assert seq == fc["seq"]
+        return head
+
+    def _frames_text(self, table, counts, outs):
+        """outs[i]["text"]: the BVH rows of record i as the bytes of a file -- ONE table through the device formatter
+        (zeggs_table_text_device), cut at the records' last row ends; a value outside its domain sends the table through the
+        host formatter (anim._host_pieces, counted in anim.TEXT_FALLBACKS)"""
+        cuts = np.cumsum(counts)[:-1].tolist()
+        for o, piece in zip(outs, anim.format_rows_device(table, cuts)):
+            o["text"] = bytes(piece)
+
+    def _frames_step(self, out, live):
+        """the output head of a step: out[sid]["frames"] for the rows `live`, from the tensors out[sid] holds -- ONE launch and
+        ONE download whatever their number"""
+        fr, stg, fc = self._fr, self._fr_stage, self.frames_conf
+        src = [out[self._rows[r].sid] for r in live]
+        counts = [int(o["pose"].shape[0]) for o in src]
+        N, J = sum(counts), fr.J
+        use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
+        base = stg.dev.data_ptr()
+        o_loc = N * fr.bvh_doubles * 8 * use[0]
+        o_wld = o_loc + N * fr.local_floats * 4 * use[1]
+        a = 0
+        for q, r, o, c in zip(stg.recs, live, src, counts):
+            q.pose, q.rpos, q.rrot = o["pose"].data_ptr(), o["rpos"].data_ptr(), o["rrot"].data_ptr()
+            q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
+            q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
+            q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
+            q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
+            q.row, q.count = r, c
+            a += c
+        ops.live_frames(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
+        nbytes = frames_block_bytes(N, J, fc["mask"])
+        got = frames_unpack(stg.download(nbytes), counts, J, fc["mask"])
+        self._ops += 2
+        self.stats["frame_bytes"] += nbytes
+        if fc["text"]:
+            self._frames_text(stg.dev[:o_loc].view(torch.float64).view(N, fr.bvh_doubles), counts, got)
+            self._ops += 3                               # (the formatter's call and its two downloads: row ends, then the text)
+        for r, g in zip(live, got):
+            out[self._rows[r].sid]["frames"] = g
+
+    def _frames_close(self, r, o):
+        """the output head of close(): the tail `o` of row r through the same kernel and state, max_frames frames a call"""
+        fr, fc = self._fr, self.frames_conf
+        n, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
+        use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
+        nbytes = frames_block_bytes(n, J, fc["mask"])
+        block = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        o_loc = n * fr.bvh_doubles * 8 * use[0]
+        o_wld = o_loc + n * fr.local_floats * 4 * use[1]
+        rec = (ops.FramesRow * 1)()
+        q, base = rec[0], block.data_ptr()
+        for a in range(0, n, M):
+            q.pose, q.rpos, q.rrot = o["pose"][a:].data_ptr(), o["rpos"][a:].data_ptr(), o["rrot"][a:].data_ptr()
+            q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
+            q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
+            q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
+            q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
+            q.row, q.count = r, min(M, n - a)
+            ops.live_frames(fr, rec, 1)
+        got = frames_unpack(block.cpu().numpy(), [n], J, fc["mask"])
+        self.stats["frame_bytes"] += nbytes
+        if fc["text"]:
+            self._frames_text(block[:o_loc].view(torch.float64).view(n, fr.bvh_doubles), [n], got)
+        return got[0]
 
     # ------------------------------------------------------------------ audio
     def _grow_feats(self, FC):
@@ -683,6 +913,8 @@ class LiveServer:
                     row = self._rows[r]
                     out[row.sid] = self._emit(heads[r], pose[r], rpos[r], rrot[r])
                     row.kd += tick
+            if self._fr is not None:
+                self._frames_step(out, live)
         self.stats["launches_per_step"] = self._ops
         self.stats["steps"] += 1
         return out
@@ -696,7 +928,11 @@ class LiveServer:
                 break
             for sid, o in out.items():
                 acc.setdefault(sid, []).append(o)
-        return {sid: {k: torch.cat([o[k] for o in v]) for k in v[0]} for sid, v in acc.items()}
+        out = {sid: {k: torch.cat([o[k] for o in v]) for k in v[0] if k != "frames"} for sid, v in acc.items()}
+        if self._fr is not None:
+            for sid, v in acc.items():
+                out[sid]["frames"] = frames_cat([o["frames"] for o in v])
+        return out
 
     def close(self, sid):
         """end of stream `sid`'s signal: its remaining frames with the right-edge rules of the offline path (reflect padding of the
@@ -725,8 +961,9 @@ class LiveServer:
                 pose, rpos, rrot = self._decode_one(r, speech, style, n)
                 outs.append((pose[1:], rpos[1:], rrot[1:]))
                 row.kd += n
+            out = {k: torch.cat([o[i] for o in outs]).contiguous() for i, k in enumerate(("pose", "rpos", "rrot"))} if outs else {}
+            if outs and self._fr is not None:
+                out["frames"] = self._frames_close(r, out)
         self._rows[r] = None
         del self._sids[sid]
-        if not outs:
-            return {}
-        return {k: torch.cat([o[i] for o in outs]) for i, k in enumerate(("pose", "rpos", "rrot"))}
+        return out

@@ -12,8 +12,8 @@ import torch
 
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
-                   DecStats, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow, ResampleDims, ResampleRow,
-                   Seg, SpeechDims, SpeechPtrs,
+                   DecStats, FramesDims, FramesRow, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
+                   ResampleDims, ResampleRow, Seg, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
@@ -1050,6 +1050,76 @@ def live_resample_push(rs, rows, n, rows_dev=None):
     """zeggs_resample_push: rows[:n] a HOST array of ResampleRow (device addresses, the caller's counters), `rows_dev` the device
     address of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
     api().zeggs_resample_push(rs.d, rows, _records(ResampleRow, rows_dev), int(n), rs.state, rs.state.numel(), _stream())
+
+
+FRAMES_WHAT = {"local": 1, "world": 2, "bvh": 4}              # ZEGGS_FRAMES_LOCAL / _WORLD / _BVH
+FRAMES_KEYS = {"local": ("root_pos", "root_rot", "lrot", "lpos"), "world": ("gpos", "grot"), "bvh": ("bvh",)}
+
+
+def frames_what(what):
+    """("local", "world", "bvh") -> the bit mask of ZeggsFramesDims.what; ValueError for an unknown or an empty selection"""
+    try:
+        names = (what,) if isinstance(what, str) else tuple(what)
+    except TypeError:
+        names = ()
+    if not names or any(not isinstance(n, str) or n not in FRAMES_WHAT for n in names):
+        raise ValueError(f"frames: what {what!r} (one or more of {sorted(FRAMES_WHAT)})")
+    return sum(FRAMES_WHAT[n] for n in set(names))
+
+
+def frames_seq(parents):
+    """the joint order of the BVH file (anim.bvh_header: depth first, children in index order) for `parents`; ValueError where
+    the entry points would refuse the skeleton (parents[0] != -1, a parent that does not come before its child)"""
+    parents = [int(p) for p in parents]
+    if not parents or parents[0] != -1 or any(not 0 <= p < j for j, p in enumerate(parents) if j):
+        raise ValueError("frames: parents[0] is -1 and every other joint's parent comes before it")
+    children = [[j for j, p in enumerate(parents) if p == i] for i in range(len(parents))]
+    seq, todo = [], [0]
+    while todo:
+        i = todo.pop()
+        seq.append(i)
+        todo.extend(reversed(children[i]))
+    return seq
+
+
+class LiveFrames:
+    """The output head of `rows` live rows (include/zeggs_hip_frames.h): the dims record and the state buffer -- the skeleton
+    tables (`parents`, and `seq`, the joint order of the BVH rows: frames_seq(parents) unless given) and per row the placement
+    and the quaternions last emitted.  `what`: names or the bit mask; `order`: "zyx" or "xzy"."""
+
+    def __init__(self, rows, parents, max_frames, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
+        from . import anim
+        self.parents = [int(p) for p in parents]
+        self.seq = frames_seq(self.parents) if seq is None else [int(k) for k in seq]
+        self.what = what if isinstance(what, int) else frames_what(what)
+        self.J = len(self.parents)
+        self.d = FramesDims(int(rows), self.J, int(max_frames), self.what, anim._to_euler_order(order))
+        nbytes = api().zeggs_live_frames_state_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LiveFrames: {api().zeggs_last_error().decode()}")
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        if len(self.seq) != self.J:
+            raise ValueError(f"LiveFrames: seq has {len(self.seq)} entries for {self.J} joints")
+        api().zeggs_live_frames_prepare(self.d, (C.c_int * self.J)(*self.parents), (C.c_int * self.J)(*self.seq), self.state,
+                                        self.state.numel(), _stream())
+        self.local_floats, self.world_floats, self.bvh_doubles = 7 + 7 * self.J, 7 * self.J, 3 + 3 * self.J
+
+
+def live_frames_reset(lf, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
+    """zeggs_live_frames_reset: the row's next frame is the first of a stream; with a placement (all four given) the root is
+    re-based: start_rot ref_rot^-1 (x - ref_pos) + start_pos"""
+    place = [ref_pos, ref_rot, start_pos, start_rot]
+    if all(p is None for p in place):
+        api().zeggs_live_frames_reset(lf.d, lf.state, lf.state.numel(), int(row), None, None, None, None, 0, _stream())
+        return
+    arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
+    api().zeggs_live_frames_reset(lf.d, lf.state, lf.state.numel(), int(row), *arrs, 1, _stream())
+
+
+def live_frames(lf, rows, n, rows_dev=None):
+    """zeggs_live_frames: rows[:n] a HOST array of FramesRow (device addresses inside), `rows_dev` the device address of a copy of
+    the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
+    api().zeggs_live_frames(lf.d, rows, _records(FramesRow, rows_dev), int(n), lf.state, lf.state.numel(), _stream())
 
 
 class LiveSpeech:
