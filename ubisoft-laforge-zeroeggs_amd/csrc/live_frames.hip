@@ -11,6 +11,7 @@
 //   3. a thread per frame walks the joints in index order: forward kinematics in place in LDS (a parent comes before its
 //      children, so one sweep does it), the placed root folded into joint 0;
 //   4. a thread per joint walks the frames in order again: gpos and the sign rule on grot -> WORLD.
+// The passes are fr_pass() of frames_core.h, shared with the re-timing head (live_retime.hip); only the load of 0. and 1. is this file's.
 // The sign rule compares with what was EMITTED for the stream's previous frame (float32): within a pass that is a register,
 // across passes and calls the row's state, which the thread that owns the joint reads at the start of a pass and writes at its
 // end.  The same statement computes a frame wherever it falls, so a stream's frames are the same bits however it is cut into
@@ -19,131 +20,52 @@
 #include "common.h"
 #include "anim_math.h"
 #include "frames_math.h"
+#include "frames_core.h"
 
 namespace {
 
 static_assert(FR_LOCAL == ZEGGS_FRAMES_LOCAL && FR_WORLD == ZEGGS_FRAMES_WORLD && FR_BVH == ZEGGS_FRAMES_BVH, "the header's bits");
 
-struct FrPlace {      // what a row's state starts with
-  double ref_pos[3], ref_rot[4], start_pos[3], start_rot[4];
-  int rebase, started;
+// the LOAD of passes 0 and 1: a staged frame is a decoder frame of the record
+struct FrLoadRows {
+  ZeggsFramesRow rec;
+  const FrPlace* pl;
+  long f0;
+  int J;
+  bool rebase;
+  __device__ __forceinline__ void root(int t, DQ& rr, D3& rp) const {
+    const long f = f0 + t;
+    fr_place_root(pl, rebase, rec.rpos + f * rec.rpos_ld, rec.rrot + f * rec.rrot_ld, rr, rp);
+  }
+  __device__ __forceinline__ void joint(int t, int j, DQ& q, D3& p) const {
+    const float* row = rec.pose + (f0 + t) * rec.pose_ld;
+    const float* x = row + fr_pose_ltxy(J, j);
+    q = dq_from_xy(ldf3(x), ldf3(x + 3));
+    p = ldf3(row + fr_pose_lpos(j));
+  }
 };
-static_assert(sizeof(FrPlace) == 14 * 8 + 2 * 4, "fr_row_bytes");
-
-__device__ __forceinline__ D3 ldf3(const float* p) { return D3{(double)p[0], (double)p[1], (double)p[2]}; }
-__device__ __forceinline__ void stf3(float* p, D3 v) { p[0] = (float)v.x; p[1] = (float)v.y; p[2] = (float)v.z; }
 
 __global__ __launch_bounds__(FR_THREADS) void live_frames_k(ZeggsFramesDims d, const ZeggsFramesRow* __restrict__ recs, ZeggsFramesRow one,
                                                              char* state) {
   extern __shared__ double fr_lds[];
   const ZeggsFramesRow rec = recs ? recs[blockIdx.x] : one;
   if (rec.count <= 0) return;
-  const int J = d.J, tid = threadIdx.x, order = order_code(d.order);
+  const int J = d.J, order = order_code(d.order);
   const int FP = fr_pass_frames(J, d.max_frames);
   const int* parents = (const int*)state;
   const int* place = parents + 2 * J;
   FrPlace* pl = (FrPlace*)(state + fr_row_offset(J, rec.row));
   float* prev = (float*)(pl + 1);
   const bool rebase = pl->rebase != 0, opened = pl->started == 0;      // (read by every thread before thread 0 sets `started` below)
-  const bool local = (d.what & FR_LOCAL) != 0, world = (d.what & FR_WORLD) != 0, bvh = (d.what & FR_BVH) != 0;
   // LDS: per frame of the pass J + 1 quaternions and J + 1 positions, slot J = the placed root
   double* lq = fr_lds;
   double* lp = fr_lds + (size_t)FP * (J + 1) * 4;
-  const int LL = fr_local_floats(J), WL = fr_world_floats(J), BL = fr_bvh_doubles(J);
-
   for (int f0 = 0; f0 < rec.count; f0 += FP) {
     const int n = rec.count - f0 < FP ? rec.count - f0 : FP;
-    // ---- 0. the placed root
-    for (int t = tid; t < n; t += FR_THREADS) {
-      const long f = f0 + t;
-      const float* r = rec.rrot + f * rec.rrot_ld;
-      DQ rr = DQ{(double)r[0], (double)r[1], (double)r[2], (double)r[3]};
-      D3 rp = ldf3(rec.rpos + f * rec.rpos_ld);
-      if (rebase) {
-        const DQ r0 = dq_inv(ldq(pl->ref_rot)), sr = ldq(pl->start_rot);
-        rp = dq_mul_vec(sr, dq_mul_vec(r0, rp - ld3(pl->ref_pos))) + ld3(pl->start_pos);
-        rr = dq_mul(sr, dq_mul(r0, rr));
-      }
-      stq(lq + ((size_t)t * (J + 1) + J) * 4, rr);
-      st3(lp + ((size_t)t * (J + 1) + J) * 3, rp);
-      if (local) stf3(rec.local + f * LL + fr_local_root_pos(), rp);
-    }
-    __syncthreads();
-    // ---- 1. local quaternions and positions; LOCAL's lpos; the BVH row
-    for (int i = tid; i < n * J; i += FR_THREADS) {
-      const int t = i / J, j = i - t * J;
-      const long f = f0 + t;
-      const float* row = rec.pose + f * rec.pose_ld;
-      const float* x = row + fr_pose_ltxy(J, j);
-      const DQ q = dq_from_xy(ldf3(x), ldf3(x + 3));
-      const D3 p = ldf3(row + fr_pose_lpos(j));
-      const size_t s = (size_t)t * (J + 1) + j;
-      stq(lq + s * 4, q);
-      st3(lp + s * 3, p);
-      if (local) {
-        float* o = rec.local + f * LL + fr_local_lpos(J, j);
-        o[0] = row[fr_pose_lpos(j)]; o[1] = row[fr_pose_lpos(j) + 1]; o[2] = row[fr_pose_lpos(j) + 2];
-      }
-      if (bvh) {
-        double* b = rec.bvh + f * BL;
-        DQ e = q;
-        if (j == 0) {      // the placed root folded into joint 0
-          const DQ rr = ldq(lq + ((size_t)t * (J + 1) + J) * 4);
-          st3(b, dq_mul_vec(rr, p) + ld3(lp + ((size_t)t * (J + 1) + J) * 3));
-          e = dq_mul(rr, q);
-        }
-        const int k = place[j];      // (a state that was never prepared must not send a store astray)
-        if ((unsigned)k < (unsigned)J) dq_to_euler_deg(e, b + fr_bvh_euler(k), order);
-      }
-    }
-    __syncthreads();
-    // ---- 2. LOCAL's quaternions, frame by frame: thread j owns joint j, j == J is the root's rotation
-    if (local) {
-      for (int j = tid; j <= J; j += FR_THREADS) {
-        float* sp = prev + (j == J ? fr_prev_root() : fr_prev_lrot(j));
-        float pv[4] = {sp[0], sp[1], sp[2], sp[3]};
-        for (int t = 0; t < n; ++t) {
-          const DQ q = ldq(lq + ((size_t)t * (J + 1) + j) * 4);
-          fr_emit(!(opened && f0 + t == 0), q.w, q.x, q.y, q.z, pv,
-                  rec.local + (long)(f0 + t) * LL + (j == J ? fr_local_root_rot() : fr_local_lrot(j)));
-        }
-        sp[0] = pv[0]; sp[1] = pv[1]; sp[2] = pv[2]; sp[3] = pv[3];
-      }
-    }
-    if (world) {
-      __syncthreads();      // (3. overwrites what 2. reads)
-      // ---- 3. forward kinematics in place, joints in index order
-      for (int t = tid; t < n; t += FR_THREADS) {
-        double* q = lq + (size_t)t * (J + 1) * 4;
-        double* p = lp + (size_t)t * (J + 1) * 3;
-        const DQ rr = ldq(q + J * 4);
-        st3(p, dq_mul_vec(rr, ld3(p)) + ld3(p + J * 3));
-        stq(q, dq_mul(rr, ldq(q)));
-        for (int j = 1; j < J; ++j) {
-          const int a = (unsigned)parents[j] < (unsigned)j ? parents[j] : 0;
-          const DQ pq = ldq(q + a * 4);
-          st3(p + j * 3, dq_mul_vec(pq, ld3(p + j * 3)) + ld3(p + a * 3));
-          stq(q + j * 4, dq_mul(pq, ldq(q + j * 4)));
-        }
-      }
-      __syncthreads();
-      // ---- 4. WORLD, frame by frame
-      for (int j = tid; j < J; j += FR_THREADS) {
-        float* sp = prev + fr_prev_grot(J, j);
-        float pv[4] = {sp[0], sp[1], sp[2], sp[3]};
-        for (int t = 0; t < n; ++t) {
-          const size_t s = (size_t)t * (J + 1) + j;
-          float* o = rec.world + (long)(f0 + t) * WL;
-          stf3(o + fr_world_gpos(j), ld3(lp + s * 3));
-          const DQ q = ldq(lq + s * 4);
-          fr_emit(!(opened && f0 + t == 0), q.w, q.x, q.y, q.z, pv, o + fr_world_grot(J, j));
-        }
-        sp[0] = pv[0]; sp[1] = pv[1]; sp[2] = pv[2]; sp[3] = pv[3];
-      }
-    }
-    __syncthreads();      // (the next pass rewrites the LDS)
+    fr_pass(FrLoadRows{rec, pl, f0, J, rebase}, J, order, d.what, parents, place, prev, lq, lp, f0, n, opened ? 0L : -1L, rec.local, rec.world,
+            rec.bvh);
   }
-  if (tid == 0) pl->started = 1;
+  if (threadIdx.x == 0) pl->started = 1;
 }
 
 __global__ void live_frames_reset_k(FrPlace place, char* row_state) { *(FrPlace*)row_state = place; }

@@ -1,0 +1,240 @@
+// Live serving: the output head at each stream's own frame rate -- the frames of live_frames.hip, handed out at frame_rate =
+// fps L / M instead of the model's fps (include/zeggs_hip_retime.h; the counting rules, the state layout and the interpolation
+// weights are retime_math.h, the definition DESIGN.md 3.7).
+//
+// One workgroup of 256 threads per record, ONE launch per step whatever the rows' ratios; the server enqueues it INSTEAD of
+// live_frames_k.  A record brings `count` input frames and emits the output frames m whose position m M / L = k + num / L became
+// computable with them, n_out(n_in + count) - n_out(n_in) of them, possibly none.  They are walked in passes of rt_pass_frames
+// output frames, and a pass is fr_pass() of frames_core.h, the plain head's passes 0 - 4 word for word; only the LOAD of passes 0
+// and 1 is this file's:
+//   num == 0  the staged frame is input frame k, loaded as live_frames_k loads it (no interpolation: the plain head's bits);
+//   num != 0  both ends k and k + 1 are loaded that way -- the root placed, the joints' quaternions from their two-axis encoding
+//             -- and the staged frame is a + t (b - a) for positions and the shortest arc for rotations, t = num / L.
+// Input frame k of an output can be the row's LAST frame of an earlier call: the state keeps it as the raw float32 it arrived in
+// (rpos, rrot, lpos, ltxy), written once all passes are through, so the frame between two calls is computed by the same statement
+// from the same bits as inside one call.  The sign rule compares with the previous OUTPUT frame, kept as in the plain head.
+#include "../../include/zeggs_hip_retime.h"
+#include "common.h"
+#include "anim_math.h"
+#include "frames_math.h"
+#include "retime_math.h"
+#include "frames_core.h"
+
+namespace {
+
+static_assert(FR_LOCAL == ZEGGS_FRAMES_LOCAL && FR_WORLD == ZEGGS_FRAMES_WORLD && FR_BVH == ZEGGS_FRAMES_BVH, "the header's bits");
+static_assert(sizeof(ZeggsRetimeRow) == 104, "the record of the sixth header");
+
+__device__ __forceinline__ DQ rt_slerp(DQ a, DQ b, double t) {
+  double d = a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z;
+  if (d < 0.0) {
+    b = DQ{-b.w, -b.x, -b.y, -b.z};
+    d = -d;
+  }
+  double wa, wb;
+  rt_slerp_weights(d, t, &wa, &wb);
+  const DQ q = DQ{wa * a.w + wb * b.w, wa * a.x + wb * b.x, wa * a.y + wb * b.y, wa * a.z + wb * b.z};
+  const double n = sqrt(q.w * q.w + q.x * q.x + q.y * q.y + q.z * q.z);
+  return DQ{q.w / n, q.x / n, q.y / n, q.z / n};
+}
+
+// the LOAD of passes 0 and 1: staged frame t is output frame m0 + t of the stream
+struct RtLoad {
+  ZeggsRetimeRow rec;
+  const FrPlace* pl;
+  const float* raw;      // the row's last input frame of an earlier call (input frame n_in - 1)
+  long m0;
+  int J;
+  bool rebase;
+  // input frame i of the call, i = -1: the kept one (an index the counting rule cannot give is brought back into the call)
+  __device__ __forceinline__ long clamp(long i, long lo) const { return i < lo ? lo : (i > rec.count - 1 ? rec.count - 1 : i); }
+  __device__ __forceinline__ void where(int t, long& i, long& num) const {
+    long k;
+    rt_position(m0 + t, rec.L, rec.M, &k, &num);
+    i = clamp(k - rec.n_in, rec.n_in > 0 ? -1 : 0);
+  }
+  __device__ __forceinline__ void root_of(long i, DQ& rr, D3& rp) const {
+    const float* p = i < 0 ? raw + rt_raw_rpos() : rec.rpos + i * rec.rpos_ld;
+    const float* r = i < 0 ? raw + rt_raw_rrot() : rec.rrot + i * rec.rrot_ld;
+    fr_place_root(pl, rebase, p, r, rr, rp);
+  }
+  __device__ __forceinline__ void joint_of(long i, int j, DQ& q, D3& p) const {
+    const float* row = rec.pose + (i < 0 ? 0 : i) * rec.pose_ld;
+    const float* x = i < 0 ? raw + rt_raw_ltxy(J, j) : row + fr_pose_ltxy(J, j);
+    q = dq_from_xy(ldf3(x), ldf3(x + 3));
+    p = ldf3(i < 0 ? raw + rt_raw_lpos(j) : row + fr_pose_lpos(j));
+  }
+  __device__ __forceinline__ void root(int t, DQ& rr, D3& rp) const {
+    long i, num;
+    where(t, i, num);
+    root_of(i, rr, rp);
+    if (num != 0) {
+      DQ rb;
+      D3 pb;
+      root_of(clamp(i + 1, 0), rb, pb);
+      const double u = (double)num / (double)rec.L;
+      rp = rp + u * (pb - rp);
+      rr = rt_slerp(rr, rb, u);
+    }
+  }
+  __device__ __forceinline__ void joint(int t, int j, DQ& q, D3& p) const {
+    long i, num;
+    where(t, i, num);
+    joint_of(i, j, q, p);
+    if (num != 0) {
+      DQ qb;
+      D3 pb;
+      joint_of(clamp(i + 1, 0), j, qb, pb);
+      const double u = (double)num / (double)rec.L;
+      p = p + u * (pb - p);
+      q = rt_slerp(q, qb, u);
+    }
+  }
+};
+
+__global__ __launch_bounds__(FR_THREADS) void live_retime_k(ZeggsFramesDims d, const ZeggsRetimeRow* __restrict__ recs, ZeggsRetimeRow one,
+                                                             char* state) {
+  extern __shared__ double rt_lds[];
+  const ZeggsRetimeRow rec = recs ? recs[blockIdx.x] : one;
+  if (rec.count <= 0) return;
+  const int J = d.J, order = order_code(d.order);
+  const int FP = rt_pass_frames(J, d.max_frames);
+  const int* parents = (const int*)state;
+  const int* place = parents + 2 * J;
+  char* row_state = state + rt_row_offset(J, rec.row);
+  FrPlace* pl = (FrPlace*)row_state;
+  float* prev = (float*)(pl + 1);
+  float* raw = (float*)(row_state + rt_row_raw_offset(J));
+  const bool rebase = pl->rebase != 0;
+  const long m0 = rt_n_out(rec.n_in, rec.L, rec.M);
+  const long outs = rt_n_out(rec.n_in + rec.count, rec.L, rec.M) - m0;
+  double* lq = rt_lds;
+  double* lp = rt_lds + (size_t)FP * (J + 1) * 4;
+  for (long f0 = 0; f0 < outs; f0 += FP) {
+    const int n = (int)(outs - f0 < FP ? outs - f0 : FP);
+    fr_pass(RtLoad{rec, pl, raw, m0 + f0, J, rebase}, J, order, d.what, parents, place, prev, lq, lp, f0, n, m0 == 0 ? 0L : -1L, rec.local,
+            rec.world, rec.bvh);
+  }
+  // the last input frame stays, raw (every pass ends behind a barrier: nothing reads the kept frame any more)
+  const long last = rec.count - 1;
+  const float* row = rec.pose + last * rec.pose_ld;
+  for (int i = threadIdx.x; i < rt_raw_floats(J); i += FR_THREADS)
+    raw[i] = i < 3 ? rec.rpos[last * rec.rpos_ld + i] : i < 7 ? rec.rrot[last * rec.rrot_ld + i - 3] : row[fr_pose_lpos(0) + i - 7];
+  if (threadIdx.x == 0) pl->started = 1;
+}
+
+__global__ void live_retime_reset_k(FrPlace place, char* row_state) { *(FrPlace*)row_state = place; }
+
+int rt_dims_ok(const ZeggsFramesDims* d, const void* state, size_t state_bytes) {
+  ZCHECK(d != nullptr, "retime: NULL dims");
+  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "retime: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
+  const int why = fr_shape_refused(d->J, d->max_frames);
+  ZCHECK(why != 1, "retime: %d joints (1..%d)", d->J, FR_MAX_JOINTS);
+  ZCHECK(why != 2, "retime: max_frames %d (1..%d)", d->max_frames, FR_MAX_FRAMES);
+  ZCHECK(why == 0, "retime: a frame of %d joints needs %ld bytes of LDS, the kernel may have %d", d->J, fr_frame_lds_bytes(d->J), FR_LDS_BYTES);
+  ZCHECK(d->what >= 1 && d->what <= (FR_LOCAL | FR_WORLD | FR_BVH), "retime: what = %d (a mask of LOCAL 1 | WORLD 2 | BVH 4)", d->what);
+  ZCHECK(order_code(d->order) == ORDER_ZYX || d->order == ORDER_XZY, "retime: channel order %d (\"zyx\" and \"xzy\" are supported)", d->order);
+  if (state_bytes != (size_t)-1) {
+    ZCHECK(state != nullptr, "retime: NULL state");
+    ZCHECK(state_bytes >= (size_t)rt_state_bytes(d->rows, d->J), "retime: state too small (%zu < %zu)", state_bytes,
+           (size_t)rt_state_bytes(d->rows, d->J));
+    ZCHECK((uintptr_t)state % 8 == 0, "retime: misaligned state");
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" int zeggs_live_retime_version(void) { return 1; }
+
+extern "C" size_t zeggs_live_retime_state_bytes(const ZeggsFramesDims* d) {
+  if (rt_dims_ok(d, nullptr, (size_t)-1) != 0) return 0;
+  return (size_t)rt_state_bytes(d->rows, d->J);
+}
+
+extern "C" int zeggs_live_retime_prepare(const ZeggsFramesDims* d, const int* parents, const int* seq, void* state, size_t state_bytes,
+                                         void* stream) {
+  ZTRY(rt_dims_ok(d, state, state_bytes));
+  ZCHECK(parents != nullptr && seq != nullptr, "retime prepare: NULL parents / seq");
+  const int J = d->J;
+  int bad = fr_bad_parent(parents, J);
+  ZCHECK(bad != 0, "retime prepare: parents[0] = %d (the root has parent -1)", parents[0]);
+  ZCHECK(bad < 0, "retime prepare: parents[%d] = %d (a parent comes before its children: 0 .. %d)", bad, parents[bad], bad - 1);
+  int tables[3 * FR_MAX_JOINTS];
+  bad = fr_bad_seq(seq, J, tables + 2 * J);
+  ZCHECK(bad < 0, "retime prepare: seq[%d] = %d: seq is no permutation of 0 .. %d", bad, seq[bad], J - 1);
+  memcpy(tables, parents, sizeof(int) * J);
+  memcpy(tables + J, seq, sizeof(int) * J);
+  // once per server, never on the tick path: the copy is waited for, `tables` is gone when the call returns
+  hipError_t e = hipMemcpyAsync(state, tables, sizeof(int) * 3 * J, hipMemcpyHostToDevice, (hipStream_t)stream);
+  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+  ZCHECK(e == hipSuccess, "retime prepare: %s", hipGetErrorString(e));
+  return 0;
+}
+
+extern "C" int zeggs_live_retime_reset(const ZeggsFramesDims* d, void* state, size_t state_bytes, int row, const float* ref_pos,
+                                       const float* ref_rot, const double* start_pos, const double* start_rot, int rebase, void* stream) {
+  ZTRY(rt_dims_ok(d, state, state_bytes));
+  ZCHECK(row >= 0 && row < d->rows, "retime reset: row %d of %d", row, d->rows);
+  FrPlace p = {};
+  p.ref_rot[0] = p.start_rot[0] = 1.0;
+  if (rebase) {
+    ZCHECK(ref_pos != nullptr && ref_rot != nullptr && start_pos != nullptr && start_rot != nullptr,
+           "retime reset: row %d: a placement needs ref_pos, ref_rot, start_pos and start_rot", row);
+    for (int i = 0; i < 3; ++i) { p.ref_pos[i] = (double)ref_pos[i]; p.start_pos[i] = start_pos[i]; }
+    for (int i = 0; i < 4; ++i) { p.ref_rot[i] = (double)ref_rot[i]; p.start_rot[i] = start_rot[i]; }
+    p.rebase = 1;
+  }
+  hipLaunchKernelGGL(live_retime_reset_k, dim3(1), dim3(1), 0, (hipStream_t)stream, p, (char*)state + rt_row_offset(d->J, row));
+  ZLAUNCH_CHECK("live_retime_reset");
+  return 0;
+}
+
+extern "C" int zeggs_live_frames_retimed(const ZeggsFramesDims* d, const ZeggsRetimeRow* rows, const ZeggsRetimeRow* rows_dev, int R, void* state,
+                                         size_t state_bytes, void* stream) {
+  const char* who = "retime";
+  ZTRY(rt_dims_ok(d, state, state_bytes));
+  ZCHECK(R >= 0 && R <= d->rows, "%s: %d records for %d rows", who, R, d->rows);
+  if (R == 0) return 0;
+  ZCHECK(rows != nullptr, "%s: NULL records", who);
+  bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
+  bool work = false;
+  const int J = d->J;
+  for (int i = 0; i < R; ++i) {
+    const ZeggsRetimeRow& w = rows[i];
+    ZCHECK(w.row >= 0 && w.row < d->rows, "%s: record %d: row %d of %d", who, i, w.row, d->rows);
+    ZCHECK(!seen[w.row], "%s: record %d: row %d twice in one call", who, i, w.row);
+    seen[w.row] = true;
+    ZCHECK(w.count >= 0, "%s: record %d: negative count %d", who, i, w.count);
+    ZCHECK(w.count <= d->max_frames, "%s: record %d: %d frames, max_frames is %d", who, i, w.count, d->max_frames);
+    const int why = rt_ratio_refused(w.L, w.M);
+    ZCHECK(why != 1 && why != 2, "%s: record %d: ratio %d / %d (1 <= L, M <= %d)", who, i, w.L, w.M, RT_MAX_TERM);
+    ZCHECK(why != 3, "%s: record %d: ratio %d / %d is not in lowest terms", who, i, w.L, w.M);
+    ZCHECK(why == 0, "%s: record %d: ratio %d / %d is above %d", who, i, w.L, w.M, RT_MAX_UP);
+    ZCHECK(w.n_in >= 0 && w.n_in <= (1L << 40), "%s: record %d: input counter %ld", who, i, w.n_in);
+    const long want = rt_n_out(w.n_in + w.count, w.L, w.M) - rt_n_out(w.n_in, w.L, w.M);
+    ZCHECK(w.outputs == want, "%s: record %d: %ld outputs disagree with n_out(%ld) - n_out(%ld) = %ld at %d / %d", who, i, w.outputs,
+           w.n_in + w.count, w.n_in, want, w.L, w.M);
+    if (w.count == 0) continue;
+    ZCHECK(w.pose != nullptr && (uintptr_t)w.pose % 4 == 0 && w.rpos != nullptr && (uintptr_t)w.rpos % 4 == 0 && w.rrot != nullptr &&
+               (uintptr_t)w.rrot % 4 == 0, "%s: record %d: NULL or misaligned source", who, i);
+    ZCHECK(w.pose_ld >= fr_pose_floats_read(J) && w.rpos_ld >= 3 && w.rrot_ld >= 4,
+           "%s: record %d: leading dimensions %ld, %ld, %ld (at least %d, 3, 4 floats)", who, i, w.pose_ld, w.rpos_ld, w.rrot_ld,
+           fr_pose_floats_read(J));
+    if (w.outputs > 0) {
+      ZCHECK(!(d->what & FR_LOCAL) || (w.local != nullptr && (uintptr_t)w.local % 4 == 0), "%s: record %d: NULL or misaligned LOCAL destination",
+             who, i);
+      ZCHECK(!(d->what & FR_WORLD) || (w.world != nullptr && (uintptr_t)w.world % 4 == 0), "%s: record %d: NULL or misaligned WORLD destination",
+             who, i);
+      ZCHECK(!(d->what & FR_BVH) || (w.bvh != nullptr && (uintptr_t)w.bvh % 8 == 0), "%s: record %d: NULL or misaligned BVH destination", who, i);
+    }
+    work = true;
+  }
+  if (!work) return 0;
+  ZCHECK(rows_dev != nullptr || R == 1, "%s: %d records must also be in device memory (rows_dev)", who, R);
+  ZCHECK(rows_dev == nullptr || (uintptr_t)rows_dev % 8 == 0, "%s: misaligned rows_dev", who);
+  hipLaunchKernelGGL(live_retime_k, dim3((unsigned)R), dim3(FR_THREADS), (size_t)rt_lds_bytes(J, d->max_frames), (hipStream_t)stream, *d, rows_dev,
+                     rows[0], (char*)state);
+  ZLAUNCH_CHECK("live_retime");
+  return 0;
+}

@@ -13,8 +13,9 @@ A new entry point is a declaration in the header plus one row in PROTOTYPES (tes
 header include/zeggs_hip_live.h has its own tables, EXT_STRUCTS / EXT_PROTOTYPES (tests/test_live_push_cpu.py), the third,
 include/zeggs_hip_loudness.h, LOUD_STRUCTS / LOUD_PROTOTYPES (tests/test_live_loudness_cpu.py), the fourth,
 include/zeggs_hip_resample.h, RS_STRUCTS / RS_PROTOTYPES (tests/test_live_resample_cpu.py), the fifth,
-include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_cpu.py): same loader.  torch is imported when a
-tensor is first converted, not when this module is.
+include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_cpu.py), the sixth, include/zeggs_hip_retime.h,
+RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py): same loader.  torch is imported when a tensor is first converted, not
+when this module is.
 """
 import ctypes as C
 import os
@@ -284,6 +285,21 @@ FR_PROTOTYPES = {
     "zeggs_live_frames": "status: ZeggsFramesDims* ZeggsFramesRow* ZeggsFramesRow* int any* size_t stream",
 }
 
+# ----------------------------------------------------------------------------- the sixth header (include/zeggs_hip_retime.h)
+# The output head at each stream's own frame rate (tests/test_live_retime_cpu.py compares these tables with the header).
+RetimeRow = _struct("RetimeRow", [(C.c_void_p, "pose rpos rrot local world bvh"), (C.c_long, "pose_ld rpos_ld rrot_ld n_in outputs"),
+                                  (C.c_int, "row count L M")])
+RT_STRUCTS = {"ZeggsRetimeRow": RetimeRow}
+RT_PROTOTYPES = {
+    "zeggs_live_retime_version": "int:",
+    "zeggs_live_retime_state_bytes": "size_t: ZeggsFramesDims*",
+    # parents / seq, ref / start: HOST arrays, as in the fifth header
+    "zeggs_live_retime_prepare": "status: ZeggsFramesDims* host* host* any* size_t stream",
+    "zeggs_live_retime_reset": "status: ZeggsFramesDims* any* size_t int host* host* host* host* int stream",
+    # rows_host / rows_dev as in zeggs_live_loudness_push
+    "zeggs_live_frames_retimed": "status: ZeggsFramesDims* ZeggsRetimeRow* ZeggsRetimeRow* int any* size_t stream",
+}
+
 
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
@@ -323,14 +339,14 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -368,7 +384,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -380,7 +396,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

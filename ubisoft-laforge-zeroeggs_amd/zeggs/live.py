@@ -24,7 +24,12 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
   * LiveServer(frames=dict(parents=...)) adds an output head: step() and close() also return, under "frames", what a renderer or
     a BVH recorder takes of the new frames -- the placed root, local and world-space joint transforms, BVH motion rows (and their
     text) -- converted for all rows by ONE launch (zeggs_live_frames) and brought down by ONE copy into pinned memory per step;
-    open(..., start_position=, start_rotation=) says where a character stands, bvh_header(sid, n) gives the head of its file.
+    open(..., start_position=, start_rotation=) says where a character stands, bvh_header(sid, n) gives the head of its file;
+  * LiveServer(frames=..., retime=True) hands those frames out at each stream's own frame rate: open(..., frame_rate=30) (24, 25,
+    50, 72, 90, 120, 30000/1001, ...) and "frames" holds the stream's new frames at ITS rate, possibly none in a step -- frames
+    that fall on a model frame are the plain head's, frames between two are interpolated ahead of FK (positions on the line,
+    rotations on the shortest arc) and go through the head's own Euler conversion, FK, sign rule and formatter; going down in
+    rate is point sampling.  Still ONE launch (zeggs_live_frames_retimed, in place of zeggs_live_frames) and one download a step.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -240,6 +245,34 @@ def frames_options(frames):
                 order=o["order"], text=bool(o["text"]), seq=seq)
 
 
+RETIME_DEFAULTS = dict(max_rate=None)
+
+
+def retime_options(retime, frames_conf, fps):
+    """LiveServer's `retime` argument -> None (off) or dict(max_rate: the highest frame rate a stream may ask for, a Fraction,
+    ratio: max_rate / fps as (L, M)): True is the defaults, a dict overrides them; max_rate None is the server's own rate `fps`
+    (re-timing downward only: the staging blocks are the plain head's).  ValueError for anything else, for `retime` without
+    `frames`, and for a max_rate the kernel does not take (naming both rates)."""
+    if retime is None or retime is False:
+        return None
+    if retime is True:
+        retime = {}
+    if not isinstance(retime, dict) or set(retime) - set(RETIME_DEFAULTS):
+        raise ValueError(f"LiveServer: retime is None, True or a dict with keys {sorted(RETIME_DEFAULTS)}")
+    if frames_conf is None:
+        raise ValueError("LiveServer: retime re-times the frames of the output head: it needs frames=dict(parents=...)")
+    o = dict(RETIME_DEFAULTS, **retime)
+    rate = fps if o["max_rate"] is None else o["max_rate"]
+    try:
+        L, M = ops.retime_ratio(rate, fps)
+    except ValueError as e:
+        raise ValueError(f"LiveServer: retime max_rate: {e}") from None
+    if L < M:
+        raise ValueError(f"LiveServer: retime max_rate {rate!r} is below the server's own {fps!r} frames per second")
+    from fractions import Fraction
+    return dict(max_rate=Fraction(L, M) * Fraction(str(float(fps))), ratio=(L, M))
+
+
 def frames_placement(start_position, start_rotation):
     """open()'s placement -> None (neither given: the root is handed out as it is) or (position [3], rotation [4], float64);
     ValueError when only one of the two is given or a shape is wrong"""
@@ -283,8 +316,10 @@ def frames_unpack(buf, counts, J, mask, copy=True):
 
 
 def frames_cat(parts):
-    """the "frames" of consecutive steps of a stream as one: arrays concatenated along the frames, "text" joined"""
-    return {k: b"".join(p[k] for p in parts) if k == "text" else np.concatenate([p[k] for p in parts]) for k in parts[0]}
+    """the "frames" of consecutive steps of a stream as one: arrays concatenated along the frames, "text" joined, "frame0" (a
+    re-timing server: the index of a part's first frame) the first part's"""
+    return {k: b"".join(p[k] for p in parts) if k == "text" else parts[0][k] if k == "frame0" else np.concatenate([p[k] for p in parts])
+            for k in parts[0]}
 
 
 def frames_block_bytes(N, J, mask):
@@ -301,14 +336,15 @@ class _FrameStaging:
     records are rewritten only after the step that used them has waited for its download, which is ordered behind the launch."""
     RING = 3
 
-    def __init__(self, rows, max_frames, J, mask, dev):
+    def __init__(self, rows, max_frames, J, mask, dev, record=None):
+        record = record or ops.FramesRow              # (the re-timing head: ops.RetimeRow, max_frames OUTPUT frames a row)
         self.J, self.mask = J, mask
         self.nbytes = frames_block_bytes(rows * max_frames, J, mask)
         self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
         self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
         self.events, self.turn = [None] * self.RING, 0
-        self.rec_mem = torch.zeros(rows * C.sizeof(ops.FramesRow), dtype=torch.uint8).pin_memory()
-        self.recs = (ops.FramesRow * rows).from_buffer(self.rec_mem.numpy())
+        self.rec_mem = torch.zeros(rows * C.sizeof(record), dtype=torch.uint8).pin_memory()
+        self.recs = (record * rows).from_buffer(self.rec_mem.numpy())
 
     def download(self, nbytes):
         """one device-to-host copy of the block's first nbytes into the next pinned block -> that block's bytes, once they are
@@ -339,7 +375,7 @@ def _samples(chunk, rs):
 
 
 class _Row:
-    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs", "offsets")
+    __slots__ = ("sid", "n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs", "offsets", "rt")
 
     def __init__(self, sid):
         self.sid, self.n, self.base = sid, 0, 0          # samples received (absolute) / absolute index of window[0]
@@ -348,6 +384,7 @@ class _Row:
         self.k_style, self.fade = 0, 0                   # last set_style: from frame k_style on, over `fade` frames
         self.rs = None                                   # a converting row: dict(fi, fmt, table, L, M, WL, n_in: raw samples received)
         self.offsets = None                              # frames: the joint positions of frame 0 as placed (the OFFSETs of a BVH file)
+        self.rt = None                                   # a re-timing server: dict(L, M, n_in: frames through the head, n_out: frames emitted)
 
 
 class LiveServer:
@@ -371,14 +408,24 @@ class LiveServer:
     [n, J, 3], "grot" [n, J, 4] (world, the root folded into joint 0), "bvh" [n, 3 + 3J] float64 (the motion rows of a BVH file
     in the joint order of bvh_header()) and with text=True "text", those rows as the bytes of the file.  One more launch
     (zeggs_live_frames) and one download per step whatever the number of rows; quaternions keep their sign from frame to
-    frame and from step to step.  With None the server holds no such state and enqueues what it always did."""
+    frame and from step to step.  With None the server holds no such state and enqueues what it always did.
+
+    `retime`: None, True or dict(max_rate=...) (with `frames`; retime_options) -- every row's head runs through the
+    re-timing kernel (zeggs_live_frames_retimed in place of zeggs_live_frames: the same number of launches), and
+    open(..., frame_rate=) gives a stream a frame rate of its own, frame_rate / fps = L / M with 1 <= L, M <= 4096 and L / M <= 8,
+    at most `max_rate` (default: the server's own rate, so that only lower rates are taken and the staging blocks stay the
+    size they were).  out[sid]["frames"] then holds the stream's new frames at ITS rate (possibly none: empty arrays) and
+    "frame0", the index of the first of them; "pose" / "rpos" / "rrot" stay the decoder's rows at `fps`.  Going down in rate is
+    point sampling -- 30 from 60 is every second frame, and motion above half the output rate aliases, as decimating a BVH
+    file would.  With None the server is the one it was."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None):
         g = audio_conf
         loud = loudness_options(loudness)
         self.resample_conf = audio.resample_options(resample)
         self.frames_conf = frames_options(frames)
+        self.retime_conf = retime_options(retime, self.frames_conf, fps)
         if loud is None and g.get("normalize_loudness"):
             raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
         if tuple(feature_type) != ("mel_spec", "energy"):
@@ -441,8 +488,13 @@ class LiveServer:
             if 6 + 15 * len(fc["parents"]) != PO:
                 raise ValueError(f"LiveServer: frames has {len(fc['parents'])} joints, the decoder's pose rows hold {(PO - 6) // 15}")
             # a record: a step's tick frames (+ frame 0 once), or what close() flushes in one decoder call
-            self._fr = ops.LiveFrames(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
-            self._fr_stage = _FrameStaging(R, self._fr.d.max_frames, self._fr.J, fc["mask"], self.dev)
+            if self.retime_conf is None:
+                self._fr = ops.LiveFrames(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
+                self._fr_stage = _FrameStaging(R, self._fr.d.max_frames, self._fr.J, fc["mask"], self.dev)
+            else:                                    # a row's share of the blocks: what max_rate makes of a record's input frames
+                self._fr = ops.LiveRetime(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
+                L, M = self.retime_conf["ratio"]
+                self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev, ops.RetimeRow)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -460,7 +512,28 @@ class LiveServer:
         r = self._sids[sid]
         return r, self._rows[r]
 
-    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None):
+    def _frame_rate(self, frame_rate):
+        """open()'s `frame_rate` -> None (a server without re-timing) or the row's dict(L, M, n_in, n_out); ValueError naming both
+        rates on a server without `retime`, for a ratio the kernel does not take and for a rate above max_rate"""
+        conf = self.retime_conf
+        if conf is None:
+            if frame_rate is None:
+                return None
+            raise ValueError(f"LiveServer.open: frame_rate {frame_rate!r} on a server that hands out {self.fps!r} frames per second: "
+                             "re-timing is off (LiveServer(frames=..., retime=True))")
+        if frame_rate is None:
+            L, M = 1, 1
+        else:
+            try:
+                L, M = ops.retime_ratio(frame_rate, self.fps)
+            except ValueError as e:
+                raise ValueError(f"LiveServer.open: {e}") from None
+        if L * conf["ratio"][1] > conf["ratio"][0] * M:
+            raise ValueError(f"LiveServer.open: frame_rate {frame_rate!r} on a server at {self.fps!r} frames per second is above its "
+                             f"max_rate {float(conf['max_rate'])!r} (LiveServer(retime=dict(max_rate=...)))")
+        return dict(L=L, M=M, n_in=0, n_out=0)
+
+    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None, frame_rate=None):
         """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
         -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
         what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing.
@@ -470,13 +543,18 @@ class LiveServer:
         take raises ValueError naming both rates.
         `start_position` [3] / `start_rotation` [4] (a server with `frames`; both or neither): where the character stands -- the
         root of the stream's frames is re-based on its frame 0, start_rot ref_rot^-1 (x - ref_pos) + start_pos, as write_bvh
-        does for a clip; with neither the root is handed out as the decoder integrates it."""
+        does for a clip; with neither the root is handed out as the decoder integrates it.
+        `frame_rate` (a server with `retime`): the rate this stream's "frames" leave at -- an int, a fractions.Fraction, a
+        (num, den) pair, or a float taken as Fraction(str(x)) (29.97 is 2997/100; the NTSC rate proper is (30000, 1001));
+        None: the server's rate.  ValueError naming both rates on a server without `retime`, for a ratio outside 1 <= L, M
+        <= 4096, L / M <= 8 and for a rate above the server's max_rate."""
         rs = resample_row(rate, pcm, self.fs)
         place = frames_placement(start_position, start_rotation)
         if place is not None and self._fr is None:
             raise ValueError("LiveServer.open: a placement needs the output head (LiveServer(frames=...))")
         if self._loud is None and float(gain) != 1.0:
             raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
+        rt = self._frame_rate(frame_rate)
         free = [r for r in range(self.rows) if self._rows[r] is None]
         if not free:
             raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
@@ -502,10 +580,12 @@ class LiveServer:
         if self._fr is not None:
             J = self._fr.J
             p0, r0 = f32(root_pos).reshape(1, 3), f32(root_rot).reshape(1, 4)
+            row.rt = rt
+            reset = ops.live_frames_reset if rt is None else ops.live_retime_reset
             if place is None:
-                ops.live_frames_reset(self._fr, r)
+                reset(self._fr, r)
             else:
-                ops.live_frames_reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
+                reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
             pos0, _ = anim.bvh_channels(p0, r0, pose0[:, 6:6 + 3 * J].reshape(1, J, 3), pose0[:, 6 + 3 * J:6 + 9 * J].reshape(1, J, 2, 3),
                                         *(place or (None, None)), order=self.frames_conf["order"])
             row.offsets = pos0[0].cpu().numpy()
@@ -515,12 +595,13 @@ class LiveServer:
     # ------------------------------------------------------------------ frames out
     def bvh_header(self, sid, nframes=0):
         """the head of a BVH file for stream `sid` (anim.bvh_header: HIERARCHY and the MOTION head for `nframes` frames at the
-        server's dt) with the joint positions of the stream's frame 0, as placed, as OFFSETs -- what write_bvh and
-        generate_gesture write.  Followed by the stream's "text" (or anim.format_rows of its "bvh" rows) it is a BVH file."""
+        server's dt, or the stream's own frame time dt M / L on a re-timing server) with the joint positions of the stream's frame
+        0, as placed, as OFFSETs -- what write_bvh and generate_gesture write.  Followed by the stream's "text" (or anim.format_rows of its "bvh" rows) it is a BVH file."""
         if self._fr is None:
             raise RuntimeError("LiveServer: the output head is off (LiveServer(frames=...))")
-        fc = self.frames_conf
-        head, seq = anim.bvh_header(self._row(sid)[1].offsets, fc["parents"], fc["names"], fc["order"], int(nframes), self.dt)
+        fc, row = self.frames_conf, self._row(sid)[1]
+        dt = self.dt if row.rt is None or row.rt["L"] == row.rt["M"] else self.dt * row.rt["M"] / row.rt["L"]
+        head, seq = anim.bvh_header(row.offsets, fc["parents"], fc["names"], fc["order"], int(nframes), dt)
         assert seq == fc["seq"]
         return head
 
@@ -537,55 +618,80 @@ class LiveServer:
         ONE download whatever their number"""
         fr, stg, fc = self._fr, self._fr_stage, self.frames_conf
         src = [out[self._rows[r].sid] for r in live]
-        counts = [int(o["pose"].shape[0]) for o in src]
+        n_in = [int(o["pose"].shape[0]) for o in src]
+        rts = [self._rows[r].rt for r in live] if self.retime_conf is not None else None
+        # a re-timing server: a record emits what the counting rule gives its row for these input frames
+        counts = n_in if rts is None else [ops.retime_n_out(t["n_in"] + c, t["L"], t["M"]) - t["n_out"] for t, c in zip(rts, n_in)]
         N, J = sum(counts), fr.J
         use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
         base = stg.dev.data_ptr()
         o_loc = N * fr.bvh_doubles * 8 * use[0]
         o_wld = o_loc + N * fr.local_floats * 4 * use[1]
         a = 0
-        for q, r, o, c in zip(stg.recs, live, src, counts):
+        for i, (q, r, o, c) in enumerate(zip(stg.recs, live, src, counts)):
             q.pose, q.rpos, q.rrot = o["pose"].data_ptr(), o["rpos"].data_ptr(), o["rrot"].data_ptr()
             q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
             q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
             q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
             q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
-            q.row, q.count = r, c
+            q.row, q.count = r, n_in[i]
+            if rts is not None:
+                q.L, q.M, q.n_in, q.outputs = rts[i]["L"], rts[i]["M"], rts[i]["n_in"], c
             a += c
-        ops.live_frames(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
         nbytes = frames_block_bytes(N, J, fc["mask"])
-        got = frames_unpack(stg.download(nbytes), counts, J, fc["mask"])
+        if rts is None:
+            ops.live_frames(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
+        else:
+            ops.live_frames_retimed(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
+        # (a step in which no row of a re-timing server emits a frame has nothing to bring down; it counts as if it had)
+        got = frames_unpack(stg.download(nbytes) if N else np.zeros(0, np.uint8), counts, J, fc["mask"])
         self._ops += 2
         self.stats["frame_bytes"] += nbytes
         if fc["text"]:
             self._frames_text(stg.dev[:o_loc].view(torch.float64).view(N, fr.bvh_doubles), counts, got)
             self._ops += 3                               # (the formatter's call and its two downloads: row ends, then the text)
-        for r, g in zip(live, got):
+        for i, (r, g) in enumerate(zip(live, got)):
+            if rts is not None:
+                g["frame0"] = rts[i]["n_out"]
+                rts[i]["n_in"] += n_in[i]
+                rts[i]["n_out"] += counts[i]
             out[self._rows[r].sid]["frames"] = g
 
     def _frames_close(self, r, o):
-        """the output head of close(): the tail `o` of row r through the same kernel and state, max_frames frames a call"""
-        fr, fc = self._fr, self.frames_conf
-        n, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
+        """the output head of close(): the tail `o` of row r through the same kernel and state, max_frames frames a call; on a
+        re-timing server the output frames the counting rule gives the row for them -- there is no tail of its own"""
+        fr, fc, rt = self._fr, self.frames_conf, self._rows[r].rt
+        n_in, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
+        n = n_in if rt is None else ops.retime_n_out(rt["n_in"] + n_in, rt["L"], rt["M"]) - rt["n_out"]
         use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
         nbytes = frames_block_bytes(n, J, fc["mask"])
         block = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         o_loc = n * fr.bvh_doubles * 8 * use[0]
         o_wld = o_loc + n * fr.local_floats * 4 * use[1]
-        rec = (ops.FramesRow * 1)()
-        q, base = rec[0], block.data_ptr()
-        for a in range(0, n, M):
-            q.pose, q.rpos, q.rrot = o["pose"][a:].data_ptr(), o["rpos"][a:].data_ptr(), o["rrot"][a:].data_ptr()
+        rec = ((ops.FramesRow if rt is None else ops.RetimeRow) * 1)()
+        q, base, a = rec[0], block.data_ptr(), 0          # a: output frames written so far
+        for i in range(0, n_in, M):
+            q.pose, q.rpos, q.rrot = o["pose"][i:].data_ptr(), o["rpos"][i:].data_ptr(), o["rrot"][i:].data_ptr()
             q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
             q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
             q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
             q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
-            q.row, q.count = r, min(M, n - a)
-            ops.live_frames(fr, rec, 1)
+            q.row, q.count = r, min(M, n_in - i)
+            if rt is None:
+                ops.live_frames(fr, rec, 1)
+                a += q.count
+            else:
+                q.L, q.M, q.n_in = rt["L"], rt["M"], rt["n_in"] + i
+                q.outputs = ops.retime_n_out(q.n_in + q.count, q.L, q.M) - ops.retime_n_out(q.n_in, q.L, q.M)
+                ops.live_frames_retimed(fr, rec, 1)
+                a += q.outputs
         got = frames_unpack(block.cpu().numpy(), [n], J, fc["mask"])
         self.stats["frame_bytes"] += nbytes
         if fc["text"]:
             self._frames_text(block[:o_loc].view(torch.float64).view(n, fr.bvh_doubles), [n], got)
+        if rt is not None:
+            got[0]["frame0"] = rt["n_out"]
+            rt["n_in"], rt["n_out"] = rt["n_in"] + n_in, rt["n_out"] + n
         return got[0]
 
     # ------------------------------------------------------------------ audio
@@ -876,7 +982,8 @@ class LiveServer:
 
     def step(self):
         """-> {sid: {"pose": [tick, PO], "rpos": [tick, 3], "rrot": [tick, 4]}} for every row that had `tick` decodable frames
-        (the first step of a stream also carries frame 0, the first pose, in front)."""
+        (the first step of a stream also carries frame 0, the first pose, in front).  With `frames` also "frames"; on a re-timing
+        server those are the stream's new frames at ITS rate, possibly none, and "frame0" the index of the first of them."""
         rows = [None if x is None else dict(n_feat=x.n_feat, n_ring=x.n_ring, kd=x.kd) for x in self._rows]
         plan = plan_step(rows, self.tick, self.D)
         live = [r for r in range(self.rows) if plan[r] is not None]

@@ -13,7 +13,7 @@ import torch
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
                    DecStats, FramesDims, FramesRow, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
-                   ResampleDims, ResampleRow, Seg, SpeechDims, SpeechPtrs,
+                   ResampleDims, ResampleRow, RetimeRow, Seg, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
@@ -1087,6 +1087,8 @@ class LiveFrames:
     tables (`parents`, and `seq`, the joint order of the BVH rows: frames_seq(parents) unless given) and per row the placement
     and the quaternions last emitted.  `what`: names or the bit mask; `order`: "zyx" or "xzy"."""
 
+    state_bytes, prepare = "zeggs_live_frames_state_bytes", "zeggs_live_frames_prepare"      # (LiveRetime: the sixth header's)
+
     def __init__(self, rows, parents, max_frames, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
         from . import anim
         self.parents = [int(p) for p in parents]
@@ -1094,14 +1096,14 @@ class LiveFrames:
         self.what = what if isinstance(what, int) else frames_what(what)
         self.J = len(self.parents)
         self.d = FramesDims(int(rows), self.J, int(max_frames), self.what, anim._to_euler_order(order))
-        nbytes = api().zeggs_live_frames_state_bytes(self.d)
+        nbytes = getattr(api(), self.state_bytes)(self.d)
         if nbytes == 0:
-            raise ValueError(f"LiveFrames: {api().zeggs_last_error().decode()}")
+            raise ValueError(f"{type(self).__name__}: {api().zeggs_last_error().decode()}")
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         if len(self.seq) != self.J:
-            raise ValueError(f"LiveFrames: seq has {len(self.seq)} entries for {self.J} joints")
-        api().zeggs_live_frames_prepare(self.d, (C.c_int * self.J)(*self.parents), (C.c_int * self.J)(*self.seq), self.state,
-                                        self.state.numel(), _stream())
+            raise ValueError(f"{type(self).__name__}: seq has {len(self.seq)} entries for {self.J} joints")
+        getattr(api(), self.prepare)(self.d, (C.c_int * self.J)(*self.parents), (C.c_int * self.J)(*self.seq), self.state,
+                                     self.state.numel(), _stream())
         self.local_floats, self.world_floats, self.bvh_doubles = 7 + 7 * self.J, 7 * self.J, 3 + 3 * self.J
 
 
@@ -1120,6 +1122,77 @@ def live_frames(lf, rows, n, rows_dev=None):
     """zeggs_live_frames: rows[:n] a HOST array of FramesRow (device addresses inside), `rows_dev` the device address of a copy of
     the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
     api().zeggs_live_frames(lf.d, rows, _records(FramesRow, rows_dev), int(n), lf.state, lf.state.numel(), _stream())
+
+
+RETIME_MAX_TERM, RETIME_MAX_UP = 4096, 8         # csrc/retime_math.h: 1 <= L, M <= 4096 and L / M <= 8
+
+
+def retime_ratio(frame_rate, fps):
+    """frame_rate / fps = L / M in lowest terms -> (L, M).  `frame_rate`: an int, a fractions.Fraction, a (num, den) pair or a float
+    (taken as Fraction(str(x))); `fps` likewise.  ValueError naming both rates for a rate that is not positive and for a ratio
+    outside 1 <= L, M <= 4096, L / M <= 8."""
+    from fractions import Fraction
+
+    def frac(x):
+        if isinstance(x, bool):
+            raise TypeError
+        if isinstance(x, (tuple, list)):
+            num, den = x
+            return Fraction(frac(num), frac(den))
+        if isinstance(x, (float, np.floating)):
+            return Fraction(str(float(x)))
+        return Fraction(x)
+    try:
+        a, b = frac(frame_rate), frac(fps)
+        if a <= 0 or b <= 0:
+            raise ValueError
+        r = a / b
+    except (TypeError, ValueError, ZeroDivisionError):
+        raise ValueError(f"retime: frame rate {frame_rate!r} on a server at {fps!r} frames per second: not a positive rate") from None
+    L, M = r.numerator, r.denominator
+    if L > RETIME_MAX_TERM or M > RETIME_MAX_TERM or L > RETIME_MAX_UP * M:
+        raise ValueError(f"retime: frame rate {frame_rate!r} on a server at {fps!r} frames per second is the ratio {L} / {M} "
+                         f"(supported: 1 <= L, M <= {RETIME_MAX_TERM} in lowest terms and L / M <= {RETIME_MAX_UP})")
+    return int(L), int(M)
+
+
+def retime_n_out(n, L, M):
+    """output frames a stream has emitted after n input frames: ((n - 1) L) div M + 1, 0 for n = 0"""
+    return 0 if n < 1 else ((int(n) - 1) * int(L)) // int(M) + 1
+
+
+def retime_position(m, L, M):
+    """output frame m sits at input position m M / L -> (k, num): k + num / L"""
+    return divmod(int(m) * int(M), int(L))
+
+
+def retime_max_outputs(count, L, M):
+    """the most output frames a record of `count` input frames can give: ceil(count L / M) + 1"""
+    return 0 if count < 1 else -(-int(count) * int(L) // int(M)) + 1
+
+
+class LiveRetime(LiveFrames):
+    """The output head of `rows` live rows at each row's own frame rate (include/zeggs_hip_retime.h): LiveFrames' dims record and
+    tables, the rows' state with the last input frame kept raw behind the plain head's fields.  `max_frames` bounds the INPUT
+    frames of a record."""
+
+    state_bytes, prepare = "zeggs_live_retime_state_bytes", "zeggs_live_retime_prepare"
+
+
+def live_retime_reset(lr, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
+    """zeggs_live_retime_reset: the row's next input frame is frame 0 of a stream; the placement as live_frames_reset"""
+    place = [ref_pos, ref_rot, start_pos, start_rot]
+    if all(p is None for p in place):
+        api().zeggs_live_retime_reset(lr.d, lr.state, lr.state.numel(), int(row), None, None, None, None, 0, _stream())
+        return
+    arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
+    api().zeggs_live_retime_reset(lr.d, lr.state, lr.state.numel(), int(row), *arrs, 1, _stream())
+
+
+def live_frames_retimed(lr, rows, n, rows_dev=None):
+    """zeggs_live_frames_retimed: rows[:n] a HOST array of RetimeRow (device addresses, the caller's counters), `rows_dev` the device
+    address of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
+    api().zeggs_live_frames_retimed(lr.d, rows, _records(RetimeRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
 
 
 class LiveSpeech:
