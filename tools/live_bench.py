@@ -40,6 +40,13 @@
   enqueues per step (the same number: asserted) and the bytes it downloads per step.  The yardstick is the plain-head column of
   the same run -> profiles/live_retime.json.
 
+  --leg refilter: what the band-limiting filter of the re-timing head costs a step, per rows in {1, 8, 32, 64}: four servers in ONE
+  process with all three outputs -- the re-timing head without the filter, every row at 30 and at 120 frames a second, and the
+  same two with retime=dict(filter=True) (every row filtered, H = 8 and 4 model frames) -- are brought to 10 s through
+  push_many, then fed the same chunks tick by tick; each step() synchronised before and after, the servers taking turns at going
+  first, >= 200 ticks: median, p95, min, max of each, what each enqueues per step (the same number: asserted), the frames a row
+  got.  The yardstick is the unfiltered column of the same run -> profiles/live_refilter.json.
+
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
     python tools/live_bench.py [--out profiles/live_stream.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
@@ -48,6 +55,7 @@ Every case is a child process under its own `timeout`; the first one that fails 
     python tools/live_bench.py --leg resample [--out profiles/live_resample.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg frames [--out profiles/live_frames.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg retime [--out profiles/live_retime.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg refilter [--out profiles/live_refilter.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -418,6 +426,61 @@ def case_retime(rows, steps, age=10):
                 frame_bytes_per_step={k: round((srv[k].stats["frame_bytes"] - bytes0[k]) / len(t[k])) for k in names})
 
 
+REFILTER_LEGS = (("30", 30, False), ("120", 120, False), ("30 filtered", 30, True), ("120 filtered", 120, True))
+
+
+def case_refilter(rows, steps, age=10):
+    """step() with the re-timing head without and with its filter stage, every row at 30 and at 120 frames a second (local, world,
+    bvh): four servers in ONE process, the same rows' signals up to `age` (1 s push_many calls, drained), then tick by tick,
+    taking turns"""
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    head = dict(parents=synth.PARENTS, names=synth.BONE_NAMES, what=("local", "world", "bvh"), order="zyx", text=False)
+    place = dict(start_position=[0.0, 0.0, 0.0], start_rotation=[1.0, 0.0, 0.0, 0.0])
+    srv = {k: live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, frames=head,
+                              retime=dict(max_rate=120, filter=True) if filt else dict(max_rate=120)) for k, _, filt in REFILTER_LEGS}
+    sids = {k: [srv[k].open(first, st, **place, frame_rate=rate) for st in styles] for k, rate, _ in REFILTER_LEGS}
+    delay = {k: srv[k].frame_delay(sids[k][0])[0] for k in srv}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    names = [k for k, _, _ in REFILTER_LEGS]
+    t, frames = {k: [] for k in names}, {k: 0 for k in names}
+    ops_seen, i = {k: set() for k in names}, 0
+    while len(t[names[0]]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]
+        for k in names[i % 4:] + names[:i % 4]:                                    # taking turns at going first
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            while True:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k].append(dt)
+                frames[k] += out[sids[k][0]]["frames"]["bvh"].shape[0]
+                ops_seen[k].add(srv[k].stats["launches_per_step"])
+        pos = nxt
+    assert len({tuple(sorted(v)) for v in ops_seen.values()}) == 1 and len(ops_seen[names[0]]) == 1, ops_seen
+    n = len(t[names[0]])
+    assert abs(frames["30"] * 2 - n * TICK) <= 2 and abs(frames["120"] - 2 * n * TICK) <= 2, frames
+    assert abs(frames["30 filtered"] - frames["30"]) <= 1 and abs(frames["120 filtered"] - frames["120"]) <= 1, frames      # the filter only delays
+    return dict(kind="refilter", rows=rows, age_s=age, tick=TICK, launches_per_step=sorted(ops_seen[names[0]]), delay_frames=delay,
+                step={k: _summary(t[k]) for k in names}, frames_per_row={k: frames[k] for k in names})
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -449,10 +512,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600 or retime:64")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64 or refilter:64")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -463,7 +526,8 @@ def main():
                case_loudness(int(rest[0]), int(rest[1]), a.steps) if kind == "loudness" else
                case_resample(int(rest[0]), int(rest[1]), a.steps) if kind == "resample" else
                case_frames(int(rest[0]), int(rest[1]), a.steps) if kind == "frames" else
-               case_retime(int(rest[0]), a.steps) if kind == "retime" else case_baseline(int(rest[0]), a.steps))
+               case_retime(int(rest[0]), a.steps) if kind == "retime" else
+               case_refilter(int(rest[0]), a.steps) if kind == "refilter" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -488,6 +552,10 @@ def main():
         cases = [f"retime:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_retime.json")
+    if a.leg == "refilter":
+        cases = [f"refilter:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_refilter.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -570,6 +638,20 @@ def main():
                                                   frame_bytes_per_step=r["frame_bytes_per_step"][k]) for k, v in r["step"].items()}
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, step_with_the_plain_head_and_the_retiming_head=table, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "refilter":
+        table = {}
+        for r in results:
+            st = r["step"]
+            table[f"{r['rows']} rows"] = {rate: dict(unfiltered_median_ms=st[rate]["median_ms"], unfiltered_p95_ms=st[rate]["p95_ms"],
+                                                     filtered_median_ms=st[rate + " filtered"]["median_ms"], filtered_p95_ms=st[rate + " filtered"]["p95_ms"],
+                                                     filtered_over_unfiltered=round(st[rate + " filtered"]["median_ms"] / st[rate]["median_ms"], 4),
+                                                     delay_frames=r["delay_frames"][rate + " filtered"]) for rate in ("30", "120")}
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, step_without_and_with_the_filter=table, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

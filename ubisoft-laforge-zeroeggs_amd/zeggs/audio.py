@@ -261,24 +261,33 @@ def resample_options(options=None):
     return dict(zero_crossings=Z, rolloff=rolloff, beta=beta)
 
 
-def resample_table(fi, fo, zero_crossings=64, rolloff=0.95, beta=10.0):
-    """The converter's coefficients in float64 -> (table [L, taps], (L, M, WL)).  Row `phase` serves the outputs m with
-    (m M) mod L == phase; its tap j sits on input k = floor(m M / L) - H + j, H = ceil(W), taps = 2 H + 1:
+def sinc_table(L, M, zero_crossings, rolloff, beta):
+    """The Kaiser-windowed-sinc polyphase table of the ratio L / M in float64 -> (table [L, taps], WL), without the audio
+    converter's limits on the ratio and the options (resample_table and ops.refilter_table check their own): row `phase`, tap j:
     table[phase, j] = h(phase / L + H - j), h(t) = c sinc(c t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta) for |t| < W, else 0,
-    with s = min(1, L / M), c = rolloff s, W = zero_crossings / s = WL / L."""
-    L, M = resample_ratio(fi, fo)
-    o = resample_options(dict(zero_crossings=zero_crossings, rolloff=rolloff, beta=beta))
-    Z = o["zero_crossings"]
+    with s = min(1, L / M), c = rolloff s, WL = zero_crossings max(L, M), W = WL / L, H = ceil(W), taps = 2 H + 1."""
+    L, M, Z = int(L), int(M), int(zero_crossings)
     WL = Z * max(L, M)
     H = -(-WL // L)
     num = np.arange(L, dtype=np.int64)[:, None] + (H - np.arange(2 * H + 1, dtype=np.int64))[None, :] * L    # t L, exact
     t = num / float(L)
     W = WL / float(L)
-    c = o["rolloff"] * min(1.0, L / float(M))
+    c = rolloff * min(1.0, L / float(M))
     inside = np.abs(num) < WL
     r = np.where(inside, t / W, 0.0)
-    h = c * np.sinc(c * t) * np.i0(o["beta"] * np.sqrt(1.0 - r * r)) / np.i0(o["beta"])
-    return np.ascontiguousarray(np.where(inside, h, 0.0)), (L, M, WL)
+    h = c * np.sinc(c * t) * np.i0(beta * np.sqrt(1.0 - r * r)) / np.i0(beta)
+    return np.ascontiguousarray(np.where(inside, h, 0.0)), WL
+
+
+def resample_table(fi, fo, zero_crossings=64, rolloff=0.95, beta=10.0):
+    """The converter's coefficients in float64 -> (table [L, taps], (L, M, WL)).  Row `phase` serves the outputs m with
+    (m M) mod L == phase; its tap j sits on input k = floor(m M / L) - H + j, H = ceil(W), taps = 2 H + 1:
+    table[phase, j] = h(phase / L + H - j), h(t) = c sinc(c t) I0(beta sqrt(1 - (t / W)^2)) / I0(beta) for |t| < W, else 0,
+    with s = min(1, L / M), c = rolloff s, W = zero_crossings / s = WL / L (sinc_table)."""
+    L, M = resample_ratio(fi, fo)
+    o = resample_options(dict(zero_crossings=zero_crossings, rolloff=rolloff, beta=beta))
+    table, WL = sinc_table(L, M, o["zero_crossings"], o["rolloff"], o["beta"])
+    return table, (L, M, WL)
 
 
 def resample_ready(n, L, M, WL):

@@ -14,7 +14,8 @@ header include/zeggs_hip_live.h has its own tables, EXT_STRUCTS / EXT_PROTOTYPES
 include/zeggs_hip_loudness.h, LOUD_STRUCTS / LOUD_PROTOTYPES (tests/test_live_loudness_cpu.py), the fourth,
 include/zeggs_hip_resample.h, RS_STRUCTS / RS_PROTOTYPES (tests/test_live_resample_cpu.py), the fifth,
 include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_cpu.py), the sixth, include/zeggs_hip_retime.h,
-RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py): same loader.  torch is imported when a tensor is first converted, not
+RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py), the seventh, include/zeggs_hip_refilter.h, RF_STRUCTS / RF_PROTOTYPES
+(tests/test_live_refilter_cpu.py): same loader.  torch is imported when a tensor is first converted, not
 when this module is.
 """
 import ctypes as C
@@ -300,6 +301,21 @@ RT_PROTOTYPES = {
     "zeggs_live_frames_retimed": "status: ZeggsFramesDims* ZeggsRetimeRow* ZeggsRetimeRow* int any* size_t stream",
 }
 
+# ----------------------------------------------------------------------------- the seventh header (include/zeggs_hip_refilter.h)
+# The filter stage of the re-timing output head (tests/test_live_refilter_cpu.py compares these tables with the header).
+RefilterRow = _struct("RefilterRow", [(C.c_void_p, "pose rpos rrot local world bvh"), (C.c_long, "pose_ld rpos_ld rrot_ld n_in outputs"),
+                                      (C.c_int, "row count L M"), (C.c_void_p, "table"), (C.c_int, "half final")])
+RF_STRUCTS = {"ZeggsRefilterRow": RefilterRow}
+RF_PROTOTYPES = {
+    "zeggs_live_refilter_version": "int:",
+    "zeggs_live_refilter_state_bytes": "size_t: ZeggsFramesDims* int",
+    # parents / seq, ref / start: HOST arrays, as in the fifth header
+    "zeggs_live_refilter_prepare": "status: ZeggsFramesDims* int host* host* any* size_t stream",
+    "zeggs_live_refilter_reset": "status: ZeggsFramesDims* int any* size_t int host* host* host* host* int stream",
+    # rows_host / rows_dev as in zeggs_live_loudness_push
+    "zeggs_live_frames_refiltered": "status: ZeggsFramesDims* int ZeggsRefilterRow* ZeggsRefilterRow* int any* size_t stream",
+}
+
 
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
@@ -339,14 +355,14 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -384,7 +400,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -396,7 +412,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

@@ -29,7 +29,12 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
     50, 72, 90, 120, 30000/1001, ...) and "frames" holds the stream's new frames at ITS rate, possibly none in a step -- frames
     that fall on a model frame are the plain head's, frames between two are interpolated ahead of FK (positions on the line,
     rotations on the shortest arc) and go through the head's own Euler conversion, FK, sign rule and formatter; going down in
-    rate is point sampling.  Still ONE launch (zeggs_live_frames_retimed, in place of zeggs_live_frames) and one download a step.
+    rate is point sampling.  Still ONE launch (zeggs_live_frames_retimed, in place of zeggs_live_frames) and one download a step;
+  * LiveServer(frames=..., retime=dict(filter=True)) band-limits that re-timing: a stream at another rate than the server's (or
+    one opened with filtered=True) gets every frame as a windowed-sinc combination of the 2 H + 1 model frames around it, ahead
+    of FK -- nothing above half the output rate folds down, no corner at every model frame going up -- H model frames later
+    (frame_delay(sid)); the frames still owed at the end come with close().  Still ONE launch (zeggs_live_frames_refiltered),
+    filtered and unfiltered rows together.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -245,14 +250,20 @@ def frames_options(frames):
                 order=o["order"], text=bool(o["text"]), seq=seq)
 
 
-RETIME_DEFAULTS = dict(max_rate=None)
+RETIME_DEFAULTS = dict(max_rate=None, min_rate=None, filter=None)
+REFILTER_DEFAULT_HALF = 16        # the default min_rate is the lowest rate that keeps H_max at or below this
 
 
 def retime_options(retime, frames_conf, fps):
     """LiveServer's `retime` argument -> None (off) or dict(max_rate: the highest frame rate a stream may ask for, a Fraction,
     ratio: max_rate / fps as (L, M)): True is the defaults, a dict overrides them; max_rate None is the server's own rate `fps`
     (re-timing downward only: the staging blocks are the plain head's).  ValueError for anything else, for `retime` without
-    `frames`, and for a max_rate the kernel does not take (naming both rates)."""
+    `frames`, and for a max_rate the kernel does not take (naming both rates).
+    With filter=True | dict(zero_crossings, rolloff, beta) (ops.refilter_options) the dict also holds `filter` (the checked
+    options), `min_rate` (a Fraction: the lowest rate a FILTERED stream may ask for; default the lowest that keeps H_max <= 16,
+    never below fps / 4) and `half_max` = H_max = ceil(zero_crossings fps / min_rate), what the rows' rings are sized for.
+    ValueError naming both rates for a min_rate below fps / 4 (the filter takes M <= 4 L) or above fps, and for a min_rate
+    without `filter`."""
     if retime is None or retime is False:
         return None
     if retime is True:
@@ -270,7 +281,31 @@ def retime_options(retime, frames_conf, fps):
     if L < M:
         raise ValueError(f"LiveServer: retime max_rate {rate!r} is below the server's own {fps!r} frames per second")
     from fractions import Fraction
-    return dict(max_rate=Fraction(L, M) * Fraction(str(float(fps))), ratio=(L, M))
+    conf = dict(max_rate=Fraction(L, M) * Fraction(str(float(fps))), ratio=(L, M))
+    if o["filter"] is None or o["filter"] is False:
+        if o["min_rate"] is not None:
+            raise ValueError(f"LiveServer: retime min_rate {o['min_rate']!r} sizes the filter's history: it needs filter=True or a dict")
+        return conf
+    try:
+        fopt = ops.refilter_options(o["filter"])
+    except ValueError as e:
+        raise ValueError(f"LiveServer: retime filter: {e}") from None
+    Z, fr = fopt["zero_crossings"], Fraction(str(float(fps)))
+    if o["min_rate"] is None:
+        lo = max(fr * Z / REFILTER_DEFAULT_HALF, fr / ops.REFILTER_MAX_DOWN)
+    else:
+        try:
+            l, m = ops.retime_ratio(o["min_rate"], fps)
+        except ValueError as e:
+            raise ValueError(f"LiveServer: retime min_rate: {e}") from None
+        if m > ops.REFILTER_MAX_DOWN * l:
+            raise ValueError(f"LiveServer: retime min_rate {o['min_rate']!r} on a server at {fps!r} frames per second is below a quarter of "
+                             f"it, {float(fr / ops.REFILTER_MAX_DOWN)!r}: the filter takes M <= {ops.REFILTER_MAX_DOWN} L")
+        if l > m:
+            raise ValueError(f"LiveServer: retime min_rate {o['min_rate']!r} is above the server's own {fps!r} frames per second")
+        lo = fr * l / m
+    half_max = -(-(Z * fr) // lo)
+    return dict(conf, filter=fopt, min_rate=lo, half_max=int(half_max))
 
 
 def frames_placement(start_position, start_rotation):
@@ -384,7 +419,7 @@ class _Row:
         self.k_style, self.fade = 0, 0                   # last set_style: from frame k_style on, over `fade` frames
         self.rs = None                                   # a converting row: dict(fi, fmt, table, L, M, WL, n_in: raw samples received)
         self.offsets = None                              # frames: the joint positions of frame 0 as placed (the OFFSETs of a BVH file)
-        self.rt = None                                   # a re-timing server: dict(L, M, n_in: frames through the head, n_out: frames emitted)
+        self.rt = None                                   # a re-timing server: dict(L, M, n_in: frames through the head, n_out: frames emitted; with the filter stage also half, table)
 
 
 class LiveServer:
@@ -417,7 +452,17 @@ class LiveServer:
     size they were).  out[sid]["frames"] then holds the stream's new frames at ITS rate (possibly none: empty arrays) and
     "frame0", the index of the first of them; "pose" / "rpos" / "rrot" stay the decoder's rows at `fps`.  Going down in rate is
     point sampling -- 30 from 60 is every second frame, and motion above half the output rate aliases, as decimating a BVH
-    file would.  With None the server is the one it was."""
+    file would.  With None the server is the one it was.
+    retime=dict(..., filter=True | dict(zero_crossings=4, rolloff=0.75, beta=5.0), min_rate=None) adds the filter stage (DESIGN
+    3.7): every row's head runs through zeggs_live_frames_refiltered (the same number of launches), and a stream opened at
+    another rate than the server's, or with open(filtered=True), gets each frame as the Kaiser-windowed-sinc combination of the
+    2 H + 1 model frames around its position, ahead of FK: H = ceil(zero_crossings max(L, M) / L), 4 at or above the server's
+    rate and 10 at 24 from 60 with the defaults.  Such a stream's frames leave H model frames later (frame_delay(sid)): a step's
+    "frames" hold what became computable, "frame0" still counts the stream's own frames from 0, and close() hands out the
+    rest, so that the stream ends with exactly the frames an unfiltered one has.  `min_rate`: the lowest rate a filtered stream
+    may ask for; it sizes the rows' history, 2 ceil(zero_crossings fps / min_rate) raw frames a row; at least fps / 4, default
+    the lowest rate that keeps 16 frames to either side.  Rows opened with filtered=False (and rows at the server's rate)
+    run the unfiltered rules in the same launch, the same bits as without `filter`."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
                  device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None):
@@ -492,9 +537,17 @@ class LiveServer:
                 self._fr = ops.LiveFrames(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
                 self._fr_stage = _FrameStaging(R, self._fr.d.max_frames, self._fr.J, fc["mask"], self.dev)
             else:                                    # a row's share of the blocks: what max_rate makes of a record's input frames
-                self._fr = ops.LiveRetime(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
-                L, M = self.retime_conf["ratio"]
-                self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev, ops.RetimeRow)
+                rc = self.retime_conf
+                if "filter" in rc:                   # the filter stage: every row's head runs through its kernel, half = 0 without
+                    self._fr = ops.LiveRefilter(R, fc["parents"], self.tick + LOOKAHEAD + 1, rc["half_max"], rc["filter"], fc["mask"],
+                                                fc["order"], fc["seq"], self.dev)
+                else:
+                    self._fr = ops.LiveRetime(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
+                L, M = rc["ratio"]
+                # (a step's record never emits more than its input frames make at max_rate, filtered or not: the filter only
+                # delays; the tail record of close() has a block of its own, sized for it)
+                self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev,
+                                               ops.RefilterRow if "filter" in rc else ops.RetimeRow)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -533,7 +586,40 @@ class LiveServer:
                              f"max_rate {float(conf['max_rate'])!r} (LiveServer(retime=dict(max_rate=...)))")
         return dict(L=L, M=M, n_in=0, n_out=0)
 
-    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None, frame_rate=None):
+    def _filter_of(self, rt, frame_rate, filtered):
+        """open()'s `filtered` -> the row's dict with the filter's half = H and table where the stream is filtered (the table is
+        built and uploaded here, the first time a row opens at the ratio).  None: filtered if and only if the server has the
+        filter stage and the stream's rate differs from the server's.  ValueError naming both rates for filtered=True on a
+        server without `filter`, for a ratio the filter does not take and for a rate below the server's min_rate."""
+        conf = self.retime_conf
+        rate = self.fps if frame_rate is None else frame_rate
+        if conf is None or "filter" not in conf:
+            if filtered:
+                raise ValueError(f"LiveServer.open: filtered=True at frame_rate {rate!r} on a server that hands out {self.fps!r} frames per "
+                                 "second: the filter stage is off (LiveServer(frames=..., retime=dict(filter=True)))")
+            return rt
+        L, M = rt["L"], rt["M"]
+        if not (L != M if filtered is None else filtered):
+            return dict(rt, half=0, table=None)
+        if L > ops.REFILTER_MAX_L or M > ops.REFILTER_MAX_DOWN * L:
+            raise ValueError(f"LiveServer.open: frame_rate {rate!r} on a server at {self.fps!r} frames per second is the ratio {L} / {M}: a "
+                             f"filtered stream takes L <= {ops.REFILTER_MAX_L} and M <= {ops.REFILTER_MAX_DOWN} L (filtered=False: point sampling)")
+        from fractions import Fraction
+        if Fraction(L, M) * Fraction(str(float(self.fps))) < conf["min_rate"]:
+            raise ValueError(f"LiveServer.open: frame_rate {rate!r} on a server at {self.fps!r} frames per second is below its min_rate "
+                             f"{float(conf['min_rate'])!r} (LiveServer(retime=dict(min_rate=...)) sizes the filter's history)")
+        t = self._fr.table(L, M)
+        return dict(rt, half=t["half"], table=t["table"])
+
+    def frame_delay(self, sid):
+        """what the filter stage adds to stream `sid`'s latency -> (input frames, seconds): H frames of the server's rate for a
+        filtered stream (4 at or above the server's rate, 10 at 24 from 60 with the defaults), (0, 0.0) for any other"""
+        rt = self._row(sid)[1].rt
+        H = 0 if rt is None else int(rt.get("half", 0))
+        return H, H / self.fps
+
+    def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None, frame_rate=None,
+             filtered=None):
         """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
         -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
         what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing.
@@ -547,14 +633,19 @@ class LiveServer:
         `frame_rate` (a server with `retime`): the rate this stream's "frames" leave at -- an int, a fractions.Fraction, a
         (num, den) pair, or a float taken as Fraction(str(x)) (29.97 is 2997/100; the NTSC rate proper is (30000, 1001));
         None: the server's rate.  ValueError naming both rates on a server without `retime`, for a ratio outside 1 <= L, M
-        <= 4096, L / M <= 8 and for a rate above the server's max_rate."""
+        <= 4096, L / M <= 8 and for a rate above the server's max_rate.
+        `filtered` (a server with retime=dict(filter=...)): True -- the stream's frames are band-limited ahead of FK, a windowed-sinc
+        combination of the 2 H + 1 model frames around each output frame (DESIGN 3.7), H = frame_delay(sid)[0] model frames later;
+        False -- the two cheap rules (point sampling downward, the shortest arc upward); None: filtered if and only if the
+        stream's rate differs from the server's.  filtered=True at the server's own rate is a jitter filter.  ValueError naming
+        both rates for filtered=True on a server without `filter`, a ratio with L > 1024 or M > 4 L and a rate below min_rate."""
         rs = resample_row(rate, pcm, self.fs)
         place = frames_placement(start_position, start_rotation)
         if place is not None and self._fr is None:
             raise ValueError("LiveServer.open: a placement needs the output head (LiveServer(frames=...))")
         if self._loud is None and float(gain) != 1.0:
             raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
-        rt = self._frame_rate(frame_rate)
+        rt = LiveServer._filter_of(self, self._frame_rate(frame_rate), frame_rate, filtered)
         free = [r for r in range(self.rows) if self._rows[r] is None]
         if not free:
             raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
@@ -581,7 +672,8 @@ class LiveServer:
             J = self._fr.J
             p0, r0 = f32(root_pos).reshape(1, 3), f32(root_rot).reshape(1, 4)
             row.rt = rt
-            reset = ops.live_frames_reset if rt is None else ops.live_retime_reset
+            reset = (ops.live_frames_reset if rt is None else ops.live_refilter_reset if isinstance(self._fr, ops.LiveRefilter)
+                     else ops.live_retime_reset)
             if place is None:
                 reset(self._fr, r)
             else:
@@ -596,7 +688,8 @@ class LiveServer:
     def bvh_header(self, sid, nframes=0):
         """the head of a BVH file for stream `sid` (anim.bvh_header: HIERARCHY and the MOTION head for `nframes` frames at the
         server's dt, or the stream's own frame time dt M / L on a re-timing server) with the joint positions of the stream's frame
-        0, as placed, as OFFSETs -- what write_bvh and generate_gesture write.  Followed by the stream's "text" (or anim.format_rows of its "bvh" rows) it is a BVH file."""
+        0, as placed, as OFFSETs (the MODEL's frame 0, for a filtered stream too: its own frame 0 already leans on the frames behind it) -- what
+        write_bvh and generate_gesture write.  `nframes` of a closed stream is the same with and without the filter.  Followed by the stream's "text" (or anim.format_rows of its "bvh" rows) it is a BVH file."""
         if self._fr is None:
             raise RuntimeError("LiveServer: the output head is off (LiveServer(frames=...))")
         fc, row = self.frames_conf, self._row(sid)[1]
@@ -621,7 +714,8 @@ class LiveServer:
         n_in = [int(o["pose"].shape[0]) for o in src]
         rts = [self._rows[r].rt for r in live] if self.retime_conf is not None else None
         # a re-timing server: a record emits what the counting rule gives its row for these input frames
-        counts = n_in if rts is None else [ops.retime_n_out(t["n_in"] + c, t["L"], t["M"]) - t["n_out"] for t, c in zip(rts, n_in)]
+        counts = n_in if rts is None else [self._emitted(t, t["n_in"] + c, False) - t["n_out"] for t, c in zip(rts, n_in)]
+        filt = isinstance(fr, ops.LiveRefilter)
         N, J = sum(counts), fr.J
         use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
         base = stg.dev.data_ptr()
@@ -637,12 +731,15 @@ class LiveServer:
             q.row, q.count = r, n_in[i]
             if rts is not None:
                 q.L, q.M, q.n_in, q.outputs = rts[i]["L"], rts[i]["M"], rts[i]["n_in"], c
+                if filt:
+                    q.half, q.final = rts[i]["half"], 0
+                    q.table = rts[i]["table"].data_ptr() if q.half else None
             a += c
         nbytes = frames_block_bytes(N, J, fc["mask"])
         if rts is None:
             ops.live_frames(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
         else:
-            ops.live_frames_retimed(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
+            (ops.live_frames_refiltered if filt else ops.live_frames_retimed)(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
         # (a step in which no row of a re-timing server emits a frame has nothing to bring down; it counts as if it had)
         got = frames_unpack(stg.download(nbytes) if N else np.zeros(0, np.uint8), counts, J, fc["mask"])
         self._ops += 2
@@ -657,20 +754,29 @@ class LiveServer:
                 rts[i]["n_out"] += counts[i]
             out[self._rows[r].sid]["frames"] = g
 
+    @staticmethod
+    def _emitted(rt, n, final):
+        """output frames a re-timing row has emitted after n input frames: the filtered rule while a filtered stream runs"""
+        if rt.get("half", 0) and not final:
+            return ops.refilter_n_out(n, rt["L"], rt["M"], rt["half"])
+        return ops.retime_n_out(n, rt["L"], rt["M"])
+
     def _frames_close(self, r, o):
         """the output head of close(): the tail `o` of row r through the same kernel and state, max_frames frames a call; on a
-        re-timing server the output frames the counting rule gives the row for them -- there is no tail of its own"""
+        re-timing server the output frames the counting rule gives the row for them -- there is no tail of its own, except for
+        a filtered stream: its last record is marked final and emits everything up to retime_n_out of all its input frames"""
         fr, fc, rt = self._fr, self.frames_conf, self._rows[r].rt
         n_in, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
-        n = n_in if rt is None else ops.retime_n_out(rt["n_in"] + n_in, rt["L"], rt["M"]) - rt["n_out"]
+        filt = isinstance(fr, ops.LiveRefilter)
+        n = n_in if rt is None else self._emitted(rt, rt["n_in"] + n_in, True) - rt["n_out"]
         use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
         nbytes = frames_block_bytes(n, J, fc["mask"])
         block = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
         o_loc = n * fr.bvh_doubles * 8 * use[0]
         o_wld = o_loc + n * fr.local_floats * 4 * use[1]
-        rec = ((ops.FramesRow if rt is None else ops.RetimeRow) * 1)()
+        rec = ((ops.FramesRow if rt is None else ops.RefilterRow if filt else ops.RetimeRow) * 1)()
         q, base, a = rec[0], block.data_ptr(), 0          # a: output frames written so far
-        for i in range(0, n_in, M):
+        for i in range(0, max(n_in, 1 if filt and rt["half"] else 0), M):       # (a filtered stream: the final record, even an empty one)
             q.pose, q.rpos, q.rrot = o["pose"][i:].data_ptr(), o["rpos"][i:].data_ptr(), o["rrot"][i:].data_ptr()
             q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
             q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
@@ -682,8 +788,14 @@ class LiveServer:
                 a += q.count
             else:
                 q.L, q.M, q.n_in = rt["L"], rt["M"], rt["n_in"] + i
-                q.outputs = ops.retime_n_out(q.n_in + q.count, q.L, q.M) - ops.retime_n_out(q.n_in, q.L, q.M)
-                ops.live_frames_retimed(fr, rec, 1)
+                if filt:
+                    q.half, q.final = rt["half"], int(i + M >= n_in)
+                    q.table = rt["table"].data_ptr() if q.half else None
+                    q.outputs = self._emitted(rt, q.n_in + q.count, q.final) - self._emitted(rt, q.n_in, False)
+                    ops.live_frames_refiltered(fr, rec, 1)
+                else:
+                    q.outputs = ops.retime_n_out(q.n_in + q.count, q.L, q.M) - ops.retime_n_out(q.n_in, q.L, q.M)
+                    ops.live_frames_retimed(fr, rec, 1)
                 a += q.outputs
         got = frames_unpack(block.cpu().numpy(), [n], J, fc["mask"])
         self.stats["frame_bytes"] += nbytes
@@ -1070,6 +1182,10 @@ class LiveServer:
                 row.kd += n
             out = {k: torch.cat([o[i] for o in outs]).contiguous() for i, k in enumerate(("pose", "rpos", "rrot"))} if outs else {}
             if outs and self._fr is not None:
+                out["frames"] = self._frames_close(r, out)
+            elif self._fr is not None and row.rt is not None and row.rt.get("half", 0) and row.rt["n_in"] > 0:
+                # a filtered stream whose frames all left through step(): the final record brings no frame and emits the tail
+                out = dict(pose=self.pose[r:r], rpos=self.rpos[r:r], rrot=self.rrot[r:r])
                 out["frames"] = self._frames_close(r, out)
         self._rows[r] = None
         del self._sids[sid]

@@ -13,7 +13,7 @@ import torch
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
                    DecStats, FramesDims, FramesRow, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
-                   ResampleDims, ResampleRow, RetimeRow, Seg, SpeechDims, SpeechPtrs,
+                   ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
@@ -1088,6 +1088,7 @@ class LiveFrames:
     and the quaternions last emitted.  `what`: names or the bit mask; `order`: "zyx" or "xzy"."""
 
     state_bytes, prepare = "zeggs_live_frames_state_bytes", "zeggs_live_frames_prepare"      # (LiveRetime: the sixth header's)
+    extra = ()                                   # what the entry points take behind the dims (LiveRefilter: max_half)
 
     def __init__(self, rows, parents, max_frames, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
         from . import anim
@@ -1096,13 +1097,13 @@ class LiveFrames:
         self.what = what if isinstance(what, int) else frames_what(what)
         self.J = len(self.parents)
         self.d = FramesDims(int(rows), self.J, int(max_frames), self.what, anim._to_euler_order(order))
-        nbytes = getattr(api(), self.state_bytes)(self.d)
+        nbytes = getattr(api(), self.state_bytes)(self.d, *self.extra)
         if nbytes == 0:
             raise ValueError(f"{type(self).__name__}: {api().zeggs_last_error().decode()}")
         self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
         if len(self.seq) != self.J:
             raise ValueError(f"{type(self).__name__}: seq has {len(self.seq)} entries for {self.J} joints")
-        getattr(api(), self.prepare)(self.d, (C.c_int * self.J)(*self.parents), (C.c_int * self.J)(*self.seq), self.state,
+        getattr(api(), self.prepare)(self.d, *self.extra, (C.c_int * self.J)(*self.parents), (C.c_int * self.J)(*self.seq), self.state,
                                      self.state.numel(), _stream())
         self.local_floats, self.world_floats, self.bvh_doubles = 7 + 7 * self.J, 7 * self.J, 3 + 3 * self.J
 
@@ -1193,6 +1194,101 @@ def live_frames_retimed(lr, rows, n, rows_dev=None):
     """zeggs_live_frames_retimed: rows[:n] a HOST array of RetimeRow (device addresses, the caller's counters), `rows_dev` the device
     address of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
     api().zeggs_live_frames_retimed(lr.d, rows, _records(RetimeRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
+
+
+REFILTER_MAX_L, REFILTER_MAX_DOWN, REFILTER_MAX_Z = 1024, 4, 8        # csrc/refilter_math.h: a filtered row has L <= 1024, M <= 4 L
+REFILTER_DEFAULTS = dict(zero_crossings=4, rolloff=0.75, beta=5.0)
+
+
+def refilter_options(options=None):
+    """dict(zero_crossings, rolloff, beta) over REFILTER_DEFAULTS, checked: zero_crossings an integer 1 .. 8, 0 < rolloff <= 1,
+    beta >= 0 and finite; True or None: the defaults.  Anything else raises ValueError."""
+    if options is None or options is True:
+        options = {}
+    if not isinstance(options, dict) or set(options) - set(REFILTER_DEFAULTS):
+        raise ValueError(f"refilter: filter is True or a dict with keys {sorted(REFILTER_DEFAULTS)}")
+    o = dict(REFILTER_DEFAULTS, **options)
+    try:
+        Z, rolloff, beta = int(o["zero_crossings"]), float(o["rolloff"]), float(o["beta"])
+    except (TypeError, ValueError):
+        raise ValueError(f"refilter: options {options!r}") from None
+    if isinstance(o["zero_crossings"], bool) or Z != o["zero_crossings"] or not 1 <= Z <= REFILTER_MAX_Z:
+        raise ValueError(f"refilter: zero_crossings {o['zero_crossings']} (an integer 1 .. {REFILTER_MAX_Z})")
+    if not 0.0 < rolloff <= 1.0:
+        raise ValueError(f"refilter: rolloff {rolloff} (0 < rolloff <= 1)")
+    if not (np.isfinite(beta) and beta >= 0.0):
+        raise ValueError(f"refilter: beta {beta} (>= 0)")
+    return dict(zero_crossings=Z, rolloff=rolloff, beta=beta)
+
+
+def refilter_half(L, M, zero_crossings):
+    """H = ceil(W), W = zero_crossings max(L, M) / L: the input frames the filter reaches to either side (2 H + 1 taps)"""
+    return -(-int(zero_crossings) * max(int(L), int(M)) // int(L))
+
+
+def refilter_n_out(n, L, M, H):
+    """output frames a filtered stream has emitted after n input frames while it runs: 0 for n <= H, else
+    ((n - H) L - 1) div M + 1 (output m leaves with input frame k + H); a closed stream has retime_n_out(n)"""
+    n, H = int(n), int(H)
+    return 0 if n <= H else ((n - H) * int(L) - 1) // int(M) + 1
+
+
+def refilter_table(L, M, zero_crossings=4, rolloff=0.75, beta=5.0):
+    """The filter's coefficients in float64 -> (table [L, 2 H + 1], H): audio.sinc_table (the audio converter's h), each phase
+    row divided by its own sum accumulated in ascending j -- unit DC gain per phase, a pose held still stays that pose.
+    ValueError for a ratio a filtered row does not take (L > 1024 or M > 4 L)."""
+    from . import audio
+    L, M = int(L), int(M)
+    if L < 1 or M < 1 or L > REFILTER_MAX_L or M > REFILTER_MAX_DOWN * L:
+        raise ValueError(f"refilter: the ratio {L} / {M} (a filtered row takes L <= {REFILTER_MAX_L} and M <= {REFILTER_MAX_DOWN} L)")
+    o = refilter_options(dict(zero_crossings=zero_crossings, rolloff=rolloff, beta=beta))
+    table, _ = audio.sinc_table(L, M, o["zero_crossings"], o["rolloff"], o["beta"])
+    total = np.zeros(L)
+    for j in range(table.shape[1]):
+        total = total + table[:, j]
+    return np.ascontiguousarray(table / total[:, None]), refilter_half(L, M, o["zero_crossings"])
+
+
+class LiveRefilter(LiveFrames):
+    """The re-timing output head with its filter stage for `rows` live rows (include/zeggs_hip_refilter.h): LiveFrames' dims record
+    and tables, per row the plain head's state and a ring of the last 2 max_half input frames, and the filter's tables per ratio
+    on the device (`options`: refilter_options).  `max_frames` bounds the INPUT frames of a record, `max_half` the H of a row."""
+
+    state_bytes, prepare = "zeggs_live_refilter_state_bytes", "zeggs_live_refilter_prepare"
+
+    def __init__(self, rows, parents, max_frames, max_half, options=None, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
+        self.max_half, self.options = int(max_half), refilter_options(options)
+        self.extra = (self.max_half,)
+        self.tables = {}
+        super().__init__(rows, parents, max_frames, what, order, seq, device)
+
+    def table(self, L, M):
+        """-> dict(table: float64 tensor [L, 2 H + 1] on the device, half: H) for the ratio L / M, built and uploaded the first
+        time a row opens at it; ValueError for a ratio a filtered row does not take or an H above max_half"""
+        key = (int(L), int(M))
+        if key not in self.tables:
+            tab, H = refilter_table(*key, **self.options)
+            if H > self.max_half:
+                raise ValueError(f"refilter: the ratio {key[0]} / {key[1]} needs {H} input frames to either side, max_half is {self.max_half}")
+            self.tables[key] = dict(table=torch.as_tensor(tab).to(self.state.device).contiguous(), half=H)
+        return self.tables[key]
+
+
+def live_refilter_reset(lr, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
+    """zeggs_live_refilter_reset: the row's next input frame is frame 0 of a stream; the placement as live_frames_reset"""
+    place = [ref_pos, ref_rot, start_pos, start_rot]
+    if all(p is None for p in place):
+        api().zeggs_live_refilter_reset(lr.d, lr.max_half, lr.state, lr.state.numel(), int(row), None, None, None, None, 0, _stream())
+        return
+    arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
+    api().zeggs_live_refilter_reset(lr.d, lr.max_half, lr.state, lr.state.numel(), int(row), *arrs, 1, _stream())
+
+
+def live_frames_refiltered(lr, rows, n, rows_dev=None):
+    """zeggs_live_frames_refiltered: rows[:n] a HOST array of RefilterRow (device addresses, the caller's counters, half = 0 for a
+    row without the filter), `rows_dev` the device address of a copy of the same records (None: one record, in the kernel
+    arguments): ONE launch for all of them"""
+    api().zeggs_live_frames_refiltered(lr.d, lr.max_half, rows, _records(RefilterRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
 
 
 class LiveSpeech:
