@@ -46,6 +46,9 @@
   push_many, then fed the same chunks tick by tick; each step() synchronised before and after, the servers taking turns at going
   first, >= 200 ticks: median, p95, min, max of each, what each enqueues per step (the same number: asserted), the frames a row
   got.  The yardstick is the unfiltered column of the same run -> profiles/live_refilter.json.
+  --leg snapshot: what LiveServer.snapshot_many() of all rows and restore() of one row cost, per rows in {1, 8, 32, 64}: a server with
+  every stage on, medians over `--steps` repeats beside the median step() of the same process; the figure to look at is
+  snapshot_many at 64 rows as a fraction of the 66.7 ms tick and beside that step() -> profiles/live_snapshot.json.
 
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
@@ -56,6 +59,7 @@ Every case is a child process under its own `timeout`; the first one that fails 
     python tools/live_bench.py --leg frames [--out profiles/live_frames.json] [--steps 200] [--rows 1,8,32,64] [--ages 10,600]
     python tools/live_bench.py --leg retime [--out profiles/live_retime.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg refilter [--out profiles/live_refilter.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg snapshot [--out profiles/live_snapshot.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -481,6 +485,67 @@ def case_refilter(rows, steps, age=10):
                 step={k: _summary(t[k]) for k in names}, frames_per_row={k: frames[k] for k in names})
 
 
+def case_snapshot(rows, steps, age=10):
+    """snapshot_many() of all rows and restore() of one row beside step(), in ONE process: a server with every stage on (running
+    loudness, frames with all three outputs, the filtering re-timing head; every row at 24 frames a second, every fourth row
+    48 kHz s16) aged `age` seconds; then `steps` ticks, each timed: the step, a snapshot of every row, and the restore of row 0's
+    blob into a second server of the same configuration (its row is closed again outside the timing)"""
+    import numpy as np
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    head = dict(parents=synth.PARENTS, names=synth.BONE_NAMES, what=("local", "world", "bvh"), order="zyx", text=False)
+    kw = dict(rows=rows, tick=TICK, loudness="running", frames=head, retime=dict(max_rate=120, filter=True, min_rate=24))
+    srv, dst = (live.LiveServer(se, de, stats, CONF, synth.DT, **kw) for _ in range(2))
+    s16 = [r % 4 == 3 for r in range(rows)]
+    sids = [srv.open(first, st, frame_rate=24, **(dict(rate=3 * FS, pcm="s16") if c else {})) for st, c in zip(styles, s16)]
+
+    def chunks(lo, hi):
+        """row r's samples [lo, hi) at the server's rate; a converting row delivers each of them three times, as int16"""
+        out = {}
+        for r, sid in enumerate(sids):
+            x = _samples(base, r, lo, hi)
+            out[sid] = np.repeat(np.round(x * 32767.0).astype(np.int16), 3) if s16[r] else x
+        return out
+    pos = 0
+    while pos < age * FS:
+        srv.push_many(chunks(pos, pos + FS))
+        srv.drain()
+        pos += FS
+    torch.cuda.synchronize()
+    t = dict(step=[], snapshot_many=[], restore=[])
+    blob_bytes, i = 0, 0
+    while len(t["step"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        srv.push_many(chunks(pos, nxt))
+        pos = nxt
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = srv.step()
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        if not out:
+            continue
+        assert len(out) == rows
+        t["step"].append(dt)
+        t0 = time.perf_counter()
+        blobs = srv.snapshot_many()                                 # (returns when the download is there)
+        t["snapshot_many"].append(time.perf_counter() - t0)
+        assert len(blobs) == rows and srv.stats["ops_last_snapshot"] == 3
+        blob_bytes = sum(b.size for b in blobs.values())
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        new = dst.restore(blobs[sids[0]])
+        torch.cuda.synchronize()
+        t["restore"].append(time.perf_counter() - t0)
+        dst.close(new)
+    return dict(kind="snapshot", rows=rows, age_s=age, tick=TICK, blob_bytes_all_rows=int(blob_bytes), blob_bytes_row_0=int(blobs[sids[0]].size),
+                launches_per_step=srv.stats["launches_per_step"], **{k: _summary(v) for k, v in t.items()})
+
+
 def case_baseline(age, steps):
     import torch
     from zeggs import stream, synth
@@ -512,10 +577,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64 or refilter:64")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64 or snapshot:64")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -527,7 +592,8 @@ def main():
                case_resample(int(rest[0]), int(rest[1]), a.steps) if kind == "resample" else
                case_frames(int(rest[0]), int(rest[1]), a.steps) if kind == "frames" else
                case_retime(int(rest[0]), a.steps) if kind == "retime" else
-               case_refilter(int(rest[0]), a.steps) if kind == "refilter" else case_baseline(int(rest[0]), a.steps))
+               case_refilter(int(rest[0]), a.steps) if kind == "refilter" else
+               case_snapshot(int(rest[0]), a.steps) if kind == "snapshot" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -556,6 +622,10 @@ def main():
         cases = [f"refilter:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_refilter.json")
+    if a.leg == "snapshot":
+        cases = [f"snapshot:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_snapshot.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -652,6 +722,19 @@ def main():
                                                      delay_frames=r["delay_frames"][rate + " filtered"]) for rate in ("30", "120")}
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, step_without_and_with_the_filter=table, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "snapshot":
+        budget = 1e3 * TICK / FPS
+        table = {f"{r['rows']} rows": dict(step_median_ms=r["step"]["median_ms"], snapshot_many_median_ms=r["snapshot_many"]["median_ms"],
+                                           snapshot_many_p95_ms=r["snapshot_many"]["p95_ms"], restore_one_row_median_ms=r["restore"]["median_ms"],
+                                           snapshot_many_over_the_tick=round(r["snapshot_many"]["median_ms"] / budget, 4),
+                                           snapshot_many_over_step=round(r["snapshot_many"]["median_ms"] / r["step"]["median_ms"], 4),
+                                           blob_bytes_all_rows=r["blob_bytes_all_rows"]) for r in results}
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   tick_ms=round(budget, 2), repeats_per_case=a.steps, snapshot_of_all_rows_and_restore_of_one_beside_step=table, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

@@ -15,6 +15,7 @@
 #include "../../include/zeggs_hip_loudness.h"
 #include "common.h"
 #include "loud_math.h"
+#include "snapshot_math.h"
 
 #include <atomic>
 
@@ -30,11 +31,10 @@ struct LoudHead {            // 128 bytes in front of a row's rings
   int hold, gated, kept;     // hold flag / blocks past the relative gate at the last block / the last block left the gain alone
   double pad[7];
 };
-static_assert(sizeof(LoudHead) == 128, "LoudHead");
+static_assert(sizeof(LoudHead) == LOUD_HEAD_BYTES, "LoudHead");
 
-__host__ __device__ inline size_t loud_row_bytes(const ZeggsLoudDims& d) {
-  return sizeof(LoudHead) + sizeof(double) * ((size_t)loud_block_len(d.fs) + 2 * (size_t)d.ring_blocks);
-}
+// (the layout of a row is stated in snapshot_math.h, which also reports it as the spans of a snapshot)
+__host__ __device__ inline size_t loud_row_bytes(const ZeggsLoudDims& d) { return loud_state_row_bytes(d.fs, d.ring_blocks); }
 
 struct Biquad { double b0, b1, b2, a1, a2; };
 // one sample of direct form II transposed (scipy.signal.lfilter): y = b0 x + s1; s1 = b1 x - a1 y + s2; s2 = b2 x - a2 y

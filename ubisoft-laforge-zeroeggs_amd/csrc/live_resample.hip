@@ -16,6 +16,7 @@
 #include "../../include/zeggs_hip_resample.h"
 #include "common.h"
 #include "resample_math.h"
+#include "snapshot_math.h"
 
 namespace {
 
@@ -161,13 +162,13 @@ extern "C" int zeggs_live_resample_version(void) { return 1; }
 
 extern "C" size_t zeggs_resample_state_bytes(const ZeggsResampleDims* d) {
   if (rs_dims_ok(d, nullptr, (size_t)-1) != 0) return 0;
-  return (size_t)d->rows * (size_t)d->history * sizeof(float);
+  return (size_t)d->rows * rs_state_row_bytes(d->history);      // (a row's place is stated in snapshot_math.h)
 }
 
 extern "C" int zeggs_resample_reset(const ZeggsResampleDims* d, void* state, size_t state_bytes, int row, void* stream) {
   ZTRY(rs_dims_ok(d, state, state_bytes));
   ZCHECK(row >= 0 && row < d->rows, "resample reset: row %d of %d", row, d->rows);
-  const size_t rb = (size_t)d->history * sizeof(float);
+  const size_t rb = rs_state_row_bytes(d->history);
   hipError_t e = hipMemsetAsync((char*)state + (size_t)row * rb, 0, rb, (hipStream_t)stream);
   ZCHECK(e == hipSuccess, "resample reset: %s", hipGetErrorString(e));
   return 0;

@@ -34,12 +34,19 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
     one opened with filtered=True) gets every frame as a windowed-sinc combination of the 2 H + 1 model frames around it, ahead
     of FK -- nothing above half the output rate folds down, no corner at every model frame going up -- H model frames later
     (frame_delay(sid)); the frames still owed at the end come with close().  Still ONE launch (zeggs_live_frames_refiltered),
-    filtered and unfiltered rows together.
+    filtered and unfiltered rows together;
+  * snapshot(sid) / snapshot_many() take everything that determines a stream's future outputs off the device as one numpy.uint8
+    blob -- window, pending features, ring, decoder state, the row's spans of the loudness, converter and head state blocks
+    (include/zeggs_hip_snapshot.h), the host counters -- and restore(blob) puts it into a free row of any server with the same
+    configuration: a drain for a restart, a move to another GPU, a fork.  ONE upload, ONE launch (zeggs_live_pack) and ONE
+    download whatever the number of rows; restore() is one upload and one launch (zeggs_live_unpack) after every field was
+    checked on the host; snapshot_info(blob) reads a blob's header without a device.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
 """
 import ctypes as C
+import types
 
 import numpy as np
 import torch
@@ -396,6 +403,165 @@ class _FrameStaging:
         return host.numpy()[:nbytes]
 
 
+# ---------------------------------------------------------------------------------------------------------------- snapshots
+# A blob, little-endian: [magic 8 | format u32 | zeggs_live_snapshot_version() u32 | sid i64 | fingerprint fields u32 |
+# sections u32 | total bytes u64 | fingerprint float64[len(SNAP_FINGERPRINT)] | section table (kind u32, 0 u32, offset u64, bytes
+# u64)[len(SNAP_SECTIONS)] | sections, each on a 16-byte boundary in the table's order, zero padded].  Every kind is in the table;
+# one a stream does not have (no converter, a server without the head) has 0 bytes.
+SNAP_MAGIC, SNAP_FORMAT = b"ZEGGSNAP", 1
+# what sizes or interprets the state (LiveServer._fingerprint); NOT the weights and the statistics
+SNAP_FINGERPRINT = ("tick", "fs", "fps", "mel_n_fft", "mel_hop", "mel_n_mels", "mel_fs", "mel_fps", "mel_min_clip", "mel_pre_emph", "mel_flags",
+                    "FC", "ring_depth", "ring_width", "H", "ST", "PO", "speech_width", "KW",
+                    "loudness", "loudness_target", "loudness_ring_blocks", "loudness_warmup", "loudness_gain_lo", "loudness_gain_hi",
+                    "resample_zero_crossings", "resample_rolloff", "resample_beta",
+                    "frames", "frames_joints", "frames_what", "frames_order", "frames_seq",
+                    "retime", "retime_max_L", "retime_max_M", "filter", "filter_zero_crossings", "filter_rolloff", "filter_beta",
+                    "filter_min_rate_num", "filter_min_rate_den", "filter_half_max")
+SNAP_SECTIONS = ("row", "offsets", "window", "feats", "ring", "h", "pose", "rpos", "rrot", "gaze", "sty_old", "sty_new", "loudness",
+                 "resample", "head")
+# the `row` section, int64 each: the six counters, what _Row holds of the style fade, the converter and the output head, and how
+# the `offsets` section is to be read (bytes per value, values)
+SNAP_ROW = ("n", "base", "n_feat", "fbase", "n_ring", "kd", "sent0", "k_style", "fade", "rs", "rs_fi", "rs_fmt", "rs_n_in",
+            "rt", "rt_L", "rt_M", "rt_n_in", "rt_n_out", "rt_half", "offsets_itemsize", "offsets_count")
+_SNAP_HEAD = 8 + 4 + 4 + 8 + 4 + 4 + 8
+_a16 = lambda x: (int(x) + 15) // 16 * 16  # noqa: E731
+
+
+def snapshot_layout(sizes):
+    """bytes per section, in SNAP_SECTIONS' order -> (their offsets in the blob, the blob's length): the header, then every section
+    on the next 16-byte boundary"""
+    assert len(sizes) == len(SNAP_SECTIONS)
+    at, offs = _a16(_SNAP_HEAD + 8 * len(SNAP_FINGERPRINT) + 24 * len(SNAP_SECTIONS)), []
+    for b in sizes:
+        offs.append(at)
+        at = _a16(at + int(b))
+    return offs, at
+
+
+def snapshot_header(sid, version, fingerprint, sizes):
+    """the bytes in front of the first section: `fingerprint` a dict over SNAP_FINGERPRINT, `sizes` as snapshot_layout takes them"""
+    offs, total = snapshot_layout(sizes)
+    head = SNAP_MAGIC + np.array([SNAP_FORMAT, int(version)], "<u4").tobytes() + np.array([int(sid)], "<i8").tobytes()
+    head += np.array([len(SNAP_FINGERPRINT), len(SNAP_SECTIONS)], "<u4").tobytes() + np.array([total], "<u8").tobytes()
+    head += np.array([float(fingerprint[k]) for k in SNAP_FINGERPRINT], "<f8").tobytes()
+    for kind, (o, b) in enumerate(zip(offs, sizes)):
+        head += np.array([kind, 0], "<u4").tobytes() + np.array([o, int(b)], "<u8").tobytes()
+    return head + bytes(offs[0] - len(head))
+
+
+def snapshot_build(sid, version, fingerprint, sections):
+    """a blob on the host from its parts: `sections` {name: bytes-like} over SNAP_SECTIONS (a missing one is empty) -> numpy.uint8.
+    What snapshot_many() writes around the bytes it brings down; here for tools and tests, no device"""
+    raw = lambda x: bytes(x) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x).tobytes()  # noqa: E731
+    data = [raw(sections.get(k, b"")) for k in SNAP_SECTIONS]
+    offs, total = snapshot_layout([len(d) for d in data])
+    blob = np.zeros(total, np.uint8)
+    head = snapshot_header(sid, version, fingerprint, [len(d) for d in data])
+    blob[:len(head)] = np.frombuffer(head, np.uint8)
+    for o, d in zip(offs, data):
+        blob[o:o + len(d)] = np.frombuffer(d, np.uint8)
+    return blob
+
+
+def snapshot_info(blob):
+    """the parsed header of a blob, without touching a device -> dict(format, version, sid, nbytes, fingerprint: {field: value},
+    sections: {name: (offset, bytes)}, row: {field: value} of the `row` section).  ValueError naming the field or the section for
+    anything but a whole blob of this format: a wrong magic or format version, other field or section counts, a length that is
+    not the header's, a table that is not the layout of its own sizes (a section that is not on its 16-byte boundary, that
+    overlaps the next or ends past the blob), a `row` section of another size or whose counts disagree with the `offsets`,
+    `window` or `feats` sections."""
+    b = np.frombuffer(bytes(blob) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8), np.uint8)
+    if b.size < _SNAP_HEAD:
+        raise ValueError(f"snapshot: {b.size} bytes are shorter than the header ({_SNAP_HEAD}): truncated")
+    if b[:8].tobytes() != SNAP_MAGIC:
+        raise ValueError(f"snapshot: magic {b[:8].tobytes()!r} is not {SNAP_MAGIC!r}")
+    fmt, version = (int(x) for x in b[8:16].view("<u4"))
+    if fmt != SNAP_FORMAT:
+        raise ValueError(f"snapshot: format version {fmt} (this package reads {SNAP_FORMAT})")
+    sid = int(b[16:24].view("<i8")[0])
+    n_fp, n_sec = (int(x) for x in b[24:32].view("<u4"))
+    total = int(b[32:40].view("<u8")[0])
+    if n_fp != len(SNAP_FINGERPRINT) or n_sec != len(SNAP_SECTIONS):
+        raise ValueError(f"snapshot: {n_fp} fingerprint fields and {n_sec} sections (this package reads {len(SNAP_FINGERPRINT)} and {len(SNAP_SECTIONS)})")
+    o_tab = _SNAP_HEAD + 8 * n_fp
+    if b.size < o_tab + 24 * n_sec:
+        raise ValueError(f"snapshot: {b.size} bytes end inside the header ({o_tab + 24 * n_sec}): truncated")
+    fp = dict(zip(SNAP_FINGERPRINT, (float(x) for x in b[_SNAP_HEAD:o_tab].view("<f8"))))
+    sections, sizes = {}, []
+    for i, name in enumerate(SNAP_SECTIONS):
+        kind = int(b[o_tab + 24 * i:o_tab + 24 * i + 4].view("<u4")[0])
+        off, nb = (int(x) for x in b[o_tab + 24 * i + 8:o_tab + 24 * i + 24].view("<u8"))
+        if kind != i:
+            raise ValueError(f"snapshot: section {i} is of kind {kind}, not {i} ({name})")
+        sections[name] = (off, nb)
+        sizes.append(nb)
+    offs, want = snapshot_layout(sizes)
+    for name, o in zip(SNAP_SECTIONS, offs):
+        if sections[name][0] != o:
+            raise ValueError(f"snapshot: section {name!r} at offset {sections[name][0]} with {sections[name][1]} bytes: the table is not the layout "
+                             f"of its own sizes (offset {o} expected)")
+    for name in SNAP_SECTIONS:
+        if sum(sections[name]) > b.size:
+            raise ValueError(f"snapshot: section {name!r} ends at byte {sum(sections[name])}, the blob has {b.size}: truncated")
+    if total != want or b.size != total:
+        raise ValueError(f"snapshot: total length {b.size} bytes, the header says {total} and its sections make {want}")
+    if sections["row"][1] != 8 * len(SNAP_ROW):
+        raise ValueError(f"snapshot: section 'row' has {sections['row'][1]} bytes, {8 * len(SNAP_ROW)} expected")
+    row = dict(zip(SNAP_ROW, (int(x) for x in b[sections["row"][0]:sum(sections["row"])].view("<i8"))))
+    for name, nb in (("offsets", row["offsets_itemsize"] * row["offsets_count"]), ("window", 4 * (row["n"] - row["base"]))):
+        if sections[name][1] != nb:
+            raise ValueError(f"snapshot: section {name!r} has {sections[name][1]} bytes, its row counters ask for {nb}")
+    return dict(format=fmt, version=version, sid=sid, nbytes=total, fingerprint=fp, sections=sections, row=row)
+
+
+def snapshot_check_fingerprint(got, want):
+    """restore()'s configuration check: ValueError naming the first field of SNAP_FINGERPRINT in which the blob's fingerprint
+    `got` differs from the server's `want`, with both values"""
+    for k in SNAP_FINGERPRINT:
+        if float(got[k]) != float(want[k]):
+            raise ValueError(f"LiveServer.restore: the blob was taken from a server with {k} = {got[k]!r}, this one has {k} = {float(want[k])!r}")
+
+
+class _SnapStaging:
+    """What snapshot_many() and restore() need beside the rows' state, allocated at the first such call and grown when a call
+    needs more: one device block and a ring of pinned host blocks, each guarded by the event recorded behind its copy as
+    _FrameStaging guards its own.  A call's block is [segment records | 64-byte boundary | blobs, each on a 64-byte boundary]."""
+    RING = 2
+
+    def __init__(self, dev):
+        self.device, self.nbytes, self.dev, self.host, self.events, self.turn = dev, 0, None, [], [], 0
+
+    def take(self, nbytes):
+        """the next pinned block with room for nbytes (uint8 array), once the copy that last used it is done"""
+        if nbytes > self.nbytes:
+            for ev in self.events:
+                if ev is not None:
+                    ev.synchronize()
+            self.nbytes = max(2 * int(nbytes), 1 << 16)
+            self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=self.device)
+            self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+            self.events = [None] * self.RING
+        self.turn = (self.turn + 1) % self.RING
+        if self.events[self.turn] is not None:
+            self.events[self.turn].synchronize()
+        return self.host[self.turn].numpy()
+
+    def upload(self, lo, hi):
+        self.dev[lo:hi].copy_(self.host[self.turn][lo:hi], non_blocking=True)
+        self._mark()
+
+    def download(self, lo, hi):
+        """bytes lo .. hi of the device block into the same place of the pinned block; returns once they are there"""
+        self.host[self.turn][lo:hi].copy_(self.dev[lo:hi], non_blocking=True)
+        self._mark().synchronize()
+
+    def _mark(self):
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[self.turn] = ev
+        return ev
+
+
 def _samples(chunk, rs):
     """a pushed chunk as the flat array that is uploaded: float32, or int16 for a row opened with pcm="s16"; an array whose dtype
     does not match the row's format is refused"""
@@ -527,6 +693,7 @@ class LiveServer:
         self._chunk = z(2048) if loud else None
         self._stage = _Staging(R, R * 2048, self.dev, R if loud else 0)
         self._rs = None                              # ops.LiveResample, from the first open(..., rate= / pcm=) on
+        self._snap = None                            # _SnapStaging, from the first snapshot*() / restore() on
         self._fr = self._fr_stage = None             # the output head: the rows' state (ops.LiveFrames) and its staging blocks
         if self.frames_conf is not None:
             fc = self.frames_conf
@@ -1190,3 +1357,232 @@ class LiveServer:
         self._rows[r] = None
         del self._sids[sid]
         return out
+
+    # ------------------------------------------------------------------ snapshot and restore
+    def _fingerprint(self):
+        """{field: number} over SNAP_FINGERPRINT: everything that sizes or interprets a row's state.  Not the weights, not the
+        statistics."""
+        import zlib
+        m, lc, rc, fc, tc = self.mel, self.loudness_conf, self.resample_conf, self.frames_conf, self.retime_conf
+        fl = (tc or {}).get("filter")
+        fp = dict(tick=self.tick, fs=self.fs, fps=self.fps, mel_n_fft=m.n_fft, mel_hop=m.hop, mel_n_mels=m.n_mels, mel_fs=m.fs, mel_fps=m.fps,
+                  mel_min_clip=m.min_clip, mel_pre_emph=m.pre_emph, mel_flags=m.flags, FC=self.FC, ring_depth=self.D,
+                  ring_width=self.ring.shape[2], H=self.H, ST=self.sty_old.shape[1], PO=self.pose.shape[1], speech_width=self.enc.d.O,
+                  KW=self.D - self.tick, loudness=int(lc is not None), loudness_target=lc["target"] if lc else 0.0,
+                  loudness_ring_blocks=lc["ring_blocks"] if lc else 0, loudness_warmup=lc["warmup"] if lc else 0,
+                  loudness_gain_lo=lc["gain_db"][0] if lc else 0.0, loudness_gain_hi=lc["gain_db"][1] if lc else 0.0,
+                  resample_zero_crossings=rc["zero_crossings"], resample_rolloff=rc["rolloff"], resample_beta=rc["beta"],
+                  frames=int(fc is not None), frames_joints=len(fc["parents"]) if fc else 0, frames_what=fc["mask"] if fc else 0,
+                  frames_order=anim._to_euler_order(fc["order"]) if fc else 0,
+                  frames_seq=zlib.crc32(np.asarray(fc["seq"], "<i4").tobytes()) if fc else 0,
+                  retime=int(tc is not None), retime_max_L=tc["ratio"][0] if tc else 0, retime_max_M=tc["ratio"][1] if tc else 0,
+                  filter=int(fl is not None), filter_zero_crossings=fl["zero_crossings"] if fl else 0, filter_rolloff=fl["rolloff"] if fl else 0.0,
+                  filter_beta=fl["beta"] if fl else 0.0, filter_min_rate_num=tc["min_rate"].numerator if fl else 0,
+                  filter_min_rate_den=tc["min_rate"].denominator if fl else 0, filter_half_max=tc["half_max"] if fl else 0)
+        assert set(fp) == set(SNAP_FINGERPRINT)
+        return {k: float(v) for k, v in fp.items()}
+
+    def _snap_pieces(self, r, n_window, n_pending, rs_on):
+        """where the device side of row r's sections lives -> {section: [(device address, bytes)]}, for a row with n_window
+        live samples and n_pending pending feature rows; `rs_on`: the row converts.  A section's pieces follow one another in
+        the blob, each on a 16-byte boundary."""
+        F4 = 4 * self.feats.shape[2]
+        at = lambda t, i: t.data_ptr() + i * t.stride(0) * 4  # noqa: E731
+        p = dict(window=[(self.window[r].data_ptr(), 4 * n_window)], feats=[(at(self.feats, r), F4 * n_pending)],
+                 ring=[(at(self.ring, r), 4 * self.ring.shape[1] * self.ring.shape[2])],
+                 h=[(self.h[i, r].data_ptr(), 4 * self.H) for i in range(2)],
+                 pose=[(at(self.pose, r), 4 * self.pose.shape[1])], rpos=[(at(self.rpos, r), 12)], rrot=[(at(self.rrot, r), 16)],
+                 gaze=[(at(self.gaze, r), 12 * self.T)], sty_old=[(at(self.sty_old, r), 4 * self.sty_old.shape[1])],
+                 sty_new=[(at(self.sty_new, r), 4 * self.sty_new.shape[1])], loudness=[], resample=[], head=[])
+        rs = self._rs if rs_on else None
+        if rs_on and rs is None:                         # (restore()'s size check ahead of the converter's first use: sizes only)
+            rs = types.SimpleNamespace(state=None, d=ops.ResampleDims(self.rows, 2 * self.resample_conf["zero_crossings"] * audio.RESAMPLE_MAX_DECIMATION))
+        for name, obj, spans in (("loudness", self._loud, ops.live_loudness_spans), ("resample", rs, ops.live_resample_spans),
+                                 ("head", self._fr, ops.live_frames_spans)):
+            if obj is not None:
+                base = 0 if obj.state is None else obj.state.data_ptr()
+                p[name] = [(base + o, b) for o, b in spans(obj, r)]
+        for t in (self.feats, self.ring, self.h, self.pose, self.rpos, self.rrot, self.gaze, self.sty_old, self.sty_new):
+            assert t.is_contiguous()
+        return p
+
+    @staticmethod
+    def _snap_sizes(pieces, host):
+        """bytes per section in SNAP_SECTIONS' order: the host sections as they are, a device section's pieces on 16-byte boundaries"""
+        return [len(host[k]) if k in host else (sum(_a16(b) for _, b in pieces[k][:-1]) + pieces[k][-1][1] if pieces[k] else 0) for k in SNAP_SECTIONS]
+
+    def _snap_stage(self):
+        if self._snap is None:
+            self._snap = _SnapStaging(self.dev)          # (the first snapshot or restore: a server that never does allocates nothing)
+        return self._snap
+
+    def snapshot(self, sid):
+        """snapshot_many([sid])[sid]"""
+        return self.snapshot_many([sid])[sid]
+
+    def snapshot_many(self, sids=None):
+        """-> {sid: blob}: everything that determines the future outputs of each stream in `sids` (None: every open stream), as
+        one numpy.uint8 array per stream that restore() of any server with the same configuration takes -- on this server (a
+        fork), on another GPU, in another process.  The streams go on exactly as before.  A snapshot may be taken between any two
+        calls: right after open(), after a push no step has consumed, in a style fade, while a filtered stream's last frames
+        are held back, after hold(); not after close() (KeyError, before anything is enqueued).
+        Whatever the number of streams: ONE upload (the segment records), ONE launch (zeggs_live_pack gathers a thousand pieces
+        of 64 rows as it gathers the fifteen of one) and ONE download into a pinned block, which the call waits for; the blobs
+        are copies of its slices.  stats["ops_last_snapshot"] counts the three.
+        A blob holds the live part of the row's sample window and its pending feature rows, the layer-0 ring, the GRU state,
+        the last pose and root, gaze and both styles, the row's spans of every state block the server has (running loudness,
+        the rate converter, the output head: include/zeggs_hip_snapshot.h) and the host counters, behind a header with a
+        fingerprint of the configuration (SNAP_FINGERPRINT; snapshot_info() reads it).  It does NOT cover the networks and the
+        statistics: restoring into a server with other weights is the caller's business."""
+        sids = list(self._sids) if sids is None else list(sids)
+        rows = [self._row(sid) for sid in sids]
+        if len(set(sids)) != len(sids):
+            raise ValueError("LiveServer.snapshot_many: a stream is named twice")
+        if not sids:
+            return {}
+        fp, version = self._fingerprint(), ops.lib().zeggs_live_snapshot_version()
+        plans, n_seg, at = [], 0, 0
+        for r, row in rows:
+            rs, rt, off = row.rs, row.rt, row.offsets
+            vals = dict(n=row.n, base=row.base, n_feat=row.n_feat, fbase=row.fbase, n_ring=row.n_ring, kd=row.kd, sent0=int(row.sent0),
+                        k_style=row.k_style, fade=row.fade, rs=int(rs is not None), rs_fi=rs["fi"] if rs else 0, rs_fmt=rs["fmt"] if rs else 0,
+                        rs_n_in=rs["n_in"] if rs else 0, rt=int(rt is not None), rt_L=rt["L"] if rt else 0, rt_M=rt["M"] if rt else 0,
+                        rt_n_in=rt["n_in"] if rt else 0, rt_n_out=rt["n_out"] if rt else 0, rt_half=rt.get("half", -1) if rt else -1,
+                        offsets_itemsize=off.dtype.itemsize if off is not None else 0, offsets_count=off.size if off is not None else 0)
+            host = dict(row=np.array([vals[k] for k in SNAP_ROW], "<i8").tobytes(), offsets=b"" if off is None else np.ascontiguousarray(off).tobytes())
+            pieces = self._snap_pieces(r, row.n - row.base, row.n_feat - row.fbase, rs is not None)
+            sizes = self._snap_sizes(pieces, host)
+            offs, total = snapshot_layout(sizes)
+            plans.append(dict(host=host, pieces=pieces, sizes=sizes, offs=offs, total=total, at=at))
+            n_seg += sum(1 for v in pieces.values() for _, b in v if b)
+            at += (total + 63) // 64 * 64
+        o_blobs = (n_seg * C.sizeof(ops.SnapSeg) + 63) // 64 * 64
+        stg = self._snap_stage()
+        blk = stg.take(o_blobs + at)
+        segs, j = (ops.SnapSeg * n_seg).from_buffer(blk, 0), 0
+        for p in plans:
+            for name, o in zip(SNAP_SECTIONS, p["offs"]):
+                for addr, nb in p["pieces"].get(name, ()):
+                    if nb:
+                        segs[j].src, segs[j].dst_offset, segs[j].bytes = addr, p["at"] + o, nb
+                        j += 1
+                    o += _a16(nb)
+        assert j == n_seg
+        n_ops = 0
+        with torch.no_grad():
+            stg.upload(0, o_blobs)
+            ops.live_pack(segs, n_seg, stg.dev.data_ptr(), stg.dev.data_ptr() + o_blobs, at)
+            stg.download(o_blobs, o_blobs + at)
+            n_ops += 3
+        del segs
+        out = {}
+        for sid, p in zip(sids, plans):
+            mine = blk[o_blobs + p["at"]:o_blobs + p["at"] + p["total"]]
+            head = snapshot_header(sid, version, fp, p["sizes"])
+            mine[:len(head)] = np.frombuffer(head, np.uint8)
+            for name, o, nb in zip(SNAP_SECTIONS, p["offs"], p["sizes"]):
+                if name in p["host"]:
+                    mine[o:o + nb] = np.frombuffer(p["host"][name], np.uint8)
+                    mine[o + nb:_a16(o + nb)] = 0
+                    continue
+                for _, b in p["pieces"][name]:               # what lies between the pieces is not the stream's: zeroes
+                    mine[o + b:o + _a16(b)] = 0
+                    o += _a16(b)
+            out[sid] = np.array(mine)
+        self.stats["ops_last_snapshot"] = n_ops
+        self.stats["snapshot_bytes"] = self.stats.get("snapshot_bytes", 0) + at
+        return out
+
+    def restore(self, blob):
+        """a stream from snapshot() / snapshot_many() on a free row of THIS server -> its new stream id.  The stream goes on as the
+        one the blob was taken from would have: the same frames for the same further input, bit for bit where the stages are
+        (the audio side and the output head; the decoder's sums are what they are between any two servers).  The source is
+        not involved: restoring on the server the blob came from is a fork.
+        Everything is checked on the host before anything is enqueued -- magic and versions, every field of the configuration
+        fingerprint (ValueError naming the first that differs and both values), every section's size against this server's
+        own span reports and tensor shapes, the total length: a blob that is refused leaves the server as it was, no row taken,
+        no launch made.  With no free row: the RuntimeError of open().  Then ONE upload (the blob with its segment records) and
+        ONE launch (zeggs_live_unpack); the row's host counters come from the blob, the converter's and the filter's tables are
+        rebuilt from the recorded rate and ratio by the host functions open() uses (float64 host arithmetic: the same bits;
+        uploaded only where this server has not seen the rate yet, as in open()).  The live samples go to the front of the
+        row's window with `base` kept; a window too small for them grows first.  stats["ops_last_restore"] counts what the call
+        enqueued.  The fingerprint does NOT cover the networks and the statistics: a blob from a server with other weights is
+        taken, and what the stream then does is the caller's business."""
+        info = snapshot_info(blob)
+        version = ops.lib().zeggs_live_snapshot_version()
+        if info["version"] != version:
+            raise ValueError(f"LiveServer.restore: the blob was written by snapshot version {info['version']}, this library is version {version}")
+        snapshot_check_fingerprint(info["fingerprint"], self._fingerprint())
+        w, sec = info["row"], info["sections"]
+        if not (0 <= w["base"] <= w["n"] and 0 <= w["fbase"] <= w["n_ring"] <= w["n_feat"] and w["kd"] >= 1 and w["n_feat"] - w["fbase"] <= self.FC
+                and w["sent0"] in (0, 1) and w["rs"] in (0, 1) and w["rt"] in (0, 1) and w["fade"] >= 0):
+            raise ValueError(f"LiveServer.restore: section 'row': counters {w} are not those of a stream of this server")
+        if w["rt"] != int(self.retime_conf is not None) or (w["rt_half"] >= 0) != bool(self.retime_conf and "filter" in self.retime_conf):
+            raise ValueError("LiveServer.restore: section 'row': its re-timing fields are not those of a stream of this server")
+        free = [r for r in range(self.rows) if self._rows[r] is None]
+        r = free[0] if free else 0                       # (sizes do not depend on the row: a full server still checks them)
+        pieces = self._snap_pieces(r, w["n"] - w["base"], w["n_feat"] - w["fbase"], bool(w["rs"]))
+        J3 = 3 * len(self.frames_conf["parents"]) if self.frames_conf else 0
+        if w["offsets_count"] != J3 or (J3 and w["offsets_itemsize"] not in (4, 8)):
+            raise ValueError(f"LiveServer.restore: section 'offsets' holds {w['offsets_count']} values of {w['offsets_itemsize']} bytes, this server's "
+                             f"skeleton asks for {J3}")
+        host = dict(row=bytes(8 * len(SNAP_ROW)), offsets=bytes(J3 * w["offsets_itemsize"]))
+        for name, nb in zip(SNAP_SECTIONS, self._snap_sizes(pieces, host)):
+            if sec[name][1] != nb:
+                raise ValueError(f"LiveServer.restore: section {name!r} has {sec[name][1]} bytes, this server's row takes {nb}")
+        if not free:
+            raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        # ---- the host side of the row: tables by the functions open() uses (a refused rate or ratio raises before a row is taken)
+        row = _Row(self._next_sid)
+        row.n, row.base, row.n_feat, row.fbase, row.n_ring, row.kd = (w[k] for k in ("n", "base", "n_feat", "fbase", "n_ring", "kd"))
+        row.sent0, row.k_style, row.fade = bool(w["sent0"]), w["k_style"], w["fade"]
+        if w["rs"]:
+            if w["rs_fmt"] not in ops.RS_FORMATS.values():
+                raise ValueError(f"LiveServer.restore: section 'row': sample format {w['rs_fmt']}")
+            if w["rs_fi"] != self.fs:
+                audio.resample_ratio(w["rs_fi"], self.fs)
+            if self._rs is None:
+                self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
+            row.rs = dict(self._rs.table(w["rs_fi"]), fi=w["rs_fi"], fmt=w["rs_fmt"], n_in=w["rs_n_in"])
+        if w["rt"]:
+            row.rt = dict(L=w["rt_L"], M=w["rt_M"], n_in=w["rt_n_in"], n_out=w["rt_n_out"])
+            if w["rt_half"] > 0:
+                t = self._fr.table(w["rt_L"], w["rt_M"])
+                if t["half"] != w["rt_half"]:
+                    raise ValueError(f"LiveServer.restore: section 'row': half {w['rt_half']} at the ratio {w['rt_L']} / {w['rt_M']}, this server's filter has {t['half']}")
+                row.rt.update(half=t["half"], table=t["table"])
+            elif w["rt_half"] == 0:
+                row.rt.update(half=0, table=None)
+        b = np.frombuffer(bytes(blob) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8), np.uint8)
+        if J3:
+            row.offsets = np.array(b[sec["offsets"][0]:sum(sec["offsets"])].view("<f8" if w["offsets_itemsize"] == 8 else "<f4")).reshape(-1, 3)
+        n_ops = 0
+        if w["n"] - w["base"] > self.window[r].numel():   # growth, the one exception, as in push()
+            self.window[r] = torch.zeros(w["n"] - w["base"], device=self.dev)
+            self.stats["window_capacity"][r] = int(self.window[r].numel())
+            n_ops += 1
+        pieces = self._snap_pieces(r, w["n"] - w["base"], w["n_feat"] - w["fbase"], bool(w["rs"]))
+        n_seg = sum(1 for v in pieces.values() for _, nb in v if nb)
+        o_blob = (n_seg * C.sizeof(ops.SnapSeg) + 63) // 64 * 64
+        stg = self._snap_stage()
+        blk = stg.take(o_blob + b.size)
+        segs, j = (ops.SnapSeg * n_seg).from_buffer(blk, 0), 0
+        for name in SNAP_SECTIONS:
+            o = sec[name][0]
+            for addr, nb in pieces.get(name, ()):
+                if nb:
+                    segs[j].src, segs[j].dst_offset, segs[j].bytes = addr, o, nb
+                    j += 1
+                o += _a16(nb)
+        assert j == n_seg
+        blk[o_blob:o_blob + b.size] = b
+        with torch.no_grad():
+            stg.upload(0, o_blob + b.size)
+            ops.live_unpack(segs, n_seg, stg.dev.data_ptr(), stg.dev.data_ptr() + o_blob, b.size)
+            n_ops += 2
+        del segs
+        sid = row.sid
+        self._next_sid += 1
+        self._rows[r], self._sids[sid] = row, r
+        self.stats["ops_last_restore"] = n_ops
+        return sid

@@ -13,7 +13,7 @@ import torch
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
                    DecStats, FramesDims, FramesRow, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
-                   ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SpeechDims, SpeechPtrs,
+                   ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SnapSeg, SnapSpan, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
@@ -1289,6 +1289,46 @@ def live_frames_refiltered(lr, rows, n, rows_dev=None):
     row without the filter), `rows_dev` the device address of a copy of the same records (None: one record, in the kernel
     arguments): ONE launch for all of them"""
     api().zeggs_live_frames_refiltered(lr.d, lr.max_half, rows, _records(RefilterRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
+
+
+SNAP_MAX_SPANS, SNAP_MAX_SEGMENTS = 2, 65535       # ZEGGS_SNAP_MAX_SPANS / ZEGGS_SNAP_MAX_SEGMENTS
+
+
+def _spans(fn, *args):
+    """a span report of include/zeggs_hip_snapshot.h -> [(offset, bytes)] into the family's state block (host only)"""
+    out = (SnapSpan * SNAP_MAX_SPANS)()
+    n = fn(*args, out, SNAP_MAX_SPANS)
+    return [(int(out[i].offset), int(out[i].bytes)) for i in range(n)]
+
+
+def live_loudness_spans(ll, row):
+    """zeggs_live_loudness_spans: where row `row` lives in ll.state -> [(offset, bytes)]"""
+    return _spans(api().zeggs_live_loudness_spans, ll.d, int(row))
+
+
+def live_resample_spans(rs, row):
+    """zeggs_resample_spans: where row `row` lives in rs.state -> [(offset, bytes)]"""
+    return _spans(api().zeggs_resample_spans, rs.d, int(row))
+
+
+def live_frames_spans(lf, row):
+    """zeggs_live_frames_spans / zeggs_live_retime_spans / zeggs_live_refilter_spans, by the head's form: where row `row` lives in
+    lf.state -> [(offset, bytes)] (the skeleton tables in front of the rows are derived, not state: in no span)"""
+    L = api()
+    fn = (L.zeggs_live_refilter_spans if isinstance(lf, LiveRefilter) else L.zeggs_live_retime_spans if isinstance(lf, LiveRetime)
+          else L.zeggs_live_frames_spans)
+    return _spans(fn, lf.d, *lf.extra, int(row))
+
+
+def live_pack(segs, n, segs_dev, blob, blob_bytes):
+    """zeggs_live_pack: segs[:n] a HOST array of SnapSeg (src: a device address; dst_offset, bytes: its place in the blob),
+    segs_dev the device address of a copy of the same records, `blob` the blob's device address: ONE launch gathers them all"""
+    api().zeggs_live_pack(segs, _records(SnapSeg, segs_dev), int(n), blob, int(blob_bytes), _stream())
+
+
+def live_unpack(segs, n, segs_dev, blob, blob_bytes):
+    """zeggs_live_unpack: the records of live_pack with the direction reversed -- `src` is written: ONE launch scatters them all"""
+    api().zeggs_live_unpack(segs, _records(SnapSeg, segs_dev), int(n), blob, int(blob_bytes), _stream())
 
 
 class LiveSpeech:
