@@ -49,6 +49,11 @@
   --leg snapshot: what LiveServer.snapshot_many() of all rows and restore() of one row cost, per rows in {1, 8, 32, 64}: a server with
   every stage on, medians over `--steps` repeats beside the median step() of the same process; the figure to look at is
   snapshot_many at 64 rows as a fraction of the 66.7 ms tick and beside that step() -> profiles/live_snapshot.json.
+  --leg gaze: what the moving gaze costs a step, per rows in {1, 8, 32, 64}: a plain server and one with gaze=True in ONE process,
+  brought to 10 s on the same signals, then fed the same chunks tick by tick, taking turns at going first; on the gaze server
+  every row gets a new root-space target on an arc every tick (set_gaze_many of all rows, timed by itself).  Median and p95 of
+  step() for both, the median of set_gaze_many, what each enqueues per step; the claim to check: the gaze server's median lies
+  within the plain server's own spread of the same run (its p95 minus its median) -> profiles/live_gaze.json.
 
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
@@ -60,6 +65,7 @@ Every case is a child process under its own `timeout`; the first one that fails 
     python tools/live_bench.py --leg retime [--out profiles/live_retime.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg refilter [--out profiles/live_refilter.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg snapshot [--out profiles/live_snapshot.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg gaze [--out profiles/live_gaze.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -430,6 +436,58 @@ def case_retime(rows, steps, age=10):
                 frame_bytes_per_step={k: round((srv[k].stats["frame_bytes"] - bytes0[k]) / len(t[k])) for k in names})
 
 
+def case_gaze(rows, steps, age=10):
+    """step() of a server with the moving gaze against step() of a plain one, and a set_gaze_many of all rows: two servers in ONE
+    process, the same rows' signals up to `age` (1 s push_many calls, drained), then tick by tick, taking turns at going first.
+    On the gaze server every row gets a new target every tick (a tracker's call: root space, an arc, a fade of 12), timed by
+    itself in front of the step"""
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    srv = {"plain": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK),
+           "gaze": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, gaze=True)}
+    sids = {k: [srv[k].open(first, st) for st in styles] for k in srv}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    names = ["plain", "gaze"]
+    t, t_set, ops_seen, i = {k: [] for k in names}, [], {k: set() for k in names}, 0
+    while len(t["plain"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]
+        for k in names[i % 2:] + names[:i % 2]:
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            if k == "gaze":
+                req = {sid: dict(target=[0.5 * ((i + r) % 5) - 1.0, 1.6, 2.0], fade=12, space="root", path="arc") for r, sid in enumerate(sids[k])}
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                srv[k].set_gaze_many(req)
+                torch.cuda.synchronize()
+                t_set.append(time.perf_counter() - t0)
+            while True:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k].append(dt)
+                ops_seen[k].add(srv[k].stats["launches_per_step"])
+        pos = nxt
+    assert len(ops_seen["plain"]) == len(ops_seen["gaze"]) == 1 and max(ops_seen["gaze"]) <= max(ops_seen["plain"]), ops_seen
+    return dict(kind="gaze", rows=rows, age_s=age, tick=TICK, step={k: _summary(t[k]) for k in names}, set_gaze_many=_summary(t_set),
+                launches_per_step={k: sorted(ops_seen[k]) for k in names}, ops_per_set_gaze_many=srv["gaze"].stats["ops_last_set_gaze"])
+
+
 REFILTER_LEGS = (("30", 30, False), ("120", 120, False), ("30 filtered", 30, True), ("120 filtered", 120, True))
 
 
@@ -577,10 +635,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot", "gaze"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64 or snapshot:64")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64, snapshot:64 or gaze:64")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -593,7 +651,8 @@ def main():
                case_frames(int(rest[0]), int(rest[1]), a.steps) if kind == "frames" else
                case_retime(int(rest[0]), a.steps) if kind == "retime" else
                case_refilter(int(rest[0]), a.steps) if kind == "refilter" else
-               case_snapshot(int(rest[0]), a.steps) if kind == "snapshot" else case_baseline(int(rest[0]), a.steps))
+               case_snapshot(int(rest[0]), a.steps) if kind == "snapshot" else
+               case_gaze(int(rest[0]), a.steps) if kind == "gaze" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -626,6 +685,10 @@ def main():
         cases = [f"snapshot:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_snapshot.json")
+    if a.leg == "gaze":
+        cases = [f"gaze:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_gaze.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -735,6 +798,24 @@ def main():
                                            blob_bytes_all_rows=r["blob_bytes_all_rows"]) for r in results}
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    tick_ms=round(budget, 2), repeats_per_case=a.steps, snapshot_of_all_rows_and_restore_of_one_beside_step=table, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "gaze":
+        table = {}
+        for r in results:
+            plain, gz = r["step"]["plain"], r["step"]["gaze"]
+            spread = round(plain["p95_ms"] - plain["median_ms"], 4)
+            table[f"{r['rows']} rows"] = dict(step_plain_median_ms=plain["median_ms"], step_plain_p95_ms=plain["p95_ms"],
+                                              step_gaze_median_ms=gz["median_ms"], step_gaze_p95_ms=gz["p95_ms"],
+                                              gaze_minus_plain_ms=round(gz["median_ms"] - plain["median_ms"], 4), plain_spread_ms=spread,
+                                              gaze_median_within_the_plain_spread=abs(gz["median_ms"] - plain["median_ms"]) <= spread,
+                                              gaze_median_below_the_plain_median=gz["median_ms"] < plain["median_ms"],
+                                              set_gaze_many_all_rows_median_ms=r["set_gaze_many"]["median_ms"],
+                                              launches_per_step=r["launches_per_step"])
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, step_without_and_with_the_moving_gaze=table, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

@@ -16,7 +16,8 @@ include/zeggs_hip_resample.h, RS_STRUCTS / RS_PROTOTYPES (tests/test_live_resamp
 include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_cpu.py), the sixth, include/zeggs_hip_retime.h,
 RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py), the seventh, include/zeggs_hip_refilter.h, RF_STRUCTS / RF_PROTOTYPES
 (tests/test_live_refilter_cpu.py), the eighth, include/zeggs_hip_snapshot.h, SNAP_STRUCTS / SNAP_PROTOTYPES
-(tests/test_live_snapshot_cpu.py): same loader.  torch is imported when a tensor is first converted, not
+(tests/test_live_snapshot_cpu.py), the ninth, include/zeggs_hip_gaze.h, GZ_STRUCTS / GZ_PROTOTYPES (tests/test_live_gaze_cpu.py):
+same loader.  torch is imported when a tensor is first converted, not
 when this module is.
 """
 import ctypes as C
@@ -337,6 +338,24 @@ SNAP_PROTOTYPES = {
 }
 
 
+# ----------------------------------------------------------------------------- the ninth header (include/zeggs_hip_gaze.h)
+# A gaze target per live row that can move while speech goes on (tests/test_live_gaze_cpu.py compares these tables with the header).
+GazeDims = _struct("GazeDims", [(C.c_int, "rows ST")])
+GazeSet = _struct("GazeSet", [(C.c_float * 3, "target pivot"), (C.c_long, "k fade"), (C.c_int, "row space path ease has_pivot")])
+GazeCond = _struct("GazeCond", [(C.c_long, "k0 k_style fade_style"), (C.c_int, "row out_row n")])
+GZ_STRUCTS = {"ZeggsGazeDims": GazeDims, "ZeggsGazeSet": GazeSet, "ZeggsGazeCond": GazeCond}
+GZ_PROTOTYPES = {
+    "zeggs_live_gaze_version": "int:",
+    "zeggs_live_gaze_state_bytes": "size_t: ZeggsGazeDims*",
+    "zeggs_live_gaze_reset": "status: ZeggsGazeDims* any* size_t int f32* stream",
+    # recs_host: a HOST array of ZeggsGazeSet; recs_dev: the same records on the device (an address cast to the pointer type), None for one
+    "zeggs_live_gaze_set": "status: ZeggsGazeDims* ZeggsGazeSet* ZeggsGazeSet* int f32* long f32* long any* size_t stream",
+    "zeggs_live_condition": "status: ZeggsGazeDims* ZeggsGazeCond* ZeggsGazeCond* int any* size_t f32* f32* f32* f32* int long stream",
+    "zeggs_live_gaze_read": "status: ZeggsGazeDims* any* size_t int long host* stream",
+    "zeggs_live_gaze_spans": "mask: ZeggsGazeDims* int ZeggsSnapSpan* int",
+}
+
+
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
     """A device-pointer parameter: takes a tensor (on a GPU, contiguous, one of `dtypes`), None, a c_void_p or an address."""
@@ -375,14 +394,14 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS, **GZ_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -420,7 +439,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -432,7 +451,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

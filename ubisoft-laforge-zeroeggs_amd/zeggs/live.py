@@ -40,13 +40,19 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
     (include/zeggs_hip_snapshot.h), the host counters -- and restore(blob) puts it into a free row of any server with the same
     configuration: a drain for a restart, a move to another GPU, a fork.  ONE upload, ONE launch (zeggs_live_pack) and ONE
     download whatever the number of rows; restore() is one upload and one launch (zeggs_live_unpack) after every field was
-    checked on the host; snapshot_info(blob) reads a blob's header without a device.
+    checked on the host; snapshot_info(blob) reads a blob's header without a device;
+  * LiveServer(gaze=True) lets the point a character looks at move while speech goes on: set_gaze(sid, target, fade, space, path)
+    / set_gaze_many({sid: ...}) put a schedule of 64 bytes per row on the device (include/zeggs_hip_gaze.h) -- from where the
+    gaze stands to the target over `fade` frames, on a line or on an arc about a pivot, a root-space target resolved on the
+    device with the row's root state at the call -- and ONE launch per decoder call (zeggs_live_condition) writes the gaze rows
+    AND the style rows of the step's frames, in place of the style fade's weight upload and torch.lerp; gaze(sid) reads it.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
 """
 import ctypes as C
 import types
+import weakref
 
 import numpy as np
 import torch
@@ -65,6 +71,114 @@ def style_weight(f, k, fade):
     """weight of the NEW style at frame f after set_style(..., fade) returned k: 0 before k, then `fade` intermediate frames on a
     straight line, 1 from frame k + fade on (fade = 0: a step at k)"""
     return float(min(max((f - k + 1) / (fade + 1.0), 0.0), 1.0))
+
+
+GAZE_DEFAULTS = dict(ease="linear")
+GAZE_REQUEST = dict(target=None, fade=0, space="world", path="line", pivot=None, ease=None)
+
+
+def gaze_options(gaze):
+    """LiveServer's `gaze` argument -> None (off) or dict(ease: the ease of a set_gaze that names none): True is the defaults, a
+    dict overrides them.  ValueError for anything else and for an ease other than "linear" / "smooth"."""
+    if gaze is None or gaze is False:
+        return None
+    if gaze is True:
+        gaze = {}
+    if not isinstance(gaze, dict) or set(gaze) - set(GAZE_DEFAULTS):
+        raise ValueError(f"LiveServer: gaze is None, True or a dict with keys {sorted(GAZE_DEFAULTS)}")
+    o = dict(GAZE_DEFAULTS, **gaze)
+    if o["ease"] not in ops.GAZE_EASES:
+        raise ValueError(f"LiveServer: gaze ease {o['ease']!r} (one of {sorted(ops.GAZE_EASES)})")
+    return dict(ease=o["ease"])
+
+
+def _point(x, what):
+    try:
+        p = np.asarray(x, np.float64).reshape(-1)
+    except (TypeError, ValueError):
+        p = np.zeros(0)
+    if p.size != 3 or not np.isfinite(p).all() or np.abs(p).max() > np.finfo(np.float32).max:      # (the records carry float32)
+        raise ValueError(f"set_gaze: {what} is three finite numbers, not {x!r}")
+    return p
+
+
+def gaze_request(req, default_ease="linear"):
+    """one entry of set_gaze_many -- a target [3] or dict(target=, fade=, space=, path=, pivot=, ease=) -> the checked request,
+    dict(target: float64 [3], fade: int, space, path, pivot: float64 [3] or None, ease).  ValueError for a negative fade, a target
+    or pivot that is not three finite numbers, an unknown space, path or ease, and an arc in world space without a pivot."""
+    if not isinstance(req, dict):
+        req = dict(target=req)
+    if set(req) - set(GAZE_REQUEST) or "target" not in req:
+        raise ValueError(f"set_gaze: a target or a dict with `target` and keys of {sorted(GAZE_REQUEST)}")
+    o = dict(GAZE_REQUEST, **req)
+    fade = o["fade"]
+    if isinstance(fade, bool) or not isinstance(fade, (int, np.integer)) or fade < 0:
+        raise ValueError(f"set_gaze: fade {fade!r} (an integer >= 0)")
+    ease = default_ease if o["ease"] is None else o["ease"]
+    for name, value, table in (("space", o["space"], ops.GAZE_SPACES), ("path", o["path"], ops.GAZE_PATHS), ("ease", ease, ops.GAZE_EASES)):
+        if not isinstance(value, str) or value not in table:
+            raise ValueError(f"set_gaze: {name} {value!r} (one of {sorted(table)})")
+    target = _point(o["target"], "the target")
+    pivot = None if o["pivot"] is None else _point(o["pivot"], "the pivot")
+    if o["path"] == "arc" and o["space"] == "world" and pivot is None:
+        raise ValueError("set_gaze: path='arc' in space='world' needs a pivot (space='root' turns about the root by default)")
+    return dict(target=target, fade=int(fade), space=o["space"], path=o["path"], pivot=pivot, ease=ease)
+
+
+def _quat_rotate(q, v):
+    """csrc/quat_math.h's quat_mul_vec in float64: t = 2 (q_v x v); v + w t + q_v x t"""
+    t = 2.0 * np.cross(q[1:], v)
+    return v + q[0] * t + np.cross(q[1:], t)
+
+
+def gaze_to_model(target, ref_pos, ref_rot, start_position, start_rotation):
+    """a point of the client's placed space -- the space open(start_position=, start_rotation=) puts a stream's frames in -- as a
+    point of the model's world, what set_gaze(space="world") takes: the inverse of open()'s re-basing
+    x' = start_rot ref_rot^-1 (x - ref_pos) + start_pos, i.e. x = ref_rot start_rot^-1 (x' - start_pos) + ref_pos, with ref_pos /
+    ref_rot the root of the stream's frame 0 (quaternions w first, taken as they are: unit length is the caller's).  float64, no
+    state, no device."""
+    x, rp, sp = (np.asarray(a, np.float64).reshape(3) for a in (target, ref_pos, start_position))
+    rr, sr = (np.asarray(a, np.float64).reshape(4) for a in (ref_rot, start_rotation))
+    inv = lambda q: q * np.array([1.0, -1.0, -1.0, -1.0])  # noqa: E731
+    return _quat_rotate(rr, _quat_rotate(inv(sr), x - sp)) + rp
+
+
+class _GazeRows(torch.Tensor):
+    """LiveServer.gaze: the rows' gaze tensor [R, T, 3] that step() hands the decoder -- and, called with a stream id, the
+    monitoring call gaze(sid) (LiveServer._gaze_read).  The tensor has carried the name since live serving began (tests and
+    tools index it); the call takes the name the other stages' calls have (loudness(sid)).  Tensor operations see a plain
+    tensor: no __torch_function__ dispatch, the same storage, nothing more enqueued."""
+    __torch_function__ = torch._C._disabled_torch_function_impl
+
+    def __call__(self, sid):
+        return self._server()._gaze_read(sid)
+
+
+class _RecStaging:
+    """The records of a gaze launch with more than one record, uploaded as ONE block: a ring of pinned host blocks, each guarded
+    by the event recorded behind its copy, and one device block (calls on a stream are ordered), as _Staging keeps its own."""
+    RING = 4
+
+    def __init__(self, record, rows, dev):
+        self.nbytes = rows * C.sizeof(record)
+        self.host = [torch.zeros(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
+        self.recs = [(record * rows).from_buffer(h.numpy()) for h in self.host]
+        self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self.events, self.turn, self.size = [None] * self.RING, 0, C.sizeof(record)
+
+    def take(self):
+        self.turn = (self.turn + 1) % self.RING
+        if self.events[self.turn] is not None:
+            self.events[self.turn].synchronize()
+        return self.recs[self.turn]
+
+    def upload(self, n):
+        nb = n * self.size
+        self.dev[:nb].copy_(self.host[self.turn][:nb], non_blocking=True)
+        ev = torch.cuda.Event()
+        ev.record()
+        self.events[self.turn] = ev
+        return self.dev.data_ptr()
 
 
 def plan_step(rows, tick, depth, lookahead=LOOKAHEAD):
@@ -628,12 +742,20 @@ class LiveServer:
     rest, so that the stream ends with exactly the frames an unfiltered one has.  `min_rate`: the lowest rate a filtered stream
     may ask for; it sizes the rows' history, 2 ceil(zero_crossings fps / min_rate) raw frames a row; at least fps / 4, default
     the lowest rate that keeps 16 frames to either side.  Rows opened with filtered=False (and rows at the server's rate)
-    run the unfiltered rules in the same launch, the same bits as without `filter`."""
+    run the unfiltered rules in the same launch, the same bits as without `filter`.
+
+    `gaze`: None, True or dict(ease="linear" | "smooth") (gaze_options) -- every row keeps a gaze schedule on the
+    device and set_gaze() / set_gaze_many() / gaze() work; step() and close() take the per-frame gaze rows and the style rows
+    from ONE launch (zeggs_live_condition) in place of _style()'s upload and torch.lerp, so launches_per_step does not grow.
+    `ease`: the ease of a set_gaze() that names none.  With None the three calls raise ValueError naming this option, and the
+    server allocates and enqueues what it always did.  (The attribute `gaze` is the rows' gaze tensor [rows, tick + 1, 3] it
+    has always been AND the call gaze(sid): _GazeRows.)"""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None, gaze=None):
         g = audio_conf
         loud = loudness_options(loudness)
+        self.gaze_conf = gaze_options(gaze)
         self.resample_conf = audio.resample_options(resample)
         self.frames_conf = frames_options(frames)
         self.retime_conf = retime_options(retime, self.frames_conf, fps)
@@ -678,7 +800,8 @@ class LiveServer:
         self.h = z(2, R, self.H)                     # GRU state after each row's last decoded frame
         self.pose, self.rpos, self.rrot = z(R, PO), z(R, 3), z(R, 4)       # each row's last decoded frame
         self.rrot[:, 0] = 1.0
-        self.gaze = z(R, self.T, 3)
+        self.gaze = z(R, self.T, 3).as_subclass(_GazeRows)          # (also the call gaze(sid): _GazeRows)
+        self.gaze._server = weakref.ref(self)
         self.sty_old, self.sty_new = z(R, ST), z(R, ST)             # style(f) = lerp(old, new, style_weight(f, k_style, fade))
         self.mel_ws = ops.mel_range_workspace(self.mel, self.FC + 2, self.dev)
         # push_many(): the window's alternate buffer (a compaction copies into it and the two swap), scratch for kept feature
@@ -694,7 +817,15 @@ class LiveServer:
         self._stage = _Staging(R, R * 2048, self.dev, R if loud else 0)
         self._rs = None                              # ops.LiveResample, from the first open(..., rate= / pcm=) on
         self._snap = None                            # _SnapStaging, from the first snapshot*() / restore() on
-        self._fr = self._fr_stage = None             # the output head: the rows' state (ops.LiveFrames) and its staging blocks
+        # a moving gaze: the rows' schedules (ops.LiveGaze), the style rows the condition launch writes beside self.gaze, and
+        # the staging blocks of the records of a set_gaze_many() and of a step with more than one row
+        self._gz = self._gz_style = self._gz_set = self._gz_cond = None
+        if self.gaze_conf is not None:
+            self._gz = ops.LiveGaze(R, ST, self.dev)
+            self._gz_style = z(R, self.T, ST)
+            self._gz_set = _RecStaging(ops.GazeSet, R, self.dev)
+            self._gz_cond = _RecStaging(ops.GazeCond, R, self.dev)
+        self._fr = self._fr_stage = None            # the output head: the rows' state (ops.LiveFrames) and its staging blocks
         if self.frames_conf is not None:
             fc = self.frames_conf
             if 6 + 15 * len(fc["parents"]) != PO:
@@ -722,6 +853,8 @@ class LiveServer:
         self._ops = 0
         self.stats = dict(uploaded_samples=0, window_capacity=[int(window_capacity)] * R, ring_bytes=self.ring.numel() * 4,
                           launches_per_step=0, steps=0, ops_last_push_many=0, uploaded_bytes=0, resampled_rows=0)
+        if self._gz is not None:
+            self.stats["ops_last_set_gaze"] = 0
         if self._fr is not None:
             self.stats["frame_bytes"] = 0            # bytes the output head has downloaded so far
 
@@ -828,6 +961,8 @@ class LiveServer:
             self.h[:, r:r + 1] = ops.decoder_state_init(self.bd, pose0, f32(root_pos), f32(root_rot), gaze0, style0)
         self.pose[r], self.rpos[r], self.rrot[r] = pose0[0], f32(root_pos)[0], f32(root_rot)[0]
         self.gaze[r] = gaze0
+        if self._gz is not None:                         # the row's schedule: it looks at the first pose's gaze until a set_gaze
+            ops.live_gaze_reset(self._gz, r, gaze0.reshape(-1))
         self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
         row = _Row(sid)
         if rs is not None:
@@ -1202,6 +1337,73 @@ class LiveServer:
         self._ops += 2
         return torch.lerp(self.sty_old[:, None], self.sty_new[:, None], torch.as_tensor(wgt, device=self.dev)).contiguous()
 
+    # ------------------------------------------------------------------ gaze
+    def _gaze_on(self, what):
+        if self._gz is None:
+            raise ValueError(f"LiveServer.{what}: the moving gaze is off (LiveServer(gaze=True))")
+
+    def set_gaze(self, sid, target, fade=0, space="world", path="line", pivot=None, ease=None):
+        """a new gaze target for stream `sid` from frame k on, k = the first frame not yet decoded (returned): frame f looks at
+        P(w(f)), w = style_weight(f, k, fade) -- with ease="smooth" w^2 (3 - 2 w) -- from P(0), where the row's gaze stands at
+        frame k - 1 (an unfinished fade goes on from where it is), to P(1) = `target`.
+        `space`: "world" -- target and pivot are points of the model's world, the space of "rpos" (gaze_to_model() brings a point
+        of a placed character's space there); "root" -- they are given in the character's root frame and resolved ON THE DEVICE,
+        once, with the row's root state after frame k - 1: world = rpos + rrot (x) p.  The call does not follow the root
+        afterwards: a client that wants the gaze re-centred on a drifting character calls again.
+        `path`: "line" -- P(w) = (1 - w) P(0) + w P(1); "arc" -- the direction turns about `pivot` on the great circle while the
+        distance goes on a line, the line where a direction is undefined; the pivot defaults to the root position in
+        root space and is required in world space.  `ease` None: the server's (LiveServer(gaze=dict(ease=...))).
+        ValueError before anything is enqueued for a negative fade, a target or pivot that is not three finite numbers, an
+        unknown space, path or ease; KeyError for a stream that is not open.  ONE launch, the record in its arguments."""
+        self._gaze_on("set_gaze")
+        return self.set_gaze_many({sid: dict(target=target, fade=fade, space=space, path=path, pivot=pivot, ease=ease)})[sid]
+
+    def set_gaze_many(self, requests):
+        """set_gaze() for many streams at once: requests = {sid: target | dict(target=, fade=, space=, path=, pivot=, ease=)} ->
+        {sid: k}.  Whatever the number of streams: ONE upload of the records and ONE launch (zeggs_live_gaze_set; a single
+        record travels in the kernel arguments, without the upload) -- the call a tracker makes every tick.  Every request is
+        checked before anything is enqueued; stats["ops_last_set_gaze"] counts what the call enqueued."""
+        self._gaze_on("set_gaze_many")
+        rows = [self._row(sid) for sid in requests]
+        reqs = [gaze_request(q, self.gaze_conf["ease"]) for q in requests.values()]
+        self.stats["ops_last_set_gaze"] = 0
+        if not reqs:
+            return {}
+        n = len(reqs)
+        recs = (ops.GazeSet * 1)() if n == 1 else self._gz_set.take()
+        for q, (r, row), o in zip(recs, rows, reqs):
+            q.target[:] = [float(v) for v in o["target"]]
+            q.pivot[:] = [0.0] * 3 if o["pivot"] is None else [float(v) for v in o["pivot"]]
+            q.k, q.fade, q.row, q.has_pivot = row.kd, o["fade"], r, int(o["pivot"] is not None)
+            q.space, q.path, q.ease = ops.GAZE_SPACES[o["space"]], ops.GAZE_PATHS[o["path"]], ops.GAZE_EASES[o["ease"]]
+        with torch.no_grad():
+            dev = None if n == 1 else self._gz_set.upload(n)
+            ops.live_gaze_set(self._gz, recs, n, self.rpos, self.rrot, dev)
+        self.stats["ops_last_set_gaze"] = 1 if n == 1 else 2
+        return {sid: row.kd for sid, (_, row) in zip(requests, rows)}
+
+    def _gaze_read(self, sid):
+        """gaze(sid) (the attribute `gaze` is the rows' tensor and this call: _GazeRows) -> dict(target [3]: what frame kd, the
+        first frame not yet decoded, will look at; k, fade, start [3], end [3], path, ease: the row's schedule, float32 points of
+        the model's world).  One small read-back that waits for the stream: monitoring, not for the tick path."""
+        self._gaze_on("gaze")
+        r, row = self._row(sid)
+        got = ops.live_gaze_read(self._gz, r, row.kd)
+        return {k: got[k] for k in ("target", "k", "fade", "start", "end", "path", "ease")}
+
+    def _condition(self, jobs, gaze_out, style_out):
+        """the conditioning rows of one decoder call on a gaze server: jobs = [(row, out_row, first frame, frames)] -> the gaze
+        rows [., n, 3] and the style rows [., n, ST] of those frames in slice out_row of the two tensors, by ONE launch
+        (zeggs_live_condition) -- in place of _style()'s weight upload and torch.lerp.  Several records are uploaded first."""
+        n = len(jobs)
+        recs = (ops.GazeCond * 1)() if n == 1 else self._gz_cond.take()
+        for q, (r, o, k0, cnt) in zip(recs, jobs):
+            row = self._rows[r]
+            q.row, q.out_row, q.k0, q.n, q.k_style, q.fade_style = r, o, k0, cnt, row.k_style, row.fade
+        dev = None if n == 1 else self._gz_cond.upload(n)
+        ops.live_condition(self._gz, recs, n, self.sty_old, self.sty_new, gaze_out, style_out, dev)
+        self._ops += 1 if n == 1 else 2
+
     # ------------------------------------------------------------------ decode
     def _encode(self, jobs, out_ld):
         """one zeggs_speech_encoder_live launch; jobs[r] = None or (enc_k0, n_out, n_new, last) -> speech [R, out_ld, O]"""
@@ -1221,12 +1423,15 @@ class LiveServer:
                 self._rows[r].n_ring += jobs[r][2]
         return speech
 
-    def _decode_one(self, r, speech, style, n):
+    def _decode_one(self, r, speech, style, n, gaze=None):
         """frames kd .. kd + n - 1 of row r alone on the B = 1 entry point (speech / style [1, n + 1, .], index 0 = frame kd - 1);
-        the give-up word is looked at before the state is committed, a chunk that gave up is redone on the stage launches"""
+        the give-up word is looked at before the state is committed, a chunk that gave up is redone on the stage launches.
+        `gaze` [1, n + 1, 3]: the per-frame rows of a gaze server (None: the row's fixed point in every frame)"""
         st = self.st
+        if gaze is None:
+            gaze = self.gaze[r:r + 1, :1].expand(1, n + 1, 3).contiguous()
         args = (self.decoder, self.pose[r:r + 1], self.rpos[r:r + 1], self.rrot[r:r + 1],
-                self.gaze[r:r + 1, :1].expand(1, n + 1, 3).contiguous(), speech, style, st["anim_input_mean"], st["anim_input_std"],
+                gaze, speech, style, st["anim_input_mean"], st["anim_input_std"],
                 st["anim_output_mean"], st["anim_output_std"], self.dt)
         h_in = self.h[:, r:r + 1].contiguous()
         pose, rpos, rrot, h = ops.decoder_chunk(*args, h_in=h_in, status=self.status)
@@ -1272,12 +1477,17 @@ class LiveServer:
         tick, T = self.tick, self.T
         with torch.no_grad():
             speech = self._encode([None if p is None else (p["enc_k0"], p["n_out"], p["n_new"], -1) for p in plan], T)
-            style = self._style([None if p is None else range(p["enc_k0"], p["k1"]) for p in plan])
+            gaze = None
+            if self._gz is None:
+                style = self._style([None if p is None else range(p["enc_k0"], p["k1"]) for p in plan])
+            else:                                    # gaze and style rows of the step's frames from ONE launch
+                gaze, style = self.gaze, self._gz_style
+                self._condition([(r, r, plan[r]["enc_k0"], T) for r in live], gaze, style)
             out = {}
             heads = {r: self._head(r) for r in live}
             if self.rows == 1:
                 row = self._rows[0]
-                pose, rpos, rrot = self._decode_one(0, speech, style, tick)
+                pose, rpos, rrot = self._decode_one(0, speech, style, tick, gaze)
                 out[row.sid] = self._emit(heads[0], pose, rpos, rrot)
                 row.kd += tick
             else:
@@ -1341,10 +1551,16 @@ class LiveServer:
                 jobs = [None] * self.rows
                 jobs[r] = (row.kd - 1, n + 1, top - row.n_ring, n_total - 1 if final else -1)
                 speech = self._encode(jobs, self.tail + 1)[r:r + 1, :n + 1].contiguous()
-                frames = [None] * self.rows
-                frames[r] = range(row.kd - 1, row.kd + n)
-                style = self._style(frames)[r:r + 1].contiguous()
-                pose, rpos, rrot = self._decode_one(r, speech, style, n)
+                gaze = None
+                if self._gz is None:
+                    frames = [None] * self.rows
+                    frames[r] = range(row.kd - 1, row.kd + n)
+                    style = self._style(frames)[r:r + 1].contiguous()
+                else:                                    # (up to tick + LOOKAHEAD + 1 frames: tensors of the call's own length)
+                    gaze = torch.empty(1, n + 1, 3, device=self.dev)
+                    style = torch.empty(1, n + 1, self.sty_old.shape[1], device=self.dev)
+                    self._condition([(r, 0, row.kd - 1, n + 1)], gaze, style)
+                pose, rpos, rrot = self._decode_one(r, speech, style, n, gaze)
                 outs.append((pose[1:], rpos[1:], rrot[1:]))
                 row.kd += n
             out = {k: torch.cat([o[i] for o in outs]).contiguous() for i, k in enumerate(("pose", "rpos", "rrot"))} if outs else {}
@@ -1394,8 +1610,10 @@ class LiveServer:
                  pose=[(at(self.pose, r), 4 * self.pose.shape[1])], rpos=[(at(self.rpos, r), 12)], rrot=[(at(self.rrot, r), 16)],
                  gaze=[(at(self.gaze, r), 12 * self.T)], sty_old=[(at(self.sty_old, r), 4 * self.sty_old.shape[1])],
                  sty_new=[(at(self.sty_new, r), 4 * self.sty_new.shape[1])], loudness=[], resample=[], head=[])
+        if self._gz is not None:                         # a gaze server: the row's schedule rides behind the gaze rows
+            p["gaze"] += [(self._gz.state.data_ptr() + o, b) for o, b in ops.live_gaze_spans(self._gz, r)]
         rs = self._rs if rs_on else None
-        if rs_on and rs is None:                         # (restore()'s size check ahead of the converter's first use: sizes only)
+        if rs_on and rs is None:                        # (restore()'s size check ahead of the converter's first use: sizes only)
             rs = types.SimpleNamespace(state=None, d=ops.ResampleDims(self.rows, 2 * self.resample_conf["zero_crossings"] * audio.RESAMPLE_MAX_DECIMATION))
         for name, obj, spans in (("loudness", self._loud, ops.live_loudness_spans), ("resample", rs, ops.live_resample_spans),
                                  ("head", self._fr, ops.live_frames_spans)):

@@ -12,7 +12,7 @@ import torch
 
 from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
-                   DecStats, FramesDims, FramesRow, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
+                   DecStats, FramesDims, FramesRow, GazeCond, GazeDims, GazeSet, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
                    ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SnapSeg, SnapSpan, SpeechDims, SpeechPtrs,
                    StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
 
@@ -1329,6 +1329,57 @@ def live_pack(segs, n, segs_dev, blob, blob_bytes):
 def live_unpack(segs, n, segs_dev, blob, blob_bytes):
     """zeggs_live_unpack: the records of live_pack with the direction reversed -- `src` is written: ONE launch scatters them all"""
     api().zeggs_live_unpack(segs, _records(SnapSeg, segs_dev), int(n), blob, int(blob_bytes), _stream())
+
+
+GAZE_SPACES = {"world": 0, "root": 1}              # ZEGGS_GAZE_WORLD / ZEGGS_GAZE_ROOT
+GAZE_PATHS = {"line": 0, "arc": 1}                 # ZEGGS_GAZE_LINE / ZEGGS_GAZE_ARC
+GAZE_EASES = {"linear": 0, "smooth": 1}            # ZEGGS_GAZE_LINEAR / ZEGGS_GAZE_SMOOTH
+
+
+class LiveGaze:
+    """The gaze schedules of `rows` live rows (include/zeggs_hip_gaze.h): the dims record -- `ST` floats per style row, which the
+    condition launch writes beside the gaze rows -- and the state block, 64 bytes a row (zeroes: a row is reset when it opens)."""
+
+    def __init__(self, rows, ST, device):
+        self.d = GazeDims(int(rows), int(ST))
+        nbytes = api().zeggs_live_gaze_state_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LiveGaze: {api().zeggs_last_error().decode()}")
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+
+
+def live_gaze_reset(lg, row, gaze0):
+    """zeggs_live_gaze_reset: the row looks at gaze0 (a float32 tensor of 3 on the device) from now on"""
+    api().zeggs_live_gaze_reset(lg.d, lg.state, lg.state.numel(), int(row), gaze0, _stream())
+
+
+def live_gaze_set(lg, recs, n, rpos, rrot, recs_dev=None):
+    """zeggs_live_gaze_set: recs[:n] a HOST array of GazeSet, `recs_dev` the device address of a copy of the same records (None: one
+    record, in the kernel arguments); rpos [rows, 3] / rrot [rows, 4]: the rows' root state on the device: ONE launch"""
+    api().zeggs_live_gaze_set(lg.d, recs, _records(GazeSet, recs_dev), int(n), rpos, rpos.stride(0), rrot, rrot.stride(0), lg.state,
+                              lg.state.numel(), _stream())
+
+
+def live_condition(lg, recs, n, sty_old, sty_new, gaze_out, style_out, recs_dev=None):
+    """zeggs_live_condition: recs[:n] a HOST array of GazeCond (`recs_dev` as above); gaze_out [B, T, 3] and style_out [B, T, ST]
+    take, in slice out_row, the gaze and style rows of the record's frames: ONE launch for all of them"""
+    api().zeggs_live_condition(lg.d, recs, _records(GazeCond, recs_dev), int(n), lg.state, lg.state.numel(), sty_old, sty_new, gaze_out,
+                               style_out, int(gaze_out.shape[0]), int(gaze_out.shape[1]), _stream())
+
+
+def live_gaze_read(lg, row, frame):
+    """zeggs_live_gaze_read (waits for the stream) -> dict(target: what `frame` looks at, k, fade, start, end, pivot, path, ease)"""
+    out = (C.c_double * 16)()
+    api().zeggs_live_gaze_read(lg.d, lg.state, lg.state.numel(), int(row), int(frame), C.addressof(out), _stream())
+    v3 = lambda i: np.array(out[i:i + 3], np.float64).astype(np.float32)  # noqa: E731
+    name = lambda table, v: [k for k, c in table.items() if c == int(v)][0]  # noqa: E731
+    return dict(target=v3(0), k=int(out[3]), fade=int(out[4]), start=v3(5), end=v3(8), pivot=v3(11), path=name(GAZE_PATHS, out[14]),
+                ease=name(GAZE_EASES, out[15]))
+
+
+def live_gaze_spans(lg, row):
+    """zeggs_live_gaze_spans: where row `row` lives in lg.state -> [(offset, bytes)]"""
+    return _spans(api().zeggs_live_gaze_spans, lg.d, int(row))
 
 
 class LiveSpeech:
