@@ -54,6 +54,12 @@
   every row gets a new root-space target on an arc every tick (set_gaze_many of all rows, timed by itself).  Median and p95 of
   step() for both, the median of set_gaze_many, what each enqueues per step; the claim to check: the gaze server's median lies
   within the plain server's own spread of the same run (its p95 minus its median) -> profiles/live_gaze.json.
+  --leg styles: what named styles cost, per rows in {1, 8, 32, 64}: a plain server and one with a style bank in ONE process,
+  brought to 10 s on the same signals, then fed the same chunks tick by tick, taking turns at going first; every tick every row
+  gets a new style -- ONE set_style_many of two-term named mixes on the bank server, a loop of tensor set_style calls on the
+  plain one, each timed by itself.  Both columns and their ratio, median and p95 of step() for both (the claim to check: the bank
+  server's median lies within the plain server's own spread), and at 1 row add_style() of a 600-frame and a 7 200-frame
+  exemplar beside the tick -> profiles/live_styles.json.
 
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
@@ -66,6 +72,7 @@ Every case is a child process under its own `timeout`; the first one that fails 
     python tools/live_bench.py --leg refilter [--out profiles/live_refilter.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg snapshot [--out profiles/live_snapshot.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg gaze [--out profiles/live_gaze.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg styles [--out profiles/live_styles.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -488,6 +495,88 @@ def case_gaze(rows, steps, age=10):
                 launches_per_step={k: sorted(ops_seen[k]) for k in names}, ops_per_set_gaze_many=srv["gaze"].stats["ops_last_set_gaze"])
 
 
+def case_styles(rows, steps, age=10):
+    """what named styles cost: a plain server and one with a style bank in ONE process, the same rows' signals up to `age` (1 s
+    push_many calls, drained), then tick by tick, taking turns at going first.  Every tick every row gets a new style: on the
+    bank server a two-term named mix by ONE set_style_many, on the plain server the same number of tensor set_style calls in a
+    loop (vectors already on the device), each timed by itself in front of the step.  At rows == 1 also add_style() of a
+    600-frame and a 7 200-frame exemplar through a style encoder of the flagship widths, beside the tick"""
+    import numpy as np
+    import torch
+    from zeggs import live, modules, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    torch.manual_seed(1234)
+    net = modules.StyleEncoder(synth.POSE_IN, 512, 64, type="attn", use_vae=True).to("cuda:0").eval()
+    srv = {"plain": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK),
+           "bank": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, styles=dict(net=net, capacity=16))}
+    vectors = [(torch.randn(128, generator=gen) * 0.5).to("cuda:0") for _ in range(8)]
+    for j, v in enumerate(vectors):
+        srv["bank"].add_style(f"s{j}", v)
+    tensors = [v[:64].contiguous() for v in vectors]
+    sids = {"plain": [srv["plain"].open(first, st) for st in styles], "bank": [srv["bank"].open(first, f"s{r % 8}") for r in range(rows)]}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    names = ["plain", "bank"]
+    t, t_set, ops_seen, i = {k: [] for k in names}, {k: [] for k in names}, {k: set() for k in names}, 0
+    while len(t["plain"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]
+        for k in names[i % 2:] + names[:i % 2]:
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            if k == "bank":
+                srv[k].set_style_many({sid: dict(style={f"s{(i + r) % 8}": 0.7, f"s{(i + r + 3) % 8}": 0.3}, fade=12) for r, sid in enumerate(sids[k])})
+            else:
+                for r, sid in enumerate(sids[k]):
+                    srv[k].set_style(sid, tensors[(i + r) % 8], fade=12)
+            torch.cuda.synchronize()
+            t_set[k].append(time.perf_counter() - t0)
+            while True:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k].append(dt)
+                ops_seen[k].add(srv[k].stats["launches_per_step"])
+        pos = nxt
+    assert len(ops_seen["plain"]) == len(ops_seen["bank"]) == 1 and ops_seen["bank"] == ops_seen["plain"], ops_seen
+    res = dict(kind="styles", rows=rows, age_s=age, tick=TICK, step={k: _summary(t[k]) for k in names},
+               set_style={"tensor_loop": _summary(t_set["plain"]), "named_many": _summary(t_set["bank"])},
+               launches_per_step={k: sorted(ops_seen[k]) for k in names}, ops_per_set_style_many=srv["bank"].stats["ops_last_set_style"])
+    if rows == 1:
+        st = synth.make_stats()
+        add = {}
+        for L in (600, 7200):
+            c = synth.make_clip_stats(L, seed=L, stats=st)
+            ex = np.concatenate([c["Y_root_vel"], c["Y_root_vrt"], c["Y_lpos"].reshape(L, -1), c["Y_ltxy"].reshape(L, -1),
+                                 c["Y_lvel"].reshape(L, -1), c["Y_lvrt"].reshape(L, -1), np.zeros((L, 3), np.float32)], axis=1)
+            ex = torch.as_tensor(ex, dtype=torch.float32, device="cuda:0")
+            srv["bank"].add_style("example", ex)          # (the first call at a length builds what the encoder keeps per length)
+            ts = []
+            for _ in range(7):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                srv["bank"].add_style("example", ex)
+                torch.cuda.synchronize()
+                ts.append(time.perf_counter() - t0)
+            add[f"{L} frames"] = _summary(ts)
+        res["add_style_of_exemplar_rows_on_the_device"] = add
+    return res
+
+
 REFILTER_LEGS = (("30", 30, False), ("120", 120, False), ("30 filtered", 30, True), ("120 filtered", 120, True))
 
 
@@ -635,10 +724,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot", "gaze"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot", "gaze", "styles"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64, snapshot:64 or gaze:64")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64, snapshot:64, gaze:64 or styles:64")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -652,7 +741,8 @@ def main():
                case_retime(int(rest[0]), a.steps) if kind == "retime" else
                case_refilter(int(rest[0]), a.steps) if kind == "refilter" else
                case_snapshot(int(rest[0]), a.steps) if kind == "snapshot" else
-               case_gaze(int(rest[0]), a.steps) if kind == "gaze" else case_baseline(int(rest[0]), a.steps))
+               case_gaze(int(rest[0]), a.steps) if kind == "gaze" else
+               case_styles(int(rest[0]), a.steps) if kind == "styles" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -689,6 +779,10 @@ def main():
         cases = [f"gaze:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_gaze.json")
+    if a.leg == "styles":
+        cases = [f"styles:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_styles.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -816,6 +910,31 @@ def main():
                                               launches_per_step=r["launches_per_step"])
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, step_without_and_with_the_moving_gaze=table, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "styles":
+        budget = 1e3 * TICK / FPS
+        table, add = {}, None
+        for r in results:
+            plain, bank = r["step"]["plain"], r["step"]["bank"]
+            loop, many = r["set_style"]["tensor_loop"], r["set_style"]["named_many"]
+            spread = round(plain["p95_ms"] - plain["median_ms"], 4)
+            table[f"{r['rows']} rows"] = dict(set_style_tensor_loop_median_ms=loop["median_ms"], set_style_many_named_median_ms=many["median_ms"],
+                                              named_over_tensor_loop=round(many["median_ms"] / loop["median_ms"], 4),
+                                              named_is_cheaper=many["median_ms"] < loop["median_ms"], ops_per_set_style_many=r["ops_per_set_style_many"],
+                                              step_plain_median_ms=plain["median_ms"], step_plain_p95_ms=plain["p95_ms"],
+                                              step_bank_median_ms=bank["median_ms"], step_bank_p95_ms=bank["p95_ms"],
+                                              bank_minus_plain_ms=round(bank["median_ms"] - plain["median_ms"], 4), plain_spread_ms=spread,
+                                              bank_median_within_the_plain_spread=abs(bank["median_ms"] - plain["median_ms"]) <= spread,
+                                              launches_per_step=r["launches_per_step"])
+            if "add_style_of_exemplar_rows_on_the_device" in r:
+                add = {k: dict(median_ms=v["median_ms"], p95_ms=v["p95_ms"], ticks=round(v["median_ms"] / budget, 3))
+                       for k, v in r["add_style_of_exemplar_rows_on_the_device"].items()}
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   tick_ms=round(budget, 2), ticks_per_case=a.steps, a_new_style_for_every_row_every_tick_and_the_step_beside_it=table,
+                   add_style_beside_the_tick=add, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

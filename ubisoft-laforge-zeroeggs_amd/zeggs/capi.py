@@ -16,8 +16,8 @@ include/zeggs_hip_resample.h, RS_STRUCTS / RS_PROTOTYPES (tests/test_live_resamp
 include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_cpu.py), the sixth, include/zeggs_hip_retime.h,
 RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py), the seventh, include/zeggs_hip_refilter.h, RF_STRUCTS / RF_PROTOTYPES
 (tests/test_live_refilter_cpu.py), the eighth, include/zeggs_hip_snapshot.h, SNAP_STRUCTS / SNAP_PROTOTYPES
-(tests/test_live_snapshot_cpu.py), the ninth, include/zeggs_hip_gaze.h, GZ_STRUCTS / GZ_PROTOTYPES (tests/test_live_gaze_cpu.py):
-same loader.  torch is imported when a tensor is first converted, not
+(tests/test_live_snapshot_cpu.py), the ninth, include/zeggs_hip_gaze.h, GZ_STRUCTS / GZ_PROTOTYPES (tests/test_live_gaze_cpu.py),
+the tenth, include/zeggs_hip_styles.h, SB_STRUCTS / SB_PROTOTYPES (tests/test_live_styles_cpu.py): same loader.  torch is imported when a tensor is first converted, not
 when this module is.
 """
 import ctypes as C
@@ -356,6 +356,22 @@ GZ_PROTOTYPES = {
 }
 
 
+# ----------------------------------------------------------------------------- the tenth header (include/zeggs_hip_styles.h)
+# A bank of named styles on the device, mixed per live row (tests/test_live_styles_cpu.py compares these tables with the header).
+StyleBankDims = _struct("StyleBankDims", [(C.c_int, "rows ST capacity")])
+StyleMix = _struct("StyleMix", [(C.c_long, "k k_style fade_style"), (C.c_float * 8, "weight"), (C.c_int * 8, "slot"), (C.c_float, "temperature"),
+                                (C.c_int, "row terms eps_row reset")])
+SB_STRUCTS = {"ZeggsStyleBankDims": StyleBankDims, "ZeggsStyleMix": StyleMix}
+SB_PROTOTYPES = {
+    "zeggs_live_styles_version": "int:",
+    "zeggs_live_style_bank_bytes": "size_t: ZeggsStyleBankDims*",
+    "zeggs_live_style_put": "status: ZeggsStyleBankDims* any* size_t int f32* int stream",
+    # recs_host: a HOST array of ZeggsStyleMix; recs_dev: the same records on the device (an address cast to the pointer type), None for one
+    "zeggs_live_style_mix": "status: ZeggsStyleBankDims* ZeggsStyleMix* ZeggsStyleMix* int any* size_t f32* int f32* f32* stream",
+    "zeggs_live_style_read": "status: ZeggsStyleBankDims* any* size_t int f32* f32* int host* stream",
+}
+
+
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
     """A device-pointer parameter: takes a tensor (on a GPU, contiguous, one of `dtypes`), None, a c_void_p or an address."""
@@ -394,14 +410,14 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS, **GZ_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS, **GZ_STRUCTS, **SB_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES.get(name) or SB_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -439,7 +455,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -451,7 +467,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

@@ -45,7 +45,12 @@ chunking of the audio gives the frames of the offline path), for `rows` independ
     / set_gaze_many({sid: ...}) put a schedule of 64 bytes per row on the device (include/zeggs_hip_gaze.h) -- from where the
     gaze stands to the target over `fade` frames, on a line or on an arc about a pivot, a root-space target resolved on the
     device with the row's root state at the call -- and ONE launch per decoder call (zeggs_live_condition) writes the gaze rows
-    AND the style rows of the step's frames, in place of the style fade's weight upload and torch.lerp; gaze(sid) reads it.
+    AND the style rows of the step's frames, in place of the style fade's weight upload and torch.lerp; gaze(sid) reads it;
+  * LiveServer(styles=True | dict(net=style_net, capacity=64, terms=8)) makes styles a resource of the server: add_style(name,
+    source) fills a slot of a style bank on the device (include/zeggs_hip_styles.h) -- from an example clip through the style
+    encoder, the encoder's row never leaving the device, or from a finished vector -- and set_style(sid, "name" | {name:
+    weight}, fade, temperature) / set_style_many({sid: ...}) / open(first_pose, "name") mix bank entries into a row's style by
+    ONE launch whatever the number of rows (zeggs_live_style_mix); style(sid) reads a row's pair back.
 
 Everything runs on the caller's current stream; nothing is captured into a graph.  Latency as GestureStream: 15 frames of
 look-ahead + one STFT window.  Not here: close() on the batched path, a network front door.
@@ -123,6 +128,84 @@ def gaze_request(req, default_ease="linear"):
     if o["path"] == "arc" and o["space"] == "world" and pivot is None:
         raise ValueError("set_gaze: path='arc' in space='world' needs a pivot (space='root' turns about the root by default)")
     return dict(target=target, fade=int(fade), space=o["space"], path=o["path"], pivot=pivot, ease=ease)
+
+
+STYLES_DEFAULTS = dict(net=None, capacity=64, terms=8)
+_F32_MAX = float(np.finfo(np.float32).max)          # (the records carry float32)
+STYLE_REQUEST = dict(style=None, fade=0, temperature=None, seed=None)
+
+
+def styles_options(styles):
+    """LiveServer's `styles` argument -> None (off) or dict(net: the style encoder or None, capacity: slots of the bank, terms:
+    the most bank entries one mix may name): True is the defaults, a dict overrides them.  ValueError for anything else, a
+    capacity outside 1 .. 4096 and terms outside 1 .. 8."""
+    if styles is None or styles is False:
+        return None
+    if styles is True:
+        styles = {}
+    if not isinstance(styles, dict) or set(styles) - set(STYLES_DEFAULTS):
+        raise ValueError(f"LiveServer: styles is None, True or a dict with keys {sorted(STYLES_DEFAULTS)}")
+    o = dict(STYLES_DEFAULTS, **styles)
+    for key, top in (("capacity", ops.STYLE_MAX_SLOTS), ("terms", ops.STYLE_MAX_TERMS)):
+        v = o[key]
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 1 <= v <= top:
+            raise ValueError(f"LiveServer: styles {key} {v!r} (an integer in 1..{top})")
+    return dict(net=o["net"], capacity=int(o["capacity"]), terms=int(o["terms"]))
+
+
+def _is_number(x):
+    return isinstance(x, (int, float, np.integer, np.floating)) and not isinstance(x, bool)
+
+
+def style_terms(style, names, max_terms=ops.STYLE_MAX_TERMS):
+    """a named style -- "name", {name: weight} or [(name, weight), ...] -> [(slot, weight)] in the order given, with `names` the
+    bank's {name: slot}.  A name alone has weight 1; the weights are taken as they are (not normalised: the offline "add" blend
+    is a plain product) and a name may come twice in a list.  ValueError for an unknown name (naming it), no term or more
+    than `max_terms`, and a weight that is not a finite number; TypeError for anything that is not one of the three forms."""
+    if isinstance(style, str):
+        pairs = [(style, 1.0)]
+    elif isinstance(style, dict):
+        pairs = list(style.items())
+    elif isinstance(style, (list, tuple)):
+        pairs = list(style)
+        if not all(isinstance(p, (list, tuple)) and len(p) == 2 for p in pairs):
+            raise TypeError(f"set_style: a list of (name, weight) pairs, not {style!r}")
+    else:
+        raise TypeError(f"set_style: a style is a tensor, a name, a {{name: weight}} dict or a list of (name, weight) pairs, not {type(style).__name__}")
+    if not 1 <= len(pairs) <= max_terms:
+        raise ValueError(f"set_style: {len(pairs)} terms (1..{max_terms}: LiveServer(styles=dict(terms=...)), at most {ops.STYLE_MAX_TERMS})")
+    out = []
+    for name, w in pairs:
+        if not isinstance(name, str) or name not in names:
+            raise ValueError(f"set_style: no style {name!r} in the bank (add_style(); it holds {sorted(names)})")
+        if not _is_number(w) or not np.isfinite(w) or abs(float(w)) > _F32_MAX:
+            raise ValueError(f"set_style: the weight of {name!r} is a finite number, not {w!r}")
+        out.append((int(names[name]), float(w)))
+    return out
+
+
+def style_request(req, names, max_terms=ops.STYLE_MAX_TERMS):
+    """one entry of set_style_many -- a named style (style_terms) or dict(style=, fade=, temperature=, seed=) -> the checked
+    request, dict(terms: [(slot, weight)], fade: int, temperature: float (0.0: the means alone), seed: int or None).  A dict
+    is the long form when it has the key "style" and that value is not a number ({"style": 0.5} mixes a style of that name).
+    ValueError for a negative fade, a temperature that is not None or a finite number >= 0, and a seed without a temperature."""
+    if not (isinstance(req, dict) and "style" in req and not _is_number(req["style"])):
+        req = dict(style=req)
+    if set(req) - set(STYLE_REQUEST):
+        raise ValueError(f"set_style: a style or a dict with `style` and keys of {sorted(STYLE_REQUEST)}")
+    o = dict(STYLE_REQUEST, **req)
+    if isinstance(o["style"], torch.Tensor):
+        raise TypeError("set_style_many: named styles only; a tensor goes through set_style(sid, tensor, fade)")
+    terms = style_terms(o["style"], names, max_terms)
+    fade, t, seed = o["fade"], o["temperature"], o["seed"]
+    if isinstance(fade, bool) or not isinstance(fade, (int, np.integer)) or fade < 0:
+        raise ValueError(f"set_style: fade {fade!r} (an integer >= 0)")
+    if t is not None and (not _is_number(t) or not np.isfinite(t) or t < 0 or float(t) > _F32_MAX):
+        raise ValueError(f"set_style: temperature {t!r} (None or a finite number >= 0)")
+    t = 0.0 if t is None else float(t)
+    if seed is not None and (t == 0.0 or isinstance(seed, bool) or not isinstance(seed, (int, np.integer))):
+        raise ValueError(f"set_style: seed {seed!r} (an integer, with a temperature > 0: the means alone draw nothing)")
+    return dict(terms=terms, fade=int(fade), temperature=t, seed=None if seed is None else int(seed))
 
 
 def _quat_rotate(q, v):
@@ -749,13 +832,24 @@ class LiveServer:
     from ONE launch (zeggs_live_condition) in place of _style()'s upload and torch.lerp, so launches_per_step does not grow.
     `ease`: the ease of a set_gaze() that names none.  With None the three calls raise ValueError naming this option, and the
     server allocates and enqueues what it always did.  (The attribute `gaze` is the rows' gaze tensor [rows, tick + 1, 3] it
-    has always been AND the call gaze(sid): _GazeRows.)"""
+    has always been AND the call gaze(sid): _GazeRows.)
+
+    `styles`: None, True or dict(net=None, capacity=64, terms=8) (styles_options) -- the server keeps a bank of
+    `capacity` named styles on the device, each a mean row and a deviation row of ST floats (include/zeggs_hip_styles.h).
+    add_style() / remove_style() / styles() manage it; `net` is the style encoder (zeggs.modules.StyleEncoder, eval mode) that
+    add_style() sends example clips through -- without it the bank takes finished vectors only.  set_style(), set_style_many()
+    and open() then also take a name, a {name: weight} dict or a list of (name, weight) pairs of at most `terms` entries, mixed
+    on the device by ONE launch whatever the number of rows (zeggs_live_style_mix); style(sid) reads a row's style back.  The
+    bank is the server's, not a row's: it is not part of a snapshot, and a row keeps the vectors it was given when a slot
+    changes afterwards.  step() and close() enqueue what they always did.  With None those calls raise ValueError naming this
+    option (set_style() with a tensor works as ever), and the server allocates and enqueues what it always did."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None, gaze=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None, gaze=None, styles=None):
         g = audio_conf
         loud = loudness_options(loudness)
         self.gaze_conf = gaze_options(gaze)
+        self.styles_conf = styles_options(styles)
         self.resample_conf = audio.resample_options(resample)
         self.frames_conf = frames_options(frames)
         self.retime_conf = retime_options(retime, self.frames_conf, fps)
@@ -825,6 +919,13 @@ class LiveServer:
             self._gz_style = z(R, self.T, ST)
             self._gz_set = _RecStaging(ops.GazeSet, R, self.dev)
             self._gz_cond = _RecStaging(ops.GazeCond, R, self.dev)
+        # named styles: the bank and the rows' noise (ops.LiveStyles), {name: slot}, and the staging blocks of the records of a
+        # set_style_many() with more than one record
+        self._sb = self._sb_set = None
+        self._style_names = {}
+        if self.styles_conf is not None:
+            self._sb = ops.LiveStyles(R, ST, self.styles_conf["capacity"], self.dev)
+            self._sb_set = _RecStaging(ops.StyleMix, R, self.dev)
         self._fr = self._fr_stage = None            # the output head: the rows' state (ops.LiveFrames) and its staging blocks
         if self.frames_conf is not None:
             fc = self.frames_conf
@@ -855,6 +956,8 @@ class LiveServer:
                           launches_per_step=0, steps=0, ops_last_push_many=0, uploaded_bytes=0, resampled_rows=0)
         if self._gz is not None:
             self.stats["ops_last_set_gaze"] = 0
+        if self._sb is not None:
+            self.stats["ops_last_set_style"] = 0
         if self._fr is not None:
             self.stats["frame_bytes"] = 0            # bytes the output head has downloaded so far
 
@@ -919,9 +1022,11 @@ class LiveServer:
         return H, H / self.fps
 
     def open(self, first_pose, style, gain=1.0, rate=None, pcm="f32", start_position=None, start_rotation=None, frame_rate=None,
-             filtered=None):
-        """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S].
-        -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
+             filtered=None, temperature=None, seed=None):
+        """a new stream on a free row: `first_pose` the 16-tuple of anim.preprocess_animation (frame 0 is used), `style` [1, S]
+        -- or, on a server with `styles`, a name, a {name: weight} dict or a list of (name, weight) pairs of the bank, with
+        `temperature` / `seed` as set_style() takes them: the mix launch writes the row's two style rows ahead of the
+        CellStateEncoder, which reads the mixed row on the device.  -> stream id.  The GRU state comes from the CellStateEncoder (zeggs_decoder_state_init).  `gain` (running loudness only):
         what the row's samples are multiplied by until its first estimate; the row's loudness state starts from nothing.
         `rate` / `pcm`: what this stream delivers -- `rate` Hz (None: the server's rate) as "f32" (float32 in [-1, 1)) or "s16"
         (int16 PCM, x = s / 32768).  Anything but float32 at the server's rate is converted on the device as it arrives
@@ -946,6 +1051,12 @@ class LiveServer:
         if self._loud is None and float(gain) != 1.0:
             raise ValueError("LiveServer.open: a gain needs running loudness (LiveServer(loudness=...))")
         rt = LiveServer._filter_of(self, self._frame_rate(frame_rate), frame_rate, filtered)
+        named = None
+        if not isinstance(style, torch.Tensor):
+            self._styles_on("open")
+            named = style_request(dict(style=style, temperature=temperature, seed=seed), self._style_names, self.styles_conf["terms"])
+        elif temperature is not None or seed is not None:
+            raise ValueError("LiveServer.open: temperature / seed sample a named style; a tensor is taken as it is")
         free = [r for r in range(self.rows) if self._rows[r] is None]
         if not free:
             raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
@@ -956,15 +1067,22 @@ class LiveServer:
         f32 = lambda a: a[0:1].to(self.dev, torch.float32).contiguous()  # noqa: E731
         root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = first_pose[:9]
         pose0 = torch.cat([f32(x).reshape(1, -1) for x in (root_vel, root_vrt, lpos, ltxy, lvel, lvrt)], dim=1)
-        gaze0, style0 = f32(first_pose[14]), style.to(self.dev, torch.float32).reshape(1, -1).contiguous()
+        gaze0 = f32(first_pose[14])
+        row = _Row(sid)
+        if named is None:
+            style0 = style.to(self.dev, torch.float32).reshape(1, -1).contiguous()
+        else:                                            # the mix writes sty_old[r] = sty_new[r] (reset); the encoder reads that row
+            with torch.no_grad():
+                self._mix([(r, row, named)], reset=True)
+            style0 = self.sty_new[r:r + 1]
         with torch.no_grad():
             self.h[:, r:r + 1] = ops.decoder_state_init(self.bd, pose0, f32(root_pos), f32(root_rot), gaze0, style0)
         self.pose[r], self.rpos[r], self.rrot[r] = pose0[0], f32(root_pos)[0], f32(root_rot)[0]
         self.gaze[r] = gaze0
         if self._gz is not None:                         # the row's schedule: it looks at the first pose's gaze until a set_gaze
             ops.live_gaze_reset(self._gz, r, gaze0.reshape(-1))
-        self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
-        row = _Row(sid)
+        if named is None:
+            self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
         if rs is not None:
             if self._rs is None:
                 self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
@@ -1314,9 +1432,24 @@ class LiveServer:
         ops.live_loudness_hold(self._loud, self._loud_row(sid), on)
 
     # ------------------------------------------------------------------ style
-    def set_style(self, sid, style, fade=0):
+    def set_style(self, sid, style, fade=0, temperature=None, seed=None):
         """a new style for stream `sid` from frame k on, k = the first frame not yet decoded (returned); `fade` > 0: a linear
-        cross-fade, frame f carries lerp(old, new, style_weight(f, k, fade))"""
+        cross-fade, frame f carries lerp(old, new, style_weight(f, k, fade)).
+        `style`: a tensor [S] / [1, S] -- or, on a server with `styles`, a name, a {name: weight} dict or a list of (name,
+        weight) pairs of the bank (style_terms): the row's new style is sum_i w_i (mean_i + (dev_i / temperature) eps_i) over the
+        named slots, in float64, rounded once, and its old style is where an unfinished fade stands at frame k - 1,
+        both written by ONE launch with the record in its arguments (zeggs_live_style_mix).
+        `temperature` None (or 0): the means alone -- deterministic.  This is a default of the LIVE path only: the offline entry
+        points sample at temperature 1.0 unless told otherwise.  With temperature t > 0 the noise is ops.randn((terms, S),
+        seed=seed), one more launch into the row's slice of the server's noise tensor (`seed` None: ops.next_seed()); one term
+        of weight 1 is then the offline style_net(example, t, eps).  Neither applies to a tensor.
+        ValueError before anything is enqueued for a negative fade, an unknown name, too many terms, a weight or temperature
+        that is not finite, and a named style on a server without `styles`; KeyError for a stream that is not open."""
+        if not isinstance(style, torch.Tensor):
+            self._styles_on("set_style")
+            return self.set_style_many({sid: dict(style=style, fade=fade, temperature=temperature, seed=seed)})[sid]
+        if temperature is not None or seed is not None:
+            raise ValueError("set_style: temperature / seed sample a named style; a tensor is taken as it is")
         r, row = self._row(sid)
         if fade < 0:
             raise ValueError("set_style: fade >= 0")
@@ -1325,6 +1458,153 @@ class LiveServer:
         self.sty_new[r] = style.to(self.dev, torch.float32).reshape(-1)
         row.k_style, row.fade = row.kd, int(fade)
         return row.kd
+
+    # ------------------------------------------------------------------ named styles
+    def _styles_on(self, what):
+        if self._sb is None:
+            raise ValueError(f"LiveServer.{what}: named styles are off (LiveServer(styles=True))")
+
+    def styles(self):
+        """-> {name: slot} of the bank"""
+        self._styles_on("styles")
+        return dict(self._style_names)
+
+    def add_style(self, name, source, trim=None):
+        """put a style into the bank under `name` -> its slot.  A name the bank already has keeps its slot and is overwritten;
+        rows that were set from it keep the vectors they were given.  `source`:
+          * a BVH path, a parsed clip (the dict of anim.bvh_load) or un-normalised exemplar rows [L, F] -- an EXAMPLE: it goes
+            through the calls the offline front end makes (anim.preprocess_animation, the exemplar feature rows, (x -
+            anim_input_mean) / anim_input_std, the style encoder) and the encoder's raw row -- mean | log-variance for a VAE
+            encoder -- goes into the slot without leaving the device (zeggs_live_style_put).  The encoder's products run in a
+            fixed summation order here (ops.fixed_order_gemms), so the same example gives the same slot, bit for bit, on every
+            call and every server; the offline call gives these bits under the same switch and differs in the last place
+            without it, from run to run.  Needs LiveServer(styles=dict(net=));
+            `trim` = (a, b) keeps frames a .. b - 1 of the clip, as generate_gesture's (path, (a, b)) does;
+          * a 1-D tensor or array of S floats -- an embedding computed elsewhere, or a one-hot label of a label-conditioned
+            model: the slot's mean, deviation 0 -- or of 2 S floats, an encoder row computed elsewhere (mean | log-variance).
+            Needs no encoder.
+        Set-up work, not for the tick path: a clip is parsed on the host and encoded by a call of its own.  ValueError for a
+        name that is not a string, an example without `net`, a vector or encoder row of another length; RuntimeError naming the
+        capacity when the bank is full."""
+        self._styles_on("add_style")
+        if not isinstance(name, str):
+            raise ValueError(f"add_style: a name is a string, not {name!r}")
+        ST, conf = int(self.sty_old.shape[1]), self.styles_conf
+        vector = isinstance(source, (torch.Tensor, np.ndarray)) and source.ndim == 1
+        if not vector and conf["net"] is None:
+            raise ValueError("add_style: an example needs the style encoder (LiveServer(styles=dict(net=style_net))); without it the "
+                             f"bank takes vectors of {ST} floats")
+        if vector and int(source.shape[0]) not in (ST, 2 * ST):
+            raise ValueError(f"add_style: a vector of {int(source.shape[0])} floats, the model's styles have {ST} (or {2 * ST}: mean | log-variance)")
+        if trim is not None and (vector or len(trim) != 2):
+            raise ValueError(f"add_style: trim {trim!r} is (first frame, end) of an example")
+        if name not in self._style_names and len(self._style_names) >= conf["capacity"]:
+            raise RuntimeError(f"add_style: the bank is full, all {conf['capacity']} slots are in use (LiveServer(styles=dict(capacity=...)); "
+                               "remove_style() frees one)")
+        with torch.no_grad():
+            if vector:
+                enc = torch.as_tensor(source).to(self.dev, torch.float32).contiguous()
+            else:
+                enc = self._encode_example(source, trim)
+                if int(enc.numel()) not in (ST, 2 * ST):
+                    raise ValueError(f"add_style: the style encoder returns {int(enc.numel())} floats, the model's styles have {ST}")
+            if name in self._style_names:
+                slot = self._style_names[name]
+            else:
+                slot = min(set(range(conf["capacity"])) - set(self._style_names.values()))
+            ops.live_style_put(self._sb, slot, enc)
+        self._style_names[name] = slot
+        return slot
+
+    def _encode_example(self, source, trim):
+        """the style encoder's raw output row [E] for an example (add_style), on the device"""
+        import pathlib
+        from . import modules
+        from .generate import _example_features
+        if isinstance(source, (torch.Tensor, np.ndarray)):
+            rows = torch.as_tensor(source).to(self.dev, torch.float32)
+            if rows.ndim != 2 or rows.shape[1] != self.st["anim_input_mean"].numel():
+                raise ValueError(f"add_style: exemplar rows are [L, {self.st['anim_input_mean'].numel()}], not {list(rows.shape)}")
+            if trim is not None:
+                rows = rows[trim[0]:trim[1]]
+        else:
+            if isinstance(source, (pathlib.PurePath, str)):
+                clip = anim.bvh_load(source)
+            elif isinstance(source, dict):
+                clip = {k: (v.copy() if isinstance(v, np.ndarray) else v) for k, v in source.items()}
+            else:
+                raise ValueError(f"add_style: a BVH path, a parsed clip, exemplar rows [L, F] or a vector, not {type(source).__name__}")
+            if trim is not None:
+                clip["rotations"] = clip["rotations"][trim[0]:trim[1]]
+                clip["positions"] = clip["positions"][trim[0]:trim[1]]
+            rows = _example_features(anim.preprocess_animation(clip, self.dev))
+        if rows.shape[0] < 1:
+            raise ValueError("add_style: the example has no frames")
+        ex = ((rows - self.st["anim_input_mean"]) / self.st["anim_input_std"])[None].contiguous()
+        net = self.styles_conf["net"]
+        enc = net.encoder
+        with ops.fixed_order_gemms():                    # no split-K atomics: the same example fills a slot with the same bits on every server
+            out = ops.style_encoder_gru(ex, enc) if isinstance(enc, modules.StyleEncoderGRU) else ops.style_encoder_attn(ex, enc, net.training)
+        return out.reshape(-1).contiguous()
+
+    def remove_style(self, name):
+        """take `name` out of the bank; its slot is free for the next add_style().  Rows keep the vectors they were given"""
+        self._styles_on("remove_style")
+        if name not in self._style_names:
+            raise ValueError(f"remove_style: no style {name!r} in the bank (it holds {sorted(self._style_names)})")
+        del self._style_names[name]
+
+    def set_style_many(self, requests):
+        """set_style() with named styles for many streams at once: requests = {sid: style | dict(style=, fade=, temperature=,
+        seed=)} -> {sid: k}.  Whatever the number of streams: ONE upload of the records and ONE launch (zeggs_live_style_mix; a
+        single record travels in the kernel arguments, without the upload), plus one noise launch per record that samples --
+        what a director changing the mood of every character in a tick calls.  The rows' vectors and counters are bit for bit
+        those of the same requests as single set_style() calls.  Every request is checked before anything is enqueued;
+        stats["ops_last_set_style"] counts what the call enqueued."""
+        self._styles_on("set_style_many")
+        rows = [self._row(sid) for sid in requests]
+        reqs = [style_request(q, self._style_names, self.styles_conf["terms"]) for q in requests.values()]
+        self.stats["ops_last_set_style"] = 0
+        if not reqs:
+            return {}
+        with torch.no_grad():
+            self.stats["ops_last_set_style"] = self._mix([(r, row, o) for (r, row), o in zip(rows, reqs)], reset=False)
+        for (_, row), o in zip(rows, reqs):
+            row.k_style, row.fade = row.kd, o["fade"]
+        return {sid: row.kd for sid, (_, row) in zip(requests, rows)}
+
+    def _mix(self, jobs, reset):
+        """ONE zeggs_live_style_mix launch for jobs = [(r, row, checked request)], in front of it the upload of the records where
+        there are several and a noise launch per record that samples -> the number of operations enqueued"""
+        n, sb = len(jobs), self._sb
+        recs = (ops.StyleMix * 1)() if n == 1 else self._sb_set.take()
+        count = 1 if n == 1 else 2
+        for q, (r, row, o) in zip(recs, jobs):
+            terms = o["terms"]
+            q.slot[:] = [s for s, _ in terms] + [0] * (ops.STYLE_MAX_TERMS - len(terms))
+            q.weight[:] = [w for _, w in terms] + [0.0] * (ops.STYLE_MAX_TERMS - len(terms))
+            q.k, q.k_style, q.fade_style = row.kd, row.k_style, row.fade
+            q.row, q.terms, q.reset, q.temperature, q.eps_row = r, len(terms), int(reset), o["temperature"], -1
+            if o["temperature"] > 0.0:
+                ops.randn_into(sb.eps[r, :len(terms)], o["seed"])
+                q.eps_row = r
+                count += 1
+        dev = None if n == 1 else self._sb_set.upload(n)
+        ops.live_style_mix(sb, recs, n, self.sty_old, self.sty_new, dev)
+        return count
+
+    def style(self, sid):
+        """-> dict(old [S], new [S]: the row's two style vectors, k, fade: its fade, current [S]: the style of frame kd, the first
+        frame not yet decoded, lerp(old, new, style_weight(kd, k, fade)) by torch.lerp's float32 formula with the multiply-add in
+        one rounding, as the device evaluates it).  One small read-back that waits for the stream: monitoring, not for the tick
+        path."""
+        self._styles_on("style")
+        r, row = self._row(sid)
+        old, new = ops.live_style_read(self._sb, row=r, sty_old=self.sty_old, sty_new=self.sty_new)
+        w = np.float32(style_weight(row.kd, row.k_style, row.fade))
+        d = (new - old).astype(np.float64)              # (a product of two float32 values is exact in float64)
+        current = (old + np.float64(w) * d if w < 0.5 else new - d * np.float64(np.float32(1.0) - w)).astype(np.float32)
+        return dict(old=old, new=new, k=row.k_style, fade=row.fade, current=current)
 
     def _style(self, frames):
         """style rows [R, n, ST] of the frames frames[r] + 0 .. n - 1 (frames[r] None: the row's current style)"""

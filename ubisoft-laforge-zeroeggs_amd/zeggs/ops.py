@@ -14,7 +14,7 @@ from . import capi
 from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_GRU_FIELDS, DecCall, DecDims, DecPtrs,  # noqa: F401
                    DecStats, FramesDims, FramesRow, GazeCond, GazeDims, GazeSet, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
                    ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SnapSeg, SnapSpan, SpeechDims, SpeechPtrs,
-                   StyleDims, StyleGruDims, StyleGruPtrs, StylePtrs, api)
+                   StyleBankDims, StyleDims, StyleGruDims, StyleGruPtrs, StyleMix, StylePtrs, api)
 
 _LIB_PATH = capi.LIB_PATH
 
@@ -240,6 +240,15 @@ def randn(shape, device, seed=None):
     out = torch.empty(*shape, device=device, dtype=torch.float32)
     api().zeggs_randn(out, out.numel(), next_seed() if seed is None else int(seed), _stream())
     return out
+
+
+def randn_into(view, seed=None):
+    """randn() into a contiguous float32 slice of a persistent buffer: the same zeggs_randn launch, so view == randn(view.shape,
+    seed=seed) bit for bit, and nothing is allocated"""
+    if view.dtype is not torch.float32 or not view.is_contiguous():
+        raise ValueError("randn_into: a contiguous float32 view")
+    api().zeggs_randn(view, view.numel(), next_seed() if seed is None else int(seed), _stream())
+    return view
 
 
 class _BroadcastTimeFn(torch.autograd.Function):
@@ -1380,6 +1389,48 @@ def live_gaze_read(lg, row, frame):
 def live_gaze_spans(lg, row):
     """zeggs_live_gaze_spans: where row `row` lives in lg.state -> [(offset, bytes)]"""
     return _spans(api().zeggs_live_gaze_spans, lg.d, int(row))
+
+
+STYLE_MAX_TERMS, STYLE_MAX_SLOTS = 8, 4096         # ZEGGS_STYLE_MAX_TERMS / ZEGGS_STYLE_MAX_SLOTS
+
+
+class LiveStyles:
+    """The style bank of a live server (include/zeggs_hip_styles.h): the dims record, the bank [capacity, 2, ST] (a slot's mean
+    row and its deviation row; zeroes) and the noise tensor [rows, STYLE_MAX_TERMS, ST] the sampling records of a mix read,
+    slice r the noise of row r."""
+
+    def __init__(self, rows, ST, capacity, device):
+        self.d = StyleBankDims(int(rows), int(ST), int(capacity))
+        nbytes = api().zeggs_live_style_bank_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LiveStyles: {api().zeggs_last_error().decode()}")
+        self.bank = torch.zeros(int(capacity), 2, int(ST), dtype=torch.float32, device=device)
+        self.eps = torch.zeros(int(rows), STYLE_MAX_TERMS, int(ST), dtype=torch.float32, device=device)
+
+
+def live_style_put(ls, slot, enc):
+    """zeggs_live_style_put: slot `slot` of the bank from `enc`, a float32 row on the device of 2 ST floats (the style encoder's
+    VAE output: mean | log-variance) or ST floats (a plain vector: deviation 0): ONE launch"""
+    api().zeggs_live_style_put(ls.d, ls.bank, ls.bank.numel() * 4, int(slot), enc, int(enc.numel()), _stream())
+
+
+def live_style_mix(ls, recs, n, sty_old, sty_new, recs_dev=None, eps=None):
+    """zeggs_live_style_mix: recs[:n] a HOST array of StyleMix, `recs_dev` the device address of a copy of the same records (None:
+    one record, in the kernel arguments); sty_old / sty_new [rows, ST] are rewritten in the rows the records name; `eps`: the
+    noise tensor [., STYLE_MAX_TERMS, ST] the records' eps_row index (None: ls.eps): ONE launch for all of them"""
+    eps = ls.eps if eps is None else eps
+    api().zeggs_live_style_mix(ls.d, recs, _records(StyleMix, recs_dev), int(n), ls.bank, ls.bank.numel() * 4, eps, int(eps.shape[0]),
+                               sty_old, sty_new, _stream())
+
+
+def live_style_read(ls, slot=None, row=None, sty_old=None, sty_new=None):
+    """zeggs_live_style_read (waits for the stream): slot= -> (mean, dev) of a bank slot; row= with the two style tensors ->
+    (old, new) of a live row; float32 arrays of ST"""
+    ST = ls.d.ST
+    out = np.empty(2 * ST, np.float32)
+    api().zeggs_live_style_read(ls.d, ls.bank, ls.bank.numel() * 4, -1 if slot is None else int(slot), sty_old, sty_new,
+                                -1 if row is None else int(row), out.ctypes.data, _stream())
+    return out[:ST].copy(), out[ST:].copy()
 
 
 class LiveSpeech:
