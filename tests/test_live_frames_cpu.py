@@ -364,3 +364,65 @@ def test_the_packed_block_unpacks_to_the_documented_arrays():
             assert a["gpos"].shape == (5, 3, 3) and a["grot"].shape == (5, 3, 4) and a["grot"][1, 0, 0] == 5000 + 3 * 21 + 9
         buf[:] = 0
         assert all(v.any() for g in (got[0], got[2]) for v in g.values())      # nothing aliases the block
+
+
+# ----------------------------------------------------------------------------- the head's three forms behind one table
+class _Recorder:
+    """stands in for the typed API: every call is written down, none reaches the library (a size query answers 64 bytes)"""
+
+    def __init__(self):
+        self.calls = []
+
+    def __getattr__(self, name):
+        def call(*args):
+            self.calls.append((name, args))
+            return 64 if name.endswith("_state_bytes") else 0
+        return call
+
+
+HEAD_FORMS = {
+    "frames": (ops.LiveFrames, capi.FramesRow, capi.FR_PROTOTYPES,
+               ["zeggs_live_frames_state_bytes", "zeggs_live_frames_prepare", "zeggs_live_frames_reset", "zeggs_live_frames", "zeggs_live_frames_spans"]),
+    "retime": (ops.LiveRetime, capi.RetimeRow, capi.RT_PROTOTYPES,
+               ["zeggs_live_retime_state_bytes", "zeggs_live_retime_prepare", "zeggs_live_retime_reset", "zeggs_live_frames_retimed", "zeggs_live_retime_spans"]),
+    "refilter": (ops.LiveRefilter, capi.RefilterRow, capi.RF_PROTOTYPES,
+                 ["zeggs_live_refilter_state_bytes", "zeggs_live_refilter_prepare", "zeggs_live_refilter_reset", "zeggs_live_frames_refiltered",
+                  "zeggs_live_refilter_spans"]),
+}
+
+
+@pytest.mark.parametrize("form", list(HEAD_FORMS))
+def test_each_head_form_reaches_its_own_entry_points_and_no_other(form, monkeypatch):
+    """ops.LiveFrames' table of entry points, which the constructor, the one reset, the one launch and live_frames_spans read: an
+    object of each form calls the five entry points of its own header (the span report: the eighth's), in the order asked and
+    nothing else, with its own record type behind rows_dev; max_half follows the dims in every call of the filtered form and in
+    none of the others; the six names of the headers' calls are the two shared functions.  No device: the API is a recorder."""
+    cls, record, protos, names = HEAD_FORMS[form]
+    assert all(n in protos or n in capi.SNAP_PROTOTYPES for n in names)
+    rec = _Recorder()
+    monkeypatch.setattr(ops, "api", lambda: rec)
+    monkeypatch.setattr(ops, "_stream", lambda: "stream")
+    args = (4, SKELETONS["tree"], 20) + ((16,) if form == "refilter" else ())
+    head = cls(*args, device="cpu")
+    extra = (16,) if form == "refilter" else ()
+    assert head.extra == extra and head.record is record
+    rows = (record * 4)()
+    ops.live_head_reset(head, 2)
+    ops.live_head_reset(head, 3, [0, 0, 0], [1, 0, 0, 0], [1, 2, 3], [0, 1, 0, 0])
+    ops.live_head_launch(head, rows, 1)
+    ops.live_head_launch(head, rows, 3, 0x7000)
+    ops.live_frames_spans(head, 1)
+    assert [c[0] for c in rec.calls] == [names[0], names[1], names[2], names[2], names[3], names[3], names[4]]
+    for name, a in rec.calls:
+        assert a[0] is head.d and a[1:1 + len(extra)] == extra, name
+    tail = [a[1 + len(extra):] for _, a in rec.calls]           # what follows the dims and, on the filtered form, max_half
+    assert tail[0] == () and len(tail[1]) == 5 and list(tail[1][0]) == SKELETONS["tree"] and tail[1][2:] == (head.state, 64, "stream")
+    assert tail[2] == (head.state, 64, 2, None, None, None, None, 0, "stream")
+    assert tail[3][:3] == (head.state, 64, 3) and [list(v) for v in tail[3][3:7]] == [[0, 0, 0], [1, 0, 0, 0], [1, 2, 3], [0, 1, 0, 0]]
+    assert tail[3][7:] == (1, "stream")
+    assert tail[4] == (rows, None, 1, head.state, 64, "stream")
+    assert tail[5][0] is rows and isinstance(tail[5][1], ctypes.POINTER(record)) and tail[5][2:] == (3, head.state, 64, "stream")
+    assert ctypes.cast(tail[5][1], ctypes.c_void_p).value == 0x7000
+    assert tail[6][0] == 1 and len(tail[6]) == 3 and tail[6][2] == ops.SNAP_MAX_SPANS
+    assert ops.live_frames_reset is ops.live_retime_reset is ops.live_refilter_reset is ops.live_head_reset
+    assert ops.live_frames is ops.live_frames_retimed is ops.live_frames_refiltered is ops.live_head_launch

@@ -157,25 +157,16 @@ __global__ __launch_bounds__(FR_THREADS) void live_refilter_k(ZeggsFramesDims d,
   if (threadIdx.x == 0) pl->started = 1;
 }
 
-__global__ void live_refilter_reset_k(FrPlace place, char* row_state) { *(FrPlace*)row_state = place; }
+}  // namespace
+
+#include "frames_host.h"      // the host contract the three forms of the head share
+
+namespace {
 
 int rf_dims_ok(const ZeggsFramesDims* d, int max_half, const void* state, size_t state_bytes) {
-  ZCHECK(d != nullptr, "refilter: NULL dims");
-  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "refilter: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
-  const int why = fr_shape_refused(d->J, d->max_frames);
-  ZCHECK(why != 1, "refilter: %d joints (1..%d)", d->J, FR_MAX_JOINTS);
-  ZCHECK(why != 2, "refilter: max_frames %d (1..%d)", d->max_frames, FR_MAX_FRAMES);
-  ZCHECK(why == 0, "refilter: a frame of %d joints needs %ld bytes of LDS, the kernel may have %d", d->J, fr_frame_lds_bytes(d->J), FR_LDS_BYTES);
-  ZCHECK(d->what >= 1 && d->what <= (FR_LOCAL | FR_WORLD | FR_BVH), "refilter: what = %d (a mask of LOCAL 1 | WORLD 2 | BVH 4)", d->what);
-  ZCHECK(order_code(d->order) == ORDER_ZYX || d->order == ORDER_XZY, "refilter: channel order %d (\"zyx\" and \"xzy\" are supported)", d->order);
+  ZTRY(fh_shape_ok("refilter", d));
   ZCHECK(max_half >= 1 && max_half <= RF_MAX_HALF, "refilter: max_half %d (1..%d)", max_half, RF_MAX_HALF);
-  if (state_bytes != (size_t)-1) {
-    ZCHECK(state != nullptr, "refilter: NULL state");
-    ZCHECK(state_bytes >= (size_t)rf_state_bytes(d->rows, d->J, max_half), "refilter: state too small (%zu < %zu)", state_bytes,
-           (size_t)rf_state_bytes(d->rows, d->J, max_half));
-    ZCHECK((uintptr_t)state % 8 == 0, "refilter: misaligned state");
-  }
-  return 0;
+  return fh_state_ok("refilter", state, state_bytes, (size_t)rf_state_bytes(d->rows, d->J, max_half));
 }
 
 }  // namespace
@@ -190,39 +181,14 @@ extern "C" size_t zeggs_live_refilter_state_bytes(const ZeggsFramesDims* d, int 
 extern "C" int zeggs_live_refilter_prepare(const ZeggsFramesDims* d, int max_half, const int* parents, const int* seq, void* state,
                                            size_t state_bytes, void* stream) {
   ZTRY(rf_dims_ok(d, max_half, state, state_bytes));
-  ZCHECK(parents != nullptr && seq != nullptr, "refilter prepare: NULL parents / seq");
-  const int J = d->J;
-  int bad = fr_bad_parent(parents, J);
-  ZCHECK(bad != 0, "refilter prepare: parents[0] = %d (the root has parent -1)", parents[0]);
-  ZCHECK(bad < 0, "refilter prepare: parents[%d] = %d (a parent comes before its children: 0 .. %d)", bad, parents[bad], bad - 1);
-  int tables[3 * FR_MAX_JOINTS];
-  bad = fr_bad_seq(seq, J, tables + 2 * J);
-  ZCHECK(bad < 0, "refilter prepare: seq[%d] = %d: seq is no permutation of 0 .. %d", bad, seq[bad], J - 1);
-  memcpy(tables, parents, sizeof(int) * J);
-  memcpy(tables + J, seq, sizeof(int) * J);
-  // once per server, never on the tick path: the copy is waited for, `tables` is gone when the call returns
-  hipError_t e = hipMemcpyAsync(state, tables, sizeof(int) * 3 * J, hipMemcpyHostToDevice, (hipStream_t)stream);
-  if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
-  ZCHECK(e == hipSuccess, "refilter prepare: %s", hipGetErrorString(e));
-  return 0;
+  return fh_prepare("refilter", d, parents, seq, state, stream);
 }
 
 extern "C" int zeggs_live_refilter_reset(const ZeggsFramesDims* d, int max_half, void* state, size_t state_bytes, int row, const float* ref_pos,
                                          const float* ref_rot, const double* start_pos, const double* start_rot, int rebase, void* stream) {
   ZTRY(rf_dims_ok(d, max_half, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "refilter reset: row %d of %d", row, d->rows);
-  FrPlace p = {};
-  p.ref_rot[0] = p.start_rot[0] = 1.0;
-  if (rebase) {
-    ZCHECK(ref_pos != nullptr && ref_rot != nullptr && start_pos != nullptr && start_rot != nullptr,
-           "refilter reset: row %d: a placement needs ref_pos, ref_rot, start_pos and start_rot", row);
-    for (int i = 0; i < 3; ++i) { p.ref_pos[i] = (double)ref_pos[i]; p.start_pos[i] = start_pos[i]; }
-    for (int i = 0; i < 4; ++i) { p.ref_rot[i] = (double)ref_rot[i]; p.start_rot[i] = start_rot[i]; }
-    p.rebase = 1;
-  }
-  hipLaunchKernelGGL(live_refilter_reset_k, dim3(1), dim3(1), 0, (hipStream_t)stream, p, (char*)state + rf_row_offset(d->J, max_half, row));
-  ZLAUNCH_CHECK("live_refilter_reset");
-  return 0;
+  return fh_reset("refilter", "live_refilter_reset", d, state, rf_row_offset(d->J, max_half, row), row, ref_pos, ref_rot, start_pos, start_rot,
+                  rebase, stream);
 }
 
 extern "C" int zeggs_live_frames_refiltered(const ZeggsFramesDims* d, int max_half, const ZeggsRefilterRow* rows, const ZeggsRefilterRow* rows_dev,
@@ -237,21 +203,14 @@ extern "C" int zeggs_live_frames_refiltered(const ZeggsFramesDims* d, int max_ha
   const int J = d->J;
   for (int i = 0; i < R; ++i) {
     const ZeggsRefilterRow& w = rows[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "%s: record %d: row %d of %d", who, i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "%s: record %d: row %d twice in one call", who, i, w.row);
-    seen[w.row] = true;
-    ZCHECK(w.count >= 0, "%s: record %d: negative count %d", who, i, w.count);
-    ZCHECK(w.count <= d->max_frames, "%s: record %d: %d frames, max_frames is %d", who, i, w.count, d->max_frames);
-    const int why = rf_ratio_refused(w.L, w.M);
-    ZCHECK(why != 1 && why != 2, "%s: record %d: ratio %d / %d (1 <= L, M <= %d)", who, i, w.L, w.M, RT_MAX_TERM);
-    ZCHECK(why != 3, "%s: record %d: ratio %d / %d is not in lowest terms", who, i, w.L, w.M);
-    ZCHECK(why != 4, "%s: record %d: ratio %d / %d is above %d", who, i, w.L, w.M, RT_MAX_UP);
-    ZCHECK(w.n_in >= 0 && w.n_in <= (1L << 40), "%s: record %d: input counter %ld", who, i, w.n_in);
+    ZTRY(fh_row_ok(who, i, w, d, seen));
+    ZTRY(fh_ratio_ok(who, i, w));
     ZCHECK(w.half >= 0, "%s: record %d: negative half %d", who, i, w.half);
     const bool filtered = w.half > 0;
     long want;
     if (filtered) {
-      ZCHECK(why == 0, "%s: record %d: a filtered row at ratio %d / %d (L <= %d and M <= %d L)", who, i, w.L, w.M, RF_MAX_L, RF_MAX_DOWN);
+      ZCHECK(rf_ratio_refused(w.L, w.M) == 0, "%s: record %d: a filtered row at ratio %d / %d (L <= %d and M <= %d L)", who, i, w.L, w.M, RF_MAX_L,
+             RF_MAX_DOWN);
       ZCHECK(rf_half_fits(w.L, w.M, w.half), "%s: record %d: half %d is no ceil(Z max(L, M) / L) for Z = 1 .. %d at %d / %d", who, i, w.half,
              RF_MAX_Z, w.L, w.M);
       ZCHECK(w.half <= max_half, "%s: record %d: half %d, max_half is %d", who, i, w.half, max_half);
@@ -265,26 +224,13 @@ extern "C" int zeggs_live_frames_refiltered(const ZeggsFramesDims* d, int max_ha
       ZCHECK(w.outputs == want, "%s: record %d: %ld outputs disagree with n_out(%ld) - n_out(%ld) = %ld at %d / %d", who, i, w.outputs,
              w.n_in + w.count, w.n_in, want, w.L, w.M);
     }
-    if (w.count > 0) {
-      ZCHECK(w.pose != nullptr && (uintptr_t)w.pose % 4 == 0 && w.rpos != nullptr && (uintptr_t)w.rpos % 4 == 0 && w.rrot != nullptr &&
-                 (uintptr_t)w.rrot % 4 == 0, "%s: record %d: NULL or misaligned source", who, i);
-      ZCHECK(w.pose_ld >= fr_pose_floats_read(J) && w.rpos_ld >= 3 && w.rrot_ld >= 4,
-             "%s: record %d: leading dimensions %ld, %ld, %ld (at least %d, 3, 4 floats)", who, i, w.pose_ld, w.rpos_ld, w.rrot_ld,
-             fr_pose_floats_read(J));
-    }
+    if (w.count > 0) ZTRY(fh_sources_ok(who, i, w, J));
     if (w.count == 0 && !(filtered && w.final)) continue;
-    if (w.outputs > 0) {
-      ZCHECK(!(d->what & FR_LOCAL) || (w.local != nullptr && (uintptr_t)w.local % 4 == 0), "%s: record %d: NULL or misaligned LOCAL destination",
-             who, i);
-      ZCHECK(!(d->what & FR_WORLD) || (w.world != nullptr && (uintptr_t)w.world % 4 == 0), "%s: record %d: NULL or misaligned WORLD destination",
-             who, i);
-      ZCHECK(!(d->what & FR_BVH) || (w.bvh != nullptr && (uintptr_t)w.bvh % 8 == 0), "%s: record %d: NULL or misaligned BVH destination", who, i);
-    }
+    if (w.outputs > 0) ZTRY(fh_dests_ok(who, i, w, d->what));
     if (w.count > 0 || w.outputs > 0) work = true;
   }
   if (!work) return 0;
-  ZCHECK(rows_dev != nullptr || R == 1, "%s: %d records must also be in device memory (rows_dev)", who, R);
-  ZCHECK(rows_dev == nullptr || (uintptr_t)rows_dev % 8 == 0, "%s: misaligned rows_dev", who);
+  ZTRY(fh_rows_dev_ok(who, rows_dev, R));
   hipLaunchKernelGGL(live_refilter_k, dim3((unsigned)R), dim3(FR_THREADS), (size_t)rf_lds_bytes(J, d->max_frames), (hipStream_t)stream, *d, max_half,
                      rows_dev, rows[0], (char*)state);
   ZLAUNCH_CHECK("live_refilter");

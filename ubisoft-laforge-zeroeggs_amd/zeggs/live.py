@@ -525,29 +525,35 @@ def frames_placement(start_position, start_rotation):
     return pos, rot
 
 
+def frames_layout(N, J, mask):
+    """the packed block of N frames, the one place that states it: [BVH rows float64 [N][3 + 3J] | LOCAL float32 [N][7 + 7J] |
+    WORLD float32 [N][7J]], an area whose bit is off in `mask` missing -> ((bvh, local, world), bytes of the block): an area is
+    (its offset, its bytes a frame), or None where it is missing"""
+    areas, total = [], 0
+    for k, per in (("bvh", (3 + 3 * J) * 8), ("local", (7 + 7 * J) * 4), ("world", 7 * J * 4)):
+        areas.append((total, per) if mask & ops.FRAMES_WHAT[k] else None)
+        total += int(N) * per if areas[-1] else 0
+    return tuple(areas), total
+
+
 def frames_unpack(buf, counts, J, mask, copy=True):
-    """the packed block of one zeggs_live_frames call on the host (uint8) -> per record the dict of arrays.  The block:
-    [BVH rows float64 [N][3 + 3J] | LOCAL float32 [N][7 + 7J] | WORLD float32 [N][7J]], N = sum(counts), an area whose bit is off
-    in `mask` missing; record i owns rows sum(counts[:i]) .. of each."""
-    N, BL, LL, WL = int(sum(counts)), 3 + 3 * J, 7 + 7 * J, 7 * J
-    use = [bool(mask & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
-    o_loc = N * BL * 8 * use[0]
-    o_wld = o_loc + N * LL * 4 * use[1]
-    bvh = buf[:o_loc].view(np.float64).reshape(N, BL) if use[0] else None
-    loc = buf[o_loc:o_wld].view(np.float32).reshape(N, LL) if use[1] else None
-    wld = buf[o_wld:o_wld + N * WL * 4].view(np.float32).reshape(N, WL) if use[2] else None
+    """the packed block of one zeggs_live_frames call on the host (uint8, frames_layout) -> per record the dict of arrays;
+    N = sum(counts), record i owns rows sum(counts[:i]) .. of each area."""
+    N = int(sum(counts))
+    rows = lambda area, t: buf[area[0]:area[0] + N * area[1]].view(t).reshape(N, area[1] // np.dtype(t).itemsize) if area else None  # noqa: E731
+    bvh, loc, wld = (rows(area, t) for area, t in zip(frames_layout(N, J, mask)[0], (np.float64, np.float32, np.float32)))
     out, a = [], 0
     own = (lambda x: np.array(x)) if copy else (lambda x: x)
     for c in counts:
         o = {}
-        if use[1]:
+        if loc is not None:
             x = loc[a:a + c]
             o.update(root_pos=own(x[:, 0:3]), root_rot=own(x[:, 3:7]), lrot=own(x[:, 7:7 + 4 * J]).reshape(c, J, 4),
                      lpos=own(x[:, 7 + 4 * J:]).reshape(c, J, 3))
-        if use[2]:
+        if wld is not None:
             x = wld[a:a + c]
             o.update(gpos=own(x[:, :3 * J]).reshape(c, J, 3), grot=own(x[:, 3 * J:]).reshape(c, J, 4))
-        if use[0]:
+        if bvh is not None:
             o["bvh"] = own(bvh[a:a + c])
         out.append(o)
         a += c
@@ -562,9 +568,8 @@ def frames_cat(parts):
 
 
 def frames_block_bytes(N, J, mask):
-    """bytes of the packed block of N frames (frames_unpack)"""
-    per = sum(n for k, n in (("bvh", (3 + 3 * J) * 8), ("local", (7 + 7 * J) * 4), ("world", 7 * J * 4)) if mask & ops.FRAMES_WHAT[k])
-    return int(N) * per
+    """bytes of the packed block of N frames (frames_layout)"""
+    return frames_layout(N, J, mask)[1]
 
 
 class _FrameStaging:
@@ -931,22 +936,21 @@ class LiveServer:
             fc = self.frames_conf
             if 6 + 15 * len(fc["parents"]) != PO:
                 raise ValueError(f"LiveServer: frames has {len(fc['parents'])} joints, the decoder's pose rows hold {(PO - 6) // 15}")
-            # a record: a step's tick frames (+ frame 0 once), or what close() flushes in one decoder call
-            if self.retime_conf is None:
+            # a record: a step's tick frames (+ frame 0 once), or what close() flushes in one decoder call.  The head's form is
+            # chosen here and nowhere else: its entry points and its record type are the head object's (ops.LiveFrames)
+            rc, L, M = self.retime_conf, 1, 1
+            if rc is None:
                 self._fr = ops.LiveFrames(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
-                self._fr_stage = _FrameStaging(R, self._fr.d.max_frames, self._fr.J, fc["mask"], self.dev)
             else:                                    # a row's share of the blocks: what max_rate makes of a record's input frames
-                rc = self.retime_conf
                 if "filter" in rc:                   # the filter stage: every row's head runs through its kernel, half = 0 without
                     self._fr = ops.LiveRefilter(R, fc["parents"], self.tick + LOOKAHEAD + 1, rc["half_max"], rc["filter"], fc["mask"],
                                                 fc["order"], fc["seq"], self.dev)
                 else:
                     self._fr = ops.LiveRetime(R, fc["parents"], self.tick + LOOKAHEAD + 1, fc["mask"], fc["order"], fc["seq"], self.dev)
                 L, M = rc["ratio"]
-                # (a step's record never emits more than its input frames make at max_rate, filtered or not: the filter only
-                # delays; the tail record of close() has a block of its own, sized for it)
-                self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev,
-                                               ops.RefilterRow if "filter" in rc else ops.RetimeRow)
+            # (a step's record never emits more than its input frames make at max_rate, filtered or not: the filter only
+            # delays; the tail record of close() has a block of its own, sized for it)
+            self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev, self._fr.record)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -1092,12 +1096,10 @@ class LiveServer:
             J = self._fr.J
             p0, r0 = f32(root_pos).reshape(1, 3), f32(root_rot).reshape(1, 4)
             row.rt = rt
-            reset = (ops.live_frames_reset if rt is None else ops.live_refilter_reset if isinstance(self._fr, ops.LiveRefilter)
-                     else ops.live_retime_reset)
             if place is None:
-                reset(self._fr, r)
+                ops.live_head_reset(self._fr, r)
             else:
-                reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
+                ops.live_head_reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
             pos0, _ = anim.bvh_channels(p0, r0, pose0[:, 6:6 + 3 * J].reshape(1, J, 3), pose0[:, 6 + 3 * J:6 + 9 * J].reshape(1, J, 2, 3),
                                         *(place or (None, None)), order=self.frames_conf["order"])
             row.offsets = pos0[0].cpu().numpy()
@@ -1126,6 +1128,32 @@ class LiveServer:
         for o, piece in zip(outs, anim.format_rows_device(table, cuts)):
             o["text"] = bytes(piece)
 
+    @staticmethod
+    def _frames_records(recs, rows, rts, srcs, i, counts, outputs, final, base, areas, a=0):
+        """fills the head records of ONE launch: record k brings counts[k] input frames of row rows[k] from frame i of its output
+        tensors srcs[k] (float32 rows) and emits behind the records before it, the first behind output frame `a` of the packed
+        block at the device address `base` (`areas`: frames_layout).  On a re-timing server -- rts[k] is the row's dict -- also the
+        ratio, the input counter and outputs[k], which the caller has from _emitted; with the filter stage -- the dict carries
+        half -- also the row's half and table, and `final`.  -> the output frame behind the last record"""
+        bvh, loc, wld = areas
+        for q, r, rt, o, count, outs in zip(recs, rows, rts, srcs, counts, outputs):
+            pose, rpos, rrot = o["pose"], o["rpos"], o["rrot"]
+            ld = q.pose_ld, q.rpos_ld, q.rrot_ld = pose.stride(0), rpos.stride(0), rrot.stride(0)
+            q.pose, q.rpos, q.rrot = pose.data_ptr() + 4 * i * ld[0], rpos.data_ptr() + 4 * i * ld[1], rrot.data_ptr() + 4 * i * ld[2]
+            q.bvh = base + bvh[0] + a * bvh[1] if bvh else None
+            q.local = base + loc[0] + a * loc[1] if loc else None
+            q.world = base + wld[0] + a * wld[1] if wld else None
+            q.row, q.count = r, count
+            if rt is None:
+                a += count
+                continue
+            q.L, q.M, q.n_in, q.outputs = rt["L"], rt["M"], rt["n_in"] + i, outs
+            if "half" in rt:
+                half = q.half = rt["half"]
+                q.final, q.table = final, rt["table"].data_ptr() if half else None
+            a += outs
+        return a
+
     def _frames_step(self, out, live):
         """the output head of a step: out[sid]["frames"] for the rows `live`, from the tensors out[sid] holds -- ONE launch and
         ONE download whatever their number"""
@@ -1135,37 +1163,16 @@ class LiveServer:
         rts = [self._rows[r].rt for r in live] if self.retime_conf is not None else None
         # a re-timing server: a record emits what the counting rule gives its row for these input frames
         counts = n_in if rts is None else [self._emitted(t, t["n_in"] + c, False) - t["n_out"] for t, c in zip(rts, n_in)]
-        filt = isinstance(fr, ops.LiveRefilter)
         N, J = sum(counts), fr.J
-        use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
-        base = stg.dev.data_ptr()
-        o_loc = N * fr.bvh_doubles * 8 * use[0]
-        o_wld = o_loc + N * fr.local_floats * 4 * use[1]
-        a = 0
-        for i, (q, r, o, c) in enumerate(zip(stg.recs, live, src, counts)):
-            q.pose, q.rpos, q.rrot = o["pose"].data_ptr(), o["rpos"].data_ptr(), o["rrot"].data_ptr()
-            q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
-            q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
-            q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
-            q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
-            q.row, q.count = r, n_in[i]
-            if rts is not None:
-                q.L, q.M, q.n_in, q.outputs = rts[i]["L"], rts[i]["M"], rts[i]["n_in"], c
-                if filt:
-                    q.half, q.final = rts[i]["half"], 0
-                    q.table = rts[i]["table"].data_ptr() if q.half else None
-            a += c
-        nbytes = frames_block_bytes(N, J, fc["mask"])
-        if rts is None:
-            ops.live_frames(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
-        else:
-            (ops.live_frames_refiltered if filt else ops.live_frames_retimed)(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
+        areas, nbytes = frames_layout(N, J, fc["mask"])
+        self._frames_records(stg.recs, live, rts or [None] * len(live), src, 0, n_in, counts, 0, stg.dev.data_ptr(), areas)
+        ops.live_head_launch(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
         # (a step in which no row of a re-timing server emits a frame has nothing to bring down; it counts as if it had)
         got = frames_unpack(stg.download(nbytes) if N else np.zeros(0, np.uint8), counts, J, fc["mask"])
         self._ops += 2
         self.stats["frame_bytes"] += nbytes
         if fc["text"]:
-            self._frames_text(stg.dev[:o_loc].view(torch.float64).view(N, fr.bvh_doubles), counts, got)
+            self._frames_text(stg.dev[:N * areas[0][1]].view(torch.float64).view(N, fr.bvh_doubles), counts, got)
             self._ops += 3                               # (the formatter's call and its two downloads: row ends, then the text)
         for i, (r, g) in enumerate(zip(live, got)):
             if rts is not None:
@@ -1187,40 +1194,21 @@ class LiveServer:
         a filtered stream: its last record is marked final and emits everything up to retime_n_out of all its input frames"""
         fr, fc, rt = self._fr, self.frames_conf, self._rows[r].rt
         n_in, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
-        filt = isinstance(fr, ops.LiveRefilter)
         n = n_in if rt is None else self._emitted(rt, rt["n_in"] + n_in, True) - rt["n_out"]
-        use = [bool(fc["mask"] & ops.FRAMES_WHAT[k]) for k in ("bvh", "local", "world")]
-        nbytes = frames_block_bytes(n, J, fc["mask"])
+        areas, nbytes = frames_layout(n, J, fc["mask"])
         block = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
-        o_loc = n * fr.bvh_doubles * 8 * use[0]
-        o_wld = o_loc + n * fr.local_floats * 4 * use[1]
-        rec = ((ops.FramesRow if rt is None else ops.RefilterRow if filt else ops.RetimeRow) * 1)()
-        q, base, a = rec[0], block.data_ptr(), 0          # a: output frames written so far
-        for i in range(0, max(n_in, 1 if filt and rt["half"] else 0), M):       # (a filtered stream: the final record, even an empty one)
-            q.pose, q.rpos, q.rrot = o["pose"][i:].data_ptr(), o["rpos"][i:].data_ptr(), o["rrot"][i:].data_ptr()
-            q.pose_ld, q.rpos_ld, q.rrot_ld = o["pose"].stride(0), o["rpos"].stride(0), o["rrot"].stride(0)
-            q.bvh = base + a * fr.bvh_doubles * 8 if use[0] else None
-            q.local = base + o_loc + a * fr.local_floats * 4 if use[1] else None
-            q.world = base + o_wld + a * fr.world_floats * 4 if use[2] else None
-            q.row, q.count = r, min(M, n_in - i)
-            if rt is None:
-                ops.live_frames(fr, rec, 1)
-                a += q.count
-            else:
-                q.L, q.M, q.n_in = rt["L"], rt["M"], rt["n_in"] + i
-                if filt:
-                    q.half, q.final = rt["half"], int(i + M >= n_in)
-                    q.table = rt["table"].data_ptr() if q.half else None
-                    q.outputs = self._emitted(rt, q.n_in + q.count, q.final) - self._emitted(rt, q.n_in, False)
-                    ops.live_frames_refiltered(fr, rec, 1)
-                else:
-                    q.outputs = ops.retime_n_out(q.n_in + q.count, q.L, q.M) - ops.retime_n_out(q.n_in, q.L, q.M)
-                    ops.live_frames_retimed(fr, rec, 1)
-                a += q.outputs
+        rec = (fr.record * 1)()
+        base, a = block.data_ptr(), 0                    # a: output frames written so far
+        for i in range(0, max(n_in, 1 if rt is not None and rt.get("half", 0) else 0), M):       # (a filtered stream: the final record, even an empty one)
+            count, final, outputs = min(M, n_in - i), int(i + M >= n_in), None
+            if rt is not None:
+                outputs = self._emitted(rt, rt["n_in"] + i + count, final) - self._emitted(rt, rt["n_in"] + i, False)
+            a = self._frames_records(rec, (r,), (rt,), (o,), i, (count,), (outputs,), final, base, areas, a)
+            ops.live_head_launch(fr, rec, 1)
         got = frames_unpack(block.cpu().numpy(), [n], J, fc["mask"])
         self.stats["frame_bytes"] += nbytes
         if fc["text"]:
-            self._frames_text(block[:o_loc].view(torch.float64).view(n, fr.bvh_doubles), [n], got)
+            self._frames_text(block[:n * areas[0][1]].view(torch.float64).view(n, fr.bvh_doubles), [n], got)
         if rt is not None:
             got[0]["frame0"] = rt["n_out"]
             rt["n_in"], rt["n_out"] = rt["n_in"] + n_in, rt["n_out"] + n

@@ -1096,7 +1096,11 @@ class LiveFrames:
     tables (`parents`, and `seq`, the joint order of the BVH rows: frames_seq(parents) unless given) and per row the placement
     and the quaternions last emitted.  `what`: names or the bit mask; `order`: "zyx" or "xzy"."""
 
-    state_bytes, prepare = "zeggs_live_frames_state_bytes", "zeggs_live_frames_prepare"      # (LiveRetime: the sixth header's)
+    # the form's entry points and its record (LiveRetime: the sixth header's, LiveRefilter: the seventh's) -- read by the constructor,
+    # live_head_reset, live_head_launch and live_frames_spans; a server asks the head object, never which form it is
+    state_bytes, prepare = "zeggs_live_frames_state_bytes", "zeggs_live_frames_prepare"
+    reset, launch, spans = "zeggs_live_frames_reset", "zeggs_live_frames", "zeggs_live_frames_spans"
+    record = FramesRow
     extra = ()                                   # what the entry points take behind the dims (LiveRefilter: max_half)
 
     def __init__(self, rows, parents, max_frames, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
@@ -1117,21 +1121,30 @@ class LiveFrames:
         self.local_floats, self.world_floats, self.bvh_doubles = 7 + 7 * self.J, 7 * self.J, 3 + 3 * self.J
 
 
-def live_frames_reset(lf, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
-    """zeggs_live_frames_reset: the row's next frame is the first of a stream; with a placement (all four given) the root is
-    re-based: start_rot ref_rot^-1 (x - ref_pos) + start_pos"""
+def live_head_reset(lf, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
+    """the reset of lf's form (zeggs_live_frames_reset / zeggs_live_retime_reset / zeggs_live_refilter_reset): the row's next input
+    frame is the first of a stream; with a placement (all four given) the root is re-based: start_rot ref_rot^-1 (x - ref_pos) +
+    start_pos"""
     place = [ref_pos, ref_rot, start_pos, start_rot]
+    reset = getattr(api(), lf.reset)
     if all(p is None for p in place):
-        api().zeggs_live_frames_reset(lf.d, lf.state, lf.state.numel(), int(row), None, None, None, None, 0, _stream())
+        reset(lf.d, *lf.extra, lf.state, lf.state.numel(), int(row), None, None, None, None, 0, _stream())
         return
     arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
-    api().zeggs_live_frames_reset(lf.d, lf.state, lf.state.numel(), int(row), *arrs, 1, _stream())
+    reset(lf.d, *lf.extra, lf.state, lf.state.numel(), int(row), *arrs, 1, _stream())
 
 
-def live_frames(lf, rows, n, rows_dev=None):
-    """zeggs_live_frames: rows[:n] a HOST array of FramesRow (device addresses inside), `rows_dev` the device address of a copy of
-    the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
-    api().zeggs_live_frames(lf.d, rows, _records(FramesRow, rows_dev), int(n), lf.state, lf.state.numel(), _stream())
+def live_head_launch(lf, rows, n, rows_dev=None):
+    """the launch of lf's form (zeggs_live_frames / zeggs_live_frames_retimed / zeggs_live_frames_refiltered): rows[:n] a HOST array
+    of lf.record (device addresses inside; the re-timing forms: the caller's counters; the filtered form: half = 0 for a row
+    without the filter), `rows_dev` the device address of a copy of the same records (None: one record, in the kernel arguments):
+    ONE launch for all of them"""
+    getattr(api(), lf.launch)(lf.d, *lf.extra, rows, _records(lf.record, rows_dev), int(n), lf.state, lf.state.numel(), _stream())
+
+
+# the names of the three headers' calls: the form is the head object's
+live_frames_reset = live_retime_reset = live_refilter_reset = live_head_reset
+live_frames = live_frames_retimed = live_frames_refiltered = live_head_launch
 
 
 RETIME_MAX_TERM, RETIME_MAX_UP = 4096, 8         # csrc/retime_math.h: 1 <= L, M <= 4096 and L / M <= 8
@@ -1187,22 +1200,8 @@ class LiveRetime(LiveFrames):
     frames of a record."""
 
     state_bytes, prepare = "zeggs_live_retime_state_bytes", "zeggs_live_retime_prepare"
-
-
-def live_retime_reset(lr, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
-    """zeggs_live_retime_reset: the row's next input frame is frame 0 of a stream; the placement as live_frames_reset"""
-    place = [ref_pos, ref_rot, start_pos, start_rot]
-    if all(p is None for p in place):
-        api().zeggs_live_retime_reset(lr.d, lr.state, lr.state.numel(), int(row), None, None, None, None, 0, _stream())
-        return
-    arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
-    api().zeggs_live_retime_reset(lr.d, lr.state, lr.state.numel(), int(row), *arrs, 1, _stream())
-
-
-def live_frames_retimed(lr, rows, n, rows_dev=None):
-    """zeggs_live_frames_retimed: rows[:n] a HOST array of RetimeRow (device addresses, the caller's counters), `rows_dev` the device
-    address of a copy of the same records (None: one record, in the kernel arguments): ONE launch for all of them"""
-    api().zeggs_live_frames_retimed(lr.d, rows, _records(RetimeRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
+    reset, launch, spans = "zeggs_live_retime_reset", "zeggs_live_frames_retimed", "zeggs_live_retime_spans"
+    record = RetimeRow
 
 
 REFILTER_MAX_L, REFILTER_MAX_DOWN, REFILTER_MAX_Z = 1024, 4, 8        # csrc/refilter_math.h: a filtered row has L <= 1024, M <= 4 L
@@ -1264,6 +1263,8 @@ class LiveRefilter(LiveFrames):
     on the device (`options`: refilter_options).  `max_frames` bounds the INPUT frames of a record, `max_half` the H of a row."""
 
     state_bytes, prepare = "zeggs_live_refilter_state_bytes", "zeggs_live_refilter_prepare"
+    reset, launch, spans = "zeggs_live_refilter_reset", "zeggs_live_frames_refiltered", "zeggs_live_refilter_spans"
+    record = RefilterRow
 
     def __init__(self, rows, parents, max_frames, max_half, options=None, what=("local", "world", "bvh"), order="zyx", seq=None, device="cuda"):
         self.max_half, self.options = int(max_half), refilter_options(options)
@@ -1281,23 +1282,6 @@ class LiveRefilter(LiveFrames):
                 raise ValueError(f"refilter: the ratio {key[0]} / {key[1]} needs {H} input frames to either side, max_half is {self.max_half}")
             self.tables[key] = dict(table=torch.as_tensor(tab).to(self.state.device).contiguous(), half=H)
         return self.tables[key]
-
-
-def live_refilter_reset(lr, row, ref_pos=None, ref_rot=None, start_pos=None, start_rot=None):
-    """zeggs_live_refilter_reset: the row's next input frame is frame 0 of a stream; the placement as live_frames_reset"""
-    place = [ref_pos, ref_rot, start_pos, start_rot]
-    if all(p is None for p in place):
-        api().zeggs_live_refilter_reset(lr.d, lr.max_half, lr.state, lr.state.numel(), int(row), None, None, None, None, 0, _stream())
-        return
-    arrs = [(t * n)(*[float(v) for v in p]) for p, t, n in zip(place, (C.c_float, C.c_float, C.c_double, C.c_double), (3, 4, 3, 4))]
-    api().zeggs_live_refilter_reset(lr.d, lr.max_half, lr.state, lr.state.numel(), int(row), *arrs, 1, _stream())
-
-
-def live_frames_refiltered(lr, rows, n, rows_dev=None):
-    """zeggs_live_frames_refiltered: rows[:n] a HOST array of RefilterRow (device addresses, the caller's counters, half = 0 for a
-    row without the filter), `rows_dev` the device address of a copy of the same records (None: one record, in the kernel
-    arguments): ONE launch for all of them"""
-    api().zeggs_live_frames_refiltered(lr.d, lr.max_half, rows, _records(RefilterRow, rows_dev), int(n), lr.state, lr.state.numel(), _stream())
 
 
 SNAP_MAX_SPANS, SNAP_MAX_SEGMENTS = 2, 65535       # ZEGGS_SNAP_MAX_SPANS / ZEGGS_SNAP_MAX_SEGMENTS
@@ -1323,10 +1307,7 @@ def live_resample_spans(rs, row):
 def live_frames_spans(lf, row):
     """zeggs_live_frames_spans / zeggs_live_retime_spans / zeggs_live_refilter_spans, by the head's form: where row `row` lives in
     lf.state -> [(offset, bytes)] (the skeleton tables in front of the rows are derived, not state: in no span)"""
-    L = api()
-    fn = (L.zeggs_live_refilter_spans if isinstance(lf, LiveRefilter) else L.zeggs_live_retime_spans if isinstance(lf, LiveRetime)
-          else L.zeggs_live_frames_spans)
-    return _spans(fn, lf.d, *lf.extra, int(row))
+    return _spans(getattr(api(), lf.spans), lf.d, *lf.extra, int(row))
 
 
 def live_pack(segs, n, segs_dev, blob, blob_bytes):
