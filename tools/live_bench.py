@@ -60,6 +60,11 @@
   plain one, each timed by itself.  Both columns and their ratio, median and p95 of step() for both (the claim to check: the bank
   server's median lies within the plain server's own spread), and at 1 row add_style() of a 600-frame and a 7 200-frame
   exemplar beside the tick -> profiles/live_styles.json.
+  --leg plant: what feet that stay planted cost a step, per rows in {1, 8, 32, 64}: a server without the head, a plain-head server
+  and a planting server (frames=..., plant=... with thresholds the test networks' motion meets, so that chains are held and
+  solved) in ONE process, brought to 10 s on the same signals, then fed the same chunks tick by tick, taking turns at going
+  first.  Median and p95 of step() for the three, the stage's added cost beside the head's own (head minus no head), the share
+  of contact flags that were set, what each enqueues per step -> profiles/live_plant.json.
 
 Every case is a child process under its own `timeout`; the first one that fails ends the run (as a chain of `&&` would).
 
@@ -73,6 +78,7 @@ Every case is a child process under its own `timeout`; the first one that fails 
     python tools/live_bench.py --leg snapshot [--out profiles/live_snapshot.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg gaze [--out profiles/live_gaze.json] [--steps 200] [--rows 1,8,32,64]
     python tools/live_bench.py --leg styles [--out profiles/live_styles.json] [--steps 200] [--rows 1,8,32,64]
+    python tools/live_bench.py --leg plant [--out profiles/live_plant.json] [--steps 200] [--rows 1,8,32,64]
 """
 import argparse
 import json
@@ -495,6 +501,58 @@ def case_gaze(rows, steps, age=10):
                 launches_per_step={k: sorted(ops_seen[k]) for k in names}, ops_per_set_gaze_many=srv["gaze"].stats["ops_last_set_gaze"])
 
 
+# thresholds the test networks' motion meets now and then (NOT a tuning for captured motion): chains are held, solved and released
+PLANT_BENCH = dict(chains="auto", speed=(60.0, 120.0), height=(1e6, 2e6), ground=0.0, slack=3.0, release=5, stretch=0.999)
+
+
+def case_plant(rows, steps, age=10):
+    """step() of a server without the head, of a plain-head server and of a planting server: three servers in ONE process, the
+    same rows' signals up to `age` (1 s push_many calls, drained), then tick by tick, taking turns at going first"""
+    import torch
+    from zeggs import live, synth
+    se, de, stats, first, base = _setup()
+    gen = torch.Generator("cpu").manual_seed(0)
+    styles = [torch.randn(1, 64, generator=gen) * 0.5 for _ in range(rows)]
+    head = dict(parents=synth.PARENTS, names=synth.BONE_NAMES, what=("local", "world", "bvh"), order="zyx", text=False)
+    srv = {"no head": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK),
+           "head": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, frames=head),
+           "plant": live.LiveServer(se, de, stats, CONF, synth.DT, rows=rows, tick=TICK, frames=head, plant=PLANT_BENCH)}
+    sids = {k: [srv[k].open(first, st) for st in styles] for k in srv}
+    pos = 0
+    while pos < age * FS:
+        for k in srv:
+            srv[k].push_many({sid: _samples(base, r, pos, pos + FS) for r, sid in enumerate(sids[k])})
+            srv[k].drain()
+        pos += FS
+    torch.cuda.synchronize()
+    names = list(srv)
+    t, ops_seen, i, flags, held = {k: [] for k in names}, {k: set() for k in names}, 0, 0, 0
+    while len(t["head"]) < steps:
+        i += 1
+        nxt = age * FS + int(round(i * TICK * FS / FPS))
+        chunks = [_samples(base, r, pos, nxt) for r in range(rows)]
+        for k in names[i % 3:] + names[:i % 3]:
+            srv[k].push_many(dict(zip(sids[k], chunks)))
+            while True:
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                out = srv[k].step()
+                torch.cuda.synchronize()
+                dt = time.perf_counter() - t0
+                if not out:
+                    break
+                assert len(out) == rows
+                t[k].append(dt)
+                ops_seen[k].add(srv[k].stats["launches_per_step"])
+                if k == "plant":
+                    for o in out.values():
+                        flags, held = flags + o["contacts"].size, held + int(o["contacts"].sum())
+        pos = nxt
+    assert all(len(v) == 1 for v in ops_seen.values()) and max(ops_seen["plant"]) == max(ops_seen["head"]) + 1, ops_seen
+    return dict(kind="plant", rows=rows, age_s=age, tick=TICK, step={k: _summary(t[k]) for k in names}, contact_share=round(held / max(flags, 1), 4),
+                launches_per_step={k: sorted(ops_seen[k]) for k in names})
+
+
 def case_styles(rows, steps, age=10):
     """what named styles cost: a plain server and one with a style bank in ONE process, the same rows' signals up to `age` (1 s
     push_many calls, drained), then tick by tick, taking turns at going first.  Every tick every row gets a new style: on the
@@ -724,10 +782,10 @@ def main():
     ap.add_argument("--rows", default="1,8,32,64")
     ap.add_argument("--ages", default="10,600")
     ap.add_argument("--limit", type=int, default=420, help="seconds per case")
-    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot", "gaze", "styles"))
+    ap.add_argument("--leg", default="step", choices=("step", "push_many", "loudness", "resample", "frames", "retime", "refilter", "snapshot", "gaze", "styles", "plant"))
     ap.add_argument("--loudness", action="store_true", help="the same as --leg loudness")
     ap.add_argument("--case", default=None,
-                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64, snapshot:64, gaze:64 or styles:64")
+                    help="internal: one case in a child process, e.g. server:8:10, baseline:600, push_many:64, loudness:64:600, resample:64:600, frames:64:600, retime:64, refilter:64, snapshot:64, gaze:64, styles:64 or plant:64")
     a = ap.parse_args()
     if a.loudness:
         a.leg = "loudness"
@@ -742,7 +800,8 @@ def main():
                case_refilter(int(rest[0]), a.steps) if kind == "refilter" else
                case_snapshot(int(rest[0]), a.steps) if kind == "snapshot" else
                case_gaze(int(rest[0]), a.steps) if kind == "gaze" else
-               case_styles(int(rest[0]), a.steps) if kind == "styles" else case_baseline(int(rest[0]), a.steps))
+               case_styles(int(rest[0]), a.steps) if kind == "styles" else
+               case_plant(int(rest[0]), a.steps) if kind == "plant" else case_baseline(int(rest[0]), a.steps))
         print("RESULT " + json.dumps(res), flush=True)
         return 0
     ages, rows = [int(x) for x in a.ages.split(",")], [int(x) for x in a.rows.split(",")]
@@ -783,6 +842,10 @@ def main():
         cases = [f"styles:{r}" for r in rows]
         if a.out == ap.get_default("out"):
             a.out = str(ROOT / "profiles" / "live_styles.json")
+    if a.leg == "plant":
+        cases = [f"plant:{r}" for r in rows]
+        if a.out == ap.get_default("out"):
+            a.out = str(ROOT / "profiles" / "live_plant.json")
     results = []
     for c in cases:                 # each GPU case under its own time limit; the first failure ends the run
         cmd = ["timeout", "-k", "10", str(a.limit), sys.executable, str(Path(__file__).resolve()), "--case", c, "--steps", str(a.steps)]
@@ -910,6 +973,21 @@ def main():
                                               launches_per_step=r["launches_per_step"])
         rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
                    ticks_per_case=a.steps, step_without_and_with_the_moving_gaze=table, results=results)
+        Path(a.out).parent.mkdir(parents=True, exist_ok=True)
+        Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
+        print(f"wrote {a.out}")
+        return 0
+    if a.leg == "plant":
+        table = {}
+        for r in results:
+            off, head, pl = (r["step"][k] for k in ("no head", "head", "plant"))
+            own, added = round(head["median_ms"] - off["median_ms"], 4), round(pl["median_ms"] - head["median_ms"], 4)
+            table[f"{r['rows']} rows"] = dict(step_no_head_median_ms=off["median_ms"], step_head_median_ms=head["median_ms"], step_head_p95_ms=head["p95_ms"],
+                                              step_plant_median_ms=pl["median_ms"], step_plant_p95_ms=pl["p95_ms"], head_own_ms=own, plant_added_ms=added,
+                                              plant_added_exceeds_the_heads_own=added > own, contact_share=r["contact_share"],
+                                              launches_per_step=r["launches_per_step"])
+        rec = dict(command="python tools/live_bench.py " + " ".join(sys.argv[1:]), device=torch.cuda.get_device_name(0), tick_frames=TICK,
+                   ticks_per_case=a.steps, step_without_the_head_with_it_and_with_planted_feet=table, results=results)
         Path(a.out).parent.mkdir(parents=True, exist_ok=True)
         Path(a.out).write_text(json.dumps(rec, indent=1) + "\n")
         print(f"wrote {a.out}")

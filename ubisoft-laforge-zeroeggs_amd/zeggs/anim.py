@@ -329,6 +329,44 @@ def bvh_channels(root_pos, root_rot, lpos, ltxy, start_position=None, start_rota
     return positions, euler
 
 
+def plant_stage(parents, names, dt, device="cuda", max_frames=4096, **options):
+    """a fresh one-row planting state (ops.LivePlant, reset) for plant_feet(..., stage=): what carries a clip's contact state from
+    one piece of it to the next.  `options`: the keys of ops.PLANT_DEFAULTS (ops.plant_options checks them)."""
+    conf = ops.plant_options(dict(options), parents, names)
+    stage = ops.LivePlant(1, parents, max_frames, conf, dt, device)
+    ops.live_plant_reset(stage, 0)
+    return stage
+
+
+def plant_feet(pose, rpos, rrot, parents, names, dt, stage=None, **options):
+    """feet that stay planted (include/zeggs_hip_plant.h): the decoder's rows of a whole clip -- pose [T, 6 + 15J], rpos
+    [T, 3], rrot [T, 4], float32 on the device -- through the contact lock and the leg IK, on the device -> (planted pose
+    [T, 6 + 15J] float32: the ltxy of the chains' joints corrected, every other float the same bits; contacts [T, chains] uint8).
+    `options`: chains="auto" | [(upper leg, lower leg, foot)] by name or index, speed=(v_on, v_off), height=(h_on, h_off), ground,
+    slack, release, stretch (ops.PLANT_DEFAULTS: NOT tuned on captured motion).  A fresh one-row state a call; with `stage`
+    (plant_stage) the state of the piece before is carried on and `options` are the stage's."""
+    if stage is None:
+        stage = plant_stage(parents, names, dt, pose.device, **options)
+    elif options:
+        raise ValueError("plant_feet: a stage carries its own options")
+    f = lambda t: t.detach().to(torch.float32).contiguous()  # noqa: E731
+    pose, rpos, rrot = f(pose), f(rpos), f(rrot)
+    T, PO = int(pose.shape[0]), stage.pose_floats
+    if pose.dim() != 2 or pose.shape[1] != PO or tuple(rpos.shape) != (T, 3) or tuple(rrot.shape) != (T, 4):
+        raise ValueError(f"plant_feet: pose [T, {PO}], rpos [T, 3], rrot [T, 4] for {stage.J} joints, not {tuple(pose.shape)}, {tuple(rpos.shape)}, "
+                         f"{tuple(rrot.shape)}")
+    out = torch.empty_like(pose)
+    contacts = torch.zeros(T, stage.C, dtype=torch.uint8, device=pose.device)
+    rec, M = (ops.PlantRow * 1)(), stage.d.max_frames
+    for i in range(0, T, M):
+        q = rec[0]
+        q.pose, q.rpos, q.rrot = pose.data_ptr() + 4 * i * PO, rpos.data_ptr() + 12 * i, rrot.data_ptr() + 16 * i
+        q.out, q.contacts = out.data_ptr() + 4 * i * PO, contacts.data_ptr() + i * stage.C
+        q.pose_ld, q.rpos_ld, q.rrot_ld, q.out_ld, q.row, q.count = PO, 3, 4, PO, 0, min(M, T - i)
+        ops.live_plant(stage, rec, 1)
+    return out, contacts
+
+
 def write_bvh(filename, root_pos, root_rot, lpos, ltxy, parents, names, order, dt, start_position=None,
               start_rotation=None, text=None):
     """reference utils.write_bvh, fed with the decoder's two-axis rotations (the quaternion / euler conversion of

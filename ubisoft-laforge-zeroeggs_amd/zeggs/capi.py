@@ -17,7 +17,8 @@ include/zeggs_hip_frames.h, FR_STRUCTS / FR_PROTOTYPES (tests/test_live_frames_c
 RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py), the seventh, include/zeggs_hip_refilter.h, RF_STRUCTS / RF_PROTOTYPES
 (tests/test_live_refilter_cpu.py), the eighth, include/zeggs_hip_snapshot.h, SNAP_STRUCTS / SNAP_PROTOTYPES
 (tests/test_live_snapshot_cpu.py), the ninth, include/zeggs_hip_gaze.h, GZ_STRUCTS / GZ_PROTOTYPES (tests/test_live_gaze_cpu.py),
-the tenth, include/zeggs_hip_styles.h, SB_STRUCTS / SB_PROTOTYPES (tests/test_live_styles_cpu.py): same loader.  torch is imported when a tensor is first converted, not
+the tenth, include/zeggs_hip_styles.h, SB_STRUCTS / SB_PROTOTYPES (tests/test_live_styles_cpu.py), the eleventh,
+include/zeggs_hip_plant.h, PL_STRUCTS / PL_PROTOTYPES (tests/test_live_plant_cpu.py): same loader.  torch is imported when a tensor is first converted, not
 when this module is.
 """
 import ctypes as C
@@ -372,6 +373,23 @@ SB_PROTOTYPES = {
 }
 
 
+# ----------------------------------------------------------------------------- the eleventh header (include/zeggs_hip_plant.h)
+# Feet that stay planted: contact lock and leg IK for live rows (tests/test_live_plant_cpu.py compares these tables with the header).
+PlantDims = _struct("PlantDims", [(C.c_int, "rows J max_frames chains release pad"), (C.c_double, "dt v_on v_off h_on h_off ground slack stretch")])
+PlantRow = _struct("PlantRow", [(C.c_void_p, "pose rpos rrot out contacts"), (C.c_long, "pose_ld rpos_ld rrot_ld out_ld"), (C.c_int, "row count")])
+PL_STRUCTS = {"ZeggsPlantDims": PlantDims, "ZeggsPlantRow": PlantRow}
+PL_PROTOTYPES = {
+    "zeggs_live_plant_version": "int:",
+    "zeggs_live_plant_state_bytes": "size_t: ZeggsPlantDims*",
+    # parents / chains: HOST arrays of int
+    "zeggs_live_plant_prepare": "status: ZeggsPlantDims* host* host* any* size_t stream",
+    "zeggs_live_plant_reset": "status: ZeggsPlantDims* any* size_t int stream",
+    "zeggs_live_plant_spans": "mask: ZeggsPlantDims* int ZeggsSnapSpan* int",
+    # recs_host / recs_dev as in zeggs_live_frames
+    "zeggs_live_plant": "status: ZeggsPlantDims* ZeggsPlantRow* ZeggsPlantRow* int any* size_t stream",
+}
+
+
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
     """A device-pointer parameter: takes a tensor (on a GPU, contiguous, one of `dtypes`), None, a c_void_p or an address."""
@@ -410,14 +428,14 @@ KINDS = {"int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "uint64": C.c_u
          "f32*": _device_pointer("f32_p", ("float32",)), "f64*": _device_pointer("f64_p", ("float64",)),
          "i32*": _device_pointer("i32_p", ("int32",)), "i64*": _device_pointer("i64_p", ("int64",)),
          "u8*": _device_pointer("u8_p", ("uint8", "bool")), "any*": _device_pointer("any_p", None)}
-KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS, **GZ_STRUCTS, **SB_STRUCTS}.items()})
+KINDS.update({name + "*": C.POINTER(cls) for name, cls in {**STRUCTS, **EXT_STRUCTS, **LOUD_STRUCTS, **RS_STRUCTS, **FR_STRUCTS, **RT_STRUCTS, **RF_STRUCTS, **SNAP_STRUCTS, **GZ_STRUCTS, **SB_STRUCTS, **PL_STRUCTS}.items()})
 RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long, "size_t": C.c_size_t, "str": C.c_char_p}
 
 
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES.get(name) or SB_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES.get(name) or SB_PROTOTYPES.get(name) or PL_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -455,7 +473,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -467,7 +485,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

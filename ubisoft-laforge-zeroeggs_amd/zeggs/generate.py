@@ -78,7 +78,7 @@ STREAM_BLOCK = 512            # rows per formatting task (host threads; anim.TEX
 
 
 def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, style, stats, dt, path, parents, names,
-                             chunk=None, block=None, threads=None):
+                             chunk=None, block=None, threads=None, plant=None):
     """Long clips (configs[4]: 108 000 frames): the B = 1 rollout runs as a sequence of persistent launches of `chunk` frames,
     each resumed from the state of the one before (zeggs_decoder_fwd_state_ex); behind every chunk its frames are converted to
     the rows of the BVH motion block ON THE DEVICE (zeggs_pose_to_bvh_table) and formatted there (zeggs_table_text_device: what
@@ -88,7 +88,9 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
     re-association at the chunk boundaries (joint rotations a few hundredths of a degree apart after 700 free-running frames):
     tests/test_gpu_parity.py::test_generate_gesture_streaming_writer_equals_one_launch.  The decoder's frames are not kept
     (488 MB for 30 minutes).  Give-ups of the persistent kernel are collected in one status word that is looked at ONCE, after
-    the last chunk: then everything is redone on the stage launches."""
+    the last chunk: then everything is redone on the stage launches.
+    `plant` (the options of anim.plant_feet): every chunk's rows go through the planting stage between the decoder and the
+    conversion, the chains' contact state carried from chunk to chunk (anim.plant_stage); the decoder resumes from its raw rows."""
     import time as _t0
     from concurrent.futures import ThreadPoolExecutor
     from . import ops
@@ -127,6 +129,7 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
         """decode chunk by chunk; chunk c's text is written while chunks c + 1 .. c + RING - 1 are queued on the device"""
         stage.pool = pool
         pending = []                                     # per chunk in flight: the getters of its text, in row order
+        planting = None if plant is None else anim.plant_stage(parents, names, dt, dev, **plant)      # (a redo starts afresh)
         state = (pose0, rpos0, rrot0, None)
         k = 0                                            # last frame produced so far
 
@@ -153,6 +156,8 @@ def _decode_to_bvh_streaming(decoder, pose0, rpos0, rrot0, gaze_row, speech, sty
             # (named, not temporaries: a tensor freed between two argument expressions hands its block to the next one)
             P = pose[0, lo:]
             a_rpos, a_rrot = rpos[0, lo:].contiguous(), rrot[0, lo:].contiguous()
+            if planting is not None:                     # feet that stay planted: the conversion reads the corrected rows
+                P = anim.plant_feet(P, a_rpos, a_rrot, parents, names, dt, stage=planting)[0]
             a_lpos, a_ltxy = P[:, 6:6 + 3 * J].contiguous(), P[:, 6 + 3 * J:6 + 9 * J].contiguous()
             L.zeggs_pose_to_bvh_table(d, a_rpos, a_rrot, a_lpos, a_ltxy, ref_pos, ref_rot, seq_dev, table, main.cuda_stream)
             del a_rpos, a_rrot, a_lpos, a_ltxy
@@ -471,8 +476,9 @@ def _first_frame(feat):
     return pose0, g(root_pos), g(root_rot), g(feat[14])
 
 
-def _decode_one(ld, fe, audio_file, results_path, return_poses=False):
-    """decoder rollout of ONE clip (B = 1) + BVH / WAV files: the tail of generate_gesture()"""
+def _decode_one(ld, fe, audio_file, results_path, return_poses=False, plant=None):
+    """decoder rollout of ONE clip (B = 1) + BVH / WAV files: the tail of generate_gesture().  `plant`: the options of
+    anim.plant_feet (None: off) -- the planting stage between the decoder and the BVH conversion, on both paths"""
     in_mean, in_std, out_mean, out_std = ld.stats
     decoder, dt, parents, bone_names = ld.decoder, ld.dt, ld.parents, ld.bone_names
     speech, final, feat, file_name = fe["speech"], fe["final"], fe["feat"], fe["file_name"]
@@ -492,7 +498,7 @@ def _decode_one(ld, fe, audio_file, results_path, return_poses=False):
                 with _stage("decode+pose_to_bvh_device_with_bvh_text_write_host_underneath"):
                     _decode_to_bvh_streaming(decoder, pose0, g(root_pos), g(root_rot), g(gaze_pos), speech,
                                              final.contiguous(), (in_mean, in_std, out_mean, out_std), dt,
-                                             str(results_path / (file_name + ".bvh")), parents, bone_names)
+                                             str(results_path / (file_name + ".bvh")), parents, bone_names, plant=plant)
                 copier.result()
             except (PermissionError, OSError) as e:
                 print(e)
@@ -502,6 +508,12 @@ def _decode_one(ld, fe, audio_file, results_path, return_poses=False):
         out = decoder(g(root_pos), g(root_rot), g(root_vel), g(root_vrt), g(lpos), g(ltxy), g(lvel), g(lvrt),
                       gaze.contiguous(), speech, final.contiguous(), None, in_mean, in_std, out_mean, out_std, dt)
     V_root_pos, V_root_rot, _, _, V_lpos, V_ltxy = out[0], out[1], out[2], out[3], out[4], out[5]
+    if plant is not None:                                # feet that stay planted: the decoded rows through the stage, whole
+        with _stage("plant_feet_device"):
+            J = V_lpos.shape[2]
+            rows = torch.cat([o[0].reshape(T, -1) for o in out[2:8]], dim=1)
+            rows = anim.plant_feet(rows, V_root_pos[0], V_root_rot[0], parents, bone_names, dt, **plant)[0]
+            V_lpos, V_ltxy = rows[None, :, 6:6 + 3 * J].reshape(1, T, J, 3), rows[None, :, 6 + 3 * J:6 + 9 * J].reshape(1, T, J, 2, 3)
     try:
         with _stage("pose_to_bvh_device"):
             channels = anim.bvh_channels(V_root_pos[0], V_root_rot[0], V_lpos[0], V_ltxy[0], np.array([0, 0, 0]),
@@ -518,7 +530,12 @@ def _decode_one(ld, fe, audio_file, results_path, return_poses=False):
 
 def generate_gesture(audio_file, styles, network_path, data_path, results_path, style_encoding_type="example",
                      blend_type="add", blend_ratio=[0.5, 0.5], file_name=None, first_pose=None, temperature=1.0,
-                     seed=1234, use_gpu=True, use_script=False):
+                     seed=1234, use_gpu=True, use_script=False, plant=None):
+    """the reference's generate_gesture.  `plant` (not the reference's): None, True or dict(chains="auto", speed=(v_on, v_off),
+    height=(h_on, h_off), ground, slack, release, stretch) -- feet that stay planted (anim.plant_feet): the decoded
+    rows go through the contact lock and the leg IK on the device before they become the BVH file, on the one-launch path and
+    on the chunked long-clip path (the contact state carried from chunk to chunk).  The defaults are NOT tuned on captured
+    motion.  ValueError before anything is decoded for options or chains the skeleton does not have."""
     network_path, data_path = Path(network_path), Path(data_path)
     if results_path is not None:
         results_path = Path(results_path)
@@ -528,10 +545,16 @@ def generate_gesture(audio_file, styles, network_path, data_path, results_path, 
         raise RuntimeError("the ZeroEGGS MI355X engine has no CPU path (use_gpu=False / no GPU visible)")
     _seed_all(seed)
     ld = _Loaded(network_path, data_path, style_encoding_type, torch.device("cuda"))
+    if plant is not None and plant is not False:
+        from . import ops
+        ops.plant_options(plant, ld.parents, ld.bone_names)          # (checked here, ahead of the front end)
+        plant = {} if plant is True else dict(plant)
+    else:
+        plant = None
     with torch.no_grad():
         fe = _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature)
         if audio_file is not None:
-            _decode_one(ld, fe, audio_file, results_path)
+            _decode_one(ld, fe, audio_file, results_path, plant=plant)
     return fe["final"]
 
 

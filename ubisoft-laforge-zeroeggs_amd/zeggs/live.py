@@ -512,6 +512,20 @@ def retime_options(retime, frames_conf, fps):
     return dict(conf, filter=fopt, min_rate=lo, half_max=int(half_max))
 
 
+def plant_options(plant, frames_conf):
+    """LiveServer's `plant` argument -> None (off) or ops.plant_options' dict against the skeleton of `frames`: True is the
+    defaults (NOT tuned on captured motion), a dict overrides them.  ValueError for `plant` without `frames` and for whatever
+    ops.plant_options refuses, the chain named."""
+    if plant is None or plant is False:
+        return None
+    if frames_conf is None:
+        raise ValueError("LiveServer: plant corrects the rows the output head reads: it needs frames=dict(parents=...)")
+    try:
+        return ops.plant_options(plant, frames_conf["parents"], frames_conf["names"])
+    except ValueError as e:
+        raise ValueError(f"LiveServer: {e}") from None
+
+
 def frames_placement(start_position, start_rotation):
     """open()'s placement -> None (neither given: the root is handed out as it is) or (position [3], rotation [4], float64);
     ValueError when only one of the two is given or a shape is wrong"""
@@ -580,10 +594,15 @@ class _FrameStaging:
     records are rewritten only after the step that used them has waited for its download, which is ordered behind the launch."""
     RING = 3
 
-    def __init__(self, rows, max_frames, J, mask, dev, record=None):
+    def __init__(self, rows, max_frames, J, mask, dev, record=None, tail_bytes=0, tail_record=None):
         record = record or ops.FramesRow              # (the re-timing head: ops.RetimeRow, max_frames OUTPUT frames a row)
         self.J, self.mask = J, mask
-        self.nbytes = frames_block_bytes(rows * max_frames, J, mask)
+        # tail_bytes: room behind the three areas (a planting server: the contact flags of a step's model frames), and with
+        # tail_record the records of the stage in front of the head, staged as the head's are
+        self.nbytes = frames_block_bytes(rows * max_frames, J, mask) + int(tail_bytes)
+        if tail_record is not None:
+            self.tail_mem = torch.zeros(rows * C.sizeof(tail_record), dtype=torch.uint8).pin_memory()
+            self.tail_recs = (tail_record * rows).from_buffer(self.tail_mem.numpy())
         self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
         self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
         self.events, self.turn = [None] * self.RING, 0
@@ -619,6 +638,10 @@ SNAP_FINGERPRINT = ("tick", "fs", "fps", "mel_n_fft", "mel_hop", "mel_n_mels", "
                     "frames", "frames_joints", "frames_what", "frames_order", "frames_seq",
                     "retime", "retime_max_L", "retime_max_M", "filter", "filter_zero_crossings", "filter_rolloff", "filter_beta",
                     "filter_min_rate_num", "filter_min_rate_den", "filter_half_max")
+# a planting server's blobs carry these behind SNAP_FINGERPRINT (the header's field count says which kind a blob is); the blobs of
+# a server without `plant` are what they were
+SNAP_FINGERPRINT_PLANT = ("plant_chains", "plant_v_on", "plant_v_off", "plant_h_on", "plant_h_off", "plant_ground", "plant_slack",
+                          "plant_release", "plant_stretch")
 SNAP_SECTIONS = ("row", "offsets", "window", "feats", "ring", "h", "pose", "rpos", "rrot", "gaze", "sty_old", "sty_new", "loudness",
                  "resample", "head")
 # the `row` section, int64 each: the six counters, what _Row holds of the style fade, the converter and the output head, and how
@@ -629,11 +652,17 @@ _SNAP_HEAD = 8 + 4 + 4 + 8 + 4 + 4 + 8
 _a16 = lambda x: (int(x) + 15) // 16 * 16  # noqa: E731
 
 
-def snapshot_layout(sizes):
+def _snap_fields(fingerprint):
+    """the fingerprint fields a blob with this fingerprint carries: SNAP_FINGERPRINT, a planting server's also SNAP_FINGERPRINT_PLANT"""
+    return SNAP_FINGERPRINT + SNAP_FINGERPRINT_PLANT if SNAP_FINGERPRINT_PLANT[0] in fingerprint else SNAP_FINGERPRINT
+
+
+def snapshot_layout(sizes, n_fp=None):
     """bytes per section, in SNAP_SECTIONS' order -> (their offsets in the blob, the blob's length): the header, then every section
-    on the next 16-byte boundary"""
+    on the next 16-byte boundary.  `n_fp`: the fingerprint fields of the header (None: len(SNAP_FINGERPRINT))"""
     assert len(sizes) == len(SNAP_SECTIONS)
-    at, offs = _a16(_SNAP_HEAD + 8 * len(SNAP_FINGERPRINT) + 24 * len(SNAP_SECTIONS)), []
+    n_fp = len(SNAP_FINGERPRINT) if n_fp is None else int(n_fp)
+    at, offs = _a16(_SNAP_HEAD + 8 * n_fp + 24 * len(SNAP_SECTIONS)), []
     for b in sizes:
         offs.append(at)
         at = _a16(at + int(b))
@@ -641,11 +670,13 @@ def snapshot_layout(sizes):
 
 
 def snapshot_header(sid, version, fingerprint, sizes):
-    """the bytes in front of the first section: `fingerprint` a dict over SNAP_FINGERPRINT, `sizes` as snapshot_layout takes them"""
-    offs, total = snapshot_layout(sizes)
+    """the bytes in front of the first section: `fingerprint` a dict over SNAP_FINGERPRINT (a planting server's: also over
+    SNAP_FINGERPRINT_PLANT), `sizes` as snapshot_layout takes them"""
+    fields = _snap_fields(fingerprint)
+    offs, total = snapshot_layout(sizes, len(fields))
     head = SNAP_MAGIC + np.array([SNAP_FORMAT, int(version)], "<u4").tobytes() + np.array([int(sid)], "<i8").tobytes()
-    head += np.array([len(SNAP_FINGERPRINT), len(SNAP_SECTIONS)], "<u4").tobytes() + np.array([total], "<u8").tobytes()
-    head += np.array([float(fingerprint[k]) for k in SNAP_FINGERPRINT], "<f8").tobytes()
+    head += np.array([len(fields), len(SNAP_SECTIONS)], "<u4").tobytes() + np.array([total], "<u8").tobytes()
+    head += np.array([float(fingerprint[k]) for k in fields], "<f8").tobytes()
     for kind, (o, b) in enumerate(zip(offs, sizes)):
         head += np.array([kind, 0], "<u4").tobytes() + np.array([o, int(b)], "<u8").tobytes()
     return head + bytes(offs[0] - len(head))
@@ -656,7 +687,7 @@ def snapshot_build(sid, version, fingerprint, sections):
     What snapshot_many() writes around the bytes it brings down; here for tools and tests, no device"""
     raw = lambda x: bytes(x) if isinstance(x, (bytes, bytearray)) else np.ascontiguousarray(x).tobytes()  # noqa: E731
     data = [raw(sections.get(k, b"")) for k in SNAP_SECTIONS]
-    offs, total = snapshot_layout([len(d) for d in data])
+    offs, total = snapshot_layout([len(d) for d in data], len(_snap_fields(fingerprint)))
     blob = np.zeros(total, np.uint8)
     head = snapshot_header(sid, version, fingerprint, [len(d) for d in data])
     blob[:len(head)] = np.frombuffer(head, np.uint8)
@@ -683,12 +714,12 @@ def snapshot_info(blob):
     sid = int(b[16:24].view("<i8")[0])
     n_fp, n_sec = (int(x) for x in b[24:32].view("<u4"))
     total = int(b[32:40].view("<u8")[0])
-    if n_fp != len(SNAP_FINGERPRINT) or n_sec != len(SNAP_SECTIONS):
+    if n_fp not in (len(SNAP_FINGERPRINT), len(SNAP_FINGERPRINT) + len(SNAP_FINGERPRINT_PLANT)) or n_sec != len(SNAP_SECTIONS):
         raise ValueError(f"snapshot: {n_fp} fingerprint fields and {n_sec} sections (this package reads {len(SNAP_FINGERPRINT)} and {len(SNAP_SECTIONS)})")
     o_tab = _SNAP_HEAD + 8 * n_fp
     if b.size < o_tab + 24 * n_sec:
         raise ValueError(f"snapshot: {b.size} bytes end inside the header ({o_tab + 24 * n_sec}): truncated")
-    fp = dict(zip(SNAP_FINGERPRINT, (float(x) for x in b[_SNAP_HEAD:o_tab].view("<f8"))))
+    fp = dict(zip(SNAP_FINGERPRINT + SNAP_FINGERPRINT_PLANT, (float(x) for x in b[_SNAP_HEAD:o_tab].view("<f8"))))
     sections, sizes = {}, []
     for i, name in enumerate(SNAP_SECTIONS):
         kind = int(b[o_tab + 24 * i:o_tab + 24 * i + 4].view("<u4")[0])
@@ -697,7 +728,7 @@ def snapshot_info(blob):
             raise ValueError(f"snapshot: section {i} is of kind {kind}, not {i} ({name})")
         sections[name] = (off, nb)
         sizes.append(nb)
-    offs, want = snapshot_layout(sizes)
+    offs, want = snapshot_layout(sizes, n_fp)
     for name, o in zip(SNAP_SECTIONS, offs):
         if sections[name][0] != o:
             raise ValueError(f"snapshot: section {name!r} at offset {sections[name][0]} with {sections[name][1]} bytes: the table is not the layout "
@@ -718,8 +749,12 @@ def snapshot_info(blob):
 
 def snapshot_check_fingerprint(got, want):
     """restore()'s configuration check: ValueError naming the first field of SNAP_FINGERPRINT in which the blob's fingerprint
-    `got` differs from the server's `want`, with both values"""
-    for k in SNAP_FINGERPRINT:
+    `got` differs from the server's `want`, with both values; a blob of a planting server against a server without `plant`, and
+    the other way round, is named as that"""
+    if (SNAP_FINGERPRINT_PLANT[0] in got) != (SNAP_FINGERPRINT_PLANT[0] in want):
+        raise ValueError("LiveServer.restore: the blob was taken from a server " + ("with plant, this one has none" if SNAP_FINGERPRINT_PLANT[0] in got
+                         else "without plant, this one has it (LiveServer(plant=...))"))
+    for k in _snap_fields(want):
         if float(got[k]) != float(want[k]):
             raise ValueError(f"LiveServer.restore: the blob was taken from a server with {k} = {got[k]!r}, this one has {k} = {float(want[k])!r}")
 
@@ -847,10 +882,21 @@ class LiveServer:
     on the device by ONE launch whatever the number of rows (zeggs_live_style_mix); style(sid) reads a row's style back.  The
     bank is the server's, not a row's: it is not part of a snapshot, and a row keeps the vectors it was given when a slot
     changes afterwards.  step() and close() enqueue what they always did.  With None those calls raise ValueError naming this
-    option (set_style() with a tensor works as ever), and the server allocates and enqueues what it always did."""
+    option (set_style() with a tensor works as ever), and the server allocates and enqueues what it always did.
+
+    `plant`: None, True or dict(chains="auto", speed=(v_on, v_off), height=(h_on, h_off), ground=0.0, slack=..., release=...,
+    stretch=0.999) (with `frames`; plant_options) -- feet that stay planted.  A planting stage runs in front of the
+    output head (zeggs_live_plant: ONE more launch per step whatever the number of rows): per stream and leg chain -- (upper leg,
+    lower leg, foot) by name or index, "auto": the Right and Left UpLeg / Leg / Foot of `names` -- it detects ground contact with
+    hysteresis (speed in model units a second and height above `ground`), holds the ankle of a foot in contact at a fixed world
+    point by an analytic two-bone solve of hip and knee, releases it when the unconstrained ankle leaves by more than `slack`,
+    and fades the correction out over `release` frames.  The head reads the corrected copy of the rows, in all three forms;
+    "pose" / "rpos" / "rrot" and the decoder's feedback stay the raw rows.  out[sid]["contacts"] [n, chains] bool: the flags of the
+    step's MODEL frames (also on a re-timing server), in the step's one download.  The defaults are NOT tuned on captured
+    motion.  With None the server allocates and enqueues what it always did."""
 
     def __init__(self, speech_net, decoder, stats, audio_conf, dt, rows=8, tick=4, feature_type=("mel_spec", "energy"), fps=60.0,
-                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None, gaze=None, styles=None):
+                 device="cuda", window_capacity=16384, loudness=None, resample=None, frames=None, retime=None, gaze=None, styles=None, plant=None):
         g = audio_conf
         loud = loudness_options(loudness)
         self.gaze_conf = gaze_options(gaze)
@@ -858,6 +904,7 @@ class LiveServer:
         self.resample_conf = audio.resample_options(resample)
         self.frames_conf = frames_options(frames)
         self.retime_conf = retime_options(retime, self.frames_conf, fps)
+        self.plant_conf = plant_options(plant, self.frames_conf)
         if loud is None and g.get("normalize_loudness"):
             raise ValueError("loudness normalisation needs the whole signal: apply audio.normalize_loudness() first")
         if tuple(feature_type) != ("mel_spec", "energy"):
@@ -932,6 +979,7 @@ class LiveServer:
             self._sb = ops.LiveStyles(R, ST, self.styles_conf["capacity"], self.dev)
             self._sb_set = _RecStaging(ops.StyleMix, R, self.dev)
         self._fr = self._fr_stage = None            # the output head: the rows' state (ops.LiveFrames) and its staging blocks
+        self._pl = self._pl_pose = None
         if self.frames_conf is not None:
             fc = self.frames_conf
             if 6 + 15 * len(fc["parents"]) != PO:
@@ -950,7 +998,14 @@ class LiveServer:
                 L, M = rc["ratio"]
             # (a step's record never emits more than its input frames make at max_rate, filtered or not: the filter only
             # delays; the tail record of close() has a block of its own, sized for it)
-            self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev, self._fr.record)
+            # feet that stay planted: the chains' states (ops.LivePlant), the corrected copy of a step's rows, which the head
+            # reads in place of the decoder's, and behind the head's three areas the contact flags of the step's model frames
+            tail = {}
+            if self.plant_conf is not None:
+                self._pl = ops.LivePlant(R, fc["parents"], self._fr.d.max_frames, self.plant_conf, self.dt, self.dev)
+                self._pl_pose = torch.empty(R, self._fr.d.max_frames, PO, device=self.dev, dtype=torch.float32)
+                tail = dict(tail_bytes=R * self._fr.d.max_frames * self._pl.C, tail_record=ops.PlantRow)
+            self._fr_stage = _FrameStaging(R, -(-self._fr.d.max_frames * L // M), self._fr.J, fc["mask"], self.dev, self._fr.record, **tail)
         self.status = ops.new_status(self.dev)       # give-up word of THIS server's decoder calls, looked at after every step
         self.redone_steps = 0
         self._rows = [None] * R
@@ -1100,6 +1155,8 @@ class LiveServer:
                 ops.live_head_reset(self._fr, r)
             else:
                 ops.live_head_reset(self._fr, r, p0[0].cpu().numpy(), r0[0].cpu().numpy(), *place)
+            if self._pl is not None:
+                ops.live_plant_reset(self._pl, r)
             pos0, _ = anim.bvh_channels(p0, r0, pose0[:, 6:6 + 3 * J].reshape(1, J, 3), pose0[:, 6 + 3 * J:6 + 9 * J].reshape(1, J, 2, 3),
                                         *(place or (None, None)), order=self.frames_conf["order"])
             row.offsets = pos0[0].cpu().numpy()
@@ -1154,6 +1211,22 @@ class LiveServer:
             a += outs
         return a
 
+    def _plant_records(self, recs, rows, srcs, i, counts, dests, flags):
+        """fills the planting records of ONE launch: record k takes counts[k] frames of row rows[k] from frame i of its output
+        tensors srcs[k], writes the corrected rows to the same frames of dests[k] (float32 rows of PO) and the contact flags behind
+        those of the records before it, the first at the device address `flags` -> what the head's records read in place of
+        srcs: the same root tensors, the corrected rows as "pose"."""
+        C_, planted = self._pl.C, []
+        for q, r, o, count, dst in zip(recs, rows, srcs, counts, dests):
+            pose, rpos, rrot = o["pose"], o["rpos"], o["rrot"]
+            ld = q.pose_ld, q.rpos_ld, q.rrot_ld = pose.stride(0), rpos.stride(0), rrot.stride(0)
+            q.pose, q.rpos, q.rrot = pose.data_ptr() + 4 * i * ld[0], rpos.data_ptr() + 4 * i * ld[1], rrot.data_ptr() + 4 * i * ld[2]
+            q.out, q.out_ld, q.contacts = dst.data_ptr() + 4 * i * dst.stride(0), dst.stride(0), flags
+            q.row, q.count = r, count
+            flags += count * C_
+            planted.append(dict(pose=dst, rpos=rpos, rrot=rrot))
+        return planted
+
     def _frames_step(self, out, live):
         """the output head of a step: out[sid]["frames"] for the rows `live`, from the tensors out[sid] holds -- ONE launch and
         ONE download whatever their number"""
@@ -1165,12 +1238,24 @@ class LiveServer:
         counts = n_in if rts is None else [self._emitted(t, t["n_in"] + c, False) - t["n_out"] for t, c in zip(rts, n_in)]
         N, J = sum(counts), fr.J
         areas, nbytes = frames_layout(N, J, fc["mask"])
+        flags = 0                                        # bytes of the contact flags behind the three areas (a planting server)
+        if self._pl is not None:                         # ONE more launch: the head's records then point at the planted copy
+            flags = sum(n_in) * self._pl.C
+            src = self._plant_records(stg.tail_recs, live, src, 0, n_in, [self._pl_pose[r] for r in live], stg.dev.data_ptr() + nbytes)
+            ops.live_plant(self._pl, stg.tail_recs, len(live), stg.tail_mem.data_ptr() if len(live) > 1 else None)
+            self._ops += 1
         self._frames_records(stg.recs, live, rts or [None] * len(live), src, 0, n_in, counts, 0, stg.dev.data_ptr(), areas)
         ops.live_head_launch(fr, stg.recs, len(live), stg.rec_mem.data_ptr() if len(live) > 1 else None)
         # (a step in which no row of a re-timing server emits a frame has nothing to bring down; it counts as if it had)
-        got = frames_unpack(stg.download(nbytes) if N else np.zeros(0, np.uint8), counts, J, fc["mask"])
+        buf = stg.download(nbytes + flags) if N or flags else np.zeros(0, np.uint8)
+        got = frames_unpack(buf, counts, J, fc["mask"])
         self._ops += 2
-        self.stats["frame_bytes"] += nbytes
+        self.stats["frame_bytes"] += nbytes + flags
+        if self._pl is not None:
+            a = nbytes
+            for r, c in zip(live, n_in):
+                out[self._rows[r].sid]["contacts"] = np.array(buf[a:a + c * self._pl.C]).reshape(c, self._pl.C).astype(bool)
+                a += c * self._pl.C
         if fc["text"]:
             self._frames_text(stg.dev[:N * areas[0][1]].view(torch.float64).view(N, fr.bvh_doubles), counts, got)
             self._ops += 3                               # (the formatter's call and its two downloads: row ends, then the text)
@@ -1196,17 +1281,27 @@ class LiveServer:
         n_in, J, M = int(o["pose"].shape[0]), fr.J, fr.d.max_frames
         n = n_in if rt is None else self._emitted(rt, rt["n_in"] + n_in, True) - rt["n_out"]
         areas, nbytes = frames_layout(n, J, fc["mask"])
-        block = torch.empty(nbytes, dtype=torch.uint8, device=self.dev)
+        pl = self._pl
+        block = torch.empty(nbytes + (n_in * pl.C if pl is not None else 0), dtype=torch.uint8, device=self.dev)
         rec = (fr.record * 1)()
         base, a = block.data_ptr(), 0                    # a: output frames written so far
+        if pl is not None:                               # the tail's corrected rows, and its contact flags behind the three areas
+            prec, planted = (ops.PlantRow * 1)(), torch.empty(max(n_in, 1), o["pose"].shape[1], device=self.dev, dtype=torch.float32)
         for i in range(0, max(n_in, 1 if rt is not None and rt.get("half", 0) else 0), M):       # (a filtered stream: the final record, even an empty one)
             count, final, outputs = min(M, n_in - i), int(i + M >= n_in), None
             if rt is not None:
                 outputs = self._emitted(rt, rt["n_in"] + i + count, final) - self._emitted(rt, rt["n_in"] + i, False)
-            a = self._frames_records(rec, (r,), (rt,), (o,), i, (count,), (outputs,), final, base, areas, a)
+            src = o
+            if pl is not None and count > 0:
+                src = self._plant_records(prec, (r,), (o,), i, (count,), (planted,), base + nbytes + i * pl.C)[0]
+                ops.live_plant(pl, prec, 1)
+            a = self._frames_records(rec, (r,), (rt,), (src,), i, (count,), (outputs,), final, base, areas, a)
             ops.live_head_launch(fr, rec, 1)
-        got = frames_unpack(block.cpu().numpy(), [n], J, fc["mask"])
-        self.stats["frame_bytes"] += nbytes
+        buf = block.cpu().numpy()
+        got = frames_unpack(buf, [n], J, fc["mask"])
+        if pl is not None:
+            got[0]["contacts"] = np.array(buf[nbytes:]).reshape(n_in, pl.C).astype(bool)
+        self.stats["frame_bytes"] += int(block.numel())
         if fc["text"]:
             self._frames_text(block[:n * areas[0][1]].view(torch.float64).view(n, fr.bvh_doubles), [n], got)
         if rt is not None:
@@ -1792,7 +1887,10 @@ class LiveServer:
                 break
             for sid, o in out.items():
                 acc.setdefault(sid, []).append(o)
-        out = {sid: {k: torch.cat([o[k] for o in v]) for k in v[0] if k != "frames"} for sid, v in acc.items()}
+        out = {sid: {k: torch.cat([o[k] for o in v]) for k in v[0] if k not in ("frames", "contacts")} for sid, v in acc.items()}
+        if self._pl is not None:
+            for sid, v in acc.items():
+                out[sid]["contacts"] = np.concatenate([o["contacts"] for o in v])
         if self._fr is not None:
             for sid, v in acc.items():
                 out[sid]["frames"] = frames_cat([o["frames"] for o in v])
@@ -1834,10 +1932,14 @@ class LiveServer:
             out = {k: torch.cat([o[i] for o in outs]).contiguous() for i, k in enumerate(("pose", "rpos", "rrot"))} if outs else {}
             if outs and self._fr is not None:
                 out["frames"] = self._frames_close(r, out)
+                if self._pl is not None:
+                    out["contacts"] = out["frames"].pop("contacts")
             elif self._fr is not None and row.rt is not None and row.rt.get("half", 0) and row.rt["n_in"] > 0:
                 # a filtered stream whose frames all left through step(): the final record brings no frame and emits the tail
                 out = dict(pose=self.pose[r:r], rpos=self.rpos[r:r], rrot=self.rrot[r:r])
                 out["frames"] = self._frames_close(r, out)
+                if self._pl is not None:
+                    out["contacts"] = out["frames"].pop("contacts")
         self._rows[r] = None
         del self._sids[sid]
         return out
@@ -1864,6 +1966,12 @@ class LiveServer:
                   filter_beta=fl["beta"] if fl else 0.0, filter_min_rate_num=tc["min_rate"].numerator if fl else 0,
                   filter_min_rate_den=tc["min_rate"].denominator if fl else 0, filter_half_max=tc["half_max"] if fl else 0)
         assert set(fp) == set(SNAP_FINGERPRINT)
+        pc = self.plant_conf
+        if pc is not None:                               # only a planting server's fingerprint has these
+            fp.update(plant_chains=zlib.crc32(np.asarray(pc["chains"], "<i4").tobytes()), plant_v_on=pc["speed"][0], plant_v_off=pc["speed"][1],
+                      plant_h_on=pc["height"][0], plant_h_off=pc["height"][1], plant_ground=pc["ground"], plant_slack=pc["slack"],
+                      plant_release=pc["release"], plant_stretch=pc["stretch"])
+            assert set(fp) == set(SNAP_FINGERPRINT + SNAP_FINGERPRINT_PLANT)
         return {k: float(v) for k, v in fp.items()}
 
     def _snap_pieces(self, r, n_window, n_pending, rs_on):
@@ -1888,6 +1996,8 @@ class LiveServer:
             if obj is not None:
                 base = 0 if obj.state is None else obj.state.data_ptr()
                 p[name] = [(base + o, b) for o, b in spans(obj, r)]
+        if self._pl is not None:                         # a planting server: the chains' states ride behind the head's pieces
+            p["head"] += [(self._pl.state.data_ptr() + o, b) for o, b in ops.live_plant_spans(self._pl, r)]
         for t in (self.feats, self.ring, self.h, self.pose, self.rpos, self.rrot, self.gaze, self.sty_old, self.sty_new):
             assert t.is_contiguous()
         return p
@@ -1938,7 +2048,7 @@ class LiveServer:
             host = dict(row=np.array([vals[k] for k in SNAP_ROW], "<i8").tobytes(), offsets=b"" if off is None else np.ascontiguousarray(off).tobytes())
             pieces = self._snap_pieces(r, row.n - row.base, row.n_feat - row.fbase, rs is not None)
             sizes = self._snap_sizes(pieces, host)
-            offs, total = snapshot_layout(sizes)
+            offs, total = snapshot_layout(sizes, len(_snap_fields(fp)))
             plans.append(dict(host=host, pieces=pieces, sizes=sizes, offs=offs, total=total, at=at))
             n_seg += sum(1 for v in pieces.values() for _, b in v if b)
             at += (total + 63) // 64 * 64

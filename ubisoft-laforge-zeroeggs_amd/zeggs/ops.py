@@ -15,6 +15,7 @@ from .capi import (DEC_FIELDS, SPEECH_FIELDS, STATS_FIELDS, STYLE_FIELDS, STYLE_
                    DecStats, FramesDims, FramesRow, GazeCond, GazeDims, GazeSet, HipLibraryMissing, LiveDims, LiveRow, LossDims, LoudDims, LoudRow, MelRow,
                    ResampleDims, ResampleRow, RefilterRow, RetimeRow, Seg, SnapSeg, SnapSpan, SpeechDims, SpeechPtrs,
                    StyleBankDims, StyleDims, StyleGruDims, StyleGruPtrs, StyleMix, StylePtrs, api)
+from .capi import PlantDims, PlantRow  # noqa: E402,F401
 
 _LIB_PATH = capi.LIB_PATH
 
@@ -1370,6 +1371,114 @@ def live_gaze_read(lg, row, frame):
 def live_gaze_spans(lg, row):
     """zeggs_live_gaze_spans: where row `row` lives in lg.state -> [(offset, bytes)]"""
     return _spans(api().zeggs_live_gaze_spans, lg.d, int(row))
+
+
+PLANT_MAX_CHAINS = 4                                # ZEGGS_PLANT_MAX_CHAINS
+PLANT_AUTO = (("RightUpLeg", "RightLeg", "RightFoot"), ("LeftUpLeg", "LeftLeg", "LeftFoot"))
+# NOT tuned on captured motion (no dataset was at hand when they were chosen): speeds in model units a second, lengths in model units
+PLANT_DEFAULTS = dict(chains="auto", speed=(15.0, 30.0), height=(12.0, 16.0), ground=0.0, slack=8.0, release=8, stretch=0.999)
+
+
+def plant_options(plant, parents, names=None):
+    """the `plant` options (a dict with keys of PLANT_DEFAULTS, or True: the defaults) against a skeleton -> dict(chains: [(u, m, e)]
+    joint indices, speed, height, ground, slack, release, stretch).  A chain is three joints given by name or by index with
+    parents[m] == u and parents[e] == m; "auto" picks PLANT_AUTO's triples where `names` holds them.  ValueError for anything
+    else, the chain named: an unknown name, an index out of range, joints that are no chain, a joint in two chains, no chain or
+    more than PLANT_MAX_CHAINS, thresholds with on > off, a negative slack or release, a stretch outside (0, 1]."""
+    if plant is True:
+        plant = {}
+    if not isinstance(plant, dict) or set(plant) - set(PLANT_DEFAULTS):
+        raise ValueError(f"plant: True or a dict with keys {sorted(PLANT_DEFAULTS)}")
+    o = dict(PLANT_DEFAULTS, **plant)
+    parents = [int(p) for p in parents]
+    names = None if names is None else [str(n) for n in names]
+    chains = o["chains"]
+    if isinstance(chains, str):
+        if chains != "auto":
+            raise ValueError(f"plant: chains {chains!r} ('auto' or a list of (upper leg, lower leg, foot) triples)")
+        chains = [c for c in PLANT_AUTO if names is not None and all(n in names for n in c)]
+        if not chains:
+            raise ValueError(f"plant: chains 'auto' needs joint names that hold {' or '.join(str(c) for c in PLANT_AUTO)}")
+    try:
+        chains = [tuple(c) for c in chains]
+    except TypeError:
+        raise ValueError(f"plant: chains {o['chains']!r} ('auto' or a list of (upper leg, lower leg, foot) triples)") from None
+    if not 1 <= len(chains) <= PLANT_MAX_CHAINS:
+        raise ValueError(f"plant: {len(chains)} chains (1..{PLANT_MAX_CHAINS})")
+    out, taken = [], set()
+    for c in chains:
+        if len(c) != 3:
+            raise ValueError(f"plant: chain {c!r} is not (upper leg, lower leg, foot)")
+        idx = []
+        for j in c:
+            if isinstance(j, str):
+                if names is None or j not in names:
+                    raise ValueError(f"plant: chain {c!r}: no joint named {j!r}")
+                idx.append(names.index(j))
+            elif isinstance(j, (int, np.integer)) and not isinstance(j, bool) and 0 <= int(j) < len(parents):
+                idx.append(int(j))
+            else:
+                raise ValueError(f"plant: chain {c!r}: joint {j!r} (a name or an index in 0..{len(parents) - 1})")
+        u, m, e = idx
+        if parents[m] != u or parents[e] != m:
+            raise ValueError(f"plant: chain {c!r} is no chain: the parent of {c[1]!r} is joint {parents[m]}, the parent of {c[2]!r} is joint {parents[e]}")
+        if taken & set(idx) or len(set(idx)) != 3:
+            raise ValueError(f"plant: chain {c!r} shares a joint with an earlier chain")
+        taken |= set(idx)
+        out.append((u, m, e))
+    pair = lambda k: tuple(float(x) for x in o[k]) if isinstance(o[k], (tuple, list)) and len(o[k]) == 2 else None  # noqa: E731
+    speed, height = pair("speed"), pair("height")
+    if speed is None or not 0.0 <= speed[0] <= speed[1] < float("inf"):
+        raise ValueError(f"plant: speed {o['speed']!r} ((v_on, v_off) with 0 <= v_on <= v_off)")
+    if height is None or not height[0] <= height[1] or not all(np.isfinite(height)):
+        raise ValueError(f"plant: height {o['height']!r} ((h_on, h_off) with h_on <= h_off)")
+    release = o["release"]
+    if isinstance(release, bool) or not isinstance(release, (int, np.integer)) or not 0 <= int(release) <= 4096:
+        raise ValueError(f"plant: release {release!r} (frames, 0..4096)")
+    ground, slack, stretch = float(o["ground"]), float(o["slack"]), float(o["stretch"])
+    if not np.isfinite(ground):
+        raise ValueError(f"plant: ground {o['ground']!r}")
+    if not 0.0 <= slack < float("inf"):
+        raise ValueError(f"plant: slack {o['slack']!r} (>= 0)")
+    if not 0.0 < stretch <= 1.0:
+        raise ValueError(f"plant: stretch {o['stretch']!r} (0 < stretch <= 1)")
+    return dict(chains=out, speed=speed, height=height, ground=ground, slack=slack, release=int(release), stretch=stretch)
+
+
+class LivePlant:
+    """The planting stage of `rows` live rows (include/zeggs_hip_plant.h): the dims record -- the thresholds of `conf`
+    (plant_options) and the frame time `dt` -- and the state block: the skeleton's parents and the chain table, then per row the
+    chains' contact states (zeroes: a row is reset when it opens)."""
+
+    def __init__(self, rows, parents, max_frames, conf, dt, device="cuda"):
+        self.parents, self.chains = [int(p) for p in parents], [tuple(c) for c in conf["chains"]]
+        self.J, self.C = len(self.parents), len(self.chains)
+        self.d = PlantDims(int(rows), self.J, int(max_frames), self.C, int(conf["release"]), 0, float(dt), conf["speed"][0], conf["speed"][1],
+                           conf["height"][0], conf["height"][1], conf["ground"], conf["slack"], conf["stretch"])
+        nbytes = api().zeggs_live_plant_state_bytes(self.d)
+        if nbytes == 0:
+            raise ValueError(f"LivePlant: {api().zeggs_last_error().decode()}")
+        self.state = torch.zeros(nbytes, dtype=torch.uint8, device=device)
+        flat = [j for c in self.chains for j in c]
+        api().zeggs_live_plant_prepare(self.d, (C.c_int * self.J)(*self.parents), (C.c_int * len(flat))(*flat), self.state, self.state.numel(),
+                                       _stream())
+        self.pose_floats = 6 + 15 * self.J
+
+
+def live_plant_reset(lp, row):
+    """zeggs_live_plant_reset: every chain of the row FREE, its next frame the first of a stream"""
+    api().zeggs_live_plant_reset(lp.d, lp.state, lp.state.numel(), int(row), _stream())
+
+
+def live_plant(lp, recs, n, recs_dev=None):
+    """zeggs_live_plant: recs[:n] a HOST array of PlantRow (device addresses inside), `recs_dev` the device address of a copy of the
+    same records (None: one record, in the kernel arguments): ONE launch for all of them"""
+    api().zeggs_live_plant(lp.d, recs, _records(PlantRow, recs_dev), int(n), lp.state, lp.state.numel(), _stream())
+
+
+def live_plant_spans(lp, row):
+    """zeggs_live_plant_spans: where row `row` lives in lp.state -> [(offset, bytes)]"""
+    return _spans(api().zeggs_live_plant_spans, lp.d, int(row))
 
 
 STYLE_MAX_TERMS, STYLE_MAX_SLOTS = 8, 4096         # ZEGGS_STYLE_MAX_TERMS / ZEGGS_STYLE_MAX_SLOTS
