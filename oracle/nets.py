@@ -241,8 +241,8 @@ def style_encoder_gru(w, x, prefix="encoder."):
     """StyleEncoderGRU.forward (modules.py:307-343): two conv(3)+ReLU, one bidirectional GRU layer, projection of
     the LAST time step (forward direction: final state; reverse direction: its first step, which saw x[-1] only)."""
     p = prefix
-    h = torch.relu(_conv3(x, w[p + "convs.0.conv.weight"], w[p + "convs.0.conv.bias"]))
-    h = torch.relu(_conv3(h, w[p + "convs.2.conv.weight"], w[p + "convs.2.conv.bias"]))
+    h = F.relu(_conv3(x, w[p + "convs.0.conv.weight"], w[p + "convs.0.conv.bias"]))     # (F.relu: tests/helpers.py relu_sites sees it)
+    h = F.relu(_conv3(h, w[p + "convs.2.conv.weight"], w[p + "convs.2.conv.bias"]))
     B, L, Hh = h.shape
     hf = torch.zeros(B, Hh, dtype=h.dtype)
     for t in range(L):

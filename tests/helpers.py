@@ -287,6 +287,40 @@ def style_case(B, L, S, seed):
             [torch.randn(B, S, generator=gen) for _ in range(3)])
 
 
+def build_style_gru(H, S, seed=SEED):
+    """a seeded recurrent style encoder (type "gru", VAE) of hidden width H and encoding size S (projection width 2 S)"""
+    torch.manual_seed(seed)
+    return modules.StyleEncoder(synth.POSE_IN, H, S, type="gru", use_vae=True)
+
+
+# The shape matrix of the recurrent style encoder (tests/test_style_gru_oracle_cpu.py pins the oracle at every point,
+# tests/test_gpu_style_gru_dims.py runs the device there): (H, S, ((B, L), ...), path).  "fast": the forward-direction recurrence on
+# the decoder's stage kernels (csrc/decoder_fast.hip sg_fast_supported: H % 16 == 0, 1 <= B <= 64), "generic": a product plus a gate
+# kernel per frame.  Which stage_k instantiation each point launches: the docstring of tests/test_gpu_style_gru_dims.py.
+STYLE_GRU_ROWS = (
+    (16, 8, ((1, 1), (1, 2), (16, 3), (17, 2)), "fast"),
+    (48, 64, ((17, 2), (48, 3)), "fast"),
+    (80, 20, ((33, 3), (64, 2)), "fast"),
+    (512, 64, ((1, 40), (49, 3), (64, 1), (64, 2)), "fast"),
+    (800, 64, ((1, 2), (32, 2), (64, 2)), "fast"),
+    (24, 64, ((5, 4),), "generic"),
+    (30, 64, ((3, 5),), "generic"),
+    (512, 64, ((65, 2),), "generic"),
+)
+STYLE_GRU_OUT_BOUND, STYLE_GRU_GRAD_BOUND = 5e-5, 3e-4        # tests/test_gpu_parity.py::test_gru_style_encoder_stage_path_batch
+STYLE_GRU_TEMPERATURE = 1.0
+
+
+def style_gru_points():
+    """every (H, S, B, L, path) of STYLE_GRU_ROWS"""
+    return [(H, S, B, L, path) for H, S, pts, path in STYLE_GRU_ROWS for B, L in pts]
+
+
+def style_gru_case(H, S, B, L):
+    """seeded inputs of one point (style_case: x [B, L, 1134], eps [B, S], weights of z / mu / logvar), seeded by the shape"""
+    return style_case(B, L, S, seed=7000 + 131 * H + 17 * B + L)
+
+
 def f64_weights(module):
     return {k: v.detach().cpu().double().clone().requires_grad_(True) for k, v in module.state_dict().items()}
 

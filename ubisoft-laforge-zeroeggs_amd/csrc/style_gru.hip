@@ -116,7 +116,8 @@ extern "C" int zeggs_style_encoder_gru_fwd(const ZeggsStyleGruDims* dp, const Ze
   ZCHECK(d.B >= 1 && d.L >= 1, "style encoder (gru): empty batch or sequence");
   Arena a(ws, ws_bytes);
   SgWs w = carve_sg(d, a);
-  ZCHECK(a.ok(), "style encoder (gru): workspace too small (%zu < %zu)", ws_bytes, a.off);
+  // (what zeggs_style_encoder_gru_workspace_bytes asks for, its 256 spare bytes included: one contract for the caller)
+  ZCHECK(a.ok() && ws_bytes >= a.off + 256, "style encoder (gru): workspace too small (%zu < %zu)", ws_bytes, a.off + 256);
   const int B = d.B, L = d.L, C = d.C, H = d.H, LP = L + 2;
   const long sH = (long)B * H, s3 = 3 * sH;
   ZTRY(k_pad_rows(w.xp, x, B, L, C, 1, 1, 0, s));
@@ -155,7 +156,7 @@ extern "C" int zeggs_style_encoder_gru_bwd(const ZeggsStyleGruDims* dp, const Ze
   hipStream_t s = (hipStream_t)stream;
   Arena a(ws, ws_bytes);
   SgWs w = carve_sg(d, a);
-  ZCHECK(a.ok(), "style encoder (gru) bwd: workspace too small");
+  ZCHECK(a.ok() && ws_bytes >= a.off + 256, "style encoder (gru) bwd: workspace too small");
   const int B = d.B, L = d.L, C = d.C, H = d.H, LP = L + 2;
   const long sH = (long)B * H, s3 = 3 * sH, BL = (long)B * L;
   // projection
