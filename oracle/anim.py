@@ -83,16 +83,26 @@ def q_to_euler(q, order="zyx"):
                      np.arctan2(2.0 * (w * x + y * z), 1.0 - 2.0 * (x * x + y * y))], axis=-1)
 
 
-def q_unroll(q):
+def q_unroll(q, bug=None):
     """make consecutive frames sign-continuous"""
     out = q.copy()
+    if bug == "no_unroll":
+        return out
     for i in range(1, len(out)):
-        flip = np.sum(out[i] * out[i - 1], axis=-1) < 0.0
+        flip = np.sum(out[i] * (q if bug == "unroll_by_raw_sign" else out)[i - 1], axis=-1) < 0.0
         out[i][flip] = -out[i][flip]
     return out
 
 
-def q_from_xform(m, eps=1e-10):
+def xform_branch(m):
+    """the branch quat.from_xform takes per matrix: 0 trace, 1 / 2 / 3 largest diagonal element m00 / m11 / m22"""
+    m00, m11, m22 = m[..., 0, 0], m[..., 1, 1], m[..., 2, 2]
+    x_big = (m00 > m11) & (m00 > m22)
+    y_big = ~x_big & (m11 > m22)
+    return np.where(m00 + m11 + m22 > 0, 0, np.where(x_big, 1, np.where(y_big, 2, 3)))
+
+
+def q_from_xform(m, eps=1e-10, bug=None):
     """rotation matrices [..., 3, 3] -> quaternions (branch choice as reference quat.from_xform)"""
     m00, m11, m22 = m[..., 0, 0], m[..., 1, 1], m[..., 2, 2]
     tr = m00 + m11 + m22
@@ -106,9 +116,9 @@ def q_from_xform(m, eps=1e-10):
             np.stack([a / sx, 0.25 * sx, p / sx, q / sx], axis=-1),
             np.stack([b / sy, p / sy, 0.25 * sy, r / sy], axis=-1),
             np.stack([c / sz, q / sz, r / sz, 0.25 * sz], axis=-1)]
-    x_big = (m00 > m11) & (m00 > m22)
-    y_big = ~x_big & (m11 > m22)
-    case = np.where(tr > 0, 0, np.where(x_big, 1, np.where(y_big, 2, 3)))[..., None]
+    case = xform_branch(m)[..., None]
+    if bug in ("trace_for_branch_1", "trace_for_branch_2", "trace_for_branch_3"):
+        case = np.where(case == int(bug[-1]), 0, case)
     return np.select([case == 0, case == 1, case == 2, case == 3], cand)
 
 
@@ -140,11 +150,31 @@ def _finite_diff_first(x):
     return x
 
 
-def preprocess_animation(anim):
+# Restatements of plausible kernel bugs (negative controls: tests/test_anim_oracle_cpu.py).  `bug` is one of these names or None.
+ANIM_BUGS = ("no_unroll", "unroll_by_raw_sign", "median_lower_middle", "median_by_bit_pattern", "hips_spine2_exchanged",
+             "root_vel_same_frame")
+BVH_BUGS = ("trace_for_branch_1", "trace_for_branch_2", "trace_for_branch_3")
+
+
+def _median(x, bug=None):
+    """np.median over axis 0; the two ways a radix select goes wrong: the lower of the two middle values alone, and the order of
+    the bit patterns read as unsigned integers (negative doubles then sort above the positive ones, largest magnitude last)"""
+    if bug == "median_lower_middle":
+        return np.sort(x, axis=0)[(len(x) - 1) // 2]
+    if bug == "median_by_bit_pattern":
+        key = np.ascontiguousarray(x).view(np.uint64)
+        srt = np.take_along_axis(x, np.argsort(key, axis=0, kind="stable"), axis=0)
+        return 0.5 * (srt[(len(x) - 1) // 2] + srt[len(x) // 2])
+    return np.median(x, axis=0)
+
+
+def preprocess_animation(anim, bug=None):
     """BVH dict -> the 16 feature arrays of reference data_pipeline.preprocess_animation (same order)."""
     names, parents, dt = anim["names"], anim["parents"], anim["frametime"]
+    if bug == "hips_spine2_exchanged":
+        names = [{"Hips": "Spine2", "Spine2": "Hips"}.get(k, k) for k in names]
     n = len(anim["rotations"])
-    lrot = q_unroll(q_from_euler(np.radians(anim["rotations"].astype(np.float64)), anim["order"]))
+    lrot = q_unroll(q_from_euler(np.radians(anim["rotations"].astype(np.float64)), anim["order"]), bug)
     lpos = anim["positions"].astype(np.float64).copy()
     grot, gpos = q_fk(lrot, lpos, parents)
     fwd = np.array([[0.0, 0.0, 1.0]])
@@ -156,7 +186,7 @@ def preprocess_animation(anim):
     look = q_mul_vec(grot[:, names.index("Head")], fwd[0])
     look[:, 1] = 0.0
     look /= np.linalg.norm(look, axis=-1, keepdims=True)
-    gaze_pos = np.repeat(np.median(root_pos + 100.0 * look, axis=0)[None], n, axis=0)
+    gaze_pos = np.repeat(_median(root_pos + 100.0 * look, bug)[None], n, axis=0)
     inv_root = q_inv(root_rot)
     gaze_dir = q_mul_vec(inv_root, gaze_pos - root_pos)
     lrot[:, 0] = q_mul(inv_root, lrot[:, 0])
@@ -176,7 +206,7 @@ def preprocess_animation(anim):
     root_vel = np.zeros_like(root_pos)
     root_vel[1:] = (root_pos[1:] - root_pos[:-1]) / dt
     _finite_diff_first(root_vel)
-    root_vel[1:] = q_mul_vec(inv_root[:-1], root_vel[1:])
+    root_vel[1:] = q_mul_vec(inv_root[1:] if bug == "root_vel_same_frame" else inv_root[:-1], root_vel[1:])
     root_vel[0] = q_mul_vec(inv_root[0], root_vel[0])
 
     crot, cpos, cvrt, cvel = q_fk_vel(lrot, lpos, lvrt, lvel, parents)
@@ -196,10 +226,10 @@ def xform_from_xy(xy, eps=1e-10):
     return np.swapaxes(rows, -1, -2)
 
 
-def bvh_channels(root_pos, root_rot, lpos, ltxy, start_position=None, start_rotation=None, order="zyx"):
+def bvh_channels(root_pos, root_rot, lpos, ltxy, start_position=None, start_rotation=None, order="zyx", bug=None):
     """decoder output -> (positions [T,J,3], euler degrees [T,J,3]) as written by reference utils.write_bvh after
     generate.py:389 turned the two-axis encodings into quaternions."""
-    lrot = q_from_xform(xform_from_xy(np.asarray(ltxy, np.float64)))
+    lrot = q_from_xform(xform_from_xy(np.asarray(ltxy, np.float64)), bug=bug)
     root_pos, root_rot = np.asarray(root_pos, np.float64), np.asarray(root_rot, np.float64)
     if start_position is not None and start_rotation is not None:
         p0, r0 = root_pos[0:1].copy(), root_rot[0:1].copy()

@@ -2170,3 +2170,326 @@ def live_bound(srv):
     path = ops.batch_last_path()
     assert path == ("persistent" if srv.bd.sweep else "stage"), (path, srv.bd.sweep)
     return 1e-4 if path == "persistent" else 5e-5
+
+
+# ----------------------------------------------------------------------------- animation kernels (tests/test_gpu_anim_dims.py)
+# Rigs, exemplar clips and decoder-side rows for csrc/anim.hip at other skeletons, frame counts and rotations than the one rig of
+# tests/test_gpu_parity.py.  tests/test_anim_oracle_cpu.py proves on the CPU that every case below meets the conditions it was built
+# for (on the oracle's intermediates) and that the comparison is sharp (negative controls).
+ANIM_FEATURES = ("root_pos", "root_rot", "root_vel", "root_vrt", "lpos", "lrot", "ltxy", "lvel", "lvrt", "cpos", "crot", "ctxy", "cvel",
+                 "cvrt", "gaze_pos", "gaze_dir")
+ANIM_F64_BOUND, ANIM_F32_BOUND = 1e-9, 1e-6       # tests/test_gpu_parity.py::test_anim_features_vs_oracle_and_reference
+BVH_POS_BOUND, BVH_QUAT_BOUND, BVH_ANGLE_BOUND = 1e-9, 1e-9, 1e-9      # ::test_pose_to_bvh_vs_oracle_and_reference; degrees
+ANIM_ORDER_ZYX, ANIM_ORDER_XZY = 6, 24            # anim_math.h ORDER_ZYX / ORDER_XZY (0 stands for zyx)
+
+
+class _OneJoint(list):
+    """the names of the one-joint rig: Hips, Spine2 and Head are all joint 0 (the raw ABI takes it, the Python wrapper cannot)"""
+
+    def index(self, name, *a):
+        return 0
+
+
+def _anim_rigs():
+    def named(parents, **at):
+        names = [f"joint_{i}" for i in range(len(parents))]
+        for n, i in at.items():
+            names[i] = n
+        return parents, names
+
+    def tree(n_fixed, J, seed):
+        rng = np.random.default_rng(seed)
+        return [int(rng.integers(0, i)) for i in range(n_fixed, J)]
+
+    spine = [-1, 0, 1, 2, 3]                                       # Hips, Spine, Spine2, Neck, Head
+    j24 = [-1, 0, 1, 2, 3, 4, 5,                                   # Root, Hips, Spine, Spine1, Spine2, Neck, Head
+           1, 7, 8, 1, 10, 11,                                     # two legs below Hips
+           4, 13, 14, 15, 4, 17, 18, 19,                           # two arms below Spine2
+           6, 0, 22]                                               # a head end, a prop of two joints below Root
+    return {
+        "j3": named([-1, 0, 1], Hips=0, Spine2=1, Head=2),
+        "j24-root": named(j24, Root=0, Hips=1, Spine2=4, Head=6),
+        "j64": named(spine + tree(5, 64, 64), Hips=0, Spine2=2, Head=4),
+        "j65": named(spine + tree(5, 64, 64) + [40], Hips=0, Spine2=2, Head=4),       # j64 and one joint in the unroll's second block
+        "j130": named([-1] + list(range(44)) + tree(45, 130, 130), Hips=0, Spine2=20, Head=44),     # Head 44 levels deep
+        "j1": ([-1], _OneJoint(["Hips"])),
+    }
+
+
+ANIM_RIGS = _anim_rigs()
+# every features case of tests/test_gpu_anim_dims.py: (rig, N, variant); variant: {} | static_head | order | dt
+ANIM_CASES = ([(r, 10, {}) for r in ANIM_RIGS] +
+              [(r, N, {}) for r in ("j3", "j24-root") for N in (4, 5, 8, 9, 17, 64, 65)] +
+              [(r, 17, {}) for r in ("j65", "j130")] +
+              [("j24-root", N, dict(static_head=True)) for N in (9, 10)] +
+              [("j24-root", 10, dict(order=o)) for o in ("xyz", "yzx", "xzy")] +
+              [("j3", 10, dict(dt=dt)) for dt in (1.0 / 30.0, 1.0 / 120.0)])
+
+
+def anim_case_id(case):
+    rig, N, var = case
+    return "-".join([rig, f"N{N}"] + [k if v is True else (f"dt{round(1 / v)}" if k == "dt" else str(v)) for k, v in var.items()])
+
+
+def _ancestors(parents, j):
+    out = []
+    while parents[j] >= 0:
+        j = parents[j]
+        out.append(j)
+    return out
+
+
+def anim_roles(rig):
+    """-> dict(hips, spine2, head, chain: the joints whose rotation reaches Hips, Spine2 or Head, sweep / alternate: the joints that
+    carry a sign-flipping channel, static: the joint whose channels never change)"""
+    parents, names = ANIM_RIGS[rig]
+    J = len(parents)
+    h, s, e = names.index("Hips"), names.index("Spine2"), names.index("Head")
+    chain = sorted({h, s, e} | set(_ancestors(parents, h)) | set(_ancestors(parents, s)) | set(_ancestors(parents, e)))
+    free = [j for j in range(J) if j not in chain]
+    return dict(hips=h, spine2=s, head=e, chain=chain, static=s if J > 1 else None,
+                sweep=[j for j in free if j % 4 in (1, 2)], alternate=[e] + [j for j in free if j % 4 == 3 or j == J - 1])
+
+
+def anim_clip(rig, N, seed, order="zyx", dt=1.0 / 60.0, static_head=False):
+    """A clip dict as synth.make_bvh_clip gives, for a rig of ANIM_RIGS: float64 Euler degrees in (-180, 180], channel order `order`.
+      Hips      its yaw channel goes from -170 to +170 degrees over the clip, its other channels are 0 (165 where Hips has a parent,
+                whose small rotations add to it, and on the one-joint rig): the facing direction stays 10 degrees off -z
+      Head      its yaw goes from +175 to -150 degrees and its roll channel ALTERNATES between about +172 and -172 degrees: every raw
+                dot product with the frame before is negative; where the roll is applied outside the yaw its half turn mirrors the yaw
+                (the sweep runs the other way in the other orders), so Head's forward turns nearly twice about the vertical and the
+                gaze candidates change sign in x and in z
+      Spine2    (static) the same three angles in every frame
+      others    smooth small motion; some (anim_roles: sweep) with a channel that advances ~95 degrees a frame through the wrap, some
+                (alternate) with the alternating channel; the joints whose rotation reaches Hips, Spine2 or Head stay small
+      positions offsets plus a smooth wobble of every joint, joint 0 travelling
+    static_head: every joint between the root and Hips / Spine2 / Head keeps one pose and joint 0 its place: all N gaze candidates
+    are the same three doubles."""
+    parents, names = ANIM_RIGS[rig]
+    J, R = len(parents), anim_roles(rig)
+    rng = np.random.default_rng(seed)
+    t = np.arange(N)
+    u = t / (N - 1.0)
+    ax = {c: order.index(c) for c in "xyz"}
+
+    def smooth(shape, amp):
+        f = rng.uniform(0.3, 1.5, shape)
+        return amp * np.sin(2.0 * np.pi * f * u.reshape((N,) + (1,) * len(shape)) + rng.uniform(0, 2.0 * np.pi, shape))
+
+    rot = smooth((J, 3), 9.0)
+    for j in R["chain"]:
+        rot[:, j] = smooth((3,), 2.0)
+    for j in R["sweep"]:
+        rot[:, j, j % 3] = (95.0 + 0.37 * j) * t + rng.uniform(0.0, 360.0) + rng.uniform(-3.0, 3.0, N)
+    for j in R["alternate"]:
+        rot[:, j, j % 3 if j != R["head"] else ax["z"]] = (1.0 - 2.0 * (t % 2)) * (172.0 - rng.uniform(0.0, 3.0, N))
+    if J > 1:
+        rot[:, R["head"], ax["y"]] = (1.0 if ax["z"] < ax["y"] else -1.0) * (175.0 - 325.0 * u)
+        rot[:, R["head"], ax["x"]] = 0.0
+        rot[:, R["static"]] = np.array([20.0, -35.0, 50.0])
+    amp = 170.0 if R["hips"] == 0 and J > 1 else 165.0
+    rot[:, R["hips"]] = 0.0
+    rot[:, R["hips"], ax["y"]] = -amp + 2.0 * amp * u
+    if J == 1:
+        rot[:, 0, ax["z"]] = (1.0 - 2.0 * (t % 2)) * (172.0 - rng.uniform(0.0, 3.0, N))
+    offsets = rng.normal(0.0, 6.0, (J, 3))
+    offsets[:, 1] = np.abs(offsets[:, 1])
+    offsets[0] = [0.0, 90.0, 0.0]
+    pos = offsets[None] + smooth((J, 3), 0.4)
+    pos[:, 0] += smooth((3,), 30.0) * np.array([1.0, 0.1, 1.0])
+    if static_head:
+        for j in R["chain"]:
+            rot[:, j] = rot[N // 2, j]
+            pos[:, j] = pos[N // 2, j]
+    rot = 180.0 - (180.0 - rot) % 360.0               # into (-180, 180], as BVH files store the channels
+    return dict(rotations=rot, positions=pos, offsets=offsets, parents=np.asarray(parents, np.int32), names=names, order=order,
+                frametime=float(dt))
+
+
+def anim_case_clip(case):
+    rig, N, var = case
+    return anim_clip(rig, N, seed=1000 * sorted(ANIM_RIGS).index(rig) + N, **var)
+
+
+def anim_unroll_ranges(N):
+    """the frames anim_unroll_k takes in its groups of eight and in its scalar tail"""
+    g = 1 + 8 * ((N - 1) // 8)
+    return range(1, g), range(g, N)
+
+
+def anim_intermediates(clip):
+    """what the conditions of a clip are stated on, from the oracle's own functions: d [N-1, J] raw dot products of consecutive
+    frames, facing / look [N] angles (degrees from +z about y) of the projected Hips / Head forward, look_len [N] length of Head's
+    forward before it is normalised, cand [N, 3] gaze candidates, rel_w [N-1, J] |w| of the unrolled frame-to-frame rotation"""
+    from oracle import anim as oa
+    names = clip["names"]
+    raw = oa.q_from_euler(np.radians(clip["rotations"]), clip["order"])
+    d = np.sum(raw[1:] * raw[:-1], axis=-1)
+    lrot = oa.q_unroll(raw)
+    grot, gpos = oa.q_fk(lrot, clip["positions"], clip["parents"])
+    fwd = np.array([0.0, 0.0, 1.0])
+    f = oa.q_mul_vec(grot[:, names.index("Hips")], fwd)
+    l = oa.q_mul_vec(grot[:, names.index("Head")], fwd)
+    lh = l * np.array([1.0, 0.0, 1.0])
+    cand = gpos[:, names.index("Spine2")] * np.array([1.0, 0.0, 1.0]) + 100.0 * lh / np.linalg.norm(lh, axis=-1, keepdims=True)
+    return dict(d=d, facing=np.degrees(np.arctan2(f[:, 0], f[:, 2])), look=np.degrees(np.arctan2(l[:, 0], l[:, 2])),
+                look_len=np.linalg.norm(lh, axis=-1), cand=cand, rel_w=np.abs(oa.q_mul(lrot[1:], oa.q_inv(lrot[:-1]))[..., 0]))
+
+
+def anim_oracle(clip, bug=None):
+    from oracle import anim as oa
+    return oa.preprocess_animation(clip, bug=bug)
+
+
+def anim_errors(got, ref):
+    """per feature array: max |got - ref| / (1 + |ref|): err <= bound is np.allclose with atol = rtol = bound"""
+    out = {}
+    for n, a, b in zip(ANIM_FEATURES, got, ref):
+        a, b = np.asarray(a, np.float64), np.asarray(b, np.float64)
+        assert a.shape == b.shape, (n, a.shape, b.shape)
+        out[n] = float(np.max(np.abs(a - b) / (1.0 + np.abs(b)))) if np.isfinite(a).all() else float("inf")
+    return out
+
+
+def anim_bound(name):
+    return ANIM_F32_BOUND if name in ("ltxy", "ctxy") else ANIM_F64_BOUND
+
+
+# ---- decoder-side rows
+def _q_to_xy(q):
+    """unit quaternions -> two-axis rows [..., 2, 3]: the rotated x and y axes"""
+    from oracle import anim as oa
+    return np.stack([oa.q_mul_vec(q, np.array([1.0, 0.0, 0.0])), oa.q_mul_vec(q, np.array([0.0, 1.0, 0.0]))], axis=-2)
+
+
+def _rows_from_quats(q, rng):
+    """what the decoder emits for the rotations q: each row scaled by its own factor in [0.3, 3], the second sheared by 0.3 of the
+    first, rounded to float32"""
+    xy = _q_to_xy(q)
+    x = xy[..., 0, :] * rng.uniform(0.3, 3.0, q.shape[:-1] + (1,))
+    y = xy[..., 1, :] * rng.uniform(0.3, 3.0, q.shape[:-1] + (1,)) + 0.3 * x
+    return np.stack([x, y], axis=-2).astype(np.float32)
+
+
+def bvh_case(J, T, seed):
+    """-> dict(root_pos [T, 3], root_rot [T, 4], lpos [T, J, 3], ltxy [T, J, 2, 3] float32, branch [T, J]: the branch of
+    oracle.anim.q_from_xform each item takes).  Item i of the T J items belongs to group (i + seed) % 4: 0 rotations by up to 115 degrees about any axis
+    (trace branch), 1 / 2 / 3 rotations by 150 ... 210 degrees about an axis near x / y / z, every fourth of those by 180 degrees exactly (there the
+    trace formula divides by sqrt(tr + 1) = 0).  root_rot: general, norms 0.7 ... 1.3 (the decoder does not normalise)."""
+    from oracle import anim as oa
+    rng = np.random.default_rng(seed)
+    n = T * J
+    grp = (np.arange(n) + seed) % 4
+    axis = np.where((grp > 0)[:, None], np.eye(3)[np.maximum(grp - 1, 0)] + 0.15 * rng.uniform(-1.0, 1.0, (n, 3)),
+                    rng.standard_normal((n, 3)))
+    axis /= np.linalg.norm(axis, axis=-1, keepdims=True)
+    ang = np.where(grp > 0, rng.uniform(150.0, 210.0, n), rng.uniform(-115.0, 115.0, n))      # trace = 1 + 2 cos(angle) > 0 below 120
+    ang[((np.arange(n) // 4) % 4 == 0) & (grp > 0)] = 180.0
+    q = oa.q_from_angle_axis(np.radians(ang), axis).reshape(T, J, 4)
+    ltxy = _rows_from_quats(q, rng)
+    rr = rng.standard_normal((T, 4))
+    rr = rr / np.linalg.norm(rr, axis=-1, keepdims=True) * rng.uniform(0.7, 1.3, (T, 1))
+    return dict(root_pos=rng.normal(0.0, 50.0, (T, 3)).astype(np.float32), root_rot=rr.astype(np.float32),
+                lpos=rng.normal(0.0, 8.0, (T, J, 3)).astype(np.float32), ltxy=ltxy,
+                branch=oa.xform_branch(oa.xform_from_xy(ltxy.astype(np.float64))))
+
+
+BVH_START = (np.array([1.0, 2.0, 3.0]), np.array([0.6, 0.0, 0.8, 0.0]))      # the general start of test_pose_to_bvh_vs_oracle_and_reference
+BVH_STARTS = dict(none=None, identity=(np.zeros(3), np.array([1.0, 0.0, 0.0, 0.0])), general=BVH_START)
+
+
+def bvh_pole_case(order, k, seed=5):
+    """rows whose middle Euler angle (zyx: the y angle, xzy: the z angle, the asin of quat.to_euler) is +-(90 - 10^-k) degrees, k = None:
+    +-90 exactly; the other two angles random.  T = 8 frames of J = 3 joints; identity root with a float32 norm just above 1, so that
+    joint 0 of the exact-pole rows has |sin| > 1 before the clamp.  -> bvh_case's dict + middle [T, J] the angle asked for"""
+    from oracle import anim as oa
+    rng = np.random.default_rng(seed + (0 if k is None else k))
+    T, J = 8, 3
+    build, mid = BVH_EULER_INVERSE[order][1], 1      # the composition quat.to_euler(order) inverts; its middle factor is the asin's
+    e = rng.uniform(-180.0, 180.0, (T, J, 3))
+    e[..., mid] = (1.0 - 2.0 * (np.arange(T * J).reshape(T, J) % 2)) * (90.0 - (0.0 if k is None else 10.0 ** -k))
+    q = oa.q_from_euler(np.radians(e), build)
+    if k is None:
+        q[:, 0] = oa.q_from_euler(np.radians(e[:, 0] * (np.arange(3) == mid)), build)   # joint 0: the pole turn alone, w = +-component
+    xy = _q_to_xy(q).astype(np.float32)
+    rr = np.zeros((T, 4), np.float32)
+    rr[:, 0] = np.nextafter(np.float32(1.0), np.float32(2.0)) if k is None else 1.0
+    return dict(root_pos=np.zeros((T, 3), np.float32), root_rot=rr, lpos=rng.normal(0.0, 8.0, (T, J, 3)).astype(np.float32), ltxy=xy,
+                middle=e[..., mid])
+
+
+def bvh_raw_sin(case, order):
+    """the UNCLAMPED argument of the asin of quat.to_euler per item (the oracle's quaternions, joint 0 with the root folded in)"""
+    from oracle import anim as oa
+    q = oa.q_from_xform(oa.xform_from_xy(case["ltxy"].astype(np.float64)))
+    q[:, 0] = oa.q_mul(case["root_rot"].astype(np.float64), q[:, 0])
+    w, x, y, z = (q[..., i] for i in range(4))
+    return 2.0 * (x * y + z * w) if order == "xzy" else 2.0 * (w * y - z * x)
+
+
+def bvh_oracle(case, order="zyx", start=None, bug=None, rows=None):
+    """oracle.anim.bvh_channels of a bvh_case (rows: a slice of its frames, re-based on ITS first frame)"""
+    from oracle import anim as oa
+    r = slice(None) if rows is None else rows
+    kw = {} if start is None else dict(start_position=start[0], start_rotation=start[1])
+    return oa.bvh_channels(case["root_pos"][r], case["root_rot"][r], case["lpos"][r], case["ltxy"][r], order=order, bug=bug, **kw)
+
+
+# quat.to_euler("xzy") returns (x angle, y angle, z angle = the asin) of the rotation Ry Rz Rx -- NOT the inverse of from_euler("xzy"), which
+# composes Rx Rz Ry.  The exact inverse of each to_euler: (positions of the three outputs in from_euler's argument, its order).
+BVH_EULER_INVERSE = dict(zyx=((0, 1, 2), "zyx"), xzy=((1, 2, 0), "yzx"))
+BVH_ASIN_OUTPUT = dict(zyx=1, xzy=2)              # which output of to_euler is the asin (the "middle" angle)
+
+
+def euler_to_quat(deg, order):
+    """the rotation that quat.to_euler(order) turned into the degrees `deg` [..., 3]"""
+    from oracle import anim as oa
+    take, build = BVH_EULER_INVERSE[order]
+    return oa.q_from_euler(np.radians(np.asarray(deg, np.float64)[..., list(take)]), build)
+
+
+def euler_quat_error(got_deg, ref_deg, order):
+    """Euler degrees [..., 3] -> per item || q_got - s q_ref ||_inf, s the sign that aligns the two quaternions"""
+    qa, qb = euler_to_quat(got_deg, order), euler_to_quat(ref_deg, order)
+    s = np.where(np.sum(qa * qb, axis=-1, keepdims=True) < 0.0, -1.0, 1.0)
+    return np.abs(qa - s * qb).max(axis=-1)
+
+
+def euler_angle_error(got_deg, ref_deg, order):
+    """per item max |angle difference| in degrees (mod 360) where the oracle's middle angle is below 89 degrees, 0 elsewhere"""
+    mid = BVH_ASIN_OUTPUT[order]
+    diff = np.abs((got_deg - ref_deg + 180.0) % 360.0 - 180.0).max(axis=-1)
+    return np.where(np.abs(ref_deg[..., mid]) < 89.0, diff, 0.0)
+
+
+def bvh_table_seq(J):
+    """a joint sequence for zeggs_pose_to_bvh_table that is no identity: reversed, then rotated by one where J is odd so that the middle
+    joint moves too (J = 1: the only one there is)"""
+    seq = list(range(J))[::-1]
+    return seq[1:] + seq[:1] if J % 2 else seq
+
+
+def bvh_table_expected(case, seq, order, start, t0=0, t1=None, bug=None):
+    """rows [t0, t1) of the BVH motion block of the WHOLE clip: [root position | Euler angles of joint seq[0], seq[1], ...] from
+    the oracle's bvh_channels.  bug: "seq_ignored" | "chunk_reference" (the chunk re-based on its own first frame) |
+    "xzy_as_zyx" (negative controls)"""
+    t1 = len(case["lpos"]) if t1 is None else t1
+    if bug == "chunk_reference":
+        pos, eul = bvh_oracle(case, order, start, rows=slice(t0, t1))
+    else:
+        pos, eul = bvh_oracle(case, "zyx" if bug == "xzy_as_zyx" else order, start)
+        pos, eul = pos[t0:t1], eul[t0:t1]
+    eul = eul if bug == "seq_ignored" else eul[:, list(seq)]
+    return np.concatenate([pos[:, 0], eul.reshape(len(eul), -1)], axis=1)
+
+
+def bvh_table_errors(got, want, order):
+    """two motion-block tables [T, 3 + 3 J] -> (positions: max |got - want| / (1 + |want|), rotations: worst euler_quat_error, angles:
+    worst euler_angle_error)"""
+    T = len(want)
+    assert got.shape == want.shape, (got.shape, want.shape)
+    if not np.isfinite(got).all():
+        return float("inf"), float("inf"), float("inf")
+    ge, we = got[:, 3:].reshape(T, -1, 3), want[:, 3:].reshape(T, -1, 3)
+    return (float(np.max(np.abs(got[:, :3] - want[:, :3]) / (1.0 + np.abs(want[:, :3])))), float(euler_quat_error(ge, we, order).max()),
+            float(euler_angle_error(ge, we, order).max()))

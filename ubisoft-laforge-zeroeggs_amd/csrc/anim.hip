@@ -139,8 +139,17 @@ __global__ void anim_local_k(ZeggsAnimDims d, const SelState* st, const double* 
 __device__ __forceinline__ D3 pos_diff(const double* x, long stride, long f, double dt) {
   return (1.0 / dt) * (ld3(x + f * stride) - ld3(x + (f - 1) * stride));
 }
+// a b^-1 with every product rounded on its own, as NumPy forms it (quat.py mul): for a joint that keeps its pose the vector part
+// of q q^-1 is then EXACTLY zero and its lvrt exactly 0, as the reference's.  A fused w x - round(w x) leaves the rounding residue
+// of one product there (lvrt 8.8e-16 at dt = 1/60: tests/test_gpu_anim_dims.py).
+__device__ __forceinline__ DQ dq_mul_inv_unfused(DQ a, DQ b) {
+#pragma clang fp contract(off)
+  const double wx = a.w * b.x, xw = b.w * a.x, wy = a.w * b.y, yw = b.w * a.y, wz = a.w * b.z, zw = b.w * a.z;
+  const double yz = a.y * b.z, zy = a.z * b.y, zx = a.z * b.x, xz = a.x * b.z, xy = a.x * b.y, yx = a.y * b.x;
+  return DQ{a.w * b.w + a.x * b.x + a.y * b.y + a.z * b.z, (xw - wx) + (zy - yz), (yw - wy) + (xz - zx), (zw - wz) + (yx - xy)};
+}
 __device__ __forceinline__ D3 rot_diff(const double* q, long stride, long f, double dt) {
-  return (1.0 / dt) * dq_to_helical(dq_abs(dq_mul(ldq(q + f * stride), dq_inv(ldq(q + (f - 1) * stride)))));
+  return (1.0 / dt) * dq_to_helical(dq_abs(dq_mul_inv_unfused(ldq(q + f * stride), ldq(q + (f - 1) * stride))));
 }
 __global__ void anim_vel_k(ZeggsAnimDims d, ZeggsAnimOut o) {
   const long n = (long)d.N * (d.J + 1);   // item J of a frame = the root trajectory
@@ -270,6 +279,14 @@ AnimWs carve_anim(const ZeggsAnimDims& d, Arena& a) {
   return w;
 }
 inline dim3 grid_for(long n, int block) { long g = (n + block - 1) / block; return dim3((unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g))); }
+// The packed channel orders an entry point takes (checked on the host, ahead of any launch): to_euler has the two orders of
+// quat.py:111-127, from_euler any permutation of the three axes; 0 stands for "zyx" in both.
+inline bool to_euler_order_ok(int order) { return order == 0 || order == ORDER_ZYX || order == ORDER_XZY; }
+inline bool from_euler_order_ok(int order) {
+  if (order == 0) return true;
+  const int a = order & 3, b = (order >> 2) & 3, c = (order >> 4) & 3;
+  return (order >> 6) == 0 && a < 3 && b < 3 && c < 3 && a != b && a != c && b != c;
+}
 
 }  // namespace
 
@@ -288,6 +305,9 @@ extern "C" int zeggs_anim_features(const ZeggsAnimDims* dp, const int* parents, 
   ZCHECK(d.J >= 1 && d.hips >= 0 && d.hips < d.J && d.spine2 >= 0 && d.spine2 < d.J && d.head >= 0 && d.head < d.J,
          "anim_features: joint indices out of range");
   ZCHECK(d.dt > 0.0, "anim_features: dt must be positive");
+  ZCHECK(from_euler_order_ok(d.order),
+         "anim_features: order code %d is not a channel order (three 2-bit axis codes, a permutation of x = 0, y = 1, z = 2; 0 = zyx)",
+         d.order);
   Arena a(ws, ws_bytes);
   AnimWs w = carve_anim(d, a);
   ZCHECK(a.ok(), "anim_features: workspace too small (%zu < %zu)", ws_bytes, a.off);
@@ -313,6 +333,8 @@ extern "C" int zeggs_pose_to_bvh(const ZeggsBvhDims* dp, const float* root_pos, 
                                  const float* ltxy, double* positions, double* euler_deg, void* stream) {
   const ZeggsBvhDims& d = *dp;
   ZCHECK(d.T >= 1 && d.J >= 1, "pose_to_bvh: empty clip");
+  ZCHECK(to_euler_order_ok(d.order), "pose_to_bvh: cannot convert to order code %d: only zyx (0 or %d) and xzy (%d) convert", d.order,
+         ORDER_ZYX, ORDER_XZY);
   hipLaunchKernelGGL(pose_to_bvh_k, grid_for((long)d.T * d.J, 256), dim3(256), 0, (hipStream_t)stream, d, root_pos,
                      root_rot, lpos, ltxy, positions, euler_deg);
   ZLAUNCH_CHECK("pose_to_bvh");
@@ -325,6 +347,8 @@ extern "C" int zeggs_pose_to_bvh_table(const ZeggsBvhDims* dp, const float* root
   const ZeggsBvhDims& d = *dp;
   ZCHECK(d.T >= 1 && d.J >= 1, "pose_to_bvh_table: empty clip");
   ZCHECK(seq != nullptr && table != nullptr, "pose_to_bvh_table: seq / table missing");
+  ZCHECK(to_euler_order_ok(d.order), "pose_to_bvh_table: cannot convert to order code %d: only zyx (0 or %d) and xzy (%d) convert",
+         d.order, ORDER_ZYX, ORDER_XZY);
   hipLaunchKernelGGL(pose_to_bvh_table_k, grid_for((long)d.T * d.J, 256), dim3(256), 0, (hipStream_t)stream, d, root_pos,
                      root_rot, lpos, ltxy, ref_root_pos ? ref_root_pos : root_pos, ref_root_rot ? ref_root_rot : root_rot, seq,
                      table);
