@@ -778,7 +778,8 @@ int zeggs_spline_resample(const double* y, long N, int W, long M, double* out, v
 size_t zeggs_rot_stretch_workspace_bytes(long N, int J, long M);
 int zeggs_rot_stretch(const double* euler_deg, long N, int J, long M, int order, double* out_deg, void* ws, size_t ws_bytes, void* stream);
 /* out[i] = wav[start + i] inside the union of the sample intervals [intervals[2j], intervals[2j+1]) (int64 [n, 2]), 0 outside, for
- * start + i < min(end, n_wav) (data_pipeline.py:306-332, 403); float32 and / or float64 output (either may be NULL). */
+ * start + i < min(end, n_wav) (data_pipeline.py:306-332, 403); float32 and / or float64 output (either may be NULL; an empty cut
+ * writes nothing, returns 0 and needs neither). */
 int zeggs_audio_prepare(const float* wav, long n_wav, const long* intervals, int n_intervals, long start, long end, float* out_f32,
                         double* out_f64, void* stream);
 /* The centring of a trimmed take, in place (data_pipeline.py:449-459): positions / euler_deg [N, J, 3] float64; joint 0 is moved by

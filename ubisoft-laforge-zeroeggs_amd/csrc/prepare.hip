@@ -221,9 +221,9 @@ extern "C" int zeggs_audio_prepare(const float* wav, long n_wav, const long* int
                                    float* out_f32, double* out_f64, void* stream) {
   ZCHECK(n_wav >= 0 && start >= 0 && end >= start, "audio_prepare: bad range [%ld, %ld) of %ld samples", start, end, n_wav);
   ZCHECK(n_intervals >= 0 && n_intervals <= 4096, "audio_prepare: 0 .. 4096 intervals, got %d", n_intervals);
-  ZCHECK(out_f32 != nullptr || out_f64 != nullptr, "audio_prepare: no output");
   const long n_out = (end < n_wav ? end : n_wav) - start;            // (a slice past the end is cut short, as numpy's)
-  if (n_out <= 0) return 0;
+  if (n_out <= 0) return 0;                                          // (an empty cut: nothing to write, an empty tensor has no address)
+  ZCHECK(out_f32 != nullptr || out_f64 != nullptr, "audio_prepare: no output");
   hipLaunchKernelGGL(audio_prepare_k, grid_for(n_out, 256), dim3(256), (size_t)2 * n_intervals * sizeof(long), (hipStream_t)stream, wav,
                      n_wav, intervals, n_intervals, start, n_out, out_f32, out_f64);
   ZLAUNCH_CHECK("audio_prepare");
