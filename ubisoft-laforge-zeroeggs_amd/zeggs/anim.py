@@ -385,3 +385,257 @@ def write_bvh_channels(filename, positions, euler, parents, names, order, dt, te
     positions = positions.cpu().numpy()
     bvh_save(filename, dict(order=order, offsets=positions[0], names=names, frametime=dt, parents=parents,
                             positions=positions, rotations=euler.cpu().numpy()), text="host")
+
+
+# ----------------------------------------------------------------------------- left/right mirroring (csrc/mirror.hip)
+# The pipeline's frame is fixed: forward +z, up +y, so left/right is x and the mirror plane is x = 0.  With M = diag(-1, 1, 1),
+# M R_axis(t) M = R_axis(+t) about x and R_axis(-t) about y and z, factor by factor in any Euler order: a mirrored take is the
+# original with paired joints exchanged, x positions negated and the y / z angles negated -- a permutation plus sign flips, for
+# the BVH channels and, one level up, for every feature array.  One int32 per OUTPUT column says it: the source column in the
+# low 31 bits, the sign flip in bit 31 (include/zeggs_hip_mirror.h).
+_SEGMENT_SIGNS = {"vec": (-1, 1, 1),                  # a true vector: position, velocity, direction
+                  "axial": (1, -1, -1),               # a pseudo-vector: angular velocity, helical
+                  "quat": (1, 1, -1, -1),             # w, x, y, z
+                  "txy": (1, -1, -1, -1, 1, 1)}       # the two-axis rotation rows: R ex mirrors as an axial, R ey as a vector
+_FEATURE_KINDS = {"pos": "vec", "vel": "vec", "dir": "vec", "vrt": "axial", "rot": "quat", "txy": "txy"}     # by the name's ending
+
+
+def _mirror_axis(axis):
+    if axis != "x":
+        raise NotImplementedError(f"mirror: the mirror plane is x = 0 (forward +z, up +y); axis={axis!r} is not implemented")
+
+
+def segment_signs(kind, width=None):
+    """signs of one block of a segment kind: vec | axial | quat | txy | euler:<order> | same (width floats, default 1)"""
+    if kind in _SEGMENT_SIGNS:
+        return _SEGMENT_SIGNS[kind]
+    if kind.startswith("euler:"):
+        order_code(kind[6:])                           # (raises for anything but a permutation of xyz)
+        return tuple(1 if c == "x" else -1 for c in kind[6:])     # by the AXIS of a channel, not by its place
+    if kind == "same":
+        return (1,) * int(1 if width is None else width)
+    raise ValueError(f"mirror: unknown segment kind {kind!r} (vec, axial, quat, txy, euler:<order>, same)")
+
+
+def mirror_pairs(names, parents, left="Left", right="Right", axis="x"):
+    """-> pair [J]: the joint a joint exchanges with under the left/right mirror, itself for a joint without a side.  A sided joint
+    is one whose name holds `left` or `right`; its partner has the other word there.  ValueError (naming the joint) when a sided
+    joint has no partner, or when the pairing is no automorphism of the tree: parents[pair[j]] != pair[parents[j]]."""
+    _mirror_axis(axis)
+    names = list(names)
+    index = {n: i for i, n in enumerate(names)}
+    pair = []
+    for j, n in enumerate(names):
+        other = n.replace(left, right, 1) if left in n else (n.replace(right, left, 1) if right in n else n)
+        if other not in index:
+            raise ValueError(f"mirror_pairs: joint {n!r} has no partner ({other!r} is not a joint)")
+        pair.append(index[other])
+    return _check_pairs(pair, names, parents)
+
+
+def _check_pairs(pair, names, parents):
+    J = len(parents)
+    name = (lambda j: repr(names[j])) if names is not None else (lambda j: str(j))
+    if len(pair) != J or any(not (0 <= int(p) < J) for p in pair):
+        raise ValueError(f"mirror: a pairing of {len(pair)} entries for {J} joints (each 0 .. {J - 1})")
+    pair = [int(p) for p in pair]
+    for j in range(J):
+        if pair[pair[j]] != j:
+            raise ValueError(f"mirror: joint {name(j)} pairs with {name(pair[j])}, which pairs with {name(pair[pair[j]])}")
+        pj, pp = int(parents[j]), int(parents[pair[j]])
+        if pp != (pair[pj] if pj >= 0 else -1):
+            raise ValueError(f"mirror: joint {name(j)} and its partner {name(pair[j])} hang under parents that are not partners "
+                             "(the pairing is not an automorphism of the tree)")
+    return pair
+
+
+def resolve_pairs(pairs, names, parents, axis="x"):
+    """what `pairs=` takes everywhere: "auto" (mirror_pairs by the names), an index list [J], or a dict of partners by name or
+    index (one direction is enough; joints it does not mention pair with themselves) -> the checked index list"""
+    _mirror_axis(axis)
+    if isinstance(pairs, str):
+        if pairs != "auto":
+            raise ValueError(f"mirror: pairs={pairs!r} ('auto', a list or a dict)")
+        return mirror_pairs(names, parents)
+    if isinstance(pairs, dict):
+        idx = lambda k: list(names).index(k) if isinstance(k, str) else int(k)  # noqa: E731
+        out = list(range(len(parents)))
+        for a, b in pairs.items():
+            out[idx(a)], out[idx(b)] = idx(b), idx(a)
+        pairs = out
+    return _check_pairs(list(pairs), None if names is None else list(names), parents)
+
+
+def named_layout(name, order="zyx"):
+    """The row layouts the code base already states, as segment lists for mirror_table -- all of UN-normalised rows:
+      "rotations" / "positions"   the BVH channel tables [F, J, 3] of bvh_load (euler degrees in channel order `order`; vectors)
+      a feature of ANIM_OUT       "root_pos" .. "gaze_dir": one of the 16 arrays of preprocess_animation (kind by the name's
+                                  ending, width and per-joint from ANIM_OUT); "Y_<feature>": the dataset key of the same array
+      "decoder_in" / "example"    the decoder's input row of vectorize_input and the exemplar row of generate._example_features:
+                                  the arrays of data_pipeline._IN_STATS one behind another, [9 + 15 J]
+      "decoder_out"               the pose row of devectorize_output: data_pipeline._OUT_STATS, [6 + 15 J]"""
+    if name == "rotations":
+        return [("euler:" + order, "joint")]
+    if name == "positions":
+        return [("vec", "joint")]
+    if name in ("decoder_in", "example", "decoder_out"):
+        from . import data_pipeline
+        keys = data_pipeline._OUT_STATS if name == "decoder_out" else data_pipeline._IN_STATS
+        return [seg for k in keys for seg in named_layout(k)]
+    feature = name[2:] if name.startswith("Y_") else name
+    widths = {n: w for n, w, _ in ANIM_OUT}
+    if feature not in widths:
+        raise ValueError(f"mirror: no row layout called {name!r}")
+    kind = _FEATURE_KINDS[feature[-3:]]
+    assert len(segment_signs(kind)) == abs(widths[feature]), feature
+    return [(kind, "joint" if widths[feature] < 0 else "single")]
+
+
+def mirror_table(layout, pairs, axis="x", order="zyx"):
+    """-> int32 [cols]: the signed column table of a row layout (include/zeggs_hip_mirror.h).  `layout`: a name of named_layout
+    (`order`: the channel order of "rotations") or a sequence of segments (kind, scope[, width]) -- kind as in segment_signs,
+    scope "joint" (one block per joint in joint order, block j read from block pairs[j]) or "single" (one block), width for
+    "same".  `pairs`: the checked index list (mirror_pairs / resolve_pairs)."""
+    _mirror_axis(axis)
+    segments = named_layout(layout, order) if isinstance(layout, str) else list(layout)
+    pairs = [int(p) for p in pairs]
+    if sorted(pairs) != list(range(len(pairs))):
+        raise ValueError("mirror_table: pairs is not a permutation of the joints")
+    table, off = [], 0
+    for seg in segments:
+        kind, scope = seg[0], seg[1]
+        signs = segment_signs(kind, seg[2] if len(seg) > 2 else None)
+        if scope not in ("joint", "single"):
+            raise ValueError(f"mirror_table: scope {scope!r} of segment {seg!r} ('joint' or 'single')")
+        blocks = pairs if scope == "joint" else [0]
+        w = len(signs)
+        for src in blocks:
+            table += [(off + src * w + k) | (0x80000000 if s < 0 else 0) for k, s in enumerate(signs)]
+        off += w * len(blocks)
+    return np.asarray(table, dtype=np.uint32).view(np.int32)
+
+
+def check_mirror_table(table):
+    """ValueError unless every column is the source of exactly one column (the check the library makes before it builds a plan)"""
+    table = np.ascontiguousarray(table, dtype=np.int32)
+    try:
+        api().zeggs_mirror_table_check(table.ctypes.data, int(table.size))
+    except RuntimeError as e:
+        raise ValueError(str(e)) from None
+    return table
+
+
+def mirror_rows_host(x, table):
+    """the kernel's statement in NumPy: out[..., c] = x[..., source(c)] with the sign bit flipped where bit 31 of table[c] is set
+    (float32 or float64; an exclusive-or on the integer view, so -0.0, infinities and NaN payloads keep their other bits)"""
+    x = np.ascontiguousarray(x)
+    bits = {4: np.uint32, 8: np.uint64}[x.dtype.itemsize]
+    t = np.asarray(table, dtype=np.int32).view(np.uint32)
+    flat = x.reshape(-1, t.size).view(bits)
+    flip = ((t >> 31).astype(bits) << bits(8 * x.dtype.itemsize - 1))
+    return (flat[:, t & 0x7FFFFFFF] ^ flip[None]).view(x.dtype).reshape(x.shape)
+
+
+class _MirrorPlan:
+    """a plan of the library (the table on the device); freed with the object"""
+
+    def __init__(self, table):
+        self.table = np.ascontiguousarray(table, dtype=np.int32)
+        self.handle = C.c_void_p()
+        api().zeggs_mirror_plan_create(self.table.ctypes.data, int(self.table.size), C.addressof(self.handle))
+
+    def __del__(self):
+        try:
+            if self.handle:
+                api().zeggs_mirror_plan_free(self.handle)
+        except Exception:          # (interpreter shutdown)
+            pass
+
+
+_MIRROR_PLANS = {}            # (device, table bytes) -> plan, the most recently used last; at most _MIRROR_PLANS_MAX of them
+_MIRROR_PLANS_MAX = 64        # (a rig has some twenty layouts; an evicted plan is freed when its last user lets go of it)
+_MIRROR_TABLES = {}           # (layout name, pairs, order) -> table: building one is a Python loop over its columns
+
+
+def _mirror_plan(table, device):
+    key = (device.index if device.index is not None else torch.cuda.current_device(), table.tobytes())
+    plan = _MIRROR_PLANS.pop(key, None)
+    if plan is None:
+        with torch.cuda.device(key[0]):
+            plan = _MirrorPlan(table)
+        while len(_MIRROR_PLANS) >= _MIRROR_PLANS_MAX:
+            del _MIRROR_PLANS[next(iter(_MIRROR_PLANS))]
+    _MIRROR_PLANS[key] = plan
+    return plan
+
+
+def _mirror_table_of(layout, pairs, axis, order):
+    """mirror_table, kept per (name, pairs, order) for the named layouts"""
+    if not isinstance(layout, str):
+        return mirror_table(layout, pairs, axis, order)
+    key = (layout, tuple(int(p) for p in pairs), order)
+    table = _MIRROR_TABLES.get(key)
+    if table is None:
+        if len(_MIRROR_TABLES) >= _MIRROR_PLANS_MAX:
+            _MIRROR_TABLES.clear()
+        table = _MIRROR_TABLES[key] = mirror_table(layout, pairs, axis, order)
+    return table
+
+
+def mirror_rows(x, layout, pairs=None, axis="x", order="zyx"):
+    """x: device tensor (float32 or float64) whose trailing dimensions flatten to the rows of `layout` -> its left/right mirror, a new
+    tensor of the same shape: ONE launch of the signed column gather.  `layout`: as in mirror_table, or a ready int32 table
+    (`pairs` is then not needed).  The table of a named layout is built on its first use and kept per (name, pairs, order); the
+    plan -- the table on the device -- is made on first use of a table and kept, the 64 most recently used per process."""
+    _mirror_axis(axis)
+    if not (torch.is_tensor(x) and x.is_cuda and x.dtype in (torch.float32, torch.float64)):
+        raise RuntimeError("mirror_rows: a float32 or float64 tensor on the GPU is needed (the HIP engine has no CPU path)")
+    table = np.ascontiguousarray(layout, np.int32) if isinstance(layout, np.ndarray) else _mirror_table_of(layout, pairs, axis, order)
+    cols = int(table.size)
+    trailing = list(np.cumprod([1] + list(x.shape[::-1])))          # a row is some number of whole trailing dimensions
+    if cols not in trailing:
+        raise ValueError(f"mirror_rows: a tensor of shape {tuple(x.shape)} does not hold rows of {cols} columns")
+    x = x.contiguous()
+    out = torch.empty_like(x)
+    plan = _mirror_plan(table, x.device)
+    with torch.cuda.device(x.device):
+        api().zeggs_mirror_rows(plan.handle, x, out, x.numel() // cols, x.element_size(), ops._stream())
+    return out
+
+
+def rig_asymmetry(offsets, pairs):
+    """the largest distance between a joint's offset and the reflection of its partner's offset, relative to the bone's length
+    (0 for a rig that is its own mirror image; a bone of length 0 counts with a length of 1)"""
+    off = np.asarray(offsets, dtype=np.float64)
+    if off.size == 0:
+        return 0.0
+    refl = off[np.asarray(pairs)] * np.array([-1.0, 1.0, 1.0])
+    length = np.linalg.norm(off, axis=-1)
+    return float(np.max(np.linalg.norm(off - refl, axis=-1) / np.where(length > 0.0, length, 1.0)))
+
+
+def mirror_take(take, pairs="auto", symmetry_tol=None, axis="x"):
+    """take: the dict of bvh_load -- `rotations` / `positions` [F, J, 3] as host arrays or as device tensors (float32 / float64)
+    -> the left/right mirrored take: paired joints exchanged, x positions and the angles about y and z negated (exactly: only
+    sign bits change), `offsets[pair]` with x negated, the same names, parents, order and frametime; device tensors go through
+    the kernel (one launch each) and stay on the device.  `take["asymmetry"]` reports rig_asymmetry of the ORIGINAL's offsets;
+    an asymmetric rig is mirrored all the same (its bones then change length with the side) unless `symmetry_tol` is given:
+    ValueError above it."""
+    _mirror_axis(axis)
+    pair = resolve_pairs(pairs, take.get("names"), take["parents"])
+    offsets = take["offsets"].cpu().numpy() if torch.is_tensor(take["offsets"]) else np.asarray(take["offsets"])
+    asym = rig_asymmetry(offsets, pair)
+    if symmetry_tol is not None and not asym <= symmetry_tol:
+        raise ValueError(f"mirror_take: the rig's asymmetry is {asym:.6g}, above symmetry_tol = {symmetry_tol}")
+    order = take.get("order", "zyx")
+    tables = {"rotations": mirror_table("rotations", pair, order=order), "positions": mirror_table("positions", pair)}
+    out = dict(take)
+    for k, t in tables.items():
+        a = take[k]
+        if torch.is_tensor(a) and a.is_cuda:
+            out[k] = mirror_rows(a, t)
+        else:
+            out[k] = mirror_rows_host(a.numpy() if torch.is_tensor(a) else np.asarray(a), t)
+    out["offsets"] = mirror_rows_host(np.ascontiguousarray(offsets).reshape(1, -1), tables["positions"]).reshape(offsets.shape)
+    out["asymmetry"] = asym
+    return out

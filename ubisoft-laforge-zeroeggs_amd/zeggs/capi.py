@@ -18,7 +18,8 @@ RT_STRUCTS / RT_PROTOTYPES (tests/test_live_retime_cpu.py), the seventh, include
 (tests/test_live_refilter_cpu.py), the eighth, include/zeggs_hip_snapshot.h, SNAP_STRUCTS / SNAP_PROTOTYPES
 (tests/test_live_snapshot_cpu.py), the ninth, include/zeggs_hip_gaze.h, GZ_STRUCTS / GZ_PROTOTYPES (tests/test_live_gaze_cpu.py),
 the tenth, include/zeggs_hip_styles.h, SB_STRUCTS / SB_PROTOTYPES (tests/test_live_styles_cpu.py), the eleventh,
-include/zeggs_hip_plant.h, PL_STRUCTS / PL_PROTOTYPES (tests/test_live_plant_cpu.py): same loader.  torch is imported when a tensor is first converted, not
+include/zeggs_hip_plant.h, PL_STRUCTS / PL_PROTOTYPES (tests/test_live_plant_cpu.py), the twelfth, include/zeggs_hip_mirror.h,
+MR_PROTOTYPES (tests/test_mirror_cpu.py; it has no structs): same loader.  torch is imported when a tensor is first converted, not
 when this module is.
 """
 import ctypes as C
@@ -390,6 +391,18 @@ PL_PROTOTYPES = {
 }
 
 
+# ----------------------------------------------------------------------------- the twelfth header (include/zeggs_hip_mirror.h)
+# The signed column gather behind left/right mirroring (tests/test_mirror_cpu.py compares this table with the header).
+MR_PROTOTYPES = {
+    "zeggs_mirror_version": "int:",
+    "zeggs_mirror_table_check": "status: host* int",              # table: a HOST array of int32
+    "zeggs_mirror_plan_create": "status: host* int host*",        # table (HOST), cols, void** plan
+    "zeggs_mirror_plan_free": "status: host*",
+    "zeggs_mirror_plan_cols": "mask: host*",
+    "zeggs_mirror_rows": "status: host* any* any* long int stream",
+}
+
+
 # ----------------------------------------------------------------------------- parameter types
 class DevicePointer(C.c_void_p):
     """A device-pointer parameter: takes a tensor (on a GPU, contiguous, one of `dtypes`), None, a c_void_p or an address."""
@@ -435,7 +448,7 @@ RETURNS = {"status": C.c_int, "mask": C.c_int, "int": C.c_int, "long": C.c_long,
 def signature(name):
     """-> (return kind, [parameter kinds]) of a row"""
     ret, _, params = (PROTOTYPES.get(name) or EXT_PROTOTYPES.get(name) or LOUD_PROTOTYPES.get(name) or RS_PROTOTYPES.get(name) or
-                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES.get(name) or SB_PROTOTYPES.get(name) or PL_PROTOTYPES[name]).partition(":")
+                       FR_PROTOTYPES.get(name) or RT_PROTOTYPES.get(name) or RF_PROTOTYPES.get(name) or SNAP_PROTOTYPES.get(name) or GZ_PROTOTYPES.get(name) or SB_PROTOTYPES.get(name) or PL_PROTOTYPES.get(name) or MR_PROTOTYPES[name]).partition(":")
     return ret, params.split()
 
 
@@ -473,7 +486,7 @@ def _load():
                 f"{LIB_PATH} not found: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(hipcc --offload-arch=gfx950). The ZeroEGGS MI355X engine has no CPU fallback.")
         typed, plain = _Typed(str(LIB_PATH)), C.CDLL(str(LIB_PATH))
-        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES) if not hasattr(plain, n)]
+        missing = [n for n in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES, *MR_PROTOTYPES) if not hasattr(plain, n)]
         if missing:
             raise HipLibraryMissing(f"{LIB_PATH} is older than this package (no {', '.join(missing)}): rebuild it")
         last_error = typed.zeggs_last_error
@@ -485,7 +498,7 @@ def _load():
 
         def mask(rc, fn, args):
             return rc if rc >= 0 else status(rc, fn, args)
-        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES):
+        for name in (*PROTOTYPES, *EXT_PROTOTYPES, *LOUD_PROTOTYPES, *RS_PROTOTYPES, *FR_PROTOTYPES, *RT_PROTOTYPES, *RF_PROTOTYPES, *SNAP_PROTOTYPES, *GZ_PROTOTYPES, *SB_PROTOTYPES, *PL_PROTOTYPES, *MR_PROTOTYPES):
             ret, params = signature(name)
             fn = getattr(typed, name)
             fn.argtypes, fn.restype = [KINDS[k] for k in params], RETURNS[ret]

@@ -52,6 +52,8 @@ def cmd_prepare(a):
     conf = json.loads(Path(a.conf).read_text())
     if a.base_path:
         conf["base_path"] = a.base_path
+    if a.mirror:
+        conf["mirror"] = True
     data_pipeline(conf, log=lambda line: print(line, flush=True))
     return 0
 
@@ -89,14 +91,14 @@ def cmd_generate(a):
         from .generate import Job, generate_gestures
         print(f"{len(jobs)} jobs, {a.batch} clips per decode", flush=True)
         generate_gestures([Job(j["audio"], [j["style"]], file_name=j["file_name"], first_pose=j["first_pose"],
-                               temperature=j["temperature"], seed=j["seed"]) for j in jobs],
+                               temperature=j["temperature"], seed=j["seed"], mirror_style=a.mirror_style) for j in jobs],
                           network_path=network, data_path=data, results_path=results, style_encoding_type=kind, batch=a.batch)
         return 0
     for k, j in enumerate(jobs):
         print(f"[{k + 1}/{len(jobs)}] {j['audio']}  style {j['style']}", flush=True)
         generate_gesture(audio_file=j["audio"], styles=[j["style"]], network_path=network, data_path=data, results_path=results,
                          style_encoding_type=kind, file_name=j["file_name"], first_pose=j["first_pose"],
-                         temperature=j["temperature"], seed=j["seed"], use_gpu=True)
+                         temperature=j["temperature"], seed=j["seed"], use_gpu=True, mirror_style=a.mirror_style)
     return 0
 
 
@@ -152,6 +154,7 @@ def main(argv=None):
     d = sub.add_parser("prepare", help="raw takes -> processed_data.npz, stats.npz, data_definition.json (reference: python data_pipeline.py)")
     d.add_argument("-c", "--conf", required=True, help="pipeline conf (configs/data_pipeline_conf_v*.json layout)")
     d.add_argument("--base-path", default=None, help="overrides the conf's base_path (the directory that holds original/ and the info CSV)")
+    d.add_argument("--mirror", action="store_true", help="add every take's left/right reflection to the dataset (the conf key `mirror`: true)")
     d.set_defaults(fn=cmd_prepare)
     t = sub.add_parser("train", help="train the networks (reference: python main.py -o ... -n ...)")
     t.add_argument("-o", "--options", required=True, help="options file (configs_v*.json layout)")
@@ -169,6 +172,7 @@ def main(argv=None):
     g.add_argument("-r", "--seed", type=int, nargs="?", default=1234)
     g.add_argument("-g", "--use_gpu", action="store_true", help="accepted for compatibility: the engine always runs on the GPU")
     g.add_argument("-f", "--frames", type=int, nargs=2, help="start and end frame of the exemplar")
+    g.add_argument("--mirror-style", action="store_true", help="use the left/right reflection of every style exemplar")
     g.add_argument("-c", "--csv", help="CSV with one audio / style pair per row (evaluation_example_based.csv layout)")
     g.add_argument("-b", "--batch", type=int, default=0, metavar="N",
                    help="decode the jobs N clips at a time on the weight-stationary batch sweep (default: one clip per decode)")

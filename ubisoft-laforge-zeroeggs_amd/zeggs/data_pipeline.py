@@ -20,7 +20,10 @@ Differences from the reference, on purpose:
     `ranges_valid` is then an empty [0, 2] array;
   * `visualize_spectrogram`, `visualize_gaze` and `save_normalized_animations` raise NotImplementedError, and `data_info.html`
     is not written (cosmetics);
-  * WAV files must already have `audio_conf.sampling_rate` (the reference shells out to SoX otherwise).
+  * WAV files must already have `audio_conf.sampling_rate` (the reference shells out to SoX otherwise);
+  * the conf key `mirror` (the reference has none: it expects `*_mirror.bvh` files, made outside its code base, in the corpus): every
+    info row is followed by its left/right reflection, made on the device from the loaded take (zeggs.anim.mirror_take) and taken
+    through the same stages as any take, with the capture's audio side computed once.  Without the key nothing changes.
 """
 import csv
 import ctypes as C
@@ -130,6 +133,47 @@ def check_conf(conf):
     for k in NOT_IMPLEMENTED_KEYS:
         if conf.get(k, False):
             raise NotImplementedError(f"data_pipeline: conf key {k!r} is not supported (plots and normalised BVH dumps are not ported)")
+    mirror_options(conf)
+
+
+MIRROR_SUFFIX = "_mirror"
+
+
+def mirror_options(conf):
+    """the conf key `mirror` (an addition: the reference expects the mirrored files to exist) -> None (absent or false: the pipeline
+    as it is) or dict(suffix, pairs); true is {"suffix": "_mirror", "pairs": "auto"}.  ValueError for anything malformed."""
+    m = conf.get("mirror", False)
+    if m is False or m is None:
+        return None
+    if m is True:
+        m = {}
+    if not isinstance(m, dict) or set(m) - {"suffix", "pairs"}:
+        raise ValueError(f"data_pipeline: conf key 'mirror' must be false, true or {{'suffix': ..., 'pairs': ...}}, not {m!r}")
+    suffix, pairs = m.get("suffix", MIRROR_SUFFIX), m.get("pairs", "auto")
+    if not isinstance(suffix, str) or not suffix or "." in suffix or "/" in suffix:
+        raise ValueError(f"data_pipeline: mirror suffix {suffix!r} (a non-empty string without '.' or '/')")
+    if not (pairs == "auto" or (isinstance(pairs, (list, tuple)) and all(isinstance(p, int) and not isinstance(p, bool) for p in pairs)) or
+            (isinstance(pairs, dict) and all(isinstance(v, (str, int)) for kv in pairs.items() for v in kv))):
+        raise ValueError(f"data_pipeline: mirror pairs {pairs!r} ('auto', a list of joint indices or a dict of partners)")
+    return dict(suffix=suffix, pairs=pairs)
+
+
+def mirrored_name(anim_bvh, suffix):
+    """'take.bvh' -> 'take_mirror.bvh'.  The stem ends at the FIRST dot, as in trimmed_name (the reference's `split(".")[0]`), so that
+    the trimmed files of a take and of its reflection get different names: 'take.v2.bvh' -> 'take_mirror.v2.bvh'"""
+    stem, dot, ext = str(anim_bvh).partition(".")
+    return stem + suffix + dot + ext
+
+
+def mirror_plan_of_info(info, suffix):
+    """-> per info row the `anim_bvh` its mirrored take gets, None for a row that gets none: its name already carries the suffix, or
+    the mirrored name is listed itself"""
+    listed = {str(r["anim_bvh"]) for r in info}
+    out = []
+    for r in info:
+        name = mirrored_name(r["anim_bvh"], suffix)
+        out.append(None if str(r["anim_bvh"]).partition(".")[0].endswith(suffix) or name in listed else name)
+    return out
 
 
 # ----------------------------------------------------------------------------- device kernels (csrc/prepare.hip)
@@ -271,6 +315,73 @@ def write_wav(path, samples, fs):
     wavfile.write(str(path), fs, (np.asarray(samples) * 2 ** 15).astype("int16"))
 
 
+def _device_statistics(arrays, mask):
+    """arrays: key -> device float32 rows -> masked_stats of the audio rows and of every array of _IN_STATS (device tensors)"""
+    return {k: masked_stats(arrays[k], mask) for k in ("X_audio_features",) + _IN_STATS}
+
+
+def _normalisation(where):
+    """the statistics of _device_statistics, downloaded -> the six normalisation entries of stats.npz in their order"""
+    f32 = np.float32
+    st = {k: tuple(t.cpu().numpy() for t in v) for k, v in where.items()}
+    audio_mean, _, audio_pooled = st["X_audio_features"]
+    in_mean = np.hstack([st[k][0] for k in _IN_STATS]).astype(f32)
+    in_std = np.hstack([np.repeat(st[k][2] + 1e-10, len(st[k][0])) for k in _IN_STATS]).astype(f32)     # pooled scalars + eps
+    out_mean = np.hstack([st[k][0] for k in _OUT_STATS]).astype(f32)
+    out_std = np.hstack([st[k][1] for k in _OUT_STATS]).astype(f32)                                     # per column, no eps
+    return dict(audio_input_mean=audio_mean.astype(f32), audio_input_std=f32(audio_pooled[0] + 1e-10), anim_input_mean=in_mean,
+                anim_input_std=in_std, anim_output_mean=out_mean, anim_output_std=out_std)
+
+
+_PROCESSED_KEYS = ("X_audio_features", "Y_root_pos", "Y_root_rot", "Y_root_vel", "Y_root_vrt", "Y_lpos", "Y_ltxy", "Y_lvel", "Y_lvrt",
+                   "Y_gaze_pos")
+
+
+def mirror_processed(processed, definition, pairs="auto", ranges_per_take=1, device="cuda"):
+    """A processed dataset WITHOUT mirrored ranges (the dict of processed_data.npz) -> the dataset `data_pipeline` makes of the same
+    corpus with `mirror`: for users who have a processed_data.npz and no raw takes.  The `Y_*` rows go through anim.mirror_rows
+    (one launch per array), the audio rows are copied; every take's ranges are followed by the ranges of its reflection --
+    `ranges_per_take` consecutive ranges are one take: the number of `len_ratios` the dataset was made with -- with the same
+    labels, and the statistics are recomputed over the new train ranges with masked_stats.  The dataset does not store the gaze
+    direction (only its statistics): it is restated here from the stored float32 root and gaze rows, so its four statistics
+    agree with a pipeline run to float32 rounding, not bit for bit; every other number is the pipeline's.
+    -> (processed, definition): new dicts, the inputs are not modified."""
+    import torch
+    from . import anim as zanim
+    if not torch.cuda.is_available():
+        raise RuntimeError("mirror_processed: no GPU (the HIP engine has no CPU path)")
+    dev = torch.device(device)
+    pair = zanim.resolve_pairs(pairs, definition["bone_names"], definition["parents"])
+    k = int(ranges_per_take)
+    tr, va = np.asarray(processed["ranges_train"]).reshape(-1, 2), np.asarray(processed["ranges_valid"]).reshape(-1, 2)
+    spans = sorted([(int(s), int(e), False, int(l)) for (s, e), l in zip(tr, processed["ranges_train_labels"])] +
+                   [(int(s), int(e), True, int(l)) for (s, e), l in zip(va, processed["ranges_valid_labels"])])
+    if k < 1 or len(spans) % k:
+        raise ValueError(f"mirror_processed: {len(spans)} ranges are not whole takes of {k} ranges each")
+    up = {key: torch.as_tensor(np.ascontiguousarray(processed[key], dtype=np.float32)).to(dev) for key in _PROCESSED_KEYS}
+    both = {key: (t, t if key == "X_audio_features" else zanim.mirror_rows(t, key, pair)) for key, t in up.items()}
+    # rows: per take its ranges, then the same ranges of the reflection
+    pieces, ranges, names = [], Ranges(), list(definition["label_names"])
+    for g in range(0, len(spans), k):
+        for side in (0, 1):
+            for s, e, valid, label in spans[g:g + k]:
+                pieces.append((side, s, e))
+                ranges.add(e - s, names[label], valid)
+    new = {key: torch.cat([both[key][side][s:e] for side, s, e in pieces]) for key in _PROCESSED_KEYS}
+    ranges_train, ranges_valid, train_labels, valid_labels, new_names = ranges.finish()
+    relabel = lambda idx: np.asarray([names.index(new_names[i]) for i in idx], dtype=np.int32)  # noqa: E731   (the definition keeps its order)
+    # the gaze direction: inverse root rotation times (gaze - root), as preprocess_animation states it, from the stored rows
+    q, v = new["Y_root_rot"].double(), new["Y_gaze_pos"].double() - new["Y_root_pos"].double()
+    qv = -q[:, 1:]
+    t = 2.0 * torch.linalg.cross(qv, v)
+    arrays = dict(new, Y_gaze_dir=(v + q[:, :1] * t + torch.linalg.cross(qv, t)).float())
+    norm = _normalisation(_device_statistics(arrays, torch.as_tensor(ranges.stats_mask()).to(dev)))
+    out = {key: new[key].cpu().numpy() for key in _PROCESSED_KEYS}
+    out.update(ranges_train=ranges_train, ranges_valid=ranges_valid, ranges_train_labels=relabel(train_labels),
+               ranges_valid_labels=relabel(valid_labels), **norm)
+    return out, dict(definition)
+
+
 def data_pipeline(conf, device="cuda", log=None, timings=None):
     """Prepare audio and animation data for training (reference data_pipeline.data_pipeline, same conf keys, same return value
     (processed_data, data_definition) and the same files).  `log`: callable for the progress lines (one per take, totals per label);
@@ -306,6 +417,9 @@ def data_pipeline(conf, device="cuda", log=None, timings=None):
     rows = {k: _Rows(dev) for k in ("X_audio_features",) + tuple(k for k, _ in _ANIM_KEYS)}
     ranges = Ranges()
     last = None
+    mirror = mirror_options(conf)
+    mirror_names = mirror_plan_of_info(info, mirror["suffix"]) if mirror else [None] * len(info)
+    n_row = 0
     for row in info:
         # ---- load
         take = zanim.bvh_load(str(original / row["anim_bvh"]))
@@ -325,40 +439,58 @@ def data_pipeline(conf, device="cuda", log=None, timings=None):
         valid = is_validation(row["validation"])
         folder = out_dir / "trimmed" / ("valid" if valid else "train")
         lap("trim")
-        for ratio in len_ratios:
+        # the takes of this row: the capture and, with `mirror`, its left/right reflection directly after it -- an independent take
+        # in every stage below (made from the LOADED channels, before the loop writes into them), with the capture's audio; both have
+        # n0 frames of nj joints
+        versions = [(row["anim_bvh"], take, rot0, pos0)]
+        if mirror_names[n_row] is not None:
+            mtake = zanim.mirror_take(dict(take, rotations=rot0, positions=pos0), mirror["pairs"])
+            versions.append((mirror_names[n_row], mtake, mtake["rotations"], mtake["positions"]))
+            lap("mirror")
+        n_row += 1
+        audio_side = {}          # len_ratio -> (float64 wave or None, float32 wave, audio features): computed for the first version
+        for (v_bvh, v_take, v_rot0, v_pos0), ratio in ((v, r) for v in versions for r in len_ratios):
             # the take at 1.0 IS the trimmed original (float32 channels): what the centring does to it stays for the ratios after it
             if ratio != 1.0:
                 m = int(ratio * n0)
-                pos = spline_resample(pos0.reshape(n0, -1), m).reshape(m, nj, 3)
-                rot = rot_stretch(rot0, m, take["order"])
-                wave64 = spline_resample(a64, int(ratio * a64.numel()))
-                wave = wave64.to(torch.float32)
+                pos = spline_resample(v_pos0.reshape(n0, -1), m).reshape(m, nj, 3)
+                rot = rot_stretch(v_rot0, m, v_take["order"])
             else:
-                pos, rot, wave64, wave = pos0, rot0, None, a32
+                pos, rot = v_pos0, v_rot0
+            if ratio in audio_side:
+                wave64, wave, audio_feats = audio_side[ratio]
+            elif ratio != 1.0:
+                wave64 = spline_resample(a64, int(ratio * a64.numel()))
+                wave, audio_feats = wave64.to(torch.float32), None
+            else:
+                wave64, wave, audio_feats = None, a32, None
             lap("stretch")
-            name = trimmed_name(row["anim_bvh"], ratio)
+            name = trimmed_name(v_bvh, ratio)
             if conf["save_trimmed_audio"]:
                 folder.mkdir(exist_ok=True, parents=True)
                 write_wav(folder / (name + ".wav"), (wave64 if wave64 is not None else wave).cpu().numpy(), fs)
                 lap("write_wav")
             if conf["save_trimmed_animation"]:
                 folder.mkdir(exist_ok=True, parents=True)
-                center_take(pos, rot, take["order"], round_f32=(ratio == 1.0))
+                center_take(pos, rot, v_take["order"], round_f32=(ratio == 1.0))
                 # (device float64 channels: the motion text is formatted where they are, anim.TEXT = "host" downloads them instead)
-                zanim.bvh_save(folder / (name + ".bvh"), dict(take, positions=pos, rotations=rot))
+                zanim.bvh_save(folder / (name + ".bvh"), dict(v_take, positions=pos, rotations=rot))
                 lap("write_bvh")
             # ---- features, straight into the dataset's buffers
             nframes = rot.shape[0]
-            rows["X_audio_features"].put(zaudio.preprocess_audio_device(wave, ANIM_FPS, nframes, conf["audio_conf"],
-                                                                        conf["audio_feature_type"], dev))
+            if audio_feats is None:
+                audio_feats = zaudio.preprocess_audio_device(wave, ANIM_FPS, nframes, conf["audio_conf"], conf["audio_feature_type"], dev)
+                if len(versions) > 1:
+                    audio_side[ratio] = (wave64, wave, audio_feats)
+            rows["X_audio_features"].put(audio_feats)
             lap("audio_features")
-            feats = zanim.preprocess_animation_device(rot, pos, take["parents"], take["names"], take["frametime"], take["order"])
+            feats = zanim.preprocess_animation_device(rot, pos, v_take["parents"], v_take["names"], v_take["frametime"], v_take["order"])
             for k, i in _ANIM_KEYS:
                 rows[k].put(feats[i])
             if ratio == 1.0:
                 # the reference's preprocess_animation writes the root-relative hips position into the take it was given
                 # (data_pipeline.py:97, 147: `lpos` IS anim_data["positions"]); at 1.0 that is the trimmed original (float32)
-                pos0[:, 0] = feats[4][:, 0].to(torch.float32)
+                v_pos0[:, 0] = feats[4][:, 0].to(torch.float32)
             lap("anim_features")
             span = ranges.add(nframes, row["style"], valid)
             log(f"{name}: {nframes} frames -> rows [{span[0]}, {span[1]}) {'valid' if valid else 'train'} {row['style']}")
@@ -371,24 +503,14 @@ def data_pipeline(conf, device="cuda", log=None, timings=None):
         raise ValueError("data_pipeline: NaN in the audio features (a take's animation outlasts its audio)")
     # ---- statistics over rows [s + 2, e - 2) of the train ranges (device, float64 accumulation)
     mask = torch.as_tensor(ranges.stats_mask()).to(dev)
-    where = {}
-    for k in ("X_audio_features",) + _IN_STATS:
-        where[k] = masked_stats(rows[k].view(), mask)
+    where = _device_statistics({k: rows[k].view() for k in rows}, mask)
     lap("statistics")
     # ---- one download
     data = {k: rows[k].view().cpu().numpy() for k in rows}
-    st = {k: tuple(t.cpu().numpy() for t in v) for k, v in where.items()}
+    norm = _normalisation(where)
     lap("download")
-    f32 = np.float32
-    audio_mean, _, audio_pooled = st["X_audio_features"]
-    in_mean = np.hstack([st[k][0] for k in _IN_STATS]).astype(f32)
-    in_std = np.hstack([np.repeat(st[k][2] + 1e-10, len(st[k][0])) for k in _IN_STATS]).astype(f32)     # pooled scalars + eps
-    out_mean = np.hstack([st[k][0] for k in _OUT_STATS]).astype(f32)
-    out_std = np.hstack([st[k][1] for k in _OUT_STATS]).astype(f32)                                     # per column, no eps
     stats = dict(ranges_train=ranges_train, ranges_valid=ranges_valid, ranges_train_labels=train_labels,
-                 ranges_valid_labels=valid_labels, audio_input_mean=audio_mean.astype(f32),
-                 audio_input_std=f32(audio_pooled[0] + 1e-10), anim_input_mean=in_mean, anim_input_std=in_std,
-                 anim_output_mean=out_mean, anim_output_std=out_std)
+                 ranges_valid_labels=valid_labels, **norm)
     processed = {k: data[k] for k in ("X_audio_features", "Y_root_pos", "Y_root_rot", "Y_root_vel", "Y_root_vrt", "Y_lpos", "Y_ltxy",
                                       "Y_lvel", "Y_lvrt", "Y_gaze_pos")}
     processed.update(stats)

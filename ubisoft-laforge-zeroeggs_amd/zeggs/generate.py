@@ -342,6 +342,15 @@ class _Loaded:
         self.film = hasattr(self.decoder.recurrent_decoder, "gammas_predictor")
 
 
+def _style_mirrored(style):
+    """a style entry (bvh, frames) or (bvh, frames, "mirror")"""
+    if len(style) > 2 and style[2] not in (None, False):
+        if style[2] not in ("mirror", True):
+            raise ValueError(f"style entry {style!r}: the third field is 'mirror' (or absent)")
+        return True
+    return False
+
+
 def _seed_all(seed):
     from . import ops
     np.random.seed(seed)
@@ -351,11 +360,12 @@ def _seed_all(seed):
 
 
 def _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature,
-               cache=None):
+               cache=None, mirror_style=False):
     """Everything of generate_gesture() in front of the decoder: WAV read, loudness + mel, speech encoder, exemplar parse, style
     encoder, blend.  -> dict(final, speech, feat, file_name).  `cache` (generate_gestures: a dict shared by the jobs of a list)
     keeps parsed BVH files and exemplar features across calls; without it files are parsed on a host thread beside the audio
-    front-end, every distinct file once per call."""
+    front-end, every distinct file once per call.  An exemplar entry (bvh, frames, "mirror"), or every exemplar with
+    `mirror_style`, is reflected left/right after loading and before the features (anim.mirror_take)."""
     device = ld.device
     in_mean, in_std = ld.stats[0], ld.stats[1]
     # exemplar / first-pose BVH files are parsed on a host thread (the C parser releases the GIL) while this thread reads the WAV
@@ -405,7 +415,8 @@ def _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ra
         if style_encoding_type == "example":
             if isinstance(style[0], (pathlib.PurePath, str)):
                 anim_name = Path(style[0]).stem
-                fkey = (str(Path(style[0]).resolve()), None if style[1] is None else tuple(style[1]))
+                mirrored = bool(mirror_style) or _style_mirrored(style)
+                fkey = (str(Path(style[0]).resolve()), None if style[1] is None else tuple(style[1])) + (("mirror",) if mirrored else ())
                 if cache is not None and fkey in parsed:
                     feat = parsed[fkey]
                 else:
@@ -415,6 +426,8 @@ def _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ra
                         clip["rotations"] = clip["rotations"][style[1][0]:style[1][1]]
                         clip["positions"] = clip["positions"][style[1][0]:style[1][1]]
                     assert int(np.ceil(1 / clip["frametime"])) == 60
+                    if mirrored:
+                        clip = anim.mirror_take(clip)
                     with _stage("exemplar_features_device"):
                         feat = anim.preprocess_animation(clip, device)
                         parsed[fkey] = feat
@@ -424,6 +437,9 @@ def _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ra
                     z, _, _ = ld.style_net(ex[None].contiguous(), temperature)
                 encodings.append(z)
             elif isinstance(style[0], np.ndarray):
+                if mirror_style or (len(style) > 2 and style[2] not in (None, False)):
+                    raise ValueError("a style entry (embedding, name) cannot be mirrored: mirror reflects an exemplar's BVH channels, "
+                                     "an embedding has none")
                 anim_name = style[1]
                 encodings.append(torch.as_tensor(style[0], dtype=torch.float32, device=device)[None])
         elif style_encoding_type == "label":
@@ -530,8 +546,10 @@ def _decode_one(ld, fe, audio_file, results_path, return_poses=False, plant=None
 
 def generate_gesture(audio_file, styles, network_path, data_path, results_path, style_encoding_type="example",
                      blend_type="add", blend_ratio=[0.5, 0.5], file_name=None, first_pose=None, temperature=1.0,
-                     seed=1234, use_gpu=True, use_script=False, plant=None):
-    """the reference's generate_gesture.  `plant` (not the reference's): None, True or dict(chains="auto", speed=(v_on, v_off),
+                     seed=1234, use_gpu=True, use_script=False, plant=None, mirror_style=False):
+    """the reference's generate_gesture.  A style entry (bvh, frames, "mirror") -- or every exemplar, with `mirror_style` (not the
+    reference's) -- is used as its left/right reflection: the exemplar's channels are mirrored after loading, before the
+    features; nothing else changes.  `plant` (not the reference's): None, True or dict(chains="auto", speed=(v_on, v_off),
     height=(h_on, h_off), ground, slack, release, stretch) -- feet that stay planted (anim.plant_feet): the decoded
     rows go through the contact lock and the leg IK on the device before they become the BVH file, on the one-launch path and
     on the chunked long-clip path (the contact state carried from chunk to chunk).  The defaults are NOT tuned on captured
@@ -552,7 +570,8 @@ def generate_gesture(audio_file, styles, network_path, data_path, results_path, 
     else:
         plant = None
     with torch.no_grad():
-        fe = _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature)
+        fe = _front_end(ld, audio_file, styles, style_encoding_type, blend_type, blend_ratio, file_name, first_pose, temperature,
+                        mirror_style=mirror_style)
         if audio_file is not None:
             _decode_one(ld, fe, audio_file, results_path, plant=plant)
     return fe["final"]
@@ -595,8 +614,9 @@ class Job:
     """one row of a job list: the arguments of generate_gesture() that vary per clip"""
 
     def __init__(self, audio_file, styles, file_name=None, first_pose=None, temperature=1.0, seed=1234, blend_type="add",
-                 blend_ratio=(0.5, 0.5)):
+                 blend_ratio=(0.5, 0.5), mirror_style=False):
         self.audio_file, self.styles, self.file_name, self.first_pose = audio_file, list(styles), file_name, first_pose
+        self.mirror_style = bool(mirror_style)
         self.temperature, self.seed, self.blend_type, self.blend_ratio = temperature, seed, blend_type, list(blend_ratio)
 
 
@@ -792,7 +812,7 @@ def generate_gestures(jobs, network_path, data_path, results_path, style_encodin
         for j in jobs:
             _seed_all(j.seed)
             fes.append(_front_end(ld, j.audio_file, j.styles, style_encoding_type, j.blend_type, j.blend_ratio, j.file_name,
-                                  j.first_pose, j.temperature, cache=cache))
+                                  j.first_pose, j.temperature, cache=cache, mirror_style=j.mirror_style))
         bd = None
         rows = min(int(batch), len(jobs))
         if rows >= 2 and not ld.film and int(chunk) >= 4:

@@ -1552,7 +1552,7 @@ class LiveServer:
         self._styles_on("styles")
         return dict(self._style_names)
 
-    def add_style(self, name, source, trim=None):
+    def add_style(self, name, source, trim=None, mirror=False):
         """put a style into the bank under `name` -> its slot.  A name the bank already has keeps its slot and is overwritten;
         rows that were set from it keep the vectors they were given.  `source`:
           * a BVH path, a parsed clip (the dict of anim.bvh_load) or un-normalised exemplar rows [L, F] -- an EXAMPLE: it goes
@@ -1562,7 +1562,8 @@ class LiveServer:
             fixed summation order here (ops.fixed_order_gemms), so the same example gives the same slot, bit for bit, on every
             call and every server; the offline call gives these bits under the same switch and differs in the last place
             without it, from run to run.  Needs LiveServer(styles=dict(net=));
-            `trim` = (a, b) keeps frames a .. b - 1 of the clip, as generate_gesture's (path, (a, b)) does;
+            `trim` = (a, b) keeps frames a .. b - 1 of the clip, as generate_gesture's (path, (a, b)) does; `mirror`: the clip's
+            left/right reflection (anim.mirror_take after loading, before the features: a BVH path or a parsed clip only);
           * a 1-D tensor or array of S floats -- an embedding computed elsewhere, or a one-hot label of a label-conditioned
             model: the slot's mean, deviation 0 -- or of 2 S floats, an encoder row computed elsewhere (mean | log-variance).
             Needs no encoder.
@@ -1581,6 +1582,8 @@ class LiveServer:
             raise ValueError(f"add_style: a vector of {int(source.shape[0])} floats, the model's styles have {ST} (or {2 * ST}: mean | log-variance)")
         if trim is not None and (vector or len(trim) != 2):
             raise ValueError(f"add_style: trim {trim!r} is (first frame, end) of an example")
+        if mirror and (vector or isinstance(source, (torch.Tensor, np.ndarray))):
+            raise ValueError("add_style: mirror reflects an example's BVH channels: give a BVH path or a parsed clip")
         if name not in self._style_names and len(self._style_names) >= conf["capacity"]:
             raise RuntimeError(f"add_style: the bank is full, all {conf['capacity']} slots are in use (LiveServer(styles=dict(capacity=...)); "
                                "remove_style() frees one)")
@@ -1588,7 +1591,7 @@ class LiveServer:
             if vector:
                 enc = torch.as_tensor(source).to(self.dev, torch.float32).contiguous()
             else:
-                enc = self._encode_example(source, trim)
+                enc = self._encode_example(source, trim, mirror)
                 if int(enc.numel()) not in (ST, 2 * ST):
                     raise ValueError(f"add_style: the style encoder returns {int(enc.numel())} floats, the model's styles have {ST}")
             if name in self._style_names:
@@ -1599,7 +1602,7 @@ class LiveServer:
         self._style_names[name] = slot
         return slot
 
-    def _encode_example(self, source, trim):
+    def _encode_example(self, source, trim, mirror=False):
         """the style encoder's raw output row [E] for an example (add_style), on the device"""
         import pathlib
         from . import modules
@@ -1620,6 +1623,8 @@ class LiveServer:
             if trim is not None:
                 clip["rotations"] = clip["rotations"][trim[0]:trim[1]]
                 clip["positions"] = clip["positions"][trim[0]:trim[1]]
+            if mirror:
+                clip = anim.mirror_take(clip)
             rows = _example_features(anim.preprocess_animation(clip, self.dev))
         if rows.shape[0] < 1:
             raise ValueError("add_style: the example has no frames")
