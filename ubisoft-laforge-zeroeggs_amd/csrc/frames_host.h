@@ -4,17 +4,19 @@
 // here; an entry point keeps what is its own -- the order of its checks, its `outputs` rule, its skip and `work` conditions and
 // its launch.  Nothing here asks which form calls it: a form that needs more makes a call of its own between these.
 // `who` is the form's word in every message ("frames", "retime", "refilter"), `i` the index of the record a message names.
+// What the head shares with every other stage of live serving -- the head of the dims record, the state block, the row of a
+// single-row call, a record's row once a call, the device copy of the records -- is live_host.h's, called from here.
 // Host code, and the one kernel of a reset: include it behind a unit's own kernels (common.h, anim_math.h, frames_math.h and
 // frames_core.h first), so that they stay the first of its code object.
 #pragma once
+#include "live_host.h"
 #include "retime_math.h"
 
 namespace {
 
 // ---- the dims record.  The shape: what the three kernels take alike
 int fh_shape_ok(const char* who, const ZeggsFramesDims* d) {
-  ZCHECK(d != nullptr, "%s: NULL dims", who);
-  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "%s: %d rows (1..%d)", who, d->rows, ZEGGS_LIVE_MAX_ROWS);
+  ZTRY(lh_dims_ok(who, d));
   const int why = fr_shape_refused(d->J, d->max_frames);
   ZCHECK(why != 1, "%s: %d joints (1..%d)", who, d->J, FR_MAX_JOINTS);
   ZCHECK(why != 2, "%s: max_frames %d (1..%d)", who, d->max_frames, FR_MAX_FRAMES);
@@ -23,15 +25,7 @@ int fh_shape_ok(const char* who, const ZeggsFramesDims* d) {
   ZCHECK(order_code(d->order) == ORDER_ZYX || d->order == ORDER_XZY, "%s: channel order %d (\"zyx\" and \"xzy\" are supported)", who, d->order);
   return 0;
 }
-// The state block against `need`, the form's own size for dims that passed.  state_bytes == (size_t)-1: the size query of
-// *_state_bytes, which has no block yet
-int fh_state_ok(const char* who, const void* state, size_t state_bytes, size_t need) {
-  if (state_bytes == (size_t)-1) return 0;
-  ZCHECK(state != nullptr, "%s: NULL state", who);
-  ZCHECK(state_bytes >= need, "%s: state too small (%zu < %zu)", who, state_bytes, need);
-  ZCHECK((uintptr_t)state % 8 == 0, "%s: misaligned state", who);
-  return 0;
-}
+// (the state block against the form's own size: lh_block_ok(who, "state", state, state_bytes, need, 8))
 
 // ---- prepare, behind the form's dims check: the skeleton tables [parents | seq | place] to the front of the state
 int fh_prepare(const char* who, const ZeggsFramesDims* d, const int* parents, const int* seq, void* state, void* stream) {
@@ -58,7 +52,7 @@ __global__ void live_head_reset_k(FrPlace place, char* row_state) { *(FrPlace*)r
 
 int fh_reset(const char* who, const char* name, const ZeggsFramesDims* d, void* state, long row_offset, int row, const float* ref_pos,
              const float* ref_rot, const double* start_pos, const double* start_rot, int rebase, void* stream) {
-  ZCHECK(row >= 0 && row < d->rows, "%s reset: row %d of %d", who, row, d->rows);
+  ZTRY(lh_row_ok(who, "reset", row, d->rows));
   FrPlace p = {};
   p.ref_rot[0] = p.start_rot[0] = 1.0;
   if (rebase) {
@@ -77,9 +71,7 @@ int fh_reset(const char* who, const char* name, const ZeggsFramesDims* d, void* 
 // its row, once a call (`seen`: one flag a row, the caller's), and its count of input frames
 template <class Row>
 int fh_row_ok(const char* who, int i, const Row& w, const ZeggsFramesDims* d, bool* seen) {
-  ZCHECK(w.row >= 0 && w.row < d->rows, "%s: record %d: row %d of %d", who, i, w.row, d->rows);
-  ZCHECK(!seen[w.row], "%s: record %d: row %d twice in one call", who, i, w.row);
-  seen[w.row] = true;
+  ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
   ZCHECK(w.count >= 0, "%s: record %d: negative count %d", who, i, w.count);
   ZCHECK(w.count <= d->max_frames, "%s: record %d: %d frames, max_frames is %d", who, i, w.count, d->max_frames);
   return 0;
@@ -94,16 +86,8 @@ int fh_ratio_ok(const char* who, int i, const Row& w) {
   ZCHECK(w.n_in >= 0 && w.n_in <= (1L << 40), "%s: record %d: input counter %ld", who, i, w.n_in);
   return 0;
 }
-// the sources of a record that brings frames, and their leading dimensions
-template <class Row>
-int fh_sources_ok(const char* who, int i, const Row& w, int J) {
-  ZCHECK(w.pose != nullptr && (uintptr_t)w.pose % 4 == 0 && w.rpos != nullptr && (uintptr_t)w.rpos % 4 == 0 && w.rrot != nullptr &&
-             (uintptr_t)w.rrot % 4 == 0, "%s: record %d: NULL or misaligned source", who, i);
-  ZCHECK(w.pose_ld >= fr_pose_floats_read(J) && w.rpos_ld >= 3 && w.rrot_ld >= 4,
-         "%s: record %d: leading dimensions %ld, %ld, %ld (at least %d, 3, 4 floats)", who, i, w.pose_ld, w.rpos_ld, w.rrot_ld,
-         fr_pose_floats_read(J));
-  return 0;
-}
+// (the sources of a record that brings frames: lh_sources_ok(who, i, w, fr_pose_floats_read(J)), which the plant stage calls
+// with the whole pose row -- this header has a kernel, so a unit that is no head cannot include it)
 // the destinations of a record that emits frames: those `what` asks for
 template <class Row>
 int fh_dests_ok(const char* who, int i, const Row& w, int what) {
@@ -112,12 +96,6 @@ int fh_dests_ok(const char* who, int i, const Row& w, int what) {
   ZCHECK(!(what & FR_BVH) || (w.bvh != nullptr && (uintptr_t)w.bvh % 8 == 0), "%s: record %d: NULL or misaligned BVH destination", who, i);
   return 0;
 }
-// the device copy of the records of a call that has work: one record travels in the kernel arguments, more do not
-template <class Row>
-int fh_rows_dev_ok(const char* who, const Row* rows_dev, int R) {
-  ZCHECK(rows_dev != nullptr || R == 1, "%s: %d records must also be in device memory (rows_dev)", who, R);
-  ZCHECK(rows_dev == nullptr || (uintptr_t)rows_dev % 8 == 0, "%s: misaligned rows_dev", who);
-  return 0;
-}
+// (the device copy of the records of a call that has work: lh_dev_ok(who, "rows_dev", rows_dev, R, 8))
 
 }  // namespace

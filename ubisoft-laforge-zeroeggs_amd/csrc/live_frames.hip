@@ -76,7 +76,7 @@ namespace {
 
 int fr_dims_ok(const ZeggsFramesDims* d, const void* state, size_t state_bytes) {
   ZTRY(fh_shape_ok("frames", d));
-  return fh_state_ok("frames", state, state_bytes, (size_t)fr_state_bytes(d->rows, d->J));
+  return lh_block_ok("frames", "state", state, state_bytes, (size_t)fr_state_bytes(d->rows, d->J), 8);
 }
 
 }  // namespace
@@ -104,7 +104,7 @@ extern "C" int zeggs_live_frames(const ZeggsFramesDims* d, const ZeggsFramesRow*
                                  size_t state_bytes, void* stream) {
   const char* who = "frames";
   ZTRY(fr_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "%s: %d records for %d rows", who, R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(rows != nullptr, "%s: NULL records", who);
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
@@ -114,12 +114,12 @@ extern "C" int zeggs_live_frames(const ZeggsFramesDims* d, const ZeggsFramesRow*
     const ZeggsFramesRow& w = rows[i];
     ZTRY(fh_row_ok(who, i, w, d, seen));
     if (w.count == 0) continue;
-    ZTRY(fh_sources_ok(who, i, w, J));
+    ZTRY(lh_sources_ok(who, i, w, fr_pose_floats_read(J)));
     ZTRY(fh_dests_ok(who, i, w, d->what));
     work = true;
   }
   if (!work) return 0;
-  ZTRY(fh_rows_dev_ok(who, rows_dev, R));
+  ZTRY(lh_dev_ok(who, "rows_dev", rows_dev, R, 8));
   hipLaunchKernelGGL(live_frames_k, dim3((unsigned)R), dim3(FR_THREADS), (size_t)fr_lds_bytes(J, d->max_frames), (hipStream_t)stream, *d, rows_dev,
                      rows[0], (char*)state);
   ZLAUNCH_CHECK("live_frames");

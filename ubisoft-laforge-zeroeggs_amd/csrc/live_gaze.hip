@@ -76,16 +76,16 @@ __global__ __launch_bounds__(GAZE_THREADS) void live_condition_k(const ZeggsGaze
   }
 }
 
+}  // namespace
+
+#include "live_host.h"      // the host contract every stage of live serving keeps
+
+namespace {
+
 int gaze_dims_ok(const ZeggsGazeDims* d, const void* state, size_t state_bytes) {
-  ZCHECK(d != nullptr, "live gaze: NULL dims");
-  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "live gaze: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
+  ZTRY(lh_dims_ok("live gaze", d));
   ZCHECK(d->ST >= 1 && d->ST <= (1 << 16), "live gaze: style rows of %d floats", d->ST);
-  if (state_bytes != (size_t)-1) {
-    ZCHECK(state != nullptr, "live gaze: NULL state");
-    ZCHECK(state_bytes >= (size_t)d->rows * GAZE_ROW_BYTES, "live gaze: state too small (%zu < %zu)", state_bytes, (size_t)d->rows * GAZE_ROW_BYTES);
-    ZCHECK((uintptr_t)state % 8 == 0, "live gaze: misaligned state");
-  }
-  return 0;
+  return lh_block_ok("live gaze", "state", state, state_bytes, (size_t)d->rows * GAZE_ROW_BYTES, 8);
 }
 
 bool finite3(const float* v) { return isfinite(v[0]) && isfinite(v[1]) && isfinite(v[2]); }
@@ -101,7 +101,7 @@ extern "C" size_t zeggs_live_gaze_state_bytes(const ZeggsGazeDims* d) {
 
 extern "C" int zeggs_live_gaze_reset(const ZeggsGazeDims* d, void* state, size_t state_bytes, int row, const float* gaze0, void* stream) {
   ZTRY(gaze_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "live gaze reset: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("live gaze", "reset", row, d->rows));
   ZCHECK(gaze0 != nullptr && (uintptr_t)gaze0 % 4 == 0, "live gaze reset: NULL or misaligned gaze");
   hipLaunchKernelGGL(live_gaze_reset_k, dim3(1), dim3(64), 0, (hipStream_t)stream, (GazeRow*)state + row, gaze0);
   ZLAUNCH_CHECK("live_gaze_reset");
@@ -110,17 +110,16 @@ extern "C" int zeggs_live_gaze_reset(const ZeggsGazeDims* d, void* state, size_t
 
 extern "C" int zeggs_live_gaze_set(const ZeggsGazeDims* d, const ZeggsGazeSet* recs, const ZeggsGazeSet* recs_dev, int R, const float* rpos,
                                    long rpos_ld, const float* rrot, long rrot_ld, void* state, size_t state_bytes, void* stream) {
+  const char* who = "live gaze set";
   ZTRY(gaze_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "live gaze set: %d records for %d rows", R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(recs != nullptr, "live gaze set: NULL records");
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
   bool root = false;
   for (int i = 0; i < R; ++i) {
     const ZeggsGazeSet& w = recs[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "live gaze set: record %d: row %d of %d", i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "live gaze set: record %d: row %d twice in one call", i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
     ZCHECK(w.k >= 1, "live gaze set: record %d: frame %ld (>= 1)", i, w.k);
     ZCHECK(w.fade >= 0, "live gaze set: record %d: negative fade %ld", i, w.fade);
     ZCHECK(w.space == ZEGGS_GAZE_WORLD || w.space == ZEGGS_GAZE_ROOT, "live gaze set: record %d: space %d", i, w.space);
@@ -136,7 +135,7 @@ extern "C" int zeggs_live_gaze_set(const ZeggsGazeDims* d, const ZeggsGazeSet* r
            "live gaze set: root space needs the rows' root state (NULL or misaligned rpos / rrot)");
     ZCHECK(rpos_ld >= 3 && rrot_ld >= 4, "live gaze set: root strides %ld / %ld (>= 3 / >= 4)", rpos_ld, rrot_ld);
   }
-  ZCHECK(recs_dev != nullptr || R == 1, "live gaze set: %d records must also be in device memory (recs_dev)", R);
+  ZTRY(lh_dev_ok(who, "recs_dev", recs_dev, R));
   hipLaunchKernelGGL(live_gaze_set_k, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, recs_dev, recs[0], (GazeRow*)state, rpos, rpos_ld,
                      rrot, rrot_ld);
   ZLAUNCH_CHECK("live_gaze_set");
@@ -155,9 +154,7 @@ extern "C" int zeggs_live_condition(const ZeggsGazeDims* d, const ZeggsGazeCond*
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {}, taken[ZEGGS_LIVE_MAX_ROWS] = {};
   for (int i = 0; i < R; ++i) {
     const ZeggsGazeCond& w = recs[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "live condition: record %d: row %d of %d", i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "live condition: record %d: row %d twice in one call", i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok("live condition", i, w.row, d->rows, seen));
     ZCHECK(w.out_row >= 0 && w.out_row < out_rows, "live condition: record %d: output slice %d of %d", i, w.out_row, out_rows);
     ZCHECK(!taken[w.out_row], "live condition: record %d: output slice %d twice in one call", i, w.out_row);
     taken[w.out_row] = true;
@@ -167,7 +164,7 @@ extern "C" int zeggs_live_condition(const ZeggsGazeDims* d, const ZeggsGazeCond*
   }
   ZCHECK(sty_old != nullptr && sty_new != nullptr && gaze_out != nullptr && style_out != nullptr, "live condition: NULL tensor");
   ZCHECK(((uintptr_t)sty_old | (uintptr_t)sty_new | (uintptr_t)gaze_out | (uintptr_t)style_out) % 4 == 0, "live condition: misaligned tensor");
-  ZCHECK(recs_dev != nullptr || R == 1, "live condition: %d records must also be in device memory (recs_dev)", R);
+  ZTRY(lh_dev_ok("live condition", "recs_dev", recs_dev, R));
   hipLaunchKernelGGL(live_condition_k, dim3((unsigned)R), dim3(GAZE_THREADS), 0, (hipStream_t)stream, recs_dev, recs[0], (const GazeRow*)state,
                      sty_old, sty_new, gaze_out, style_out, stride, d->ST);
   ZLAUNCH_CHECK("live_condition");
@@ -176,7 +173,7 @@ extern "C" int zeggs_live_condition(const ZeggsGazeDims* d, const ZeggsGazeCond*
 
 extern "C" int zeggs_live_gaze_read(const ZeggsGazeDims* d, const void* state, size_t state_bytes, int row, long frame, double* out, void* stream) {
   ZTRY(gaze_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "live gaze read: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("live gaze", "read", row, d->rows));
   ZCHECK(out != nullptr, "live gaze read: NULL output");
   GazeRow g;
   hipError_t e = hipMemcpyAsync(&g, (const GazeRow*)state + row, sizeof(g), hipMemcpyDeviceToHost, (hipStream_t)stream);
@@ -199,8 +196,6 @@ extern "C" int zeggs_live_gaze_read(const ZeggsGazeDims* d, const void* state, s
 
 extern "C" int zeggs_live_gaze_spans(const ZeggsGazeDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_gaze_state_bytes(d) == 0) return -1;
-  ZCHECK(row >= 0 && row < d->rows, "live gaze spans: row %d of %d", row, d->rows);
-  ZCHECK(spans != nullptr && max_spans >= 1, "live gaze spans: room for %d spans, the row has 1", spans ? max_spans : 0);
-  spans[0] = ZeggsSnapSpan{(size_t)row * GAZE_ROW_BYTES, (size_t)GAZE_ROW_BYTES};
-  return 1;
+  const size_t o = (size_t)row * GAZE_ROW_BYTES, b = GAZE_ROW_BYTES;
+  return lh_spans_out("live gaze spans", row >= 0 && row < d->rows ? 1 : -1, row, d->rows, max_spans, &o, &b, spans);
 }

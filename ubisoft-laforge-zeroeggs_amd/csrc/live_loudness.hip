@@ -163,12 +163,17 @@ __global__ void loud_hold_k(char* row, int on) {
   if (blockIdx.x == 0 && threadIdx.x == 0) ((LoudHead*)row)->hold = on;
 }
 
+}  // namespace
+
+#include "live_host.h"      // the host contract every stage of live serving keeps
+
+namespace {
+
 std::atomic<int> g_rate_ok{0};      // the last rate loud_rate_ok accepted (a push does not walk the block table again)
 
 int loud_dims_ok(const ZeggsLoudDims* dp, const void* state, size_t state_bytes) {
-  ZCHECK(dp != nullptr, "live loudness: NULL dims");
+  ZTRY(lh_dims_ok("live loudness", dp));
   const ZeggsLoudDims& d = *dp;
-  ZCHECK(d.rows >= 1 && d.rows <= ZEGGS_LIVE_MAX_ROWS, "live loudness: %d rows (1..%d)", d.rows, ZEGGS_LIVE_MAX_ROWS);
   ZCHECK(d.fs >= 1000 && d.fs <= 768000, "live loudness: sampling rate %d", d.fs);
   ZCHECK(d.ring_blocks >= 1 && d.ring_blocks <= (1 << 20), "live loudness: a ring of %d blocks", d.ring_blocks);
   ZCHECK(d.warmup >= 1, "live loudness: warmup %d (>= 1)", d.warmup);
@@ -178,13 +183,7 @@ int loud_dims_ok(const ZeggsLoudDims* dp, const void* state, size_t state_bytes)
     ZCHECK(loud_rate_ok(d.fs, 4096), "live loudness: the gating blocks of %d Hz do not have one length", d.fs);
     g_rate_ok.store(d.fs, std::memory_order_relaxed);
   }
-  if (state_bytes != (size_t)-1) {
-    ZCHECK(state != nullptr, "live loudness: NULL state");
-    ZCHECK(state_bytes >= (size_t)d.rows * loud_row_bytes(d), "live loudness: state too small (%zu < %zu)", state_bytes,
-           (size_t)d.rows * loud_row_bytes(d));
-    ZCHECK((uintptr_t)state % 8 == 0, "live loudness: misaligned state");
-  }
-  return 0;
+  return lh_block_ok("live loudness", "state", state, state_bytes, (size_t)d.rows * loud_row_bytes(d), 8);
 }
 
 }  // namespace
@@ -196,7 +195,7 @@ extern "C" size_t zeggs_live_loudness_state_bytes(const ZeggsLoudDims* d) {
 
 extern "C" int zeggs_live_loudness_reset(const ZeggsLoudDims* d, void* state, size_t state_bytes, int row, float gain0, void* stream) {
   ZTRY(loud_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "live loudness reset: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("live loudness", "reset", row, d->rows));
   ZCHECK(gain0 == gain0 && gain0 >= 0.f && gain0 < INFINITY, "live loudness reset: gain %g", (double)gain0);
   const size_t rb = loud_row_bytes(*d);
   hipLaunchKernelGGL(loud_reset_k, dim3(8), dim3(256), 0, (hipStream_t)stream, (char*)state + (size_t)row * rb, rb, gain0);
@@ -206,7 +205,7 @@ extern "C" int zeggs_live_loudness_reset(const ZeggsLoudDims* d, void* state, si
 
 extern "C" int zeggs_live_loudness_hold(const ZeggsLoudDims* d, void* state, size_t state_bytes, int row, int on, void* stream) {
   ZTRY(loud_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "live loudness hold: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("live loudness", "hold", row, d->rows));
   hipLaunchKernelGGL(loud_hold_k, dim3(1), dim3(64), 0, (hipStream_t)stream, (char*)state + (size_t)row * loud_row_bytes(*d), on ? 1 : 0);
   ZLAUNCH_CHECK("live_loudness_hold");
   return 0;
@@ -214,17 +213,16 @@ extern "C" int zeggs_live_loudness_hold(const ZeggsLoudDims* d, void* state, siz
 
 extern "C" int zeggs_live_loudness_push(const ZeggsLoudDims* d, const ZeggsLoudRow* rows, const ZeggsLoudRow* rows_dev, int R, void* state,
                                         size_t state_bytes, void* stream) {
+  const char* who = "live loudness push";
   ZTRY(loud_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "live loudness push: %d records for %d rows", R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(rows != nullptr, "live loudness push: NULL records");
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
   long total = 0;
   for (int i = 0; i < R; ++i) {
     const ZeggsLoudRow& w = rows[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "live loudness push: record %d: row %d of %d", i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "live loudness push: record %d: row %d twice in one call", i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
     ZCHECK(w.count >= 0, "live loudness push: record %d: negative count %ld", i, w.count);
     if (w.count == 0) continue;
     ZCHECK(w.src != nullptr && w.dst != nullptr && (uintptr_t)w.src % 4 == 0 && (uintptr_t)w.dst % 4 == 0,
@@ -234,7 +232,7 @@ extern "C" int zeggs_live_loudness_push(const ZeggsLoudDims* d, const ZeggsLoudR
     total += w.count;
   }
   if (total == 0) return 0;
-  ZCHECK(rows_dev != nullptr || R == 1, "live loudness push: %d records must also be in device memory (rows_dev)", R);
+  ZTRY(lh_dev_ok(who, "rows_dev", rows_dev, R));
   hipLaunchKernelGGL(live_loudness_k, dim3((unsigned)R), dim3(LOUD_THREADS), 0, (hipStream_t)stream, *d, rows_dev, rows[0], (char*)state,
                      loud_row_bytes(*d));
   ZLAUNCH_CHECK("live_loudness");
@@ -243,7 +241,7 @@ extern "C" int zeggs_live_loudness_push(const ZeggsLoudDims* d, const ZeggsLoudR
 
 extern "C" int zeggs_live_loudness_read(const ZeggsLoudDims* d, const void* state, size_t state_bytes, int row, double* out, void* stream) {
   ZTRY(loud_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "live loudness read: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("live loudness", "read", row, d->rows));
   ZCHECK(out != nullptr, "live loudness read: NULL output");
   LoudHead h;
   hipError_t e = hipMemcpyAsync(&h, (const char*)state + (size_t)row * loud_row_bytes(*d), sizeof(h), hipMemcpyDeviceToHost, (hipStream_t)stream);

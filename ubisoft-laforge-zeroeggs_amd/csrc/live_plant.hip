@@ -153,10 +153,15 @@ __global__ __launch_bounds__(PL_THREADS) void live_plant_k(ZeggsPlantDims d, con
   if (tid < C) rows[tid] = st;
 }
 
+}  // namespace
+
+#include "live_host.h"      // the host contract every stage of live serving keeps
+
+namespace {
+
 int pl_dims_ok(const ZeggsPlantDims* d, const void* state, size_t state_bytes) {
-  ZCHECK(d != nullptr, "plant: NULL dims");
+  ZTRY(lh_dims_ok("plant", d));      // (pl_dims_refused's 1, the rows, is refused here: with the same words)
   const int why = pl_dims_refused(d->rows, ZEGGS_LIVE_MAX_ROWS, d->J, d->max_frames, d->chains, d->release);
-  ZCHECK(why != 1, "plant: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
   ZCHECK(why != 2, "plant: %d joints (3..%d)", d->J, PL_MAX_JOINTS);
   ZCHECK(why != 3, "plant: max_frames %d (1..%d)", d->max_frames, PL_MAX_FRAMES);
   ZCHECK(why != 4, "plant: %d chains (1..%d)", d->chains, PL_MAX_CHAINS);
@@ -169,13 +174,7 @@ int pl_dims_ok(const ZeggsPlantDims* d, const void* state, size_t state_bytes) {
   ZCHECK(bad != 4, "plant: ground %g", d->ground);
   ZCHECK(bad != 5, "plant: slack %g (>= 0)", d->slack);
   ZCHECK(bad == 0, "plant: stretch %g (0 < stretch <= 1)", d->stretch);
-  if (state_bytes != (size_t)-1) {
-    const size_t need = (size_t)pl_state_bytes(d->rows, d->J);
-    ZCHECK(state != nullptr, "plant: NULL state");
-    ZCHECK(state_bytes >= need, "plant: state too small (%zu < %zu)", state_bytes, need);
-    ZCHECK((uintptr_t)state % 8 == 0, "plant: misaligned state");
-  }
-  return 0;
+  return lh_block_ok("plant", "state", state, state_bytes, (size_t)pl_state_bytes(d->rows, d->J), 8);
 }
 
 }  // namespace
@@ -216,7 +215,7 @@ extern "C" int zeggs_live_plant_prepare(const ZeggsPlantDims* d, const int* pare
 
 extern "C" int zeggs_live_plant_reset(const ZeggsPlantDims* d, void* state, size_t state_bytes, int row, void* stream) {
   ZTRY(pl_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "plant reset: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("plant", "reset", row, d->rows));
   hipLaunchKernelGGL(live_plant_reset_k, dim3(1), dim3(64), 0, (hipStream_t)stream, (PlantChain*)((char*)state + pl_row_offset(d->J, row)));
   ZLAUNCH_CHECK("live_plant_reset");
   return 0;
@@ -224,16 +223,16 @@ extern "C" int zeggs_live_plant_reset(const ZeggsPlantDims* d, void* state, size
 
 extern "C" int zeggs_live_plant_spans(const ZeggsPlantDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_plant_state_bytes(d) == 0) return -1;
-  ZCHECK(row >= 0 && row < d->rows, "plant spans: row %d of %d", row, d->rows);
-  ZCHECK(spans != nullptr && max_spans >= 1, "plant spans: room for %d spans, the row has 1", spans ? max_spans : 0);
-  spans[0] = ZeggsSnapSpan{(size_t)pl_row_offset(d->J, row), (size_t)pl_row_bytes()};
-  return 1;
+  const bool has = row >= 0 && row < d->rows;
+  const size_t o = has ? (size_t)pl_row_offset(d->J, row) : 0, b = (size_t)pl_row_bytes();
+  return lh_spans_out("plant spans", has ? 1 : -1, row, d->rows, max_spans, &o, &b, spans);
 }
 
 extern "C" int zeggs_live_plant(const ZeggsPlantDims* d, const ZeggsPlantRow* recs, const ZeggsPlantRow* recs_dev, int R, void* state,
                                 size_t state_bytes, void* stream) {
+  const char* who = "plant";
   ZTRY(pl_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "plant: %d records for %d rows", R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(recs != nullptr, "plant: NULL records");
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
@@ -241,16 +240,11 @@ extern "C" int zeggs_live_plant(const ZeggsPlantDims* d, const ZeggsPlantRow* re
   const int PO = pl_pose_floats(d->J);
   for (int i = 0; i < R; ++i) {
     const ZeggsPlantRow& w = recs[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "plant: record %d: row %d of %d", i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "plant: record %d: row %d twice in one call", i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
     ZCHECK(w.count >= 0, "plant: record %d: negative count %d", i, w.count);
     ZCHECK(w.count <= d->max_frames, "plant: record %d: %d frames, max_frames is %d", i, w.count, d->max_frames);
     if (w.count == 0) continue;
-    ZCHECK(w.pose != nullptr && (uintptr_t)w.pose % 4 == 0 && w.rpos != nullptr && (uintptr_t)w.rpos % 4 == 0 && w.rrot != nullptr &&
-               (uintptr_t)w.rrot % 4 == 0, "plant: record %d: NULL or misaligned source", i);
-    ZCHECK(w.pose_ld >= PO && w.rpos_ld >= 3 && w.rrot_ld >= 4, "plant: record %d: leading dimensions %ld, %ld, %ld (at least %d, 3, 4 floats)", i,
-           w.pose_ld, w.rpos_ld, w.rrot_ld, PO);
+    ZTRY(lh_sources_ok(who, i, w, PO));
     ZCHECK(w.out != nullptr && (uintptr_t)w.out % 4 == 0, "plant: record %d: NULL or misaligned destination", i);
     ZCHECK(w.out != w.pose, "plant: record %d: the destination is the source (the stage writes a copy)", i);
     ZCHECK(w.out_ld >= PO, "plant: record %d: destination leading dimension %ld (at least %d floats)", i, w.out_ld, PO);
@@ -258,8 +252,7 @@ extern "C" int zeggs_live_plant(const ZeggsPlantDims* d, const ZeggsPlantRow* re
     work = true;
   }
   if (!work) return 0;
-  ZCHECK(recs_dev != nullptr || R == 1, "plant: %d records must also be in device memory (recs_dev)", R);
-  ZCHECK(recs_dev == nullptr || (uintptr_t)recs_dev % 8 == 0, "plant: misaligned recs_dev");
+  ZTRY(lh_dev_ok(who, "recs_dev", recs_dev, R, 8));
   hipLaunchKernelGGL(live_plant_k, dim3((unsigned)R), dim3(PL_THREADS), 0, (hipStream_t)stream, *d, recs_dev, recs[0], (char*)state);
   ZLAUNCH_CHECK("live_plant");
   return 0;

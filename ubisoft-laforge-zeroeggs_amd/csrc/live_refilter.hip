@@ -166,7 +166,7 @@ namespace {
 int rf_dims_ok(const ZeggsFramesDims* d, int max_half, const void* state, size_t state_bytes) {
   ZTRY(fh_shape_ok("refilter", d));
   ZCHECK(max_half >= 1 && max_half <= RF_MAX_HALF, "refilter: max_half %d (1..%d)", max_half, RF_MAX_HALF);
-  return fh_state_ok("refilter", state, state_bytes, (size_t)rf_state_bytes(d->rows, d->J, max_half));
+  return lh_block_ok("refilter", "state", state, state_bytes, (size_t)rf_state_bytes(d->rows, d->J, max_half), 8);
 }
 
 }  // namespace
@@ -195,7 +195,7 @@ extern "C" int zeggs_live_frames_refiltered(const ZeggsFramesDims* d, int max_ha
                                             int R, void* state, size_t state_bytes, void* stream) {
   const char* who = "refilter";
   ZTRY(rf_dims_ok(d, max_half, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "%s: %d records for %d rows", who, R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(rows != nullptr, "%s: NULL records", who);
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
@@ -224,13 +224,13 @@ extern "C" int zeggs_live_frames_refiltered(const ZeggsFramesDims* d, int max_ha
       ZCHECK(w.outputs == want, "%s: record %d: %ld outputs disagree with n_out(%ld) - n_out(%ld) = %ld at %d / %d", who, i, w.outputs,
              w.n_in + w.count, w.n_in, want, w.L, w.M);
     }
-    if (w.count > 0) ZTRY(fh_sources_ok(who, i, w, J));
+    if (w.count > 0) ZTRY(lh_sources_ok(who, i, w, fr_pose_floats_read(J)));
     if (w.count == 0 && !(filtered && w.final)) continue;
     if (w.outputs > 0) ZTRY(fh_dests_ok(who, i, w, d->what));
     if (w.count > 0 || w.outputs > 0) work = true;
   }
   if (!work) return 0;
-  ZTRY(fh_rows_dev_ok(who, rows_dev, R));
+  ZTRY(lh_dev_ok(who, "rows_dev", rows_dev, R, 8));
   hipLaunchKernelGGL(live_refilter_k, dim3((unsigned)R), dim3(FR_THREADS), (size_t)rf_lds_bytes(J, d->max_frames), (hipStream_t)stream, *d, max_half,
                      rows_dev, rows[0], (char*)state);
   ZLAUNCH_CHECK("live_refilter");

@@ -89,17 +89,16 @@ __global__ __launch_bounds__(RS_THREADS) void resample_whole_k(const double* __r
           [=](long k) -> float { return k < 0 || k >= n_in ? 0.f : rs_load(src, fmt, k); });
 }
 
+}  // namespace
+
+#include "live_host.h"      // the host contract every stage of live serving keeps
+
+namespace {
+
 int rs_dims_ok(const ZeggsResampleDims* d, const void* state, size_t state_bytes) {
-  ZCHECK(d != nullptr, "resample: NULL dims");
-  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "resample: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
+  ZTRY(lh_dims_ok("resample", d));
   ZCHECK(d->history >= 1 && d->history <= (1 << 20), "resample: a history of %d samples", d->history);
-  if (state_bytes != (size_t)-1) {
-    ZCHECK(state != nullptr, "resample: NULL state");
-    ZCHECK(state_bytes >= (size_t)d->rows * d->history * sizeof(float), "resample: state too small (%zu < %zu)", state_bytes,
-           (size_t)d->rows * d->history * sizeof(float));
-    ZCHECK((uintptr_t)state % 4 == 0, "resample: misaligned state");
-  }
-  return 0;
+  return lh_block_ok("resample", "state", state, state_bytes, (size_t)d->rows * d->history * sizeof(float), 4);
 }
 
 // L, M, WL of a record or of the whole-signal call: a supported ratio and a support that belongs to it
@@ -116,7 +115,7 @@ int rs_filter_ok(const char* who, int L, int M, long WL) {
 int rs_push(const char* who, const ZeggsResampleDims* d, const ZeggsResampleRow* rows, const ZeggsResampleRow* rows_dev, int R, bool final,
             void* state, size_t state_bytes, void* stream) {
   ZTRY(rs_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "%s: %d records for %d rows", who, R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(rows != nullptr, "%s: NULL records", who);
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
@@ -124,9 +123,7 @@ int rs_push(const char* who, const ZeggsResampleDims* d, const ZeggsResampleRow*
   char name[96];
   for (int i = 0; i < R; ++i) {
     const ZeggsResampleRow& w = rows[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "%s: record %d: row %d of %d", who, i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "%s: record %d: row %d twice in one call", who, i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
     ZCHECK(w.count >= 0, "%s: record %d: negative count %ld", who, i, w.count);
     ZCHECK(w.format == ZEGGS_RS_F32 || w.format == ZEGGS_RS_S16, "%s: record %d: format %d", who, i, w.format);
     snprintf(name, sizeof(name), "%s: record %d", who, i);
@@ -148,7 +145,7 @@ int rs_push(const char* who, const ZeggsResampleDims* d, const ZeggsResampleRow*
     work = work || w.count > 0 || w.outputs > 0;
   }
   if (!work) return 0;
-  ZCHECK(rows_dev != nullptr || R == 1, "%s: %d records must also be in device memory (rows_dev)", who, R);
+  ZTRY(lh_dev_ok(who, "rows_dev", rows_dev, R));
   ZeggsResampleRow one = rows[0];
   if (final) one.final = 1;
   hipLaunchKernelGGL(live_resample_k, dim3((unsigned)R), dim3(RS_THREADS), 0, (hipStream_t)stream, rows_dev, one, (float*)state, d->history);
@@ -167,7 +164,7 @@ extern "C" size_t zeggs_resample_state_bytes(const ZeggsResampleDims* d) {
 
 extern "C" int zeggs_resample_reset(const ZeggsResampleDims* d, void* state, size_t state_bytes, int row, void* stream) {
   ZTRY(rs_dims_ok(d, state, state_bytes));
-  ZCHECK(row >= 0 && row < d->rows, "resample reset: row %d of %d", row, d->rows);
+  ZTRY(lh_row_ok("resample", "reset", row, d->rows));
   const size_t rb = rs_state_row_bytes(d->history);
   hipError_t e = hipMemsetAsync((char*)state + (size_t)row * rb, 0, rb, (hipStream_t)stream);
   ZCHECK(e == hipSuccess, "resample reset: %s", hipGetErrorString(e));

@@ -66,7 +66,7 @@ namespace {
 
 int rt_dims_ok(const ZeggsFramesDims* d, const void* state, size_t state_bytes) {
   ZTRY(fh_shape_ok("retime", d));
-  return fh_state_ok("retime", state, state_bytes, (size_t)rt_state_bytes(d->rows, d->J));
+  return lh_block_ok("retime", "state", state, state_bytes, (size_t)rt_state_bytes(d->rows, d->J), 8);
 }
 
 }  // namespace
@@ -94,7 +94,7 @@ extern "C" int zeggs_live_frames_retimed(const ZeggsFramesDims* d, const ZeggsRe
                                          size_t state_bytes, void* stream) {
   const char* who = "retime";
   ZTRY(rt_dims_ok(d, state, state_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "%s: %d records for %d rows", who, R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   if (R == 0) return 0;
   ZCHECK(rows != nullptr, "%s: NULL records", who);
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
@@ -108,12 +108,12 @@ extern "C" int zeggs_live_frames_retimed(const ZeggsFramesDims* d, const ZeggsRe
     ZCHECK(w.outputs == want, "%s: record %d: %ld outputs disagree with n_out(%ld) - n_out(%ld) = %ld at %d / %d", who, i, w.outputs,
            w.n_in + w.count, w.n_in, want, w.L, w.M);
     if (w.count == 0) continue;
-    ZTRY(fh_sources_ok(who, i, w, J));
+    ZTRY(lh_sources_ok(who, i, w, fr_pose_floats_read(J)));
     if (w.outputs > 0) ZTRY(fh_dests_ok(who, i, w, d->what));
     work = true;
   }
   if (!work) return 0;
-  ZTRY(fh_rows_dev_ok(who, rows_dev, R));
+  ZTRY(lh_dev_ok(who, "rows_dev", rows_dev, R, 8));
   hipLaunchKernelGGL(live_retime_k, dim3((unsigned)R), dim3(FR_THREADS), (size_t)rt_lds_bytes(J, d->max_frames), (hipStream_t)stream, *d, rows_dev,
                      rows[0], (char*)state);
   ZLAUNCH_CHECK("live_retime");

@@ -101,14 +101,9 @@ int snap_launch(const char* who, bool pack, const ZeggsSnapSeg* segs, const Zegg
   return 0;
 }
 
-int spans_out(const char* who, int count, int row, int rows, int max_spans, const size_t* offset, const size_t* bytes, ZeggsSnapSpan* spans) {
-  ZCHECK(count >= 0, "%s: row %d of %d", who, row, rows);
-  ZCHECK(spans != nullptr && max_spans >= count, "%s: room for %d spans, the row has %d", who, spans ? max_spans : 0, count);
-  for (int i = 0; i < count; ++i) spans[i] = ZeggsSnapSpan{offset[i], bytes[i]};
-  return count;
-}
-
 }  // namespace
+
+#include "live_host.h"      // the span writer, with the rest of the stages' host contract
 
 extern "C" int zeggs_live_snapshot_version(void) { return 1; }
 
@@ -116,31 +111,31 @@ extern "C" int zeggs_live_snapshot_version(void) { return 1; }
 extern "C" int zeggs_live_loudness_spans(const ZeggsLoudDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_loudness_state_bytes(d) == 0) return -1;
   size_t o[SNAP_MAX_SPANS], b[SNAP_MAX_SPANS];
-  return spans_out("live loudness spans", snap_loud_spans(d->fs, d->ring_blocks, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
+  return lh_spans_out("live loudness spans", snap_loud_spans(d->fs, d->ring_blocks, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
 }
 
 extern "C" int zeggs_resample_spans(const ZeggsResampleDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_resample_state_bytes(d) == 0) return -1;
   size_t o[SNAP_MAX_SPANS], b[SNAP_MAX_SPANS];
-  return spans_out("resample spans", snap_resample_spans(d->history, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
+  return lh_spans_out("resample spans", snap_resample_spans(d->history, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
 }
 
 extern "C" int zeggs_live_frames_spans(const ZeggsFramesDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_frames_state_bytes(d) == 0) return -1;
   size_t o[SNAP_MAX_SPANS], b[SNAP_MAX_SPANS];
-  return spans_out("frames spans", snap_frames_spans(d->J, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
+  return lh_spans_out("frames spans", snap_frames_spans(d->J, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
 }
 
 extern "C" int zeggs_live_retime_spans(const ZeggsFramesDims* d, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_retime_state_bytes(d) == 0) return -1;
   size_t o[SNAP_MAX_SPANS], b[SNAP_MAX_SPANS];
-  return spans_out("retime spans", snap_retime_spans(d->J, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
+  return lh_spans_out("retime spans", snap_retime_spans(d->J, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
 }
 
 extern "C" int zeggs_live_refilter_spans(const ZeggsFramesDims* d, int max_half, int row, ZeggsSnapSpan* spans, int max_spans) {
   if (zeggs_live_refilter_state_bytes(d, max_half) == 0) return -1;
   size_t o[SNAP_MAX_SPANS], b[SNAP_MAX_SPANS];
-  return spans_out("refilter spans", snap_refilter_spans(d->J, max_half, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
+  return lh_spans_out("refilter spans", snap_refilter_spans(d->J, max_half, d->rows, row, o, b, SNAP_MAX_SPANS), row, d->rows, max_spans, o, b, spans);
 }
 
 extern "C" int zeggs_live_pack(const ZeggsSnapSeg* segs_host, const ZeggsSnapSeg* segs_dev, int n, void* blob_dev, size_t blob_bytes, void* stream) {

@@ -45,18 +45,17 @@ __global__ __launch_bounds__(STYLE_THREADS) void live_style_mix_k(const ZeggsSty
   }
 }
 
+}  // namespace
+
+#include "live_host.h"      // the host contract every stage of live serving keeps
+
+namespace {
+
 int style_dims_ok(const ZeggsStyleBankDims* d, const void* bank, size_t bank_bytes) {
-  ZCHECK(d != nullptr, "live styles: NULL dims");
-  ZCHECK(d->rows >= 1 && d->rows <= ZEGGS_LIVE_MAX_ROWS, "live styles: %d rows (1..%d)", d->rows, ZEGGS_LIVE_MAX_ROWS);
+  ZTRY(lh_dims_ok("live styles", d));
   ZCHECK(d->ST >= 1 && d->ST <= (1 << 16), "live styles: style rows of %d floats", d->ST);
   ZCHECK(d->capacity >= 1 && d->capacity <= ZEGGS_STYLE_MAX_SLOTS, "live styles: a bank of %d slots (1..%d)", d->capacity, ZEGGS_STYLE_MAX_SLOTS);
-  if (bank_bytes != (size_t)-1) {
-    const size_t need = (size_t)d->capacity * 2 * d->ST * sizeof(float);
-    ZCHECK(bank != nullptr, "live styles: NULL bank");
-    ZCHECK(bank_bytes >= need, "live styles: bank too small (%zu < %zu)", bank_bytes, need);
-    ZCHECK((uintptr_t)bank % 4 == 0, "live styles: misaligned bank");
-  }
-  return 0;
+  return lh_block_ok("live styles", "bank", bank, bank_bytes, (size_t)d->capacity * 2 * d->ST * sizeof(float), 4);
 }
 
 }  // namespace
@@ -82,17 +81,16 @@ extern "C" int zeggs_live_style_put(const ZeggsStyleBankDims* d, void* bank, siz
 
 extern "C" int zeggs_live_style_mix(const ZeggsStyleBankDims* d, const ZeggsStyleMix* recs, const ZeggsStyleMix* recs_dev, int R, const void* bank,
                                     size_t bank_bytes, const float* eps, int eps_rows, float* sty_old, float* sty_new, void* stream) {
+  const char* who = "live style mix";
   ZTRY(style_dims_ok(d, bank, bank_bytes));
-  ZCHECK(R >= 0 && R <= d->rows, "live style mix: %d records for %d rows", R, d->rows);
+  ZTRY(lh_count_ok(who, R, d->rows));
   ZCHECK(eps_rows >= 0 && eps_rows <= (1 << 20), "live style mix: a noise tensor of %d slices", eps_rows);
   if (R == 0) return 0;
   ZCHECK(recs != nullptr, "live style mix: NULL records");
   bool seen[ZEGGS_LIVE_MAX_ROWS] = {};
   for (int i = 0; i < R; ++i) {
     const ZeggsStyleMix& w = recs[i];
-    ZCHECK(w.row >= 0 && w.row < d->rows, "live style mix: record %d: row %d of %d", i, w.row, d->rows);
-    ZCHECK(!seen[w.row], "live style mix: record %d: row %d twice in one call", i, w.row);
-    seen[w.row] = true;
+    ZTRY(lh_once_ok(who, i, w.row, d->rows, seen));
     ZCHECK(w.terms >= 1 && w.terms <= ZEGGS_STYLE_MAX_TERMS, "live style mix: record %d: %d terms (1..%d)", i, w.terms, ZEGGS_STYLE_MAX_TERMS);
     for (int t = 0; t < w.terms; ++t) {
       ZCHECK(w.slot[t] >= 0 && w.slot[t] < d->capacity, "live style mix: record %d: term %d: slot %d of %d", i, t, w.slot[t], d->capacity);
@@ -107,7 +105,7 @@ extern "C" int zeggs_live_style_mix(const ZeggsStyleBankDims* d, const ZeggsStyl
   }
   ZCHECK(sty_old != nullptr && sty_new != nullptr && sty_old != sty_new, "live style mix: NULL style tensor (or one tensor twice)");
   ZCHECK(((uintptr_t)sty_old | (uintptr_t)sty_new | (uintptr_t)eps) % 4 == 0, "live style mix: misaligned tensor");
-  ZCHECK(recs_dev != nullptr || R == 1, "live style mix: %d records must also be in device memory (recs_dev)", R);
+  ZTRY(lh_dev_ok(who, "recs_dev", recs_dev, R));
   hipLaunchKernelGGL(live_style_mix_k, dim3((unsigned)R), dim3(STYLE_THREADS), 0, (hipStream_t)stream, recs_dev, recs[0], (const float*)bank, eps,
                      sty_old, sty_new, d->ST);
   ZLAUNCH_CHECK("live_style_mix");

@@ -237,30 +237,57 @@ class _GazeRows(torch.Tensor):
         return self._server()._gaze_read(sid)
 
 
-class _RecStaging:
-    """The records of a gaze launch with more than one record, uploaded as ONE block: a ring of pinned host blocks, each guarded
-    by the event recorded behind its copy, and one device block (calls on a stream are ordered), as _Staging keeps its own."""
-    RING = 4
+class _Ring:
+    """The staging of every stage of live serving, stated once: RING pinned host blocks of `nbytes` that take turns, one event a
+    block, recorded behind the copy that last used it and waited for before the block is used again, and ONE device block
+    (calls on a stream are ordered).  A subclass states what its block holds and which way its copies go."""
+    RING, turn = 2, 0
 
-    def __init__(self, record, rows, dev):
-        self.nbytes = rows * C.sizeof(record)
-        self.host = [torch.zeros(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-        self.recs = [(record * rows).from_buffer(h.numpy()) for h in self.host]
+    def _blocks(self, nbytes, dev, make=torch.empty):
+        self.nbytes = int(nbytes)
+        self.host = [make(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
         self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
-        self.events, self.turn, self.size = [None] * self.RING, 0, C.sizeof(record)
+        self.events = [None] * self.RING
 
-    def take(self):
-        self.turn = (self.turn + 1) % self.RING
-        if self.events[self.turn] is not None:
-            self.events[self.turn].synchronize()
-        return self.recs[self.turn]
+    def _next(self):
+        """the next block's index, once the copy that last used it is done"""
+        self.turn = t = (self.turn + 1) % self.RING
+        if self.events[t] is not None:
+            self.events[t].synchronize()
+        return t
 
-    def upload(self, n):
-        nb = n * self.size
-        self.dev[:nb].copy_(self.host[self.turn][:nb], non_blocking=True)
+    def _copy(self, lo, hi, up=True):
+        """bytes lo .. hi of the turn's block to the same place of the device block (up) or back -> the event behind the copy"""
+        host, dev = self.host[self.turn][lo:hi], self.dev[lo:hi]
+        if up:
+            dev.copy_(host, non_blocking=True)
+        else:
+            host.copy_(dev, non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         self.events[self.turn] = ev
+        return ev
+
+    def idle(self):
+        for ev in self.events:
+            if ev is not None:
+                ev.synchronize()
+
+
+class _RecStaging(_Ring):
+    """The records of a gaze launch with more than one record, uploaded as ONE block."""
+    RING = 4
+
+    def __init__(self, record, rows, dev):
+        self._blocks(rows * C.sizeof(record), dev, torch.zeros)
+        self.recs = [(record * rows).from_buffer(h.numpy()) for h in self.host]
+        self.size = C.sizeof(record)
+
+    def take(self):
+        return self.recs[self._next()]
+
+    def upload(self, n):
+        self._copy(0, n * self.size)
         return self.dev.data_ptr()
 
 
@@ -328,12 +355,11 @@ def plan_push(rows, caps, lens, FC, width, first_sample, frames_ready):
     return dict(rows=out, segs=segs, segs_back=back, FC=FC, n_stage=soff)
 
 
-class _Staging:
+class _Staging(_Ring):
     """What one push_many() uploads, as ONE block: [copy records | copy records of the second launch | mel records | loudness
     records (`loud_rows` of them: none on a server without running loudness) | samples], and in a call with converting rows,
     behind the samples the call stages (tail()): [converter records | the converting rows' raw input, 2 bytes a sample for s16].
-    Two pinned host blocks take turns, each guarded by an event recorded behind its copy, so a block is never rewritten while a
-    copy from it may be in flight; one device block (calls on a stream are ordered)."""
+    Two pinned host blocks take turns (_Ring), so a block is never rewritten while a copy from it may be in flight."""
 
     def __init__(self, rows, n_samples, dev, loud_rows=0, tail_bytes=0):
         a64 = lambda x: (x + 63) // 64 * 64  # noqa: E731
@@ -343,9 +369,7 @@ class _Staging:
         self.o_loud = self.o_mel + a64(rows * C.sizeof(ops.MelRow))
         self.o_smp = self.o_loud + a64(self.loud_rows * C.sizeof(ops.LoudRow))
         self.tail_bytes = int(tail_bytes)               # room behind the samples for converter records and raw input
-        self.nbytes = self.o_smp + 4 * self.n_samples + self.tail_bytes
-        self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(2)]
-        self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
+        self._blocks(self.o_smp + 4 * self.n_samples + self.tail_bytes, dev)
         self.view = []
         for h in self.host:
             b = h.numpy()
@@ -353,14 +377,10 @@ class _Staging:
                                   mel=(ops.MelRow * rows).from_buffer(b, self.o_mel),
                                   smp=b[self.o_smp:self.o_smp + 4 * self.n_samples].view(np.float32), block=b,
                                   loud=(ops.LoudRow * self.loud_rows).from_buffer(b, self.o_loud)))
-        self.events, self.turn = [None, None], 0
 
     def take(self):
         """the next host block, once the copy that last read it is done"""
-        self.turn ^= 1
-        if self.events[self.turn] is not None:
-            self.events[self.turn].synchronize()
-        return self.view[self.turn]
+        return self.view[self._next()]
 
     def tail(self, n_samples, n_records, raw_bytes):
         """where a call that stages n_samples floats puts its converter records and raw input, and where the block then ends"""
@@ -370,16 +390,7 @@ class _Staging:
         return o_rs, o_raw, o_raw + int(raw_bytes)
 
     def upload(self, n_samples, end=None):
-        nb = self.o_smp + 4 * int(n_samples) if end is None else int(end)
-        self.dev[:nb].copy_(self.host[self.turn][:nb], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[self.turn] = ev
-
-    def idle(self):
-        for ev in self.events:
-            if ev is not None:
-                ev.synchronize()
+        self._copy(0, self.o_smp + 4 * int(n_samples) if end is None else int(end))
 
 
 LOUDNESS_DEFAULTS = dict(target=-20.0, horizon=60.0, warmup=1, gain_db=(-30.0, 30.0))
@@ -586,10 +597,10 @@ def frames_block_bytes(N, J, mask):
     return frames_layout(N, J, mask)[1]
 
 
-class _FrameStaging:
+class _FrameStaging(_Ring):
     """What the output head of a step needs beside the rows' state, allocated once: the device block the one launch writes
-    (frames_unpack's layout, sized for every row at max_frames), a small ring of pinned host blocks the one download lands in,
-    each guarded by the event recorded behind its copy, and the records of the launch in pinned host memory -- page-locked
+    (frames_unpack's layout, sized for every row at max_frames), a small ring of pinned host blocks the one download lands in
+    (_Ring), and the records of the launch in pinned host memory -- page-locked
     memory is device accessible, so the kernel reads its records where the host wrote them and no upload is enqueued.  The
     records are rewritten only after the step that used them has waited for its download, which is ordered behind the launch."""
     RING = 3
@@ -599,29 +610,19 @@ class _FrameStaging:
         self.J, self.mask = J, mask
         # tail_bytes: room behind the three areas (a planting server: the contact flags of a step's model frames), and with
         # tail_record the records of the stage in front of the head, staged as the head's are
-        self.nbytes = frames_block_bytes(rows * max_frames, J, mask) + int(tail_bytes)
+        self._blocks(frames_block_bytes(rows * max_frames, J, mask) + int(tail_bytes), dev)
         if tail_record is not None:
             self.tail_mem = torch.zeros(rows * C.sizeof(tail_record), dtype=torch.uint8).pin_memory()
             self.tail_recs = (tail_record * rows).from_buffer(self.tail_mem.numpy())
-        self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=dev)
-        self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-        self.events, self.turn = [None] * self.RING, 0
         self.rec_mem = torch.zeros(rows * C.sizeof(record), dtype=torch.uint8).pin_memory()
         self.recs = (record * rows).from_buffer(self.rec_mem.numpy())
 
     def download(self, nbytes):
         """one device-to-host copy of the block's first nbytes into the next pinned block -> that block's bytes, once they are
         there (a view: frames_unpack copies what it hands out)"""
-        self.turn = (self.turn + 1) % self.RING
-        if self.events[self.turn] is not None:
-            self.events[self.turn].synchronize()
-        host = self.host[self.turn]
-        host[:nbytes].copy_(self.dev[:nbytes], non_blocking=True)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[self.turn] = ev
-        ev.synchronize()
-        return host.numpy()[:nbytes]
+        t = self._next()
+        self._copy(0, nbytes, up=False).synchronize()
+        return self.host[t].numpy()[:nbytes]
 
 
 # ---------------------------------------------------------------------------------------------------------------- snapshots
@@ -759,10 +760,9 @@ def snapshot_check_fingerprint(got, want):
             raise ValueError(f"LiveServer.restore: the blob was taken from a server with {k} = {got[k]!r}, this one has {k} = {float(want[k])!r}")
 
 
-class _SnapStaging:
+class _SnapStaging(_Ring):
     """What snapshot_many() and restore() need beside the rows' state, allocated at the first such call and grown when a call
-    needs more: one device block and a ring of pinned host blocks, each guarded by the event recorded behind its copy as
-    _FrameStaging guards its own.  A call's block is [segment records | 64-byte boundary | blobs, each on a 64-byte boundary]."""
+    needs more (_Ring's blocks, made anew once the copies of the old ones are done).  A call's block is [segment records | 64-byte boundary | blobs, each on a 64-byte boundary]."""
     RING = 2
 
     def __init__(self, dev):
@@ -771,32 +771,16 @@ class _SnapStaging:
     def take(self, nbytes):
         """the next pinned block with room for nbytes (uint8 array), once the copy that last used it is done"""
         if nbytes > self.nbytes:
-            for ev in self.events:
-                if ev is not None:
-                    ev.synchronize()
-            self.nbytes = max(2 * int(nbytes), 1 << 16)
-            self.dev = torch.empty(self.nbytes, dtype=torch.uint8, device=self.device)
-            self.host = [torch.empty(self.nbytes, dtype=torch.uint8).pin_memory() for _ in range(self.RING)]
-            self.events = [None] * self.RING
-        self.turn = (self.turn + 1) % self.RING
-        if self.events[self.turn] is not None:
-            self.events[self.turn].synchronize()
-        return self.host[self.turn].numpy()
+            self.idle()
+            self._blocks(max(2 * int(nbytes), 1 << 16), self.device)
+        return self.host[self._next()].numpy()
 
     def upload(self, lo, hi):
-        self.dev[lo:hi].copy_(self.host[self.turn][lo:hi], non_blocking=True)
-        self._mark()
+        self._copy(lo, hi)
 
     def download(self, lo, hi):
         """bytes lo .. hi of the device block into the same place of the pinned block; returns once they are there"""
-        self.host[self.turn][lo:hi].copy_(self.dev[lo:hi], non_blocking=True)
-        self._mark().synchronize()
-
-    def _mark(self):
-        ev = torch.cuda.Event()
-        ev.record()
-        self.events[self.turn] = ev
-        return ev
+        self._copy(lo, hi, up=False).synchronize()
 
 
 def _samples(chunk, rs):
@@ -1046,7 +1030,35 @@ class LiveServer:
         if L * conf["ratio"][1] > conf["ratio"][0] * M:
             raise ValueError(f"LiveServer.open: frame_rate {frame_rate!r} on a server at {self.fps!r} frames per second is above its "
                              f"max_rate {float(conf['max_rate'])!r} (LiveServer(retime=dict(max_rate=...)))")
-        return dict(L=L, M=M, n_in=0, n_out=0)
+        return LiveServer._retimed(None, L, M)
+
+    @staticmethod
+    def _retimed(fr, L, M, n_in=0, n_out=0, half=-1):
+        """a row's re-timing dict, for open() from its arguments and for restore() from a blob's counters.  half < 0: a server
+        without the filter stage; 0: an unfiltered stream of one that has it; > 0: a filtered stream -- the half and the table
+        are those of the head `fr` at the ratio (built and uploaded here, the first time a row has the ratio)"""
+        rt = dict(L=L, M=M, n_in=n_in, n_out=n_out)
+        if half > 0:
+            t = fr.table(L, M)
+            rt.update(half=t["half"], table=t["table"])
+        elif half == 0:
+            rt.update(half=0, table=None)
+        return rt
+
+    def _converter(self, fi, fmt, n_in=0):
+        """a converting row's dict, for open() and restore() alike; the server's converter is made at its first use"""
+        if self._rs is None:
+            self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
+        return dict(self._rs.table(fi), fi=fi, fmt=fmt, n_in=n_in)
+
+    def _free_row(self, needed=True):
+        """the first free row; with none the RuntimeError of open(), or None for a caller that only sizes"""
+        for r, row in enumerate(self._rows):
+            if row is None:
+                return r
+        if needed:
+            raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        return None
 
     def _filter_of(self, rt, frame_rate, filtered):
         """open()'s `filtered` -> the row's dict with the filter's half = H and table where the stream is filtered (the table is
@@ -1062,7 +1074,7 @@ class LiveServer:
             return rt
         L, M = rt["L"], rt["M"]
         if not (L != M if filtered is None else filtered):
-            return dict(rt, half=0, table=None)
+            return LiveServer._retimed(None, L, M, rt["n_in"], rt["n_out"], half=0)
         if L > ops.REFILTER_MAX_L or M > ops.REFILTER_MAX_DOWN * L:
             raise ValueError(f"LiveServer.open: frame_rate {rate!r} on a server at {self.fps!r} frames per second is the ratio {L} / {M}: a "
                              f"filtered stream takes L <= {ops.REFILTER_MAX_L} and M <= {ops.REFILTER_MAX_DOWN} L (filtered=False: point sampling)")
@@ -1070,8 +1082,7 @@ class LiveServer:
         if Fraction(L, M) * Fraction(str(float(self.fps))) < conf["min_rate"]:
             raise ValueError(f"LiveServer.open: frame_rate {rate!r} on a server at {self.fps!r} frames per second is below its min_rate "
                              f"{float(conf['min_rate'])!r} (LiveServer(retime=dict(min_rate=...)) sizes the filter's history)")
-        t = self._fr.table(L, M)
-        return dict(rt, half=t["half"], table=t["table"])
+        return LiveServer._retimed(self._fr, L, M, rt["n_in"], rt["n_out"], half=1)
 
     def frame_delay(self, sid):
         """what the filter stage adds to stream `sid`'s latency -> (input frames, seconds): H frames of the server's rate for a
@@ -1116,12 +1127,9 @@ class LiveServer:
             named = style_request(dict(style=style, temperature=temperature, seed=seed), self._style_names, self.styles_conf["terms"])
         elif temperature is not None or seed is not None:
             raise ValueError("LiveServer.open: temperature / seed sample a named style; a tensor is taken as it is")
-        free = [r for r in range(self.rows) if self._rows[r] is None]
-        if not free:
-            raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        r, sid = self._free_row(), self._next_sid
         if self._loud is not None:
-            ops.live_loudness_reset(self._loud, free[0], gain)
-        r, sid = free[0], self._next_sid
+            ops.live_loudness_reset(self._loud, r, gain)
         self._next_sid += 1
         f32 = lambda a: a[0:1].to(self.dev, torch.float32).contiguous()  # noqa: E731
         root_pos, root_rot, root_vel, root_vrt, lpos, lrot, ltxy, lvel, lvrt = first_pose[:9]
@@ -1143,9 +1151,7 @@ class LiveServer:
         if named is None:
             self.sty_old[r], self.sty_new[r] = style0[0], style0[0]
         if rs is not None:
-            if self._rs is None:
-                self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
-            row.rs = dict(self._rs.table(rs[0]), fi=rs[0], fmt=rs[1], n_in=0)
+            row.rs = self._converter(*rs)
             ops.live_resample_reset(self._rs, r)
         if self._fr is not None:
             J = self._fr.J
@@ -1694,14 +1700,14 @@ class LiveServer:
         current = (old + np.float64(w) * d if w < 0.5 else new - d * np.float64(np.float32(1.0) - w)).astype(np.float32)
         return dict(old=old, new=new, k=row.k_style, fade=row.fade, current=current)
 
-    def _style(self, frames):
-        """style rows [R, n, ST] of the frames frames[r] + 0 .. n - 1 (frames[r] None: the row's current style)"""
-        n = max(len(f) for f in frames if f is not None)
+    def _style(self, jobs):
+        """style rows [R, n, ST] of the jobs' frames, jobs = [(row, -, first frame, frames)] as _condition() takes them (a row
+        without a job: its current style)"""
+        n = max(j[3] for j in jobs)
         wgt = np.ones((self.rows, n, 1), np.float32)
-        for r, f in enumerate(frames):
-            if f is not None:
-                row = self._rows[r]
-                wgt[r, :len(f), 0] = [style_weight(x, row.k_style, row.fade) for x in f]
+        for r, _, k0, cnt in jobs:
+            row = self._rows[r]
+            wgt[r, :cnt, 0] = [style_weight(x, row.k_style, row.fade) for x in range(k0, k0 + cnt)]
         self._ops += 2
         return torch.lerp(self.sty_old[:, None], self.sty_new[:, None], torch.as_tensor(wgt, device=self.dev)).contiguous()
 
@@ -1758,6 +1764,21 @@ class LiveServer:
         r, row = self._row(sid)
         got = ops.live_gaze_read(self._gz, r, row.kd)
         return {k: got[k] for k in ("target", "k", "fade", "start", "end", "path", "ease")}
+
+    def _conditioned(self, jobs, own=False):
+        """the conditioning of ONE decoder call, jobs = [(row, output slice, first frame, frames)] -> (gaze rows or None, style
+        rows).  A gaze server: both from ONE launch (_condition), into the step's tensors or, for `own` (close(): one job of up
+        to tick + LOOKAHEAD + 1 frames), into tensors of the call's own length.  Any other server: no gaze rows, and style rows
+        by _style() -- those of every row of the server, or for `own` the job's row alone."""
+        if self._gz is None:
+            style = self._style(jobs)
+            return None, style[jobs[0][0]:jobs[0][0] + 1].contiguous() if own else style
+        gaze, style = self.gaze, self._gz_style
+        if own:
+            n = jobs[0][3]
+            gaze, style = torch.empty(1, n, 3, device=self.dev), torch.empty(1, n, self.sty_old.shape[1], device=self.dev)
+        self._condition(jobs, gaze, style)
+        return gaze, style
 
     def _condition(self, jobs, gaze_out, style_out):
         """the conditioning rows of one decoder call on a gaze server: jobs = [(row, out_row, first frame, frames)] -> the gaze
@@ -1845,12 +1866,7 @@ class LiveServer:
         tick, T = self.tick, self.T
         with torch.no_grad():
             speech = self._encode([None if p is None else (p["enc_k0"], p["n_out"], p["n_new"], -1) for p in plan], T)
-            gaze = None
-            if self._gz is None:
-                style = self._style([None if p is None else range(p["enc_k0"], p["k1"]) for p in plan])
-            else:                                    # gaze and style rows of the step's frames from ONE launch
-                gaze, style = self.gaze, self._gz_style
-                self._condition([(r, r, plan[r]["enc_k0"], T) for r in live], gaze, style)
+            gaze, style = self._conditioned([(r, r, plan[r]["enc_k0"], T) for r in live])
             out = {}
             heads = {r: self._head(r) for r in live}
             if self.rows == 1:
@@ -1922,26 +1938,15 @@ class LiveServer:
                 jobs = [None] * self.rows
                 jobs[r] = (row.kd - 1, n + 1, top - row.n_ring, n_total - 1 if final else -1)
                 speech = self._encode(jobs, self.tail + 1)[r:r + 1, :n + 1].contiguous()
-                gaze = None
-                if self._gz is None:
-                    frames = [None] * self.rows
-                    frames[r] = range(row.kd - 1, row.kd + n)
-                    style = self._style(frames)[r:r + 1].contiguous()
-                else:                                    # (up to tick + LOOKAHEAD + 1 frames: tensors of the call's own length)
-                    gaze = torch.empty(1, n + 1, 3, device=self.dev)
-                    style = torch.empty(1, n + 1, self.sty_old.shape[1], device=self.dev)
-                    self._condition([(r, 0, row.kd - 1, n + 1)], gaze, style)
+                gaze, style = self._conditioned([(r, 0, row.kd - 1, n + 1)], own=True)
                 pose, rpos, rrot = self._decode_one(r, speech, style, n, gaze)
                 outs.append((pose[1:], rpos[1:], rrot[1:]))
                 row.kd += n
             out = {k: torch.cat([o[i] for o in outs]).contiguous() for i, k in enumerate(("pose", "rpos", "rrot"))} if outs else {}
-            if outs and self._fr is not None:
-                out["frames"] = self._frames_close(r, out)
-                if self._pl is not None:
-                    out["contacts"] = out["frames"].pop("contacts")
-            elif self._fr is not None and row.rt is not None and row.rt.get("half", 0) and row.rt["n_in"] > 0:
+            if not outs and self._fr is not None and row.rt is not None and row.rt.get("half", 0) and row.rt["n_in"] > 0:
                 # a filtered stream whose frames all left through step(): the final record brings no frame and emits the tail
                 out = dict(pose=self.pose[r:r], rpos=self.rpos[r:r], rrot=self.rrot[r:r])
+            if out and self._fr is not None:
                 out["frames"] = self._frames_close(r, out)
                 if self._pl is not None:
                     out["contacts"] = out["frames"].pop("contacts")
@@ -1991,18 +1996,17 @@ class LiveServer:
                  pose=[(at(self.pose, r), 4 * self.pose.shape[1])], rpos=[(at(self.rpos, r), 12)], rrot=[(at(self.rrot, r), 16)],
                  gaze=[(at(self.gaze, r), 12 * self.T)], sty_old=[(at(self.sty_old, r), 4 * self.sty_old.shape[1])],
                  sty_new=[(at(self.sty_new, r), 4 * self.sty_new.shape[1])], loudness=[], resample=[], head=[])
-        if self._gz is not None:                         # a gaze server: the row's schedule rides behind the gaze rows
-            p["gaze"] += [(self._gz.state.data_ptr() + o, b) for o, b in ops.live_gaze_spans(self._gz, r)]
         rs = self._rs if rs_on else None
         if rs_on and rs is None:                        # (restore()'s size check ahead of the converter's first use: sizes only)
             rs = types.SimpleNamespace(state=None, d=ops.ResampleDims(self.rows, 2 * self.resample_conf["zero_crossings"] * audio.RESAMPLE_MAX_DECIMATION))
-        for name, obj, spans in (("loudness", self._loud, ops.live_loudness_spans), ("resample", rs, ops.live_resample_spans),
-                                 ("head", self._fr, ops.live_frames_spans)):
+        # (section, the stage or None, its span report, whether its pieces ride behind what the section has: a gaze server's
+        # schedule behind the gaze rows, a planting server's chains behind the head's pieces)
+        for name, obj, spans, behind in (("gaze", self._gz, ops.live_gaze_spans, True), ("loudness", self._loud, ops.live_loudness_spans, False),
+                                         ("resample", rs, ops.live_resample_spans, False), ("head", self._fr, ops.live_frames_spans, False),
+                                         ("head", self._pl, ops.live_plant_spans, True)):
             if obj is not None:
                 base = 0 if obj.state is None else obj.state.data_ptr()
-                p[name] = [(base + o, b) for o, b in spans(obj, r)]
-        if self._pl is not None:                         # a planting server: the chains' states ride behind the head's pieces
-            p["head"] += [(self._pl.state.data_ptr() + o, b) for o, b in ops.live_plant_spans(self._pl, r)]
+                p[name] = (p[name] if behind else []) + [(base + o, b) for o, b in spans(obj, r)]
         for t in (self.feats, self.ring, self.h, self.pose, self.rpos, self.rrot, self.gaze, self.sty_old, self.sty_new):
             assert t.is_contiguous()
         return p
@@ -2120,8 +2124,7 @@ class LiveServer:
             raise ValueError(f"LiveServer.restore: section 'row': counters {w} are not those of a stream of this server")
         if w["rt"] != int(self.retime_conf is not None) or (w["rt_half"] >= 0) != bool(self.retime_conf and "filter" in self.retime_conf):
             raise ValueError("LiveServer.restore: section 'row': its re-timing fields are not those of a stream of this server")
-        free = [r for r in range(self.rows) if self._rows[r] is None]
-        r = free[0] if free else 0                       # (sizes do not depend on the row: a full server still checks them)
+        r = self._free_row(needed=False) or 0            # (sizes do not depend on the row: a full server still checks them)
         pieces = self._snap_pieces(r, w["n"] - w["base"], w["n_feat"] - w["fbase"], bool(w["rs"]))
         J3 = 3 * len(self.frames_conf["parents"]) if self.frames_conf else 0
         if w["offsets_count"] != J3 or (J3 and w["offsets_itemsize"] not in (4, 8)):
@@ -2131,8 +2134,7 @@ class LiveServer:
         for name, nb in zip(SNAP_SECTIONS, self._snap_sizes(pieces, host)):
             if sec[name][1] != nb:
                 raise ValueError(f"LiveServer.restore: section {name!r} has {sec[name][1]} bytes, this server's row takes {nb}")
-        if not free:
-            raise RuntimeError(f"LiveServer: all {self.rows} rows are in use")
+        r = self._free_row()
         # ---- the host side of the row: tables by the functions open() uses (a refused rate or ratio raises before a row is taken)
         row = _Row(self._next_sid)
         row.n, row.base, row.n_feat, row.fbase, row.n_ring, row.kd = (w[k] for k in ("n", "base", "n_feat", "fbase", "n_ring", "kd"))
@@ -2142,18 +2144,11 @@ class LiveServer:
                 raise ValueError(f"LiveServer.restore: section 'row': sample format {w['rs_fmt']}")
             if w["rs_fi"] != self.fs:
                 audio.resample_ratio(w["rs_fi"], self.fs)
-            if self._rs is None:
-                self._rs = ops.LiveResample(self.fs, self.rows, self.resample_conf, self.dev)
-            row.rs = dict(self._rs.table(w["rs_fi"]), fi=w["rs_fi"], fmt=w["rs_fmt"], n_in=w["rs_n_in"])
+            row.rs = self._converter(w["rs_fi"], w["rs_fmt"], w["rs_n_in"])
         if w["rt"]:
-            row.rt = dict(L=w["rt_L"], M=w["rt_M"], n_in=w["rt_n_in"], n_out=w["rt_n_out"])
-            if w["rt_half"] > 0:
-                t = self._fr.table(w["rt_L"], w["rt_M"])
-                if t["half"] != w["rt_half"]:
-                    raise ValueError(f"LiveServer.restore: section 'row': half {w['rt_half']} at the ratio {w['rt_L']} / {w['rt_M']}, this server's filter has {t['half']}")
-                row.rt.update(half=t["half"], table=t["table"])
-            elif w["rt_half"] == 0:
-                row.rt.update(half=0, table=None)
+            row.rt = self._retimed(self._fr, w["rt_L"], w["rt_M"], w["rt_n_in"], w["rt_n_out"], w["rt_half"])
+            if w["rt_half"] > 0 and row.rt["half"] != w["rt_half"]:
+                raise ValueError(f"LiveServer.restore: section 'row': half {w['rt_half']} at the ratio {w['rt_L']} / {w['rt_M']}, this server's filter has {row.rt['half']}")
         b = np.frombuffer(bytes(blob) if isinstance(blob, (bytes, bytearray, memoryview)) else np.ascontiguousarray(blob, np.uint8), np.uint8)
         if J3:
             row.offsets = np.array(b[sec["offsets"][0]:sum(sec["offsets"])].view("<f8" if w["offsets_itemsize"] == 8 else "<f4")).reshape(-1, 3)
